@@ -12,7 +12,13 @@ synchronisation behind every step is ms_per_step_synchronised).  With N>1
 every rank runs the same pass on its own replica (a single JSON document does not shard: weak scaling, no data-path
 collective).
 
-Objects on the same line (all measured live in this run unless they say "committed profile"):
+A plain run does only what that figure needs: set up, warm up, time the K steps, write the outputs if --dump-outputs DIR is
+given, print the line (metric, value, unit, ms_per_step, ...).  --dump-outputs DIR: the last timed step's result as a caller of
+the step receives it -- verdict and structural count (stage1_verdict_count.npy) and the structural indexes, a fixed seeded
+sample of them when there are more than DUMP_SAMPLE (structural_indexes.npy, taken at structural_indexes_at.npy) -- in float64.
+
+--full adds everything else, measured in the same run: ms_per_step_synchronised, and the objects below (all measured live in
+this run unless they say "committed profile"):
   roofline      the stage-1 kernel: algorithmic bytes (N + 4*S) / average kernel time (hipEvents on the
                 kernel's own stream) vs the 8 TB/s HBM3E peak; input_frac = N bytes only; read_frac = 2*FETCH_SIZE of the
                 committed PMC passes / the live kernel time; at_1GiB = the same kernel on a 1.07 GB document (x1700:
@@ -49,6 +55,46 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 METRIC = "GB/s parsed (stage1+stage2) + %HBM-peak, twitter.json 1GPU / parking-citations NDJSON 1-8GPU"  # BASELINE.json
 PUBLISHED = {"source": "reference README.md:517-557 (Go 1.x, hardware not stated)", "unit": "GB/s",
              "parse_twitter": 1.07, "parse_canada": 0.17, "parse_twitterescaped": 0.58}
+DUMP_SAMPLE = 1 << 21  # structural indexes --dump-outputs keeps (configs[1] has 23.5 M of them: 188 MB as float64)
+
+
+def dump_outputs(out_dir, d_pos, ok, n):
+    """--dump-outputs: the verdict, the count and the structural indexes (d_pos[:n], uint32 positions) of the last timed step as
+    float64 .npy files.  Beyond DUMP_SAMPLE indexes a sample is kept, drawn with a fixed seed, so equal arguments keep equal
+    positions; the positions themselves go beside it."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "stage1_verdict_count.npy"), np.array([float(ok), float(n)], dtype=np.float64))
+    at = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+    vals = d_pos[torch.from_numpy(at).to(d_pos.device)].cpu().numpy().view(np.uint32)
+    np.save(os.path.join(out_dir, "structural_indexes.npy"), vals.astype(np.float64))
+    np.save(os.path.join(out_dir, "structural_indexes_at.npy"), at.astype(np.float64))
+
+
+def headline(args, world, n_bytes, s_expect, dt):
+    """The line's contract fields: the K queued steps of configs[1] stage 1 (`dt` = their wall time, slowest rank)."""
+    return {
+        "metric": METRIC,
+        "value": round(world * n_bytes / (dt / args.steps) / 1e9, 2),
+        "value_is": "stage 1 only (configs[1] as BASELINE.json names it); stage1+stage2 of the same document: value_stage1_stage2 "
+                    "(--full)",
+        "unit": "GB/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 4),
+        "step_mode": "queued: the K launches go behind one another on one stream, one synchronisation per 64 steps, every step's "
+                     "count and verdict checked inside the timed region (sjhip_stage1_device_queue / _wait / _result)",
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic (testdata/twitter.json replicated into one JSON array)",
+        "config": {"workload": f"configs[1]: twitter.json x{args.copies} array, {n_bytes} B, stage-1 (structural index), "
+                               f"one document replica per GPU", "bytes_per_gpu": n_bytes,
+                   "structurals": s_expect, "parallelism": f"replicas x{world}"},
+    }
 
 
 def _profile(name):
@@ -162,8 +208,10 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--copies", type=int, default=426, help="twitter.json copies in the array (426 = 256.56 MiB)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--stage1-only", action="store_true", help="skip every extra leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's result to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also every leg beyond the headline figure (module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline")
+    ap.add_argument("--stage1-only", action="store_true", help="with --full: skip every extra leg")
     args = ap.parse_args()
 
     import torch
@@ -183,7 +231,8 @@ def main():
     import __graft_entry__ as G
     if rank == 0:
         G.build_lib()
-        G.build_oracle()
+        if args.full:
+            G.build_oracle()  # cpu_baseline()
     if distributed:
         dist.barrier()
     import sjhip
@@ -222,11 +271,12 @@ def main():
     # synchronises once per batch of records -- the way the reference's ParseNDStream keeps stage 1 of the next block
     # running beside stage 2 of the previous one (simdjson_amd64.go:127-215), and what the contract's timed region (K steps
     # between two barriers) asks for.  Every step's count and verdict are checked inside the timed region.  The same K
-    # steps with a synchronisation behind each (sjhip_stage1_device) are timed behind it: ms_per_step_synchronised.
+    # steps with a synchronisation behind each (sjhip_stage1_device) are timed behind it with --full: ms_per_step_synchronised.
     QS = sjhip.Context.STAGE1_QUEUE_SLOTS
 
     def queued_steps(k):
         done = 0
+        ok_q = n_q = None
         while done < k:
             m = min(QS, k - done)
             for slot in range(m):
@@ -236,13 +286,28 @@ def main():
                 ok_q, n_q = ctx.stage1_result(slot, n_bytes)
                 assert ok_q and n_q == s_expect, (slot, ok_q, n_q, s_expect)
             done += m
+        return ok_q, n_q
 
     queued_steps(min(args.warmup, 2))
     barrier()
     t0 = time.perf_counter()
-    queued_steps(args.steps)
+    ok_last, n_last = queued_steps(args.steps)
     barrier()
     dt = time.perf_counter() - t0
+    if distributed:
+        tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
+        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+        dt = float(tmax.item())
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_pos, ok_last, n_last)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, world, n_bytes, s_expect, dt)), flush=True)
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     barrier()
     t1 = time.perf_counter()
@@ -687,34 +752,14 @@ def main():
         extra["extra_error"] = repr(e)
 
     if rank == 0:
-        ms_per_step = dt / args.steps * 1e3
-        value = world * n_bytes / (dt / args.steps) / 1e9
-        line = {
-            "metric": METRIC,
-            "value": round(value, 2),
-            "value_is": "stage 1 only (configs[1] as BASELINE.json names it); stage1+stage2 of the same document: value_stage1_stage2",
-            "value_stage1_stage2": (extra.get("full_parse") or {}).get("GBps"),
-            "unit": "GB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "step_mode": "queued: the K launches go behind one another on one stream, one synchronisation per 64 steps, every step's "
-                         "count and verdict checked inside the timed region (sjhip_stage1_device_queue / _wait / _result); "
-                         "ms_per_step_synchronised = the same K steps with a stream synchronisation behind each (sjhip_stage1_device)",
-            "ms_per_step_synchronised": round(dt_sync / args.steps * 1e3, 4),
-            "value_synchronised": round(n_bytes * world / (dt_sync / args.steps) / 1e9, 2),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic (testdata/twitter.json replicated into one JSON array)",
-            "config": {"workload": f"configs[1]: twitter.json x{args.copies} array, {n_bytes} B, stage-1 (structural index), "
-                                   f"one document replica per GPU; stage1+stage2 of the same document in full_parse, "
-                                   f"parking-citations NDJSON in ndjson", "bytes_per_gpu": n_bytes,
-                       "structurals": s_expect, "parallelism": f"replicas x{world}"},
-            "roofline": roof,
-        }
+        line = headline(args, world, n_bytes, s_expect, dt)
+        line["value_stage1_stage2"] = (extra.get("full_parse") or {}).get("GBps")
+        line["step_mode"] += ("; ms_per_step_synchronised = the same K steps with a stream synchronisation behind each "
+                              "(sjhip_stage1_device)")
+        line["ms_per_step_synchronised"] = round(dt_sync / args.steps * 1e3, 4)
+        line["value_synchronised"] = round(n_bytes * world / (dt_sync / args.steps) / 1e9, 2)
+        line["config"]["workload"] += "; stage1+stage2 of the same document in full_parse, parking-citations NDJSON in ndjson"
+        line["roofline"] = roof
         line.update(extra)
         if world == 1 and not args.no_cpu_baseline:
             try:

@@ -1,4 +1,4 @@
-"""one-screen summary of a bench.py JSON line: python tools/bench_brief.py <file>"""
+"""one-screen summary of a `bench.py --full` JSON line: python tools/bench_brief.py <file>"""
 import json
 import sys
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round-6 profile (GPU box, repo root): tools/profile_r6.sh <name>  -> gpurun_out/<name>/
-#  (1) bench.py plain (the bench line), (2) kernel trace + stats of the whole parse on the two BASELINE workloads (both copy modes),
+#  (1) bench.py --full (the bench line), (2) kernel trace + stats of the whole parse on the two BASELINE workloads (both copy modes),
 #  (3) HBM counters of every parse kernel (FETCH_SIZE / WRITE_SIZE in separate PMC passes, MI355X_MICROARCH.md),
 #  (5) MarshalJSON / serializer kernels on configs[4]'s tape,
 #  (4) stage 1 alone: kernel trace + FETCH/WRITE passes on the 64 MiB document (x107), configs[1] and the 1 GiB document (x1700).
@@ -9,8 +9,8 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/${1:-prof_r6}
 mkdir -p $OUT
 cd $REPO
-timeout 900 python bench.py > $OUT/bench_plain.log 2>&1
-grep -h "^{" $OUT/bench_plain.log | tail -1 > $OUT/bench.json
+timeout 900 python bench.py --full > $OUT/bench_full.log 2>&1
+grep -h "^{" $OUT/bench_full.log | tail -1 > $OUT/bench.json
 cd /tmp && export TMPDIR=/tmp
 for w in twitter parking; do
   timeout 60 rocprofv3 --kernel-trace --stats -d $OUT/trace_$w -o p -- python $REPO/tools/parse_loop.py $w 6 > $OUT/trace_$w.log 2>&1
