@@ -313,8 +313,10 @@ int sjhip_stage1_time(sjhip_ctx *ctx, const void *d_msg, size_t len, int ndjson,
 /* ---- profiling aids (not needed by a binding) -------------------------------------------------------------------
  * sjhip_stage1_set_variant: kernel variant used by this process for stage 1 (A/B runs on hardware): 0 512-thread
  *   blocks with barriers, 1 1024 with barriers (default), 2 768 with barriers, 3 1024 barrier-free with 2 tiles in
- *   flight per block, 4 the same with 3;
- *   -1 = the SJHIP_S1_VARIANT environment variable or the default.  Returns the variant in effect.
+ *   flight per block, 4 the same with 3, 5 1024 with barriers and one
+ *   64-byte pass per lane instead of two (64 KiB tiles);
+ *   -1 = the SJHIP_S1_VARIANT environment variable or the default.  Returns the variant in effect.  It applies to
+ *   stage 1 alone (sjhip_stage1*, sjhip_stage1_trace); the whole parse always runs the default variant.
  * sjhip_stage1_trace: one stage-1 launch of a profiling build of the current variant that stamps s_memtime at the
  *   phase boundaries of every (tile, wave): trace_out[(tile * waves + wave) * words + k], k = 0 phase A begins,
  *   1 phase A done, 2 serial section done (only the wave that ran it), 3 state of the tile known, 4 flatten done,

@@ -1076,8 +1076,12 @@ struct S1Variant {
     int block, ch, wpe;
     int depth;  // 0: the barrier kernel; otherwise tiles in flight of the barrier-free kernel
 };
-static const S1Variant S1_VARIANTS[] = {{512, 2, 4, 0}, {1024, 2, 4, 0}, {768, 2, 3, 0},
-                                        {1024, 2, 4, 2}, {1024, 2, 4, 3}, {1024, 1, 4, 0}};
+static constexpr S1Variant S1_VARIANTS[] = {{512, 2, 4, 0}, {1024, 2, 4, 0}, {768, 2, 3, 0},
+                                           {1024, 2, 4, 2}, {1024, 2, 4, 3}, {1024, 1, 4, 0}};
+// the whole parse always launches stage1_kernel<1024, 2, 4> (stage1_launch) and plans its tiles with this variant
+static_assert(S1_VARIANTS[S1_DEFAULT_VARIANT].block == 1024 && S1_VARIANTS[S1_DEFAULT_VARIANT].ch == 2 &&
+                  S1_VARIANTS[S1_DEFAULT_VARIANT].depth == 0,
+              "the whole-parse launch and its tile plan must agree");
 static constexpr int S1_NVARIANTS = (int)(sizeof S1_VARIANTS / sizeof S1_VARIANTS[0]);
 static int g_s1_variant = -1;
 int stage1_set_variant(int v) {  // -1: back to SJHIP_S1_VARIANT / the default; returns the variant in effect
@@ -1124,8 +1128,8 @@ static u32 s1_block_slots(const S1Variant &v) {  // blocks the device runs at on
     const int per_cu = over > 0 ? over : (v.block <= 512 ? 2 : 1);  // 16 waves per CU
     return (u32)cus * (u32)per_cu;
 }
-static S1Plan s1_plan(size_t len, size_t lead) {
-    const S1Variant v = s1_variant();
+// v: the variant whose kernel is launched -- the kernel walks its own UNITS (tile_unit<UNITS>), TileMap does not carry it
+static S1Plan s1_plan(size_t len, size_t lead, const S1Variant &v) {
     const u64 units_per_tile = (u64)(v.block / 64) * v.ch;
     const u64 units = ((u64)lead + len + 4095) / 4096;
     const u64 slots = s1_block_slots(v);
@@ -1172,7 +1176,7 @@ hipError_t stage1_prepare(S1Ws &ws, hipStream_t stream, void *zero2, size_t zero
 // words of trace a launch of the current variant writes (sjhip_stage1_trace): tiles x waves x TRACE_WORDS
 size_t stage1_trace_words(size_t len, size_t lead, unsigned *tiles_out, int *waves_out) {
     const S1Variant v = s1_variant();
-    const u32 tiles = s1_plan(len, lead).tiles;
+    const u32 tiles = s1_plan(len, lead, v).tiles;
     if (tiles_out) *tiles_out = tiles;
     if (waves_out) *waves_out = v.block / 64;
     return (size_t)tiles * (size_t)(v.block / 64) * TRACE_WORDS;
@@ -1187,7 +1191,10 @@ hipError_t stage1_launch(const void *d_msg, size_t len, int ndjson, u32 *d_pos, 
     const uintptr_t a = reinterpret_cast<uintptr_t>(d_msg);
     const u8 *base = reinterpret_cast<const u8 *>(a & ~(uintptr_t)63);
     const u64 lead = a & 63;
-    const S1Plan plan = s1_plan(len, lead);
+    // the whole parse runs the default kernel whatever variant is selected for stage 1 alone: plan for that kernel
+    const bool whole = aux_buf || d_kind;
+    const S1Variant v = whole ? S1_VARIANTS[S1_DEFAULT_VARIANT] : s1_variant();
+    const S1Plan plan = s1_plan(len, lead, v);
     const u32 tiles = plan.tiles;
     Stage1State *st = reinterpret_cast<Stage1State *>(ws.p);
     const unsigned par = ws.epoch & 1u;
@@ -1196,7 +1203,6 @@ hipError_t stage1_launch(const void *d_msg, size_t len, int ndjson, u32 *d_pos, 
     if (tiles == 0) {  // (nothing is launched: the stage-2 state of an empty message is zeroed the plain way)
         return zero2 && zero2_bytes ? hipMemsetAsync(zero2, 0, zero2_bytes, stream) : hipSuccess;
     }
-    const S1Variant v = s1_variant();
     const u32 nd = (u32)((ndjson & 1) != 0);
     S1Aux aux = {};
     aux.kind = nullptr;
@@ -1253,7 +1259,7 @@ hipError_t stage1_launch(const void *d_msg, size_t len, int ndjson, u32 *d_pos, 
             S1_LAUNCHK((stage1_kernel_nb<B, C, D, W, false, false>), B);                   \
         }                                                                                  \
     } while (0)
-    if (aux_buf || d_kind) {  // the whole parse: the barrier kernel in its default shape (the variants are for plain stage 1)
+    if (whole) {  // the whole parse: the barrier kernel in its default shape (the variants are for plain stage 1)
         S1_LAUNCH(stage1_kernel, 1024, 2, 4);
     } else if (v.depth) {
         if (v.depth == 2) S1_LAUNCH_NB(1024, 2, 2, 4);
