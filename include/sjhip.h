@@ -198,6 +198,33 @@ int sjhip_count_where_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *
                            const void *value, size_t vlen, uint64_t *count);
 int sjhip_project_keys(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, uint64_t *out,
                        size_t cap_records, size_t *records);
+/* Columns: the VALUE at `path` of every record, converted on the device, so that only the column crosses PCIe (the
+ * reference's Iter.FindElement(path...) followed by a conversion of the element; records, paths, the probe with too small
+ * a cap_records (SJHIP_ERR_ARG, *records set) and the limits are those of sjhip_find_path):
+ *   sjhip_extract_path     what Iter.Float / Int / Uint / Bool (parsed_json.go:560-749, 867-875) return: `values` holds
+ *                          cap_records doubles / int64_t / uint64_t (FLOAT / INT / UINT) or bytes 0 / 1 (BOOL), `status`
+ *                          one byte per record; a record whose status is not OK has the value 0.  The number conversions
+ *                          are those of sjhip_count_where_path (the amd64 results at 2^63 for INT and 2^64 for UINT).
+ *   sjhip_extract_path_strings  Iter.StringBytes (the unescaped string), or with SJHIP_COL_CVT Iter.StringCvt
+ *                          (parsed_json.go:775-800: strings as they are, integers in decimal, floats as appendFloat writes
+ *                          them -- the text of MarshalJSON --, true / false / null; objects and arrays are TYPE), built on
+ *                          the device: *records, *bytes = the total length of the column.
+ *   sjhip_fetch_path_strings    the column in Arrow's "large string" layout: offsets[records + 1] (offsets[0] = 0), data[bytes],
+ *                          status[records]; a record that is not OK has an empty slot.  The column stays on the device
+ *                          until the next parse or the next sjhip_extract_path_strings of the context (other queries,
+ *                          MarshalJSON and the serializer leave it alone); without one: SJHIP_ERR_ARG. */
+enum { SJHIP_COL_FLOAT = 0, SJHIP_COL_INT = 1, SJHIP_COL_UINT = 2, SJHIP_COL_BOOL = 3 };
+enum { SJHIP_COL_OK = 0, SJHIP_COL_NOT_FOUND = 1, /* ErrPathNotFound */
+       SJHIP_COL_NOT_OBJECT = 2,                  /* the root value, or that of a key that is not the last one, is not an object */
+       SJHIP_COL_TYPE = 3,                        /* "unable to convert type ..." / "value is not string" / StringCvt of {} [] */
+       SJHIP_COL_NULL = 4,                        /* the element is null and the conversion rejects it (a type error there) */
+       SJHIP_COL_RANGE = 5 };                     /* overflows / underflows int64; negative or above 2^64 for UINT */
+int sjhip_extract_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int kind, void *values,
+                       uint8_t *status, size_t cap_records, size_t *records);
+#define SJHIP_COL_CVT 1u /* StringCvt instead of StringBytes */
+int sjhip_extract_path_strings(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, uint32_t flags,
+                               size_t *records, size_t *bytes);
+int sjhip_fetch_path_strings(sjhip_ctx *ctx, uint64_t *offsets, uint8_t *data, uint8_t *status);
 
 /* ---- Serializer.Serialize on the device (parsed_serialize.go:200-431, format version 3) -----------------------------
  * Splits the device-resident tape of the last parse (SJHIP_FLAG_COPY_STRINGS) into the reference's three columns --

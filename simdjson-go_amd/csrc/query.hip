@@ -14,10 +14,13 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 
+#include <vector>
+
 #include "../../include/sjhip.h"
 #include "sj_ctx.h"
 #include "sj_device.h"
 #include "sj_bounds.h"
+#include "sj_ftoa.h"
 #include "sj_stage2.h"
 
 using namespace sj;
@@ -423,53 +426,69 @@ __device__ u64 record_find_path(const QView &q, const QPath &pth, u32 r) {
     }
     return SJHIP_PATH_NOT_FOUND;
 }
-// the typed comparisons: what Iter.String / Int / Uint / Float / Bool return for the element (parsed_json.go:560-749:
-// integers, unsigned integers and floats convert into each other where the value fits), compared with the wanted value
+// what Iter.Float / Int / Uint / Bool return for the element whose first word is tape[v] (parsed_json.go:560-749, 867-875:
+// integers, unsigned integers and floats convert into each other where the value fits): SJHIP_COL_OK with the value's bits
+// in *out, or the error the reference returns (SJHIP_COL_NULL for null, SJHIP_COL_TYPE for the other types)
+__device__ __forceinline__ int element_to(const QView &q, u64 v, int kind, u64 *out) {
+    const u64 w = q.tape[v];
+    const u32 t = (u32)(w >> 56);
+    *out = 0;
+    if (t == 'n') return SJHIP_COL_NULL;
+    if (kind == SJHIP_COL_BOOL) {
+        if (t != 't' && t != 'f') return SJHIP_COL_TYPE;
+        *out = t == 't';
+        return SJHIP_COL_OK;
+    }
+    if (t != 'l' && t != 'u' && t != 'd') return SJHIP_COL_TYPE;
+    const u64 raw = q.tape[v + 1];
+    const double d = __longlong_as_double((long long)raw);
+    if (kind == SJHIP_COL_FLOAT) {
+        *out = t == 'd' ? raw : (u64)__double_as_longlong(t == 'l' ? (double)(long long)raw : (double)raw);
+        return SJHIP_COL_OK;
+    }
+    if (kind == SJHIP_COL_INT) {
+        if (t == 'l') *out = raw;
+        else if (t == 'u') {
+            if (raw > 0x7fffffffffffffffull) return SJHIP_COL_RANGE;
+            *out = raw;
+        } else {
+            // an error above math.MaxInt64 / below math.MinInt64 (as float64 constants: 2^63 and -2^63), else int64(v) -- which
+            // for v == 2^63 is the amd64 conversion's "integer indefinite", MinInt64
+            if (d > 9223372036854775808.0 || d < -9223372036854775808.0) return SJHIP_COL_RANGE;
+            *out = d >= 9223372036854775808.0 || d != d ? 0x8000000000000000ull : (u64)(long long)d;
+        }
+        return SJHIP_COL_OK;
+    }
+    // SJHIP_COL_UINT
+    if (t == 'u') *out = raw;
+    else if (t == 'l') {
+        if ((long long)raw < 0) return SJHIP_COL_RANGE;
+        *out = raw;
+    } else {
+        // an error only for v > math.MaxUint64 -- which as a float64 constant is 2^64 -- and for v < 0; uint64(v) of exactly 2^64
+        // is the amd64 conversion's result: (v - 2^63) converts to the integer indefinite 0x8000000000000000, XORed with the sign
+        // bit = 0 (the mirror image of the INT edge at 2^63)
+        if (d != d) *out = 0x8000000000000000ull;  // NaN never reaches the tape (parse_number rejects it); amd64: indefinite
+        else if (d < 0.0 || d > 18446744073709551616.0) return SJHIP_COL_RANGE;
+        else *out = d >= 18446744073709551616.0 ? 0ull : (u64)d;
+    }
+    return SJHIP_COL_OK;
+}
+// the typed comparisons: the element converted as above (StringBytes for EQ_STRING), compared with the wanted value
 __device__ bool element_is(const QView &q, u64 v, int op, u64 want) {
     const u64 w = q.tape[v];
     const u32 t = (u32)(w >> 56);
+    u64 got;
     switch (op) {
     case SJHIP_OP_EXISTS: return true;
     case SJHIP_OP_EQ_STRING: return t == '"' && str_equals(q, w, q.tape[v + 1], q.val, q.vlen);
-    case SJHIP_OP_EQ_BOOL: return (t == 't' && want != 0) || (t == 'f' && want == 0);
+    case SJHIP_OP_EQ_BOOL: return element_to(q, v, SJHIP_COL_BOOL, &got) == SJHIP_COL_OK && got == (want != 0);
     case SJHIP_OP_IS_NULL: return t == 'n';
-    case SJHIP_OP_EQ_INT: {
-        const u64 raw = (t == 'l' || t == 'u' || t == 'd') ? q.tape[v + 1] : 0;
-        if (t == 'l') return (long long)raw == (long long)want;
-        if (t == 'u') return raw <= 0x7fffffffffffffffull && (long long)raw == (long long)want;
-        if (t == 'd') {
-            // Iter.Int: an error above math.MaxInt64 / below math.MinInt64 (as float64 constants: 2^63 and -2^63), else int64(v) --
-            // which for v == 2^63 is the amd64 conversion's "integer indefinite", MinInt64
-            const double d = __longlong_as_double((long long)raw);
-            if (d > 9223372036854775808.0 || d < -9223372036854775808.0) return false;
-            const long long iv = d >= 9223372036854775808.0 || d != d ? (long long)0x8000000000000000ull : (long long)d;
-            return iv == (long long)want;
-        }
-        return false;
-    }
-    case SJHIP_OP_EQ_UINT: {
-        const u64 raw = (t == 'l' || t == 'u' || t == 'd') ? q.tape[v + 1] : 0;
-        if (t == 'u') return raw == want;
-        if (t == 'l') return (long long)raw >= 0 && raw == want;
-        if (t == 'd') {
-            // Iter.Uint (parsed_json.go:679-692): an error only for v > math.MaxUint64 -- which as a float64 constant is 2^64 --
-            // and for v < 0; uint64(v) of exactly 2^64 is the amd64 conversion's result: (v - 2^63) converts to the integer
-            // indefinite 0x8000000000000000, XORed with the sign bit = 0 (the mirror image of EQ_INT's 2^63 edge above)
-            const double d = __longlong_as_double((long long)raw);
-            if (d != d) return want == 0x8000000000000000ull;  // NaN never reaches the tape (parse_number rejects it); amd64: indefinite
-            if (d < 0.0 || d > 18446744073709551616.0) return false;
-            const u64 uv = d >= 18446744073709551616.0 ? 0ull : (u64)d;
-            return uv == want;
-        }
-        return false;
-    }
-    case SJHIP_OP_EQ_FLOAT: {
-        const double wd = __longlong_as_double((long long)want);
-        if (t == 'd') return __longlong_as_double((long long)q.tape[v + 1]) == wd;
-        if (t == 'l') return (double)(long long)q.tape[v + 1] == wd;
-        if (t == 'u') return (double)q.tape[v + 1] == wd;
-        return false;
-    }
+    case SJHIP_OP_EQ_INT: return element_to(q, v, SJHIP_COL_INT, &got) == SJHIP_COL_OK && got == want;
+    case SJHIP_OP_EQ_UINT: return element_to(q, v, SJHIP_COL_UINT, &got) == SJHIP_COL_OK && got == want;
+    case SJHIP_OP_EQ_FLOAT:  // (a comparison of doubles: -0.0 equals 0.0)
+        return element_to(q, v, SJHIP_COL_FLOAT, &got) == SJHIP_COL_OK &&
+               __longlong_as_double((long long)got) == __longlong_as_double((long long)want);
     }
     return false;
 }
@@ -512,6 +531,145 @@ __global__ __launch_bounds__(256) void k_q_project(QView q, QPath set, u64 *out)
     for (; n < set.n; n++) dst[n] = ~0ull;
 }
 
+// ---- columns: the value at a path of every record, converted (sjhip_extract_path / sjhip_extract_path_strings) -------------
+// Numbers and bools: one lane per record -- FindElement, the conversion of element_to, one store of the value and one of the
+// status; nothing is scanned.
+__device__ __forceinline__ int path_status(u64 v) {
+    return v == SJHIP_PATH_NOT_FOUND ? SJHIP_COL_NOT_FOUND : SJHIP_COL_NOT_OBJECT;
+}
+__global__ __launch_bounds__(256) void k_q_extract(QView q, QPath pth, int kind, void *values, u8 *status) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    if (r > q.R) return;
+    const u64 v = record_find_path(q, pth, r);
+    u64 x = 0;
+    const int st = v < SJHIP_PATH_NOT_OBJECT ? element_to(q, v, kind, &x) : path_status(v);
+    if (kind == SJHIP_COL_BOOL) ((u8 *)values)[r] = (u8)x;
+    else ((u64 *)values)[r] = x;
+    status[r] = (u8)st;
+}
+
+// Strings (Arrow's "large string" layout: u64 offsets, the bytes end to end) in three steps over the n = R + 1 records:
+//   k_q_col_len      one lane per record: FindElement, the status, the length of the record's text and the tape index of the
+//                    element (the gather does not walk the record again); entry n has length 0
+//   scan             exclusive prefix of the n + 1 lengths in place (the filter's tile pattern: sums -> one-block scan -> apply),
+//                    entry n = the total
+//   k_q_col_gather   one lane per record: a number's text (StringCvt: at most 25 bytes) and a short string by the lane, a long
+//                    string by the whole wave, 64 bytes at a time (strings run from 0 bytes to megabytes)
+// A float's text is formatted twice -- its length in the first step (float_text_len: the counting form of the formatter), its
+// bytes in the last -- instead of being stashed: the formatter is registers only, and a 32-byte stash for every record would
+// cost more memory traffic than the float records' second formatting costs ALU time.
+struct QCol {
+    u64 *idx;                    // [n] tape index of the element
+    u64 *off;                    // [n + 1] length of the record's text -> its offset in the column (entry n: the total)
+    u8 *status;                  // [n]
+    unsigned long long *tiles;   // [tiles] tile sums -> their exclusive prefix (k_q_tile_scan<false>)
+};
+// status and text length of what StringBytes (cvt = false) / StringCvt (parsed_json.go:775-800) return for tape[v]
+__device__ __forceinline__ int element_text_len(const QView &q, u64 v, bool cvt, u64 *len) {
+    const u32 t = (u32)(q.tape[v] >> 56);
+    *len = 0;
+    if (t == '"') {
+        *len = q.tape[v + 1];
+        return SJHIP_COL_OK;
+    }
+    if (!cvt) return t == 'n' ? SJHIP_COL_NULL : SJHIP_COL_TYPE;
+    switch (t) {
+    case 'l': *len = int_text_len(q.tape[v + 1]); return SJHIP_COL_OK;
+    case 'u': *len = digit_count(q.tape[v + 1]); return SJHIP_COL_OK;
+    case 'd': *len = float_text_len(q.tape[v + 1]); return *len ? SJHIP_COL_OK : SJHIP_COL_TYPE;  // (0: Inf / NaN, never on a tape)
+    case 't': *len = 4; return SJHIP_COL_OK;
+    case 'f': *len = 5; return SJHIP_COL_OK;
+    case 'n': *len = 4; return SJHIP_COL_OK;
+    }
+    return SJHIP_COL_TYPE;  // { [
+}
+__global__ __launch_bounds__(256) void k_q_col_len(QView q, QPath pth, u32 cvt, QCol c) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    if (r > q.R) {
+        if (r == q.R + 1) c.off[r] = 0;
+        return;
+    }
+    const u64 v = record_find_path(q, pth, r);
+    u64 len = 0;
+    const int st = v < SJHIP_PATH_NOT_OBJECT ? element_text_len(q, v, cvt != 0, &len) : path_status(v);
+    c.idx[r] = v;
+    c.off[r] = len;
+    c.status[r] = (u8)st;
+}
+__global__ __launch_bounds__(QT) void k_q_col_tile_sums(QCol c, u32 m) {
+    __shared__ unsigned long long s_w[QT / 64];
+    const int tid = threadIdx.x;
+    const u32 base = blockIdx.x * QTILE + (u32)tid * QI;
+    u64 len[QI];
+    q_load4(c.off, base, m, (u64)0, len);
+    unsigned long long tb = 0;
+#pragma unroll
+    for (int k = 0; k < QI; k++) tb += len[k];
+    unsigned long long tot = 0;
+    (void)q_block_excl_sum(tb, s_w, tid, &tot);
+    if (tid == 0) c.tiles[blockIdx.x] = tot;
+}
+__global__ __launch_bounds__(QT) void k_q_col_tile_apply(QCol c, u32 m) {
+    __shared__ unsigned long long s_w[QT / 64];
+    const int tid = threadIdx.x;
+    const u32 base = blockIdx.x * QTILE + (u32)tid * QI;
+    u64 len[QI];
+    q_load4(c.off, base, m, (u64)0, len);
+    unsigned long long tb = 0;
+#pragma unroll
+    for (int k = 0; k < QI; k++) tb += len[k];
+    unsigned long long pb = c.tiles[blockIdx.x] + q_block_excl_sum(tb, s_w, tid, nullptr);
+#pragma unroll
+    for (int k = 0; k < QI; k++) {
+        if (base + k < m) c.off[base + k] = pb;
+        pb += len[k];
+    }
+}
+// out_off[0 .. n] (the part's own offsets, from 0), out_status[n], data: the column (d_col).  One lane per record for what is
+// per record -- the offset, the status, a number's text (at most 25 bytes), a string of up to SHORT bytes -- and the whole wave
+// for each longer string of its 64 records in turn, 64 bytes at a time (strings run from 0 bytes to megabytes).
+static constexpr u64 COL_SHORT = 32;
+__device__ __forceinline__ void copy_bytes(u8 *dst, const u8 *src, u64 len, u64 first, u64 step) {
+    for (u64 k = first; k < len; k += step) dst[k] = src[k];
+}
+__global__ __launch_bounds__(256) void k_q_col_gather(QView q, QCol c, u64 *out_off, u8 *out_status, Arr<u8> data) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    u64 o = 0, len = 0, w = 0;
+    bool wide = false;
+    if (r <= q.R) {
+        o = c.off[r];
+        len = c.off[r + 1] - o;
+        const u8 st = c.status[r];
+        out_off[r] = o;
+        out_status[r] = st;
+        if (r == q.R) out_off[r + 1] = o + len;
+        if (st == SJHIP_COL_OK && len) {
+            const u64 v = c.idx[r];
+            w = q.tape[v];
+            const u32 t = (u32)(w >> 56);
+            if (t == '"') {
+                wide = len > COL_SHORT;
+                if (!wide) copy_bytes(arr_at(data, o, len), str_bytes(q, w, len), len, 0, 1);
+            } else {
+                u8 *dst = arr_at(data, o, len);
+                if (t == 'l') (void)format_int(q.tape[v + 1], dst);
+                else if (t == 'u') (void)format_uint(q.tape[v + 1], dst);
+                else if (t == 'd') (void)format_float(q.tape[v + 1], dst);
+                else {
+                    const char *lit = t == 't' ? "true" : (t == 'f' ? "false" : "null");
+                    for (u64 k = 0; k < len; k++) dst[k] = (u8)lit[k];
+                }
+            }
+        }
+    }
+    for (u64 todo = __ballot(wide); todo; todo &= todo - 1) {  // the wave's long strings, one after another
+        const int j = __ffsll((unsigned long long)todo) - 1;
+        const u64 oj = (u64)__shfl((long long)o, j, 64), lj = (u64)__shfl((long long)len, j, 64), wj = (u64)__shfl((long long)w, j, 64);
+        copy_bytes(arr_at(data, oj, lj), str_bytes(q, wj, lj), lj, (u64)lane, 64);
+    }
+}
+
 }  // namespace
 
 namespace sj {
@@ -552,6 +710,16 @@ static int result_parts(sjhip_ctx *ctx, sjhip_ctx **parts, int cap) {
     return n;
 }
 static constexpr int MAX_PARTS = 4096;  // (parse_nd_big's own limit)
+// the same on the heap, as many as there are (no thread_local array: a library linked at start-up carries its thread_local
+// storage in the static TLS block of every thread of the process)
+static std::vector<sjhip_ctx *> result_parts(sjhip_ctx *ctx) {
+    std::vector<sjhip_ctx *> parts;
+    if (!ctx->big_valid) parts.push_back(ctx);
+    else
+        for (int k = 0; k < nd_big_shards(ctx); k++)
+            if (sjhip_ctx *c = nd_big_shard(ctx, k)) parts.push_back(c);
+    return parts;
+}
 
 // view of the result held by `part` (ctx itself, or one shard context of ctx's sharded result); errors are left in ctx
 static int make_view(sjhip_ctx *ctx, sjhip_ctx *part, const uint8_t *key, size_t klen, const uint8_t *val, size_t vlen, QView *q,
@@ -740,15 +908,20 @@ static int make_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_le
     return SJHIP_OK;
 }
 
-// Per-record answers (`per` 8-byte words for every record) of every part of ctx's result, laid end to end in `out` in document
-// order: launch(part, q, n, d_out) fills n * per words on the part's device.  cap_records: room in `out`; *records: records of
-// the whole result.
+// Per-record answers of every part of ctx's result, laid end to end in document order: output k holds outs[k].width bytes for
+// every record at outs[k].dst; launch(part, q, n, d) fills n records of every output, output k at d[k] on the part's device.
+// cap_records: room in the outputs; *records: records of the whole result.
+struct RecOut {
+    void *dst;
+    uint32_t width;  // bytes per record
+};
+static constexpr int MAX_OUTS = 2;
 template <typename F>
-static int records_over_parts(sjhip_ctx *ctx, const uint8_t *keys, size_t klen, uint32_t per, uint64_t *out, size_t cap_records,
+static int outputs_over_parts(sjhip_ctx *ctx, const uint8_t *keys, size_t klen, const RecOut *outs, int n_outs, size_t cap_records,
                               size_t *records, const char *who, F launch) {
     static const uint8_t none = 0;
-    static thread_local sjhip_ctx *parts[MAX_PARTS];
-    const int np = result_parts(ctx, parts, MAX_PARTS);
+    const std::vector<sjhip_ctx *> parts = result_parts(ctx);
+    const int np = (int)parts.size();
     if (np == 0) return make_view(ctx, nullptr, keys, klen, &none, 0, nullptr, nullptr);
     size_t total = 0;
     for (int k = 0; k < np; k++) total += (size_t)parts[k]->q_records + 1u;
@@ -765,12 +938,20 @@ static int records_over_parts(sjhip_ctx *ctx, const uint8_t *keys, size_t klen, 
         int rc = make_view(ctx, part, keys, klen, &none, 0, &q, &n);
         if (rc) return rc;
         HIPCHK(hipSetDevice(part->device), "hipSetDevice");
-        const size_t bytes = (size_t)n * per * 8;
-        rc = arena_reserve(part, part->d_kat, bytes + 64);
+        size_t bytes[MAX_OUTS], sum = 0;
+        for (int j = 0; j < n_outs; j++) {
+            bytes[j] = (size_t)n * outs[j].width;
+            sum += (bytes[j] + 255) / 256 * 256;
+        }
+        rc = arena_reserve(part, part->d_kat, sum + 64);
         if (rc) return rc;
-        launch(part, q, n, (u64 *)part->d_kat.p);
+        u8 *d[MAX_OUTS];
+        for (int j = 0, o = 0; j < n_outs; o += (int)((bytes[j] + 255) / 256 * 256), j++) d[j] = (u8 *)part->d_kat.p + o;
+        launch(part, q, n, d);
         HIPCHK(hipGetLastError(), "query launch");
-        HIPCHK(hipMemcpyAsync(out + at * per, part->d_kat.p, bytes, hipMemcpyDeviceToHost, part->stream), "D2H per-record answers");
+        for (int j = 0; j < n_outs; j++)
+            HIPCHK(hipMemcpyAsync((u8 *)outs[j].dst + at * outs[j].width, d[j], bytes[j], hipMemcpyDeviceToHost, part->stream),
+                   "D2H per-record answers");
         at += n;
     }
     for (int k = 0; k < np; k++) {
@@ -779,6 +960,14 @@ static int records_over_parts(sjhip_ctx *ctx, const uint8_t *keys, size_t klen, 
     }
     HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
     return query_bounds_check(ctx);
+}
+// `per` 8-byte words for every record in `out`
+template <typename F>
+static int records_over_parts(sjhip_ctx *ctx, const uint8_t *keys, size_t klen, uint32_t per, uint64_t *out, size_t cap_records,
+                              size_t *records, const char *who, F launch) {
+    const RecOut o = {out, per * 8u};
+    return outputs_over_parts(ctx, keys, klen, &o, 1, cap_records, records, who,
+                              [&](sjhip_ctx *part, const QView &q, uint32_t n, u8 *const *d) { launch(part, q, n, (u64 *)d[0]); });
 }
 
 int sjhip_find_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, uint64_t *index_out,
@@ -838,4 +1027,149 @@ int sjhip_project_keys(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_
                               [&](sjhip_ctx *part, const QView &q, uint32_t n, u64 *d) {
                                   hipLaunchKernelGGL(k_q_project, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, set, d);
                               });
+}
+
+// ---- columns ------------------------------------------------------------------------------------------------------------------
+int sjhip_extract_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int kind, void *values,
+                       uint8_t *status, size_t cap_records, size_t *records) {
+    if (!values || !status || !records || kind < SJHIP_COL_FLOAT || kind > SJHIP_COL_BOOL) return SJHIP_ERR_ARG;
+    QPath pth;
+    size_t klen = 0;
+    const int rc = make_path(ctx, keys, key_lens, n_keys, &pth, &klen);
+    if (rc) return rc;
+    const RecOut outs[2] = {{values, kind == SJHIP_COL_BOOL ? 1u : 8u}, {status, 1u}};
+    return outputs_over_parts(ctx, keys, klen, outs, 2, cap_records, records, "sjhip_extract_path",
+                              [&](sjhip_ctx *part, const QView &q, uint32_t n, u8 *const *d) {
+                                  hipLaunchKernelGGL(k_q_extract, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, pth, kind,
+                                                     (void *)d[0], d[1]);
+                              });
+}
+
+// The column of every part lives in the part's d_col: offsets [n + 1] (from 0 in every part), status [n], the bytes; the work
+// arrays of the three steps (QCol) in its d_kat, which only lives for one call.
+static size_t col_align(size_t b) { return (b + 255) / 256 * 256; }
+static void col_layout(sjhip_ctx *part, size_t n, u64 **off, u8 **status, u8 **data) {
+    u8 *w = (u8 *)part->d_col.p;
+    *off = (u64 *)w;
+    *status = w + col_align((n + 1) * 8);
+    *data = *status + col_align(n);
+}
+
+int sjhip_extract_path_strings(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, uint32_t flags,
+                               size_t *records, size_t *bytes) {
+    if (!records || !bytes || (flags & ~SJHIP_COL_CVT)) return SJHIP_ERR_ARG;
+    QPath pth;
+    size_t klen = 0;
+    int rc = make_path(ctx, keys, key_lens, n_keys, &pth, &klen);
+    if (rc) return rc;
+    ctx->col_valid = 0;  // (the last column is replaced, whatever happens below)
+    static const uint8_t none = 0;
+    const std::vector<sjhip_ctx *> parts = result_parts(ctx);
+    const int np = (int)parts.size();
+    if (np == 0) return make_view(ctx, nullptr, keys, klen, &none, 0, nullptr, nullptr);
+    std::vector<QView> views((size_t)np);  // (a QView carries 2 KiB of keys: on the heap, one per part)
+    std::vector<QCol> cols((size_t)np);
+    // lengths and their scan on every part, each on its own stream; then the totals
+    for (int k = 0; k < np; k++) {
+        sjhip_ctx *part = parts[k];
+        QView &q = views[k];
+        uint32_t n = 0;
+        rc = make_view(ctx, part, keys, klen, &none, 0, &q, &n);
+        if (rc) return rc;
+        HIPCHK(hipSetDevice(part->device), "hipSetDevice");
+        const u32 m = n + 1u, tiles = (m + QTILE - 1) / QTILE;
+        rc = arena_reserve(part, part->d_kat, 256 + col_align((size_t)n * 8) + col_align((size_t)m * 8) + col_align(n) +
+                                                  col_align((size_t)tiles * 8) + 64);
+        if (rc) return rc;
+        u8 *w = (u8 *)part->d_kat.p;
+        unsigned long long *totals = (unsigned long long *)w;
+        QCol &c = cols[k];
+        c.idx = (u64 *)(w + 256);
+        c.off = (u64 *)((u8 *)c.idx + col_align((size_t)n * 8));
+        c.status = (u8 *)c.off + col_align((size_t)m * 8);
+        c.tiles = (unsigned long long *)(c.status + col_align(n));
+        QTiles T = {};
+        T.tb = c.tiles;
+        hipLaunchKernelGGL(k_q_col_len, dim3((m + 255) / 256), dim3(256), 0, part->stream, q, pth, flags & SJHIP_COL_CVT, c);
+        hipLaunchKernelGGL(k_q_col_tile_sums, dim3(tiles), dim3(QT), 0, part->stream, c, m);
+        hipLaunchKernelGGL(k_q_tile_scan<false>, dim3(1), dim3(1024), 0, part->stream, T, tiles, totals, 0u);
+        hipLaunchKernelGGL(k_q_col_tile_apply, dim3(tiles), dim3(QT), 0, part->stream, c, m);
+        HIPCHK(hipGetLastError(), "column launch");
+        HIPCHK(hipMemcpyAsync(part->h_scratch + 512, totals + 2, 8, hipMemcpyDeviceToHost, part->stream), "D2H column bytes");
+    }
+    size_t total_records = 0, total_bytes = 0;
+    for (int k = 0; k < np; k++) {
+        sjhip_ctx *part = parts[k];
+        HIPCHK(hipSetDevice(part->device), "hipSetDevice");
+        HIPCHK(hipStreamSynchronize(part->stream), "column sync");
+        part->col_records = (size_t)views[k].R + 1u;
+        part->col_bytes = (size_t)*(const unsigned long long *)(part->h_scratch + 512);
+        total_records += part->col_records;
+        total_bytes += part->col_bytes;
+    }
+    // the gather on every part, into the part's d_col
+    for (int k = 0; k < np; k++) {
+        sjhip_ctx *part = parts[k];
+        const size_t n = part->col_records;
+        HIPCHK(hipSetDevice(part->device), "hipSetDevice");
+        rc = arena_reserve(part, part->d_col, col_align((n + 1) * 8) + col_align(n) + part->col_bytes + 64);
+        if (rc) return rc;
+        u64 *off;
+        u8 *status, *data;
+        col_layout(part, n, &off, &status, &data);
+        hipLaunchKernelGGL(k_q_col_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, part->stream, views[k], cols[k], off, status,
+                           SJ_ARR(data, part->col_bytes, A_COL));
+        HIPCHK(hipGetLastError(), "column gather launch");
+    }
+    for (int k = 0; k < np; k++) {  // (the work arrays in d_kat are free for the next query once this returns)
+        HIPCHK(hipSetDevice(parts[k]->device), "hipSetDevice");
+        HIPCHK(hipStreamSynchronize(parts[k]->stream), "column gather sync");
+    }
+    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    *records = total_records;
+    *bytes = total_bytes;
+    rc = query_bounds_check(ctx);
+    if (rc == SJHIP_OK) ctx->col_valid = 1;
+    return rc;
+}
+
+int sjhip_fetch_path_strings(sjhip_ctx *ctx, uint64_t *offsets, uint8_t *data, uint8_t *status) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!ctx->col_valid) {  // no column was built, or a parse (or sjhip_ctx_trim) came after it
+        ctx_set_error(ctx, "no string column on the device (sjhip_fetch_path_strings follows sjhip_extract_path_strings, with no parse in between)");
+        return SJHIP_ERR_ARG;
+    }
+    const std::vector<sjhip_ctx *> parts = result_parts(ctx);
+    const int np = (int)parts.size();
+    size_t total_bytes = 0;
+    for (int k = 0; k < np; k++) total_bytes += parts[k]->col_bytes;
+    if (!offsets || !status || (!data && total_bytes)) return SJHIP_ERR_ARG;
+    size_t rec_at = 0, byte_at = 0;
+    for (int k = 0; k < np; k++) {  // every part's offsets but its last (the next part's first, rebased below) + status + bytes
+        sjhip_ctx *part = parts[k];
+        const size_t n = part->col_records;
+        u64 *off;
+        u8 *st, *bytes;
+        col_layout(part, n, &off, &st, &bytes);
+        HIPCHK(hipSetDevice(part->device), "hipSetDevice");
+        HIPCHK(hipMemcpyAsync(offsets + rec_at, off, n * 8, hipMemcpyDeviceToHost, part->stream), "D2H column offsets");
+        HIPCHK(hipMemcpyAsync(status + rec_at, st, n, hipMemcpyDeviceToHost, part->stream), "D2H column status");
+        if (part->col_bytes)
+            HIPCHK(hipMemcpyAsync(data + byte_at, bytes, part->col_bytes, hipMemcpyDeviceToHost, part->stream), "D2H column bytes");
+        rec_at += n;
+        byte_at += part->col_bytes;
+    }
+    rec_at = byte_at = 0;
+    for (int k = 0; k < np; k++) {
+        sjhip_ctx *part = parts[k];
+        HIPCHK(hipSetDevice(part->device), "hipSetDevice");
+        HIPCHK(hipStreamSynchronize(part->stream), "column fetch sync");
+        if (byte_at)  // the offsets of a later shard: from the end of the shards in front of it
+            for (size_t i = rec_at; i < rec_at + part->col_records; i++) offsets[i] += byte_at;
+        rec_at += part->col_records;
+        byte_at += part->col_bytes;
+    }
+    offsets[rec_at] = byte_at;
+    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    return SJHIP_OK;
 }

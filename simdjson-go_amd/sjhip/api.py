@@ -286,6 +286,48 @@ class Context:
         self._check(L.sjhip_project_keys(self._h, blob, lens, n, out.ctypes.data, out.shape[0], C.byref(cnt)))
         return out[: cnt.value]
 
+    # ---- columns (include/sjhip.h: sjhip_extract_path / _extract_path_strings / _fetch_path_strings) --------------------------
+    COL_FLOAT, COL_INT, COL_UINT, COL_BOOL = range(4)
+    COL_OK, COL_NOT_FOUND, COL_NOT_OBJECT, COL_TYPE, COL_NULL, COL_RANGE = range(6)
+    COL_CVT = 1
+    _COL_DTYPES = {0: np.float64, 1: np.int64, 2: np.uint64, 3: np.uint8}
+
+    def extract_path(self, path, kind):
+        """Iter.FindElement(path...) then Iter.Float / Int / Uint / Bool (kind = COL_*) on every record, on the device.
+        -> (values: float64 / int64 / uint64 / uint8 array, status: uint8 array of COL_OK ... COL_RANGE); 0 where not OK"""
+        blob, lens, n = self._keys(path)
+        L = _lib.lib()
+        dt = self._COL_DTYPES[int(kind)]
+        cnt = C.c_size_t(0)
+        probe_v, probe_s = np.empty(1, dtype=dt), np.empty(1, dtype=np.uint8)
+        L.sjhip_extract_path(self._h, blob, lens, n, int(kind), probe_v.ctypes.data, probe_s.ctypes.data, 0,
+                             C.byref(cnt))  # (no room: only the record count is set)
+        values = np.empty(max(cnt.value, 1), dtype=dt)
+        status = np.empty(max(cnt.value, 1), dtype=np.uint8)
+        self._check(L.sjhip_extract_path(self._h, blob, lens, n, int(kind), values.ctypes.data, status.ctypes.data, values.size,
+                                         C.byref(cnt)))
+        return values[: cnt.value], status[: cnt.value]
+
+    def extract_path_strings(self, path, cvt=False, fetch=True):
+        """Iter.FindElement(path...) then Iter.StringBytes (or StringCvt with cvt=True) on every record, built on the device.
+        -> (offsets: uint64 array of records + 1, data: bytes, status: uint8 array) -- Arrow's large-string layout; with
+        fetch=False the column stays on the device and (records, bytes) is returned"""
+        blob, lens, n = self._keys(path)
+        L = _lib.lib()
+        nr, nb = C.c_size_t(0), C.c_size_t(0)
+        self._check(L.sjhip_extract_path_strings(self._h, blob, lens, n, self.COL_CVT if cvt else 0, C.byref(nr), C.byref(nb)))
+        if not fetch:
+            return nr.value, nb.value
+        return self.fetch_path_strings(nr.value, nb.value)
+
+    def fetch_path_strings(self, records, nbytes):
+        """the column of the last extract_path_strings (its records and bytes) -> (offsets, data, status)"""
+        offsets = np.empty(records + 1, dtype=np.uint64)
+        data = np.empty(max(nbytes, 1), dtype=np.uint8)
+        status = np.empty(max(records, 1), dtype=np.uint8)
+        self._check(_lib.lib().sjhip_fetch_path_strings(self._h, offsets.ctypes.data, data.ctypes.data, status.ctypes.data))
+        return offsets, data[:nbytes].tobytes(), status[:records]
+
     def serialize(self, fetch=True, dedup=False):
         """Serializer.Serialize (format v3, CompressNone) of the device-resident result of the last parse.
         -> the framed stream as a uint8 array (what the reference's Deserialize reads), or its sizes with fetch=False.
