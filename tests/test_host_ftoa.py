@@ -3,7 +3,6 @@ appendFloat + its copy of Go's Ryu, ftoaryu.go) against an independent source of
 Python's repr (David Gay's algorithm) -- laid out by Go's rules (parsed_json.go:1250-1272, appendfloat_f.go, strconv %e),
 and against the floats in the reference's expected MarshalJSON texts."""
 import ctypes as C
-import decimal
 import math
 import random
 import struct
@@ -11,6 +10,7 @@ import struct
 import pytest
 
 import __graft_entry__ as G
+from number_cases import go_format  # appendFloat(x) from Python's shortest digits
 
 
 @pytest.fixture(scope="module")
@@ -21,36 +21,6 @@ def L():
     lib.sj_selftest_format_int.argtypes = [C.c_uint64, C.c_int, C.c_char_p]
     lib.sj_selftest_format_int.restype = C.c_uint
     return lib
-
-
-def go_format(x):
-    """appendFloat(x) from Python's shortest digits."""
-    if x == 0:
-        return "-0" if math.copysign(1, x) < 0 else "0"
-    sign, digits, exp = decimal.Decimal(repr(x)).as_tuple()
-    digits = list(digits)
-    while len(digits) > 1 and digits[-1] == 0:
-        digits.pop()
-        exp += 1
-    nd, dp = len(digits), len(digits) + exp
-    ds = "".join(map(str, digits))
-    out = "-" if sign else ""
-    a = abs(x)
-    if 1e-6 <= a < 1e21:
-        if dp > 0:
-            out += ds[:min(nd, dp)] + "0" * max(0, dp - nd)
-        else:
-            out += "0"
-        prec = max(nd - dp, 0)
-        if prec:
-            out += "." + "".join(ds[dp + i] if 0 <= dp + i < nd else "0" for i in range(prec))
-        return out
-    out += ds[0] + ("." + ds[1:] if nd > 1 else "")
-    e = dp - 1
-    es = "%s%02d" % ("-" if e < 0 else "+", abs(e))
-    if es[0] == "-" and es[1] == "0":
-        es = "-" + es[2:]
-    return out + "e" + es
 
 
 def fmt(L, bits):

@@ -11,7 +11,7 @@ import pytest
 import fixtures
 import golden_util as GU
 import oracle_lib as O
-from test_host_ftoa import go_format
+from number_cases import go_format
 
 CORP = GU.load("corpus")
 

@@ -1,6 +1,7 @@
 """Time-boxed randomized parity run on the GPU against the oracle (fresh seeds every run unless one is given):
     python tools/gpu_soak.py [seconds] [seed]
-Generated records (tests/test_gpu_parse._random_value: nested containers, every escape form, numbers of all shapes) as
+Generated records (tests/test_gpu_parse._random_value: nested containers, every escape form, numbers of all shapes; one
+value in eight is a number text of a tests/number_cases.py family: ties, binade edges, subnormals, long mantissas) as
 single documents, arrays and NDJSON, plus byte mutations of them (flipped, deleted, duplicated bytes: mostly invalid
 documents -- the verdict must match), and every eighth round a document of 4-7 MB of a random token density (large documents are
 laid out for the density the context has learned: the path depends on the order) -- each through Parse / ParseND in both copy
@@ -18,12 +19,23 @@ for p in (os.path.join(ROOT, "simdjson-go_amd"), os.path.join(ROOT, "tests")):
 import numpy as np  # noqa: E402
 import oracle_lib as O  # noqa: E402
 import sjhip  # noqa: E402
-from test_gpu_parse import _random_value  # noqa: E402
+import number_cases  # noqa: E402
+from test_gpu_parse import _random_value as _generated_value  # noqa: E402
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else int(time.time())
 rnd = random.Random(seed)
 ctx = sjhip.Context(0)
+
+
+def _random_value(rnd, depth):
+    """a generated value; one in eight is a number drawn from the families of tests/number_cases.py (the oracle decides, as
+    for everything else here; tests/test_gpu_numbers.py holds the same texts against CPython's conversions)"""
+    if rnd.random() < 0.125:
+        return number_cases.sample(rnd, 1)[0]
+    return _generated_value(rnd, depth)
+
+
 stats = {"docs": 0, "valid": 0, "invalid": 0, "bytes": 0, "marshal": 0, "serialize": 0}
 
 
