@@ -175,12 +175,6 @@ int sjhip_ctx_set_stream(sjhip_ctx *ctx, void *hip_stream) {
 // ---------------------------------------------------------------------------------------------
 // stage 1
 // ---------------------------------------------------------------------------------------------
-#define HIPCHK(call, what)                                   \
-    do {                                                     \
-        hipError_t e_ = (call);                              \
-        if (e_ != hipSuccess) return ctx_hip_fail(ctx, e_, what); \
-    } while (0)
-
 // Reads back the Stage1State and applies the reference's end-of-document verdict
 // (stage1_find_marks_amd64.go:115-129,147).  `last_byte` is msg[len-1].
 static int stage1_verdict(const Stage1State &st, size_t len, uint8_t last_byte) {

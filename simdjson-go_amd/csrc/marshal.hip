@@ -31,12 +31,6 @@
 
 using namespace sj;
 
-#define HIPCHK(call, what)                                        \
-    do {                                                          \
-        hipError_t e_ = (call);                                   \
-        if (e_ != hipSuccess) return ctx_hip_fail(ctx, e_, what); \
-    } while (0)
-
 namespace {
 
 struct MsView {
@@ -157,18 +151,6 @@ __global__ __launch_bounds__(256) void k_ms_keys(KeyView p) {
 #pragma unroll
     for (int k = 0; k < 16; k++)
         if (kd[k] == K_STRING) p.keyflag[o++] = kd[k + 1] == K_COLON ? 1 : 0;
-}
-
-// one block: exclusive prefix sums of up to two per-tile counts; totals[0..1]
-__global__ __launch_bounds__(1024) void k_ms_scan(unsigned long long *a, unsigned long long *b, u32 tiles,
-                                                  unsigned long long *totals) {
-    __shared__ long long s_w[16];
-    const long long ta = block1024_scan_array<false>((long long *)a, tiles, s_w, (int)threadIdx.x);
-    const long long tb = b ? block1024_scan_array<false>((long long *)b, tiles, s_w, (int)threadIdx.x) : 0;
-    if (threadIdx.x == 0 && totals) {
-        totals[0] = (unsigned long long)ta;
-        totals[1] = (unsigned long long)tb;
-    }
 }
 
 // ---- descriptors of the single-pass form: status in the two top bits, a byte count below -----------------------------
@@ -350,7 +332,7 @@ __device__ __forceinline__ u64 low_bytes(u64 w, u32 valid) { return valid >= 8u 
 
 // WPE: waves per SIMD the register allocation aims at (launch bound), WINDOW: bytes of text a tile stages in LDS
 // MODE 0: the counting pass (per-tile sizes; escaped lengths of the strings kept in slen), MODE 1: the writing pass of that
-// pair (sizes scanned by k_ms_scan in between), MODE 2: both in ONE pass -- a tile measures, publishes its size in a
+// pair (sizes scanned by k_tw_scan_sums in between), MODE 2: both in ONE pass -- a tile measures, publishes its size in a
 // descriptor, takes the sum of the tiles in front of it from their descriptors (decoupled look-back, tiles numbered by a
 // ticket so that every predecessor is running or done) and writes; the text buffer is sized by a bound (ms_text_bound).
 // STAGE (round 6): bytes of Strings.B a tile reads into LDS with coalesced 16-byte loads before it looks at its short strings --
@@ -890,11 +872,8 @@ static void launch_ms_tile(const MsView &p, hipStream_t st) {
 // debug build (-DSJ_DEBUG_BOUNDS): an out-of-bounds string of a MarshalJSON kernel fails the call (this translation unit's record)
 static int marshal_bounds_check(sjhip_ctx *ctx) {
 #if defined(SJ_DEBUG_BOUNDS)
-    BoundsHit hit = {};
-    if (hipMemcpyFromSymbol(&hit, HIP_SYMBOL(g_bounds_hit), sizeof hit) != hipSuccess) return SJHIP_OK;
-    if (hit.hits) {
-        const BoundsHit zero = {};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bounds_hit), &zero, sizeof zero);
+    BoundsHit hit;
+    if (bounds_take(&hit) && hit.hits) {
         ctx_set_error(ctx, "bounds check (MarshalJSON): %u out-of-bounds strings, the first in array %u (sj_bounds.h ArrId) at byte %llu of %llu",
                       hit.hits, hit.id, hit.index, hit.size);
         return SJHIP_ERR_HIP;
@@ -974,8 +953,8 @@ static int marshal_part(sjhip_ctx *ctx, sjhip_ctx *part, size_t *text_len) {
     p.kf_tape = (part->kf_valid) ? (const u8 *)part->d_keyflag.p : nullptr;
     if (!p.kf_tape) {
         hipLaunchKernelGGL(k_ms_keys<false>, dim3(kv.tiles), dim3(256), 0, part->stream, kv);
-        hipLaunchKernelGGL(k_ms_scan, dim3(1), dim3(1024), 0, part->stream, kv.cnt, (unsigned long long *)nullptr, kv.tiles,
-                           (unsigned long long *)nullptr);
+        hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, part->stream, kv.cnt, (unsigned long long *)nullptr,
+                           (unsigned long long *)nullptr, kv.tiles, (unsigned long long *)nullptr);
         hipLaunchKernelGGL(k_ms_keys<true>, dim3(kv.tiles), dim3(256), 0, part->stream, kv);
     }
     long long *const tile_last = p.tile_last;
@@ -1056,8 +1035,8 @@ static int marshal_part(sjhip_ctx *ctx, sjhip_ctx *part, size_t *text_len) {
         }
         launch_ms_tile<0>(p, part->stream);
         // (the prefix of the string counts is only needed to index the recovered key flags)
-        hipLaunchKernelGGL(k_ms_scan, dim3(1), dim3(1024), 0, part->stream, p.cnt_b, p.kf_tape ? (unsigned long long *)nullptr : p.cnt_s,
-                           p.tiles, p.totals);
+        hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, part->stream, p.cnt_b, p.kf_tape ? (unsigned long long *)nullptr : p.cnt_s,
+                           (unsigned long long *)nullptr, p.tiles, p.totals);  // (totals[2] stays the tiles' error flags)
         HIPCHK(hipGetLastError(), "marshal launch");
         HIPCHK(hipMemcpyAsync(h, p.totals, 24, hipMemcpyDeviceToHost, part->stream), "D2H totals");
         HIPCHK(hipStreamSynchronize(part->stream), "marshal sync");
@@ -1092,9 +1071,7 @@ int sjhip_marshal_json(sjhip_ctx *ctx, size_t *text_len) {
     if (!ctx->big_valid) return marshal_part(ctx, ctx, text_len);
     size_t total = 0;
     int np = 0;
-    for (int k = 0; k < nd_big_shards(ctx); k++) {
-        sjhip_ctx *part = nd_big_shard(ctx, k);
-        if (!part) continue;
+    for (sjhip_ctx *part : result_parts(ctx)) {
         size_t len = 0;
         const int rc = marshal_part(ctx, part, &len);
         if (rc) {
@@ -1121,9 +1098,8 @@ int sjhip_fetch_marshaled(sjhip_ctx *ctx, uint8_t *dst) {
     if (ctx->big_valid) {  // the shards' texts, joined with the newline between two records
         size_t at = 0;
         int np = 0;
-        for (int k = 0; k < nd_big_shards(ctx); k++) {
-            sjhip_ctx *part = nd_big_shard(ctx, k);
-            if (!part || !part->ms_valid) continue;
+        for (sjhip_ctx *part : result_parts(ctx)) {
+            if (!part->ms_valid) continue;
             if (np++ && dst) dst[at++] = '\n';
             HIPCHK(hipSetDevice(part->device), "hipSetDevice");
             if (part->ms_len && dst)

@@ -328,6 +328,14 @@ sjhip_ctx *sj::nd_big_shard(const sjhip_ctx *ctx, int k) {
     const Shard &s = ctx->big->shards[(size_t)k];
     return s.len ? s.ctx : nullptr;
 }
+std::vector<sjhip_ctx *> sj::result_parts(sjhip_ctx *ctx) {
+    std::vector<sjhip_ctx *> parts;
+    if (!ctx->big_valid) parts.push_back(ctx);
+    else
+        for (int k = 0; k < nd_big_shards(ctx); k++)
+            if (sjhip_ctx *c = nd_big_shard(ctx, k)) parts.push_back(c);
+    return parts;
+}
 
 void sj::release_nd_big(sjhip_ctx *ctx) {
     if (ctx->big) sjhip_multi_destroy(ctx->big);

@@ -14,12 +14,6 @@
 
 using namespace sj;
 
-#define HIPCHK(call, what)                                        \
-    do {                                                          \
-        hipError_t e_ = (call);                                   \
-        if (e_ != hipSuccess) return ctx_hip_fail(ctx, e_, what); \
-    } while (0)
-
 // Phase 1 (parse_begin): stage 1, then stage 2 up to the device-wide scans; a shard reads back the sizes.
 // Phase 2 (parse_finish): the rest of stage 2 with the rebasing offsets, then the verdict.
 // documents up to this size are parsed with one host synchronisation (SJHIP_SMALL_BYTES overrides; 0 turns it off)

@@ -22,18 +22,12 @@
 #include "sj_bounds.h"
 #include "sj_ftoa.h"
 #include "sj_stage2.h"
+#include "sj_tapewalk.h"
 
 using namespace sj;
 
-#define HIPCHK(call, what)                                        \
-    do {                                                          \
-        hipError_t e_ = (call);                                   \
-        if (e_ != hipSuccess) return ctx_hip_fail(ctx, e_, what); \
-    } while (0)
-
 namespace {
 
-static constexpr u64 PAYLOAD = 0x00ffffffffffffffull;  // JSONVALUEMASK, parsed_json.go:27
 static constexpr u32 NONE32 = 0xffffffffu;
 static constexpr int QMAX = 1024;  // longest key / value a query may name (they travel as kernel arguments)
 
@@ -62,7 +56,7 @@ __device__ __forceinline__ u64 rec_open(const QView &q, u32 r) { return q.tape_b
 __device__ __forceinline__ u64 rec_close(const QView &q, u32 r) { return r == q.R ? q.tape_len - 1u : q.tape_base + q.nl_off[r]; }
 
 __device__ __forceinline__ const u8 *str_bytes(const QView &q, u64 word, u64 len) {
-    const u64 p = word & PAYLOAD;
+    const u64 p = word & TW_PAYLOAD;
     return (p & STRINGBUFBIT) ? arr_at(q.strings, p & (STRINGBUFBIT - 1), len) : arr_at(q.msg, p, len);
 }
 __device__ __forceinline__ bool str_equals(const QView &q, u64 word, u64 len, const u8 *want, u32 wlen) {
@@ -71,316 +65,6 @@ __device__ __forceinline__ bool str_equals(const QView &q, u64 word, u64 len, co
     for (u32 k = 0; k < wlen; k++)
         if (s[k] != want[k]) return false;
     return true;
-}
-
-// FindKey(key) on the root object of record r + the string compare of countWhere
-__device__ bool record_matches(const QView &q, u32 r) {
-    const u64 o = rec_open(q, r);
-    const u64 w = q.tape[o + 1];
-    if ((w >> 56) != '{') return false;
-    const u64 end = (w & PAYLOAD) - 1;  // index of the closing '}'
-    u64 i = (u64)o + 2;
-    while (i < end) {
-        const u64 kw = q.tape[i], kl = q.tape[i + 1];  // member key
-        const u64 v = i + 2, vw = q.tape[v];
-        const u32 vt = (u32)(vw >> 56);
-        if (str_equals(q, kw, kl, q.key, q.klen))
-            return vt == '"' && str_equals(q, vw, q.tape[v + 1], q.val, q.vlen);  // FindKey returns the first match
-        if (vt == '{' || vt == '[') i = vw & PAYLOAD;  // behind the matching close
-        else if (vt == '"' || vt == 'l' || vt == 'u' || vt == 'd') i = v + 2;
-        else i = v + 1;  // t f n
-    }
-    return false;
-}
-
-__global__ __launch_bounds__(256) void k_q_count(QView q, unsigned long long *count) {
-    const u32 r = blockIdx.x * 256 + threadIdx.x;
-    const bool m = r <= q.R && record_matches(q, r);
-    const u64 b = __ballot(m);
-    if ((threadIdx.x & 63) == 0 && b) atomicAdd(count, (unsigned long long)__popcll(b));
-}
-
-// ---- filter: pass 1, one lane per record ------------------------------------------------------------------------
-struct QRec {
-    u32 *flag;      // [R+1] 1 if the record matches
-    u32 *words;     // [R+1] its tape words if it matches, else 0      -> exclusive prefix = new index of its open root
-    u32 *first_str; // [R+1] Strings.B offset of its first string, NONE32 if it has none
-    u32 *s_len;     // [R+1] bytes of Strings.B a matching record owns (pass 2)
-    u32 *s_pre;     // [R+1] their exclusive prefix = new Strings.B offset of its first string (pass 2)
-    unsigned long long *totals;  // matching records, tape words, Strings.B bytes
-};
-
-__global__ __launch_bounds__(256) void k_q_mark(QView q, QRec o) {
-    const u32 r = blockIdx.x * 256 + threadIdx.x;
-    if (r > q.R) return;
-    const bool m = record_matches(q, r);
-    const u32 a = rec_open(q, r), c = rec_close(q, r);
-    o.flag[r] = m ? 1u : 0u;
-    o.words[r] = m ? c - a + 1u : 0u;
-    // first string of the record: walk its items (a number's second word is raw data and must be stepped over)
-    u32 fs = NONE32;
-    for (u64 i = (u64)a + 1; i < c;) {
-        const u64 w = q.tape[i];
-        const u32 t = (u32)(w >> 56);
-        if (t == '"') {
-            fs = (u32)(w & (STRINGBUFBIT - 1));  // every string is copied (checked by the host): a Strings.B offset
-            break;
-        }
-        i += (t == 'l' || t == 'u' || t == 'd') ? 2 : 1;
-    }
-    o.first_str[r] = fs;
-}
-
-// ---- pass 2: exclusive prefixes of words / string bytes over the records, and the Strings.B range of every record:
-// [its first string, the first string of any later record) -- strings are laid out in document order, so "the first
-// string of any later record" is a minimum over the records behind it.  Tiles of 1024 records (256 threads x 4
-// consecutive records), tile sums scanned by one block, then applied: sums -> scan -> apply (word prefixes, string
-// lengths and their tile sums) -> scan -> apply (string prefixes).
-static constexpr int QT = 256, QI = 4, QTILE = QT * QI;
-struct QTiles {
-    unsigned long long *tw;  // [tiles] tape words of the tile's matching records -> their exclusive prefix
-    unsigned long long *tb;  // [tiles] Strings.B bytes of the tile's matching records -> their exclusive prefix
-    u32 *tc;                 // [tiles] matching records of the tile
-    u32 *tf;                 // [tiles] first string of the tile -> first string of any later tile
-};
-__device__ __forceinline__ unsigned long long q_block_excl_sum(unsigned long long v, unsigned long long *s_w, int tid,
-                                                                unsigned long long *total) {
-    const int lane = tid & 63, wave = tid >> 6;
-    unsigned long long incl = v;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const unsigned long long o = (unsigned long long)__shfl_up((long long)incl, s, 64);
-        if (lane >= s) incl += o;
-    }
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    unsigned long long before = 0, tot = 0;
-    for (int w = 0; w < QT / 64; w++) {
-        if (w < wave) before += s_w[w];
-        tot += s_w[w];
-    }
-    if (total) *total = tot;
-    __syncthreads();
-    return before + incl - v;
-}
-// minimum over the threads behind this one (NONE32 if there is none)
-__device__ __forceinline__ u32 q_block_excl_suffix_min(u32 v, u32 *s_w, int tid) {
-    const int lane = tid & 63, wave = tid >> 6;
-    u32 incl = v;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const u32 o = (u32)__shfl_down((int)incl, s, 64);
-        if (lane + s < 64) incl = o < incl ? o : incl;
-    }
-    if (lane == 0) s_w[wave] = incl;
-    __syncthreads();
-    u32 after = NONE32;
-    for (int w = 0; w < QT / 64; w++)
-        if (w > wave) after = s_w[w] < after ? s_w[w] : after;
-    u32 ex = (u32)__shfl_down((int)incl, 1, 64);
-    if (lane == 63) ex = NONE32;
-    __syncthreads();
-    return ex < after ? ex : after;
-}
-template <typename T>
-__device__ __forceinline__ void q_load4(const T *p, u32 base, u32 n, T fill, T (&v)[QI]) {
-#pragma unroll
-    for (int k = 0; k < QI; k++) v[k] = base + k < n ? p[base + k] : fill;  // consecutive: 16 bytes per thread
-}
-
-__global__ __launch_bounds__(QT) void k_q_tile_sums(QRec o, u32 n, QTiles T) {
-    __shared__ unsigned long long s_w[QT / 64];
-    __shared__ u32 s_m[QT / 64];
-    const int tid = threadIdx.x;
-    const u32 base = blockIdx.x * QTILE + (u32)tid * QI;
-    u32 w[QI], fl[QI], f[QI];
-    q_load4(o.words, base, n, 0u, w);
-    q_load4(o.flag, base, n, 0u, fl);
-    q_load4(o.first_str, base, n, NONE32, f);
-    unsigned long long tw = 0, tc = 0;
-    u32 mn = NONE32;
-#pragma unroll
-    for (int k = 0; k < QI; k++) {
-        tw += w[k];
-        tc += fl[k];
-        mn = f[k] < mn ? f[k] : mn;
-    }
-    unsigned long long tot_w = 0, tot_c = 0;
-    (void)q_block_excl_sum(tw, s_w, tid, &tot_w);
-    (void)q_block_excl_sum(tc, s_w, tid, &tot_c);
-    const u32 later = q_block_excl_suffix_min(mn, s_m, tid);
-    if (tid == 0) {
-        T.tw[blockIdx.x] = tot_w;
-        T.tc[blockIdx.x] = (u32)tot_c;
-        T.tf[blockIdx.x] = mn < later ? mn : later;
-    }
-}
-
-// one block over the tiles.  FIRST: tw -> exclusive prefix, tf -> first string of any later tile, totals[0], [1];
-// otherwise tb -> exclusive prefix, totals[2]
-template <bool FIRST>
-__global__ __launch_bounds__(1024) void k_q_tile_scan(QTiles T, u32 tiles, unsigned long long *totals, u32 strings_len) {
-    __shared__ unsigned long long s_a[1024], s_c[1024];
-    __shared__ u32 s_f[1024];
-    const u32 tid = threadIdx.x, per = (tiles + 1023u) / 1024u;
-    const u32 lo = tid * per < tiles ? tid * per : tiles, hi = lo + per < tiles ? lo + per : tiles;
-    unsigned long long *col = FIRST ? T.tw : T.tb;
-    unsigned long long a = 0, c = 0;
-    u32 first = NONE32;
-    for (u32 t = lo; t < hi; t++) {
-        a += col[t];
-        if (FIRST) {
-            c += T.tc[t];
-            first = T.tf[t] < first ? T.tf[t] : first;
-        }
-    }
-    s_a[tid] = a;
-    s_c[tid] = c;
-    s_f[tid] = first;
-    __syncthreads();
-    if (tid == 0) {  // 1024 partials: serial is fine
-        unsigned long long ra = 0, rc = 0;
-        for (int k = 0; k < 1024; k++) {
-            const unsigned long long va = s_a[k];
-            s_a[k] = ra;
-            ra += va;
-            rc += s_c[k];
-        }
-        if (FIRST) {
-            totals[0] = rc;
-            totals[1] = ra;
-            u32 nxt = strings_len;
-            for (int k = 1023; k >= 0; k--) {
-                const u32 v = s_f[k];
-                s_f[k] = nxt;
-                nxt = v < nxt ? v : nxt;
-            }
-        } else {
-            totals[2] = ra;
-        }
-    }
-    __syncthreads();
-    unsigned long long run = s_a[tid];
-    for (u32 t = lo; t < hi; t++) {
-        const unsigned long long v = col[t];
-        col[t] = run;
-        run += v;
-    }
-    if (FIRST) {
-        u32 nxt = s_f[tid];
-        for (u32 t = hi; t > lo; t--) {
-            const u32 v = T.tf[t - 1];
-            T.tf[t - 1] = nxt;
-            nxt = v < nxt ? v : nxt;
-        }
-    }
-}
-
-// words[r] := new index of the record's open root; s_len[r]; tile sums of s_len
-__global__ __launch_bounds__(QT) void k_q_tile_apply1(QRec o, u32 n, QTiles T) {
-    __shared__ unsigned long long s_w[QT / 64];
-    __shared__ u32 s_m[QT / 64];
-    const int tid = threadIdx.x;
-    const u32 base = blockIdx.x * QTILE + (u32)tid * QI;
-    u32 w[QI], fl[QI], f[QI];
-    q_load4(o.words, base, n, 0u, w);
-    q_load4(o.flag, base, n, 0u, fl);
-    q_load4(o.first_str, base, n, NONE32, f);
-    unsigned long long tw = 0;
-    u32 mn = NONE32;
-#pragma unroll
-    for (int k = 0; k < QI; k++) {
-        tw += w[k];
-        mn = f[k] < mn ? f[k] : mn;
-    }
-    unsigned long long pw = T.tw[blockIdx.x] + q_block_excl_sum(tw, s_w, tid, nullptr);
-    const u32 later = q_block_excl_suffix_min(mn, s_m, tid), behind_tile = T.tf[blockIdx.x];
-    u32 nxt = later < behind_tile ? later : behind_tile;  // first string of any record behind this thread's four
-    u32 len[QI];
-    unsigned long long tb = 0;
-#pragma unroll
-    for (int k = QI - 1; k >= 0; k--) {
-        u32 l = 0;
-        if (f[k] != NONE32) {
-            l = nxt - f[k];
-            nxt = f[k];
-        }
-        len[k] = fl[k] ? l : 0u;
-        tb += len[k];
-    }
-#pragma unroll
-    for (int k = 0; k < QI; k++) {
-        if (base + k < n) {
-            o.words[base + k] = (u32)pw;
-            o.s_len[base + k] = len[k];
-        }
-        pw += w[k];
-    }
-    unsigned long long tot_b = 0;
-    (void)q_block_excl_sum(tb, s_w, tid, &tot_b);
-    if (tid == 0) T.tb[blockIdx.x] = tot_b;
-}
-
-// s_pre[r] := new Strings.B offset of the record's first string
-__global__ __launch_bounds__(QT) void k_q_tile_apply2(QRec o, u32 n, QTiles T) {
-    __shared__ unsigned long long s_w[QT / 64];
-    const int tid = threadIdx.x;
-    const u32 base = blockIdx.x * QTILE + (u32)tid * QI;
-    u32 len[QI];
-    q_load4(o.s_len, base, n, 0u, len);
-    unsigned long long tb = 0;
-#pragma unroll
-    for (int k = 0; k < QI; k++) tb += len[k];
-    unsigned long long pb = T.tb[blockIdx.x] + q_block_excl_sum(tb, s_w, tid, nullptr);
-#pragma unroll
-    for (int k = 0; k < QI; k++) {
-        if (base + k < n) o.s_pre[base + k] = (u32)pb;
-        pb += len[k];
-    }
-}
-
-// ---- pass 3: one wave per record: its tape words with every stored index rebased, then its strings -------------------
-// Which words are tags?  A number's value and a string's length are raw 64-bit data whose top byte can look like any
-// tag.  Raw words only ever follow a two-word tag (" l u d) that is itself not raw, so with c(i) = "the top byte of
-// word i is one of \" l u d" and p = the last index below i with c(p) = 0 (the opening root word always is one):
-//     word i is raw  <=>  i - p - 1 is odd
-// which a wave evaluates for 64 words at a time from one ballot.
-__global__ __launch_bounds__(256) void k_q_copy(QView q, QRec o, u64 *out_tape, u8 *out_strings, u32 total_words) {
-    const u32 r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (r > q.R || !o.flag[r]) return;  // wave-uniform
-    const u32 a = rec_open(q, r), c = rec_close(q, r);
-    const u32 na = o.words[r];  // new index of the opening root
-    const u32 nwords = c - a + 1u;
-    const long long dw = (long long)na - (long long)a;
-    const u32 sb = o.first_str[r], slen = o.s_len[r], ns = o.s_pre[r];
-    const u64 ds = (u64)((long long)ns - (long long)sb);  // only used when the record has a string
-    long long p_prev = -1;  // last index below the group with c = 0, relative to the record (none: word 0 is the first)
-    for (u32 g = 0; g < nwords; g += 64) {
-        const u32 i = g + (u32)lane;
-        const bool in = i < nwords;
-        const u64 w = in ? q.tape[a + i] : 0;
-        const u32 t = (u32)(w >> 56);
-        const bool two = t == '"' || t == 'l' || t == 'u' || t == 'd';
-        const u64 inmask = __ballot(in);
-        const u64 zm = ~__ballot(in && two) & inmask;  // words of the group with c = 0
-        const u64 zeros_below = zm & (lane ? (~0ull >> (64 - lane)) : 0ull);
-        const long long p = zeros_below ? (long long)g + (63 - __builtin_clzll(zeros_below)) : p_prev;
-        const bool raw = p >= 0 && ((((long long)i - p - 1) & 1) != 0);
-        if (in) {
-            u64 v = w;
-            if (!raw) {
-                if (i == 0) v = ((u64)'r' << 56) | (u64)(na + nwords);  // the next record's open root, or the tape length
-                else if (i == nwords - 1) v = ((u64)'r' << 56) | (u64)na;  // its own open root
-                else if (t == '{' || t == '[' || t == '}' || t == ']') v = (w & ~PAYLOAD) | (u64)((long long)(w & PAYLOAD) + dw);
-                else if (t == '"') v = w + ds;
-            }
-            out_tape[na + i] = v;
-        }
-        if (zm) p_prev = (long long)g + (63 - __builtin_clzll(zm));
-    }
-    (void)total_words;
-    for (u32 k = (u32)lane; k < slen; k += 64) out_strings[ns + k] = q.strings[sb + k];
 }
 
 // ---- paths, typed values, key sets (round 5: Iter.FindElement parsed_json.go:833-865, Object.FindPath parsed_object.go:256-313,
@@ -395,11 +79,10 @@ __device__ __forceinline__ bool key_is(const QView &q, const QPath &pth, u32 j, 
     const u32 b = j ? pth.end[j - 1] : 0u;
     return str_equals(q, word, len, q.key + b, pth.end[j] - b);
 }
-__device__ __forceinline__ u64 skip_value(const QView &q, u64 v) {  // index behind the value whose first word is tape[v]
-    const u64 vw = q.tape[v];
+__device__ __forceinline__ u64 skip_value(u64 v, u64 vw) {  // index behind the value whose first word is vw = tape[v]
     const u32 vt = (u32)(vw >> 56);
-    if (vt == '{' || vt == '[') return vw & PAYLOAD;  // behind the matching close
-    return (vt == '"' || vt == 'l' || vt == 'u' || vt == 'd') ? v + 2 : v + 1;
+    if (vt == '{' || vt == '[') return vw & TW_PAYLOAD;  // behind the matching close
+    return two_word_tag(vw) ? v + 2 : v + 1;
 }
 // FindElement on record r: into the root, into objects, not into arrays; the first member with the key wins at every
 // level.  Returns the tape index of the element's value, SJHIP_PATH_NOT_FOUND (ErrPathNotFound) or SJHIP_PATH_NOT_OBJECT
@@ -408,21 +91,21 @@ __device__ u64 record_find_path(const QView &q, const QPath &pth, u32 r) {
     const u64 o = rec_open(q, r);
     const u64 w = q.tape[o + 1];
     if ((w >> 56) != '{') return SJHIP_PATH_NOT_OBJECT;
-    u64 end = (w & PAYLOAD) - 1;  // index of the closing '}'
+    u64 end = (w & TW_PAYLOAD) - 1;  // index of the closing '}'
     u64 i = (u64)o + 2;
     u32 seg = 0;
     while (i < end) {
-        const u64 v = i + 2;
-        if (key_is(q, pth, seg, q.tape[i], q.tape[i + 1])) {
+        const u64 kw = q.tape[i], kl = q.tape[i + 1];  // member key
+        const u64 v = i + 2, vw = q.tape[v];           // (asked for with the key, as countWhere's walk always did: one round trip per member)
+        if (key_is(q, pth, seg, kw, kl)) {
             if (seg + 1 == pth.n) return v;
-            const u64 vw = q.tape[v];
             if ((vw >> 56) != '{') return SJHIP_PATH_NOT_OBJECT;
-            end = (vw & PAYLOAD) - 1;
+            end = (vw & TW_PAYLOAD) - 1;
             i = v + 1;
             seg++;
             continue;
         }
-        i = skip_value(q, v);
+        i = skip_value(v, vw);
     }
     return SJHIP_PATH_NOT_FOUND;
 }
@@ -492,19 +175,225 @@ __device__ bool element_is(const QView &q, u64 v, int op, u64 want) {
     }
     return false;
 }
+// the record's element at the path exists and satisfies the predicate
+__device__ __forceinline__ bool record_is(const QView &q, const QPath &pth, u32 r, int op, u64 want) {
+    const u64 v = record_find_path(q, pth, r);
+    return v < SJHIP_PATH_NOT_OBJECT && element_is(q, v, op, want);
+}
+// one atomic per wave: the lanes whose record counts
+__device__ __forceinline__ void count_ballot(bool m, unsigned long long *count) {
+    const u64 b = __ballot(m);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(count, (unsigned long long)__popcll(b));
+}
+
+// ---- filter: pass 1, one lane per record ------------------------------------------------------------------------
+struct QRec {
+    u32 *flag;      // [R+1] 1 if the record matches
+    u32 *words;     // [R+1] its tape words if it matches, else 0      -> exclusive prefix = new index of its open root
+    u32 *first_str; // [R+1] Strings.B offset of its first string, NONE32 if it has none
+    u32 *s_len;     // [R+1] bytes of Strings.B a matching record owns (pass 2)
+    u32 *s_pre;     // [R+1] their exclusive prefix = new Strings.B offset of its first string (pass 2)
+    unsigned long long *totals;  // matching records, tape words, Strings.B bytes
+};
+// (key: the one-key path of countWhere(key, value), whose match is FindElement + the string compare)
+__global__ __launch_bounds__(256) void k_q_mark(QView q, QPath key, QRec o) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    if (r > q.R) return;
+    const bool m = record_is(q, key, r, SJHIP_OP_EQ_STRING, 0);
+    const u32 a = rec_open(q, r), c = rec_close(q, r);
+    o.flag[r] = m ? 1u : 0u;
+    o.words[r] = m ? c - a + 1u : 0u;
+    // first string of the record: walk its items, into the containers (a number's second word is raw data and is stepped over)
+    u32 fs = NONE32;
+    for (u64 i = (u64)a + 1; i < c;) {
+        const u64 w = q.tape[i];
+        if ((w >> 56) == '"') {
+            fs = (u32)(w & (STRINGBUFBIT - 1));  // every string is copied (checked by the host): a Strings.B offset
+            break;
+        }
+        i += two_word_tag(w) ? 2 : 1;
+    }
+    o.first_str[r] = fs;
+}
+
+// ---- pass 2: exclusive prefixes of words / string bytes over the records, and the Strings.B range of every record:
+// [its first string, the first string of any later record) -- strings are laid out in document order, so "the first
+// string of any later record" is a minimum over the records behind it.  Tiles of 1024 records (256 threads x 4
+// consecutive records), tile sums scanned by one block (sj_tapewalk.h), then applied: sums -> scans -> apply (word
+// prefixes, string lengths and their tile sums) -> scan -> apply (string prefixes).
+static constexpr int QT = TW_THREADS, QI = 4, QTILE = QT * QI;
+static_assert(QT == 256, "block_excl_sum / block_excl_max of sj_tapewalk.h scan the four waves of a 256-thread block");
+struct QTiles {
+    unsigned long long *tw;  // [tiles] tape words of the tile's matching records -> their exclusive prefix
+    unsigned long long *tb;  // [tiles] Strings.B bytes of the tile's matching records -> their exclusive prefix
+    unsigned long long *tc;  // [tiles] matching records of the tile
+    // [tiles] entry tiles - 1 - t: NONE32 - the first string of tile t (0: it has none).  "The first string of any later tile" is
+    // a minimum over the tiles behind t; mirrored and complemented it is the exclusive running maximum k_tw_scan_last computes
+    // (-1 for the last tile: no tile behind it).
+    long long *tf;
+};
+// minimum over the threads behind this one (NONE32 if there is none)
+__device__ __forceinline__ u32 q_block_excl_suffix_min(u32 v, u32 *s_w, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    u32 incl = v;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const u32 o = (u32)__shfl_down((int)incl, s, 64);
+        if (lane + s < 64) incl = o < incl ? o : incl;
+    }
+    if (lane == 0) s_w[wave] = incl;
+    __syncthreads();
+    u32 after = NONE32;
+    for (int w = 0; w < QT / 64; w++)
+        if (w > wave) after = s_w[w] < after ? s_w[w] : after;
+    u32 ex = (u32)__shfl_down((int)incl, 1, 64);
+    if (lane == 63) ex = NONE32;
+    __syncthreads();
+    return ex < after ? ex : after;
+}
+// the thread's QI consecutive elements of the tile (16 or 32 bytes per thread); -> their sum
+template <typename T>
+__device__ __forceinline__ unsigned long long q_load4(const T *p, u32 n, T fill, T (&v)[QI]) {
+    const u32 base = blockIdx.x * QTILE + threadIdx.x * QI;
+    unsigned long long sum = 0;
+#pragma unroll
+    for (int k = 0; k < QI; k++) {
+        v[k] = base + k < n ? p[base + k] : fill;
+        sum += v[k];
+    }
+    return sum;
+}
+// The two tile steps of an exclusive prefix over a[0 .. n), around the one-block scan of the tile sums (k_tw_scan_sums):
+// sums[tile] := the sum of the tile's elements;  dst[i] := sums[tile] (scanned) + the elements of the tile in front of i.
+template <typename T>
+__device__ __forceinline__ void tile_sums(const T *a, u32 n, unsigned long long *sums) {
+    __shared__ unsigned long long s_w[QT / 64];
+    T v[QI];
+    unsigned long long tot = 0;
+    (void)block_excl_sum(q_load4(a, n, (T)0, v), s_w, (int)threadIdx.x, &tot);
+    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
+}
+template <typename T>
+__device__ __forceinline__ void tile_apply(const T *a, T *dst, u32 n, const unsigned long long *sums) {
+    __shared__ unsigned long long s_w[QT / 64];
+    const u32 base = blockIdx.x * QTILE + threadIdx.x * QI;
+    T v[QI];
+    unsigned long long pre = block_excl_sum(q_load4(a, n, (T)0, v), s_w, (int)threadIdx.x, nullptr) + sums[blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < QI; k++) {
+        if (base + k < n) dst[base + k] = (T)pre;
+        pre += v[k];
+    }
+}
+
+// tile sums of words and flags, and the tile's first string (mirrored: QTiles::tf)
+__global__ __launch_bounds__(QT) void k_q_tile_sums(QRec o, u32 n, QTiles T) {
+    __shared__ long long s_l[QT / 64];
+    const int tid = threadIdx.x;
+    tile_sums(o.words, n, T.tw);
+    tile_sums(o.flag, n, T.tc);
+    u32 f[QI], mn = NONE32;
+    (void)q_load4(o.first_str, n, NONE32, f);
+#pragma unroll
+    for (int k = 0; k < QI; k++) mn = f[k] < mn ? f[k] : mn;
+    const long long mine = (long long)(NONE32 - mn), before = block_excl_max(mine, s_l, tid);
+    if (tid == QT - 1) T.tf[gridDim.x - 1 - blockIdx.x] = before > mine ? before : mine;  // the block's maximum
+}
+
+// words[r] := new index of the record's open root; s_len[r]; tile sums of s_len
+__global__ __launch_bounds__(QT) void k_q_tile_apply1(QRec o, u32 n, QTiles T, u32 strings_len) {
+    __shared__ unsigned long long s_w[QT / 64];
+    __shared__ u32 s_m[QT / 64];
+    const int tid = threadIdx.x;
+    const u32 base = blockIdx.x * QTILE + (u32)tid * QI;
+    u32 w[QI], fl[QI], f[QI];
+    const unsigned long long tw = q_load4(o.words, n, 0u, w);
+    (void)q_load4(o.flag, n, 0u, fl);
+    (void)q_load4(o.first_str, n, NONE32, f);
+    u32 mn = NONE32;
+#pragma unroll
+    for (int k = 0; k < QI; k++) mn = f[k] < mn ? f[k] : mn;
+    unsigned long long pw = T.tw[blockIdx.x] + block_excl_sum(tw, s_w, tid, nullptr);
+    const long long later_tiles = T.tf[gridDim.x - 1 - blockIdx.x];
+    u32 behind_tile = later_tiles < 0 ? NONE32 : NONE32 - (u32)later_tiles;  // first string of any later tile ...
+    behind_tile = behind_tile < strings_len ? behind_tile : strings_len;     // ... or the end of Strings.B
+    const u32 later = q_block_excl_suffix_min(mn, s_m, tid);
+    u32 nxt = later < behind_tile ? later : behind_tile;  // first string of any record behind this thread's four
+    u32 len[QI];
+    unsigned long long tb = 0;
+#pragma unroll
+    for (int k = QI - 1; k >= 0; k--) {
+        u32 l = 0;
+        if (f[k] != NONE32) {
+            l = nxt - f[k];
+            nxt = f[k];
+        }
+        len[k] = fl[k] ? l : 0u;
+        tb += len[k];
+    }
+#pragma unroll
+    for (int k = 0; k < QI; k++) {
+        if (base + k < n) {
+            o.words[base + k] = (u32)pw;
+            o.s_len[base + k] = len[k];
+        }
+        pw += w[k];
+    }
+    unsigned long long tot_b = 0;
+    (void)block_excl_sum(tb, s_w, tid, &tot_b);
+    if (tid == 0) T.tb[blockIdx.x] = tot_b;
+}
+
+// s_pre[r] := new Strings.B offset of the record's first string
+__global__ __launch_bounds__(QT) void k_q_tile_apply2(QRec o, u32 n, QTiles T) { tile_apply(o.s_len, o.s_pre, n, T.tb); }
+
+// ---- pass 3: one wave per record: its tape words with every stored index rebased, then its strings -------------------
+// Which words are tags is decided by the parity rule stated at the top of sj_tapewalk.h (the record's opening root is an
+// anchor), which a wave evaluates for 64 words at a time from one ballot.
+__global__ __launch_bounds__(256) void k_q_copy(QView q, QRec o, u64 *out_tape, u8 *out_strings) {
+    const u32 r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (r > q.R || !o.flag[r]) return;  // wave-uniform
+    const u32 a = rec_open(q, r), c = rec_close(q, r);
+    const u32 na = o.words[r];  // new index of the opening root
+    const u32 nwords = c - a + 1u;
+    const long long dw = (long long)na - (long long)a;
+    const u32 sb = o.first_str[r], slen = o.s_len[r], ns = o.s_pre[r];
+    const u64 ds = (u64)((long long)ns - (long long)sb);  // only used when the record has a string
+    long long p_prev = -1;  // last anchor below the group, relative to the record (none: word 0 is the first)
+    for (u32 g = 0; g < nwords; g += 64) {
+        const u32 i = g + (u32)lane;
+        const bool in = i < nwords;
+        const u64 w = in ? q.tape[a + i] : 0;
+        const u32 t = (u32)(w >> 56);
+        const u64 inmask = __ballot(in);
+        const u64 zm = ~__ballot(in && two_word_tag(w)) & inmask;  // the anchors of the group
+        const u64 zeros_below = zm & (lane ? (~0ull >> (64 - lane)) : 0ull);
+        const long long p = zeros_below ? (long long)g + (63 - __builtin_clzll(zeros_below)) : p_prev;
+        const bool raw = p >= 0 && ((((long long)i - p - 1) & 1) != 0);
+        if (in) {
+            u64 v = w;
+            if (!raw) {
+                if (i == 0) v = ((u64)'r' << 56) | (u64)(na + nwords);  // the next record's open root, or the tape length
+                else if (i == nwords - 1) v = ((u64)'r' << 56) | (u64)na;  // its own open root
+                else if (t == '{' || t == '[' || t == '}' || t == ']') v = (w & ~TW_PAYLOAD) | (u64)((long long)(w & TW_PAYLOAD) + dw);
+                else if (t == '"') v = w + ds;
+            }
+            out_tape[na + i] = v;
+        }
+        if (zm) p_prev = (long long)g + (63 - __builtin_clzll(zm));
+    }
+    for (u32 k = (u32)lane; k < slen; k += 64) out_strings[ns + k] = q.strings[sb + k];
+}
+
+// ---- the kernels of the path queries ------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_q_find_path(QView q, QPath pth, u64 *out) {
     const u32 r = blockIdx.x * 256 + threadIdx.x;
     if (r <= q.R) out[r] = record_find_path(q, pth, r);
 }
 __global__ __launch_bounds__(256) void k_q_count_path(QView q, QPath pth, int op, u64 want, unsigned long long *count) {
     const u32 r = blockIdx.x * 256 + threadIdx.x;
-    bool m = false;
-    if (r <= q.R) {
-        const u64 v = record_find_path(q, pth, r);
-        m = v < SJHIP_PATH_NOT_OBJECT && element_is(q, v, op, want);
-    }
-    const u64 b = __ballot(m);
-    if ((threadIdx.x & 63) == 0 && b) atomicAdd(count, (unsigned long long)__popcll(b));
+    count_ballot(r <= q.R && record_is(q, pth, r, op, want), count);
 }
 // ForEach(fn, onlyKeys) on the root object of record r: the members whose key is in the set, in document order, until as
 // many members as the set has keys have been delivered (parsed_object.go:190-194: a key that occurs twice counts twice).
@@ -517,7 +406,7 @@ __global__ __launch_bounds__(256) void k_q_project(QView q, QPath set, u64 *out)
     const u64 o = rec_open(q, r);
     const u64 w = q.tape[o + 1];
     if ((w >> 56) == '{') {
-        const u64 end = (w & PAYLOAD) - 1;
+        const u64 end = (w & TW_PAYLOAD) - 1;
         for (u64 i = (u64)o + 2; i < end && n < set.n;) {
             const u64 v = i + 2;
             for (u32 j = 0; j < set.n; j++)
@@ -525,7 +414,7 @@ __global__ __launch_bounds__(256) void k_q_project(QView q, QPath set, u64 *out)
                     dst[n++] = ((u64)j << 56) | v;
                     break;
                 }
-            i = skip_value(q, v);
+            i = skip_value(v, q.tape[v]);
         }
     }
     for (; n < set.n; n++) dst[n] = ~0ull;
@@ -562,7 +451,7 @@ struct QCol {
     u64 *idx;                    // [n] tape index of the element
     u64 *off;                    // [n + 1] length of the record's text -> its offset in the column (entry n: the total)
     u8 *status;                  // [n]
-    unsigned long long *tiles;   // [tiles] tile sums -> their exclusive prefix (k_q_tile_scan<false>)
+    unsigned long long *tiles;   // [tiles] tile sums -> their exclusive prefix (k_tw_scan_sums)
 };
 // status and text length of what StringBytes (cvt = false) / StringCvt (parsed_json.go:775-800) return for tape[v]
 __device__ __forceinline__ int element_text_len(const QView &q, u64 v, bool cvt, u64 *len) {
@@ -596,35 +485,8 @@ __global__ __launch_bounds__(256) void k_q_col_len(QView q, QPath pth, u32 cvt, 
     c.off[r] = len;
     c.status[r] = (u8)st;
 }
-__global__ __launch_bounds__(QT) void k_q_col_tile_sums(QCol c, u32 m) {
-    __shared__ unsigned long long s_w[QT / 64];
-    const int tid = threadIdx.x;
-    const u32 base = blockIdx.x * QTILE + (u32)tid * QI;
-    u64 len[QI];
-    q_load4(c.off, base, m, (u64)0, len);
-    unsigned long long tb = 0;
-#pragma unroll
-    for (int k = 0; k < QI; k++) tb += len[k];
-    unsigned long long tot = 0;
-    (void)q_block_excl_sum(tb, s_w, tid, &tot);
-    if (tid == 0) c.tiles[blockIdx.x] = tot;
-}
-__global__ __launch_bounds__(QT) void k_q_col_tile_apply(QCol c, u32 m) {
-    __shared__ unsigned long long s_w[QT / 64];
-    const int tid = threadIdx.x;
-    const u32 base = blockIdx.x * QTILE + (u32)tid * QI;
-    u64 len[QI];
-    q_load4(c.off, base, m, (u64)0, len);
-    unsigned long long tb = 0;
-#pragma unroll
-    for (int k = 0; k < QI; k++) tb += len[k];
-    unsigned long long pb = c.tiles[blockIdx.x] + q_block_excl_sum(tb, s_w, tid, nullptr);
-#pragma unroll
-    for (int k = 0; k < QI; k++) {
-        if (base + k < m) c.off[base + k] = pb;
-        pb += len[k];
-    }
-}
+__global__ __launch_bounds__(QT) void k_q_col_tile_sums(QCol c, u32 m) { tile_sums(c.off, m, c.tiles); }
+__global__ __launch_bounds__(QT) void k_q_col_tile_apply(QCol c, u32 m) { tile_apply(c.off, c.off, m, c.tiles); }
 // out_off[0 .. n] (the part's own offsets, from 0), out_status[n], data: the column (d_col).  One lane per record for what is
 // per record -- the offset, the status, a number's text (at most 25 bytes), a string of up to SHORT bytes -- and the whole wave
 // for each longer string of its 64 records in turn, 64 bytes at a time (strings run from 0 bytes to megabytes).
@@ -680,11 +542,8 @@ void stage2_records_view(void *ws, size_t n_tokens, const uint32_t **nl_off);
 // debug build (-DSJ_DEBUG_BOUNDS): an out-of-bounds access of a query kernel fails the call (this translation unit's record)
 static int query_bounds_check(sjhip_ctx *ctx) {
 #if defined(SJ_DEBUG_BOUNDS)
-    BoundsHit h = {};
-    if (hipMemcpyFromSymbol(&h, HIP_SYMBOL(g_bounds_hit), sizeof h) != hipSuccess) return SJHIP_OK;
-    if (h.hits) {
-        const BoundsHit zero = {};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bounds_hit), &zero, sizeof zero);
+    BoundsHit h;
+    if (bounds_take(&h) && h.hits) {
         ctx_set_error(ctx, "bounds check (query): %u out-of-bounds accesses, the first to array %u (sj_bounds.h ArrId) at element %llu of %llu",
                       h.hits, h.id, h.index, h.size);
         return SJHIP_ERR_HIP;
@@ -695,44 +554,22 @@ static int query_bounds_check(sjhip_ctx *ctx) {
     return SJHIP_OK;
 }
 
-// The contexts whose device-resident results make up the last parse of `ctx`, in document order: the context itself, or --
-// after an ND message beyond one context's reach (parse_nd_big) -- the contexts of its shards.  Iter / ForEach / FindElement of
-// the reference work on any ParsedJson (parsed_json.go:96,125,833); here the count and path queries run shard by shard in the
-// merged index space (QView) and the host adds the counts up / lays the per-record answers end to end.
-static int result_parts(sjhip_ctx *ctx, sjhip_ctx **parts, int cap) {
-    if (!ctx->big_valid) {
-        parts[0] = ctx;
-        return 1;
-    }
-    int n = 0;
-    for (int k = 0; k < nd_big_shards(ctx) && n < cap; k++)
-        if (sjhip_ctx *c = nd_big_shard(ctx, k)) parts[n++] = c;
-    return n;
+static int no_result(sjhip_ctx *ctx) {
+    ctx_set_error(ctx, "no parse result on the device (queries follow a successful sjhip_parse / sjhip_parse_device)");
+    return SJHIP_ERR_ARG;
 }
-static constexpr int MAX_PARTS = 4096;  // (parse_nd_big's own limit)
-// the same on the heap, as many as there are (no thread_local array: a library linked at start-up carries its thread_local
-// storage in the static TLS block of every thread of the process)
-static std::vector<sjhip_ctx *> result_parts(sjhip_ctx *ctx) {
-    std::vector<sjhip_ctx *> parts;
-    if (!ctx->big_valid) parts.push_back(ctx);
-    else
-        for (int k = 0; k < nd_big_shards(ctx); k++)
-            if (sjhip_ctx *c = nd_big_shard(ctx, k)) parts.push_back(c);
-    return parts;
-}
-
-// view of the result held by `part` (ctx itself, or one shard context of ctx's sharded result); errors are left in ctx
-static int make_view(sjhip_ctx *ctx, sjhip_ctx *part, const uint8_t *key, size_t klen, const uint8_t *val, size_t vlen, QView *q,
-                     uint32_t *records) {
+static int check_key_value(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const uint8_t *val, size_t vlen) {
     if (!ctx || !key || !val) return SJHIP_ERR_ARG;
     if (klen > QMAX || vlen > QMAX) {
         ctx_set_error(ctx, "query key / value longer than %d bytes", QMAX);
         return SJHIP_ERR_ARG;
     }
-    if (!part || !part->r_valid || part->tape_len == 0) {
-        ctx_set_error(ctx, "no parse result on the device (queries follow a successful sjhip_parse / sjhip_parse_device)");
-        return SJHIP_ERR_ARG;
-    }
+    return SJHIP_OK;
+}
+// view of the result held by `part` (ctx itself, or one shard context of ctx's sharded result) with the key and the value of a
+// query (checked by the caller: check_key_value); errors are left in ctx
+static int make_view(sjhip_ctx *ctx, sjhip_ctx *part, const uint8_t *key, size_t klen, const uint8_t *val, size_t vlen, QView *q) {
+    if (!part->r_valid || part->tape_len == 0) return no_result(ctx);
     const uint32_t *nl = nullptr;
     stage2_records_view(part->d_s2.p, part->p_nlay, &nl);
     // (pointers moved down by the shard's bases: see QView; all zero for an unsharded result)
@@ -751,63 +588,101 @@ static int make_view(sjhip_ctx *ctx, sjhip_ctx *part, const uint8_t *key, size_t
     memcpy(q->val, val, vlen);
     q->klen = (u32)klen;
     q->vlen = (u32)vlen;
-    *records = part->q_records + 1u;
     return SJHIP_OK;
 }
-// the unsharded result of ctx itself (filter / what needs q_valid)
-static int make_view(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const uint8_t *val, size_t vlen, QView *q, uint32_t *records) {
-    if (ctx && !ctx->q_valid) {
-        if (ctx->big_valid) ctx_set_error(ctx, "sjhip_filter_where works on the result of one context; this ND result was parsed shard by shard");
-        else ctx_set_error(ctx, "no parse result on the device (queries follow a successful sjhip_parse / sjhip_parse_device)");
-        return SJHIP_ERR_ARG;
+
+// Every part of ctx's result (sj_ctx.h result_parts): Iter / ForEach / FindElement of the reference work on any ParsedJson
+// (parsed_json.go:96,125,833); here the queries run part by part in the merged index space (QView) and the host adds the counts
+// up / lays the per-record answers end to end.  enqueue(k, part) queues the work of part k on the part's stream (its device is
+// current); when every part has been queued -- so the shards on different devices overlap -- each is waited for and collect(k, part)
+// reads what came back.  `sync`: the name of the wait in an error.
+template <typename E, typename C>
+static int walk_parts(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, const char *sync, E enqueue, C collect) {
+    for (size_t k = 0; k < parts.size(); k++) {
+        HIPCHK(hipSetDevice(parts[k]->device), "hipSetDevice");
+        const int rc = enqueue(k, parts[k]);
+        if (rc) return rc;
     }
-    return make_view(ctx, ctx, key, klen, val, vlen, q, records);
+    for (size_t k = 0; k < parts.size(); k++) {
+        HIPCHK(hipSetDevice(parts[k]->device), "hipSetDevice");
+        HIPCHK(hipStreamSynchronize(parts[k]->stream), sync);
+        collect(k, parts[k]);
+    }
+    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    return SJHIP_OK;
 }
+// The parts of a query with a key (or the keys of a path) and a value; an error if there is nothing to ask.
+static int query_parts(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const uint8_t *val, size_t vlen, std::vector<sjhip_ctx *> *parts) {
+    const int rc = check_key_value(ctx, key, klen, val, vlen);
+    if (rc) return rc;
+    *parts = result_parts(ctx);
+    return parts->empty() ? no_result(ctx) : SJHIP_OK;
+}
+// ... and the walk of a query kernel over them: enqueue(k, part, q, n) gets the part's view, its n records and kat_bytes(n) bytes
+// of the part's d_kat; the bounds check of the debug build follows the last wait.
+template <typename K, typename E, typename C>
+static int query_over_parts(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, const uint8_t *key, size_t klen, const uint8_t *val,
+                            size_t vlen, const char *sync, K kat_bytes, E enqueue, C collect) {
+    const int rc = walk_parts(ctx, parts, sync, [&](size_t k, sjhip_ctx *part) -> int {
+        QView q;
+        int rc = make_view(ctx, part, key, klen, val, vlen, &q);
+        if (rc) return rc;
+        const uint32_t n = part->q_records + 1u;
+        rc = arena_reserve(part, part->d_kat, kat_bytes(n));
+        return rc ? rc : enqueue(k, part, q, n);
+    }, collect);
+    return rc ? rc : query_bounds_check(ctx);
+}
+static const uint8_t NO_VALUE = 0;  // the value of a query that has none (vlen 0)
+
 // Runs `launch(part, q, n, d_count)` on every part of ctx's result and adds the 8-byte counts up.
 template <typename F>
 static int count_over_parts(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const uint8_t *val, size_t vlen, uint64_t *count, F launch) {
-    if (!ctx) return SJHIP_ERR_ARG;
-    static thread_local sjhip_ctx *parts[MAX_PARTS];
-    const int np = result_parts(ctx, parts, MAX_PARTS);
-    if (np == 0) return make_view(ctx, nullptr, key, klen, val, vlen, nullptr, nullptr);  // (the error text)
+    std::vector<sjhip_ctx *> parts;
+    const int rc = query_parts(ctx, key, klen, val, vlen, &parts);
+    if (rc) return rc;
     uint64_t total = 0;
-    for (int k = 0; k < np; k++) {  // every part is queued on its own stream (its own device) before any is waited for
-        sjhip_ctx *part = parts[k];
-        QView q;
-        uint32_t n = 0;
-        int rc = make_view(ctx, part, key, klen, val, vlen, &q, &n);
-        if (rc) return rc;
-        HIPCHK(hipSetDevice(part->device), "hipSetDevice");
-        rc = arena_reserve(part, part->d_kat, 64);
-        if (rc) return rc;
-        HIPCHK(hipMemsetAsync(part->d_kat.p, 0, 8, part->stream), "count memset");
-        launch(part, q, n, (unsigned long long *)part->d_kat.p);
-        HIPCHK(hipGetLastError(), "count launch");
-        HIPCHK(hipMemcpyAsync(part->h_scratch + 512, part->d_kat.p, 8, hipMemcpyDeviceToHost, part->stream), "D2H count");
-    }
-    for (int k = 0; k < np; k++) {
-        HIPCHK(hipSetDevice(parts[k]->device), "hipSetDevice");
-        HIPCHK(hipStreamSynchronize(parts[k]->stream), "count sync");
-        total += *(const unsigned long long *)(parts[k]->h_scratch + 512);
-    }
-    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
-    *count = total;
-    return query_bounds_check(ctx);
+    const int rc2 = query_over_parts(ctx, parts, key, klen, val, vlen, "count sync", [](uint32_t) { return (size_t)64; },
+        [&](size_t, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
+            HIPCHK(hipMemsetAsync(part->d_kat.p, 0, 8, part->stream), "count memset");
+            launch(part, q, n, (unsigned long long *)part->d_kat.p);
+            HIPCHK(hipGetLastError(), "count launch");
+            HIPCHK(hipMemcpyAsync(part->h_scratch + 512, part->d_kat.p, 8, hipMemcpyDeviceToHost, part->stream), "D2H count");
+            return SJHIP_OK;
+        },
+        [&](size_t, sjhip_ctx *part) { total += *(const unsigned long long *)(part->h_scratch + 512); });
+    if (rc2 == SJHIP_OK) *count = total;
+    return rc2;
 }
 
+// countWhere(key, value) is the path count with one key: the first member with the key wins, top level only, and its value must
+// be a string equal to `value` after unescaping
+static QPath one_key_path(size_t klen) {
+    QPath pth;
+    for (u32 &e : pth.end) e = (u32)klen;
+    pth.n = 1;
+    return pth;
+}
 int sjhip_count_where(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const uint8_t *value, size_t vlen, uint64_t *count) {
     if (!count) return SJHIP_ERR_ARG;
-    return count_over_parts(ctx, key, klen, value, vlen, count, [](sjhip_ctx *part, const QView &q, uint32_t n, unsigned long long *d) {
-        hipLaunchKernelGGL(k_q_count, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, d);
+    const QPath pth = one_key_path(klen);
+    return count_over_parts(ctx, key, klen, value, vlen, count, [&](sjhip_ctx *part, const QView &q, uint32_t n, unsigned long long *d) {
+        hipLaunchKernelGGL(k_q_count_path, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, pth, (int)SJHIP_OP_EQ_STRING, (u64)0, d);
     });
 }
 
 int sjhip_filter_where(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const uint8_t *value, size_t vlen,
                        uint64_t *n_records, size_t *tape_len, size_t *strings_len) {
+    if (ctx && !ctx->q_valid) {  // the unsharded result of ctx itself
+        if (ctx->big_valid) ctx_set_error(ctx, "sjhip_filter_where works on the result of one context; this ND result was parsed shard by shard");
+        else ctx_set_error(ctx, "no parse result on the device (queries follow a successful sjhip_parse / sjhip_parse_device)");
+        return SJHIP_ERR_ARG;
+    }
     QView q;
-    uint32_t n = 0;
-    int rc = make_view(ctx, key, klen, value, vlen, &q, &n);
+    int rc = check_key_value(ctx, key, klen, value, vlen);
+    if (rc == SJHIP_OK) rc = make_view(ctx, ctx, key, klen, value, vlen, &q);
     if (rc) return rc;
+    const uint32_t n = ctx->q_records + 1u;
     if (!(ctx->p_flags & SJHIP_FLAG_COPY_STRINGS)) {
         ctx_set_error(ctx, "sjhip_filter_where needs a parse with SJHIP_FLAG_COPY_STRINGS (the filtered Strings.B is self-contained)");
         return SJHIP_ERR_ARG;
@@ -816,41 +691,36 @@ int sjhip_filter_where(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const ui
     ctx->ser_valid = 0;  // the serializer's columns live in the same arenas
     ctx->ms_valid = 0;
     ctx->f_valid = 0;
-    const size_t per = ((size_t)n * 4 + 255) / 256 * 256;
     const u32 tiles = (n + QTILE - 1) / QTILE;
-    const size_t per_t = ((size_t)tiles * 8 + 255) / 256 * 256;
-    rc = arena_reserve(ctx, ctx->d_q, per * 5 + per_t * 3 + 256);
+    QRec o;
+    QTiles T;
+    auto layout = [&](Carve c) {
+        o.totals = c.take<unsigned long long>(32);
+        o.flag = c.take<u32>(n);
+        o.words = c.take<u32>(n);
+        o.first_str = c.take<u32>(n);
+        o.s_len = c.take<u32>(n);
+        o.s_pre = c.take<u32>(n);
+        T.tw = c.take<unsigned long long>(tiles);
+        T.tb = c.take<unsigned long long>(tiles);
+        T.tc = c.take<unsigned long long>(tiles);
+        T.tf = c.take<long long>(tiles);
+        return c.used;
+    };
+    rc = arena_reserve(ctx, ctx->d_q, layout(Carve()));
     if (rc) return rc;
     rc = arena_reserve(ctx, ctx->d_qtape, ctx->tape_len * 8 + 64);
     if (rc) return rc;
     rc = arena_reserve(ctx, ctx->d_qstrings, ctx->strings_len + 64);
     if (rc) return rc;
-    char *w = (char *)ctx->d_q.p;
-    QRec o;
-    o.totals = (unsigned long long *)w;
-    w += 256;
-    o.flag = (u32 *)w;
-    w += per;
-    o.words = (u32 *)w;
-    w += per;
-    o.first_str = (u32 *)w;
-    w += per;
-    o.s_len = (u32 *)w;
-    w += per;
-    o.s_pre = (u32 *)w;
-    w += per;
-    QTiles T;
-    T.tw = (unsigned long long *)w;
-    w += per_t;
-    T.tb = (unsigned long long *)w;
-    w += per_t;
-    T.tc = (u32 *)w;
-    T.tf = (u32 *)(w + per_t / 2);
-    hipLaunchKernelGGL(k_q_mark, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, q, o);
+    (void)layout(Carve(ctx->d_q.p));
+    unsigned long long *const none = nullptr;
+    hipLaunchKernelGGL(k_q_mark, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, q, one_key_path(klen), o);
     hipLaunchKernelGGL(k_q_tile_sums, dim3(tiles), dim3(QT), 0, ctx->stream, o, n, T);
-    hipLaunchKernelGGL(k_q_tile_scan<true>, dim3(1), dim3(1024), 0, ctx->stream, T, tiles, o.totals, (u32)q.strings_len);
-    hipLaunchKernelGGL(k_q_tile_apply1, dim3(tiles), dim3(QT), 0, ctx->stream, o, n, T);
-    hipLaunchKernelGGL(k_q_tile_scan<false>, dim3(1), dim3(1024), 0, ctx->stream, T, tiles, o.totals, (u32)q.strings_len);
+    hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, T.tc, T.tw, none, tiles, o.totals);
+    hipLaunchKernelGGL(k_tw_scan_last, dim3(1), dim3(1024), 0, ctx->stream, T.tf, tiles);
+    hipLaunchKernelGGL(k_q_tile_apply1, dim3(tiles), dim3(QT), 0, ctx->stream, o, n, T, (u32)q.strings_len);
+    hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, none, none, T.tb, tiles, o.totals);
     hipLaunchKernelGGL(k_q_tile_apply2, dim3(tiles), dim3(QT), 0, ctx->stream, o, n, T);
     HIPCHK(hipGetLastError(), "filter launch");
     unsigned long long *h = (unsigned long long *)(ctx->h_scratch + 512);
@@ -863,8 +733,7 @@ int sjhip_filter_where(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const ui
     if (tape_len) *tape_len = ctx->q_tape_len;
     if (strings_len) *strings_len = ctx->q_strings_len;
     if (h[0] == 0) return query_bounds_check(ctx);
-    hipLaunchKernelGGL(k_q_copy, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, q, o, (u64 *)ctx->d_qtape.p, (u8 *)ctx->d_qstrings.p,
-                       (u32)h[1]);
+    hipLaunchKernelGGL(k_q_copy, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, q, o, (u64 *)ctx->d_qtape.p, (u8 *)ctx->d_qstrings.p);
     HIPCHK(hipGetLastError(), "filter copy launch");
     return SJHIP_OK;
 }
@@ -919,47 +788,38 @@ static constexpr int MAX_OUTS = 2;
 template <typename F>
 static int outputs_over_parts(sjhip_ctx *ctx, const uint8_t *keys, size_t klen, const RecOut *outs, int n_outs, size_t cap_records,
                               size_t *records, const char *who, F launch) {
-    static const uint8_t none = 0;
-    const std::vector<sjhip_ctx *> parts = result_parts(ctx);
-    const int np = (int)parts.size();
-    if (np == 0) return make_view(ctx, nullptr, keys, klen, &none, 0, nullptr, nullptr);
+    std::vector<sjhip_ctx *> parts;
+    const int rc = query_parts(ctx, keys, klen, &NO_VALUE, 0, &parts);
+    if (rc) return rc;
     size_t total = 0;
-    for (int k = 0; k < np; k++) total += (size_t)parts[k]->q_records + 1u;
+    for (sjhip_ctx *part : parts) total += (size_t)part->q_records + 1u;
     *records = total;
     if (cap_records < total) {
         ctx_set_error(ctx, "%s: room for %zu records, the result holds %zu", who, cap_records, total);
         return SJHIP_ERR_ARG;
     }
+    auto layout = [&](Carve c, uint32_t n, u8 **d) {
+        for (int j = 0; j < n_outs; j++) d[j] = c.take<u8>((size_t)n * outs[j].width);
+        return c.used;
+    };
     size_t at = 0;
-    for (int k = 0; k < np; k++) {
-        sjhip_ctx *part = parts[k];
-        QView q;
-        uint32_t n = 0;
-        int rc = make_view(ctx, part, keys, klen, &none, 0, &q, &n);
-        if (rc) return rc;
-        HIPCHK(hipSetDevice(part->device), "hipSetDevice");
-        size_t bytes[MAX_OUTS], sum = 0;
-        for (int j = 0; j < n_outs; j++) {
-            bytes[j] = (size_t)n * outs[j].width;
-            sum += (bytes[j] + 255) / 256 * 256;
-        }
-        rc = arena_reserve(part, part->d_kat, sum + 64);
-        if (rc) return rc;
-        u8 *d[MAX_OUTS];
-        for (int j = 0, o = 0; j < n_outs; o += (int)((bytes[j] + 255) / 256 * 256), j++) d[j] = (u8 *)part->d_kat.p + o;
-        launch(part, q, n, d);
-        HIPCHK(hipGetLastError(), "query launch");
-        for (int j = 0; j < n_outs; j++)
-            HIPCHK(hipMemcpyAsync((u8 *)outs[j].dst + at * outs[j].width, d[j], bytes[j], hipMemcpyDeviceToHost, part->stream),
-                   "D2H per-record answers");
-        at += n;
-    }
-    for (int k = 0; k < np; k++) {
-        HIPCHK(hipSetDevice(parts[k]->device), "hipSetDevice");
-        HIPCHK(hipStreamSynchronize(parts[k]->stream), "query sync");
-    }
-    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
-    return query_bounds_check(ctx);
+    return query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, "query sync",
+        [&](uint32_t n) {
+            u8 *d[MAX_OUTS];
+            return layout(Carve(), n, d) + 64;
+        },
+        [&](size_t, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
+            u8 *d[MAX_OUTS];
+            (void)layout(Carve(part->d_kat.p), n, d);
+            launch(part, q, n, d);
+            HIPCHK(hipGetLastError(), "query launch");
+            for (int j = 0; j < n_outs; j++)
+                HIPCHK(hipMemcpyAsync((u8 *)outs[j].dst + at * outs[j].width, d[j], (size_t)n * outs[j].width, hipMemcpyDeviceToHost,
+                                      part->stream), "D2H per-record answers");
+            at += n;
+            return SJHIP_OK;
+        },
+        [](size_t, sjhip_ctx *) {});
 }
 // `per` 8-byte words for every record in `out`
 template <typename F>
@@ -1001,8 +861,7 @@ int sjhip_count_where_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *
     size_t klen = 0;
     const int rc = make_path(ctx, keys, key_lens, n_keys, &pth, &klen);
     if (rc) return rc;
-    static const uint8_t none = 0;
-    return count_over_parts(ctx, keys, klen, is_str && value ? (const uint8_t *)value : &none, is_str ? vlen : 0, count,
+    return count_over_parts(ctx, keys, klen, is_str && value ? (const uint8_t *)value : &NO_VALUE, is_str ? vlen : 0, count,
                             [&](sjhip_ctx *part, const QView &q, uint32_t n, unsigned long long *d) {
                                 hipLaunchKernelGGL(k_q_count_path, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, pth, op, want, d);
                             });
@@ -1047,12 +906,15 @@ int sjhip_extract_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_
 
 // The column of every part lives in the part's d_col: offsets [n + 1] (from 0 in every part), status [n], the bytes; the work
 // arrays of the three steps (QCol) in its d_kat, which only lives for one call.
-static size_t col_align(size_t b) { return (b + 255) / 256 * 256; }
-static void col_layout(sjhip_ctx *part, size_t n, u64 **off, u8 **status, u8 **data) {
-    u8 *w = (u8 *)part->d_col.p;
-    *off = (u64 *)w;
-    *status = w + col_align((n + 1) * 8);
-    *data = *status + col_align(n);
+struct ColOut {
+    u64 *off;
+    u8 *status, *data;
+};
+static size_t col_layout(Carve c, size_t n, size_t bytes, ColOut *o) {
+    o->off = c.take<u64>(n + 1);
+    o->status = c.take<u8>(n);
+    o->data = c.take<u8>(bytes);
+    return c.used;
 }
 
 int sjhip_extract_path_strings(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, uint32_t flags,
@@ -1063,74 +925,65 @@ int sjhip_extract_path_strings(sjhip_ctx *ctx, const uint8_t *keys, const uint32
     int rc = make_path(ctx, keys, key_lens, n_keys, &pth, &klen);
     if (rc) return rc;
     ctx->col_valid = 0;  // (the last column is replaced, whatever happens below)
-    static const uint8_t none = 0;
-    const std::vector<sjhip_ctx *> parts = result_parts(ctx);
-    const int np = (int)parts.size();
-    if (np == 0) return make_view(ctx, nullptr, keys, klen, &none, 0, nullptr, nullptr);
-    std::vector<QView> views((size_t)np);  // (a QView carries 2 KiB of keys: on the heap, one per part)
-    std::vector<QCol> cols((size_t)np);
+    std::vector<sjhip_ctx *> parts;
+    rc = query_parts(ctx, keys, klen, &NO_VALUE, 0, &parts);
+    if (rc) return rc;
+    std::vector<QCol> cols(parts.size());
+    auto tiles_of = [](uint32_t n) { return (n + 1u + QTILE - 1) / QTILE; };
+    auto work = [&](Carve c, uint32_t n, QCol *col, unsigned long long **totals) {
+        *totals = c.take<unsigned long long>(32);
+        col->idx = c.take<u64>(n);
+        col->off = c.take<u64>((size_t)n + 1);
+        col->status = c.take<u8>(n);
+        col->tiles = c.take<unsigned long long>(tiles_of(n));
+        return c.used;
+    };
     // lengths and their scan on every part, each on its own stream; then the totals
-    for (int k = 0; k < np; k++) {
-        sjhip_ctx *part = parts[k];
-        QView &q = views[k];
-        uint32_t n = 0;
-        rc = make_view(ctx, part, keys, klen, &none, 0, &q, &n);
-        if (rc) return rc;
-        HIPCHK(hipSetDevice(part->device), "hipSetDevice");
-        const u32 m = n + 1u, tiles = (m + QTILE - 1) / QTILE;
-        rc = arena_reserve(part, part->d_kat, 256 + col_align((size_t)n * 8) + col_align((size_t)m * 8) + col_align(n) +
-                                                  col_align((size_t)tiles * 8) + 64);
-        if (rc) return rc;
-        u8 *w = (u8 *)part->d_kat.p;
-        unsigned long long *totals = (unsigned long long *)w;
-        QCol &c = cols[k];
-        c.idx = (u64 *)(w + 256);
-        c.off = (u64 *)((u8 *)c.idx + col_align((size_t)n * 8));
-        c.status = (u8 *)c.off + col_align((size_t)m * 8);
-        c.tiles = (unsigned long long *)(c.status + col_align(n));
-        QTiles T = {};
-        T.tb = c.tiles;
-        hipLaunchKernelGGL(k_q_col_len, dim3((m + 255) / 256), dim3(256), 0, part->stream, q, pth, flags & SJHIP_COL_CVT, c);
-        hipLaunchKernelGGL(k_q_col_tile_sums, dim3(tiles), dim3(QT), 0, part->stream, c, m);
-        hipLaunchKernelGGL(k_q_tile_scan<false>, dim3(1), dim3(1024), 0, part->stream, T, tiles, totals, 0u);
-        hipLaunchKernelGGL(k_q_col_tile_apply, dim3(tiles), dim3(QT), 0, part->stream, c, m);
-        HIPCHK(hipGetLastError(), "column launch");
-        HIPCHK(hipMemcpyAsync(part->h_scratch + 512, totals + 2, 8, hipMemcpyDeviceToHost, part->stream), "D2H column bytes");
-    }
     size_t total_records = 0, total_bytes = 0;
-    for (int k = 0; k < np; k++) {
-        sjhip_ctx *part = parts[k];
-        HIPCHK(hipSetDevice(part->device), "hipSetDevice");
-        HIPCHK(hipStreamSynchronize(part->stream), "column sync");
-        part->col_records = (size_t)views[k].R + 1u;
-        part->col_bytes = (size_t)*(const unsigned long long *)(part->h_scratch + 512);
-        total_records += part->col_records;
-        total_bytes += part->col_bytes;
-    }
-    // the gather on every part, into the part's d_col
-    for (int k = 0; k < np; k++) {
-        sjhip_ctx *part = parts[k];
-        const size_t n = part->col_records;
-        HIPCHK(hipSetDevice(part->device), "hipSetDevice");
-        rc = arena_reserve(part, part->d_col, col_align((n + 1) * 8) + col_align(n) + part->col_bytes + 64);
-        if (rc) return rc;
-        u64 *off;
-        u8 *status, *data;
-        col_layout(part, n, &off, &status, &data);
-        hipLaunchKernelGGL(k_q_col_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, part->stream, views[k], cols[k], off, status,
-                           SJ_ARR(data, part->col_bytes, A_COL));
-        HIPCHK(hipGetLastError(), "column gather launch");
-    }
-    for (int k = 0; k < np; k++) {  // (the work arrays in d_kat are free for the next query once this returns)
-        HIPCHK(hipSetDevice(parts[k]->device), "hipSetDevice");
-        HIPCHK(hipStreamSynchronize(parts[k]->stream), "column gather sync");
-    }
-    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, "column sync",
+        [&](uint32_t n) {
+            QCol c;
+            unsigned long long *totals;
+            return work(Carve(), n, &c, &totals) + 64;
+        },
+        [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
+            QCol &c = cols[k];
+            unsigned long long *totals, *const none = nullptr;
+            (void)work(Carve(part->d_kat.p), n, &c, &totals);
+            const u32 m = n + 1u, tiles = tiles_of(n);
+            hipLaunchKernelGGL(k_q_col_len, dim3((m + 255) / 256), dim3(256), 0, part->stream, q, pth, flags & SJHIP_COL_CVT, c);
+            hipLaunchKernelGGL(k_q_col_tile_sums, dim3(tiles), dim3(QT), 0, part->stream, c, m);
+            hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, part->stream, none, none, c.tiles, tiles, totals);
+            hipLaunchKernelGGL(k_q_col_tile_apply, dim3(tiles), dim3(QT), 0, part->stream, c, m);
+            HIPCHK(hipGetLastError(), "column launch");
+            HIPCHK(hipMemcpyAsync(part->h_scratch + 512, totals + 2, 8, hipMemcpyDeviceToHost, part->stream), "D2H column bytes");
+            return SJHIP_OK;
+        },
+        [&](size_t, sjhip_ctx *part) {
+            part->col_records = (size_t)part->q_records + 1u;
+            part->col_bytes = (size_t)*(const unsigned long long *)(part->h_scratch + 512);
+            total_records += part->col_records;
+            total_bytes += part->col_bytes;
+        });
+    if (rc) return rc;
+    // the gather on every part, into the part's d_col (the work arrays stay where they are: nothing more of d_kat is asked for)
+    rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, "column gather sync", [](uint32_t) { return (size_t)0; },
+        [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
+            ColOut o;
+            const int rc = arena_reserve(part, part->d_col, col_layout(Carve(), n, part->col_bytes, &o) + 64);
+            if (rc) return rc;
+            (void)col_layout(Carve(part->d_col.p), n, part->col_bytes, &o);
+            hipLaunchKernelGGL(k_q_col_gather, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, cols[k], o.off, o.status,
+                               SJ_ARR(o.data, part->col_bytes, A_COL));
+            HIPCHK(hipGetLastError(), "column gather launch");
+            return SJHIP_OK;
+        },
+        [](size_t, sjhip_ctx *) {});  // (the work arrays in d_kat are free for the next query once this returns)
+    if (rc) return rc;
     *records = total_records;
     *bytes = total_bytes;
-    rc = query_bounds_check(ctx);
-    if (rc == SJHIP_OK) ctx->col_valid = 1;
-    return rc;
+    ctx->col_valid = 1;
+    return SJHIP_OK;
 }
 
 int sjhip_fetch_path_strings(sjhip_ctx *ctx, uint64_t *offsets, uint8_t *data, uint8_t *status) {
@@ -1140,36 +993,30 @@ int sjhip_fetch_path_strings(sjhip_ctx *ctx, uint64_t *offsets, uint8_t *data, u
         return SJHIP_ERR_ARG;
     }
     const std::vector<sjhip_ctx *> parts = result_parts(ctx);
-    const int np = (int)parts.size();
     size_t total_bytes = 0;
-    for (int k = 0; k < np; k++) total_bytes += parts[k]->col_bytes;
+    for (sjhip_ctx *part : parts) total_bytes += part->col_bytes;
     if (!offsets || !status || (!data && total_bytes)) return SJHIP_ERR_ARG;
-    size_t rec_at = 0, byte_at = 0;
-    for (int k = 0; k < np; k++) {  // every part's offsets but its last (the next part's first, rebased below) + status + bytes
-        sjhip_ctx *part = parts[k];
-        const size_t n = part->col_records;
-        u64 *off;
-        u8 *st, *bytes;
-        col_layout(part, n, &off, &st, &bytes);
-        HIPCHK(hipSetDevice(part->device), "hipSetDevice");
-        HIPCHK(hipMemcpyAsync(offsets + rec_at, off, n * 8, hipMemcpyDeviceToHost, part->stream), "D2H column offsets");
-        HIPCHK(hipMemcpyAsync(status + rec_at, st, n, hipMemcpyDeviceToHost, part->stream), "D2H column status");
-        if (part->col_bytes)
-            HIPCHK(hipMemcpyAsync(data + byte_at, bytes, part->col_bytes, hipMemcpyDeviceToHost, part->stream), "D2H column bytes");
-        rec_at += n;
-        byte_at += part->col_bytes;
+    std::vector<size_t> rec_at(parts.size() + 1, 0), byte_at(parts.size() + 1, 0);  // where every part's records and bytes start
+    for (size_t k = 0; k < parts.size(); k++) {
+        rec_at[k + 1] = rec_at[k] + parts[k]->col_records;
+        byte_at[k + 1] = byte_at[k] + parts[k]->col_bytes;
     }
-    rec_at = byte_at = 0;
-    for (int k = 0; k < np; k++) {
-        sjhip_ctx *part = parts[k];
-        HIPCHK(hipSetDevice(part->device), "hipSetDevice");
-        HIPCHK(hipStreamSynchronize(part->stream), "column fetch sync");
-        if (byte_at)  // the offsets of a later shard: from the end of the shards in front of it
-            for (size_t i = rec_at; i < rec_at + part->col_records; i++) offsets[i] += byte_at;
-        rec_at += part->col_records;
-        byte_at += part->col_bytes;
-    }
-    offsets[rec_at] = byte_at;
-    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    const int rc = walk_parts(ctx, parts, "column fetch sync",
+        [&](size_t k, sjhip_ctx *part) -> int {  // every part's offsets but its last (the next part's first, rebased below) + status + bytes
+            const size_t n = part->col_records;
+            ColOut o;
+            (void)col_layout(Carve(part->d_col.p), n, part->col_bytes, &o);
+            HIPCHK(hipMemcpyAsync(offsets + rec_at[k], o.off, n * 8, hipMemcpyDeviceToHost, part->stream), "D2H column offsets");
+            HIPCHK(hipMemcpyAsync(status + rec_at[k], o.status, n, hipMemcpyDeviceToHost, part->stream), "D2H column status");
+            if (part->col_bytes)
+                HIPCHK(hipMemcpyAsync(data + byte_at[k], o.data, part->col_bytes, hipMemcpyDeviceToHost, part->stream), "D2H column bytes");
+            return SJHIP_OK;
+        },
+        [&](size_t k, sjhip_ctx *part) {
+            if (byte_at[k])  // the offsets of a later shard: from the end of the shards in front of it
+                for (size_t i = rec_at[k]; i < rec_at[k] + part->col_records; i++) offsets[i] += byte_at[k];
+        });
+    if (rc) return rc;
+    offsets[rec_at[parts.size()]] = byte_at[parts.size()];
     return SJHIP_OK;
 }

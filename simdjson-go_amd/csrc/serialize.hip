@@ -33,12 +33,6 @@
 
 using namespace sj;
 
-#define HIPCHK(call, what)                                        \
-    do {                                                          \
-        hipError_t e_ = (call);                                   \
-        if (e_ != hipSuccess) return ctx_hip_fail(ctx, e_, what); \
-    } while (0)
-
 namespace {
 
 static constexpr u64 PAYLOAD = TW_PAYLOAD;
@@ -93,19 +87,6 @@ __device__ __forceinline__ bool ser_equal(const u8 *a, const u8 *b, u64 len) {
     for (; i < len; i++)
         if (a[i] != b[i]) return false;
     return true;
-}
-
-// one block: exclusive prefix sums of the per-tile counts + totals (a: entries, b: value bytes, c: kept string bytes)
-__global__ __launch_bounds__(1024) void k_ser_scan_cnt(unsigned long long *cnt_a, unsigned long long *cnt_b,
-                                                       unsigned long long *cnt_c, u32 tiles, unsigned long long *totals) {
-    __shared__ long long s_w[16];
-#pragma unroll 1
-    for (int k = 0; k < 3; k++) {  // (one copy of the scan: three inlined ones spilled 84 bytes per lane under the 1024-thread bound)
-        unsigned long long *const cnt = k == 0 ? cnt_a : (k == 1 ? cnt_b : cnt_c);
-        const long long t = cnt ? block1024_scan_array<false>((long long *)cnt, tiles, s_w, (int)threadIdx.x) : 0;
-        if (threadIdx.x == 0) totals[k] = (unsigned long long)t;
-        __syncthreads();
-    }
 }
 
 // The passes over the tape.  MODE 0: (de-duplication) every string entry enters its tape index into its table slot with
@@ -331,7 +312,7 @@ int sjhip_serialize_ex(sjhip_ctx *ctx, uint32_t flags, size_t *tags_len, size_t 
         }
         if (dedup) hipLaunchKernelGGL(k_ser_tile<0>, dim3(p.tiles), dim3(ST_THREADS), 0, ctx->stream, p);
         hipLaunchKernelGGL(k_ser_tile<1>, dim3(p.tiles), dim3(ST_THREADS), 0, ctx->stream, p);
-        hipLaunchKernelGGL(k_ser_scan_cnt, dim3(1), dim3(1024), 0, ctx->stream, p.cnt_t, p.cnt_v, dedup ? p.cnt_s : nullptr, p.tiles, p.totals);
+        hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, p.cnt_t, p.cnt_v, dedup ? p.cnt_s : nullptr, p.tiles, p.totals);  // entries, value bytes, kept string bytes
         if (dedup) hipLaunchKernelGGL(k_ser_tile<2>, dim3(p.tiles), dim3(ST_THREADS), 0, ctx->stream, p);
         hipLaunchKernelGGL(k_ser_tile<3>, dim3(p.tiles), dim3(ST_THREADS), 0, ctx->stream, p);
         HIPCHK(hipGetLastError(), "serialize launch");
@@ -341,10 +322,8 @@ int sjhip_serialize_ex(sjhip_ctx *ctx, uint32_t flags, size_t *tags_len, size_t 
     }
 #if defined(SJ_DEBUG_BOUNDS)
     {   // debug build: a string entry outside Strings.B fails the call (this translation unit's record, sj_bounds.h)
-        BoundsHit hit = {};
-        if (hipMemcpyFromSymbol(&hit, HIP_SYMBOL(g_bounds_hit), sizeof hit) == hipSuccess && hit.hits) {
-            const BoundsHit zero = {};
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bounds_hit), &zero, sizeof zero);
+        BoundsHit hit;
+        if (bounds_take(&hit) && hit.hits) {
             ctx_set_error(ctx, "bounds check (Serialize): %u out-of-bounds strings, the first at byte %llu of %llu", hit.hits, hit.index, hit.size);
             return SJHIP_ERR_HIP;
         }
@@ -637,7 +616,7 @@ int sjhip_deserialize(sjhip_ctx *ctx, const uint8_t *stream, size_t len, size_t 
     if (ms) HIPCHK(hipMemcpyAsync(ctx->d_msg.p, stream + off_m, ms, hipMemcpyHostToDevice, ctx->stream), "H2D message");
     if (p.tiles) {
         hipLaunchKernelGGL(k_des_tile<0>, dim3(p.tiles), dim3(DS_THREADS), 0, ctx->stream, p);
-        hipLaunchKernelGGL(k_ser_scan_cnt, dim3(1), dim3(1024), 0, ctx->stream, p.cnt_w, p.cnt_v, (unsigned long long *)nullptr, p.tiles, p.totals);
+        hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, p.cnt_w, p.cnt_v, (unsigned long long *)nullptr, p.tiles, p.totals);
         hipLaunchKernelGGL(k_des_tile<1>, dim3(p.tiles), dim3(DS_THREADS), 0, ctx->stream, p);
         hipLaunchKernelGGL(k_des_tile<2>, dim3(p.tiles), dim3(DS_THREADS), 0, ctx->stream, p);
         HIPCHK(hipGetLastError(), "deserialize launch");

@@ -38,7 +38,7 @@ struct BoundsHit {
     unsigned long long index, size;
 };
 #if defined(__HIPCC__)
-static __device__ BoundsHit g_bounds_hit;                 // one per translation unit; stage2.hip reads and clears its own
+static __device__ BoundsHit g_bounds_hit;                 // one per translation unit; each reads and clears its own (bounds_take)
 static __device__ unsigned long long g_bounds_sink[8];    // target of accesses to an array without a single element
 __device__ __forceinline__ void bounds_report(uint32_t id, unsigned long long index, unsigned long long size) {
     if (atomicAdd(&g_bounds_hit.hits, 1u) == 0u) {
@@ -46,6 +46,16 @@ __device__ __forceinline__ void bounds_report(uint32_t id, unsigned long long in
         g_bounds_hit.index = index;
         g_bounds_hit.size = size;
     }
+}
+// host: this translation unit's record, read and cleared (false, and an empty record: it could not be read)
+static inline bool bounds_take(BoundsHit *h) {
+    *h = BoundsHit{};
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_bounds_hit), sizeof *h) != hipSuccess) return false;
+    if (h->hits) {
+        const BoundsHit zero = {};
+        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bounds_hit), &zero, sizeof zero);
+    }
+    return true;
 }
 #else
 inline void bounds_report(uint32_t, unsigned long long, unsigned long long) {}

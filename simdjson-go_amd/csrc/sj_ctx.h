@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "sj_device.h"
 
 namespace sj {
@@ -89,6 +91,25 @@ inline hipError_t pinned_alloc(void **p, size_t bytes) { return hipHostMalloc(p,
 void ctx_set_error(sjhip_ctx *ctx, const char *fmt, ...);
 int ctx_hip_fail(sjhip_ctx *ctx, hipError_t e, const char *what);
 int arena_reserve(sjhip_ctx *ctx, DevBuf &b, size_t bytes);
+// a failed HIP call ends the calling function with the error left in `ctx` (the name in scope at the call)
+#define HIPCHK(call, what)                                              \
+    do {                                                                \
+        hipError_t e_ = (call);                                         \
+        if (e_ != hipSuccess) return ::sj::ctx_hip_fail(ctx, e_, what); \
+    } while (0)
+// The work areas of an arena: 256-byte aligned slices off a base pointer, one after another; `used` is what to reserve.  A layout
+// written once as a function of a Carve is run twice: without a base for the size, then on the reserved arena.
+struct Carve {
+    char *base;
+    size_t used = 0;
+    explicit Carve(void *b = nullptr) : base((char *)b) {}
+    template <typename T>
+    T *take(size_t count) {
+        T *p = (T *)(base + used);
+        used += (count * sizeof(T) + 255) / 256 * 256;
+        return p;
+    }
+};
 int parse_packed(sjhip_ctx *ctx, size_t len, uint32_t flags, uint8_t last_byte, int have_last, size_t *tape_len,
                  size_t *strings_len);  // parse_api.hip
 int parse_nd_big(sjhip_ctx *ctx, const uint8_t *msg, size_t len, uint32_t flags, bool d_resident, size_t shard_bytes,
@@ -99,6 +120,10 @@ size_t nd_big_device_bytes(const sjhip_ctx *ctx);  // arenas of the shard contex
 // the shards of the merged result of parse_nd_big, in document order (empty shards have no context to look at: null)
 int nd_big_shards(const sjhip_ctx *ctx);
 sjhip_ctx *nd_big_shard(const sjhip_ctx *ctx, int k);
+// The contexts whose device-resident results make up the last parse of `ctx`, in document order: the context itself, or -- after
+// parse_nd_big -- the contexts of its shards that hold something.  On the heap, as many as there are (no thread_local array: a
+// library linked at start-up carries its thread_local storage in the static TLS block of every thread of the process).
+std::vector<sjhip_ctx *> result_parts(sjhip_ctx *ctx);
 int stage1_enqueue(sjhip_ctx *ctx, const void *d_msg, size_t len, int ndjson, void *d_pos, size_t pos_cap, void *str_aux,
                    uint8_t *d_kind, void *zero2, size_t zero2_bytes, unsigned long long *host_rec = nullptr);
 // host_rec: the launch's record in pinned host memory (S1_HOST_WORDS words; null: the context's own at h_scratch)

@@ -1,5 +1,5 @@
-// sj_tapewalk.h -- device helpers shared by the kernels that walk a finished tape (serialize.hip, marshal.hip):
-// 2048-word tiles, block-wide scans, and the tag / raw-word classification.
+// sj_tapewalk.h -- device helpers shared by the kernels that walk a finished tape (serialize.hip, marshal.hip, query.hip):
+// 2048-word tiles, block-wide scans, the one-block scans over per-tile values, and the tag / raw-word classification.
 //
 // A tape entry is one word (brackets, roots, atoms) or two (strings: tag + length, numbers: tag + value).  The second
 // word is raw 64-bit data whose top byte can look like any tag, so "is this word a tag?" is not a local question.
@@ -167,6 +167,20 @@ __global__ __launch_bounds__(TW_THREADS) void k_tw_last(const u64 *tape, u64 n, 
 __global__ __launch_bounds__(1024) void k_tw_scan_last(long long *tile_last, u32 tiles) {
     __shared__ long long s_w[16];
     block1024_scan_array<true>(tile_last, tiles, s_w, (int)threadIdx.x);
+}
+
+// one block: a0, a1, a2 [tiles] := their exclusive prefix sums, totals[k] := the sum of array k.  A null array is skipped and
+// its total left as it is; null totals: nobody wants them.
+__global__ __launch_bounds__(1024) void k_tw_scan_sums(unsigned long long *a0, unsigned long long *a1, unsigned long long *a2,
+                                                       u32 tiles, unsigned long long *totals) {
+    __shared__ long long s_w[16];
+#pragma unroll 1
+    for (int k = 0; k < 3; k++) {  // (one copy of the scan: three inlined ones spilled 84 bytes per lane under the 1024-thread bound)
+        unsigned long long *const a = k == 0 ? a0 : (k == 1 ? a1 : a2);
+        if (!a) continue;
+        const long long t = block1024_scan_array<false>((long long *)a, tiles, s_w, (int)threadIdx.x);
+        if (threadIdx.x == 0 && totals) totals[k] = (unsigned long long)t;
+    }
 }
 
 }  // namespace

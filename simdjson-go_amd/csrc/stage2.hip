@@ -2188,12 +2188,8 @@ int stage2_debug_bounds(unsigned *hits, unsigned *id, unsigned long long *index,
     *hits = *id = 0;
     *index = *size = 0;
 #if defined(SJ_DEBUG_BOUNDS)
-    BoundsHit h = {};
-    if (hipMemcpyFromSymbol(&h, HIP_SYMBOL(g_bounds_hit), sizeof h) != hipSuccess) return 1;
-    if (h.hits) {
-        const BoundsHit zero = {};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bounds_hit), &zero, sizeof zero);
-    }
+    BoundsHit h;
+    (void)bounds_take(&h);
     *hits = h.hits;
     *id = h.id;
     *index = h.index;
