@@ -225,6 +225,46 @@ int sjhip_extract_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_
 int sjhip_extract_path_strings(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, uint32_t flags,
                                size_t *records, size_t *bytes);
 int sjhip_fetch_path_strings(sjhip_ctx *ctx, uint64_t *offsets, uint8_t *data, uint8_t *status);
+/* List columns: the ARRAY at `path` of every record, converted on the device -- the reference's Iter.FindElement(path...),
+ * Iter.Array() and then Array.AsFloat / AsInteger / AsUint64 / AsString / AsStringCvt (parsed_array.go:145-344); paths, records
+ * and limits are those of sjhip_find_path.
+ *   sjhip_extract_path_list          kind = SJHIP_COL_FLOAT / INT / UINT (SJHIP_COL_BOOL: SJHIP_ERR_ARG, the reference has no such
+ *                          conversion); *records, *elems = the records and the elements of all their arrays together.
+ *   sjhip_fetch_path_list            Arrow's large_list<T>: list_offsets[records + 1] (list_offsets[0] = 0; record r owns the elements
+ *                          list_offsets[r] .. list_offsets[r + 1]), values[elems] (8 bytes each: double / int64_t / uint64_t),
+ *                          status[records].
+ *   sjhip_extract_path_list_strings  Array.AsString, or with SJHIP_COL_CVT Array.AsStringCvt; *bytes = the bytes of all the texts.
+ *   sjhip_fetch_path_list_strings    Arrow's large_list<large_string>: list_offsets as above, str_offsets[elems + 1] (element e owns
+ *                          data[str_offsets[e] .. str_offsets[e + 1]]), data[bytes], status[records].
+ * A record whose status is not SJHIP_COL_OK has an empty slot, and so has an OK record whose array is empty: the status byte
+ * tells the two apart.  The statuses are the SJHIP_COL_* values above:
+ *   NOT_FOUND / NOT_OBJECT  from FindElement, as for the scalar columns;
+ *   NULL                    the element at the path is null (the scalar columns' convention: a dataframe maps it to a null list);
+ *   TYPE                    any other element at the path that is not an array (Iter.Array: "next item is not array");
+ *   inside the array the reference returns at the first element it cannot convert: the record's status is that of the FIRST
+ *   failing element in document order.
+ *     AsFloat      l / u / d elements: float64(int64), float64(uint64), the double as it is; any other element -- null, strings,
+ *                  true / false, nested containers -- is TYPE.
+ *     AsInteger    a u element above MaxInt64, a d element > 2^63 or < -2^63: RANGE; a d element of exactly 2^63 is MinInt64 (the
+ *                  amd64 result, as for the scalar column).
+ *     AsUint64     an l or d element < 0: RANGE (-0.0 passes and gives 0); a d element > 2^63: RANGE; exactly 2^63 gives 1 << 63.
+ *     AsString     every element must be a string (its unescaped bytes), else TYPE.
+ *     AsStringCvt  every element converted like the scalar column's SJHIP_COL_CVT (numbers in decimal / as appendFloat writes them,
+ *                  true / false / null); TYPE for a nested object or array.
+ *   What differs from the scalar columns: a null ELEMENT is TYPE, not NULL (parsed_array.go has no case for it), for AsString too;
+ *   AsUint64 rejects floats in (2^63, 2^64], which Iter.Uint converts (parsed_array.go:253 compares with math.MaxInt64, Iter.Uint with
+ *   math.MaxUint64), and so never meets the 2^64 edge; there is no bool conversion.
+ * The list column lives in a device arena of its own: it and the string column of sjhip_extract_path_strings survive each other,
+ * the other queries, MarshalJSON and the serializer; it lasts until the next parse or the next list extraction of the context
+ * (sjhip_ctx_device_bytes counts it, sjhip_ctx_trim frees it).  A fetch without a list column, or of the other kind (the numeric
+ * fetch after a string extraction or the reverse), is SJHIP_ERR_ARG and sjhip_last_error says so.  On a sharded ND result every
+ * shard builds its part and the fetch joins them. */
+int sjhip_extract_path_list(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int kind, size_t *records,
+                            size_t *elems);
+int sjhip_fetch_path_list(sjhip_ctx *ctx, uint64_t *list_offsets, void *values, uint8_t *status);
+int sjhip_extract_path_list_strings(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, uint32_t flags,
+                                    size_t *records, size_t *elems, size_t *bytes);
+int sjhip_fetch_path_list_strings(sjhip_ctx *ctx, uint64_t *list_offsets, uint64_t *str_offsets, uint8_t *data, uint8_t *status);
 
 /* ---- Serializer.Serialize on the device (parsed_serialize.go:200-431, format version 3) -----------------------------
  * Splits the device-resident tape of the last parse (SJHIP_FLAG_COPY_STRINGS) into the reference's three columns --

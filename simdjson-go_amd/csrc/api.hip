@@ -84,7 +84,7 @@ sjhip_ctx *sjhip_ctx_create(int device) {
 #define SJ_CTX_ARENAS(ctx)                                                                                                   \
     {&(ctx)->d_msg, &(ctx)->d_pos, &(ctx)->d_ws, &(ctx)->d_kat, &(ctx)->d_tape, &(ctx)->d_strings, &(ctx)->d_s2, &(ctx)->d_s2z, \
      &(ctx)->d_aux, &(ctx)->d_scol, &(ctx)->d_stab, &(ctx)->d_q, &(ctx)->d_qtape, &(ctx)->d_qstrings,       \
-     &(ctx)->d_keyflag, &(ctx)->d_col}
+     &(ctx)->d_keyflag, &(ctx)->d_col, &(ctx)->d_list}
 
 size_t sjhip_ctx_device_bytes(const sjhip_ctx *ctx) {
     if (!ctx) return 0;
@@ -193,7 +193,7 @@ static int stage1_verdict(const Stage1State &st, size_t len, uint8_t last_byte) 
 // is left (they return SJHIP_ERR_ARG until the next parse).
 static void invalidate_result(sjhip_ctx *ctx) {
     ctx->q_valid = ctx->r_valid = ctx->ser_valid = ctx->ms_valid = 0;
-    ctx->col_valid = 0;
+    ctx->col_valid = ctx->list_valid = 0;
     ctx->pending = 0;
     ctx->q_tape_len = ctx->q_strings_len = 0;
     ctx->f_valid = 0;

@@ -298,7 +298,7 @@ int sj::parse_nd_big(sjhip_ctx *ctx, const uint8_t *msg, size_t len, uint32_t fl
         }
     }
     ctx->big_valid = 0;
-    ctx->col_valid = 0;
+    ctx->col_valid = ctx->list_valid = 0;
     const int rc = multi_parse(ctx->big, msg, len, flags, d_resident, tape_len, strings_len, msg_off, msg_len);
     if (rc == SJHIP_OK) {
         ctx->big_valid = 1;

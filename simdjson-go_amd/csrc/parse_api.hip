@@ -83,7 +83,7 @@ static int parse_begin(sjhip_ctx *ctx, const void *d_msg, size_t len, uint32_t f
                        size_t *tape_len, size_t *strings_len) {
     ctx->tape_len = ctx->strings_len = 0;
     ctx->big_valid = 0;
-    ctx->col_valid = 0;
+    ctx->col_valid = ctx->list_valid = 0;
     ctx->pending = 0;
     ctx->pack_valid = 0;
     ctx->q_valid = 0;
@@ -389,7 +389,7 @@ int sjhip_parse_device(sjhip_ctx *ctx, const void *d_msg, size_t len, uint32_t f
     if (nd_too_big(len, flags)) {  // shards on this device, each parsing its window of the message in place
         ctx->tape_len = ctx->strings_len = 0;
         ctx->q_valid = ctx->r_valid = ctx->ser_valid = ctx->ms_valid = ctx->f_valid = ctx->pack_valid = ctx->pending = 0;
-        ctx->col_valid = 0;
+        ctx->col_valid = ctx->list_valid = 0;
         HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
         HIPCHK(hipStreamSynchronize(ctx->stream), "stream sync");  // (the shards run on streams of their own)
         return parse_nd_big(ctx, (const uint8_t *)d_msg, len, flags, true, nd_shard_bytes(), tape_len, strings_len, nullptr, nullptr);
@@ -408,11 +408,11 @@ int sjhip_parse(sjhip_ctx *ctx, const uint8_t *msg, size_t len, uint32_t flags, 
     if (strings_len) *strings_len = 0;
     ctx->tape_len = ctx->strings_len = 0;
     ctx->big_valid = 0;
-    ctx->col_valid = 0;
+    ctx->col_valid = ctx->list_valid = 0;
     if (mlen == 0) return SJHIP_ERR_STAGE1;
     if (nd_too_big(mlen, flags)) {  // shards of the host message, H2D straight from the caller's buffer
         ctx->q_valid = ctx->r_valid = ctx->ser_valid = ctx->ms_valid = ctx->f_valid = ctx->pack_valid = ctx->pending = 0;
-        ctx->col_valid = 0;
+        ctx->col_valid = ctx->list_valid = 0;
         return parse_nd_big(ctx, msg, len, flags, false, nd_shard_bytes(), tape_len, strings_len, nullptr, nullptr);
     }
     if (mlen > SINGLE_LIMIT) {  // before anything is copied to the device

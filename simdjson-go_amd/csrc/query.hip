@@ -532,6 +532,297 @@ __global__ __launch_bounds__(256) void k_q_col_gather(QView q, QCol c, u64 *out_
     }
 }
 
+// ---- list columns: the ARRAY at a path of every record, converted (sjhip_extract_path_list / sjhip_extract_path_list_strings) ----
+// Arrow's large_list<T> / large_list<large_string>: u64 list offsets over the records, the elements end to end, and for strings
+// u64 offsets over the elements with the bytes end to end.  The conversions are those of parsed_array.go:145-344 (Array.AsFloat /
+// AsInteger / AsUint64 / AsString / AsStringCvt), which stop at the first element they cannot convert.  Three steps over the
+// n = R + 1 records, like the string column:
+//   measure   FindElement, Iter.Array, then the whole conversion check of the array: its status, its element count and (strings)
+//             the bytes of its texts; entry n is 0
+//   scan      exclusive prefixes of the n + 1 counts (and byte totals) in place: sums -> one-block scan (k_tw_scan_sums) -> apply
+//   gather    the list offsets and statuses, the values (or the string offsets and bytes) of every OK record
+// Values and float text are produced again in the gather rather than stashed (the trade of the string column, for its reason).
+// An array runs from 0 to millions of elements, so one lane per record is not enough.  For the numeric kinds and AsString every
+// acceptable element is two tape words: element k of the array opened at v is at v + 1 + 2k and there are (close - v - 1) / 2 of
+// them, PROVIDED every element in front of it is acceptable.  A short array is handled by its record's lane; every longer array of
+// the wave's 64 records by the whole wave in turn, 64 elements per step.  The first failing element is the lowest k of a step --
+// one ballot -- whose tag word is not acceptable or whose value is out of range; every position below it is known to be a
+// two-word element, the words behind it are never trusted: the walk stops at the first failing step.
+// AsStringCvt mixes one-word (t f n) and two-word elements, so positions are not strided: these arrays are walked by their
+// record's lane, whatever their length (a long array costs one lane's serial walk: DESIGN.md section 5b); strings longer than
+// COL_SHORT bytes are copied by the whole wave for every variant.
+static constexpr int LIST_STR = 4, LIST_CVT = 5;  // Array.AsString / AsStringCvt, behind SJHIP_COL_FLOAT / INT / UINT
+static constexpr u64 LIST_SHORT = 16;             // elements a record's lane converts alone
+struct QList {
+    u64 *idx;                              // [n] tape index of the array's '['
+    u64 *cnt;                              // [n + 1] elements of the record -> its list offset (entry n: the total)
+    u64 *bytes;                            // [n + 1] strings: bytes of the record's texts -> their offset (entry n: the total); else null
+    u8 *status;                            // [n]
+    unsigned long long *tiles_c, *tiles_b; // [tiles] tile sums of cnt / bytes -> their exclusive prefixes
+};
+// Status of the two-word element at p for Array.AsFloat / AsInteger / AsUint64 (kind = SJHIP_COL_*) or AsString (LIST_STR), with
+// its value bits / its byte length in *out.  Unlike Iter.Float / Int / Uint (element_to): null is a type error like any other tag
+// (parsed_array.go:175,226,277), and AsUint64 rejects a float above math.MaxInt64 -- 2^63 as a float64 -- (:253) where Iter.Uint
+// compares with 2^64; uint64(2^63) is 1 << 63.
+__device__ __forceinline__ int list_elem(const QView &q, u64 p, int kind, u64 *out) {
+    const u32 t = (u32)(q.tape[p] >> 56);
+    *out = 0;
+    if (kind == LIST_STR) {
+        if (t != '"') return SJHIP_COL_TYPE;
+        *out = q.tape[p + 1];
+        return SJHIP_COL_OK;
+    }
+    if (t != 'l' && t != 'u' && t != 'd') return SJHIP_COL_TYPE;
+    if (kind == SJHIP_COL_UINT && t == 'd') {
+        const double d = __longlong_as_double((long long)q.tape[p + 1]);
+        if (d > 9223372036854775808.0 || d < 0.0) return SJHIP_COL_RANGE;  // (-0.0 passes and converts to 0)
+        *out = d >= 9223372036854775808.0 ? 0x8000000000000000ull : (u64)d;
+        return SJHIP_COL_OK;
+    }
+    return element_to(q, p, kind, out);
+}
+// FindElement + Iter.Array on record r: SJHIP_COL_OK with the index of the '[' and of its ']', or the record's status
+__device__ __forceinline__ int record_array(const QView &q, const QPath &pth, u32 r, u64 *v, u64 *close) {
+    *v = record_find_path(q, pth, r);
+    *close = 0;
+    if (*v >= SJHIP_PATH_NOT_OBJECT) return path_status(*v);
+    const u64 w = q.tape[*v];
+    const u32 t = (u32)(w >> 56);
+    if (t == 'n') return SJHIP_COL_NULL;
+    if (t != '[') return SJHIP_COL_TYPE;  // "next item is not array"
+    *close = (w & TW_PAYLOAD) - 1;
+    return SJHIP_COL_OK;
+}
+__device__ __forceinline__ u64 wave_sum(u64 x) {
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) x += (u64)__shfl_xor((long long)x, s, 64);
+    return x;
+}
+// the strided conversion check of the array (v, close) by one lane (first = 0, step = 1) ...
+__device__ __forceinline__ int lane_list_measure(const QView &q, u64 v, u64 close, int kind, u64 *cnt, u64 *bytes) {
+    u64 sum = 0;
+    for (u64 p = v + 1; p < close; p += 2) {
+        u64 x;
+        const int st = list_elem(q, p, kind, &x);
+        if (st) return st;
+        sum += x;
+    }
+    *cnt = (close - v - 1) / 2;
+    *bytes = kind == LIST_STR ? sum : 0;
+    return SJHIP_COL_OK;
+}
+// ... and by the whole wave, 64 elements per step (all arguments and the results wave-uniform)
+__device__ __forceinline__ int wave_list_measure(const QView &q, u64 v, u64 close, int kind, int lane, u64 *cnt, u64 *bytes) {
+    u64 sum = 0;
+    for (u64 g = v + 1; g < close; g += 128) {
+        const u64 p = g + 2 * (u64)lane;
+        u64 x = 0;
+        const int st = p < close ? list_elem(q, p, kind, &x) : SJHIP_COL_OK;
+        const u64 bad = __ballot(st != SJHIP_COL_OK);
+        if (bad) return __shfl(st, __ffsll((unsigned long long)bad) - 1, 64);  // the first failing element of the array
+        sum += x;
+    }
+    *cnt = (close - v - 1) / 2;
+    *bytes = kind == LIST_STR ? wave_sum(sum) : 0;
+    return SJHIP_COL_OK;
+}
+__device__ __forceinline__ void list_measure_store(const QView &q, const QList &c, u32 r, u64 v, int st, u64 cnt, u64 bytes) {
+    if (r <= q.R) {
+        c.idx[r] = v;
+        c.cnt[r] = st == SJHIP_COL_OK ? cnt : 0;
+        if (c.bytes) c.bytes[r] = st == SJHIP_COL_OK ? bytes : 0;
+        c.status[r] = (u8)st;
+    } else if (r == q.R + 1) {
+        c.cnt[r] = 0;
+        if (c.bytes) c.bytes[r] = 0;
+    }
+}
+__global__ __launch_bounds__(256) void k_q_list_measure(QView q, QPath pth, int kind, QList c) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    u64 v = 0, close = 0, cnt = 0, bytes = 0;
+    int st = SJHIP_COL_NOT_FOUND;
+    bool wide = false;
+    if (r <= q.R) {
+        st = record_array(q, pth, r, &v, &close);
+        if (st == SJHIP_COL_OK) {
+            wide = close - v - 1 > 2 * LIST_SHORT;
+            if (!wide) st = lane_list_measure(q, v, close, kind, &cnt, &bytes);
+        }
+    }
+    for (u64 todo = __ballot(wide); todo; todo &= todo - 1) {  // the wave's long arrays, one after another
+        const int j = __ffsll((unsigned long long)todo) - 1;
+        const u64 vj = (u64)__shfl((long long)v, j, 64), cj = (u64)__shfl((long long)close, j, 64);
+        u64 n_j = 0, b_j = 0;
+        const int st_j = wave_list_measure(q, vj, cj, kind, lane, &n_j, &b_j);
+        if (lane == j) {
+            st = st_j;
+            cnt = n_j;
+            bytes = b_j;
+        }
+    }
+    list_measure_store(q, c, r, v, st, cnt, bytes);
+}
+// AsStringCvt: every element converted by StringCvt (element_text_len), one lane per record
+__global__ __launch_bounds__(256) void k_q_list_measure_cvt(QView q, QPath pth, QList c) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    u64 v = 0, close = 0, cnt = 0, bytes = 0;
+    int st = SJHIP_COL_NOT_FOUND;
+    if (r <= q.R) {
+        st = record_array(q, pth, r, &v, &close);
+        for (u64 p = v + 1; st == SJHIP_COL_OK && p < close;) {
+            u64 len;
+            st = element_text_len(q, p, true, &len);  // (TYPE for { and [: nothing is skipped over)
+            bytes += len;
+            cnt++;
+            p += two_word_tag(q.tape[p]) ? 2 : 1;
+        }
+    }
+    list_measure_store(q, c, r, v, st, cnt, bytes);
+}
+__global__ __launch_bounds__(QT) void k_q_list_tile_sums(QList c, u32 m) {
+    tile_sums(c.cnt, m, c.tiles_c);
+    if (c.bytes) tile_sums(c.bytes, m, c.tiles_b);
+}
+__global__ __launch_bounds__(QT) void k_q_list_tile_apply(QList c, u32 m) {
+    tile_apply(c.cnt, c.cnt, m, c.tiles_c);
+    if (c.bytes) tile_apply(c.bytes, c.bytes, m, c.tiles_b);
+}
+// out_off[0 .. n] (the part's own list offsets, from 0), out_status[n], values: the elements.  A short array by its record's lane;
+// a long one by the whole wave: lane l converts element g + l and stores it next to its neighbours' (consecutive 8-byte stores).
+__global__ __launch_bounds__(256) void k_q_list_gather_num(QView q, QList c, int kind, u64 *out_off, u8 *out_status, Arr<u64> values) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    u64 o = 0, cnt = 0, v = 0;
+    bool wide = false;
+    if (r <= q.R) {
+        o = c.cnt[r];
+        cnt = c.cnt[r + 1] - o;
+        out_off[r] = o;
+        out_status[r] = c.status[r];
+        if (r == q.R) out_off[r + 1] = o + cnt;
+        v = c.idx[r];
+        wide = cnt > LIST_SHORT;  // (only an OK record has elements)
+        if (!wide)
+            for (u64 k = 0; k < cnt; k++) {
+                u64 x;
+                (void)list_elem(q, v + 1 + 2 * k, kind, &x);
+                values[o + k] = x;
+            }
+    }
+    for (u64 todo = __ballot(wide); todo; todo &= todo - 1) {
+        const int j = __ffsll((unsigned long long)todo) - 1;
+        const u64 oj = (u64)__shfl((long long)o, j, 64), nj = (u64)__shfl((long long)cnt, j, 64), vj = (u64)__shfl((long long)v, j, 64);
+        for (u64 k = (u64)lane; k < nj; k += 64) {
+            u64 x;
+            (void)list_elem(q, vj + 1 + 2 * k, kind, &x);
+            values[oj + k] = x;
+        }
+    }
+}
+// Strings: soff[e] = where the text of element e starts in `data` (entry elems: the total).  Every lane walks the elements of
+// its record's array (AsStringCvt: every array; AsString: the short ones), writes their offsets, the converted texts and the
+// strings of up to COL_SHORT bytes; when it meets a longer string it waits, and the wave copies the waiting lanes' strings one
+// after another, 64 bytes at a time, before the walks go on.  AsString's long arrays follow, each by the whole wave: 64 lengths
+// per step, their prefix by a shuffle scan (consecutive 8-byte stores of the offsets), short strings by their lanes, long ones
+// by the wave.
+template <bool CVT>
+__device__ __forceinline__ void list_gather_strings(const QView &q, const QList &c, u64 *out_off, u8 *out_status, Arr<u64> soff,
+                                                    Arr<u8> data) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    u64 o = 0, cnt = 0, v = 0, at = 0;
+    bool wide = false;
+    if (r <= q.R) {
+        o = c.cnt[r];
+        cnt = c.cnt[r + 1] - o;
+        at = c.bytes[r];
+        out_off[r] = o;
+        out_status[r] = c.status[r];
+        if (r == q.R) {
+            out_off[r + 1] = o + cnt;
+            soff[o + cnt] = c.bytes[r + 1];
+        }
+        v = c.idx[r];
+        wide = !CVT && cnt > LIST_SHORT;
+    }
+    const u64 at0 = at;
+    u64 p = v + 1, k = wide ? cnt : 0;
+    for (;;) {
+        u64 sw = 0, sl = 0, so = 0;
+        bool pend = false;
+        while (k < cnt && !pend) {
+            const u64 w = q.tape[p];
+            const u32 t = (u32)(w >> 56);
+            u64 len = 0;
+            soff[o + k] = at;
+            if (t == '"') {
+                len = q.tape[p + 1];
+                if (len > COL_SHORT) {
+                    pend = true;
+                    sw = w;
+                    sl = len;
+                    so = at;
+                } else if (len) copy_bytes(arr_at(data, at, len), str_bytes(q, w, len), len, 0, 1);
+            } else if (CVT) {  // (AsString's elements are strings)
+                (void)element_text_len(q, p, true, &len);
+                u8 *dst = arr_at(data, at, len);
+                if (t == 'l') (void)format_int(q.tape[p + 1], dst);
+                else if (t == 'u') (void)format_uint(q.tape[p + 1], dst);
+                else if (t == 'd') (void)format_float(q.tape[p + 1], dst);
+                else {
+                    const char *lit = t == 't' ? "true" : (t == 'f' ? "false" : "null");
+                    for (u64 i = 0; i < len; i++) dst[i] = (u8)lit[i];
+                }
+            }
+            at += len;
+            k++;
+            p += two_word_tag(w) ? 2 : 1;
+        }
+        u64 todo = __ballot(pend);
+        if (!todo) break;
+        for (; todo; todo &= todo - 1) {
+            const int j = __ffsll((unsigned long long)todo) - 1;
+            const u64 oj = (u64)__shfl((long long)so, j, 64), lj = (u64)__shfl((long long)sl, j, 64), wj = (u64)__shfl((long long)sw, j, 64);
+            copy_bytes(arr_at(data, oj, lj), str_bytes(q, wj, lj), lj, (u64)lane, 64);
+        }
+    }
+    if (CVT) return;
+    for (u64 todo = __ballot(wide); todo; todo &= todo - 1) {  // AsString: the wave's long arrays, one after another
+        const int j = __ffsll((unsigned long long)todo) - 1;
+        const u64 oj = (u64)__shfl((long long)o, j, 64), nj = (u64)__shfl((long long)cnt, j, 64), vj = (u64)__shfl((long long)v, j, 64);
+        u64 base = (u64)__shfl((long long)at0, j, 64);
+        for (u64 g = 0; g < nj; g += 64) {
+            const u64 e = g + (u64)lane;
+            const bool in = e < nj;
+            const u64 w = in ? q.tape[vj + 1 + 2 * e] : 0, len = in ? q.tape[vj + 2 + 2 * e] : 0;
+            u64 incl = len;
+#pragma unroll
+            for (int s = 1; s < 64; s <<= 1) {
+                const u64 x = (u64)__shfl_up((long long)incl, s, 64);
+                if (lane >= s) incl += x;
+            }
+            const u64 mine = base + incl - len;
+            if (in) {
+                soff[oj + e] = mine;
+                if (len && len <= COL_SHORT) copy_bytes(arr_at(data, mine, len), str_bytes(q, w, len), len, 0, 1);
+            }
+            for (u64 big = __ballot(len > COL_SHORT); big; big &= big - 1) {
+                const int i = __ffsll((unsigned long long)big) - 1;
+                const u64 oi = (u64)__shfl((long long)mine, i, 64), li = (u64)__shfl((long long)len, i, 64), wi = (u64)__shfl((long long)w, i, 64);
+                copy_bytes(arr_at(data, oi, li), str_bytes(q, wi, li), li, (u64)lane, 64);
+            }
+            base += (u64)__shfl((long long)incl, 63, 64);
+        }
+    }
+}
+__global__ __launch_bounds__(256) void k_q_list_gather_str(QView q, QList c, u64 *out_off, u8 *out_status, Arr<u64> soff, Arr<u8> data) {
+    list_gather_strings<false>(q, c, out_off, out_status, soff, data);
+}
+__global__ __launch_bounds__(256) void k_q_list_gather_cvt(QView q, QList c, u64 *out_off, u8 *out_status, Arr<u64> soff, Arr<u8> data) {
+    list_gather_strings<true>(q, c, out_off, out_status, soff, data);
+}
+
 }  // namespace
 
 namespace sj {
@@ -1019,4 +1310,174 @@ int sjhip_fetch_path_strings(sjhip_ctx *ctx, uint64_t *offsets, uint8_t *data, u
     if (rc) return rc;
     offsets[rec_at[parts.size()]] = byte_at[parts.size()];
     return SJHIP_OK;
+}
+
+// ---- list columns --------------------------------------------------------------------------------------------------------------
+// The list column of every part lives in the part's d_list, an arena of its own (d_col keeps the string column): list offsets
+// [n + 1] (from 0 in every part), status [n], then the values [elems], or the string offsets [elems + 1] (from 0) and the bytes;
+// the work arrays of the three steps (QList) in its d_kat, which only lives for one call.
+struct ListOut {
+    u64 *off;
+    u8 *status;
+    u64 *values, *soff;
+    u8 *data;
+};
+static size_t list_layout(Carve c, size_t n, size_t elems, size_t bytes, bool strings, ListOut *o) {
+    o->off = c.take<u64>(n + 1);
+    o->status = c.take<u8>(n);
+    o->values = strings ? nullptr : c.take<u64>(elems);
+    o->soff = strings ? c.take<u64>(elems + 1) : nullptr;
+    o->data = strings ? c.take<u8>(bytes) : nullptr;
+    return c.used;
+}
+static const char NO_LIST[] = "no list column of this kind on the device (sjhip_fetch_path_list follows sjhip_extract_path_list, "
+                              "sjhip_fetch_path_list_strings follows sjhip_extract_path_list_strings, with no parse in between)";
+
+// mode: SJHIP_COL_FLOAT / INT / UINT, LIST_STR or LIST_CVT
+static int list_extract(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int mode, size_t *records,
+                        size_t *elems, size_t *bytes) {
+    QPath pth;
+    size_t klen = 0;
+    int rc = make_path(ctx, keys, key_lens, n_keys, &pth, &klen);
+    if (rc) return rc;
+    ctx->list_valid = 0;  // (the last list column is replaced, whatever happens below)
+    const bool strings = mode >= LIST_STR;
+    std::vector<sjhip_ctx *> parts;
+    rc = query_parts(ctx, keys, klen, &NO_VALUE, 0, &parts);
+    if (rc) return rc;
+    std::vector<QList> lists(parts.size());
+    auto tiles_of = [](uint32_t n) { return (n + 1u + QTILE - 1) / QTILE; };
+    auto work = [&](Carve c, uint32_t n, QList *l, unsigned long long **totals) {
+        *totals = c.take<unsigned long long>(32);
+        l->idx = c.take<u64>(n);
+        l->cnt = c.take<u64>((size_t)n + 1);
+        l->bytes = strings ? c.take<u64>((size_t)n + 1) : nullptr;
+        l->status = c.take<u8>(n);
+        l->tiles_c = c.take<unsigned long long>(tiles_of(n));
+        l->tiles_b = strings ? c.take<unsigned long long>(tiles_of(n)) : nullptr;
+        return c.used;
+    };
+    // the conversion check, the counts and their scans on every part, each on its own stream; then the totals
+    size_t total_records = 0, total_elems = 0, total_bytes = 0;
+    rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, "list column sync",
+        [&](uint32_t n) {
+            QList l;
+            unsigned long long *totals;
+            return work(Carve(), n, &l, &totals) + 64;
+        },
+        [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
+            QList &l = lists[k];
+            unsigned long long *totals, *const none = nullptr;
+            (void)work(Carve(part->d_kat.p), n, &l, &totals);
+            const u32 m = n + 1u, tiles = tiles_of(n);
+            HIPCHK(hipMemsetAsync(totals, 0, 16, part->stream), "list totals memset");
+            if (mode == LIST_CVT) hipLaunchKernelGGL(k_q_list_measure_cvt, dim3((m + 255) / 256), dim3(256), 0, part->stream, q, pth, l);
+            else hipLaunchKernelGGL(k_q_list_measure, dim3((m + 255) / 256), dim3(256), 0, part->stream, q, pth, mode, l);
+            hipLaunchKernelGGL(k_q_list_tile_sums, dim3(tiles), dim3(QT), 0, part->stream, l, m);
+            hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, part->stream, l.tiles_c, l.tiles_b, none, tiles, totals);
+            hipLaunchKernelGGL(k_q_list_tile_apply, dim3(tiles), dim3(QT), 0, part->stream, l, m);
+            HIPCHK(hipGetLastError(), "list column launch");
+            HIPCHK(hipMemcpyAsync(part->h_scratch + 512, totals, 16, hipMemcpyDeviceToHost, part->stream), "D2H list totals");
+            return SJHIP_OK;
+        },
+        [&](size_t, sjhip_ctx *part) {
+            const unsigned long long *h = (const unsigned long long *)(part->h_scratch + 512);
+            part->list_records = (size_t)part->q_records + 1u;
+            part->list_elems = (size_t)h[0];
+            part->list_bytes = strings ? (size_t)h[1] : 0;
+            total_records += part->list_records;
+            total_elems += part->list_elems;
+            total_bytes += part->list_bytes;
+        });
+    if (rc) return rc;
+    // the gather on every part, into the part's d_list (the work arrays stay where they are: nothing more of d_kat is asked for)
+    rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, "list gather sync", [](uint32_t) { return (size_t)0; },
+        [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
+            ListOut o;
+            const int rc = arena_reserve(part, part->d_list, list_layout(Carve(), n, part->list_elems, part->list_bytes, strings, &o) + 64);
+            if (rc) return rc;
+            (void)list_layout(Carve(part->d_list.p), n, part->list_elems, part->list_bytes, strings, &o);
+            const dim3 grid((n + 255) / 256), block(256);
+            if (!strings)
+                hipLaunchKernelGGL(k_q_list_gather_num, grid, block, 0, part->stream, q, lists[k], mode, o.off, o.status,
+                                   SJ_ARR(o.values, part->list_elems, A_LIST_VAL));
+            else if (mode == LIST_STR)
+                hipLaunchKernelGGL(k_q_list_gather_str, grid, block, 0, part->stream, q, lists[k], o.off, o.status,
+                                   SJ_ARR(o.soff, part->list_elems + 1, A_LIST_SOFF), SJ_ARR(o.data, part->list_bytes, A_LIST_DATA));
+            else
+                hipLaunchKernelGGL(k_q_list_gather_cvt, grid, block, 0, part->stream, q, lists[k], o.off, o.status,
+                                   SJ_ARR(o.soff, part->list_elems + 1, A_LIST_SOFF), SJ_ARR(o.data, part->list_bytes, A_LIST_DATA));
+            HIPCHK(hipGetLastError(), "list gather launch");
+            return SJHIP_OK;
+        },
+        [](size_t, sjhip_ctx *) {});
+    if (rc) return rc;
+    *records = total_records;
+    *elems = total_elems;
+    if (bytes) *bytes = total_bytes;
+    ctx->list_valid = strings ? 2 : 1;
+    return SJHIP_OK;
+}
+
+int sjhip_extract_path_list(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int kind, size_t *records,
+                            size_t *elems) {
+    if (!records || !elems) return SJHIP_ERR_ARG;
+    if (kind < SJHIP_COL_FLOAT || kind > SJHIP_COL_UINT) {
+        if (ctx) ctx_set_error(ctx, "sjhip_extract_path_list: kind %d (the reference's arrays convert to float, integer and unsigned integer)", kind);
+        return SJHIP_ERR_ARG;
+    }
+    return list_extract(ctx, keys, key_lens, n_keys, kind, records, elems, nullptr);
+}
+int sjhip_extract_path_list_strings(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, uint32_t flags,
+                                    size_t *records, size_t *elems, size_t *bytes) {
+    if (!records || !elems || !bytes || (flags & ~SJHIP_COL_CVT)) return SJHIP_ERR_ARG;
+    return list_extract(ctx, keys, key_lens, n_keys, (flags & SJHIP_COL_CVT) ? LIST_CVT : LIST_STR, records, elems, bytes);
+}
+
+// inner: the values (numbers) or the string offsets (strings) of the elements
+static int list_fetch(sjhip_ctx *ctx, bool strings, uint64_t *list_offsets, uint64_t *inner, uint8_t *data, uint8_t *status) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (ctx->list_valid != (strings ? 2 : 1)) {  // none was built, a parse (or sjhip_ctx_trim) came after it, or it is of the other kind
+        ctx_set_error(ctx, "%s", NO_LIST);
+        return SJHIP_ERR_ARG;
+    }
+    const std::vector<sjhip_ctx *> parts = result_parts(ctx);
+    const size_t P = parts.size();
+    std::vector<size_t> rec_at(P + 1, 0), elem_at(P + 1, 0), byte_at(P + 1, 0);  // where every part's records, elements and bytes start
+    for (size_t k = 0; k < P; k++) {
+        rec_at[k + 1] = rec_at[k] + parts[k]->list_records;
+        elem_at[k + 1] = elem_at[k] + parts[k]->list_elems;
+        byte_at[k + 1] = byte_at[k] + parts[k]->list_bytes;
+    }
+    if (!list_offsets || !status || (!inner && (strings || elem_at[P])) || (strings && !data && byte_at[P])) return SJHIP_ERR_ARG;
+    const int rc = walk_parts(ctx, parts, "list fetch sync",
+        [&](size_t k, sjhip_ctx *part) -> int {  // every part's offsets but their last (the next part's first, rebased below)
+            const size_t n = part->list_records, ne = part->list_elems;
+            ListOut o;
+            (void)list_layout(Carve(part->d_list.p), n, ne, part->list_bytes, strings, &o);
+            HIPCHK(hipMemcpyAsync(list_offsets + rec_at[k], o.off, n * 8, hipMemcpyDeviceToHost, part->stream), "D2H list offsets");
+            HIPCHK(hipMemcpyAsync(status + rec_at[k], o.status, n, hipMemcpyDeviceToHost, part->stream), "D2H list status");
+            if (ne)
+                HIPCHK(hipMemcpyAsync(inner + elem_at[k], strings ? o.soff : o.values, ne * 8, hipMemcpyDeviceToHost, part->stream),
+                       "D2H list elements");
+            if (part->list_bytes)
+                HIPCHK(hipMemcpyAsync(data + byte_at[k], o.data, part->list_bytes, hipMemcpyDeviceToHost, part->stream), "D2H list bytes");
+            return SJHIP_OK;
+        },
+        [&](size_t k, sjhip_ctx *part) {  // the offsets of a later shard: from the end of the shards in front of it
+            if (elem_at[k])
+                for (size_t i = rec_at[k]; i < rec_at[k] + part->list_records; i++) list_offsets[i] += elem_at[k];
+            if (strings && byte_at[k])
+                for (size_t i = elem_at[k]; i < elem_at[k] + part->list_elems; i++) inner[i] += byte_at[k];
+        });
+    if (rc) return rc;
+    list_offsets[rec_at[P]] = elem_at[P];
+    if (strings) inner[elem_at[P]] = byte_at[P];
+    return query_bounds_check(ctx);  // (debug build: the gather kernel has finished here)
+}
+int sjhip_fetch_path_list(sjhip_ctx *ctx, uint64_t *list_offsets, void *values, uint8_t *status) {
+    return list_fetch(ctx, false, list_offsets, (uint64_t *)values, nullptr, status);
+}
+int sjhip_fetch_path_list_strings(sjhip_ctx *ctx, uint64_t *list_offsets, uint64_t *str_offsets, uint8_t *data, uint8_t *status) {
+    return list_fetch(ctx, true, list_offsets, str_offsets, data, status);
 }

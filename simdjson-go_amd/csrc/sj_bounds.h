@@ -28,7 +28,8 @@ enum ArrId : uint32_t {
     A_UNIT_COPY, A_S1_POS, A_S1_KIND, A_S1_QM, A_S1_Q, A_S1_ST, A_S1_UNIT_H, A_S1_UNIT_SLOW,  // stage 1's outputs (stage1.hip)
     A_S1_REC, A_S1_UNIT_CNT, A_S1_UNIT_COPY, A_S1_UNIT_STR, A_UNIT_STR, A_SOFF,
     A_S1_TILE_UNIT, A_TILE_UNIT, A_UNIT_TQ,
-    A_COL  // the bytes of a string column (query.hip)
+    A_COL,  // the bytes of a string column (query.hip)
+    A_LIST_VAL, A_LIST_SOFF, A_LIST_DATA  // a list column (query.hip): its values / its string offsets / its string bytes
 };
 
 #if defined(SJ_DEBUG_BOUNDS)

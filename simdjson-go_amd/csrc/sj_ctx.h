@@ -39,6 +39,7 @@ struct sjhip_ctx {
     sj::DevBuf d_scol, d_stab;         // serializer with de-duplication: the string column, the hash table
     sj::DevBuf d_q, d_qtape, d_qstrings;  // queries over the last result (query.hip): work arrays, filtered tape / Strings.B
     sj::DevBuf d_col;                  // the string column of the last sjhip_extract_path_strings (query.hip): offsets, status, bytes
+    sj::DevBuf d_list;                 // the list column of the last sjhip_extract_path_list[_strings] (query.hip), apart from d_col
     unsigned ws_clean_gen = 0;         // d_ws.gen of the allocation that has been zeroed for stage 1 (0: none; stage1_enqueue)
     sj::S1Ws s1ws;                     // ... and its launch count (sj_device.h: a launch cleans up for the next one)
     unsigned s1_par = 0;               // control slot of the last stage-1 launch (Stage1State::c[]: stage 2 reads has_starter there)
@@ -53,6 +54,8 @@ struct sjhip_ctx {
     int f_valid = 0;              // a filtered result is resident (sjhip_fetch_filtered)
     int col_valid = 0;            // a string column of the resident result is in d_col (of this context, or of its shards)
     size_t col_records = 0, col_bytes = 0;  // ... its records and bytes (of this context's part of the result)
+    int list_valid = 0;           // a list column of the resident result is in d_list (of this context, or of its shards): 1 numbers, 2 strings
+    size_t list_records = 0, list_elems = 0, list_bytes = 0;  // ... its records, elements and string bytes (this context's part)
     int ser_valid = 0;            // last sjhip_serialize (serialize.hip): column sizes, framed stream size
     size_t ser_tags = 0, ser_vals = 0, ser_rest = 0, ser_stream = 0, ser_slen = 0;
     int ser_dedup = 0;

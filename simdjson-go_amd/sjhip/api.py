@@ -328,6 +328,49 @@ class Context:
         self._check(_lib.lib().sjhip_fetch_path_strings(self._h, offsets.ctypes.data, data.ctypes.data, status.ctypes.data))
         return offsets, data[:nbytes].tobytes(), status[:records]
 
+    # ---- list columns (include/sjhip.h: sjhip_extract_path_list / _list_strings and their fetches) -----------------------------
+    def extract_path_list(self, path, kind, fetch=True):
+        """Iter.FindElement(path...), Iter.Array, then Array.AsFloat / AsInteger / AsUint64 (kind = COL_FLOAT / COL_INT / COL_UINT)
+        on every record, on the device.  -> (list_offsets: uint64 array of records + 1, values: float64 / int64 / uint64 array,
+        status: uint8 array) -- Arrow's large_list layout; with fetch=False the column stays on the device and
+        (records, elems) is returned"""
+        blob, lens, n = self._keys(path)
+        nr, ne = C.c_size_t(0), C.c_size_t(0)
+        self._check(_lib.lib().sjhip_extract_path_list(self._h, blob, lens, n, int(kind), C.byref(nr), C.byref(ne)))
+        if not fetch:
+            return nr.value, ne.value
+        return self.fetch_path_list(nr.value, ne.value, kind)
+
+    def fetch_path_list(self, records, elems, kind):
+        """the column of the last extract_path_list (its records, elements and kind) -> (list_offsets, values, status)"""
+        offsets = np.empty(records + 1, dtype=np.uint64)
+        values = np.empty(max(elems, 1), dtype=self._COL_DTYPES[int(kind)])
+        status = np.empty(max(records, 1), dtype=np.uint8)
+        self._check(_lib.lib().sjhip_fetch_path_list(self._h, offsets.ctypes.data, values.ctypes.data, status.ctypes.data))
+        return offsets, values[:elems], status[:records]
+
+    def extract_path_list_strings(self, path, cvt=False, fetch=True):
+        """... then Array.AsString (or AsStringCvt with cvt=True).  -> (list_offsets: uint64 array of records + 1, str_offsets:
+        uint64 array of elems + 1, data: bytes, status: uint8 array) -- Arrow's large_list<large_string>; with fetch=False
+        the column stays on the device and (records, elems, bytes) is returned"""
+        blob, lens, n = self._keys(path)
+        nr, ne, nb = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        self._check(_lib.lib().sjhip_extract_path_list_strings(self._h, blob, lens, n, self.COL_CVT if cvt else 0, C.byref(nr),
+                                                               C.byref(ne), C.byref(nb)))
+        if not fetch:
+            return nr.value, ne.value, nb.value
+        return self.fetch_path_list_strings(nr.value, ne.value, nb.value)
+
+    def fetch_path_list_strings(self, records, elems, nbytes):
+        """the column of the last extract_path_list_strings -> (list_offsets, str_offsets, data, status)"""
+        offsets = np.empty(records + 1, dtype=np.uint64)
+        soff = np.empty(elems + 1, dtype=np.uint64)
+        data = np.empty(max(nbytes, 1), dtype=np.uint8)
+        status = np.empty(max(records, 1), dtype=np.uint8)
+        self._check(_lib.lib().sjhip_fetch_path_list_strings(self._h, offsets.ctypes.data, soff.ctypes.data, data.ctypes.data,
+                                                             status.ctypes.data))
+        return offsets, soff, data[:nbytes].tobytes(), status[:records]
+
     def serialize(self, fetch=True, dedup=False):
         """Serializer.Serialize (format v3, CompressNone) of the device-resident result of the last parse.
         -> the framed stream as a uint8 array (what the reference's Deserialize reads), or its sizes with fetch=False.
