@@ -74,7 +74,9 @@ int sjhip_ctx_trim(sjhip_ctx *ctx);
  * msg is a HOST buffer.  The library applies bytes.TrimSpace (parse_json_amd64.go:55) and reports
  * the trimmed window so that the caller can alias pj.Message = msg[msg_off : msg_off+msg_len].
  * On SJHIP_OK the tape/strings stay on the device until sjhip_fetch copies them into
- * caller-owned memory of at least tape_len*8 / strings_len bytes. */
+ * caller-owned memory of at least tape_len*8 / strings_len bytes.
+ * A parse call on a context (this one, sjhip_parse_device, sjhip_parse_batch[_device]), successful or not, drops the
+ * previous result and everything derived from it. */
 int sjhip_parse(sjhip_ctx *ctx, const uint8_t *msg, size_t len, uint32_t flags, size_t *tape_len,
                 size_t *strings_len, size_t *msg_off, size_t *msg_len);
 int sjhip_fetch(sjhip_ctx *ctx, uint64_t *tape_dst, uint8_t *strings_dst);

@@ -35,6 +35,20 @@ void sj::ctx_set_error(sjhip_ctx *ctx, const char *fmt, ...) {
     va_end(ap);
 }
 
+int sj::no_result(sjhip_ctx *ctx, const char *follows) {
+    ctx_set_error(ctx, "no parse result on the device (%s a successful sjhip_parse / sjhip_parse_device)", follows);
+    return SJHIP_ERR_ARG;
+}
+int sj::no_whole_result(sjhip_ctx *ctx, const char *call, const char *follows) {
+    if (!ctx->res.sharded()) return no_result(ctx, follows);
+    ctx_set_error(ctx, "%s works on the result of one context; this ND result was parsed shard by shard", call);
+    return SJHIP_ERR_ARG;
+}
+int sj::published(sjhip_ctx *ctx, bool ok) {
+    if (ok) return SJHIP_OK;
+    ctx_set_error(ctx, "internal: a product was published without a parse result on the device");
+    return SJHIP_ERR_HIP;
+}
 int sj::ctx_hip_fail(sjhip_ctx *ctx, hipError_t e, const char *what) {
     ctx_set_error(ctx, "%s: %s", what, hipGetErrorString(e));
     return SJHIP_ERR_HIP;
@@ -94,14 +108,11 @@ size_t sjhip_ctx_device_bytes(const sjhip_ctx *ctx) {
     return total + sj::nd_big_device_bytes(ctx);
 }
 
-static void invalidate_result(sjhip_ctx *ctx);
-
 int sjhip_ctx_trim(sjhip_ctx *ctx) {
     if (!ctx) return SJHIP_ERR_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
         return ctx_hip_fail(ctx, hipGetLastError(), "sjhip_ctx_trim");
-    invalidate_result(ctx);
-    ctx->kf_valid = 0;
+    ctx->res.drop_result();
     ctx->tape_len = ctx->strings_len = 0;
     DevBuf *bufs[] = SJ_CTX_ARENAS(ctx);
     for (DevBuf *b : bufs) {
@@ -190,14 +201,13 @@ static int stage1_verdict(const Stage1State &st, size_t len, uint8_t last_byte) 
 
 // A stage-1-only call re-uses (and may re-allocate) the arenas a device-resident parse result lives in -- the message
 // copy, the positions with the token kinds behind them: queries, the serializer and MarshalJSON must not run on what
-// is left (they return SJHIP_ERR_ARG until the next parse).
-static void invalidate_result(sjhip_ctx *ctx) {
-    ctx->q_valid = ctx->r_valid = ctx->ser_valid = ctx->ms_valid = 0;
-    ctx->col_valid = ctx->list_valid = 0;
-    ctx->pending = 0;
-    ctx->q_tape_len = ctx->q_strings_len = 0;
-    ctx->f_valid = 0;
-    ctx->pack_valid = 0;  // (sjhip_fetch goes back to the device copies, which a stage-1 call does not touch)
+// is left (they return SJHIP_ERR_ARG until the next parse).  sjhip_fetch goes back to the device copies of the tape and
+// Strings.B, which a stage-1 call does not touch; a sharded result lies in the shards' arenas and only loses its products.
+static void stage1_only(sjhip_ctx *ctx) {
+    if (!ctx->res.sharded()) return ctx->res.drop_result();
+    ctx->res.claim_shared();
+    ctx->res.begin_column();
+    ctx->res.begin_list();
 }
 
 // stage 1 in two halves: enqueue (workspace, launch; the last block of the kernel leaves the packed result -- count,
@@ -290,7 +300,7 @@ int sj::stage1_run_device(sjhip_ctx *ctx, const void *d_msg, size_t len, int ndj
 int sjhip_stage1_device(sjhip_ctx *ctx, const void *d_msg, size_t len, int ndjson, void *d_pos, size_t pos_cap,
                         size_t *n, int *ok) {
     if (!ctx || !n || !ok) return SJHIP_ERR_ARG;
-    invalidate_result(ctx);
+    stage1_only(ctx);
     return stage1_run_device(ctx, d_msg, len, ndjson != 0, d_pos, pos_cap, 0, 0, n, ok);
 }
 
@@ -302,7 +312,7 @@ static inline unsigned long long *s1q_record(sjhip_ctx *ctx, int slot) {
 int sjhip_stage1_device_queue(sjhip_ctx *ctx, const void *d_msg, size_t len, int ndjson, void *d_pos, size_t pos_cap, int slot) {
     if (!ctx || slot < 0 || slot >= SJHIP_STAGE1_QUEUE_SLOTS) return SJHIP_ERR_ARG;
     static_assert(SJHIP_STAGE1_QUEUE_SLOTS * 32 <= 2048 && S1_HOST_WORDS * 8 <= 32, "the records fill the upper half of h_scratch");
-    invalidate_result(ctx);
+    stage1_only(ctx);
     if (len == 0) {  // (no launch: the record says so)
         unsigned long long *r = s1q_record(ctx, slot);
         r[0] = r[1] = r[2] = 0;
@@ -324,7 +334,7 @@ int sjhip_stage1_device_result(sjhip_ctx *ctx, int slot, size_t len, size_t *n, 
 int sjhip_stage1(sjhip_ctx *ctx, const uint8_t *msg, size_t len, int ndjson, uint32_t *pos_out, size_t pos_cap,
                  size_t *n, int *ok) {
     if (!ctx || !n || !ok) return SJHIP_ERR_ARG;
-    invalidate_result(ctx);
+    stage1_only(ctx);
     if (len >= 0xffffffc0ull) {  // before anything is allocated or copied
         ctx_set_error(ctx, "message too long for uint32 positions (4 GiB - 64)");
         return SJHIP_ERR_TOOBIG;
@@ -349,7 +359,7 @@ int sjhip_stage1(sjhip_ctx *ctx, const uint8_t *msg, size_t len, int ndjson, uin
 int sjhip_stage1_time(sjhip_ctx *ctx, const void *d_msg, size_t len, int ndjson, void *d_pos, size_t pos_cap,
                       int iters, float *ms_per_launch) {
     if (!ctx || iters <= 0 || !ms_per_launch) return SJHIP_ERR_ARG;
-    invalidate_result(ctx);
+    stage1_only(ctx);
     HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
     int rc = arena_reserve(ctx, ctx->d_ws, stage1_workspace_bytes(len + 64));
     if (rc) return rc;
@@ -376,7 +386,7 @@ int sjhip_stage1_set_variant(int variant) { return stage1_set_variant(variant); 
 int sjhip_stage1_trace(sjhip_ctx *ctx, const void *d_msg, size_t len, void *d_pos, size_t pos_cap, uint64_t *trace_out,
                        size_t trace_cap_words, unsigned *tiles, int *waves, int *words) {
     if (!ctx || !trace_out || !tiles || !waves || !words) return SJHIP_ERR_ARG;
-    invalidate_result(ctx);
+    stage1_only(ctx);
     HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
     const size_t lead = (size_t)(reinterpret_cast<uintptr_t>(d_msg) & 63);
     const size_t nw = stage1_trace_words(len, lead, tiles, waves);

@@ -102,7 +102,7 @@ static int batch_common(sjhip_ctx *ctx, size_t n, uint32_t flags, size_t *tape_l
     if (tape_len) *tape_len = 0;
     if (strings_len) *strings_len = 0;
     if (!ctx) return SJHIP_ERR_ARG;
-    ctx->tape_len = ctx->strings_len = 0;
+    sj::begin_parse(ctx);
     if (!(flags & SJHIP_FLAG_COPY_STRINGS)) {
         sj::ctx_set_error(ctx, "sjhip_parse_batch needs SJHIP_FLAG_COPY_STRINGS (string words would point into the packed message)");
         return SJHIP_ERR_ARG;
@@ -115,7 +115,7 @@ static int batch_common(sjhip_ctx *ctx, size_t n, uint32_t flags, size_t *tape_l
     return SJHIP_OK;
 }
 
-// descriptors -> device (the context's query arena is free between parses)
+// descriptors -> device (d_q has no tenant after begin_parse)
 static int upload_docs(sjhip_ctx *ctx, const std::vector<DocDesc> &docs, const DocDesc **d_docs) {
     int rc = sj::arena_reserve(ctx, ctx->d_q, docs.size() * sizeof(DocDesc));
     if (rc) return rc;
@@ -243,8 +243,7 @@ int sjhip_parse_batch_device(sjhip_ctx *ctx, const void *d_buf, const size_t *of
     if (rc != SJHIP_OK && rc != SJHIP_ERR_STAGE1 && rc != SJHIP_ERR_STAGE2) return rc;
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) return SJHIP_ERR_HIP;  // (a parse that failed early may not have waited)
     if (*bad) {  // a document that Parse() rejects in stage 1: that code wins (parse_json_amd64.go:97-105,123-126)
-        ctx->tape_len = ctx->strings_len = 0;
-        ctx->q_valid = ctx->r_valid = ctx->pack_valid = ctx->col_valid = ctx->list_valid = 0;
+        sj::begin_parse(ctx);
         if (tape_len) *tape_len = 0;
         if (strings_len) *strings_len = 0;
         return SJHIP_ERR_STAGE1;

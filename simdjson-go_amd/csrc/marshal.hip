@@ -886,12 +886,8 @@ static int marshal_bounds_check(sjhip_ctx *ctx) {
 
 // Iter.MarshalJSON of the result `part` holds (ctx itself, or one shard of ctx's sharded ND result); errors are left in ctx
 static int marshal_part(sjhip_ctx *ctx, sjhip_ctx *part, size_t *text_len) {
-    part->ms_len = 0;
-    part->ms_valid = 0;
-    if (!part->r_valid || part->tape_len == 0) {
-        ctx_set_error(ctx, "no parse result on the device (sjhip_marshal_json follows a successful sjhip_parse / sjhip_parse_device)");
-        return SJHIP_ERR_ARG;
-    }
+    part->res.release_shared(ResultState::Tenant::Marshaled);
+    if (!part->res.resident()) return no_result(ctx, "sjhip_marshal_json follows");
     if (part->p_len >= (1ull << 32) && !(part->p_flags & SJHIP_FLAG_COPY_STRINGS)) {
         // k_ms_tile keeps the offset of a string in 32 bits of its queue entry: with WithCopyStrings(false) the strings that are not
         // copied lie at MESSAGE offsets, which pass 2^32 in a document of 4 GiB or more (Strings.B itself is checked to stay below)
@@ -899,16 +895,14 @@ static int marshal_part(sjhip_ctx *ctx, sjhip_ctx *part, size_t *text_len) {
         return SJHIP_ERR_TOOBIG;
     }
     HIPCHK(hipSetDevice(part->device), "hipSetDevice");
-    part->ser_valid = 0;  // shares d_q with the serializer and the filter
-    part->q_tape_len = part->q_strings_len = 0;
-    part->f_valid = 0;
+    part->res.claim_shared();  // (the filter and the serializer use the same arenas)
     MsView p;
     p.tape = (const u64 *)part->d_tape.p;
     p.n = part->tape_len;
     p.tiles = (u32)((p.n + TW_TILE - 1) / TW_TILE);
-    p.tape_base = part->r_tape_base;
-    p.strings_base = part->r_strings_base;
-    p.msg_base = part->r_msg_base;
+    p.tape_base = part->res.tape_base();
+    p.strings_base = part->res.strings_base();
+    p.msg_base = part->res.msg_base();
     p.strings = (const u8 *)part->d_strings.p;
     p.msg = (const u8 *)part->p_msg;
     p.strings_len = part->strings_len;
@@ -950,7 +944,7 @@ static int marshal_part(sjhip_ctx *ctx, sjhip_ctx *part, size_t *text_len) {
 #endif
     HIPCHK(hipMemsetAsync(p.totals, 0, 256, part->stream), "marshal memset");
     // keys: the flags the parser left (SJHIP_FLAG_KEY_FLAGS), or from the token array of the parse (three launches)
-    p.kf_tape = (part->kf_valid) ? (const u8 *)part->d_keyflag.p : nullptr;
+    p.kf_tape = part->res.key_flags() ? (const u8 *)part->d_keyflag.p : nullptr;
     if (!p.kf_tape) {
         hipLaunchKernelGGL(k_ms_keys<false>, dim3(kv.tiles), dim3(256), 0, part->stream, kv);
         hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, part->stream, kv.cnt, (unsigned long long *)nullptr,
@@ -1014,10 +1008,9 @@ static int marshal_part(sjhip_ctx *ctx, sjhip_ctx *part, size_t *text_len) {
                 ctx_set_error(ctx, "MarshalJSON: 2048 consecutive tape words produce more than 4 GiB of text");
                 return SJHIP_ERR_TOOBIG;
             }
-            part->ms_len = (size_t)h[0];
-            part->ms_valid = 1;
-            if (text_len) *text_len = part->ms_len;
-            return marshal_bounds_check(ctx);
+            if (text_len) *text_len = (size_t)h[0];
+            rc = published(ctx, part->res.publish_marshaled((size_t)h[0]));
+            return rc ? rc : marshal_bounds_check(ctx);
         }
         no_local_anchor = (h[2] & 4ull) != 0;  // (the counting pass below starts with the global anchors right away)
         HIPCHK(hipMemsetAsync(p.totals, 0, 256, part->stream), "marshal memset");
@@ -1055,10 +1048,8 @@ static int marshal_part(sjhip_ctx *ctx, sjhip_ctx *part, size_t *text_len) {
     p.text = (u8 *)part->d_qtape.p;
     launch_ms_tile<1>(p, part->stream);
     HIPCHK(hipGetLastError(), "marshal emit launch");
-    part->ms_len = (size_t)h[0];
-    part->ms_valid = 1;
-    if (text_len) *text_len = part->ms_len;
-    return SJHIP_OK;
+    if (text_len) *text_len = (size_t)h[0];
+    return published(ctx, part->res.publish_marshaled((size_t)h[0]));
 }
 
 // The device-resident result of the last parse as text.  A sharded ND result (parse_nd_big) is marshaled shard by shard -- a shard
@@ -1066,9 +1057,8 @@ static int marshal_part(sjhip_ctx *ctx, sjhip_ctx *part, size_t *text_len) {
 // (parsed_json.go:401-556 writes one between records and none behind the last).
 int sjhip_marshal_json(sjhip_ctx *ctx, size_t *text_len) {
     if (!ctx) return SJHIP_ERR_ARG;
-    ctx->ms_len = 0;
-    ctx->ms_valid = 0;
-    if (!ctx->big_valid) return marshal_part(ctx, ctx, text_len);
+    if (!ctx->res.sharded()) return marshal_part(ctx, ctx, text_len);
+    ctx->res.claim_shared();
     size_t total = 0;
     int np = 0;
     for (sjhip_ctx *part : result_parts(ctx)) {
@@ -1083,36 +1073,31 @@ int sjhip_marshal_json(sjhip_ctx *ctx, size_t *text_len) {
         np++;
     }
     (void)hipSetDevice(ctx->device);
-    if (np == 0) {
-        ctx_set_error(ctx, "no parse result on the device (sjhip_marshal_json follows a successful sjhip_parse / sjhip_parse_device)");
-        return SJHIP_ERR_ARG;
-    }
-    ctx->ms_len = total;
-    ctx->ms_valid = 1;
+    if (np == 0) return no_result(ctx, "sjhip_marshal_json follows");
     if (text_len) *text_len = total;
-    return SJHIP_OK;
+    return published(ctx, ctx->res.publish_marshaled(total));
 }
 
 int sjhip_fetch_marshaled(sjhip_ctx *ctx, uint8_t *dst) {
-    if (!ctx || !ctx->ms_valid) return SJHIP_ERR_ARG;
-    if (ctx->big_valid) {  // the shards' texts, joined with the newline between two records
+    if (!ctx || !ctx->res.marshaled()) return SJHIP_ERR_ARG;
+    if (ctx->res.sharded()) {  // the shards' texts, joined with the newline between two records
         size_t at = 0;
         int np = 0;
         for (sjhip_ctx *part : result_parts(ctx)) {
-            if (!part->ms_valid) continue;
+            if (!part->res.marshaled()) continue;
+            const size_t len = part->res.marshaled_len();
             if (np++ && dst) dst[at++] = '\n';
             HIPCHK(hipSetDevice(part->device), "hipSetDevice");
-            if (part->ms_len && dst)
-                HIPCHK(hipMemcpyAsync(dst + at, part->d_qtape.p, part->ms_len, hipMemcpyDeviceToHost, part->stream), "D2H JSON text");
+            if (len && dst) HIPCHK(hipMemcpyAsync(dst + at, part->d_qtape.p, len, hipMemcpyDeviceToHost, part->stream), "D2H JSON text");
             HIPCHK(hipStreamSynchronize(part->stream), "fetch sync");
-            at += part->ms_len;
+            at += len;
         }
         HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
-        return at == ctx->ms_len ? marshal_bounds_check(ctx) : SJHIP_ERR_ARG;
+        return at == ctx->res.marshaled_len() ? marshal_bounds_check(ctx) : SJHIP_ERR_ARG;
     }
     HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
-    if (ctx->ms_len && dst)
-        HIPCHK(hipMemcpyAsync(dst, ctx->d_qtape.p, ctx->ms_len, hipMemcpyDeviceToHost, ctx->stream), "D2H JSON text");
+    if (ctx->res.marshaled_len() && dst)
+        HIPCHK(hipMemcpyAsync(dst, ctx->d_qtape.p, ctx->res.marshaled_len(), hipMemcpyDeviceToHost, ctx->stream), "D2H JSON text");
     HIPCHK(hipStreamSynchronize(ctx->stream), "fetch sync");
     return marshal_bounds_check(ctx);  // (debug build: the writing pass has finished here)
 }

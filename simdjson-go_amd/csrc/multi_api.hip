@@ -297,14 +297,12 @@ int sj::parse_nd_big(sjhip_ctx *ctx, const uint8_t *msg, size_t len, uint32_t fl
             return SJHIP_ERR_HIP;
         }
     }
-    ctx->big_valid = 0;
-    ctx->col_valid = ctx->list_valid = 0;
     const int rc = multi_parse(ctx->big, msg, len, flags, d_resident, tape_len, strings_len, msg_off, msg_len);
     if (rc == SJHIP_OK) {
-        ctx->big_valid = 1;
         // the totals of the merged result, for sjhip_fetch_view (which sizes its view block from the context)
         ctx->tape_len = ctx->big->tape_len;
         ctx->strings_len = ctx->big->strings_len;
+        ctx->res.parse_sharded(ctx->tape_len);
     } else if (rc != SJHIP_ERR_STAGE1 && rc != SJHIP_ERR_STAGE2) sj::ctx_set_error(ctx, "%s", sjhip_multi_last_error(ctx->big));
     (void)hipSetDevice(ctx->device);
     return rc;
@@ -322,7 +320,7 @@ size_t sj::nd_big_device_bytes(const sjhip_ctx *ctx) {
     return total;
 }
 
-int sj::nd_big_shards(const sjhip_ctx *ctx) { return ctx->big && ctx->big_valid ? (int)ctx->big->shards.size() : 0; }
+int sj::nd_big_shards(const sjhip_ctx *ctx) { return ctx->big && ctx->res.sharded() ? (int)ctx->big->shards.size() : 0; }
 sjhip_ctx *sj::nd_big_shard(const sjhip_ctx *ctx, int k) {
     if (!ctx->big || k < 0 || (size_t)k >= ctx->big->shards.size()) return nullptr;
     const Shard &s = ctx->big->shards[(size_t)k];
@@ -330,7 +328,7 @@ sjhip_ctx *sj::nd_big_shard(const sjhip_ctx *ctx, int k) {
 }
 std::vector<sjhip_ctx *> sj::result_parts(sjhip_ctx *ctx) {
     std::vector<sjhip_ctx *> parts;
-    if (!ctx->big_valid) parts.push_back(ctx);
+    if (!ctx->res.sharded()) parts.push_back(ctx);
     else
         for (int k = 0; k < nd_big_shards(ctx); k++)
             if (sjhip_ctx *c = nd_big_shard(ctx, k)) parts.push_back(c);
@@ -340,7 +338,6 @@ std::vector<sjhip_ctx *> sj::result_parts(sjhip_ctx *ctx) {
 void sj::release_nd_big(sjhip_ctx *ctx) {
     if (ctx->big) sjhip_multi_destroy(ctx->big);
     ctx->big = nullptr;
-    ctx->big_valid = 0;
 }
 
 int sjhip_fetch_multi(sjhip_multi *m, uint64_t *tape_dst, uint8_t *strings_dst) {

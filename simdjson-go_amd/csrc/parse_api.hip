@@ -81,17 +81,7 @@ static size_t nd_shard_bytes() {
 
 static int parse_begin(sjhip_ctx *ctx, const void *d_msg, size_t len, uint32_t flags, uint8_t last_byte, int have_last,
                        size_t *tape_len, size_t *strings_len) {
-    ctx->tape_len = ctx->strings_len = 0;
-    ctx->big_valid = 0;
-    ctx->col_valid = ctx->list_valid = 0;
-    ctx->pending = 0;
-    ctx->pack_valid = 0;
-    ctx->q_valid = 0;
-    ctx->r_valid = 0;
-    ctx->kf_valid = 0;
-    ctx->ser_valid = 0;
-    ctx->ms_valid = 0;
-    ctx->f_valid = 0;
+    begin_parse(ctx);
     if (len == 0) return SJHIP_ERR_STAGE1;  // indexTotal == 0 (stage1_find_marks_amd64.go:147)
     if (len > SINGLE_LIMIT) {  // (an ND message beyond 4 GiB went to parse_nd_big)
         ctx_set_error(ctx, "document of %zu bytes: one context parses up to %zu", len, SINGLE_LIMIT);
@@ -192,7 +182,7 @@ static int parse_begin(sjhip_ctx *ctx, const void *d_msg, size_t len, uint32_t f
         if (rc) return rc;
     }
     ctx->p_aux = aux;
-    ctx->pending = 1;
+    ctx->res.parse_pending();
     ctx->p_msg = d_msg;
     ctx->p_len = len;
     ctx->p_n = n;
@@ -240,20 +230,20 @@ static int parse_begin(sjhip_ctx *ctx, const void *d_msg, size_t len, uint32_t f
     return SJHIP_OK;
 }
 
-static int parse_finish(sjhip_ctx *ctx, uint64_t tape_base, uint64_t strings_base, uint64_t msg_base, size_t *tape_len,
+// to_host: the caller holds host buffers (sjhip_parse), its sjhip_fetch will want the result there
+static int parse_finish(sjhip_ctx *ctx, uint64_t tape_base, uint64_t strings_base, uint64_t msg_base, bool to_host, size_t *tape_len,
                         size_t *strings_len) {
-    if (!ctx->pending) {
+    if (!ctx->res.pending()) {
         ctx_set_error(ctx, "no parse in progress");
         return SJHIP_ERR_ARG;
     }
-    ctx->pending = 0;
+    begin_parse(ctx);  // (no longer pending: a failure below leaves nothing)
     HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
     S2State *hs = (S2State *)(ctx->h_scratch + 256);
     // a small document that came from a host buffer: the state, the tape and Strings.B go to pinned memory with the last
     // launch of the chain (sj_ctx.h h_pack); sjhip_fetch then copies from there
-    const bool pack = ctx->want_pack && ctx->p_deferred && tape_base == 0 && strings_base == 0 && msg_base == 0;
-    ctx->want_pack = 0;
-    ctx->pack_valid = 0;
+    const bool pack = to_host && ctx->p_deferred && tape_base == 0 && strings_base == 0 && msg_base == 0;
+    bool packed = false;
     if (pack && !ctx->h_pack && sj::pinned_alloc((void **)&ctx->h_pack, PACK_BYTES) != hipSuccess) {
         (void)hipGetLastError();
         ctx->h_pack = nullptr;
@@ -265,13 +255,13 @@ static int parse_finish(sjhip_ctx *ctx, uint64_t tape_base, uint64_t strings_bas
             HIPCHK(stage2_launch_pack(a, ctx->h_pack, PACK_BYTES), "stage2 launch (pack)");
             HIPCHK(hipStreamSynchronize(ctx->stream), "stage2 sync");
             memcpy(hs, ctx->h_pack, sizeof(S2State));
-            ctx->pack_valid = *(const unsigned long long *)(ctx->h_pack + 64) != 0;
+            packed = *(const unsigned long long *)(ctx->h_pack + 64) != 0;
         } else {
             HIPCHK(stage2_launch_state_out(a, hs), "stage2 state");
             HIPCHK(hipStreamSynchronize(ctx->stream), "stage2 sync");
         }
         if (hs->bignum_count && !(hs->err & S2_ERR_SERIAL_STRINGS)) {  // rare: >19-digit mantissas that need the exact tie-break
-            ctx->pack_valid = 0;  // (k_pack did not copy: the tape is not final)
+            packed = false;  // (k_pack did not copy: the tape is not final)
             HIPCHK(stage2_launch_bignum(a), "stage2 launch (bignum)");
             HIPCHK(hipMemcpyAsync(hs, ctx->d_s2z.p, sizeof(S2State), hipMemcpyDeviceToHost, ctx->stream), "D2H stage2 state");
             HIPCHK(hipStreamSynchronize(ctx->stream), "stage2 sync");
@@ -335,32 +325,26 @@ static int parse_finish(sjhip_ctx *ctx, uint64_t tape_base, uint64_t strings_bas
     ctx->tape_len = (size_t)hs->tape_len;
     ctx->strings_len = ctx->p_aux ? (size_t)hs->strings_len_masks : (size_t)hs->strings_len;
     ctx->q_records = hs->records;
-    ctx->q_valid = tape_base == 0 && strings_base == 0 && msg_base == 0;  // filter / serializer / MarshalJSON work on unsharded results
-    ctx->r_valid = 1;  // the path / count queries also on a shard (in the merged index space)
-    ctx->r_tape_base = tape_base;
-    ctx->r_strings_base = strings_base;
-    ctx->r_msg_base = msg_base;
-    ctx->kf_valid = (ctx->p_flags & SJHIP_FLAG_KEY_FLAGS) && ctx->d_keyflag.p;  // (indexed by the context's own tape offsets: a shard's as well)
+    // (the key flags are indexed by the context's own tape offsets: a shard's as well)
+    ctx->res.parse_done(tape_base, strings_base, msg_base, ctx->tape_len, (ctx->p_flags & SJHIP_FLAG_KEY_FLAGS) && ctx->d_keyflag.p, packed);
     if (tape_len) *tape_len = ctx->tape_len;
     if (strings_len) *strings_len = ctx->strings_len;
     return SJHIP_OK;
 }
 
 static int parse_on_device(sjhip_ctx *ctx, const void *d_msg, size_t len, uint32_t flags, uint8_t last_byte,
-                           int have_last, size_t *tape_len, size_t *strings_len) {
-    const int want_pack = ctx->want_pack;
+                           int have_last, bool to_host, size_t *tape_len, size_t *strings_len) {
     int rc = parse_begin(ctx, d_msg, len, flags, last_byte, have_last, nullptr, nullptr);
     if (rc) return rc;
-    rc = parse_finish(ctx, 0, 0, 0, tape_len, strings_len);
+    rc = parse_finish(ctx, 0, 0, 0, to_host, tape_len, strings_len);
     if (rc == PARSE_AGAIN_SYNCHRONOUS) {  // a document denser than its layout: a small one with more than one token per four bytes,
                                           // a large one denser than the context's last parse (this parse leaves the new density)
         ctx->p_no_defer = 1;
         if (len <= small_document_bytes()) ctx->p_dense = 1;  // (minified numeric arrays come in series: the next ones are laid out for one token per byte)
-        ctx->want_pack = want_pack;
         rc = parse_begin(ctx, d_msg, len, flags, last_byte, have_last, nullptr, nullptr);
         ctx->p_no_defer = 0;
         if (rc) return rc;
-        rc = parse_finish(ctx, 0, 0, 0, tape_len, strings_len);
+        rc = parse_finish(ctx, 0, 0, 0, to_host, tape_len, strings_len);
     }
     return rc;
 }
@@ -368,53 +352,48 @@ static int parse_on_device(sjhip_ctx *ctx, const void *d_msg, size_t len, uint32
 // batch_api.hip: the whole parse of the message it packed into the context's message arena
 int sj::parse_packed(sjhip_ctx *ctx, size_t len, uint32_t flags, uint8_t last_byte, int have_last, size_t *tape_len,
                      size_t *strings_len) {
-    return parse_on_device(ctx, ctx->d_msg.p, len, flags, last_byte, have_last, tape_len, strings_len);
+    return parse_on_device(ctx, ctx->d_msg.p, len, flags, last_byte, have_last, false, tape_len, strings_len);
 }
 
 int sjhip_parse_shard_begin(sjhip_ctx *ctx, const void *d_msg, size_t len, uint32_t flags, size_t *tape_len,
                             size_t *strings_len) {
-    if (!ctx || !tape_len || !strings_len) return SJHIP_ERR_ARG;
+    if (!ctx) return SJHIP_ERR_ARG;
+    begin_parse(ctx);
+    if (!tape_len || !strings_len) return SJHIP_ERR_ARG;
     *tape_len = *strings_len = 0;
     return parse_begin(ctx, d_msg, len, flags, 0, 0, tape_len, strings_len);
 }
 
 int sjhip_parse_shard_finish(sjhip_ctx *ctx, uint64_t tape_base, uint64_t strings_base, uint64_t msg_base) {
     if (!ctx) return SJHIP_ERR_ARG;
-    return parse_finish(ctx, tape_base, strings_base, msg_base, nullptr, nullptr);
+    return parse_finish(ctx, tape_base, strings_base, msg_base, false, nullptr, nullptr);
 }
 
 int sjhip_parse_device(sjhip_ctx *ctx, const void *d_msg, size_t len, uint32_t flags, size_t *tape_len,
                        size_t *strings_len) {
     if (!ctx) return SJHIP_ERR_ARG;
+    begin_parse(ctx);
     if (nd_too_big(len, flags)) {  // shards on this device, each parsing its window of the message in place
-        ctx->tape_len = ctx->strings_len = 0;
-        ctx->q_valid = ctx->r_valid = ctx->ser_valid = ctx->ms_valid = ctx->f_valid = ctx->pack_valid = ctx->pending = 0;
-        ctx->col_valid = ctx->list_valid = 0;
         HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
         HIPCHK(hipStreamSynchronize(ctx->stream), "stream sync");  // (the shards run on streams of their own)
         return parse_nd_big(ctx, (const uint8_t *)d_msg, len, flags, true, nd_shard_bytes(), tape_len, strings_len, nullptr, nullptr);
     }
-    return parse_on_device(ctx, d_msg, len, flags, 0, 0, tape_len, strings_len);
+    return parse_on_device(ctx, d_msg, len, flags, 0, 0, false, tape_len, strings_len);
 }
 
 int sjhip_parse(sjhip_ctx *ctx, const uint8_t *msg, size_t len, uint32_t flags, size_t *tape_len, size_t *strings_len,
                 size_t *msg_off, size_t *msg_len) {
     if (!ctx) return SJHIP_ERR_ARG;
+    begin_parse(ctx);
     size_t off = 0, mlen = 0;
     if (len) trim_space(msg, len, &off, &mlen);  // pj.Message = bytes.TrimSpace(msg), parse_json_amd64.go:55
     if (msg_off) *msg_off = off;
     if (msg_len) *msg_len = mlen;
     if (tape_len) *tape_len = 0;
     if (strings_len) *strings_len = 0;
-    ctx->tape_len = ctx->strings_len = 0;
-    ctx->big_valid = 0;
-    ctx->col_valid = ctx->list_valid = 0;
     if (mlen == 0) return SJHIP_ERR_STAGE1;
-    if (nd_too_big(mlen, flags)) {  // shards of the host message, H2D straight from the caller's buffer
-        ctx->q_valid = ctx->r_valid = ctx->ser_valid = ctx->ms_valid = ctx->f_valid = ctx->pack_valid = ctx->pending = 0;
-        ctx->col_valid = ctx->list_valid = 0;
+    if (nd_too_big(mlen, flags))  // shards of the host message, H2D straight from the caller's buffer
         return parse_nd_big(ctx, msg, len, flags, false, nd_shard_bytes(), tape_len, strings_len, nullptr, nullptr);
-    }
     if (mlen > SINGLE_LIMIT) {  // before anything is copied to the device
         ctx_set_error(ctx, "document of %zu bytes: one context parses up to %zu", mlen, SINGLE_LIMIT);
         return SJHIP_ERR_TOOBIG;
@@ -423,10 +402,7 @@ int sjhip_parse(sjhip_ctx *ctx, const uint8_t *msg, size_t len, uint32_t flags, 
     int rc = arena_reserve(ctx, ctx->d_msg, mlen + 128);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(ctx->d_msg.p, msg + off, mlen, hipMemcpyHostToDevice, ctx->stream), "H2D message");
-    ctx->want_pack = 1;  // the caller holds host buffers: its sjhip_fetch will want the result there
-    rc = parse_on_device(ctx, ctx->d_msg.p, mlen, flags, msg[off + mlen - 1], 1, tape_len, strings_len);
-    ctx->want_pack = 0;
-    return rc;
+    return parse_on_device(ctx, ctx->d_msg.p, mlen, flags, msg[off + mlen - 1], 1, true, tape_len, strings_len);
 }
 
 int sjhip_debug_bounds_selftest(void) { return stage2_debug_bounds_selftest(); }
@@ -440,8 +416,8 @@ void sjhip_trim_space(const uint8_t *msg, size_t len, size_t *off, size_t *out_l
 
 int sjhip_fetch(sjhip_ctx *ctx, uint64_t *tape_dst, uint8_t *strings_dst) {
     if (!ctx) return SJHIP_ERR_ARG;
-    if (ctx->big_valid) return fetch_nd_big(ctx, tape_dst, strings_dst);  // every shard straight into its slice
-    if (ctx->pack_valid && ctx->h_pack) {  // the result of a small sjhip_parse is already in pinned host memory
+    if (ctx->res.sharded()) return fetch_nd_big(ctx, tape_dst, strings_dst);  // every shard straight into its slice
+    if (ctx->res.packed()) {  // the result of a small sjhip_parse is already in pinned host memory
         if (ctx->tape_len && tape_dst) memcpy(tape_dst, ctx->h_pack + STAGE2_PACK_HEAD, ctx->tape_len * sizeof(uint64_t));
         if (ctx->strings_len && strings_dst)
             memcpy(strings_dst, ctx->h_pack + STAGE2_PACK_HEAD + ctx->tape_len * sizeof(uint64_t), ctx->strings_len);
@@ -471,7 +447,7 @@ int sjhip_fetch_view(sjhip_ctx *ctx, const uint64_t **tape, const uint8_t **stri
     *tape = nullptr;
     *strings = nullptr;
     const size_t tb = ctx->tape_len * sizeof(uint64_t), sb = ctx->strings_len;
-    if (!ctx->big_valid && ctx->pack_valid && ctx->h_pack) {  // a small sjhip_parse: nothing to move
+    if (ctx->res.packed()) {  // a small sjhip_parse: nothing to move
         if (tb) *tape = (const uint64_t *)(ctx->h_pack + STAGE2_PACK_HEAD);
         if (sb) *strings = ctx->h_pack + STAGE2_PACK_HEAD + tb;
         return SJHIP_OK;

@@ -845,10 +845,7 @@ static int query_bounds_check(sjhip_ctx *ctx) {
     return SJHIP_OK;
 }
 
-static int no_result(sjhip_ctx *ctx) {
-    ctx_set_error(ctx, "no parse result on the device (queries follow a successful sjhip_parse / sjhip_parse_device)");
-    return SJHIP_ERR_ARG;
-}
+static int no_result(sjhip_ctx *ctx) { return sj::no_result(ctx, "queries follow"); }
 static int check_key_value(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const uint8_t *val, size_t vlen) {
     if (!ctx || !key || !val) return SJHIP_ERR_ARG;
     if (klen > QMAX || vlen > QMAX) {
@@ -860,16 +857,17 @@ static int check_key_value(sjhip_ctx *ctx, const uint8_t *key, size_t klen, cons
 // view of the result held by `part` (ctx itself, or one shard context of ctx's sharded result) with the key and the value of a
 // query (checked by the caller: check_key_value); errors are left in ctx
 static int make_view(sjhip_ctx *ctx, sjhip_ctx *part, const uint8_t *key, size_t klen, const uint8_t *val, size_t vlen, QView *q) {
-    if (!part->r_valid || part->tape_len == 0) return no_result(ctx);
+    if (!part->res.resident()) return no_result(ctx);
     const uint32_t *nl = nullptr;
     stage2_records_view(part->d_s2.p, part->p_nlay, &nl);
     // (pointers moved down by the shard's bases: see QView; all zero for an unsharded result)
-    q->tape_base = part->r_tape_base;
-    q->tape = SJ_ARR((const u64 *)part->d_tape.p - part->r_tape_base, part->r_tape_base + part->tape_len, A_TAPE);
-    q->tape_len = part->r_tape_base + part->tape_len;
-    q->strings = SJ_ARR((const u8 *)part->d_strings.p - part->r_strings_base, part->r_strings_base + part->strings_len, A_STRINGS);
+    const u64 tape_base = part->res.tape_base(), strings_base = part->res.strings_base(), msg_base = part->res.msg_base();
+    q->tape_base = tape_base;
+    q->tape = SJ_ARR((const u64 *)part->d_tape.p - tape_base, tape_base + part->tape_len, A_TAPE);
+    q->tape_len = tape_base + part->tape_len;
+    q->strings = SJ_ARR((const u8 *)part->d_strings.p - strings_base, strings_base + part->strings_len, A_STRINGS);
     q->strings_len = part->strings_len;
-    q->msg = SJ_ARR((const u8 *)part->p_msg - part->r_msg_base, part->r_msg_base + part->p_len, A_MSG);
+    q->msg = SJ_ARR((const u8 *)part->p_msg - msg_base, msg_base + part->p_len, A_MSG);
     q->msg_len = part->p_len;
     q->nl_off = SJ_ARR(nl, part->q_records, A_NL_OFF);
     q->R = part->q_records;
@@ -964,11 +962,7 @@ int sjhip_count_where(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const uin
 
 int sjhip_filter_where(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const uint8_t *value, size_t vlen,
                        uint64_t *n_records, size_t *tape_len, size_t *strings_len) {
-    if (ctx && !ctx->q_valid) {  // the unsharded result of ctx itself
-        if (ctx->big_valid) ctx_set_error(ctx, "sjhip_filter_where works on the result of one context; this ND result was parsed shard by shard");
-        else ctx_set_error(ctx, "no parse result on the device (queries follow a successful sjhip_parse / sjhip_parse_device)");
-        return SJHIP_ERR_ARG;
-    }
+    if (ctx && !ctx->res.whole()) return no_whole_result(ctx, "sjhip_filter_where", "queries follow");  // the unsharded result of ctx itself
     QView q;
     int rc = check_key_value(ctx, key, klen, value, vlen);
     if (rc == SJHIP_OK) rc = make_view(ctx, ctx, key, klen, value, vlen, &q);
@@ -979,9 +973,7 @@ int sjhip_filter_where(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const ui
         return SJHIP_ERR_ARG;
     }
     HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
-    ctx->ser_valid = 0;  // the serializer's columns live in the same arenas
-    ctx->ms_valid = 0;
-    ctx->f_valid = 0;
+    ctx->res.claim_shared();
     const u32 tiles = (n + QTILE - 1) / QTILE;
     QRec o;
     QTiles T;
@@ -1017,12 +1009,11 @@ int sjhip_filter_where(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const ui
     unsigned long long *h = (unsigned long long *)(ctx->h_scratch + 512);
     HIPCHK(hipMemcpyAsync(h, o.totals, 24, hipMemcpyDeviceToHost, ctx->stream), "D2H totals");
     HIPCHK(hipStreamSynchronize(ctx->stream), "filter sync");
-    ctx->q_tape_len = (size_t)h[1];
-    ctx->q_strings_len = (size_t)h[2];
-    ctx->f_valid = 1;
+    rc = published(ctx, ctx->res.publish_filtered({(size_t)h[1], (size_t)h[2]}));
+    if (rc) return rc;
     if (n_records) *n_records = h[0];
-    if (tape_len) *tape_len = ctx->q_tape_len;
-    if (strings_len) *strings_len = ctx->q_strings_len;
+    if (tape_len) *tape_len = (size_t)h[1];
+    if (strings_len) *strings_len = (size_t)h[2];
     if (h[0] == 0) return query_bounds_check(ctx);
     hipLaunchKernelGGL(k_q_copy, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, q, o, (u64 *)ctx->d_qtape.p, (u8 *)ctx->d_qstrings.p);
     HIPCHK(hipGetLastError(), "filter copy launch");
@@ -1031,15 +1022,16 @@ int sjhip_filter_where(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const ui
 
 int sjhip_fetch_filtered(sjhip_ctx *ctx, uint64_t *tape_dst, uint8_t *strings_dst) {
     if (!ctx) return SJHIP_ERR_ARG;
-    if (!ctx->f_valid) {  // no filter ran, or a later parse / serialize / marshal call re-used its arenas
+    if (!ctx->res.filtered()) {  // no filter ran, or a later parse / serialize / marshal call re-used its arenas
         ctx_set_error(ctx, "no filtered result on the device (sjhip_fetch_filtered follows sjhip_filter_where)");
         return SJHIP_ERR_ARG;
     }
     HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
-    if (ctx->q_tape_len && tape_dst)
-        HIPCHK(hipMemcpyAsync(tape_dst, ctx->d_qtape.p, ctx->q_tape_len * 8, hipMemcpyDeviceToHost, ctx->stream), "D2H filtered tape");
-    if (ctx->q_strings_len && strings_dst)
-        HIPCHK(hipMemcpyAsync(strings_dst, ctx->d_qstrings.p, ctx->q_strings_len, hipMemcpyDeviceToHost, ctx->stream),
+    const ResultState::Filtered &f = ctx->res.filtered_sizes();
+    if (f.tape_len && tape_dst)
+        HIPCHK(hipMemcpyAsync(tape_dst, ctx->d_qtape.p, f.tape_len * 8, hipMemcpyDeviceToHost, ctx->stream), "D2H filtered tape");
+    if (f.strings_len && strings_dst)
+        HIPCHK(hipMemcpyAsync(strings_dst, ctx->d_qstrings.p, f.strings_len, hipMemcpyDeviceToHost, ctx->stream),
                "D2H filtered strings");
     HIPCHK(hipStreamSynchronize(ctx->stream), "fetch sync");
     return query_bounds_check(ctx);  // (debug build: the copy kernel of sjhip_filter_where has finished here)
@@ -1215,11 +1207,12 @@ int sjhip_extract_path_strings(sjhip_ctx *ctx, const uint8_t *keys, const uint32
     size_t klen = 0;
     int rc = make_path(ctx, keys, key_lens, n_keys, &pth, &klen);
     if (rc) return rc;
-    ctx->col_valid = 0;  // (the last column is replaced, whatever happens below)
+    ctx->res.begin_column();  // (the last column is replaced, whatever happens below)
     std::vector<sjhip_ctx *> parts;
     rc = query_parts(ctx, keys, klen, &NO_VALUE, 0, &parts);
     if (rc) return rc;
     std::vector<QCol> cols(parts.size());
+    std::vector<ResultState::Column> sizes(parts.size());
     auto tiles_of = [](uint32_t n) { return (n + 1u + QTILE - 1) / QTILE; };
     auto work = [&](Carve c, uint32_t n, QCol *col, unsigned long long **totals) {
         *totals = c.take<unsigned long long>(32);
@@ -1230,7 +1223,7 @@ int sjhip_extract_path_strings(sjhip_ctx *ctx, const uint8_t *keys, const uint32
         return c.used;
     };
     // lengths and their scan on every part, each on its own stream; then the totals
-    size_t total_records = 0, total_bytes = 0;
+    ResultState::Column total;
     rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, "column sync",
         [&](uint32_t n) {
             QCol c;
@@ -1250,62 +1243,60 @@ int sjhip_extract_path_strings(sjhip_ctx *ctx, const uint8_t *keys, const uint32
             HIPCHK(hipMemcpyAsync(part->h_scratch + 512, totals + 2, 8, hipMemcpyDeviceToHost, part->stream), "D2H column bytes");
             return SJHIP_OK;
         },
-        [&](size_t, sjhip_ctx *part) {
-            part->col_records = (size_t)part->q_records + 1u;
-            part->col_bytes = (size_t)*(const unsigned long long *)(part->h_scratch + 512);
-            total_records += part->col_records;
-            total_bytes += part->col_bytes;
+        [&](size_t k, sjhip_ctx *part) {
+            sizes[k] = {(size_t)part->q_records + 1u, (size_t)*(const unsigned long long *)(part->h_scratch + 512)};
+            total.records += sizes[k].records;
+            total.bytes += sizes[k].bytes;
         });
     if (rc) return rc;
     // the gather on every part, into the part's d_col (the work arrays stay where they are: nothing more of d_kat is asked for)
     rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, "column gather sync", [](uint32_t) { return (size_t)0; },
         [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
             ColOut o;
-            const int rc = arena_reserve(part, part->d_col, col_layout(Carve(), n, part->col_bytes, &o) + 64);
+            const int rc = arena_reserve(part, part->d_col, col_layout(Carve(), n, sizes[k].bytes, &o) + 64);
             if (rc) return rc;
-            (void)col_layout(Carve(part->d_col.p), n, part->col_bytes, &o);
+            (void)col_layout(Carve(part->d_col.p), n, sizes[k].bytes, &o);
             hipLaunchKernelGGL(k_q_col_gather, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, cols[k], o.off, o.status,
-                               SJ_ARR(o.data, part->col_bytes, A_COL));
+                               SJ_ARR(o.data, sizes[k].bytes, A_COL));
             HIPCHK(hipGetLastError(), "column gather launch");
             return SJHIP_OK;
         },
         [](size_t, sjhip_ctx *) {});  // (the work arrays in d_kat are free for the next query once this returns)
     if (rc) return rc;
-    *records = total_records;
-    *bytes = total_bytes;
-    ctx->col_valid = 1;
-    return SJHIP_OK;
+    *records = total.records;
+    *bytes = total.bytes;
+    bool ok = true;
+    for (size_t k = 0; k < parts.size(); k++) ok &= parts[k]->res.publish_column(sizes[k]);
+    if (ctx->res.sharded()) ok &= ctx->res.publish_column(total);
+    return published(ctx, ok);
 }
 
 int sjhip_fetch_path_strings(sjhip_ctx *ctx, uint64_t *offsets, uint8_t *data, uint8_t *status) {
     if (!ctx) return SJHIP_ERR_ARG;
-    if (!ctx->col_valid) {  // no column was built, or a parse (or sjhip_ctx_trim) came after it
+    if (!ctx->res.column()) {  // no column was built, or a parse (or sjhip_ctx_trim) came after it
         ctx_set_error(ctx, "no string column on the device (sjhip_fetch_path_strings follows sjhip_extract_path_strings, with no parse in between)");
         return SJHIP_ERR_ARG;
     }
     const std::vector<sjhip_ctx *> parts = result_parts(ctx);
-    size_t total_bytes = 0;
-    for (sjhip_ctx *part : parts) total_bytes += part->col_bytes;
-    if (!offsets || !status || (!data && total_bytes)) return SJHIP_ERR_ARG;
     std::vector<size_t> rec_at(parts.size() + 1, 0), byte_at(parts.size() + 1, 0);  // where every part's records and bytes start
     for (size_t k = 0; k < parts.size(); k++) {
-        rec_at[k + 1] = rec_at[k] + parts[k]->col_records;
-        byte_at[k + 1] = byte_at[k] + parts[k]->col_bytes;
+        rec_at[k + 1] = rec_at[k] + parts[k]->res.column_sizes().records;
+        byte_at[k + 1] = byte_at[k] + parts[k]->res.column_sizes().bytes;
     }
+    if (!offsets || !status || (!data && byte_at[parts.size()])) return SJHIP_ERR_ARG;
     const int rc = walk_parts(ctx, parts, "column fetch sync",
         [&](size_t k, sjhip_ctx *part) -> int {  // every part's offsets but its last (the next part's first, rebased below) + status + bytes
-            const size_t n = part->col_records;
+            const size_t n = part->res.column_sizes().records, nb = part->res.column_sizes().bytes;
             ColOut o;
-            (void)col_layout(Carve(part->d_col.p), n, part->col_bytes, &o);
+            (void)col_layout(Carve(part->d_col.p), n, nb, &o);
             HIPCHK(hipMemcpyAsync(offsets + rec_at[k], o.off, n * 8, hipMemcpyDeviceToHost, part->stream), "D2H column offsets");
             HIPCHK(hipMemcpyAsync(status + rec_at[k], o.status, n, hipMemcpyDeviceToHost, part->stream), "D2H column status");
-            if (part->col_bytes)
-                HIPCHK(hipMemcpyAsync(data + byte_at[k], o.data, part->col_bytes, hipMemcpyDeviceToHost, part->stream), "D2H column bytes");
+            if (nb) HIPCHK(hipMemcpyAsync(data + byte_at[k], o.data, nb, hipMemcpyDeviceToHost, part->stream), "D2H column bytes");
             return SJHIP_OK;
         },
-        [&](size_t k, sjhip_ctx *part) {
+        [&](size_t k, sjhip_ctx *) {
             if (byte_at[k])  // the offsets of a later shard: from the end of the shards in front of it
-                for (size_t i = rec_at[k]; i < rec_at[k] + part->col_records; i++) offsets[i] += byte_at[k];
+                for (size_t i = rec_at[k]; i < rec_at[k + 1]; i++) offsets[i] += byte_at[k];
         });
     if (rc) return rc;
     offsets[rec_at[parts.size()]] = byte_at[parts.size()];
@@ -1340,12 +1331,13 @@ static int list_extract(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key
     size_t klen = 0;
     int rc = make_path(ctx, keys, key_lens, n_keys, &pth, &klen);
     if (rc) return rc;
-    ctx->list_valid = 0;  // (the last list column is replaced, whatever happens below)
+    ctx->res.begin_list();  // (the last list column is replaced, whatever happens below)
     const bool strings = mode >= LIST_STR;
     std::vector<sjhip_ctx *> parts;
     rc = query_parts(ctx, keys, klen, &NO_VALUE, 0, &parts);
     if (rc) return rc;
     std::vector<QList> lists(parts.size());
+    std::vector<ResultState::ListColumn> sizes(parts.size());
     auto tiles_of = [](uint32_t n) { return (n + 1u + QTILE - 1) / QTILE; };
     auto work = [&](Carve c, uint32_t n, QList *l, unsigned long long **totals) {
         *totals = c.take<unsigned long long>(32);
@@ -1358,7 +1350,7 @@ static int list_extract(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key
         return c.used;
     };
     // the conversion check, the counts and their scans on every part, each on its own stream; then the totals
-    size_t total_records = 0, total_elems = 0, total_bytes = 0;
+    ResultState::ListColumn total;
     rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, "list column sync",
         [&](uint32_t n) {
             QList l;
@@ -1380,43 +1372,44 @@ static int list_extract(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key
             HIPCHK(hipMemcpyAsync(part->h_scratch + 512, totals, 16, hipMemcpyDeviceToHost, part->stream), "D2H list totals");
             return SJHIP_OK;
         },
-        [&](size_t, sjhip_ctx *part) {
+        [&](size_t k, sjhip_ctx *part) {
             const unsigned long long *h = (const unsigned long long *)(part->h_scratch + 512);
-            part->list_records = (size_t)part->q_records + 1u;
-            part->list_elems = (size_t)h[0];
-            part->list_bytes = strings ? (size_t)h[1] : 0;
-            total_records += part->list_records;
-            total_elems += part->list_elems;
-            total_bytes += part->list_bytes;
+            sizes[k] = {(size_t)part->q_records + 1u, (size_t)h[0], strings ? (size_t)h[1] : 0};
+            total.records += sizes[k].records;
+            total.elems += sizes[k].elems;
+            total.bytes += sizes[k].bytes;
         });
     if (rc) return rc;
     // the gather on every part, into the part's d_list (the work arrays stay where they are: nothing more of d_kat is asked for)
     rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, "list gather sync", [](uint32_t) { return (size_t)0; },
         [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
             ListOut o;
-            const int rc = arena_reserve(part, part->d_list, list_layout(Carve(), n, part->list_elems, part->list_bytes, strings, &o) + 64);
+            const size_t ne = sizes[k].elems, nb = sizes[k].bytes;
+            const int rc = arena_reserve(part, part->d_list, list_layout(Carve(), n, ne, nb, strings, &o) + 64);
             if (rc) return rc;
-            (void)list_layout(Carve(part->d_list.p), n, part->list_elems, part->list_bytes, strings, &o);
+            (void)list_layout(Carve(part->d_list.p), n, ne, nb, strings, &o);
             const dim3 grid((n + 255) / 256), block(256);
             if (!strings)
                 hipLaunchKernelGGL(k_q_list_gather_num, grid, block, 0, part->stream, q, lists[k], mode, o.off, o.status,
-                                   SJ_ARR(o.values, part->list_elems, A_LIST_VAL));
+                                   SJ_ARR(o.values, ne, A_LIST_VAL));
             else if (mode == LIST_STR)
                 hipLaunchKernelGGL(k_q_list_gather_str, grid, block, 0, part->stream, q, lists[k], o.off, o.status,
-                                   SJ_ARR(o.soff, part->list_elems + 1, A_LIST_SOFF), SJ_ARR(o.data, part->list_bytes, A_LIST_DATA));
+                                   SJ_ARR(o.soff, ne + 1, A_LIST_SOFF), SJ_ARR(o.data, nb, A_LIST_DATA));
             else
                 hipLaunchKernelGGL(k_q_list_gather_cvt, grid, block, 0, part->stream, q, lists[k], o.off, o.status,
-                                   SJ_ARR(o.soff, part->list_elems + 1, A_LIST_SOFF), SJ_ARR(o.data, part->list_bytes, A_LIST_DATA));
+                                   SJ_ARR(o.soff, ne + 1, A_LIST_SOFF), SJ_ARR(o.data, nb, A_LIST_DATA));
             HIPCHK(hipGetLastError(), "list gather launch");
             return SJHIP_OK;
         },
         [](size_t, sjhip_ctx *) {});
     if (rc) return rc;
-    *records = total_records;
-    *elems = total_elems;
-    if (bytes) *bytes = total_bytes;
-    ctx->list_valid = strings ? 2 : 1;
-    return SJHIP_OK;
+    *records = total.records;
+    *elems = total.elems;
+    if (bytes) *bytes = total.bytes;
+    bool ok = true;
+    for (size_t k = 0; k < parts.size(); k++) ok &= parts[k]->res.publish_list(strings, sizes[k]);
+    if (ctx->res.sharded()) ok &= ctx->res.publish_list(strings, total);
+    return published(ctx, ok);
 }
 
 int sjhip_extract_path_list(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int kind, size_t *records,
@@ -1437,7 +1430,7 @@ int sjhip_extract_path_list_strings(sjhip_ctx *ctx, const uint8_t *keys, const u
 // inner: the values (numbers) or the string offsets (strings) of the elements
 static int list_fetch(sjhip_ctx *ctx, bool strings, uint64_t *list_offsets, uint64_t *inner, uint8_t *data, uint8_t *status) {
     if (!ctx) return SJHIP_ERR_ARG;
-    if (ctx->list_valid != (strings ? 2 : 1)) {  // none was built, a parse (or sjhip_ctx_trim) came after it, or it is of the other kind
+    if (!ctx->res.list(strings)) {  // none was built, a parse (or sjhip_ctx_trim) came after it, or it is of the other kind
         ctx_set_error(ctx, "%s", NO_LIST);
         return SJHIP_ERR_ARG;
     }
@@ -1445,30 +1438,29 @@ static int list_fetch(sjhip_ctx *ctx, bool strings, uint64_t *list_offsets, uint
     const size_t P = parts.size();
     std::vector<size_t> rec_at(P + 1, 0), elem_at(P + 1, 0), byte_at(P + 1, 0);  // where every part's records, elements and bytes start
     for (size_t k = 0; k < P; k++) {
-        rec_at[k + 1] = rec_at[k] + parts[k]->list_records;
-        elem_at[k + 1] = elem_at[k] + parts[k]->list_elems;
-        byte_at[k + 1] = byte_at[k] + parts[k]->list_bytes;
+        rec_at[k + 1] = rec_at[k] + parts[k]->res.list_sizes().records;
+        elem_at[k + 1] = elem_at[k] + parts[k]->res.list_sizes().elems;
+        byte_at[k + 1] = byte_at[k] + parts[k]->res.list_sizes().bytes;
     }
     if (!list_offsets || !status || (!inner && (strings || elem_at[P])) || (strings && !data && byte_at[P])) return SJHIP_ERR_ARG;
     const int rc = walk_parts(ctx, parts, "list fetch sync",
         [&](size_t k, sjhip_ctx *part) -> int {  // every part's offsets but their last (the next part's first, rebased below)
-            const size_t n = part->list_records, ne = part->list_elems;
+            const size_t n = part->res.list_sizes().records, ne = part->res.list_sizes().elems, nb = part->res.list_sizes().bytes;
             ListOut o;
-            (void)list_layout(Carve(part->d_list.p), n, ne, part->list_bytes, strings, &o);
+            (void)list_layout(Carve(part->d_list.p), n, ne, nb, strings, &o);
             HIPCHK(hipMemcpyAsync(list_offsets + rec_at[k], o.off, n * 8, hipMemcpyDeviceToHost, part->stream), "D2H list offsets");
             HIPCHK(hipMemcpyAsync(status + rec_at[k], o.status, n, hipMemcpyDeviceToHost, part->stream), "D2H list status");
             if (ne)
                 HIPCHK(hipMemcpyAsync(inner + elem_at[k], strings ? o.soff : o.values, ne * 8, hipMemcpyDeviceToHost, part->stream),
                        "D2H list elements");
-            if (part->list_bytes)
-                HIPCHK(hipMemcpyAsync(data + byte_at[k], o.data, part->list_bytes, hipMemcpyDeviceToHost, part->stream), "D2H list bytes");
+            if (nb) HIPCHK(hipMemcpyAsync(data + byte_at[k], o.data, nb, hipMemcpyDeviceToHost, part->stream), "D2H list bytes");
             return SJHIP_OK;
         },
-        [&](size_t k, sjhip_ctx *part) {  // the offsets of a later shard: from the end of the shards in front of it
+        [&](size_t k, sjhip_ctx *) {  // the offsets of a later shard: from the end of the shards in front of it
             if (elem_at[k])
-                for (size_t i = rec_at[k]; i < rec_at[k] + part->list_records; i++) list_offsets[i] += elem_at[k];
+                for (size_t i = rec_at[k]; i < rec_at[k + 1]; i++) list_offsets[i] += elem_at[k];
             if (strings && byte_at[k])
-                for (size_t i = elem_at[k]; i < elem_at[k] + part->list_elems; i++) inner[i] += byte_at[k];
+                for (size_t i = elem_at[k]; i < elem_at[k + 1]; i++) inner[i] += byte_at[k];
         });
     if (rc) return rc;
     list_offsets[rec_at[P]] = elem_at[P];

@@ -248,18 +248,15 @@ size_t put_uvarint(uint8_t *dst, uint64_t v) {
 
 int sjhip_serialize_ex(sjhip_ctx *ctx, uint32_t flags, size_t *tags_len, size_t *values_len, size_t *strings_len, size_t *stream_len) {
     if (!ctx) return SJHIP_ERR_ARG;
-    ctx->ser_valid = 0;
-    ctx->ms_valid = 0;
-    if (!ctx->q_valid || ctx->tape_len == 0) {
-        if (ctx->big_valid) ctx_set_error(ctx, "sjhip_serialize works on the result of one context; this ND result was parsed shard by shard");
-        else ctx_set_error(ctx, "no parse result on the device (sjhip_serialize follows a successful sjhip_parse / sjhip_parse_device)");
-        return SJHIP_ERR_ARG;
-    }
+    ctx->res.release_shared(ResultState::Tenant::Serialized);
+    ctx->res.release_shared(ResultState::Tenant::Marshaled);
+    if (!ctx->res.whole()) return no_whole_result(ctx, "sjhip_serialize", "sjhip_serialize follows");
     if (!(ctx->p_flags & SJHIP_FLAG_COPY_STRINGS)) {
         ctx_set_error(ctx, "sjhip_serialize needs a parse with SJHIP_FLAG_COPY_STRINGS (Strings.B is the string column)");
         return SJHIP_ERR_ARG;
     }
     HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    ctx->res.claim_shared();  // (the filter and MarshalJSON use the same arenas)
     const bool dedup = (flags & SJHIP_SER_DEDUP) != 0;
     SerView p;
     p.tape = (const u64 *)ctx->d_tape.p;
@@ -329,25 +326,23 @@ int sjhip_serialize_ex(sjhip_ctx *ctx, uint32_t flags, size_t *tags_len, size_t 
         }
     }
 #endif
-    ctx->ser_tags = (size_t)h[0];
-    ctx->ser_vals = (size_t)h[1];
-    ctx->ser_dedup = dedup;
-    ctx->ser_slen = dedup ? (size_t)h[2] : ctx->strings_len;
-    ctx->ser_valid = 1;
-    ctx->q_tape_len = ctx->q_strings_len = 0;  // the filter result shared these arenas
-    ctx->f_valid = 0;
+    ResultState::Serialized z;
+    z.tags = (size_t)h[0];
+    z.vals = (size_t)h[1];
+    z.dedup = dedup;
+    z.slen = dedup ? (size_t)h[2] : ctx->strings_len;
     // size of the framed stream (parsed_serialize.go:381-426)
     uint8_t tmp[16];
-    const size_t sl = ctx->ser_slen;
-    size_t rest = put_uvarint(tmp, ctx->tape_len) + 2 + put_uvarint(tmp, sl) + put_uvarint(tmp, sl + 1) + 1 + sl +
-                  put_uvarint(tmp, ctx->ser_tags) + put_uvarint(tmp, ctx->ser_tags + 1) + 1 + ctx->ser_tags +
-                  put_uvarint(tmp, ctx->ser_vals) + put_uvarint(tmp, ctx->ser_vals + 1) + 1 + ctx->ser_vals;
-    ctx->ser_rest = rest;
-    ctx->ser_stream = 1 + put_uvarint(tmp, rest) + rest;
-    if (tags_len) *tags_len = ctx->ser_tags;
-    if (values_len) *values_len = ctx->ser_vals;
-    if (strings_len) *strings_len = sl;
-    if (stream_len) *stream_len = ctx->ser_stream;
+    z.rest = put_uvarint(tmp, ctx->tape_len) + 2 + put_uvarint(tmp, z.slen) + put_uvarint(tmp, z.slen + 1) + 1 + z.slen +
+             put_uvarint(tmp, z.tags) + put_uvarint(tmp, z.tags + 1) + 1 + z.tags +
+             put_uvarint(tmp, z.vals) + put_uvarint(tmp, z.vals + 1) + 1 + z.vals;
+    z.stream = 1 + put_uvarint(tmp, z.rest) + z.rest;
+    rc = published(ctx, ctx->res.publish_serialized(z));
+    if (rc) return rc;
+    if (tags_len) *tags_len = z.tags;
+    if (values_len) *values_len = z.vals;
+    if (strings_len) *strings_len = z.slen;
+    if (stream_len) *stream_len = z.stream;
     return SJHIP_OK;
 }
 
@@ -357,16 +352,17 @@ int sjhip_serialize(sjhip_ctx *ctx, size_t *tags_len, size_t *values_len, size_t
 
 int sjhip_fetch_serialized(sjhip_ctx *ctx, uint8_t *dst, size_t cap, size_t *len) {
     if (!ctx || !dst) return SJHIP_ERR_ARG;
-    if (!ctx->ser_valid || cap < ctx->ser_stream) {
-        ctx_set_error(ctx, "sjhip_fetch_serialized: no serialized result, or destination smaller than %zu bytes", ctx->ser_stream);
+    const ResultState::Serialized &z = ctx->res.serialized_sizes();
+    if (!ctx->res.serialized() || cap < z.stream) {
+        ctx_set_error(ctx, "sjhip_fetch_serialized: no serialized result, or destination smaller than %zu bytes", z.stream);
         return SJHIP_ERR_ARG;
     }
     HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
-    const size_t sl = ctx->ser_slen, tl = ctx->ser_tags, vl = ctx->ser_vals;
-    const void *scol = ctx->ser_dedup ? ctx->d_scol.p : ctx->d_strings.p;
+    const size_t sl = z.slen, tl = z.tags, vl = z.vals;
+    const void *scol = z.dedup ? ctx->d_scol.p : ctx->d_strings.p;
     size_t o = 0;
     dst[o++] = 3;  // serializedVersion
-    const size_t rest = ctx->ser_rest;  // the size field covers everything behind it
+    const size_t rest = z.rest;  // the size field covers everything behind it
     o += put_uvarint(dst + o, rest);
     o += put_uvarint(dst + o, ctx->tape_len);
     dst[o++] = 0;  // Strings: uncompressed size 0
@@ -388,8 +384,8 @@ int sjhip_fetch_serialized(sjhip_ctx *ctx, uint8_t *dst, size_t cap, size_t *len
     o += vl;
     HIPCHK(hipStreamSynchronize(ctx->stream), "fetch sync");
     if (len) *len = o;
-    if (o != ctx->ser_stream) {
-        ctx_set_error(ctx, "serialized stream: %zu bytes written, %zu announced", o, ctx->ser_stream);
+    if (o != z.stream) {
+        ctx_set_error(ctx, "serialized stream: %zu bytes written, %zu announced", o, z.stream);
         return SJHIP_ERR_HIP;
     }
     return SJHIP_OK;
@@ -562,9 +558,7 @@ bool get_block(const uint8_t *src, size_t len, size_t *o, uint64_t *size, size_t
 
 int sjhip_deserialize(sjhip_ctx *ctx, const uint8_t *stream, size_t len, size_t *tape_len, size_t *strings_len, size_t *message_len) {
     if (!ctx || !stream) return SJHIP_ERR_ARG;
-    ctx->q_valid = ctx->r_valid = ctx->ser_valid = ctx->ms_valid = ctx->f_valid = ctx->kf_valid = ctx->col_valid = ctx->list_valid = 0;
-    ctx->pending = 0;
-    ctx->pack_valid = 0;
+    ctx->res.drop_result();  // (the tape and Strings.B below are what sjhip_fetch copies, nothing else works on them)
     ctx->tape_len = ctx->strings_len = 0;
     ctx->des_msg_len = 0;
     auto corrupt = [&](const char *what) {

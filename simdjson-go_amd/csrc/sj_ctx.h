@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "sj_device.h"
+#include "sj_result.h"
 
 namespace sj {
 struct DevBuf {
@@ -24,9 +25,7 @@ struct sjhip_ctx {
     uint8_t *h_scratch = nullptr;      // 4 KiB pinned: state read-backs
     // small documents parsed from a host buffer (sjhip_parse): the last kernel of the chain also writes the stage-2 state,
     // the tape and Strings.B into this pinned block (over PCIe, no copy commands), and sjhip_fetch is two memcpy
-    uint8_t *h_pack = nullptr;
-    int want_pack = 0;                 // set by sjhip_parse for the parse it starts
-    int pack_valid = 0;                // h_pack holds the result of the last parse
+    uint8_t *h_pack = nullptr;         // (res.packed(): it holds the result of the last parse)
     uint8_t *h_view = nullptr;         // sjhip_fetch_view of results that did not travel with the last launch (grows)
     size_t h_view_cap = 0;
     uint8_t *h_in = nullptr;           // sjhip_input_block: pinned block the caller reads its input into
@@ -34,36 +33,22 @@ struct sjhip_ctx {
     uint8_t *h_stage = nullptr;        // pinned staging of sjhip_parse_batch: runs of small documents travel as one copy
     size_t h_stage_cap = 0;
     sj::DevBuf d_msg, d_pos, d_ws, d_kat, d_tape, d_strings, d_s2, d_s2z, d_aux;
-    sj::DevBuf d_keyflag;              // SJHIP_FLAG_KEY_FLAGS: key flags of the string entries, for marshal.hip
-    int kf_valid = 0;                  // ... and they belong to the resident result
+    sj::DevBuf d_keyflag;              // SJHIP_FLAG_KEY_FLAGS: key flags of the string entries, for marshal.hip (res.key_flags())
     sj::DevBuf d_scol, d_stab;         // serializer with de-duplication: the string column, the hash table
-    sj::DevBuf d_q, d_qtape, d_qstrings;  // queries over the last result (query.hip): work arrays, filtered tape / Strings.B
+    // shared by the filter (query.hip: work arrays, filtered tape / Strings.B), the serializer and MarshalJSON: res says whose they are
+    sj::DevBuf d_q, d_qtape, d_qstrings;
     sj::DevBuf d_col;                  // the string column of the last sjhip_extract_path_strings (query.hip): offsets, status, bytes
     sj::DevBuf d_list;                 // the list column of the last sjhip_extract_path_list[_strings] (query.hip), apart from d_col
     unsigned ws_clean_gen = 0;         // d_ws.gen of the allocation that has been zeroed for stage 1 (0: none; stage1_enqueue)
     sj::S1Ws s1ws;                     // ... and its launch count (sj_device.h: a launch cleans up for the next one)
     unsigned s1_par = 0;               // control slot of the last stage-1 launch (Stage1State::c[]: stage 2 reads has_starter there)
     sj::Stage1State s1;                // last stage-1 state (host copy)
-    // last parse (kept on the device until sjhip_fetch)
+    // the tape and Strings.B in d_tape / d_strings (what sjhip_fetch copies): of the last parse, or of the last sjhip_deserialize
     size_t tape_len = 0, strings_len = 0;
-    int q_valid = 0;              // the device holds the whole result of an unsharded parse: queries are possible
-    int r_valid = 0;              // the device holds the result of a parse -- whole, or one shard of a sharded ParseND whose stored
-    uint64_t r_tape_base = 0, r_strings_base = 0, r_msg_base = 0;  // indices carry these bases (query.hip works in the merged index space)
+    sj::ResultState res;          // what the device holds of the last parse and of the products derived from it (sj_result.h)
     uint32_t q_records = 0;       // record-separating newline runs of that parse (records - 1)
-    size_t q_tape_len = 0, q_strings_len = 0;  // last sjhip_filter_where
-    int f_valid = 0;              // a filtered result is resident (sjhip_fetch_filtered)
-    int col_valid = 0;            // a string column of the resident result is in d_col (of this context, or of its shards)
-    size_t col_records = 0, col_bytes = 0;  // ... its records and bytes (of this context's part of the result)
-    int list_valid = 0;           // a list column of the resident result is in d_list (of this context, or of its shards): 1 numbers, 2 strings
-    size_t list_records = 0, list_elems = 0, list_bytes = 0;  // ... its records, elements and string bytes (this context's part)
-    int ser_valid = 0;            // last sjhip_serialize (serialize.hip): column sizes, framed stream size
-    size_t ser_tags = 0, ser_vals = 0, ser_rest = 0, ser_stream = 0, ser_slen = 0;
-    int ser_dedup = 0;
     size_t des_msg_len = 0;       // last sjhip_deserialize: length of pj.Message (in d_msg)
-    int ms_valid = 0;             // last sjhip_marshal_json (marshal.hip): the text is in d_qtape
-    size_t ms_len = 0;
-    // a parse between its two phases (sjhip_parse_shard_begin / _finish)
-    int pending = 0;
+    // a parse between its two phases (sjhip_parse_shard_begin / _finish: res.pending())
     int p_deferred = 0;   // stage 1's result has not been collected yet (small documents: one synchronisation per parse)
     int p_collected = 0;  // ... but a shard's phase 1 has: its sizes and stage 1's verdict arrive with one synchronisation (parse_begin)
     int p_no_defer = 0;   // the deferred run met more tokens than its layout holds: this parse takes the synchronous path
@@ -81,8 +66,7 @@ struct sjhip_ctx {
     uint8_t *p_kind = nullptr;  // token kinds of the pending parse (behind the positions in d_pos)
     // an ND message beyond 4 GiB - 64 is parsed shard by shard by a multi handle the context owns (multi_api.hip
     // parse_nd_big); the merged result waits there for sjhip_fetch
-    struct sjhip_multi *big = nullptr;
-    int big_valid = 0;
+    struct sjhip_multi *big = nullptr;  // (res.sharded(): it holds the last result)
     char err[256];
 };
 
@@ -92,6 +76,17 @@ namespace sj {
 // write results straight into it: the stage-1 verdict word, k_pack, the batch end check).
 inline hipError_t pinned_alloc(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocPortable | hipHostMallocMapped); }
 void ctx_set_error(sjhip_ctx *ctx, const char *fmt, ...);
+// SJHIP_ERR_ARG of a call that needs a parse result on the device and finds none (`follows`: "queries follow", "sjhip_x follows")
+int no_result(sjhip_ctx *ctx, const char *follows);
+// ... and of one that works on the whole result of one context (the filter, the serializer): a sharded result has its own text
+int no_whole_result(sjhip_ctx *ctx, const char *call, const char *follows);
+// the return code of a call that has just published a product: an internal error if there was no result to publish it on
+int published(sjhip_ctx *ctx, bool ok);
+// a parse entry point, before anything that can return: the last result and everything derived from it are gone
+inline void begin_parse(sjhip_ctx *ctx) {
+    ctx->res.begin_parse();
+    ctx->tape_len = ctx->strings_len = 0;
+}
 int ctx_hip_fail(sjhip_ctx *ctx, hipError_t e, const char *what);
 int arena_reserve(sjhip_ctx *ctx, DevBuf &b, size_t bytes);
 // a failed HIP call ends the calling function with the error left in `ctx` (the name in scope at the call)

@@ -1,0 +1,138 @@
+// sj_result.h -- what a context knows about the device-resident result of its last parse and the products derived from it.
+// Plain C++ (no HIP): host_selftest.cpp replays the transitions on the CPU (tests/test_result_state.py).
+//
+// Three facts, each written only by the transitions below (the host files call them and ask the predicates):
+//   * what the last parse left: nothing, a parse between its two phases, a whole result, one shard of a sharded ParseND (its stored
+//     indices carry the three bases), or "my shards hold it" (an ND message beyond one context's reach, multi_api.hip parse_nd_big);
+//     beside it, whether the key flags in d_keyflag belong to it and whether h_pack mirrors it;
+//   * the tenant of the shared arenas d_q / d_qtape / d_qstrings: the filtered result, the serialized columns or the MarshalJSON text
+//     -- one value, so at most one of them is resident;
+//   * the string column (d_col) and the list column (d_list, numbers or strings), independent of each other and of the tenant.
+// The rule: a parse call, successful or not, drops the previous result and everything derived from it (begin_parse); so do
+// sjhip_deserialize, sjhip_ctx_trim and the stage-1-only calls (drop_result).  A product exists from its publish to the next
+// transition that drops it; a product is only published on a resident result, and a result of no tape words is no result.
+// Every context keeps its own state: the owner of a sharded result holds `sharded`, the joined sizes and the "exists" bits, each
+// shard context holds its own part.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace sj {
+
+class ResultState {
+public:
+    enum class Tenant : uint8_t { None, Filtered, Serialized, Marshaled };
+    enum class List : uint8_t { None, Numbers, Strings };
+    struct Filtered { size_t tape_len = 0, strings_len = 0; };
+    struct Serialized { size_t tags = 0, vals = 0, slen = 0, rest = 0, stream = 0; bool dedup = false; };  // column sizes, framed stream
+    struct Column { size_t records = 0, bytes = 0; };
+    struct ListColumn { size_t records = 0, elems = 0, bytes = 0; };
+
+    // ---- transitions ----
+    // Every parse entry point, first: nothing of the last result is left.  (The sizes stay: they mean something under their flag only.)
+    void begin_parse() {
+        parse_ = Parse::None;
+        key_flags_ = packed_ = column_ = false;
+        tenant_ = Tenant::None;
+        list_ = List::None;
+    }
+    void drop_result() { begin_parse(); }  // the arenas of the result are re-used, freed or overwritten by something that is no parse
+    void parse_pending() {  // phase 1 of a parse is queued
+        begin_parse();
+        parse_ = Parse::Pending;
+    }
+    // Phase 2 succeeded.  A result whose stored indices carry no bases is a whole one (the first shard of a sharded parse as well);
+    // `packed`: the last launch also left it in h_pack (whole results only)
+    void parse_done(uint64_t tape_base, uint64_t strings_base, uint64_t msg_base, size_t tape_len, bool key_flags, bool packed) {
+        begin_parse();
+        if (tape_len == 0) return;
+        const bool whole = tape_base == 0 && strings_base == 0 && msg_base == 0;
+        parse_ = whole ? Parse::Whole : Parse::Shard;
+        tape_base_ = tape_base;
+        strings_base_ = strings_base;
+        msg_base_ = msg_base;
+        key_flags_ = key_flags;
+        packed_ = packed && whole;
+    }
+    void parse_sharded(size_t tape_len) {  // the shard contexts of this one hold the result
+        begin_parse();
+        if (tape_len) parse_ = Parse::Sharded;
+    }
+    // The shared arenas: a call gives up its own product before its checks (release_shared), claims the arenas before its first
+    // write (the previous tenant is gone, whatever happens next) and publishes on success.  A publish without a result to publish
+    // on changes nothing and says so: the caller made a mistake (sj_ctx.h published()).
+    void release_shared(Tenant t) {
+        if (tenant_ == t) tenant_ = Tenant::None;
+    }
+    void claim_shared() { tenant_ = Tenant::None; }
+    bool publish_filtered(const Filtered &f) {
+        if (!whole()) return false;
+        tenant_ = Tenant::Filtered;
+        filtered_ = f;
+        return true;
+    }
+    bool publish_serialized(const Serialized &s) {
+        if (!whole()) return false;
+        tenant_ = Tenant::Serialized;
+        serialized_ = s;
+        return true;
+    }
+    bool publish_marshaled(size_t text_len) {  // (an owner: the joined length of its shards' texts)
+        if (!resident() && !sharded()) return false;
+        tenant_ = Tenant::Marshaled;
+        marshaled_len_ = text_len;
+        return true;
+    }
+    void begin_column() { column_ = false; }
+    bool publish_column(const Column &c) {  // (an owner: the totals of its shards' columns)
+        if (!resident() && !sharded()) return false;
+        column_ = true;
+        column_sizes_ = c;
+        return true;
+    }
+    void begin_list() { list_ = List::None; }
+    bool publish_list(bool strings, const ListColumn &l) {
+        if (!resident() && !sharded()) return false;
+        list_ = strings ? List::Strings : List::Numbers;
+        list_sizes_ = l;
+        return true;
+    }
+
+    // ---- predicates ----
+    bool pending() const { return parse_ == Parse::Pending; }
+    bool whole() const { return parse_ == Parse::Whole; }                        // filter / serializer work on these
+    bool resident() const { return whole() || parse_ == Parse::Shard; }          // path / count queries, MarshalJSON: a shard as well
+    bool sharded() const { return parse_ == Parse::Sharded; }
+    bool key_flags() const { return key_flags_; }
+    bool packed() const { return packed_; }
+    bool filtered() const { return tenant_ == Tenant::Filtered; }
+    bool serialized() const { return tenant_ == Tenant::Serialized; }
+    bool marshaled() const { return tenant_ == Tenant::Marshaled; }
+    bool column() const { return column_; }
+    bool list(bool strings) const { return list_ == (strings ? List::Strings : List::Numbers); }
+
+    // ---- what the last publish / parse_done left (meaningful while the predicate beside it holds) ----
+    uint64_t tape_base() const { return tape_base_; }
+    uint64_t strings_base() const { return strings_base_; }
+    uint64_t msg_base() const { return msg_base_; }
+    const Filtered &filtered_sizes() const { return filtered_; }
+    const Serialized &serialized_sizes() const { return serialized_; }
+    size_t marshaled_len() const { return marshaled_len_; }
+    const Column &column_sizes() const { return column_sizes_; }
+    const ListColumn &list_sizes() const { return list_sizes_; }
+
+private:
+    enum class Parse : uint8_t { None, Pending, Whole, Shard, Sharded };
+    Parse parse_ = Parse::None;
+    bool key_flags_ = false, packed_ = false, column_ = false;
+    Tenant tenant_ = Tenant::None;
+    List list_ = List::None;
+    uint64_t tape_base_ = 0, strings_base_ = 0, msg_base_ = 0;
+    Filtered filtered_;
+    Serialized serialized_;
+    size_t marshaled_len_ = 0;
+    Column column_sizes_;
+    ListColumn list_sizes_;
+};
+
+}  // namespace sj
