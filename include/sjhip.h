@@ -267,6 +267,36 @@ int sjhip_fetch_path_list(sjhip_ctx *ctx, uint64_t *list_offsets, void *values, 
 int sjhip_extract_path_list_strings(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, uint32_t flags,
                                     size_t *records, size_t *elems, size_t *bytes);
 int sjhip_fetch_path_list_strings(sjhip_ctx *ctx, uint64_t *list_offsets, uint64_t *str_offsets, uint8_t *data, uint8_t *status);
+/* Tables: columns at SEVERAL paths from ONE walk of every record.  The single-column calls above walk every record from its root
+ * once per call, and the walk is what they cost; a table of n columns -- each a path and a kind -- is evaluated together: the
+ * paths' keys form a trie, every member of a record is compared once with the keys that may follow where the walk stands, and
+ * the values are converted on the device and kept there until they are fetched column by column.
+ *   sjhip_extract_table       `keys` holds the keys of all paths end to end; column c owns the next path_lens[c] entries of
+ *                          key_lens.  kinds[c] = SJHIP_COL_FLOAT / INT / UINT / BOOL, SJHIP_COL_STRING (Iter.StringBytes) or
+ *                          SJHIP_COL_STRING_CVT (Iter.StringCvt).  *records = the records; bytes[c] = the text length of a string
+ *                          column, 0 for a numeric or bool column.
+ *   sjhip_fetch_table_column  a numeric or bool column: values[records] (8 bytes each, 1 byte for BOOL) and status[records];
+ *                          offsets and data are ignored and may be NULL.  A string column: offsets[records + 1], data[bytes[col]]
+ *                          and status[records]; values is ignored.
+ * Column c is exactly what sjhip_extract_path(path c, kind c) returns, or sjhip_extract_path_strings(path c) followed by
+ * sjhip_fetch_path_strings: the same values bit for bit, the same status bytes, offsets and bytes, the same conventions (value 0
+ * where the status is not OK, an empty slot for a string record that is not OK, the amd64 results at 2^63 and 2^64).  FindElement's
+ * rules hold for every column: into the root and into objects, not into arrays; the first member with the key wins at every level
+ * and nothing is taken back -- if the first "a" is not an object, a.b is NOT_OBJECT even if a later "a" is one; if it is an object
+ * without "b", a.b is NOT_FOUND.  Two columns may name the same path with different kinds, and one path may be the beginning of
+ * another.  Limits: 1 to SJHIP_TABLE_MAX_COLS columns, 1 to 16 keys per path, at most 32 keys and 1024 bytes in all paths together;
+ * beyond them, for an unknown kind and for an empty path: SJHIP_ERR_ARG, and sjhip_last_error names which.
+ * The table lives in device arenas of its own: it survives the string column, the list column, the filter, the serializer,
+ * MarshalJSON and the other queries, and they survive it; it lasts until the next parse or the next sjhip_extract_table of the
+ * context (sjhip_ctx_device_bytes counts it, sjhip_ctx_trim frees it).  A fetch without a table, or of a column the table does not
+ * have, is SJHIP_ERR_ARG and sjhip_last_error says which.  On a sharded ND result every shard builds its table and the fetch
+ * joins the column (string offsets rebased by the bytes in front).  SJHIP_COL_STRING / _STRING_CVT are kinds of table columns
+ * only: sjhip_extract_path and sjhip_extract_path_list refuse them. */
+#define SJHIP_TABLE_MAX_COLS 16
+enum { SJHIP_COL_STRING = 4, SJHIP_COL_STRING_CVT = 5 };
+int sjhip_extract_table(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, const uint32_t *path_lens, const int *kinds,
+                        uint32_t n_cols, size_t *records, size_t *bytes /* [n_cols] */);
+int sjhip_fetch_table_column(sjhip_ctx *ctx, uint32_t col, void *values, uint64_t *offsets, uint8_t *data, uint8_t *status);
 
 /* ---- Serializer.Serialize on the device (parsed_serialize.go:200-431, format version 3) -----------------------------
  * Splits the device-resident tape of the last parse (SJHIP_FLAG_COPY_STRINGS) into the reference's three columns --

@@ -98,7 +98,7 @@ sjhip_ctx *sjhip_ctx_create(int device) {
 #define SJ_CTX_ARENAS(ctx)                                                                                                   \
     {&(ctx)->d_msg, &(ctx)->d_pos, &(ctx)->d_ws, &(ctx)->d_kat, &(ctx)->d_tape, &(ctx)->d_strings, &(ctx)->d_s2, &(ctx)->d_s2z, \
      &(ctx)->d_aux, &(ctx)->d_scol, &(ctx)->d_stab, &(ctx)->d_q, &(ctx)->d_qtape, &(ctx)->d_qstrings,       \
-     &(ctx)->d_keyflag, &(ctx)->d_col, &(ctx)->d_list}
+     &(ctx)->d_keyflag, &(ctx)->d_col, &(ctx)->d_list, &(ctx)->d_table, &(ctx)->d_tabledata}
 
 size_t sjhip_ctx_device_bytes(const sjhip_ctx *ctx) {
     if (!ctx) return 0;
@@ -208,6 +208,7 @@ static void stage1_only(sjhip_ctx *ctx) {
     ctx->res.claim_shared();
     ctx->res.begin_column();
     ctx->res.begin_list();
+    ctx->res.begin_table();
 }
 
 // stage 1 in two halves: enqueue (workspace, launch; the last block of the kernel leaves the packed result -- count,

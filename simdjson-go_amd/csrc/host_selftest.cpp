@@ -796,9 +796,9 @@ extern "C" int sj_selftest_newlines_to_cr(void) {
 //   0 begin_parse   1 drop_result   2 parse_pending   3 + 4 * shard + 2 * key_flags + packed: parse_done of one tape word
 //   11 parse_done of an empty tape   12 parse_sharded   13 claim_shared   14 / 15 / 16 publish filtered / serialized / marshaled
 //   17 begin_column   18 publish_column   19 begin_list   20 / 21 publish_list numbers / strings
-//   22 / 23 / 24 release_shared of the filtered / serialized / marshaled tenant
+//   22 / 23 / 24 release_shared of the filtered / serialized / marshaled tenant   25 begin_table   26 publish_table
 // bits: 0 pending, 1 whole, 2 resident, 3 sharded, 4 key_flags, 5 packed, 6 filtered, 7 serialized, 8 marshaled, 9 column,
-// 10 list of numbers, 11 list of strings.  Returns 0, or 1 + the index of an unknown code.
+// 10 list of numbers, 11 list of strings, 12 table.  Returns 0, or 1 + the index of an unknown code.
 #include "sj_result.h"
 extern "C" int sj_selftest_result_state(const uint8_t *ops, size_t n, uint32_t *bits_out) {
     sj::ResultState s;
@@ -819,11 +819,80 @@ extern "C" int sj_selftest_result_state(const uint8_t *ops, size_t n, uint32_t *
         else if (op == 19) s.begin_list();
         else if (op == 20 || op == 21) s.publish_list(op == 21, {1, 1, 1});
         else if (op <= 24) s.release_shared(op == 22 ? sj::ResultState::Tenant::Filtered : op == 23 ? sj::ResultState::Tenant::Serialized : sj::ResultState::Tenant::Marshaled);
+        else if (op == 25) s.begin_table();
+        else if (op == 26) s.publish_table({});
         else return 1 + (int)k;
         bits_out[k] = (uint32_t)s.pending() | (uint32_t)s.whole() << 1 | (uint32_t)s.resident() << 2 | (uint32_t)s.sharded() << 3 |
                       (uint32_t)s.key_flags() << 4 | (uint32_t)s.packed() << 5 | (uint32_t)s.filtered() << 6 |
                       (uint32_t)s.serialized() << 7 | (uint32_t)s.marshaled() << 8 | (uint32_t)s.column() << 9 |
-                      (uint32_t)s.list(false) << 10 | (uint32_t)s.list(true) << 11;
+                      (uint32_t)s.list(false) << 10 | (uint32_t)s.list(true) << 11 | (uint32_t)s.table() << 12;
     }
+    return 0;
+}
+
+// sj_table.h / sj_tablewalk.h: the plan of a table and its one-walk evaluation, as the kernel k_q_table_walk runs them.
+//   sj_selftest_table_plan  -> 0 and the plan: nodes_out[j * 6 ..] = key begin, key end (in blob_out), parent (255: the root),
+//                           first child, children, columns mask of node j; or the TablePlanError of a refused table
+//   sj_selftest_table_walk  out[r * n_cols + c] = tape index / SJHIP_PATH_NOT_* of column c in record r of the tape
+#include "sj_tablewalk.h"
+extern "C" int sj_selftest_table_plan(const uint8_t *keys, const uint32_t *key_lens, const uint32_t *path_lens, const int *kinds,
+                                      uint32_t n_cols, uint32_t *n_nodes, uint32_t *root_n, uint32_t *nodes_out, uint8_t *blob_out) {
+    sj::TablePlan pl;
+    uint32_t blob_len = 0, bad = 0;
+    const int rc = sj::table_plan(keys, key_lens, path_lens, kinds, n_cols, &pl, blob_out, &blob_len, &bad);
+    if (rc) return rc;
+    *n_nodes = pl.n_nodes;
+    *root_n = pl.root_n;
+    for (uint32_t j = 0; j < pl.n_nodes; j++) {
+        uint32_t *o = nodes_out + 6 * j;
+        o[0] = j ? pl.key_end[j - 1] : 0;
+        o[1] = pl.key_end[j];
+        o[2] = pl.parent[j];
+        o[3] = pl.child_b[j];
+        o[4] = pl.child_n[j];
+        o[5] = pl.cols[j];
+    }
+    return 0;
+}
+namespace {
+struct HostTableView {
+    const uint64_t *tape;
+    const uint8_t *strings, *msg, *key;
+    uint64_t word(uint64_t i) const { return tape[i]; }
+    bool key_equals(uint64_t kw, uint64_t kl, uint32_t key_b, uint32_t key_n) const {
+        if (kl != key_n) return false;
+        const uint64_t p = kw & 0x00ffffffffffffffull;
+        const uint8_t *s = (p & STRINGBUFBIT) ? strings + (p & (STRINGBUFBIT - 1)) : msg + p;
+        return key_n == 0 || memcmp(s, key + key_b, key_n) == 0;
+    }
+};
+struct HostTableSink {
+    uint64_t *row;
+    uint32_t *seen;
+    void operator()(uint32_t c, uint64_t v) {
+        row[c] = v;
+        seen[c]++;
+    }
+};
+}  // namespace
+extern "C" int sj_selftest_table_walk(const uint64_t *tape, size_t tape_len, const uint8_t *strings, const uint8_t *msg,
+                                      const uint8_t *keys, const uint32_t *key_lens, const uint32_t *path_lens, const int *kinds,
+                                      uint32_t n_cols, uint64_t *out, size_t cap_records, size_t *records) {
+    sj::TablePlan pl;
+    uint8_t blob[sj::TABLE_MAX_BYTES];
+    uint32_t blob_len = 0, bad = 0;
+    const int rc = sj::table_plan(keys, key_lens, path_lens, kinds, n_cols, &pl, blob, &blob_len, &bad);
+    if (rc) return rc;
+    const HostTableView view = {tape, strings, msg, blob};
+    size_t r = 0;
+    for (uint64_t open = 0; open < tape_len; open = tape[open] & 0x00ffffffffffffffull, r++) {
+        if (r >= cap_records) continue;  // (counted, not written)
+        uint32_t stack[sj::TABLE_STACK_WORDS], seen[sj::TABLE_MAX_COLS] = {};
+        HostTableSink sink = {out + r * n_cols, seen};
+        sj::table_walk(view, pl, open, stack, 1, sink);
+        for (uint32_t c = 0; c < n_cols; c++)
+            if (seen[c] != 1) return -1;  // every column is answered exactly once
+    }
+    *records = r;
     return 0;
 }

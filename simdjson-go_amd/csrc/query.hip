@@ -23,6 +23,7 @@
 #include "sj_ftoa.h"
 #include "sj_stage2.h"
 #include "sj_tapewalk.h"
+#include "sj_tablewalk.h"
 
 using namespace sj;
 
@@ -823,6 +824,60 @@ __global__ __launch_bounds__(256) void k_q_list_gather_cvt(QView q, QList c, u64
     list_gather_strings<true>(q, c, out_off, out_status, soff, data);
 }
 
+// ---- tables: columns at SEVERAL paths from one walk of every record (sjhip_extract_table) -----------------------------------------
+// One lane per record runs table_walk (sj_tablewalk.h) over the plan of the table (sj_table.h); what it resolves goes straight
+// through the conversions of the single columns -- element_to into the column's values and statuses in the table arena,
+// element_text_len into the idx / off / status of the column's QCol -- so the string columns go on through k_q_col_tile_sums,
+// k_tw_scan_sums, k_q_col_tile_apply and k_q_col_gather as they are (the gather reads idx and does not walk).  Every array is
+// a column of its own: the 64 lanes of a wave store next to each other.  The resume stack of the walk is LDS: 2 x 16 u32 per
+// lane, lane after lane in every row (no bank conflicts), 32 KiB per block of 256.
+struct QTable {
+    TablePlan pl;
+    Arr<u8> out;   // the table arena of the part: values and statuses of the numeric / bool columns
+    Arr<u8> work;  // the work arrays of the string columns (their QCol)
+    // byte offsets, column by column: numeric / bool: values and status in `out`; strings: idx, off and status in `work`
+    u64 a_off[TABLE_MAX_COLS], b_off[TABLE_MAX_COLS], st_off[TABLE_MAX_COLS];
+};
+static_assert(sizeof(QView) + sizeof(QTable) <= 4096, "k_q_table_walk: the view and the plan travel as kernel arguments (4 KiB)");
+struct TableView {
+    const QView &q;
+    __device__ __forceinline__ u64 word(u64 i) const { return q.tape[i]; }
+    __device__ __forceinline__ bool key_equals(u64 kw, u64 kl, u32 key_b, u32 key_n) const { return str_equals(q, kw, kl, q.key + key_b, key_n); }
+};
+struct TableSink {
+    const QView &q;
+    const QTable &t;
+    u32 r;
+    __device__ __forceinline__ void operator()(u32 c, u64 v) const {
+        const int kind = t.pl.kind[c];
+        u64 x = 0;
+        if (kind <= SJHIP_COL_BOOL) {
+            const int st = v < SJHIP_PATH_NOT_OBJECT ? element_to(q, v, kind, &x) : path_status(v);
+            if (kind == SJHIP_COL_BOOL) *arr_at(t.out, t.a_off[c] + r, 1) = (u8)x;
+            else *(u64 *)arr_at(t.out, t.a_off[c] + 8ull * r, 8) = x;
+            *arr_at(t.out, t.st_off[c] + r, 1) = (u8)st;
+        } else {
+            const int st = v < SJHIP_PATH_NOT_OBJECT ? element_text_len(q, v, kind == SJHIP_COL_STRING_CVT, &x) : path_status(v);
+            *(u64 *)arr_at(t.work, t.a_off[c] + 8ull * r, 8) = v;
+            *(u64 *)arr_at(t.work, t.b_off[c] + 8ull * r, 8) = x;
+            *arr_at(t.work, t.st_off[c] + r, 1) = (u8)st;
+        }
+    }
+};
+__global__ __launch_bounds__(256) void k_q_table_walk(QView q, QTable t) {
+    __shared__ u32 s_stack[TABLE_STACK_WORDS * 256];
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    if (r > q.R) {
+        if (r == q.R + 1)  // entry n of every string column's lengths, as k_q_col_len leaves it
+            for (u32 c = 0; c < t.pl.n_cols; c++)
+                if (t.pl.kind[c] > SJHIP_COL_BOOL) *(u64 *)arr_at(t.work, t.b_off[c] + 8ull * r, 8) = 0;
+        return;
+    }
+    const TableView view = {q};
+    TableSink sink = {q, t, r};
+    table_walk(view, t.pl, rec_open(q, r), s_stack + threadIdx.x, 256u, sink);
+}
+
 }  // namespace
 
 namespace sj {
@@ -1472,4 +1527,199 @@ int sjhip_fetch_path_list(sjhip_ctx *ctx, uint64_t *list_offsets, void *values, 
 }
 int sjhip_fetch_path_list_strings(sjhip_ctx *ctx, uint64_t *list_offsets, uint64_t *str_offsets, uint8_t *data, uint8_t *status) {
     return list_fetch(ctx, true, list_offsets, str_offsets, data, status);
+}
+
+// ---- tables ---------------------------------------------------------------------------------------------------------------------
+// The table of every part lives in arenas of its own.  d_table, laid out from the record count and the kinds before the walk that
+// fills it: values [n] and status [n] of every numeric / bool column, offsets [n + 1] (from 0 in every part) and status [n] of
+// every string column.  d_tabledata, laid out once the walk and the scans have said how long the texts are: the bytes of the
+// string columns, one after another.  The work arrays of the string columns (a QCol each) are in d_kat, which lives for one call.
+struct TableOut {
+    u8 *val[TABLE_MAX_COLS];   // numeric / bool
+    u64 *off[TABLE_MAX_COLS];  // strings
+    u8 *status[TABLE_MAX_COLS];
+    u8 *data[TABLE_MAX_COLS];  // strings: in d_tabledata
+};
+static bool table_is_string(int kind) { return kind > SJHIP_COL_BOOL; }
+static size_t table_layout(Carve c, size_t n, uint32_t n_cols, const uint8_t *kind, TableOut *o) {
+    for (uint32_t j = 0; j < n_cols; j++) {
+        o->val[j] = nullptr;
+        o->off[j] = nullptr;
+        if (table_is_string(kind[j])) o->off[j] = c.take<u64>(n + 1);
+        else o->val[j] = c.take<u8>(n * (kind[j] == SJHIP_COL_BOOL ? 1u : 8u));
+        o->status[j] = c.take<u8>(n);
+    }
+    return c.used;
+}
+static size_t table_data_layout(Carve c, uint32_t n_cols, const uint8_t *kind, const size_t *bytes, TableOut *o) {
+    for (uint32_t j = 0; j < n_cols; j++) o->data[j] = table_is_string(kind[j]) ? c.take<u8>(bytes[j]) : nullptr;
+    return c.used;
+}
+
+int sjhip_extract_table(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, const uint32_t *path_lens, const int *kinds,
+                        uint32_t n_cols, size_t *records, size_t *bytes) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!keys || !key_lens || !path_lens || !kinds || !records || !bytes) {
+        ctx_set_error(ctx, "sjhip_extract_table: a null argument");
+        return SJHIP_ERR_ARG;
+    }
+    QTable t;
+    uint8_t blob[TABLE_MAX_BYTES];
+    uint32_t blob_len = 0, bad_col = 0;
+    const int why = table_plan(keys, key_lens, path_lens, kinds, n_cols, &t.pl, blob, &blob_len, &bad_col);
+    if (why) {
+        ctx_set_error(ctx, "sjhip_extract_table: %s (%u columns, found at column %u)", table_plan_error(why), n_cols, bad_col);
+        return SJHIP_ERR_ARG;
+    }
+    ctx->res.begin_table();  // (the last table is replaced, whatever happens below)
+    std::vector<sjhip_ctx *> parts;
+    int rc = query_parts(ctx, blob, blob_len, &NO_VALUE, 0, &parts);
+    if (rc) return rc;
+    const uint8_t *kind = t.pl.kind;
+    std::vector<std::vector<QCol>> cols(parts.size(), std::vector<QCol>(n_cols));
+    std::vector<ResultState::Table> sizes(parts.size());
+    auto tiles_of = [](uint32_t n) { return (n + 1u + QTILE - 1) / QTILE; };
+    auto work = [&](Carve c, uint32_t n, QCol *col, unsigned long long **totals) {
+        *totals = c.take<unsigned long long>(4 * TABLE_MAX_COLS);  // (k_tw_scan_sums leaves column j's bytes in entry 4 j + 2)
+        for (uint32_t j = 0; j < n_cols; j++) {
+            if (!table_is_string(kind[j])) continue;
+            col[j].idx = c.take<u64>(n);
+            col[j].off = c.take<u64>((size_t)n + 1);
+            col[j].status = c.take<u8>(n);
+            col[j].tiles = c.take<unsigned long long>(tiles_of(n));
+        }
+        return c.used;
+    };
+    // the walk, and the scans of the string columns' lengths, on every part, each on its own stream; then the totals
+    ResultState::Table total;
+    rc = query_over_parts(ctx, parts, blob, blob_len, &NO_VALUE, 0, "table sync",
+        [&](uint32_t n) {
+            std::vector<QCol> c(n_cols);
+            unsigned long long *totals;
+            return work(Carve(), n, c.data(), &totals) + 64;
+        },
+        [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
+            TableOut o;
+            const size_t out_bytes = table_layout(Carve(), n, n_cols, kind, &o);
+            const int rc = arena_reserve(part, part->d_table, out_bytes + 64);
+            if (rc) return rc;
+            (void)table_layout(Carve(part->d_table.p), n, n_cols, kind, &o);
+            QCol *c = cols[k].data();
+            unsigned long long *totals, *const none = nullptr;
+            const size_t work_bytes = work(Carve(part->d_kat.p), n, c, &totals);
+            QTable tk = t;
+            tk.out = SJ_ARR((u8 *)part->d_table.p, out_bytes, A_TABLE_OUT);
+            tk.work = SJ_ARR((u8 *)part->d_kat.p, work_bytes, A_TABLE_WORK);
+            for (uint32_t j = 0; j < n_cols; j++) {
+                const bool str = table_is_string(kind[j]);
+                tk.a_off[j] = str ? (u64)((u8 *)c[j].idx - (u8 *)part->d_kat.p) : (u64)(o.val[j] - (u8 *)part->d_table.p);
+                tk.b_off[j] = str ? (u64)((u8 *)c[j].off - (u8 *)part->d_kat.p) : 0;
+                tk.st_off[j] = str ? (u64)(c[j].status - (u8 *)part->d_kat.p) : (u64)(o.status[j] - (u8 *)part->d_table.p);
+            }
+            const u32 m = n + 1u, tiles = tiles_of(n);
+            hipLaunchKernelGGL(k_q_table_walk, dim3((m + 255) / 256), dim3(256), 0, part->stream, q, tk);
+            for (uint32_t j = 0; j < n_cols; j++) {
+                if (!table_is_string(kind[j])) continue;
+                hipLaunchKernelGGL(k_q_col_tile_sums, dim3(tiles), dim3(QT), 0, part->stream, c[j], m);
+                hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, part->stream, none, none, c[j].tiles, tiles, totals + 4 * j);
+                hipLaunchKernelGGL(k_q_col_tile_apply, dim3(tiles), dim3(QT), 0, part->stream, c[j], m);
+            }
+            HIPCHK(hipGetLastError(), "table launch");
+            HIPCHK(hipMemcpyAsync(part->h_scratch + 512, totals, 4 * TABLE_MAX_COLS * 8, hipMemcpyDeviceToHost, part->stream),
+                   "D2H table bytes");
+            return SJHIP_OK;
+        },
+        [&](size_t k, sjhip_ctx *part) {
+            const unsigned long long *h = (const unsigned long long *)(part->h_scratch + 512);
+            ResultState::Table &s = sizes[k];
+            s.records = (size_t)part->q_records + 1u;
+            s.n_cols = n_cols;
+            total.records += s.records;
+            for (uint32_t j = 0; j < n_cols; j++) {
+                s.kind[j] = kind[j];
+                s.bytes[j] = table_is_string(kind[j]) ? (size_t)h[4 * j + 2] : 0;
+                total.bytes[j] += s.bytes[j];
+            }
+        });
+    if (rc) return rc;
+    // the gathers of the string columns on every part, into the part's d_tabledata (the work arrays stay where they are: nothing
+    // more of d_kat is asked for)
+    rc = query_over_parts(ctx, parts, blob, blob_len, &NO_VALUE, 0, "table gather sync", [](uint32_t) { return (size_t)0; },
+        [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
+            TableOut o;
+            const int rc = arena_reserve(part, part->d_tabledata, table_data_layout(Carve(), n_cols, kind, sizes[k].bytes, &o) + 64);
+            if (rc) return rc;
+            (void)table_layout(Carve(part->d_table.p), n, n_cols, kind, &o);
+            (void)table_data_layout(Carve(part->d_tabledata.p), n_cols, kind, sizes[k].bytes, &o);
+            for (uint32_t j = 0; j < n_cols; j++) {
+                if (!table_is_string(kind[j])) continue;
+                u8 *const data = o.data[j];
+                hipLaunchKernelGGL(k_q_col_gather, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, cols[k][j], o.off[j],
+                                   o.status[j], SJ_ARR(data, sizes[k].bytes[j], A_TABLE_DATA));
+            }
+            HIPCHK(hipGetLastError(), "table gather launch");
+            return SJHIP_OK;
+        },
+        [](size_t, sjhip_ctx *) {});
+    if (rc) return rc;
+    total.n_cols = n_cols;
+    memcpy(total.kind, kind, n_cols);
+    *records = total.records;
+    for (uint32_t j = 0; j < n_cols; j++) bytes[j] = total.bytes[j];
+    bool ok = true;
+    for (size_t k = 0; k < parts.size(); k++) ok &= parts[k]->res.publish_table(sizes[k]);
+    if (ctx->res.sharded()) ok &= ctx->res.publish_table(total);
+    return published(ctx, ok);
+}
+
+int sjhip_fetch_table_column(sjhip_ctx *ctx, uint32_t col, void *values, uint64_t *offsets, uint8_t *data, uint8_t *status) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!ctx->res.table()) {  // none was built, or a parse (or sjhip_ctx_trim) came after it
+        ctx_set_error(ctx, "no table on the device (sjhip_fetch_table_column follows sjhip_extract_table, with no parse in between)");
+        return SJHIP_ERR_ARG;
+    }
+    const ResultState::Table &all = ctx->res.table_sizes();
+    if (col >= all.n_cols) {
+        ctx_set_error(ctx, "sjhip_fetch_table_column: column %u of a table of %u columns", col, all.n_cols);
+        return SJHIP_ERR_ARG;
+    }
+    const int kind = all.kind[col];
+    const bool str = table_is_string(kind);
+    const std::vector<sjhip_ctx *> parts = result_parts(ctx);
+    const size_t P = parts.size();
+    std::vector<size_t> rec_at(P + 1, 0), byte_at(P + 1, 0);  // where every part's records and bytes start
+    for (size_t k = 0; k < P; k++) {
+        rec_at[k + 1] = rec_at[k] + parts[k]->res.table_sizes().records;
+        byte_at[k + 1] = byte_at[k] + parts[k]->res.table_sizes().bytes[col];
+    }
+    if (!status || (str ? !offsets || (!data && byte_at[P]) : !values)) {
+        ctx_set_error(ctx, "sjhip_fetch_table_column: a null destination for column %u (%s)", col, str ? "offsets, data, status" : "values, status");
+        return SJHIP_ERR_ARG;
+    }
+    const size_t width = kind == SJHIP_COL_BOOL ? 1u : 8u;
+    const int rc = walk_parts(ctx, parts, "table fetch sync",
+        [&](size_t k, sjhip_ctx *part) -> int {
+            const ResultState::Table &s = part->res.table_sizes();
+            const size_t n = s.records, nb = s.bytes[col];
+            TableOut o;
+            (void)table_layout(Carve(part->d_table.p), n, s.n_cols, s.kind, &o);
+            (void)table_data_layout(Carve(part->d_tabledata.p), s.n_cols, s.kind, s.bytes, &o);
+            HIPCHK(hipMemcpyAsync(status + rec_at[k], o.status[col], n, hipMemcpyDeviceToHost, part->stream), "D2H table status");
+            if (!str) {
+                HIPCHK(hipMemcpyAsync((u8 *)values + rec_at[k] * width, o.val[col], n * width, hipMemcpyDeviceToHost, part->stream),
+                       "D2H table values");
+                return SJHIP_OK;
+            }
+            // every part's offsets but its last (the next part's first, rebased below)
+            HIPCHK(hipMemcpyAsync(offsets + rec_at[k], o.off[col], n * 8, hipMemcpyDeviceToHost, part->stream), "D2H table offsets");
+            if (nb) HIPCHK(hipMemcpyAsync(data + byte_at[k], o.data[col], nb, hipMemcpyDeviceToHost, part->stream), "D2H table bytes");
+            return SJHIP_OK;
+        },
+        [&](size_t k, sjhip_ctx *) {
+            if (str && byte_at[k])  // the offsets of a later shard: from the end of the shards in front of it
+                for (size_t i = rec_at[k]; i < rec_at[k + 1]; i++) offsets[i] += byte_at[k];
+        });
+    if (rc) return rc;
+    if (str) offsets[rec_at[P]] = byte_at[P];
+    return query_bounds_check(ctx);  // (debug build: the kernels of sjhip_extract_table have finished here)
 }

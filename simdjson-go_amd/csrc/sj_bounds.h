@@ -29,7 +29,9 @@ enum ArrId : uint32_t {
     A_S1_REC, A_S1_UNIT_CNT, A_S1_UNIT_COPY, A_S1_UNIT_STR, A_UNIT_STR, A_SOFF,
     A_S1_TILE_UNIT, A_TILE_UNIT, A_UNIT_TQ,
     A_COL,  // the bytes of a string column (query.hip)
-    A_LIST_VAL, A_LIST_SOFF, A_LIST_DATA  // a list column (query.hip): its values / its string offsets / its string bytes
+    A_LIST_VAL, A_LIST_SOFF, A_LIST_DATA,  // a list column (query.hip): its values / its string offsets / its string bytes
+    // a table (query.hip): the values and statuses of its numeric columns / the work arrays of its string columns / their bytes
+    A_TABLE_OUT, A_TABLE_WORK, A_TABLE_DATA
 };
 
 #if defined(SJ_DEBUG_BOUNDS)

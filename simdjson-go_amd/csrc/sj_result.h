@@ -7,7 +7,8 @@
 //     beside it, whether the key flags in d_keyflag belong to it and whether h_pack mirrors it;
 //   * the tenant of the shared arenas d_q / d_qtape / d_qstrings: the filtered result, the serialized columns or the MarshalJSON text
 //     -- one value, so at most one of them is resident;
-//   * the string column (d_col) and the list column (d_list, numbers or strings), independent of each other and of the tenant.
+//   * the string column (d_col), the list column (d_list, numbers or strings) and the table (d_table, d_tabledata), independent of
+//     each other and of the tenant.
 // The rule: a parse call, successful or not, drops the previous result and everything derived from it (begin_parse); so do
 // sjhip_deserialize, sjhip_ctx_trim and the stage-1-only calls (drop_result).  A product exists from its publish to the next
 // transition that drops it; a product is only published on a resident result, and a result of no tape words is no result.
@@ -27,12 +28,19 @@ public:
     struct Serialized { size_t tags = 0, vals = 0, slen = 0, rest = 0, stream = 0; bool dedup = false; };  // column sizes, framed stream
     struct Column { size_t records = 0, bytes = 0; };
     struct ListColumn { size_t records = 0, elems = 0, bytes = 0; };
+    static constexpr int TABLE_COLS = 16;  // SJHIP_TABLE_MAX_COLS
+    struct Table {  // what a fetch of one column needs: its kind, and the text bytes of a string column (0 for the other kinds)
+        size_t records = 0;
+        uint32_t n_cols = 0;
+        uint8_t kind[TABLE_COLS] = {};
+        size_t bytes[TABLE_COLS] = {};
+    };
 
     // ---- transitions ----
     // Every parse entry point, first: nothing of the last result is left.  (The sizes stay: they mean something under their flag only.)
     void begin_parse() {
         parse_ = Parse::None;
-        key_flags_ = packed_ = column_ = false;
+        key_flags_ = packed_ = column_ = table_ = false;
         tenant_ = Tenant::None;
         list_ = List::None;
     }
@@ -97,6 +105,13 @@ public:
         list_sizes_ = l;
         return true;
     }
+    void begin_table() { table_ = false; }
+    bool publish_table(const Table &t) {  // (an owner: the joined sizes of its shards' tables)
+        if (!resident() && !sharded()) return false;
+        table_ = true;
+        table_sizes_ = t;
+        return true;
+    }
 
     // ---- predicates ----
     bool pending() const { return parse_ == Parse::Pending; }
@@ -110,6 +125,7 @@ public:
     bool marshaled() const { return tenant_ == Tenant::Marshaled; }
     bool column() const { return column_; }
     bool list(bool strings) const { return list_ == (strings ? List::Strings : List::Numbers); }
+    bool table() const { return table_; }
 
     // ---- what the last publish / parse_done left (meaningful while the predicate beside it holds) ----
     uint64_t tape_base() const { return tape_base_; }
@@ -120,11 +136,12 @@ public:
     size_t marshaled_len() const { return marshaled_len_; }
     const Column &column_sizes() const { return column_sizes_; }
     const ListColumn &list_sizes() const { return list_sizes_; }
+    const Table &table_sizes() const { return table_sizes_; }
 
 private:
     enum class Parse : uint8_t { None, Pending, Whole, Shard, Sharded };
     Parse parse_ = Parse::None;
-    bool key_flags_ = false, packed_ = false, column_ = false;
+    bool key_flags_ = false, packed_ = false, column_ = false, table_ = false;
     Tenant tenant_ = Tenant::None;
     List list_ = List::None;
     uint64_t tape_base_ = 0, strings_base_ = 0, msg_base_ = 0;
@@ -133,6 +150,7 @@ private:
     size_t marshaled_len_ = 0;
     Column column_sizes_;
     ListColumn list_sizes_;
+    Table table_sizes_;
 };
 
 }  // namespace sj

@@ -371,6 +371,41 @@ class Context:
                                                              status.ctypes.data))
         return offsets, soff, data[:nbytes].tobytes(), status[:records]
 
+    # ---- tables (include/sjhip.h: sjhip_extract_table / sjhip_fetch_table_column) -----------------------------------------------
+    COL_STRING, COL_STRING_CVT = 4, 5  # kinds of table columns only: Iter.StringBytes / Iter.StringCvt
+    TABLE_MAX_COLS = 16
+
+    def extract_table(self, columns, fetch=True):
+        """columns: a list of (path, kind), kind = COL_FLOAT / INT / UINT / BOOL / COL_STRING / COL_STRING_CVT -- all of them
+        evaluated in one walk of every record, on the device.  -> one entry per column, shaped like extract_path's
+        (values, status) or extract_path_strings' (offsets, data, status); with fetch=False the table stays on the device and
+        (records, [text bytes of every column]) is returned (fetch_table_column)"""
+        keys = [bytes(k) for path, _ in columns for k in path]
+        n = len(columns)
+        key_lens = (C.c_uint32 * max(len(keys), 1))(*[len(k) for k in keys])
+        path_lens = (C.c_uint32 * max(n, 1))(*[len(path) for path, _ in columns])
+        kinds = (C.c_int * max(n, 1))(*[int(kind) for _, kind in columns])
+        nr, nb = C.c_size_t(0), (C.c_size_t * max(n, 1))()
+        self._check(_lib.lib().sjhip_extract_table(self._h, b"".join(keys), key_lens, path_lens, kinds, n, C.byref(nr), nb))
+        sizes = [int(b) for b in nb[:n]]
+        if not fetch:
+            return nr.value, sizes
+        return [self.fetch_table_column(c, nr.value, kind, sizes[c]) for c, (_, kind) in enumerate(columns)]
+
+    def fetch_table_column(self, col, records, kind, nbytes=0):
+        """column `col` of the last extract_table (the table's records, the column's kind and text bytes) -> (values, status)
+        or (offsets, data, status)"""
+        L = _lib.lib()
+        status = np.empty(max(records, 1), dtype=np.uint8)
+        if int(kind) in (self.COL_STRING, self.COL_STRING_CVT):
+            offsets = np.empty(records + 1, dtype=np.uint64)
+            data = np.empty(max(nbytes, 1), dtype=np.uint8)
+            self._check(L.sjhip_fetch_table_column(self._h, int(col), None, offsets.ctypes.data, data.ctypes.data, status.ctypes.data))
+            return offsets, data[:nbytes].tobytes(), status[:records]
+        values = np.empty(max(records, 1), dtype=self._COL_DTYPES[int(kind)])
+        self._check(L.sjhip_fetch_table_column(self._h, int(col), values.ctypes.data, None, None, status.ctypes.data))
+        return values[:records], status[:records]
+
     def serialize(self, fetch=True, dedup=False):
         """Serializer.Serialize (format v3, CompressNone) of the device-resident result of the last parse.
         -> the framed stream as a uint8 array (what the reference's Deserialize reads), or its sizes with fetch=False.
