@@ -206,9 +206,7 @@ static int stage1_verdict(const Stage1State &st, size_t len, uint8_t last_byte) 
 static void stage1_only(sjhip_ctx *ctx) {
     if (!ctx->res.sharded()) return ctx->res.drop_result();
     ctx->res.claim_shared();
-    ctx->res.begin_column();
-    ctx->res.begin_list();
-    ctx->res.begin_table();
+    ctx->res.drop_products();
 }
 
 // stage 1 in two halves: enqueue (workspace, launch; the last block of the kernel leaves the packed result -- count,

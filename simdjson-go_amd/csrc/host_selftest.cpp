@@ -795,8 +795,8 @@ extern "C" int sj_selftest_newlines_to_cr(void) {
 // sj_result.h: a byte-coded sequence of transitions applied to a fresh ResultState; bits_out[k] is the predicate set after step k.
 //   0 begin_parse   1 drop_result   2 parse_pending   3 + 4 * shard + 2 * key_flags + packed: parse_done of one tape word
 //   11 parse_done of an empty tape   12 parse_sharded   13 claim_shared   14 / 15 / 16 publish filtered / serialized / marshaled
-//   17 begin_column   18 publish_column   19 begin_list   20 / 21 publish_list numbers / strings
-//   22 / 23 / 24 release_shared of the filtered / serialized / marshaled tenant   25 begin_table   26 publish_table
+//   17 column.begin   18 publish column   19 list.begin   20 / 21 publish list, numbers / strings
+//   22 / 23 / 24 release_shared of the filtered / serialized / marshaled tenant   25 table.begin   26 publish table
 // bits: 0 pending, 1 whole, 2 resident, 3 sharded, 4 key_flags, 5 packed, 6 filtered, 7 serialized, 8 marshaled, 9 column,
 // 10 list of numbers, 11 list of strings, 12 table.  Returns 0, or 1 + the index of an unknown code.
 #include "sj_result.h"
@@ -814,18 +814,18 @@ extern "C" int sj_selftest_result_state(const uint8_t *ops, size_t n, uint32_t *
         else if (op == 14) s.publish_filtered({1, 1});
         else if (op == 15) s.publish_serialized({});
         else if (op == 16) s.publish_marshaled(1);
-        else if (op == 17) s.begin_column();
-        else if (op == 18) s.publish_column({1, 1});
-        else if (op == 19) s.begin_list();
-        else if (op == 20 || op == 21) s.publish_list(op == 21, {1, 1, 1});
+        else if (op == 17) s.column.begin();
+        else if (op == 18) s.publish(&sj::ResultState::column, {1, 1});
+        else if (op == 19) s.list.begin();
+        else if (op == 20 || op == 21) s.publish(&sj::ResultState::list, {1, 1, 1, op == 21});
         else if (op <= 24) s.release_shared(op == 22 ? sj::ResultState::Tenant::Filtered : op == 23 ? sj::ResultState::Tenant::Serialized : sj::ResultState::Tenant::Marshaled);
-        else if (op == 25) s.begin_table();
-        else if (op == 26) s.publish_table({});
+        else if (op == 25) s.table.begin();
+        else if (op == 26) s.publish(&sj::ResultState::table, {});
         else return 1 + (int)k;
         bits_out[k] = (uint32_t)s.pending() | (uint32_t)s.whole() << 1 | (uint32_t)s.resident() << 2 | (uint32_t)s.sharded() << 3 |
                       (uint32_t)s.key_flags() << 4 | (uint32_t)s.packed() << 5 | (uint32_t)s.filtered() << 6 |
-                      (uint32_t)s.serialized() << 7 | (uint32_t)s.marshaled() << 8 | (uint32_t)s.column() << 9 |
-                      (uint32_t)s.list(false) << 10 | (uint32_t)s.list(true) << 11 | (uint32_t)s.table() << 12;
+                      (uint32_t)s.serialized() << 7 | (uint32_t)s.marshaled() << 8 | (uint32_t)s.column.exists() << 9 |
+                      (uint32_t)s.list_of(false) << 10 | (uint32_t)s.list_of(true) << 11 | (uint32_t)s.table.exists() << 12;
     }
     return 0;
 }

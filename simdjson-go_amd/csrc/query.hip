@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 
+#include <array>
 #include <vector>
 
 #include "../../include/sjhip.h"
@@ -1242,132 +1243,225 @@ int sjhip_extract_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_
                               });
 }
 
-// The column of every part lives in the part's d_col: offsets [n + 1] (from 0 in every part), status [n], the bytes; the work
-// arrays of the three steps (QCol) in its d_kat, which only lives for one call.
-struct ColOut {
-    u64 *off;
-    u8 *status, *data;
+// ---- products: built on the device part by part, fetched later -- the string column, the list column, the table ---------------
+// build_product, the same for all three: the last product is given up; pass 1 over the parts measures -- the product's kernels
+// leave a length per record in its work arrays in d_kat, scan_lengths turns them into offsets in place, the totals come back
+// through h_scratch + 512 --; pass 2 reserves the product's own arena for those sizes and gathers into it (the work arrays stay
+// where they are: nothing more of d_kat is asked for); then the out-parameters and the publish.  fetch_joined is the fetch.
+static u32 tiles_of(u32 n) { return (n + 1u + QTILE - 1) / QTILE; }  // the scan tiles of a length array: n + 1 entries
+// The exclusive scan, in place, of the length array(s) of `a` (a QCol: one; a QList: two), n + 1 entries each: k_tw_scan_sums
+// takes the tile sums of up to three arrays in its slots (null: none) and leaves the grand total of slot i in totals[i].
+template <typename A>
+static void scan_lengths(sjhip_ctx *part, u32 n, void (*sums)(A, u32), void (*apply)(A, u32), const A &a, unsigned long long *slot0,
+                         unsigned long long *slot1, unsigned long long *slot2, unsigned long long *totals) {
+    const u32 m = n + 1u, tiles = tiles_of(n);
+    hipLaunchKernelGGL(sums, dim3(tiles), dim3(QT), 0, part->stream, a, m);
+    hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, part->stream, slot0, slot1, slot2, tiles, totals);
+    hipLaunchKernelGGL(apply, dim3(tiles), dim3(QT), 0, part->stream, a, m);
+}
+// A layout -- a function of a Carve -- run for its size, the arena reserved for it (+ 64), and run again on the arena.
+template <typename L>
+static int reserve_layout(sjhip_ctx *part, DevBuf &arena, L layout, size_t *bytes = nullptr) {
+    const size_t need = layout(Carve());
+    const int rc = arena_reserve(part, arena, need + 64);
+    if (rc) return rc;
+    (void)layout(Carve(arena.p));
+    if (bytes) *bytes = need;
+    return SJHIP_OK;
+}
+// What a product P plugs in (ColumnBuild, ListBuild, TableBuild below):
+//   Sizes, product, SYNC_*  what it publishes, where in ResultState, the names of its two waits in an error
+//   Work, work()            its work arrays of one part and their layout in d_kat, the totals of the scans in front
+//   measure()               pass 1 on one part: its kernels and scans, then the D2H of its totals to h_scratch + 512
+//   sizes_of(), add()       a part's sizes from what came back, and their sum
+//   gather()                pass 2 on one part: its arena(s) for those sizes, its gather kernels
+//   finish()                what the total holds beyond sums, and the call's out-parameters
+// `keys` / `klen`: the keys of its path(s), which travel in the view.  Errors of the HIP calls are left in ctx, the owner.
+template <typename P>
+static int build_product(sjhip_ctx *ctx, const uint8_t *keys, size_t klen, P &p) {
+    (ctx->res.*P::product).begin();  // (the last one is replaced, whatever happens below)
+    std::vector<sjhip_ctx *> parts;
+    int rc = query_parts(ctx, keys, klen, &NO_VALUE, 0, &parts);
+    if (rc) return rc;
+    std::vector<typename P::Work> work(parts.size());
+    std::vector<typename P::Sizes> sizes(parts.size());
+    typename P::Sizes total;
+    rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, P::SYNC_MEASURE,
+        [&](uint32_t n) {
+            typename P::Work w;
+            unsigned long long *totals;
+            return p.work(Carve(), n, &w, &totals) + 64;
+        },
+        [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
+            unsigned long long *totals;
+            const size_t work_bytes = p.work(Carve(part->d_kat.p), n, &work[k], &totals);
+            return p.measure(ctx, part, q, n, work[k], work_bytes, totals);
+        },
+        [&](size_t k, sjhip_ctx *part) {
+            sizes[k] = p.sizes_of((size_t)part->q_records + 1u, (const unsigned long long *)(part->h_scratch + 512));
+            p.add(&total, sizes[k]);
+        });
+    if (rc) return rc;
+    rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, P::SYNC_GATHER, [](uint32_t) { return (size_t)0; },
+        [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int { return p.gather(ctx, part, q, n, work[k], sizes[k]); },
+        [](size_t, sjhip_ctx *) {});
+    if (rc) return rc;
+    p.finish(&total);
+    bool ok = true;  // the sizes: on every part, then joined on a sharded owner
+    for (size_t k = 0; k < parts.size(); k++) ok &= parts[k]->res.publish(P::product, sizes[k]);
+    if (ctx->res.sharded()) ok &= ctx->res.publish(P::product, total);
+    return published(ctx, ok);
+}
+
+// The joined fetch.  A product is a few arrays per part (Seg), each as long as one of the part's counts -- its records, elements
+// or bytes -- and laid end to end in the caller's destination.  An offset array (`values` names a domain) starts from 0 in every
+// part and its last entry is the next part's first: `count` entries of every part travel, those of a later part are moved up by
+// what the parts in front hold in the domain of the VALUES (not the one it is indexed by), the terminating entry is that total.
+enum Dom { RECORDS, ELEMS, BYTES, N_DOMS, NO_DOM = -1 };
+struct Seg {
+    void *dst;
+    size_t width;      // bytes per element
+    int by;            // a part holds count[by] elements
+    int values;        // an offset array: the domain its values count in; NO_DOM: data
+    bool skip_empty;   // no copy for a part that holds none
+    const char *what;  // the name of its copy in an error
 };
+struct PartArrays {  // of one part: its counts, from its published sizes, and where its arrays lie in its arena (segs' order)
+    size_t count[N_DOMS] = {};
+    const void *src[4] = {};
+};
+static int no_product(sjhip_ctx *ctx, const char *text) {  // none was built, or a parse (or sjhip_ctx_trim) came after it
+    ctx_set_error(ctx, "%s", text);
+    return SJHIP_ERR_ARG;
+}
+// layout(part, count, src) fills a part's PartArrays; null_dst(total): the product's rules about null destinations, given the joined counts.
+template <typename L, typename N>
+static int fetch_joined(sjhip_ctx *ctx, const char *sync, const Seg *segs, size_t n_segs, L layout, N null_dst) {
+    const std::vector<sjhip_ctx *> parts = result_parts(ctx);
+    const size_t P = parts.size();
+    std::vector<PartArrays> a(P);
+    std::vector<std::array<size_t, N_DOMS>> at(P + 1);  // where every part's records, elements and bytes start
+    for (size_t k = 0; k < P; k++) {
+        layout(parts[k], a[k].count, a[k].src);
+        for (int d = 0; d < N_DOMS; d++) at[k + 1][d] = at[k][d] + a[k].count[d];
+    }
+    int rc = null_dst(at[P].data());
+    if (rc) return rc;
+    rc = walk_parts(ctx, parts, sync,
+        [&](size_t k, sjhip_ctx *part) -> int {
+            for (size_t s = 0; s < n_segs; s++) {
+                const Seg &g = segs[s];
+                const size_t cnt = a[k].count[g.by];
+                if (cnt || !g.skip_empty)
+                    HIPCHK(hipMemcpyAsync((u8 *)g.dst + at[k][g.by] * g.width, a[k].src[s], cnt * g.width, hipMemcpyDeviceToHost, part->stream), g.what);
+            }
+            return SJHIP_OK;
+        },
+        [&](size_t k, sjhip_ctx *) {  // the offsets of a later part: from the end of the parts in front of it
+            for (size_t s = 0; s < n_segs; s++) {
+                const Seg &g = segs[s];
+                if (g.values == NO_DOM || !at[k][g.values]) continue;
+                for (size_t i = at[k][g.by]; i < at[k + 1][g.by]; i++) ((uint64_t *)g.dst)[i] += at[k][g.values];
+            }
+        });
+    if (rc) return rc;
+    for (size_t s = 0; s < n_segs; s++)
+        if (segs[s].values != NO_DOM) ((uint64_t *)segs[s].dst)[at[P][segs[s].by]] = at[P][segs[s].values];
+    return SJHIP_OK;
+}
+
+// ---- string columns: one QCol each, the single one (sjhip_extract_path_strings) and those of a table ------------------------------
+// A QCol -- the work arrays of one string column in d_kat, which only lives for one call -- is filled by k_q_col_len (the single
+// column) or by k_q_table_walk (a table's); everything behind the fill is the same: col_scan, col_gather.
+static void col_work(Carve &c, uint32_t n, QCol *col) {
+    col->idx = c.take<u64>(n);
+    col->off = c.take<u64>((size_t)n + 1);
+    col->status = c.take<u8>(n);
+    col->tiles = c.take<unsigned long long>(tiles_of(n));
+}
+static void col_scan(sjhip_ctx *part, uint32_t n, const QCol &c, unsigned long long *totals) {  // (the column's bytes: totals[2])
+    scan_lengths<QCol>(part, n, k_q_col_tile_sums, k_q_col_tile_apply, c, nullptr, nullptr, c.tiles, totals);
+}
+static void col_gather(sjhip_ctx *part, const QView &q, uint32_t n, const QCol &c, u64 *off, u8 *status, Arr<u8> data) {
+    hipLaunchKernelGGL(k_q_col_gather, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, c, off, status, data);
+}
+
+// The column of every part lives in the part's d_col: offsets [n + 1] (from 0 in every part), status [n], the bytes.
+struct ColOut { u64 *off; u8 *status, *data; };
 static size_t col_layout(Carve c, size_t n, size_t bytes, ColOut *o) {
     o->off = c.take<u64>(n + 1);
     o->status = c.take<u8>(n);
     o->data = c.take<u8>(bytes);
     return c.used;
 }
+struct ColumnBuild {
+    using Sizes = ResultState::Column;
+    using Work = QCol;
+    static constexpr auto product = &ResultState::column;
+    static constexpr const char *SYNC_MEASURE = "column sync", *SYNC_GATHER = "column gather sync";
+    QPath pth;
+    uint32_t cvt;
+    size_t *records, *bytes;
+    size_t work(Carve c, uint32_t n, QCol *col, unsigned long long **totals) const {
+        *totals = c.take<unsigned long long>(32);
+        col_work(c, n, col);
+        return c.used;
+    }
+    int measure(sjhip_ctx *ctx, sjhip_ctx *part, const QView &q, uint32_t n, const QCol &c, size_t, unsigned long long *totals) const {
+        hipLaunchKernelGGL(k_q_col_len, dim3((n + 1u + 255) / 256), dim3(256), 0, part->stream, q, pth, cvt, c);
+        col_scan(part, n, c, totals);
+        HIPCHK(hipGetLastError(), "column launch");
+        HIPCHK(hipMemcpyAsync(part->h_scratch + 512, totals + 2, 8, hipMemcpyDeviceToHost, part->stream), "D2H column bytes");
+        return SJHIP_OK;
+    }
+    Sizes sizes_of(size_t n, const unsigned long long *h) const { return {n, (size_t)h[0]}; }
+    void add(Sizes *t, const Sizes &s) const { t->records += s.records, t->bytes += s.bytes; }
+    int gather(sjhip_ctx *ctx, sjhip_ctx *part, const QView &q, uint32_t n, const QCol &c, const Sizes &s) const {
+        ColOut o;
+        const int rc = reserve_layout(part, part->d_col, [&](Carve cv) { return col_layout(cv, n, s.bytes, &o); });
+        if (rc) return rc;
+        col_gather(part, q, n, c, o.off, o.status, SJ_ARR(o.data, s.bytes, A_COL));
+        HIPCHK(hipGetLastError(), "column gather launch");
+        return SJHIP_OK;
+    }
+    void finish(Sizes *total) const { *records = total->records, *bytes = total->bytes; }
+};
 
 int sjhip_extract_path_strings(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, uint32_t flags,
                                size_t *records, size_t *bytes) {
     if (!records || !bytes || (flags & ~SJHIP_COL_CVT)) return SJHIP_ERR_ARG;
-    QPath pth;
+    ColumnBuild p;
+    p.cvt = flags & SJHIP_COL_CVT, p.records = records, p.bytes = bytes;
     size_t klen = 0;
-    int rc = make_path(ctx, keys, key_lens, n_keys, &pth, &klen);
-    if (rc) return rc;
-    ctx->res.begin_column();  // (the last column is replaced, whatever happens below)
-    std::vector<sjhip_ctx *> parts;
-    rc = query_parts(ctx, keys, klen, &NO_VALUE, 0, &parts);
-    if (rc) return rc;
-    std::vector<QCol> cols(parts.size());
-    std::vector<ResultState::Column> sizes(parts.size());
-    auto tiles_of = [](uint32_t n) { return (n + 1u + QTILE - 1) / QTILE; };
-    auto work = [&](Carve c, uint32_t n, QCol *col, unsigned long long **totals) {
-        *totals = c.take<unsigned long long>(32);
-        col->idx = c.take<u64>(n);
-        col->off = c.take<u64>((size_t)n + 1);
-        col->status = c.take<u8>(n);
-        col->tiles = c.take<unsigned long long>(tiles_of(n));
-        return c.used;
-    };
-    // lengths and their scan on every part, each on its own stream; then the totals
-    ResultState::Column total;
-    rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, "column sync",
-        [&](uint32_t n) {
-            QCol c;
-            unsigned long long *totals;
-            return work(Carve(), n, &c, &totals) + 64;
-        },
-        [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
-            QCol &c = cols[k];
-            unsigned long long *totals, *const none = nullptr;
-            (void)work(Carve(part->d_kat.p), n, &c, &totals);
-            const u32 m = n + 1u, tiles = tiles_of(n);
-            hipLaunchKernelGGL(k_q_col_len, dim3((m + 255) / 256), dim3(256), 0, part->stream, q, pth, flags & SJHIP_COL_CVT, c);
-            hipLaunchKernelGGL(k_q_col_tile_sums, dim3(tiles), dim3(QT), 0, part->stream, c, m);
-            hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, part->stream, none, none, c.tiles, tiles, totals);
-            hipLaunchKernelGGL(k_q_col_tile_apply, dim3(tiles), dim3(QT), 0, part->stream, c, m);
-            HIPCHK(hipGetLastError(), "column launch");
-            HIPCHK(hipMemcpyAsync(part->h_scratch + 512, totals + 2, 8, hipMemcpyDeviceToHost, part->stream), "D2H column bytes");
-            return SJHIP_OK;
-        },
-        [&](size_t k, sjhip_ctx *part) {
-            sizes[k] = {(size_t)part->q_records + 1u, (size_t)*(const unsigned long long *)(part->h_scratch + 512)};
-            total.records += sizes[k].records;
-            total.bytes += sizes[k].bytes;
-        });
-    if (rc) return rc;
-    // the gather on every part, into the part's d_col (the work arrays stay where they are: nothing more of d_kat is asked for)
-    rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, "column gather sync", [](uint32_t) { return (size_t)0; },
-        [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
-            ColOut o;
-            const int rc = arena_reserve(part, part->d_col, col_layout(Carve(), n, sizes[k].bytes, &o) + 64);
-            if (rc) return rc;
-            (void)col_layout(Carve(part->d_col.p), n, sizes[k].bytes, &o);
-            hipLaunchKernelGGL(k_q_col_gather, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, cols[k], o.off, o.status,
-                               SJ_ARR(o.data, sizes[k].bytes, A_COL));
-            HIPCHK(hipGetLastError(), "column gather launch");
-            return SJHIP_OK;
-        },
-        [](size_t, sjhip_ctx *) {});  // (the work arrays in d_kat are free for the next query once this returns)
-    if (rc) return rc;
-    *records = total.records;
-    *bytes = total.bytes;
-    bool ok = true;
-    for (size_t k = 0; k < parts.size(); k++) ok &= parts[k]->res.publish_column(sizes[k]);
-    if (ctx->res.sharded()) ok &= ctx->res.publish_column(total);
-    return published(ctx, ok);
+    const int rc = make_path(ctx, keys, key_lens, n_keys, &p.pth, &klen);
+    return rc ? rc : build_product(ctx, keys, klen, p);
 }
 
 int sjhip_fetch_path_strings(sjhip_ctx *ctx, uint64_t *offsets, uint8_t *data, uint8_t *status) {
     if (!ctx) return SJHIP_ERR_ARG;
-    if (!ctx->res.column()) {  // no column was built, or a parse (or sjhip_ctx_trim) came after it
-        ctx_set_error(ctx, "no string column on the device (sjhip_fetch_path_strings follows sjhip_extract_path_strings, with no parse in between)");
-        return SJHIP_ERR_ARG;
-    }
-    const std::vector<sjhip_ctx *> parts = result_parts(ctx);
-    std::vector<size_t> rec_at(parts.size() + 1, 0), byte_at(parts.size() + 1, 0);  // where every part's records and bytes start
-    for (size_t k = 0; k < parts.size(); k++) {
-        rec_at[k + 1] = rec_at[k] + parts[k]->res.column_sizes().records;
-        byte_at[k + 1] = byte_at[k] + parts[k]->res.column_sizes().bytes;
-    }
-    if (!offsets || !status || (!data && byte_at[parts.size()])) return SJHIP_ERR_ARG;
-    const int rc = walk_parts(ctx, parts, "column fetch sync",
-        [&](size_t k, sjhip_ctx *part) -> int {  // every part's offsets but its last (the next part's first, rebased below) + status + bytes
-            const size_t n = part->res.column_sizes().records, nb = part->res.column_sizes().bytes;
+    if (!ctx->res.column.exists())
+        return no_product(ctx, "no string column on the device (sjhip_fetch_path_strings follows sjhip_extract_path_strings, with no parse in between)");
+    const Seg segs[] = {{offsets, 8, RECORDS, BYTES, false, "D2H column offsets"},
+                        {status, 1, RECORDS, NO_DOM, false, "D2H column status"},
+                        {data, 1, BYTES, NO_DOM, true, "D2H column bytes"}};
+    // (this fetch ends without query_bounds_check, unlike the list's and the table's: the debug build reports a violation of
+    // k_q_col_gather with the next checked query call -- it has been so since the column was added, and stays so)
+    return fetch_joined(ctx, "column fetch sync", segs, 3,
+        [](sjhip_ctx *part, size_t *count, const void **src) {
+            const ResultState::Column &s = part->res.column.sizes();
             ColOut o;
-            (void)col_layout(Carve(part->d_col.p), n, nb, &o);
-            HIPCHK(hipMemcpyAsync(offsets + rec_at[k], o.off, n * 8, hipMemcpyDeviceToHost, part->stream), "D2H column offsets");
-            HIPCHK(hipMemcpyAsync(status + rec_at[k], o.status, n, hipMemcpyDeviceToHost, part->stream), "D2H column status");
-            if (nb) HIPCHK(hipMemcpyAsync(data + byte_at[k], o.data, nb, hipMemcpyDeviceToHost, part->stream), "D2H column bytes");
-            return SJHIP_OK;
+            (void)col_layout(Carve(part->d_col.p), s.records, s.bytes, &o);
+            count[RECORDS] = s.records, count[BYTES] = s.bytes;
+            src[0] = o.off, src[1] = o.status, src[2] = o.data;
         },
-        [&](size_t k, sjhip_ctx *) {
-            if (byte_at[k])  // the offsets of a later shard: from the end of the shards in front of it
-                for (size_t i = rec_at[k]; i < rec_at[k + 1]; i++) offsets[i] += byte_at[k];
-        });
-    if (rc) return rc;
-    offsets[rec_at[parts.size()]] = byte_at[parts.size()];
-    return SJHIP_OK;
+        [&](const size_t *total) { return !offsets || !status || (!data && total[BYTES]) ? SJHIP_ERR_ARG : SJHIP_OK; });
 }
 
 // ---- list columns --------------------------------------------------------------------------------------------------------------
 // The list column of every part lives in the part's d_list, an arena of its own (d_col keeps the string column): list offsets
 // [n + 1] (from 0 in every part), status [n], then the values [elems], or the string offsets [elems + 1] (from 0) and the bytes;
 // the work arrays of the three steps (QList) in its d_kat, which only lives for one call.
-struct ListOut {
-    u64 *off;
-    u8 *status;
-    u64 *values, *soff;
-    u8 *data;
-};
+struct ListOut { u64 *off, *values, *soff; u8 *status, *data; };
 static size_t list_layout(Carve c, size_t n, size_t elems, size_t bytes, bool strings, ListOut *o) {
     o->off = c.take<u64>(n + 1);
     o->status = c.take<u8>(n);
@@ -1376,95 +1470,68 @@ static size_t list_layout(Carve c, size_t n, size_t elems, size_t bytes, bool st
     o->data = strings ? c.take<u8>(bytes) : nullptr;
     return c.used;
 }
-static const char NO_LIST[] = "no list column of this kind on the device (sjhip_fetch_path_list follows sjhip_extract_path_list, "
-                              "sjhip_fetch_path_list_strings follows sjhip_extract_path_list_strings, with no parse in between)";
-
-// mode: SJHIP_COL_FLOAT / INT / UINT, LIST_STR or LIST_CVT
-static int list_extract(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int mode, size_t *records,
-                        size_t *elems, size_t *bytes) {
+struct ListBuild {
+    using Sizes = ResultState::ListColumn;
+    using Work = QList;
+    static constexpr auto product = &ResultState::list;
+    static constexpr const char *SYNC_MEASURE = "list column sync", *SYNC_GATHER = "list gather sync";
     QPath pth;
-    size_t klen = 0;
-    int rc = make_path(ctx, keys, key_lens, n_keys, &pth, &klen);
-    if (rc) return rc;
-    ctx->res.begin_list();  // (the last list column is replaced, whatever happens below)
-    const bool strings = mode >= LIST_STR;
-    std::vector<sjhip_ctx *> parts;
-    rc = query_parts(ctx, keys, klen, &NO_VALUE, 0, &parts);
-    if (rc) return rc;
-    std::vector<QList> lists(parts.size());
-    std::vector<ResultState::ListColumn> sizes(parts.size());
-    auto tiles_of = [](uint32_t n) { return (n + 1u + QTILE - 1) / QTILE; };
-    auto work = [&](Carve c, uint32_t n, QList *l, unsigned long long **totals) {
+    int mode;  // SJHIP_COL_FLOAT / INT / UINT, LIST_STR or LIST_CVT
+    size_t *records, *elems, *bytes;
+    bool strings() const { return mode >= LIST_STR; }
+    size_t work(Carve c, uint32_t n, QList *l, unsigned long long **totals) const {
         *totals = c.take<unsigned long long>(32);
         l->idx = c.take<u64>(n);
         l->cnt = c.take<u64>((size_t)n + 1);
-        l->bytes = strings ? c.take<u64>((size_t)n + 1) : nullptr;
+        l->bytes = strings() ? c.take<u64>((size_t)n + 1) : nullptr;
         l->status = c.take<u8>(n);
         l->tiles_c = c.take<unsigned long long>(tiles_of(n));
-        l->tiles_b = strings ? c.take<unsigned long long>(tiles_of(n)) : nullptr;
+        l->tiles_b = strings() ? c.take<unsigned long long>(tiles_of(n)) : nullptr;
         return c.used;
-    };
-    // the conversion check, the counts and their scans on every part, each on its own stream; then the totals
-    ResultState::ListColumn total;
-    rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, "list column sync",
-        [&](uint32_t n) {
-            QList l;
-            unsigned long long *totals;
-            return work(Carve(), n, &l, &totals) + 64;
-        },
-        [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
-            QList &l = lists[k];
-            unsigned long long *totals, *const none = nullptr;
-            (void)work(Carve(part->d_kat.p), n, &l, &totals);
-            const u32 m = n + 1u, tiles = tiles_of(n);
-            HIPCHK(hipMemsetAsync(totals, 0, 16, part->stream), "list totals memset");
-            if (mode == LIST_CVT) hipLaunchKernelGGL(k_q_list_measure_cvt, dim3((m + 255) / 256), dim3(256), 0, part->stream, q, pth, l);
-            else hipLaunchKernelGGL(k_q_list_measure, dim3((m + 255) / 256), dim3(256), 0, part->stream, q, pth, mode, l);
-            hipLaunchKernelGGL(k_q_list_tile_sums, dim3(tiles), dim3(QT), 0, part->stream, l, m);
-            hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, part->stream, l.tiles_c, l.tiles_b, none, tiles, totals);
-            hipLaunchKernelGGL(k_q_list_tile_apply, dim3(tiles), dim3(QT), 0, part->stream, l, m);
-            HIPCHK(hipGetLastError(), "list column launch");
-            HIPCHK(hipMemcpyAsync(part->h_scratch + 512, totals, 16, hipMemcpyDeviceToHost, part->stream), "D2H list totals");
-            return SJHIP_OK;
-        },
-        [&](size_t k, sjhip_ctx *part) {
-            const unsigned long long *h = (const unsigned long long *)(part->h_scratch + 512);
-            sizes[k] = {(size_t)part->q_records + 1u, (size_t)h[0], strings ? (size_t)h[1] : 0};
-            total.records += sizes[k].records;
-            total.elems += sizes[k].elems;
-            total.bytes += sizes[k].bytes;
-        });
-    if (rc) return rc;
-    // the gather on every part, into the part's d_list (the work arrays stay where they are: nothing more of d_kat is asked for)
-    rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, "list gather sync", [](uint32_t) { return (size_t)0; },
-        [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
-            ListOut o;
-            const size_t ne = sizes[k].elems, nb = sizes[k].bytes;
-            const int rc = arena_reserve(part, part->d_list, list_layout(Carve(), n, ne, nb, strings, &o) + 64);
-            if (rc) return rc;
-            (void)list_layout(Carve(part->d_list.p), n, ne, nb, strings, &o);
-            const dim3 grid((n + 255) / 256), block(256);
-            if (!strings)
-                hipLaunchKernelGGL(k_q_list_gather_num, grid, block, 0, part->stream, q, lists[k], mode, o.off, o.status,
-                                   SJ_ARR(o.values, ne, A_LIST_VAL));
-            else if (mode == LIST_STR)
-                hipLaunchKernelGGL(k_q_list_gather_str, grid, block, 0, part->stream, q, lists[k], o.off, o.status,
-                                   SJ_ARR(o.soff, ne + 1, A_LIST_SOFF), SJ_ARR(o.data, nb, A_LIST_DATA));
-            else
-                hipLaunchKernelGGL(k_q_list_gather_cvt, grid, block, 0, part->stream, q, lists[k], o.off, o.status,
-                                   SJ_ARR(o.soff, ne + 1, A_LIST_SOFF), SJ_ARR(o.data, nb, A_LIST_DATA));
-            HIPCHK(hipGetLastError(), "list gather launch");
-            return SJHIP_OK;
-        },
-        [](size_t, sjhip_ctx *) {});
-    if (rc) return rc;
-    *records = total.records;
-    *elems = total.elems;
-    if (bytes) *bytes = total.bytes;
-    bool ok = true;
-    for (size_t k = 0; k < parts.size(); k++) ok &= parts[k]->res.publish_list(strings, sizes[k]);
-    if (ctx->res.sharded()) ok &= ctx->res.publish_list(strings, total);
-    return published(ctx, ok);
+    }
+    // the conversion check, the counts (and the bytes of strings) and their scans: the elements in totals[0], the bytes in [1]
+    int measure(sjhip_ctx *ctx, sjhip_ctx *part, const QView &q, uint32_t n, const QList &l, size_t, unsigned long long *totals) const {
+        const dim3 grid((n + 1u + 255) / 256), block(256);
+        HIPCHK(hipMemsetAsync(totals, 0, 16, part->stream), "list totals memset");
+        if (mode == LIST_CVT) hipLaunchKernelGGL(k_q_list_measure_cvt, grid, block, 0, part->stream, q, pth, l);
+        else hipLaunchKernelGGL(k_q_list_measure, grid, block, 0, part->stream, q, pth, mode, l);
+        scan_lengths<QList>(part, n, k_q_list_tile_sums, k_q_list_tile_apply, l, l.tiles_c, l.tiles_b, nullptr, totals);
+        HIPCHK(hipGetLastError(), "list column launch");
+        HIPCHK(hipMemcpyAsync(part->h_scratch + 512, totals, 16, hipMemcpyDeviceToHost, part->stream), "D2H list totals");
+        return SJHIP_OK;
+    }
+    Sizes sizes_of(size_t n, const unsigned long long *h) const { return {n, (size_t)h[0], strings() ? (size_t)h[1] : 0, strings()}; }
+    void add(Sizes *t, const Sizes &s) const { t->records += s.records, t->elems += s.elems, t->bytes += s.bytes; }
+    int gather(sjhip_ctx *ctx, sjhip_ctx *part, const QView &q, uint32_t n, const QList &l, const Sizes &s) const {
+        ListOut o;
+        const size_t ne = s.elems, nb = s.bytes;
+        const int rc = reserve_layout(part, part->d_list, [&](Carve cv) { return list_layout(cv, n, ne, nb, strings(), &o); });
+        if (rc) return rc;
+        const dim3 grid((n + 255) / 256), block(256);
+        if (!strings())
+            hipLaunchKernelGGL(k_q_list_gather_num, grid, block, 0, part->stream, q, l, mode, o.off, o.status, SJ_ARR(o.values, ne, A_LIST_VAL));
+        else if (mode == LIST_STR)
+            hipLaunchKernelGGL(k_q_list_gather_str, grid, block, 0, part->stream, q, l, o.off, o.status,
+                               SJ_ARR(o.soff, ne + 1, A_LIST_SOFF), SJ_ARR(o.data, nb, A_LIST_DATA));
+        else
+            hipLaunchKernelGGL(k_q_list_gather_cvt, grid, block, 0, part->stream, q, l, o.off, o.status,
+                               SJ_ARR(o.soff, ne + 1, A_LIST_SOFF), SJ_ARR(o.data, nb, A_LIST_DATA));
+        HIPCHK(hipGetLastError(), "list gather launch");
+        return SJHIP_OK;
+    }
+    void finish(Sizes *total) const {
+        total->strings = strings();
+        *records = total->records, *elems = total->elems;
+        if (bytes) *bytes = total->bytes;
+    }
+};
+static int list_extract(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int mode, size_t *records,
+                        size_t *elems, size_t *bytes) {
+    ListBuild p;
+    p.mode = mode, p.records = records, p.elems = elems, p.bytes = bytes;
+    size_t klen = 0;
+    const int rc = make_path(ctx, keys, key_lens, n_keys, &p.pth, &klen);
+    return rc ? rc : build_product(ctx, keys, klen, p);
 }
 
 int sjhip_extract_path_list(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int kind, size_t *records,
@@ -1482,45 +1549,30 @@ int sjhip_extract_path_list_strings(sjhip_ctx *ctx, const uint8_t *keys, const u
     return list_extract(ctx, keys, key_lens, n_keys, (flags & SJHIP_COL_CVT) ? LIST_CVT : LIST_STR, records, elems, bytes);
 }
 
-// inner: the values (numbers) or the string offsets (strings) of the elements
+// inner: the values (numbers) or the string offsets (strings) of the elements.  Two offset arrays over two domains: the list
+// offsets are indexed by records and count elements, the string offsets are indexed by elements and count bytes.
 static int list_fetch(sjhip_ctx *ctx, bool strings, uint64_t *list_offsets, uint64_t *inner, uint8_t *data, uint8_t *status) {
     if (!ctx) return SJHIP_ERR_ARG;
-    if (!ctx->res.list(strings)) {  // none was built, a parse (or sjhip_ctx_trim) came after it, or it is of the other kind
-        ctx_set_error(ctx, "%s", NO_LIST);
-        return SJHIP_ERR_ARG;
-    }
-    const std::vector<sjhip_ctx *> parts = result_parts(ctx);
-    const size_t P = parts.size();
-    std::vector<size_t> rec_at(P + 1, 0), elem_at(P + 1, 0), byte_at(P + 1, 0);  // where every part's records, elements and bytes start
-    for (size_t k = 0; k < P; k++) {
-        rec_at[k + 1] = rec_at[k] + parts[k]->res.list_sizes().records;
-        elem_at[k + 1] = elem_at[k] + parts[k]->res.list_sizes().elems;
-        byte_at[k + 1] = byte_at[k] + parts[k]->res.list_sizes().bytes;
-    }
-    if (!list_offsets || !status || (!inner && (strings || elem_at[P])) || (strings && !data && byte_at[P])) return SJHIP_ERR_ARG;
-    const int rc = walk_parts(ctx, parts, "list fetch sync",
-        [&](size_t k, sjhip_ctx *part) -> int {  // every part's offsets but their last (the next part's first, rebased below)
-            const size_t n = part->res.list_sizes().records, ne = part->res.list_sizes().elems, nb = part->res.list_sizes().bytes;
+    if (!ctx->res.list_of(strings))  // (... or it is of the other kind)
+        return no_product(ctx, "no list column of this kind on the device (sjhip_fetch_path_list follows sjhip_extract_path_list, "
+                               "sjhip_fetch_path_list_strings follows sjhip_extract_path_list_strings, with no parse in between)");
+    const Seg segs[] = {{list_offsets, 8, RECORDS, ELEMS, false, "D2H list offsets"},
+                        {status, 1, RECORDS, NO_DOM, false, "D2H list status"},
+                        {inner, 8, ELEMS, strings ? BYTES : NO_DOM, true, "D2H list elements"},
+                        {data, 1, BYTES, NO_DOM, true, "D2H list bytes"}};
+    const int rc = fetch_joined(ctx, "list fetch sync", segs, 4,
+        [&](sjhip_ctx *part, size_t *count, const void **src) {
+            const ResultState::ListColumn &s = part->res.list.sizes();
             ListOut o;
-            (void)list_layout(Carve(part->d_list.p), n, ne, nb, strings, &o);
-            HIPCHK(hipMemcpyAsync(list_offsets + rec_at[k], o.off, n * 8, hipMemcpyDeviceToHost, part->stream), "D2H list offsets");
-            HIPCHK(hipMemcpyAsync(status + rec_at[k], o.status, n, hipMemcpyDeviceToHost, part->stream), "D2H list status");
-            if (ne)
-                HIPCHK(hipMemcpyAsync(inner + elem_at[k], strings ? o.soff : o.values, ne * 8, hipMemcpyDeviceToHost, part->stream),
-                       "D2H list elements");
-            if (nb) HIPCHK(hipMemcpyAsync(data + byte_at[k], o.data, nb, hipMemcpyDeviceToHost, part->stream), "D2H list bytes");
-            return SJHIP_OK;
+            (void)list_layout(Carve(part->d_list.p), s.records, s.elems, s.bytes, strings, &o);
+            count[RECORDS] = s.records, count[ELEMS] = s.elems, count[BYTES] = s.bytes;
+            src[0] = o.off, src[1] = o.status, src[2] = strings ? o.soff : o.values, src[3] = o.data;
         },
-        [&](size_t k, sjhip_ctx *) {  // the offsets of a later shard: from the end of the shards in front of it
-            if (elem_at[k])
-                for (size_t i = rec_at[k]; i < rec_at[k + 1]; i++) list_offsets[i] += elem_at[k];
-            if (strings && byte_at[k])
-                for (size_t i = elem_at[k]; i < elem_at[k + 1]; i++) inner[i] += byte_at[k];
+        [&](const size_t *total) {
+            const bool null = !list_offsets || !status || (!inner && (strings || total[ELEMS])) || (strings && !data && total[BYTES]);
+            return null ? SJHIP_ERR_ARG : SJHIP_OK;
         });
-    if (rc) return rc;
-    list_offsets[rec_at[P]] = elem_at[P];
-    if (strings) inner[elem_at[P]] = byte_at[P];
-    return query_bounds_check(ctx);  // (debug build: the gather kernel has finished here)
+    return rc ? rc : query_bounds_check(ctx);  // (debug build: the gather kernel has finished here)
 }
 int sjhip_fetch_path_list(sjhip_ctx *ctx, uint64_t *list_offsets, void *values, uint8_t *status) {
     return list_fetch(ctx, false, list_offsets, (uint64_t *)values, nullptr, status);
@@ -1555,6 +1607,77 @@ static size_t table_data_layout(Carve c, uint32_t n_cols, const uint8_t *kind, c
     for (uint32_t j = 0; j < n_cols; j++) o->data[j] = table_is_string(kind[j]) ? c.take<u8>(bytes[j]) : nullptr;
     return c.used;
 }
+struct TableBuild {
+    using Sizes = ResultState::Table;
+    struct Work { QCol c[TABLE_MAX_COLS]; };  // (of the string columns)
+    static constexpr auto product = &ResultState::table;
+    static constexpr const char *SYNC_MEASURE = "table sync", *SYNC_GATHER = "table gather sync";
+    QTable t;
+    uint32_t n_cols;
+    size_t *records, *bytes;
+    bool is_string(uint32_t j) const { return table_is_string(t.pl.kind[j]); }
+    size_t work(Carve c, uint32_t n, Work *w, unsigned long long **totals) const {
+        *totals = c.take<unsigned long long>(4 * TABLE_MAX_COLS);  // (col_scan leaves column j's bytes in entry 4 j + 2)
+        for (uint32_t j = 0; j < n_cols; j++)
+            if (is_string(j)) col_work(c, n, &w->c[j]);
+        return c.used;
+    }
+    // d_table for the record count; the walk, which fills it and the string columns' lengths; their scans
+    int measure(sjhip_ctx *ctx, sjhip_ctx *part, const QView &q, uint32_t n, const Work &w, size_t work_bytes, unsigned long long *totals) const {
+        TableOut o;
+        size_t out_bytes = 0;
+        const int rc = reserve_layout(part, part->d_table, [&](Carve cv) { return table_layout(cv, n, n_cols, t.pl.kind, &o); }, &out_bytes);
+        if (rc) return rc;
+        u8 *const out = (u8 *)part->d_table.p, *const kat = (u8 *)part->d_kat.p;
+        QTable tk = t;
+        tk.out = SJ_ARR(out, out_bytes, A_TABLE_OUT);
+        tk.work = SJ_ARR(kat, work_bytes, A_TABLE_WORK);
+        for (uint32_t j = 0; j < n_cols; j++) {
+            const bool str = is_string(j);
+            tk.a_off[j] = str ? (u64)((u8 *)w.c[j].idx - kat) : (u64)(o.val[j] - out);
+            tk.b_off[j] = str ? (u64)((u8 *)w.c[j].off - kat) : 0;
+            tk.st_off[j] = str ? (u64)(w.c[j].status - kat) : (u64)(o.status[j] - out);
+        }
+        hipLaunchKernelGGL(k_q_table_walk, dim3((n + 1u + 255) / 256), dim3(256), 0, part->stream, q, tk);
+        for (uint32_t j = 0; j < n_cols; j++)
+            if (is_string(j)) col_scan(part, n, w.c[j], totals + 4 * j);
+        HIPCHK(hipGetLastError(), "table launch");
+        HIPCHK(hipMemcpyAsync(part->h_scratch + 512, totals, 4 * TABLE_MAX_COLS * 8, hipMemcpyDeviceToHost, part->stream), "D2H table bytes");
+        return SJHIP_OK;
+    }
+    Sizes sizes_of(size_t n, const unsigned long long *h) const {
+        Sizes s;
+        s.records = n, s.n_cols = n_cols;
+        for (uint32_t j = 0; j < n_cols; j++) {
+            s.kind[j] = t.pl.kind[j];
+            s.bytes[j] = is_string(j) ? (size_t)h[4 * j + 2] : 0;
+        }
+        return s;
+    }
+    void add(Sizes *tot, const Sizes &s) const {
+        tot->records += s.records;
+        for (uint32_t j = 0; j < n_cols; j++) tot->bytes[j] += s.bytes[j];
+    }
+    // the gathers of the string columns, into the part's d_tabledata
+    int gather(sjhip_ctx *ctx, sjhip_ctx *part, const QView &q, uint32_t n, const Work &w, const Sizes &s) const {
+        TableOut o;
+        const int rc = reserve_layout(part, part->d_tabledata, [&](Carve cv) { return table_data_layout(cv, n_cols, s.kind, s.bytes, &o); });
+        if (rc) return rc;
+        (void)table_layout(Carve(part->d_table.p), n, n_cols, s.kind, &o);
+        for (uint32_t j = 0; j < n_cols; j++) {
+            if (!is_string(j)) continue;
+            u8 *const data = o.data[j];
+            col_gather(part, q, n, w.c[j], o.off[j], o.status[j], SJ_ARR(data, s.bytes[j], A_TABLE_DATA));
+        }
+        HIPCHK(hipGetLastError(), "table gather launch");
+        return SJHIP_OK;
+    }
+    void finish(Sizes *total) const {
+        total->n_cols = n_cols, *records = total->records;
+        memcpy(total->kind, t.pl.kind, n_cols);
+        for (uint32_t j = 0; j < n_cols; j++) bytes[j] = total->bytes[j];
+    }
+};
 
 int sjhip_extract_table(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, const uint32_t *path_lens, const int *kinds,
                         uint32_t n_cols, size_t *records, size_t *bytes) {
@@ -1563,163 +1686,45 @@ int sjhip_extract_table(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key
         ctx_set_error(ctx, "sjhip_extract_table: a null argument");
         return SJHIP_ERR_ARG;
     }
-    QTable t;
+    TableBuild p;
+    p.n_cols = n_cols, p.records = records, p.bytes = bytes;
     uint8_t blob[TABLE_MAX_BYTES];
     uint32_t blob_len = 0, bad_col = 0;
-    const int why = table_plan(keys, key_lens, path_lens, kinds, n_cols, &t.pl, blob, &blob_len, &bad_col);
+    const int why = table_plan(keys, key_lens, path_lens, kinds, n_cols, &p.t.pl, blob, &blob_len, &bad_col);
     if (why) {
         ctx_set_error(ctx, "sjhip_extract_table: %s (%u columns, found at column %u)", table_plan_error(why), n_cols, bad_col);
         return SJHIP_ERR_ARG;
     }
-    ctx->res.begin_table();  // (the last table is replaced, whatever happens below)
-    std::vector<sjhip_ctx *> parts;
-    int rc = query_parts(ctx, blob, blob_len, &NO_VALUE, 0, &parts);
-    if (rc) return rc;
-    const uint8_t *kind = t.pl.kind;
-    std::vector<std::vector<QCol>> cols(parts.size(), std::vector<QCol>(n_cols));
-    std::vector<ResultState::Table> sizes(parts.size());
-    auto tiles_of = [](uint32_t n) { return (n + 1u + QTILE - 1) / QTILE; };
-    auto work = [&](Carve c, uint32_t n, QCol *col, unsigned long long **totals) {
-        *totals = c.take<unsigned long long>(4 * TABLE_MAX_COLS);  // (k_tw_scan_sums leaves column j's bytes in entry 4 j + 2)
-        for (uint32_t j = 0; j < n_cols; j++) {
-            if (!table_is_string(kind[j])) continue;
-            col[j].idx = c.take<u64>(n);
-            col[j].off = c.take<u64>((size_t)n + 1);
-            col[j].status = c.take<u8>(n);
-            col[j].tiles = c.take<unsigned long long>(tiles_of(n));
-        }
-        return c.used;
-    };
-    // the walk, and the scans of the string columns' lengths, on every part, each on its own stream; then the totals
-    ResultState::Table total;
-    rc = query_over_parts(ctx, parts, blob, blob_len, &NO_VALUE, 0, "table sync",
-        [&](uint32_t n) {
-            std::vector<QCol> c(n_cols);
-            unsigned long long *totals;
-            return work(Carve(), n, c.data(), &totals) + 64;
-        },
-        [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
-            TableOut o;
-            const size_t out_bytes = table_layout(Carve(), n, n_cols, kind, &o);
-            const int rc = arena_reserve(part, part->d_table, out_bytes + 64);
-            if (rc) return rc;
-            (void)table_layout(Carve(part->d_table.p), n, n_cols, kind, &o);
-            QCol *c = cols[k].data();
-            unsigned long long *totals, *const none = nullptr;
-            const size_t work_bytes = work(Carve(part->d_kat.p), n, c, &totals);
-            QTable tk = t;
-            tk.out = SJ_ARR((u8 *)part->d_table.p, out_bytes, A_TABLE_OUT);
-            tk.work = SJ_ARR((u8 *)part->d_kat.p, work_bytes, A_TABLE_WORK);
-            for (uint32_t j = 0; j < n_cols; j++) {
-                const bool str = table_is_string(kind[j]);
-                tk.a_off[j] = str ? (u64)((u8 *)c[j].idx - (u8 *)part->d_kat.p) : (u64)(o.val[j] - (u8 *)part->d_table.p);
-                tk.b_off[j] = str ? (u64)((u8 *)c[j].off - (u8 *)part->d_kat.p) : 0;
-                tk.st_off[j] = str ? (u64)(c[j].status - (u8 *)part->d_kat.p) : (u64)(o.status[j] - (u8 *)part->d_table.p);
-            }
-            const u32 m = n + 1u, tiles = tiles_of(n);
-            hipLaunchKernelGGL(k_q_table_walk, dim3((m + 255) / 256), dim3(256), 0, part->stream, q, tk);
-            for (uint32_t j = 0; j < n_cols; j++) {
-                if (!table_is_string(kind[j])) continue;
-                hipLaunchKernelGGL(k_q_col_tile_sums, dim3(tiles), dim3(QT), 0, part->stream, c[j], m);
-                hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, part->stream, none, none, c[j].tiles, tiles, totals + 4 * j);
-                hipLaunchKernelGGL(k_q_col_tile_apply, dim3(tiles), dim3(QT), 0, part->stream, c[j], m);
-            }
-            HIPCHK(hipGetLastError(), "table launch");
-            HIPCHK(hipMemcpyAsync(part->h_scratch + 512, totals, 4 * TABLE_MAX_COLS * 8, hipMemcpyDeviceToHost, part->stream),
-                   "D2H table bytes");
-            return SJHIP_OK;
-        },
-        [&](size_t k, sjhip_ctx *part) {
-            const unsigned long long *h = (const unsigned long long *)(part->h_scratch + 512);
-            ResultState::Table &s = sizes[k];
-            s.records = (size_t)part->q_records + 1u;
-            s.n_cols = n_cols;
-            total.records += s.records;
-            for (uint32_t j = 0; j < n_cols; j++) {
-                s.kind[j] = kind[j];
-                s.bytes[j] = table_is_string(kind[j]) ? (size_t)h[4 * j + 2] : 0;
-                total.bytes[j] += s.bytes[j];
-            }
-        });
-    if (rc) return rc;
-    // the gathers of the string columns on every part, into the part's d_tabledata (the work arrays stay where they are: nothing
-    // more of d_kat is asked for)
-    rc = query_over_parts(ctx, parts, blob, blob_len, &NO_VALUE, 0, "table gather sync", [](uint32_t) { return (size_t)0; },
-        [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
-            TableOut o;
-            const int rc = arena_reserve(part, part->d_tabledata, table_data_layout(Carve(), n_cols, kind, sizes[k].bytes, &o) + 64);
-            if (rc) return rc;
-            (void)table_layout(Carve(part->d_table.p), n, n_cols, kind, &o);
-            (void)table_data_layout(Carve(part->d_tabledata.p), n_cols, kind, sizes[k].bytes, &o);
-            for (uint32_t j = 0; j < n_cols; j++) {
-                if (!table_is_string(kind[j])) continue;
-                u8 *const data = o.data[j];
-                hipLaunchKernelGGL(k_q_col_gather, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, cols[k][j], o.off[j],
-                                   o.status[j], SJ_ARR(data, sizes[k].bytes[j], A_TABLE_DATA));
-            }
-            HIPCHK(hipGetLastError(), "table gather launch");
-            return SJHIP_OK;
-        },
-        [](size_t, sjhip_ctx *) {});
-    if (rc) return rc;
-    total.n_cols = n_cols;
-    memcpy(total.kind, kind, n_cols);
-    *records = total.records;
-    for (uint32_t j = 0; j < n_cols; j++) bytes[j] = total.bytes[j];
-    bool ok = true;
-    for (size_t k = 0; k < parts.size(); k++) ok &= parts[k]->res.publish_table(sizes[k]);
-    if (ctx->res.sharded()) ok &= ctx->res.publish_table(total);
-    return published(ctx, ok);
+    return build_product(ctx, blob, blob_len, p);
 }
 
 int sjhip_fetch_table_column(sjhip_ctx *ctx, uint32_t col, void *values, uint64_t *offsets, uint8_t *data, uint8_t *status) {
     if (!ctx) return SJHIP_ERR_ARG;
-    if (!ctx->res.table()) {  // none was built, or a parse (or sjhip_ctx_trim) came after it
-        ctx_set_error(ctx, "no table on the device (sjhip_fetch_table_column follows sjhip_extract_table, with no parse in between)");
-        return SJHIP_ERR_ARG;
-    }
-    const ResultState::Table &all = ctx->res.table_sizes();
+    if (!ctx->res.table.exists())
+        return no_product(ctx, "no table on the device (sjhip_fetch_table_column follows sjhip_extract_table, with no parse in between)");
+    const ResultState::Table &all = ctx->res.table.sizes();
     if (col >= all.n_cols) {
         ctx_set_error(ctx, "sjhip_fetch_table_column: column %u of a table of %u columns", col, all.n_cols);
         return SJHIP_ERR_ARG;
     }
     const int kind = all.kind[col];
     const bool str = table_is_string(kind);
-    const std::vector<sjhip_ctx *> parts = result_parts(ctx);
-    const size_t P = parts.size();
-    std::vector<size_t> rec_at(P + 1, 0), byte_at(P + 1, 0);  // where every part's records and bytes start
-    for (size_t k = 0; k < P; k++) {
-        rec_at[k + 1] = rec_at[k] + parts[k]->res.table_sizes().records;
-        byte_at[k + 1] = byte_at[k] + parts[k]->res.table_sizes().bytes[col];
-    }
-    if (!status || (str ? !offsets || (!data && byte_at[P]) : !values)) {
-        ctx_set_error(ctx, "sjhip_fetch_table_column: a null destination for column %u (%s)", col, str ? "offsets, data, status" : "values, status");
-        return SJHIP_ERR_ARG;
-    }
-    const size_t width = kind == SJHIP_COL_BOOL ? 1u : 8u;
-    const int rc = walk_parts(ctx, parts, "table fetch sync",
-        [&](size_t k, sjhip_ctx *part) -> int {
-            const ResultState::Table &s = part->res.table_sizes();
-            const size_t n = s.records, nb = s.bytes[col];
+    const Seg status_seg = {status, 1, RECORDS, NO_DOM, false, "D2H table status"};
+    const Seg num_segs[] = {status_seg, {values, kind == SJHIP_COL_BOOL ? 1u : 8u, RECORDS, NO_DOM, false, "D2H table values"}};
+    const Seg str_segs[] = {status_seg, {offsets, 8, RECORDS, BYTES, false, "D2H table offsets"}, {data, 1, BYTES, NO_DOM, true, "D2H table bytes"}};
+    const int rc = fetch_joined(ctx, "table fetch sync", str ? str_segs : num_segs, str ? 3 : 2,
+        [&](sjhip_ctx *part, size_t *count, const void **src) {
+            const ResultState::Table &s = part->res.table.sizes();
             TableOut o;
-            (void)table_layout(Carve(part->d_table.p), n, s.n_cols, s.kind, &o);
+            (void)table_layout(Carve(part->d_table.p), s.records, s.n_cols, s.kind, &o);
             (void)table_data_layout(Carve(part->d_tabledata.p), s.n_cols, s.kind, s.bytes, &o);
-            HIPCHK(hipMemcpyAsync(status + rec_at[k], o.status[col], n, hipMemcpyDeviceToHost, part->stream), "D2H table status");
-            if (!str) {
-                HIPCHK(hipMemcpyAsync((u8 *)values + rec_at[k] * width, o.val[col], n * width, hipMemcpyDeviceToHost, part->stream),
-                       "D2H table values");
-                return SJHIP_OK;
-            }
-            // every part's offsets but its last (the next part's first, rebased below)
-            HIPCHK(hipMemcpyAsync(offsets + rec_at[k], o.off[col], n * 8, hipMemcpyDeviceToHost, part->stream), "D2H table offsets");
-            if (nb) HIPCHK(hipMemcpyAsync(data + byte_at[k], o.data[col], nb, hipMemcpyDeviceToHost, part->stream), "D2H table bytes");
-            return SJHIP_OK;
+            count[RECORDS] = s.records, count[BYTES] = s.bytes[col];
+            src[0] = o.status[col], src[1] = str ? (const void *)o.off[col] : o.val[col], src[2] = o.data[col];
         },
-        [&](size_t k, sjhip_ctx *) {
-            if (str && byte_at[k])  // the offsets of a later shard: from the end of the shards in front of it
-                for (size_t i = rec_at[k]; i < rec_at[k + 1]; i++) offsets[i] += byte_at[k];
+        [&](const size_t *total) {
+            if (status && (str ? offsets && (data || !total[BYTES]) : values != nullptr)) return SJHIP_OK;
+            ctx_set_error(ctx, "sjhip_fetch_table_column: a null destination for column %u (%s)", col, str ? "offsets, data, status" : "values, status");
+            return SJHIP_ERR_ARG;
         });
-    if (rc) return rc;
-    if (str) offsets[rec_at[P]] = byte_at[P];
-    return query_bounds_check(ctx);  // (debug build: the kernels of sjhip_extract_table have finished here)
+    return rc ? rc : query_bounds_check(ctx);  // (debug build: the kernels of sjhip_extract_table have finished here)
 }

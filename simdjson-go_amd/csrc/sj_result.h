@@ -8,7 +8,7 @@
 //   * the tenant of the shared arenas d_q / d_qtape / d_qstrings: the filtered result, the serialized columns or the MarshalJSON text
 //     -- one value, so at most one of them is resident;
 //   * the string column (d_col), the list column (d_list, numbers or strings) and the table (d_table, d_tabledata), independent of
-//     each other and of the tenant.
+//     each other and of the tenant: one mechanism (Product) used three times.
 // The rule: a parse call, successful or not, drops the previous result and everything derived from it (begin_parse); so do
 // sjhip_deserialize, sjhip_ctx_trim and the stage-1-only calls (drop_result).  A product exists from its publish to the next
 // transition that drops it; a product is only published on a resident result, and a result of no tape words is no result.
@@ -23,11 +23,10 @@ namespace sj {
 class ResultState {
 public:
     enum class Tenant : uint8_t { None, Filtered, Serialized, Marshaled };
-    enum class List : uint8_t { None, Numbers, Strings };
     struct Filtered { size_t tape_len = 0, strings_len = 0; };
     struct Serialized { size_t tags = 0, vals = 0, slen = 0, rest = 0, stream = 0; bool dedup = false; };  // column sizes, framed stream
     struct Column { size_t records = 0, bytes = 0; };
-    struct ListColumn { size_t records = 0, elems = 0, bytes = 0; };
+    struct ListColumn { size_t records = 0, elems = 0, bytes = 0; bool strings = false; };  // (numbers or strings: what was published)
     static constexpr int TABLE_COLS = 16;  // SJHIP_TABLE_MAX_COLS
     struct Table {  // what a fetch of one column needs: its kind, and the text bytes of a string column (0 for the other kinds)
         size_t records = 0;
@@ -40,9 +39,9 @@ public:
     // Every parse entry point, first: nothing of the last result is left.  (The sizes stay: they mean something under their flag only.)
     void begin_parse() {
         parse_ = Parse::None;
-        key_flags_ = packed_ = column_ = table_ = false;
+        key_flags_ = packed_ = false;
         tenant_ = Tenant::None;
-        list_ = List::None;
+        drop_products();
     }
     void drop_result() { begin_parse(); }  // the arenas of the result are re-used, freed or overwritten by something that is no parse
     void parse_pending() {  // phase 1 of a parse is queued
@@ -91,25 +90,28 @@ public:
         marshaled_len_ = text_len;
         return true;
     }
-    void begin_column() { column_ = false; }
-    bool publish_column(const Column &c) {  // (an owner: the totals of its shards' columns)
+    // The independent products: a call gives up the last one before anything can fail (begin) and publishes on success, on a
+    // resident or sharded result only (an owner: the joined sizes of its shards' parts); sizes() mean something while exists().
+    template <typename S>
+    class Product {
+        friend class ResultState;  // (publish)
+        bool exists_ = false;
+        S sizes_;
+
+    public:
+        void begin() { exists_ = false; }
+        bool exists() const { return exists_; }
+        const S &sizes() const { return sizes_; }
+    };
+    Product<Column> column;
+    Product<ListColumn> list;
+    Product<Table> table;
+    void drop_products() { column.begin(), list.begin(), table.begin(); }  // (a stage-1-only call on a sharded result: api.hip)
+    template <typename S>
+    bool publish(Product<S> ResultState::*product, const S &sizes) {  // publish(&ResultState::column, {records, bytes})
         if (!resident() && !sharded()) return false;
-        column_ = true;
-        column_sizes_ = c;
-        return true;
-    }
-    void begin_list() { list_ = List::None; }
-    bool publish_list(bool strings, const ListColumn &l) {
-        if (!resident() && !sharded()) return false;
-        list_ = strings ? List::Strings : List::Numbers;
-        list_sizes_ = l;
-        return true;
-    }
-    void begin_table() { table_ = false; }
-    bool publish_table(const Table &t) {  // (an owner: the joined sizes of its shards' tables)
-        if (!resident() && !sharded()) return false;
-        table_ = true;
-        table_sizes_ = t;
+        (this->*product).exists_ = true;
+        (this->*product).sizes_ = sizes;
         return true;
     }
 
@@ -123,9 +125,7 @@ public:
     bool filtered() const { return tenant_ == Tenant::Filtered; }
     bool serialized() const { return tenant_ == Tenant::Serialized; }
     bool marshaled() const { return tenant_ == Tenant::Marshaled; }
-    bool column() const { return column_; }
-    bool list(bool strings) const { return list_ == (strings ? List::Strings : List::Numbers); }
-    bool table() const { return table_; }
+    bool list_of(bool strings) const { return list.exists() && list.sizes().strings == strings; }  // a list column of this kind
 
     // ---- what the last publish / parse_done left (meaningful while the predicate beside it holds) ----
     uint64_t tape_base() const { return tape_base_; }
@@ -134,23 +134,16 @@ public:
     const Filtered &filtered_sizes() const { return filtered_; }
     const Serialized &serialized_sizes() const { return serialized_; }
     size_t marshaled_len() const { return marshaled_len_; }
-    const Column &column_sizes() const { return column_sizes_; }
-    const ListColumn &list_sizes() const { return list_sizes_; }
-    const Table &table_sizes() const { return table_sizes_; }
 
 private:
     enum class Parse : uint8_t { None, Pending, Whole, Shard, Sharded };
     Parse parse_ = Parse::None;
-    bool key_flags_ = false, packed_ = false, column_ = false, table_ = false;
+    bool key_flags_ = false, packed_ = false;
     Tenant tenant_ = Tenant::None;
-    List list_ = List::None;
     uint64_t tape_base_ = 0, strings_base_ = 0, msg_base_ = 0;
     Filtered filtered_;
     Serialized serialized_;
     size_t marshaled_len_ = 0;
-    Column column_sizes_;
-    ListColumn list_sizes_;
-    Table table_sizes_;
 };
 
 }  // namespace sj

@@ -1,4 +1,5 @@
 """Fixture loading for tests / bench: tests/data/<name>.json.xz (see tools/make_fixtures.py)."""
+import contextlib
 import functools
 import lzma
 import os
@@ -14,3 +15,16 @@ ALL = ["apache_builds", "canada", "citm_catalog", "github_events", "gsoc-2018", 
 def load(name: str) -> bytes:
     with open(os.path.join(DATA, name + ".json.xz"), "rb") as f:
         return lzma.decompress(f.read())
+
+
+@contextlib.contextmanager
+def nd_shard_limits(limit_bytes, shard_bytes):
+    """An ND message of more than limit_bytes (and more than 1 MiB) parsed inside the block is cut into shards of about
+    shard_bytes (SJHIP_ND_LIMIT_BYTES / SJHIP_ND_SHARD_BYTES, parse_api.hip): the sharded path on documents of a few megabytes.
+    The variables are read by the parse call, so the parse belongs inside the block; the result stays sharded after it."""
+    os.environ["SJHIP_ND_LIMIT_BYTES"] = str(limit_bytes)
+    os.environ["SJHIP_ND_SHARD_BYTES"] = str(shard_bytes)
+    try:
+        yield
+    finally:
+        del os.environ["SJHIP_ND_LIMIT_BYTES"], os.environ["SJHIP_ND_SHARD_BYTES"]

@@ -2,7 +2,6 @@
 conversions of tests/column_walk.py over the oracle's parse -- values as bits, statuses and string columns byte for byte --
 and against the existing path queries on the same paths (count_where_path, find_path); a sharded result against the same
 message parsed whole; the lifecycle of the string column."""
-import os
 import random
 import struct
 
@@ -176,13 +175,9 @@ def test_sharded_result_equals_whole():
         want = {}
         for path in paths:
             want[path] = ([one.extract_path(path, k) for k in KINDS], [one.extract_path_strings(path, cvt=c) for c in (False, True)])
-        os.environ["SJHIP_ND_LIMIT_BYTES"] = str(2 << 20)
-        os.environ["SJHIP_ND_SHARD_BYTES"] = str(1 << 20)
-        try:
+        with fixtures.nd_shard_limits(2 << 20, 1 << 20):
             many = sjhip.Context(0)
             many.parse(doc, ndjson=True, copy_strings=copy)
-        finally:
-            del os.environ["SJHIP_ND_LIMIT_BYTES"], os.environ["SJHIP_ND_SHARD_BYTES"]
         w = oracle_walk(doc, True, copy)
         for path in paths:
             nums, strs = want[path]

@@ -4,7 +4,6 @@ statuses, bit for bit, in both copy modes: generated records, long and skewed ar
 statuses, a sharded result against the same message parsed whole, the lifecycle of the list column, and the existing path queries
 on the same paths."""
 import json
-import os
 import random
 import re
 
@@ -210,13 +209,9 @@ def test_sharded_result_equals_whole():
         one.parse(doc, ndjson=True, copy_strings=copy)
         want = {p: ([one.extract_path_list(p, k) for k in KINDS], [one.extract_path_list_strings(p, cvt=c) for c in (False, True)])
                 for p in paths}
-        os.environ["SJHIP_ND_LIMIT_BYTES"] = str(2 << 20)
-        os.environ["SJHIP_ND_SHARD_BYTES"] = str(1 << 20)
-        try:
+        with fixtures.nd_shard_limits(2 << 20, 1 << 20):
             many = sjhip.Context(0)
             many.parse(doc, ndjson=True, copy_strings=copy)
-        finally:
-            del os.environ["SJHIP_ND_LIMIT_BYTES"], os.environ["SJHIP_ND_SHARD_BYTES"]
         w = oracle_walk(doc, True, copy)
         for p in paths:
             nums, strs = want[p]

@@ -4,7 +4,6 @@ untouched) and against the restated conversions of tests/column_walk.py over the
 offsets and bytes; at the wave, block and scan-tile seams; at the limits of depth and width; on a sharded result; and the
 lifecycle of the table among the other products of a context."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -175,13 +174,9 @@ def test_sharded_result_equals_whole():
     for copy in (True, False):
         one.parse(doc, ndjson=True, copy_strings=copy)
         want = one.extract_table(columns)
-        os.environ["SJHIP_ND_LIMIT_BYTES"] = str(2 << 20)
-        os.environ["SJHIP_ND_SHARD_BYTES"] = str(1 << 20)
-        try:
+        with fixtures.nd_shard_limits(2 << 20, 1 << 20):
             many = sjhip.Context(0)
             many.parse(doc, ndjson=True, copy_strings=copy)
-        finally:
-            del os.environ["SJHIP_ND_LIMIT_BYTES"], os.environ["SJHIP_ND_SHARD_BYTES"]
         got = check_table(many, oracle_walk(doc, True, copy), columns, singles=False)
         for c, (path, kind) in enumerate(columns):
             same_column(kind, got[c], want[c], ("whole", c, copy))
