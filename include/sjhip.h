@@ -297,6 +297,38 @@ enum { SJHIP_COL_STRING = 4, SJHIP_COL_STRING_CVT = 5 };
 int sjhip_extract_table(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, const uint32_t *path_lens, const int *kinds,
                         uint32_t n_cols, size_t *records, size_t *bytes /* [n_cols] */);
 int sjhip_fetch_table_column(sjhip_ctx *ctx, uint32_t col, void *values, uint64_t *offsets, uint8_t *data, uint8_t *status);
+/* Rows: the elements of the ARRAY at `path` of every record become the records of the path queries -- the reference's
+ * Iter.FindElement(path...) -> Iter.Array() -> Array.Iter() / Advance over the elements (what {"statuses":[{...}, ...]}, a root array
+ * of objects or an NDJSON line {"order":1,"items":[{...},{...}]} need before anything above can be pointed at their objects).
+ *   sjhip_select_rows     evaluates FindElement + Iter.Array on the root value of every record, as the list columns do, with their
+ *                          status bytes: OK, NOT_FOUND, NOT_OBJECT, NULL for a null element, TYPE for anything else that is not an
+ *                          array.  The direct elements of that array, in document order, are the rows -- scalars, objects and arrays
+ *                          alike; what lies inside an element is not a row.  A record whose status is not OK, or whose array is
+ *                          empty, has no rows.  n_keys == 0 is allowed here, and only here: the array is then the record's root value
+ *                          (keys and key_lens may be NULL).  Paths and limits are otherwise those of sjhip_find_path.  *records = the
+ *                          records, *rows = the rows of all of them together; no rows at all is a legal selection.
+ *   sjhip_fetch_rows      Arrow's list layout over the records: row_offsets[records + 1] (row_offsets[0] = 0; record r owns the rows
+ *                          row_offsets[r] .. row_offsets[r + 1]), row_index[rows] = the tape index of the value of every row
+ *                          (tape[index] is its tag word; in the merged index space on a sharded result), status[records].  Any
+ *                          destination may be NULL: that array is not copied.
+ *   sjhip_select_records  back to one row per record; no error if nothing was selected.
+ * While a selection exists, the calls that evaluate a path on "every record" evaluate it on every ROW instead, the row's value in the
+ * place of the record's root value: sjhip_find_path, sjhip_count_where_path, sjhip_project_keys, sjhip_extract_path,
+ * sjhip_extract_path_strings, sjhip_extract_path_list[_strings] and sjhip_extract_table; their *records and cap_records count rows.
+ * A row that is not an object gets SJHIP_PATH_NOT_OBJECT / SJHIP_COL_NOT_OBJECT, the rule for a root value that is not an object.
+ * With no rows they return *records = 0 and launch nothing.  sjhip_count_where, sjhip_filter_where, the serializer, MarshalJSON and
+ * the stream's filter work on records and ignore the selection.
+ * The selection lives in a device arena of its own (sjhip_ctx_device_bytes counts it, sjhip_ctx_trim frees it): it lasts until the
+ * next parse, the next sjhip_select_rows or sjhip_select_records, is dropped by everything that drops the other products, survives
+ * the string column, the list column, the table, the filter, the serializer and MarshalJSON, and they survive it.  A column, list or
+ * table built under a selection is materialised data: it stays fetchable after the selection has changed or gone.  sjhip_fetch_rows
+ * without a selection is SJHIP_ERR_ARG and sjhip_last_error says "no row selection".  On a sharded ND result every shard selects its
+ * rows (shards are cut at record boundaries: an array never spans two) and the fetch joins them.  The cost is a fixed number of
+ * passes over the tape, whatever the arrays' lengths and whatever the elements hold. */
+int sjhip_select_rows(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, size_t *records, size_t *rows);
+int sjhip_fetch_rows(sjhip_ctx *ctx, uint64_t *row_offsets /* [records + 1] */, uint64_t *row_index /* [rows] */,
+                     uint8_t *status /* [records] */);
+int sjhip_select_records(sjhip_ctx *ctx);
 
 /* ---- Serializer.Serialize on the device (parsed_serialize.go:200-431, format version 3) -----------------------------
  * Splits the device-resident tape of the last parse (SJHIP_FLAG_COPY_STRINGS) into the reference's three columns --

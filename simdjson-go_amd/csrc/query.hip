@@ -50,12 +50,20 @@ struct QView {
     // of such a shard holds `tape`, `strings` and `msg` as pointers moved DOWN by those bases, so that every index a tape word holds
     // -- and every index the path queries hand out -- is used as it stands; only the record bounds (nl_off: local) add tape_base.
     u64 tape_base;     // 0 for an unsharded result; tape_len: END of this context's stretch in the merged index space
+    // The row selection of the context (sjhip_select_rows): the tape index of the value of every row of this part, in document
+    // order.  Null: there is none, and the rows of a query are the records.  The filter and countWhere never see it (make_view).
+    Arr<const u64> rows;
+    u64 n_rows;
     u8 key[QMAX], val[QMAX];
     u32 klen, vlen;
 };
 
 __device__ __forceinline__ u64 rec_open(const QView &q, u32 r) { return q.tape_base + (r == 0 ? 0u : q.nl_off[r - 1] + 1u); }
 __device__ __forceinline__ u64 rec_close(const QView &q, u32 r) { return r == q.R ? q.tape_len - 1u : q.tape_base + q.nl_off[r]; }
+// what a path query runs on: the rows of the selection, or the records -- how many there are, and the tape index of the value of
+// row r: the row's element, or the record's root value
+__device__ __forceinline__ u32 q_rows(const QView &q) { return q.rows ? (u32)q.n_rows : q.R + 1u; }
+__device__ __forceinline__ u64 row_value(const QView &q, u32 r) { return q.rows ? q.rows[r] : rec_open(q, r) + 1u; }
 
 __device__ __forceinline__ const u8 *str_bytes(const QView &q, u64 word, u64 len) {
     const u64 p = word & TW_PAYLOAD;
@@ -86,15 +94,15 @@ __device__ __forceinline__ u64 skip_value(u64 v, u64 vw) {  // index behind the 
     if (vt == '{' || vt == '[') return vw & TW_PAYLOAD;  // behind the matching close
     return two_word_tag(vw) ? v + 2 : v + 1;
 }
-// FindElement on record r: into the root, into objects, not into arrays; the first member with the key wins at every
+// FindElement on row r (record r without a row selection): into the root, into objects, not into arrays; the first member with the key wins at every
 // level.  Returns the tape index of the element's value, SJHIP_PATH_NOT_FOUND (ErrPathNotFound) or SJHIP_PATH_NOT_OBJECT
 // ("type ... found before object was found" / "value of key ... is not an object").
 __device__ u64 record_find_path(const QView &q, const QPath &pth, u32 r) {
-    const u64 o = rec_open(q, r);
-    const u64 w = q.tape[o + 1];
+    const u64 o = row_value(q, r);
+    const u64 w = q.tape[o];
     if ((w >> 56) != '{') return SJHIP_PATH_NOT_OBJECT;
     u64 end = (w & TW_PAYLOAD) - 1;  // index of the closing '}'
-    u64 i = (u64)o + 2;
+    u64 i = o + 1;
     u32 seg = 0;
     while (i < end) {
         const u64 kw = q.tape[i], kl = q.tape[i + 1];  // member key
@@ -391,25 +399,25 @@ __global__ __launch_bounds__(256) void k_q_copy(QView q, QRec o, u64 *out_tape, 
 // ---- the kernels of the path queries ------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_q_find_path(QView q, QPath pth, u64 *out) {
     const u32 r = blockIdx.x * 256 + threadIdx.x;
-    if (r <= q.R) out[r] = record_find_path(q, pth, r);
+    if (r < q_rows(q)) out[r] = record_find_path(q, pth, r);
 }
 __global__ __launch_bounds__(256) void k_q_count_path(QView q, QPath pth, int op, u64 want, unsigned long long *count) {
     const u32 r = blockIdx.x * 256 + threadIdx.x;
-    count_ballot(r <= q.R && record_is(q, pth, r, op, want), count);
+    count_ballot(r < q_rows(q) && record_is(q, pth, r, op, want), count);
 }
 // ForEach(fn, onlyKeys) on the root object of record r: the members whose key is in the set, in document order, until as
 // many members as the set has keys have been delivered (parsed_object.go:190-194: a key that occurs twice counts twice).
 // out[r * n + j] = key number << 56 | tape index of the value of the j-th delivered member; ~0: no further member
 __global__ __launch_bounds__(256) void k_q_project(QView q, QPath set, u64 *out) {
     const u32 r = blockIdx.x * 256 + threadIdx.x;
-    if (r > q.R) return;
+    if (r >= q_rows(q)) return;
     u64 *dst = out + (u64)r * set.n;
     u32 n = 0;
-    const u64 o = rec_open(q, r);
-    const u64 w = q.tape[o + 1];
+    const u64 o = row_value(q, r);
+    const u64 w = q.tape[o];
     if ((w >> 56) == '{') {
         const u64 end = (w & TW_PAYLOAD) - 1;
-        for (u64 i = (u64)o + 2; i < end && n < set.n;) {
+        for (u64 i = o + 1; i < end && n < set.n;) {
             const u64 v = i + 2;
             for (u32 j = 0; j < set.n; j++)
                 if (key_is(q, set, j, q.tape[i], q.tape[i + 1])) {
@@ -430,7 +438,7 @@ __device__ __forceinline__ int path_status(u64 v) {
 }
 __global__ __launch_bounds__(256) void k_q_extract(QView q, QPath pth, int kind, void *values, u8 *status) {
     const u32 r = blockIdx.x * 256 + threadIdx.x;
-    if (r > q.R) return;
+    if (r >= q_rows(q)) return;
     const u64 v = record_find_path(q, pth, r);
     u64 x = 0;
     const int st = v < SJHIP_PATH_NOT_OBJECT ? element_to(q, v, kind, &x) : path_status(v);
@@ -476,8 +484,8 @@ __device__ __forceinline__ int element_text_len(const QView &q, u64 v, bool cvt,
 }
 __global__ __launch_bounds__(256) void k_q_col_len(QView q, QPath pth, u32 cvt, QCol c) {
     const u32 r = blockIdx.x * 256 + threadIdx.x;
-    if (r > q.R) {
-        if (r == q.R + 1) c.off[r] = 0;
+    if (r >= q_rows(q)) {
+        if (r == q_rows(q)) c.off[r] = 0;
         return;
     }
     const u64 v = record_find_path(q, pth, r);
@@ -501,13 +509,13 @@ __global__ __launch_bounds__(256) void k_q_col_gather(QView q, QCol c, u64 *out_
     const int lane = threadIdx.x & 63;
     u64 o = 0, len = 0, w = 0;
     bool wide = false;
-    if (r <= q.R) {
+    if (r < q_rows(q)) {
         o = c.off[r];
         len = c.off[r + 1] - o;
         const u8 st = c.status[r];
         out_off[r] = o;
         out_status[r] = st;
-        if (r == q.R) out_off[r + 1] = o + len;
+        if (r + 1 == q_rows(q)) out_off[r + 1] = o + len;
         if (st == SJHIP_COL_OK && len) {
             const u64 v = c.idx[r];
             w = q.tape[v];
@@ -629,12 +637,12 @@ __device__ __forceinline__ int wave_list_measure(const QView &q, u64 v, u64 clos
     return SJHIP_COL_OK;
 }
 __device__ __forceinline__ void list_measure_store(const QView &q, const QList &c, u32 r, u64 v, int st, u64 cnt, u64 bytes) {
-    if (r <= q.R) {
+    if (r < q_rows(q)) {
         c.idx[r] = v;
         c.cnt[r] = st == SJHIP_COL_OK ? cnt : 0;
         if (c.bytes) c.bytes[r] = st == SJHIP_COL_OK ? bytes : 0;
         c.status[r] = (u8)st;
-    } else if (r == q.R + 1) {
+    } else if (r == q_rows(q)) {
         c.cnt[r] = 0;
         if (c.bytes) c.bytes[r] = 0;
     }
@@ -645,7 +653,7 @@ __global__ __launch_bounds__(256) void k_q_list_measure(QView q, QPath pth, int 
     u64 v = 0, close = 0, cnt = 0, bytes = 0;
     int st = SJHIP_COL_NOT_FOUND;
     bool wide = false;
-    if (r <= q.R) {
+    if (r < q_rows(q)) {
         st = record_array(q, pth, r, &v, &close);
         if (st == SJHIP_COL_OK) {
             wide = close - v - 1 > 2 * LIST_SHORT;
@@ -670,7 +678,7 @@ __global__ __launch_bounds__(256) void k_q_list_measure_cvt(QView q, QPath pth, 
     const u32 r = blockIdx.x * 256 + threadIdx.x;
     u64 v = 0, close = 0, cnt = 0, bytes = 0;
     int st = SJHIP_COL_NOT_FOUND;
-    if (r <= q.R) {
+    if (r < q_rows(q)) {
         st = record_array(q, pth, r, &v, &close);
         for (u64 p = v + 1; st == SJHIP_COL_OK && p < close;) {
             u64 len;
@@ -697,12 +705,12 @@ __global__ __launch_bounds__(256) void k_q_list_gather_num(QView q, QList c, int
     const int lane = threadIdx.x & 63;
     u64 o = 0, cnt = 0, v = 0;
     bool wide = false;
-    if (r <= q.R) {
+    if (r < q_rows(q)) {
         o = c.cnt[r];
         cnt = c.cnt[r + 1] - o;
         out_off[r] = o;
         out_status[r] = c.status[r];
-        if (r == q.R) out_off[r + 1] = o + cnt;
+        if (r + 1 == q_rows(q)) out_off[r + 1] = o + cnt;
         v = c.idx[r];
         wide = cnt > LIST_SHORT;  // (only an OK record has elements)
         if (!wide)
@@ -735,13 +743,13 @@ __device__ __forceinline__ void list_gather_strings(const QView &q, const QList 
     const int lane = threadIdx.x & 63;
     u64 o = 0, cnt = 0, v = 0, at = 0;
     bool wide = false;
-    if (r <= q.R) {
+    if (r < q_rows(q)) {
         o = c.cnt[r];
         cnt = c.cnt[r + 1] - o;
         at = c.bytes[r];
         out_off[r] = o;
         out_status[r] = c.status[r];
-        if (r == q.R) {
+        if (r + 1 == q_rows(q)) {
             out_off[r + 1] = o + cnt;
             soff[o + cnt] = c.bytes[r + 1];
         }
@@ -868,15 +876,173 @@ struct TableSink {
 __global__ __launch_bounds__(256) void k_q_table_walk(QView q, QTable t) {
     __shared__ u32 s_stack[TABLE_STACK_WORDS * 256];
     const u32 r = blockIdx.x * 256 + threadIdx.x;
-    if (r > q.R) {
-        if (r == q.R + 1)  // entry n of every string column's lengths, as k_q_col_len leaves it
+    if (r >= q_rows(q)) {
+        if (r == q_rows(q))  // entry n of every string column's lengths, as k_q_col_len leaves it
             for (u32 c = 0; c < t.pl.n_cols; c++)
                 if (t.pl.kind[c] > SJHIP_COL_BOOL) *(u64 *)arr_at(t.work, t.b_off[c] + 8ull * r, 8) = 0;
         return;
     }
     const TableView view = {q};
     TableSink sink = {q, t, r};
-    table_walk(view, t.pl, rec_open(q, r), s_stack + threadIdx.x, 256u, sink);
+    table_walk(view, t.pl, row_value(q, r), s_stack + threadIdx.x, 256u, sink);
+}
+
+
+// ---- row selection: the elements of the ARRAY at a path of every record become the rows (sjhip_select_rows) -------------------------
+// The reference's FindElement(path...) -> Iter.Array() -> Array.Iter() / Advance over the elements, for every record at once.  An
+// array runs from 0 to millions of elements and its elements are containers of any size, so the row starts are found by passes
+// over the TAPE, not by a walk of the array:
+//   k_q_rows_records   one lane per record: record_array -- the index of the target '[' and of its ']' (0, 0: no rows), the status
+//   k_q_rows_tile<0>   per 2048-word tile: the sum of the depth deltas of its tag words (+1 for { [, -1 for } ])
+//   k_tw_scan_sums     the depth in front of every tile (the signed deltas wrap correctly in the unsigned sums)
+//   k_q_rows_tile<1>   per tile: its row starts, counted;  k_tw_scan_sums: the row number of the first one, and the total
+//   k_q_rows_tile<2>   the row starts again, written to row_index at their row numbers (the gather: d_rows has that size now)
+//   k_q_rows_offsets   one lane per record: row_offsets[r] = the rows in front of the record (a lower bound in row_index)
+// A word i is a row start iff it is a tag word (the anchor rule of sj_tapewalk.h), its tag is none of } ] r, its depth -- counted
+// from 0 at its record's root value -- is n_keys + 1, and it lies strictly inside the target array of its record.  FindElement
+// descends objects only, so the array at a path of n keys sits at depth exactly n and a word at depth n + 1 inside its range is a
+// direct element, whatever lies inside the elements.  Records are balanced and the roots carry no depth, so the depth is one
+// prefix sum over the whole tape.  A word learns its record by a search of nl_off -- once per lane, then at most one step per
+// word -- and reads the record's range from what the record lanes stored: no bitmap to clear and set, no running maximum to
+// scan.  No lane's work grows with the length of an array.
+// The tiles find the anchor of the tag / raw classification among the 64 words in front of them (tw_local_anchor); a tile that
+// cannot raises totals[3], and then -- decided on the device, nothing waits for the host -- k_q_rows_last / k_q_rows_scan_last
+// compute the global anchors, the depth pass runs again with them and the later passes use them.  Without the flag those three
+// launches end at once.
+struct QRows {
+    u64 *open, *close;            // [n] merged tape index of the record's target '[' and of its ']' (0, 0: the record has no rows)
+    u8 *status;                   // [n]
+    unsigned long long *depth;    // [tiles] sum of the depth deltas of the tile -> the depth in front of it
+    unsigned long long *cnt;      // [tiles] row starts of the tile -> the row number of its first
+    long long *tile_last;         // [tiles] the global anchors (only when a tile asked for them)
+    unsigned long long *totals;   // [1] the rows; [3] != 0: a tile found no anchor among the 64 words in front of it
+    u32 depth_want;               // n_keys + 1
+};
+__global__ __launch_bounds__(256) void k_q_rows_records(QView q, QPath pth, QRows o) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    if (r > q.R) return;
+    u64 v = rec_open(q, r) + 1u, close = 0;  // (an empty path: Iter.Array on the root value itself)
+    int st = SJHIP_COL_OK;
+    if (pth.n) st = record_array(q, pth, r, &v, &close);
+    else {
+        const u64 w = q.tape[v];
+        const u32 t = (u32)(w >> 56);
+        st = t == 'n' ? SJHIP_COL_NULL : (t != '[' ? SJHIP_COL_TYPE : SJHIP_COL_OK);
+        close = (w & TW_PAYLOAD) - 1;
+    }
+    o.open[r] = st == SJHIP_COL_OK ? v : 0;
+    o.close[r] = st == SJHIP_COL_OK ? close : 0;
+    o.status[r] = (u8)st;
+}
+__global__ __launch_bounds__(TW_THREADS) void k_q_rows_last(QView q, QRows o) {
+    __shared__ long long s_w[TW_THREADS / 64];
+    if (o.totals[3] == 0) return;
+    tw_tile_last(arr_raw(q.tape) + q.tape_base, q.tape_len - q.tape_base, o.tile_last, s_w);
+}
+__global__ __launch_bounds__(1024) void k_q_rows_scan_last(QRows o, u32 tiles) {
+    __shared__ long long s_w[16];
+    if (o.totals[3] == 0) return;
+    block1024_scan_array<true>(o.tile_last, tiles, s_w, (int)threadIdx.x);
+}
+// MODE 0: the depth sums (`again`: the second run, with the global anchors, if a tile of the first one asked for them);
+// 1: the row starts counted; 2: written.  Indices are local to the part's tape here; what is stored and compared is merged.
+template <int MODE>
+__global__ __launch_bounds__(TW_THREADS) void k_q_rows_tile(QView q, QRows o, u32 again, Arr<u64> row_index) {
+    __shared__ long long s_l[TW_THREADS / 64];
+    __shared__ unsigned long long s_s[TW_THREADS / 64];
+    __shared__ long long s_carry;
+    const int tid = threadIdx.x;
+    const bool global = MODE == 0 ? again != 0 : o.totals[3] != 0;  // (the first depth pass raises the flag: it must not read it)
+    if (MODE == 0 && again && o.totals[3] == 0) return;
+    const u64 n = q.tape_len - q.tape_base;
+    const u64 base = (u64)blockIdx.x * TW_TILE + (u64)tid * TW_ITEMS;
+    u64 w[TW_ITEMS];
+#pragma unroll
+    for (int k = 0; k < TW_ITEMS; k++) w[k] = base + k < n ? q.tape[q.tape_base + base + k] : 0;
+    long long last = -1;
+#pragma unroll
+    for (int k = 0; k < TW_ITEMS; k++)
+        if (base + k < n && !two_word_tag(w[k])) last = (long long)(base + k);
+    long long anchor = block_excl_max(last, s_l, tid);  // last anchor in front of this thread's words, inside the tile
+    const long long carry = global ? o.tile_last[blockIdx.x]
+                                   : tw_local_anchor(arr_raw(q.tape) + q.tape_base, (u64)blockIdx.x * TW_TILE, tid, &s_carry);
+    if (carry == -2) {  // (block-uniform, and only without the global anchors: the first depth pass) nothing can be classified
+        if (tid == 0) {
+            atomicOr(&o.totals[3], 1ull);
+            o.depth[blockIdx.x] = 0;
+        }
+        return;
+    }
+    anchor = anchor > carry ? anchor : carry;
+    // the thread's tag words: their depth deltas, and -- as a mask -- those whose tag may start a row
+    int delta = 0;
+    u32 tags = 0, opens = 0, closes = 0;
+#pragma unroll
+    for (int k = 0; k < TW_ITEMS; k++) {
+        const u64 i = base + k;
+        if (i >= n) continue;
+        const bool raw = anchor >= 0 && ((((long long)i - anchor - 1) & 1) != 0);
+        if (!two_word_tag(w[k])) anchor = (long long)i;
+        if (raw) continue;
+        const u32 t = (u32)(w[k] >> 56);
+        if (t == '{' || t == '[') opens |= 1u << k;
+        else if (t == '}' || t == ']') closes |= 1u << k;
+        if (t != '}' && t != ']' && t != 'r') tags |= 1u << k;
+    }
+    delta = __popc(opens) - __popc(closes);
+    unsigned long long tot = 0;
+    const unsigned long long ex = block_excl_sum((unsigned long long)(long long)delta, s_s, tid, &tot);
+    if (MODE == 0) {
+        if (tid == 0) o.depth[blockIdx.x] = tot;
+        return;
+    }
+    int depth = (int)(u32)(o.depth[blockIdx.x] + ex);  // in front of this thread's words
+    u32 starts = 0, r = NONE32;
+#pragma unroll
+    for (int k = 0; k < TW_ITEMS; k++) {
+        const u32 bit = 1u << k;
+        if ((tags & bit) && depth == (int)o.depth_want) {
+            const u64 il = base + k;  // (a word inside a record: never a root)
+            if (r == NONE32) {        // the record of the word: the first whose closing root lies behind it
+                u32 lo = 0, hi = q.R;
+                while (lo < hi) {
+                    const u32 mid = lo + (hi - lo) / 2;
+                    if (q.nl_off[mid] < il) lo = mid + 1;
+                    else hi = mid;
+                }
+                r = lo;
+            } else {
+                while (r < q.R && q.nl_off[r] < il) r++;  // (a record is three words or more: two steps at the most per word)
+            }
+            const u64 i = q.tape_base + il;
+            if (o.open[r] < i && i < o.close[r]) starts |= bit;
+        }
+        depth += (int)((opens >> k) & 1u) - (int)((closes >> k) & 1u);
+    }
+    unsigned long long at = block_excl_sum((unsigned long long)__popc(starts), s_s, tid, &tot);
+    if (MODE == 1) {
+        if (tid == 0) o.cnt[blockIdx.x] = tot;
+        return;
+    }
+    at += o.cnt[blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < TW_ITEMS; k++)
+        if (starts & (1u << k)) row_index[at++] = q.tape_base + base + k;
+}
+// row_offsets[r] = the rows in front of record r: the row starts below its opening root (they are in document order)
+__global__ __launch_bounds__(256) void k_q_rows_offsets(QView q, QRows o, Arr<const u64> row_index, u64 rows, u64 *out_off, u8 *out_status) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    if (r > q.R) return;
+    const u64 first = rec_open(q, r);
+    u64 lo = 0, hi = rows;
+    while (lo < hi) {
+        const u64 mid = lo + (hi - lo) / 2;
+        if (row_index[mid] < first) lo = mid + 1;
+        else hi = mid;
+    }
+    out_off[r] = lo;
+    out_status[r] = o.status[r];
+    if (r == q.R) out_off[r + 1] = rows;
 }
 
 }  // namespace
@@ -911,8 +1077,22 @@ static int check_key_value(sjhip_ctx *ctx, const uint8_t *key, size_t klen, cons
     return SJHIP_OK;
 }
 // view of the result held by `part` (ctx itself, or one shard context of ctx's sharded result) with the key and the value of a
-// query (checked by the caller: check_key_value); errors are left in ctx
-static int make_view(sjhip_ctx *ctx, sjhip_ctx *part, const uint8_t *key, size_t klen, const uint8_t *val, size_t vlen, QView *q) {
+// query (checked by the caller: check_key_value); errors are left in ctx.  on_rows: the query runs on the rows of ctx's row
+// selection, if it has one (the filter and countWhere stay on records).
+struct RowsOut { u64 *off, *index; u8 *status; };
+static size_t rows_layout(Carve c, size_t n, size_t rows, RowsOut *o) {  // the selection of a part in its d_rows
+    o->off = c.take<u64>(n + 1);
+    o->status = c.take<u8>(n);
+    o->index = c.take<u64>(rows);
+    return c.used;
+}
+static bool selected(const sjhip_ctx *ctx, bool on_rows) { return on_rows && ctx->res.rows.exists(); }
+// the rows of this part: what a path query of ctx runs over -- the part's rows of the selection, or its records
+static uint32_t part_rows(const sjhip_ctx *ctx, const sjhip_ctx *part, bool on_rows) {
+    return selected(ctx, on_rows) ? (uint32_t)part->res.rows.sizes().rows : part->q_records + 1u;
+}
+static int make_view(sjhip_ctx *ctx, sjhip_ctx *part, const uint8_t *key, size_t klen, const uint8_t *val, size_t vlen, QView *q,
+                     bool on_rows) {
     if (!part->res.resident()) return no_result(ctx);
     const uint32_t *nl = nullptr;
     stage2_records_view(part->d_s2.p, part->p_nlay, &nl);
@@ -927,6 +1107,15 @@ static int make_view(sjhip_ctx *ctx, sjhip_ctx *part, const uint8_t *key, size_t
     q->msg_len = part->p_len;
     q->nl_off = SJ_ARR(nl, part->q_records, A_NL_OFF);
     q->R = part->q_records;
+    q->rows = nullptr;
+    q->n_rows = 0;
+    if (selected(ctx, on_rows)) {
+        const ResultState::Rows &z = part->res.rows.sizes();
+        RowsOut o;
+        (void)rows_layout(Carve(part->d_rows.p), z.records, z.rows, &o);
+        q->rows = SJ_ARR((const u64 *)o.index, z.rows, A_ROWS);
+        q->n_rows = z.rows;
+    }
     memset(q->key, 0, QMAX);
     memset(q->val, 0, QMAX);
     memcpy(q->key, key, klen);
@@ -963,17 +1152,19 @@ static int query_parts(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const ui
     *parts = result_parts(ctx);
     return parts->empty() ? no_result(ctx) : SJHIP_OK;
 }
-// ... and the walk of a query kernel over them: enqueue(k, part, q, n) gets the part's view, its n records and kat_bytes(n) bytes
-// of the part's d_kat; the bounds check of the debug build follows the last wait.
+// ... and the walk of a query kernel over them: enqueue(k, part, q, n) gets the part's view, its n rows (part_rows) and
+// kat_bytes(part, n) bytes of the part's d_kat; a part without rows is passed over -- nothing is launched for it (a grid of 0
+// blocks is a launch error), collect(k, part) still runs.  The bounds check of the debug build follows the last wait.
 template <typename K, typename E, typename C>
 static int query_over_parts(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, const uint8_t *key, size_t klen, const uint8_t *val,
-                            size_t vlen, const char *sync, K kat_bytes, E enqueue, C collect) {
+                            size_t vlen, bool on_rows, const char *sync, K kat_bytes, E enqueue, C collect) {
     const int rc = walk_parts(ctx, parts, sync, [&](size_t k, sjhip_ctx *part) -> int {
         QView q;
-        int rc = make_view(ctx, part, key, klen, val, vlen, &q);
+        int rc = make_view(ctx, part, key, klen, val, vlen, &q, on_rows);
         if (rc) return rc;
-        const uint32_t n = part->q_records + 1u;
-        rc = arena_reserve(part, part->d_kat, kat_bytes(n));
+        const uint32_t n = part_rows(ctx, part, on_rows);
+        if (n == 0) return SJHIP_OK;
+        rc = arena_reserve(part, part->d_kat, kat_bytes(part, n));
         return rc ? rc : enqueue(k, part, q, n);
     }, collect);
     return rc ? rc : query_bounds_check(ctx);
@@ -982,12 +1173,14 @@ static const uint8_t NO_VALUE = 0;  // the value of a query that has none (vlen 
 
 // Runs `launch(part, q, n, d_count)` on every part of ctx's result and adds the 8-byte counts up.
 template <typename F>
-static int count_over_parts(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const uint8_t *val, size_t vlen, uint64_t *count, F launch) {
+static int count_over_parts(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const uint8_t *val, size_t vlen, bool on_rows, uint64_t *count,
+                            F launch) {
     std::vector<sjhip_ctx *> parts;
     const int rc = query_parts(ctx, key, klen, val, vlen, &parts);
     if (rc) return rc;
     uint64_t total = 0;
-    const int rc2 = query_over_parts(ctx, parts, key, klen, val, vlen, "count sync", [](uint32_t) { return (size_t)64; },
+    for (sjhip_ctx *part : parts) *(unsigned long long *)(part->h_scratch + 512) = 0;  // (a part without rows copies nothing back)
+    const int rc2 = query_over_parts(ctx, parts, key, klen, val, vlen, on_rows, "count sync", [](const sjhip_ctx *, uint32_t) { return (size_t)64; },
         [&](size_t, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
             HIPCHK(hipMemsetAsync(part->d_kat.p, 0, 8, part->stream), "count memset");
             launch(part, q, n, (unsigned long long *)part->d_kat.p);
@@ -1011,7 +1204,7 @@ static QPath one_key_path(size_t klen) {
 int sjhip_count_where(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const uint8_t *value, size_t vlen, uint64_t *count) {
     if (!count) return SJHIP_ERR_ARG;
     const QPath pth = one_key_path(klen);
-    return count_over_parts(ctx, key, klen, value, vlen, count, [&](sjhip_ctx *part, const QView &q, uint32_t n, unsigned long long *d) {
+    return count_over_parts(ctx, key, klen, value, vlen, false, count, [&](sjhip_ctx *part, const QView &q, uint32_t n, unsigned long long *d) {
         hipLaunchKernelGGL(k_q_count_path, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, pth, (int)SJHIP_OP_EQ_STRING, (u64)0, d);
     });
 }
@@ -1021,7 +1214,7 @@ int sjhip_filter_where(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const ui
     if (ctx && !ctx->res.whole()) return no_whole_result(ctx, "sjhip_filter_where", "queries follow");  // the unsharded result of ctx itself
     QView q;
     int rc = check_key_value(ctx, key, klen, value, vlen);
-    if (rc == SJHIP_OK) rc = make_view(ctx, ctx, key, klen, value, vlen, &q);
+    if (rc == SJHIP_OK) rc = make_view(ctx, ctx, key, klen, value, vlen, &q, false);
     if (rc) return rc;
     const uint32_t n = ctx->q_records + 1u;
     if (!(ctx->p_flags & SJHIP_FLAG_COPY_STRINGS)) {
@@ -1095,8 +1288,10 @@ int sjhip_fetch_filtered(sjhip_ctx *ctx, uint64_t *tape_dst, uint8_t *strings_ds
 
 // ---- paths, typed values, key sets ------------------------------------------------------------------------------------------
 // the keys of a path / key set: where each one ends in the concatenation (QView::key holds the bytes)
-static int make_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, QPath *pth, size_t *total_out) {
-    if (!ctx || !keys || !key_lens || n_keys == 0) return SJHIP_ERR_ARG;
+// (may_be_empty: sjhip_select_rows alone takes a path of no keys -- the array is the root value -- and then no key arrays)
+static int make_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, QPath *pth, size_t *total_out,
+                     bool may_be_empty = false) {
+    if (!ctx || ((!keys || !key_lens) && n_keys) || (n_keys == 0 && !may_be_empty)) return SJHIP_ERR_ARG;
     if (n_keys > (uint32_t)QPATH_MAX) {
         ctx_set_error(ctx, "a path / key set holds at most %d keys", QPATH_MAX);
         return SJHIP_ERR_ARG;
@@ -1116,8 +1311,8 @@ static int make_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_le
     return SJHIP_OK;
 }
 
-// Per-record answers of every part of ctx's result, laid end to end in document order: output k holds outs[k].width bytes for
-// every record at outs[k].dst; launch(part, q, n, d) fills n records of every output, output k at d[k] on the part's device.
+// Per-record answers of every part of ctx's result -- per row, under a row selection: `records` count rows then -- laid end to
+// end in document order: output k holds outs[k].width bytes for every record at outs[k].dst; launch(part, q, n, d) fills n records of every output, output k at d[k] on the part's device.
 // cap_records: room in the outputs; *records: records of the whole result.
 struct RecOut {
     void *dst;
@@ -1131,7 +1326,7 @@ static int outputs_over_parts(sjhip_ctx *ctx, const uint8_t *keys, size_t klen, 
     const int rc = query_parts(ctx, keys, klen, &NO_VALUE, 0, &parts);
     if (rc) return rc;
     size_t total = 0;
-    for (sjhip_ctx *part : parts) total += (size_t)part->q_records + 1u;
+    for (sjhip_ctx *part : parts) total += part_rows(ctx, part, true);
     *records = total;
     if (cap_records < total) {
         ctx_set_error(ctx, "%s: room for %zu records, the result holds %zu", who, cap_records, total);
@@ -1142,8 +1337,8 @@ static int outputs_over_parts(sjhip_ctx *ctx, const uint8_t *keys, size_t klen, 
         return c.used;
     };
     size_t at = 0;
-    return query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, "query sync",
-        [&](uint32_t n) {
+    return query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, true, "query sync",
+        [&](const sjhip_ctx *, uint32_t n) {
             u8 *d[MAX_OUTS];
             return layout(Carve(), n, d) + 64;
         },
@@ -1200,7 +1395,7 @@ int sjhip_count_where_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *
     size_t klen = 0;
     const int rc = make_path(ctx, keys, key_lens, n_keys, &pth, &klen);
     if (rc) return rc;
-    return count_over_parts(ctx, keys, klen, is_str && value ? (const uint8_t *)value : &NO_VALUE, is_str ? vlen : 0, count,
+    return count_over_parts(ctx, keys, klen, is_str && value ? (const uint8_t *)value : &NO_VALUE, is_str ? vlen : 0, true, count,
                             [&](sjhip_ctx *part, const QView &q, uint32_t n, unsigned long long *d) {
                                 hipLaunchKernelGGL(k_q_count_path, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, pth, op, want, d);
                             });
@@ -1271,7 +1466,7 @@ static int reserve_layout(sjhip_ctx *part, DevBuf &arena, L layout, size_t *byte
 }
 // What a product P plugs in (ColumnBuild, ListBuild, TableBuild below):
 //   Sizes, product, SYNC_*  what it publishes, where in ResultState, the names of its two waits in an error
-//   Work, work()            its work arrays of one part and their layout in d_kat, the totals of the scans in front
+//   Work, work()            its work arrays of one part (n rows) and their layout in d_kat, the totals of the scans in front
 //   measure()               pass 1 on one part: its kernels and scans, then the D2H of its totals to h_scratch + 512
 //   sizes_of(), add()       a part's sizes from what came back, and their sum
 //   gather()                pass 2 on one part: its arena(s) for those sizes, its gather kernels
@@ -1286,23 +1481,25 @@ static int build_product(sjhip_ctx *ctx, const uint8_t *keys, size_t klen, P &p)
     std::vector<typename P::Work> work(parts.size());
     std::vector<typename P::Sizes> sizes(parts.size());
     typename P::Sizes total;
-    rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, P::SYNC_MEASURE,
-        [&](uint32_t n) {
+    static const unsigned long long no_totals[4 * TABLE_MAX_COLS] = {};  // what a part without rows measures
+    rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, true, P::SYNC_MEASURE,
+        [&](const sjhip_ctx *part, uint32_t n) {
             typename P::Work w;
             unsigned long long *totals;
-            return p.work(Carve(), n, &w, &totals) + 64;
+            return p.work(Carve(), part, n, &w, &totals) + 64;
         },
         [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
             unsigned long long *totals;
-            const size_t work_bytes = p.work(Carve(part->d_kat.p), n, &work[k], &totals);
+            const size_t work_bytes = p.work(Carve(part->d_kat.p), part, n, &work[k], &totals);
             return p.measure(ctx, part, q, n, work[k], work_bytes, totals);
         },
         [&](size_t k, sjhip_ctx *part) {
-            sizes[k] = p.sizes_of((size_t)part->q_records + 1u, (const unsigned long long *)(part->h_scratch + 512));
+            const size_t n = part_rows(ctx, part, true);
+            sizes[k] = p.sizes_of(n, n ? (const unsigned long long *)(part->h_scratch + 512) : no_totals);
             p.add(&total, sizes[k]);
         });
     if (rc) return rc;
-    rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, P::SYNC_GATHER, [](uint32_t) { return (size_t)0; },
+    rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, true, P::SYNC_GATHER, [](const sjhip_ctx *, uint32_t) { return (size_t)0; },
         [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int { return p.gather(ctx, part, q, n, work[k], sizes[k]); },
         [](size_t, sjhip_ctx *) {});
     if (rc) return rc;
@@ -1319,11 +1516,10 @@ static int build_product(sjhip_ctx *ctx, const uint8_t *keys, size_t klen, P &p)
 // what the parts in front hold in the domain of the VALUES (not the one it is indexed by), the terminating entry is that total.
 enum Dom { RECORDS, ELEMS, BYTES, N_DOMS, NO_DOM = -1 };
 struct Seg {
-    void *dst;
+    void *dst;         // (null -- where the product's null_dst lets it through -- : this array is not wanted)
     size_t width;      // bytes per element
     int by;            // a part holds count[by] elements
     int values;        // an offset array: the domain its values count in; NO_DOM: data
-    bool skip_empty;   // no copy for a part that holds none
     const char *what;  // the name of its copy in an error
 };
 struct PartArrays {  // of one part: its counts, from its published sizes, and where its arrays lie in its arena (segs' order)
@@ -1352,7 +1548,7 @@ static int fetch_joined(sjhip_ctx *ctx, const char *sync, const Seg *segs, size_
             for (size_t s = 0; s < n_segs; s++) {
                 const Seg &g = segs[s];
                 const size_t cnt = a[k].count[g.by];
-                if (cnt || !g.skip_empty)
+                if (cnt && g.dst)
                     HIPCHK(hipMemcpyAsync((u8 *)g.dst + at[k][g.by] * g.width, a[k].src[s], cnt * g.width, hipMemcpyDeviceToHost, part->stream), g.what);
             }
             return SJHIP_OK;
@@ -1360,13 +1556,13 @@ static int fetch_joined(sjhip_ctx *ctx, const char *sync, const Seg *segs, size_
         [&](size_t k, sjhip_ctx *) {  // the offsets of a later part: from the end of the parts in front of it
             for (size_t s = 0; s < n_segs; s++) {
                 const Seg &g = segs[s];
-                if (g.values == NO_DOM || !at[k][g.values]) continue;
+                if (g.values == NO_DOM || !at[k][g.values] || !g.dst) continue;
                 for (size_t i = at[k][g.by]; i < at[k + 1][g.by]; i++) ((uint64_t *)g.dst)[i] += at[k][g.values];
             }
         });
     if (rc) return rc;
     for (size_t s = 0; s < n_segs; s++)
-        if (segs[s].values != NO_DOM) ((uint64_t *)segs[s].dst)[at[P][segs[s].by]] = at[P][segs[s].values];
+        if (segs[s].values != NO_DOM && segs[s].dst) ((uint64_t *)segs[s].dst)[at[P][segs[s].by]] = at[P][segs[s].values];
     return SJHIP_OK;
 }
 
@@ -1402,7 +1598,7 @@ struct ColumnBuild {
     QPath pth;
     uint32_t cvt;
     size_t *records, *bytes;
-    size_t work(Carve c, uint32_t n, QCol *col, unsigned long long **totals) const {
+    size_t work(Carve c, const sjhip_ctx *, uint32_t n, QCol *col, unsigned long long **totals) const {
         *totals = c.take<unsigned long long>(32);
         col_work(c, n, col);
         return c.used;
@@ -1441,9 +1637,9 @@ int sjhip_fetch_path_strings(sjhip_ctx *ctx, uint64_t *offsets, uint8_t *data, u
     if (!ctx) return SJHIP_ERR_ARG;
     if (!ctx->res.column.exists())
         return no_product(ctx, "no string column on the device (sjhip_fetch_path_strings follows sjhip_extract_path_strings, with no parse in between)");
-    const Seg segs[] = {{offsets, 8, RECORDS, BYTES, false, "D2H column offsets"},
-                        {status, 1, RECORDS, NO_DOM, false, "D2H column status"},
-                        {data, 1, BYTES, NO_DOM, true, "D2H column bytes"}};
+    const Seg segs[] = {{offsets, 8, RECORDS, BYTES, "D2H column offsets"},
+                        {status, 1, RECORDS, NO_DOM, "D2H column status"},
+                        {data, 1, BYTES, NO_DOM, "D2H column bytes"}};
     // (this fetch ends without query_bounds_check, unlike the list's and the table's: the debug build reports a violation of
     // k_q_col_gather with the next checked query call -- it has been so since the column was added, and stays so)
     return fetch_joined(ctx, "column fetch sync", segs, 3,
@@ -1479,7 +1675,7 @@ struct ListBuild {
     int mode;  // SJHIP_COL_FLOAT / INT / UINT, LIST_STR or LIST_CVT
     size_t *records, *elems, *bytes;
     bool strings() const { return mode >= LIST_STR; }
-    size_t work(Carve c, uint32_t n, QList *l, unsigned long long **totals) const {
+    size_t work(Carve c, const sjhip_ctx *, uint32_t n, QList *l, unsigned long long **totals) const {
         *totals = c.take<unsigned long long>(32);
         l->idx = c.take<u64>(n);
         l->cnt = c.take<u64>((size_t)n + 1);
@@ -1556,10 +1752,10 @@ static int list_fetch(sjhip_ctx *ctx, bool strings, uint64_t *list_offsets, uint
     if (!ctx->res.list_of(strings))  // (... or it is of the other kind)
         return no_product(ctx, "no list column of this kind on the device (sjhip_fetch_path_list follows sjhip_extract_path_list, "
                                "sjhip_fetch_path_list_strings follows sjhip_extract_path_list_strings, with no parse in between)");
-    const Seg segs[] = {{list_offsets, 8, RECORDS, ELEMS, false, "D2H list offsets"},
-                        {status, 1, RECORDS, NO_DOM, false, "D2H list status"},
-                        {inner, 8, ELEMS, strings ? BYTES : NO_DOM, true, "D2H list elements"},
-                        {data, 1, BYTES, NO_DOM, true, "D2H list bytes"}};
+    const Seg segs[] = {{list_offsets, 8, RECORDS, ELEMS, "D2H list offsets"},
+                        {status, 1, RECORDS, NO_DOM, "D2H list status"},
+                        {inner, 8, ELEMS, strings ? BYTES : NO_DOM, "D2H list elements"},
+                        {data, 1, BYTES, NO_DOM, "D2H list bytes"}};
     const int rc = fetch_joined(ctx, "list fetch sync", segs, 4,
         [&](sjhip_ctx *part, size_t *count, const void **src) {
             const ResultState::ListColumn &s = part->res.list.sizes();
@@ -1616,7 +1812,7 @@ struct TableBuild {
     uint32_t n_cols;
     size_t *records, *bytes;
     bool is_string(uint32_t j) const { return table_is_string(t.pl.kind[j]); }
-    size_t work(Carve c, uint32_t n, Work *w, unsigned long long **totals) const {
+    size_t work(Carve c, const sjhip_ctx *, uint32_t n, Work *w, unsigned long long **totals) const {
         *totals = c.take<unsigned long long>(4 * TABLE_MAX_COLS);  // (col_scan leaves column j's bytes in entry 4 j + 2)
         for (uint32_t j = 0; j < n_cols; j++)
             if (is_string(j)) col_work(c, n, &w->c[j]);
@@ -1709,9 +1905,9 @@ int sjhip_fetch_table_column(sjhip_ctx *ctx, uint32_t col, void *values, uint64_
     }
     const int kind = all.kind[col];
     const bool str = table_is_string(kind);
-    const Seg status_seg = {status, 1, RECORDS, NO_DOM, false, "D2H table status"};
-    const Seg num_segs[] = {status_seg, {values, kind == SJHIP_COL_BOOL ? 1u : 8u, RECORDS, NO_DOM, false, "D2H table values"}};
-    const Seg str_segs[] = {status_seg, {offsets, 8, RECORDS, BYTES, false, "D2H table offsets"}, {data, 1, BYTES, NO_DOM, true, "D2H table bytes"}};
+    const Seg status_seg = {status, 1, RECORDS, NO_DOM, "D2H table status"};
+    const Seg num_segs[] = {status_seg, {values, kind == SJHIP_COL_BOOL ? 1u : 8u, RECORDS, NO_DOM, "D2H table values"}};
+    const Seg str_segs[] = {status_seg, {offsets, 8, RECORDS, BYTES, "D2H table offsets"}, {data, 1, BYTES, NO_DOM, "D2H table bytes"}};
     const int rc = fetch_joined(ctx, "table fetch sync", str ? str_segs : num_segs, str ? 3 : 2,
         [&](sjhip_ctx *part, size_t *count, const void **src) {
             const ResultState::Table &s = part->res.table.sizes();
@@ -1727,4 +1923,97 @@ int sjhip_fetch_table_column(sjhip_ctx *ctx, uint32_t col, void *values, uint64_
             return SJHIP_ERR_ARG;
         });
     return rc ? rc : query_bounds_check(ctx);  // (debug build: the kernels of sjhip_extract_table have finished here)
+}
+
+// ---- row selection ---------------------------------------------------------------------------------------------------------------
+// The selection of every part lives in the part's d_rows, an arena of its own (rows_layout): row offsets [n + 1] over the part's n
+// records (from 0 in every part), status [n], the row index [rows] in merged tape indices.  It is built over the RECORDS -- the
+// selection it replaces is given up first (build_product) -- with the work arrays of its passes (QRows) in d_kat; the measure
+// counts the rows, the gather writes them.  While the owner's product exists, make_view hands the row index to the path queries.
+struct RowsBuild {
+    using Sizes = ResultState::Rows;
+    using Work = QRows;
+    static constexpr auto product = &ResultState::rows;
+    static constexpr const char *SYNC_MEASURE = "row selection sync", *SYNC_GATHER = "row gather sync";
+    QPath pth;
+    size_t *records, *rows;
+    static u32 tape_tiles(const sjhip_ctx *part) { return (u32)((part->tape_len + TW_TILE - 1) / TW_TILE); }
+    size_t work(Carve c, const sjhip_ctx *part, uint32_t n, QRows *w, unsigned long long **totals) const {
+        const u32 tiles = tape_tiles(part);
+        *totals = w->totals = c.take<unsigned long long>(32);
+        w->open = c.take<u64>(n);
+        w->close = c.take<u64>(n);
+        w->status = c.take<u8>(n);
+        w->depth = c.take<unsigned long long>(tiles);
+        w->cnt = c.take<unsigned long long>(tiles);
+        w->tile_last = c.take<long long>(tiles);
+        w->depth_want = pth.n + 1u;
+        return c.used;
+    }
+    int measure(sjhip_ctx *ctx, sjhip_ctx *part, const QView &q, uint32_t n, const QRows &w, size_t, unsigned long long *totals) const {
+        const dim3 tiles(tape_tiles(part)), block(TW_THREADS), one(1), wide(1024);
+        unsigned long long *const none = nullptr;
+        const Arr<u64> no_index = SJ_ARR((u64 *)nullptr, 0, A_ROWS);
+        HIPCHK(hipMemsetAsync(totals, 0, 256, part->stream), "row totals memset");
+        hipLaunchKernelGGL(k_q_rows_records, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, pth, w);
+        hipLaunchKernelGGL(k_q_rows_tile<0>, tiles, block, 0, part->stream, q, w, 0u, no_index);
+        hipLaunchKernelGGL(k_q_rows_last, tiles, block, 0, part->stream, q, w);  // (these three end at once unless a tile asked)
+        hipLaunchKernelGGL(k_q_rows_scan_last, one, wide, 0, part->stream, w, tiles.x);
+        hipLaunchKernelGGL(k_q_rows_tile<0>, tiles, block, 0, part->stream, q, w, 1u, no_index);
+        hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, part->stream, w.depth, none, none, tiles.x, totals);
+        hipLaunchKernelGGL(k_q_rows_tile<1>, tiles, block, 0, part->stream, q, w, 0u, no_index);
+        hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, part->stream, none, w.cnt, none, tiles.x, totals);  // the rows: totals[1]
+        HIPCHK(hipGetLastError(), "row selection launch");
+        HIPCHK(hipMemcpyAsync(part->h_scratch + 512, totals + 1, 8, hipMemcpyDeviceToHost, part->stream), "D2H row count");
+        return SJHIP_OK;
+    }
+    Sizes sizes_of(size_t n, const unsigned long long *h) const { return {n, (size_t)h[0]}; }
+    void add(Sizes *t, const Sizes &s) const { t->records += s.records, t->rows += s.rows; }
+    int gather(sjhip_ctx *ctx, sjhip_ctx *part, const QView &q, uint32_t n, const QRows &w, const Sizes &s) const {
+        RowsOut o;
+        const int rc = reserve_layout(part, part->d_rows, [&](Carve cv) { return rows_layout(cv, n, s.rows, &o); });
+        if (rc) return rc;
+        if (s.rows)
+            hipLaunchKernelGGL(k_q_rows_tile<2>, dim3(tape_tiles(part)), dim3(TW_THREADS), 0, part->stream, q, w, 0u, SJ_ARR(o.index, s.rows, A_ROWS));
+        hipLaunchKernelGGL(k_q_rows_offsets, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, w, SJ_ARR((const u64 *)o.index, s.rows, A_ROWS),
+                           (u64)s.rows, o.off, o.status);
+        HIPCHK(hipGetLastError(), "row gather launch");
+        return SJHIP_OK;
+    }
+    void finish(Sizes *total) const { *records = total->records, *rows = total->rows; }
+};
+
+int sjhip_select_rows(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, size_t *records, size_t *rows) {
+    if (!records || !rows) return SJHIP_ERR_ARG;
+    RowsBuild p;
+    p.records = records, p.rows = rows;
+    size_t klen = 0;
+    const int rc = make_path(ctx, keys, key_lens, n_keys, &p.pth, &klen, true);
+    return rc ? rc : build_product(ctx, keys ? keys : &NO_VALUE, klen, p);
+}
+
+int sjhip_fetch_rows(sjhip_ctx *ctx, uint64_t *row_offsets, uint64_t *row_index, uint8_t *status) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!ctx->res.rows.exists())
+        return no_product(ctx, "no row selection on the device (sjhip_fetch_rows follows sjhip_select_rows, with no parse and no sjhip_select_records in between)");
+    const Seg segs[] = {{row_offsets, 8, RECORDS, ELEMS, "D2H row offsets"},
+                        {status, 1, RECORDS, NO_DOM, "D2H row status"},
+                        {row_index, 8, ELEMS, NO_DOM, "D2H row index"}};
+    const int rc = fetch_joined(ctx, "row fetch sync", segs, 3,
+        [](sjhip_ctx *part, size_t *count, const void **src) {
+            const ResultState::Rows &s = part->res.rows.sizes();
+            RowsOut o;
+            (void)rows_layout(Carve(part->d_rows.p), s.records, s.rows, &o);
+            count[RECORDS] = s.records, count[ELEMS] = s.rows;
+            src[0] = o.off, src[1] = o.status, src[2] = o.index;
+        },
+        [](const size_t *) { return SJHIP_OK; });  // (any destination may be null: that array is not copied)
+    return rc ? rc : query_bounds_check(ctx);  // (debug build: the kernels of sjhip_select_rows have finished here)
+}
+
+int sjhip_select_records(sjhip_ctx *ctx) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    ctx->res.rows.begin();
+    for (sjhip_ctx *part : result_parts(ctx)) part->res.rows.begin();
+    return SJHIP_OK;
 }

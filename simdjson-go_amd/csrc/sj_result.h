@@ -8,7 +8,9 @@
 //   * the tenant of the shared arenas d_q / d_qtape / d_qstrings: the filtered result, the serialized columns or the MarshalJSON text
 //     -- one value, so at most one of them is resident;
 //   * the string column (d_col), the list column (d_list, numbers or strings) and the table (d_table, d_tabledata), independent of
-//     each other and of the tenant: one mechanism (Product) used three times.
+//     each other and of the tenant: one mechanism (Product) used three times -- and a fourth time for the row selection (d_rows:
+//     "the rows are the elements of the array at this path"), which the path queries and the other three products are built over
+//     while it exists and which they survive: what was built under a selection is materialised data.
 // The rule: a parse call, successful or not, drops the previous result and everything derived from it (begin_parse); so do
 // sjhip_deserialize, sjhip_ctx_trim and the stage-1-only calls (drop_result).  A product exists from its publish to the next
 // transition that drops it; a product is only published on a resident result, and a result of no tape words is no result.
@@ -28,6 +30,7 @@ public:
     struct Column { size_t records = 0, bytes = 0; };
     struct ListColumn { size_t records = 0, elems = 0, bytes = 0; bool strings = false; };  // (numbers or strings: what was published)
     static constexpr int TABLE_COLS = 16;  // SJHIP_TABLE_MAX_COLS
+    struct Rows { size_t records = 0, rows = 0; };  // the records the selection ran over, the rows it found
     struct Table {  // what a fetch of one column needs: its kind, and the text bytes of a string column (0 for the other kinds)
         size_t records = 0;
         uint32_t n_cols = 0;
@@ -106,7 +109,8 @@ public:
     Product<Column> column;
     Product<ListColumn> list;
     Product<Table> table;
-    void drop_products() { column.begin(), list.begin(), table.begin(); }  // (a stage-1-only call on a sharded result: api.hip)
+    Product<Rows> rows;  // the row selection (sjhip_select_rows; sjhip_select_records is its begin())
+    void drop_products() { column.begin(), list.begin(), table.begin(), rows.begin(); }  // (a stage-1-only call on a sharded result: api.hip)
     template <typename S>
     bool publish(Product<S> ResultState::*product, const S &sizes) {  // publish(&ResultState::column, {records, bytes})
         if (!resident() && !sharded()) return false;

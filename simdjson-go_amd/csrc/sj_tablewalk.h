@@ -1,5 +1,6 @@
 // sj_tablewalk.h -- the walk of a table (sj_table.h): every column of ONE record resolved to a tape index or a path status in one
-// pass over the record's members.  Host and device: k_q_table_walk (query.hip) runs it with one lane per record, and
+// pass over the record's members.  The walk starts at the tape index of a value -- `root`: the root value of a record, or the value
+// of a row of a row selection (query.hip row_value) -- and never looks in front of it.  Host and device: k_q_table_walk (query.hip) runs it with one lane per record, and
 // host_selftest.cpp replays it over an oracle tape (sj_selftest_table_walk, tests/test_table_walk.py).
 //
 // FindElement's rules hold for every column on its own: into the root and into objects, not into arrays; at every level the first
@@ -14,7 +15,7 @@
 //
 // State: the matched and the not-an-object nodes are two 32-bit masks; the resume stack -- the end and the node of every object
 // that is open around the current one, at most 15 -- lies behind a pointer, two u32 per level `stride` words apart (LDS on the
-// device, one column per lane; a local array on the host), the ends relative to the record's open root.  Nothing is an array
+// device, one column per lane; a local array on the host), the ends relative to `root`.  Nothing is an array
 // indexed per lane in registers.
 //   View:  u64 word(u64 i)                                        the tape
 //          bool key_equals(u64 kw, u64 kl, u32 key_b, u32 key_n)  the string (kw, kl) equals plan key bytes [key_b, key_b + key_n)
@@ -34,22 +35,22 @@ SJ_HD u32 table_children(const TablePlan &pl, u32 node) {  // the mask of the no
 }
 
 template <class View, class Sink>
-SJ_HD void table_walk(const View &q, const TablePlan &pl, u64 open, u32 *stack, u32 stride, Sink &emit) {
+SJ_HD void table_walk(const View &q, const TablePlan &pl, u64 root, u32 *stack, u32 stride, Sink &emit) {
     const u64 PAYLOAD = 0x00ffffffffffffffull;
     u32 matched = 0, notobj = 0;
-    const u64 w = q.word(open + 1);
+    const u64 w = q.word(root);
     if ((u32)(w >> 56) != (u32)'{') {
         notobj = ~0u;
     } else {
         u64 end = (w & PAYLOAD) - 1;  // index of the closing '}'
-        u64 i = open + 2;
+        u64 i = root + 1;
         u32 cur = TABLE_ROOT, todo = table_children(pl, cur), sp = 0;
         for (;;) {
             if (i >= end || (todo & ~matched) == 0) {  // this object is finished: behind it in the one around it
                 if (sp == 0) break;
                 sp--;
                 i = end + 1;
-                end = open + stack[(2 * sp) * stride];
+                end = root + stack[(2 * sp) * stride];
                 cur = stack[(2 * sp + 1) * stride];
                 todo = table_children(pl, cur);
                 continue;
@@ -71,7 +72,7 @@ SJ_HD void table_walk(const View &q, const TablePlan &pl, u64 open, u32 *stack, 
                 for (u32 cs = pl.cols[hit]; cs; cs &= cs - 1) emit((u32)__builtin_ctz(cs), v);
                 if (pl.child_n[hit]) {
                     if (vt == (u32)'{') {
-                        stack[(2 * sp) * stride] = (u32)(end - open);
+                        stack[(2 * sp) * stride] = (u32)(end - root);
                         stack[(2 * sp + 1) * stride] = cur;
                         sp++;
                         cur = hit;

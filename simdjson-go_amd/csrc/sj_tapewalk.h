@@ -139,8 +139,8 @@ __device__ __forceinline__ long long block1024_scan_array(long long *a, u32 n, l
     return total;
 }
 
-__global__ __launch_bounds__(TW_THREADS) void k_tw_last(const u64 *tape, u64 n, long long *tile_last) {
-    __shared__ long long s_w[TW_THREADS / 64];
+// tile_last[tile] := the last anchor inside the tile that starts at word tile * TW_TILE (-1: none); s_w: one slot per wave
+__device__ __forceinline__ void tw_tile_last(const u64 *tape, u64 n, long long *tile_last, long long *s_w) {
     const int tid = threadIdx.x;
     const u64 base = (u64)blockIdx.x * TW_TILE + (u64)tid * TW_ITEMS;
     long long last = -1;
@@ -161,6 +161,10 @@ __global__ __launch_bounds__(TW_THREADS) void k_tw_last(const u64 *tape, u64 n, 
         for (int w = 1; w < TW_THREADS / 64; w++) m = s_w[w] > m ? s_w[w] : m;
         tile_last[blockIdx.x] = m;
     }
+}
+__global__ __launch_bounds__(TW_THREADS) void k_tw_last(const u64 *tape, u64 n, long long *tile_last) {
+    __shared__ long long s_w[TW_THREADS / 64];
+    tw_tile_last(tape, n, tile_last, s_w);
 }
 
 // one block: tile_last[t] := the last anchor in front of tile t (exclusive running maximum)

@@ -406,6 +406,29 @@ class Context:
         self._check(L.sjhip_fetch_table_column(self._h, int(col), values.ctypes.data, None, None, status.ctypes.data))
         return values[:records], status[:records]
 
+    # ---- rows (include/sjhip.h: sjhip_select_rows / sjhip_fetch_rows / sjhip_select_records) -----------------------------------
+    def select_rows(self, path=()):
+        """Iter.FindElement(path...), Iter.Array, Array.Iter on every record: the elements of that array become the rows, and the
+        path queries, columns, lists and tables above run on every row until select_records() or the next parse.  An empty path:
+        the array is the record's root value.  -> (records, rows)"""
+        blob, lens, n = self._keys(path)
+        nr, nw = C.c_size_t(0), C.c_size_t(0)
+        self._check(_lib.lib().sjhip_select_rows(self._h, blob if n else None, lens if n else None, n, C.byref(nr), C.byref(nw)))
+        return nr.value, nw.value
+
+    def fetch_rows(self, records, rows):
+        """the selection of the last select_rows (its records and rows) -> (row_offsets: uint64 array of records + 1, row_index:
+        uint64 array of the tape index of every row's value, status: uint8 array of COL_OK ... per record)"""
+        offsets = np.empty(records + 1, dtype=np.uint64)
+        index = np.empty(max(rows, 1), dtype=np.uint64)
+        status = np.empty(max(records, 1), dtype=np.uint8)
+        self._check(_lib.lib().sjhip_fetch_rows(self._h, offsets.ctypes.data, index.ctypes.data, status.ctypes.data))
+        return offsets, index[:rows], status[:records]
+
+    def select_records(self):
+        """back to one row per record (no error if nothing was selected)"""
+        self._check(_lib.lib().sjhip_select_records(self._h))
+
     def serialize(self, fetch=True, dedup=False):
         """Serializer.Serialize (format v3, CompressNone) of the device-resident result of the last parse.
         -> the framed stream as a uint8 array (what the reference's Deserialize reads), or its sizes with fetch=False.
