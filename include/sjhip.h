@@ -193,7 +193,12 @@ int sjhip_fetch_filtered(sjhip_ctx *ctx, uint64_t *tape_dst, uint8_t *strings_ds
 #define SJHIP_PATH_NOT_FOUND (~0ull)
 #define SJHIP_PATH_NOT_OBJECT (~0ull - 1ull)
 enum { SJHIP_OP_EXISTS = 0, SJHIP_OP_EQ_STRING = 1, SJHIP_OP_EQ_INT = 2, SJHIP_OP_EQ_UINT = 3, SJHIP_OP_EQ_FLOAT = 4,
-       SJHIP_OP_EQ_BOOL = 5, SJHIP_OP_IS_NULL = 6 };
+       SJHIP_OP_EQ_BOOL = 5, SJHIP_OP_IS_NULL = 6,
+       /* the ordering operators and the prefix test (the numbering is part of the ABI): see sjhip_where_path below */
+       SJHIP_OP_LT_INT = 7, SJHIP_OP_LE_INT, SJHIP_OP_GT_INT, SJHIP_OP_GE_INT,
+       SJHIP_OP_LT_UINT, SJHIP_OP_LE_UINT, SJHIP_OP_GT_UINT, SJHIP_OP_GE_UINT,
+       SJHIP_OP_LT_FLOAT, SJHIP_OP_LE_FLOAT, SJHIP_OP_GT_FLOAT, SJHIP_OP_GE_FLOAT,
+       SJHIP_OP_PREFIX_STRING /* = 19 */ };
 int sjhip_find_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, uint64_t *index_out,
                     size_t cap, size_t *records);
 int sjhip_count_where_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int op,
@@ -329,6 +334,37 @@ int sjhip_select_rows(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_l
 int sjhip_fetch_rows(sjhip_ctx *ctx, uint64_t *row_offsets /* [records + 1] */, uint64_t *row_index /* [rows] */,
                      uint8_t *status /* [records] */);
 int sjhip_select_records(sjhip_ctx *ctx);
+/* Row predicates: keep the rows whose element at `path` satisfies a test -- the WHERE of the columns, lists and tables above; what a
+ * Go caller writes as FindElement(path...), the Iter conversion and a Go comparison, for every row at once.
+ *   sjhip_where_path      The predicate is the one of sjhip_count_where_path: the element at `path` of the row EXISTS and satisfies
+ *                          `op` -- the operators above, and
+ *                            LT / LE / GT / GE _INT / _UINT / _FLOAT  (value = an int64_t / uint64_t / double, vlen 8) the element converted
+ *                                      exactly as EQ_INT / EQ_UINT / EQ_FLOAT convert it -- Iter.Int / Uint / Float: a float is truncated
+ *                                      for INT, with the amd64 results at 2^63 and 2^64 -- then compared as int64_t, uint64_t or double;
+ *                                      an element whose conversion is not SJHIP_COL_OK (null, a type error, a range error)
+ *                                      satisfies nothing;
+ *                            PREFIX_STRING  the element is a string whose unescaped bytes (Iter.StringBytes) begin with the vlen
+ *                                      bytes of `value` (at most the 1024 bytes EQ_STRING allows; vlen 0 matches every string).
+ *                          sjhip_count_where_path accepts these operators too: its count is *rows of sjhip_where_path on the same
+ *                          selection.  flags: SJHIP_WHERE_NOT keeps exactly the rows the same call without it drops -- the rows
+ *                          where the path is not found, where an object is missing on the way and where the conversion fails
+ *                          included; any other bit is SJHIP_ERR_ARG.  n_keys == 0 is allowed, as in sjhip_select_rows: the element
+ *                          is the row's own value (a selection whose rows are scalars).  Paths and limits are otherwise those of
+ *                          sjhip_find_path.
+ * What it narrows: with a row selection in force, the selection keeps its records and their status bytes, and every record keeps
+ * the matching ones among the rows it owned, in document order.  Without one it creates a selection in which record r owns one
+ * row -- its root value -- if it matches and none otherwise, every status SJHIP_COL_OK.  Either way the result is an ordinary row
+ * selection: sjhip_fetch_rows delivers it, sjhip_select_records and everything that drops a selection drop it, every call that
+ * runs on rows runs on the kept rows, and successive calls are the conjunction of their predicates.  *records = the records,
+ * *rows = the rows kept; keeping no rows is legal (the rules of a selection without rows above).  sjhip_count_where,
+ * sjhip_filter_where, the stream's filter, the serializer and MarshalJSON keep ignoring the selection.
+ * Failure: a call that fails with SJHIP_ERR_ARG -- an unknown operator or flag, a value of the wrong size or too long, a bad path,
+ * no result on the device -- leaves the selection exactly as it was.  A call that fails later (SJHIP_ERR_HIP) gives the selection
+ * up, as sjhip_select_records does, and sjhip_last_error says so.  On a sharded ND result every shard narrows its own rows and
+ * the fetch joins them.  The cost is one walk of every row and a fixed number of passes over arrays of at most 8 bytes per row. */
+#define SJHIP_WHERE_NOT 1u
+int sjhip_where_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int op, const void *value,
+                     size_t vlen, uint32_t flags, size_t *records, size_t *rows);
 
 /* ---- Serializer.Serialize on the device (parsed_serialize.go:200-431, format version 3) -----------------------------
  * Splits the device-resident tape of the last parse (SJHIP_FLAG_COPY_STRINGS) into the reference's three columns --

@@ -12,6 +12,7 @@
 // object whose key equals `key` (top level only, FindKey does not descend) has a string value equal to `value`.
 // Strings are compared after unescaping (they are read from Strings.B / the message exactly as the Iter API does).
 #include <hip/hip_runtime.h>
+#include <stdio.h>
 #include <string.h>
 
 #include <array>
@@ -167,6 +168,36 @@ __device__ __forceinline__ int element_to(const QView &q, u64 v, int kind, u64 *
     }
     return SJHIP_COL_OK;
 }
+// the ordering comparisons and the prefix test (SJHIP_OP_LT_INT .. SJHIP_OP_PREFIX_STRING), apart from the switch of the
+// equalities below, whose code they leave as it was: the element converted as the EQ_* operator of its kind converts it -- an
+// element whose conversion is not OK satisfies nothing --, then Go's comparison of two int64 / uint64 / float64 (a NaN `want`
+// compares false with everything); PREFIX_STRING: bytes.HasPrefix(Iter.StringBytes, value)
+__device__ __forceinline__ bool element_orders(const QView &q, u64 v, int op, u64 want) {
+    if (op == SJHIP_OP_PREFIX_STRING) {
+        const u64 w = q.tape[v];
+        if ((u32)(w >> 56) != '"') return false;
+        const u64 len = q.tape[v + 1];
+        if (len < q.vlen) return false;
+        const u8 *s = str_bytes(q, w, q.vlen);
+        for (u32 k = 0; k < q.vlen; k++)
+            if (s[k] != q.val[k]) return false;
+        return true;
+    }
+    if (op < SJHIP_OP_LT_INT || op > SJHIP_OP_GE_FLOAT) return false;
+    const int o = op - SJHIP_OP_LT_INT, rel = o & 3;  // rel: < <= > >=
+    const int kind = o < 4 ? SJHIP_COL_INT : (o < 8 ? SJHIP_COL_UINT : SJHIP_COL_FLOAT);
+    u64 got;
+    if (element_to(q, v, kind, &got) != SJHIP_COL_OK) return false;
+    bool lt, gt;
+    if (kind == SJHIP_COL_INT) lt = (long long)got < (long long)want, gt = (long long)got > (long long)want;
+    else if (kind == SJHIP_COL_UINT) lt = got < want, gt = got > want;
+    else {
+        const double a = __longlong_as_double((long long)got), b = __longlong_as_double((long long)want);
+        if (a != a || b != b) return false;
+        lt = a < b, gt = a > b;
+    }
+    return rel == 0 ? lt : (rel == 1 ? !gt : (rel == 2 ? gt : !lt));
+}
 // the typed comparisons: the element converted as above (StringBytes for EQ_STRING), compared with the wanted value
 __device__ bool element_is(const QView &q, u64 v, int op, u64 want) {
     const u64 w = q.tape[v];
@@ -182,8 +213,8 @@ __device__ bool element_is(const QView &q, u64 v, int op, u64 want) {
     case SJHIP_OP_EQ_FLOAT:  // (a comparison of doubles: -0.0 equals 0.0)
         return element_to(q, v, SJHIP_COL_FLOAT, &got) == SJHIP_COL_OK &&
                __longlong_as_double((long long)got) == __longlong_as_double((long long)want);
+    default: return element_orders(q, v, op, want);
     }
-    return false;
 }
 // the record's element at the path exists and satisfies the predicate
 __device__ __forceinline__ bool record_is(const QView &q, const QPath &pth, u32 r, int op, u64 want) {
@@ -1045,6 +1076,68 @@ __global__ __launch_bounds__(256) void k_q_rows_offsets(QView q, QRows o, Arr<co
     if (r == q.R) out_off[r + 1] = rows;
 }
 
+
+// ---- row predicates: keep the rows whose element at a path satisfies a test (sjhip_where_path) -----------------------------------
+// A predicate narrows the row index: the rows of the selection -- or, without one, the root values of the records -- that satisfy
+// it are compacted, in document order, into a new index, and every record keeps the matching ones among the rows it owned.
+//   k_q_where_mark      one lane per current row: FindElement (an empty path: the row's value itself) and element_is, XORed with
+//                       NOT; the flag of the row, and the kept rows of its 1024-row tile counted from the wave's ballot (one atomic
+//                       per wave: no pass reads the flags back to sum them)
+//   k_tw_scan_sums      the kept rows in front of every tile, and the total -- the one value the host waits for: the arena of a
+//                       new selection is reserved for it
+//   k_q_where_apply     per tile: the exclusive prefix of its flags; pre[i] = the kept rows in front of row i; row_value(q, i) of
+//                       every kept row goes to its prefix in the NEW index (without a selection this materialises rec_open + 1)
+//   k_q_where_offsets   one lane per record: its new row offset = pre[] at its old one (without a selection record r owned row r
+//                       alone); the status copied, or OK
+// The new index and the new offsets are built in the work arena and copied into d_rows behind the kernels (stream order): the old
+// index is read by other blocks while the new one is produced, so it cannot be compacted in place.  No lane's work grows with
+// the rows of a record.
+struct QWhere {
+    Arr<u8> flag;                 // [n] 1: row i is kept
+    Arr<u32> pre;                 // [n] the kept rows in front of row i
+    unsigned long long *tiles;    // [tiles] kept rows of the tile -> their exclusive prefix
+    Arr<u64> index;               // [kept] the new row index (null while the rows are counted)
+    Arr<const u64> old_off;       // [records + 1] the row offsets of the selection in force; null: record r owns row r
+    const u8 *old_status;         // [records] its statuses (with old_off)
+    Arr<u64> off;                 // [records + 1] the new row offsets
+    u8 *status;                   // [records]
+};
+__global__ __launch_bounds__(256) void k_q_where_mark(QView q, QPath pth, int op, u64 want, u32 negate, QWhere w) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    bool keep = false;
+    if (i < q_rows(q)) {
+        keep = (pth.n ? record_is(q, pth, i, op, want) : element_is(q, row_value(q, i), op, want)) != (negate != 0);
+        w.flag[i] = keep ? 1 : 0;
+    }
+    const u64 b = __ballot(keep);  // (the 64 rows of a wave lie in one tile)
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&w.tiles[i / QTILE], (unsigned long long)__popcll(b));
+}
+__global__ __launch_bounds__(QT) void k_q_where_apply(QView q, QWhere w) {
+    __shared__ unsigned long long s_w[QT / 64];
+    const u32 n = q_rows(q), base = blockIdx.x * QTILE + threadIdx.x * QI;
+    u32 f[QI], sum = 0;
+#pragma unroll
+    for (int k = 0; k < QI; k++) {
+        f[k] = base + k < n ? w.flag[base + k] : 0u;
+        sum += f[k];
+    }
+    u64 at = w.tiles[blockIdx.x] + block_excl_sum(sum, s_w, (int)threadIdx.x, nullptr);
+#pragma unroll
+    for (int k = 0; k < QI; k++) {
+        if (base + k >= n) break;
+        w.pre[base + k] = (u32)at;
+        if (f[k]) w.index[at++] = row_value(q, base + k);
+    }
+}
+__global__ __launch_bounds__(256) void k_q_where_offsets(QView q, QWhere w, u64 kept) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    if (r > q.R) return;
+    const u64 old = w.old_off ? w.old_off[r] : (u64)r;
+    w.off[r] = old < q_rows(q) ? (u64)w.pre[old] : kept;  // (the records behind the last row: everything kept lies in front)
+    w.status[r] = w.old_off ? w.old_status[r] : (u8)SJHIP_COL_OK;
+    if (r == q.R) w.off[r + 1] = kept;
+}
+
 }  // namespace
 
 namespace sj {
@@ -1377,23 +1470,34 @@ int sjhip_find_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_len
                               });
 }
 
-int sjhip_count_where_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int op,
-                           const void *value, size_t vlen, uint64_t *count) {
-    if (!count || op < SJHIP_OP_EXISTS || op > SJHIP_OP_IS_NULL) return SJHIP_ERR_ARG;
-    const bool is_str = op == SJHIP_OP_EQ_STRING;
-    u64 want = 0;
-    if (op == SJHIP_OP_EQ_INT || op == SJHIP_OP_EQ_UINT || op == SJHIP_OP_EQ_FLOAT) {
-        if (!value || vlen != 8) return SJHIP_ERR_ARG;  // int64_t / uint64_t / double
-        memcpy(&want, value, 8);
+// The value of a typed predicate (sjhip_count_where_path, sjhip_where_path): a number -- an int64_t, uint64_t or double, 8 bytes --
+// or a bool (1 byte) travels as *want; a string (EQ_STRING, PREFIX_STRING) travels in the view.  An unknown operator, or a value
+// of another size: SJHIP_ERR_ARG.
+static int predicate_value(int op, const void *value, size_t vlen, u64 *want, bool *is_str) {
+    if (op < SJHIP_OP_EXISTS || op > SJHIP_OP_PREFIX_STRING) return SJHIP_ERR_ARG;
+    *is_str = op == SJHIP_OP_EQ_STRING || op == SJHIP_OP_PREFIX_STRING;
+    *want = 0;
+    if ((op >= SJHIP_OP_EQ_INT && op <= SJHIP_OP_EQ_FLOAT) || (op >= SJHIP_OP_LT_INT && op <= SJHIP_OP_GE_FLOAT)) {
+        if (!value || vlen != 8) return SJHIP_ERR_ARG;
+        memcpy(want, value, 8);
     } else if (op == SJHIP_OP_EQ_BOOL) {
         if (!value || vlen != 1) return SJHIP_ERR_ARG;
-        want = *(const uint8_t *)value != 0;
-    } else if (is_str && !value && vlen) {
+        *want = *(const uint8_t *)value != 0;
+    } else if (*is_str && !value && vlen) {
         return SJHIP_ERR_ARG;
     }
+    return SJHIP_OK;
+}
+int sjhip_count_where_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int op,
+                           const void *value, size_t vlen, uint64_t *count) {
+    if (!count) return SJHIP_ERR_ARG;
+    bool is_str = false;
+    u64 want = 0;
+    int rc = predicate_value(op, value, vlen, &want, &is_str);
+    if (rc) return rc;
     QPath pth;
     size_t klen = 0;
-    const int rc = make_path(ctx, keys, key_lens, n_keys, &pth, &klen);
+    rc = make_path(ctx, keys, key_lens, n_keys, &pth, &klen);
     if (rc) return rc;
     return count_over_parts(ctx, keys, klen, is_str && value ? (const uint8_t *)value : &NO_VALUE, is_str ? vlen : 0, true, count,
                             [&](sjhip_ctx *part, const QView &q, uint32_t n, unsigned long long *d) {
@@ -2016,4 +2120,131 @@ int sjhip_select_records(sjhip_ctx *ctx) {
     ctx->res.rows.begin();
     for (sjhip_ctx *part : result_parts(ctx)) part->res.rows.begin();
     return SJHIP_OK;
+}
+
+// ---- row predicates ----------------------------------------------------------------------------------------------------------------
+// sjhip_where_path narrows the selection of every part in place: the old selection -- or, without one, the records -- is what the
+// passes run on (make_view, on_rows) until the new one is published over it.  Two passes over the parts, the shape of
+// build_product, but nothing is given up first: pass 1 marks and counts (the kept rows of the part come back through
+// h_scratch + 512), pass 2 compacts into the work arena -- laid out in pass 1 for every row kept -- and copies offsets, statuses
+// and index into d_rows behind the kernels, which is reserved here only when there was no selection (a narrowed one fits where
+// the old one lies, and rows_layout keeps offsets and statuses in their place).
+struct WhereNew { u64 *index, *off; u8 *status; };  // the new selection of a part, in its d_kat
+static int where_build(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, const uint8_t *keys, size_t klen, const uint8_t *val,
+                       size_t vlen, const QPath &pth, int op, u64 want, u32 negate, size_t *records, size_t *rows) {
+    const bool sel = selected(ctx, true);
+    std::vector<QWhere> work(parts.size());
+    std::vector<WhereNew> fresh(parts.size());
+    std::vector<size_t> kept(parts.size(), 0);
+    auto layout = [](Carve c, const sjhip_ctx *part, uint32_t n, QWhere *w, WhereNew *nw, unsigned long long **totals) {
+        const size_t recs = (size_t)part->q_records + 1u;
+        *totals = c.take<unsigned long long>(32);
+        w->tiles = c.take<unsigned long long>((n + QTILE - 1) / QTILE);
+        u8 *const flag = c.take<u8>(n);
+        u32 *const pre = c.take<u32>(n);
+        w->flag = SJ_ARR(flag, n, A_WHERE_FLAG);
+        w->pre = SJ_ARR(pre, n, A_WHERE_PRE);
+        nw->index = c.take<u64>(n);  // (room for every row: the count is not known yet)
+        nw->off = c.take<u64>(recs + 1);
+        nw->status = c.take<u8>(recs);
+        return c.used;
+    };
+    int rc = query_over_parts(ctx, parts, keys, klen, val, vlen, true, "row predicate sync",
+        [&](const sjhip_ctx *part, uint32_t n) {
+            QWhere w;
+            WhereNew nw;
+            unsigned long long *totals;
+            return layout(Carve(), part, n, &w, &nw, &totals) + 64;
+        },
+        [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
+            unsigned long long *totals, *const none = nullptr;
+            (void)layout(Carve(part->d_kat.p), part, n, &work[k], &fresh[k], &totals);
+            const u32 tiles = (n + QTILE - 1) / QTILE;
+            HIPCHK(hipMemsetAsync(totals, 0, 256, part->stream), "row predicate totals memset");
+            HIPCHK(hipMemsetAsync(work[k].tiles, 0, (size_t)tiles * 8, part->stream), "row predicate tiles memset");
+            hipLaunchKernelGGL(k_q_where_mark, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, pth, op, want, negate, work[k]);
+            hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, part->stream, work[k].tiles, none, none, tiles, totals);
+            HIPCHK(hipGetLastError(), "row predicate launch");
+            HIPCHK(hipMemcpyAsync(part->h_scratch + 512, totals, 8, hipMemcpyDeviceToHost, part->stream), "D2H kept rows");
+            return SJHIP_OK;
+        },
+        [&](size_t k, sjhip_ctx *part) {
+            kept[k] = part_rows(ctx, part, true) ? (size_t)*(const unsigned long long *)(part->h_scratch + 512) : 0;
+        });
+    if (rc) return rc;
+    rc = query_over_parts(ctx, parts, keys, klen, val, vlen, true, "row predicate gather sync", [](const sjhip_ctx *, uint32_t) { return (size_t)0; },
+        [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
+            const size_t recs = (size_t)part->q_records + 1u;
+            RowsOut old, o;
+            QWhere w = work[k];
+            w.index = SJ_ARR(fresh[k].index, kept[k], A_ROWS);
+            w.off = SJ_ARR(fresh[k].off, recs + 1, A_WHERE_OFF);
+            w.status = fresh[k].status;
+            w.old_off = nullptr;
+            w.old_status = nullptr;
+            if (sel) {
+                const ResultState::Rows &z = part->res.rows.sizes();
+                (void)rows_layout(Carve(part->d_rows.p), z.records, z.rows, &old);
+                w.old_off = SJ_ARR((const u64 *)old.off, z.records + 1, A_WHERE_OFF);
+                w.old_status = old.status;
+                (void)rows_layout(Carve(part->d_rows.p), recs, kept[k], &o);
+            } else {
+                const int rc = reserve_layout(part, part->d_rows, [&](Carve cv) { return rows_layout(cv, recs, kept[k], &o); });
+                if (rc) return rc;
+            }
+            hipLaunchKernelGGL(k_q_where_apply, dim3((n + QTILE - 1) / QTILE), dim3(QT), 0, part->stream, q, w);
+            hipLaunchKernelGGL(k_q_where_offsets, dim3(((u32)recs + 255) / 256), dim3(256), 0, part->stream, q, w, (u64)kept[k]);
+            HIPCHK(hipGetLastError(), "row predicate gather launch");
+            HIPCHK(hipMemcpyAsync(o.off, fresh[k].off, (recs + 1) * 8, hipMemcpyDeviceToDevice, part->stream), "row offsets copy");
+            HIPCHK(hipMemcpyAsync(o.status, fresh[k].status, recs, hipMemcpyDeviceToDevice, part->stream), "row status copy");
+            if (kept[k])
+                HIPCHK(hipMemcpyAsync(o.index, fresh[k].index, kept[k] * 8, hipMemcpyDeviceToDevice, part->stream), "row index copy");
+            return SJHIP_OK;
+        },
+        [](size_t, sjhip_ctx *) {});
+    if (rc) return rc;
+    ResultState::Rows total;
+    bool ok = true;  // (a part without rows launched nothing and is republished as it was: its records, no rows)
+    for (size_t k = 0; k < parts.size(); k++) {
+        const ResultState::Rows s = {(size_t)parts[k]->q_records + 1u, kept[k]};
+        ok &= parts[k]->res.publish(&ResultState::rows, s);
+        total.records += s.records, total.rows += s.rows;
+    }
+    if (ctx->res.sharded()) ok &= ctx->res.publish(&ResultState::rows, total);
+    *records = total.records, *rows = total.rows;
+    return published(ctx, ok);
+}
+
+int sjhip_where_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int op, const void *value,
+                     size_t vlen, uint32_t flags, size_t *records, size_t *rows) {
+    if (!ctx || !records || !rows) return SJHIP_ERR_ARG;
+    if (flags & ~SJHIP_WHERE_NOT) {
+        ctx_set_error(ctx, "sjhip_where_path: unknown flag bits 0x%x", flags & ~SJHIP_WHERE_NOT);
+        return SJHIP_ERR_ARG;
+    }
+    bool is_str = false;
+    u64 want = 0;
+    int rc = predicate_value(op, value, vlen, &want, &is_str);
+    if (rc) {
+        ctx_set_error(ctx, "sjhip_where_path: operator %d with a value of %zu bytes", op, vlen);
+        return rc;
+    }
+    QPath pth;
+    size_t klen = 0;
+    rc = make_path(ctx, keys, key_lens, n_keys, &pth, &klen, true);
+    if (rc) return rc;
+    const uint8_t *const kb = keys ? keys : &NO_VALUE, *const vb = is_str && value ? (const uint8_t *)value : &NO_VALUE;
+    const size_t vl = is_str ? vlen : 0;
+    std::vector<sjhip_ctx *> parts;
+    rc = query_parts(ctx, kb, klen, vb, vl, &parts);
+    if (rc) return rc;  // (nothing has been queued: the selection is as it was)
+    rc = where_build(ctx, parts, kb, klen, vb, vl, pth, op, want, flags & SJHIP_WHERE_NOT, records, rows);
+    if (rc) {  // half-built: the old selection may have been written over
+        ctx->res.rows.begin();
+        for (sjhip_ctx *part : parts) part->res.rows.begin();
+        char why[sizeof ctx->err];
+        snprintf(why, sizeof why, "%s", ctx->err);
+        ctx_set_error(ctx, "sjhip_where_path failed and the row selection was given up: %.180s", why);
+    }
+    return rc;
 }

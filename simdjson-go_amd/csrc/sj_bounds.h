@@ -32,7 +32,9 @@ enum ArrId : uint32_t {
     A_LIST_VAL, A_LIST_SOFF, A_LIST_DATA,  // a list column (query.hip): its values / its string offsets / its string bytes
     // a table (query.hip): the values and statuses of its numeric columns / the work arrays of its string columns / their bytes
     A_TABLE_OUT, A_TABLE_WORK, A_TABLE_DATA,
-    A_ROWS  // the row index of a row selection (query.hip): written by the compaction, read by every query that runs on rows
+    A_ROWS,  // the row index of a row selection (query.hip): written by the compaction, read by every query that runs on rows
+    // a row predicate (query.hip, sjhip_where_path): the flag of every current row / the kept rows in front of it / the new row offsets
+    A_WHERE_FLAG, A_WHERE_PRE, A_WHERE_OFF
 };
 
 #if defined(SJ_DEBUG_BOUNDS)

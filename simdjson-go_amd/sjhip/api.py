@@ -232,6 +232,9 @@ class Context:
     PATH_NOT_FOUND = 0xFFFFFFFFFFFFFFFF
     PATH_NOT_OBJECT = 0xFFFFFFFFFFFFFFFE
     OP_EXISTS, OP_EQ_STRING, OP_EQ_INT, OP_EQ_UINT, OP_EQ_FLOAT, OP_EQ_BOOL, OP_IS_NULL = range(7)
+    (OP_LT_INT, OP_LE_INT, OP_GT_INT, OP_GE_INT, OP_LT_UINT, OP_LE_UINT, OP_GT_UINT, OP_GE_UINT,
+     OP_LT_FLOAT, OP_LE_FLOAT, OP_GT_FLOAT, OP_GE_FLOAT, OP_PREFIX_STRING) = range(7, 20)
+    WHERE_NOT = 1
 
     @staticmethod
     def _keys(keys):
@@ -251,23 +254,27 @@ class Context:
         self._check(L.sjhip_find_path(self._h, blob, lens, n, out.ctypes.data, out.size, C.byref(cnt)))
         return out[: cnt.value]
 
-    def count_where_path(self, path, op, value=None):
-        """records whose element at `path` exists and satisfies op (OP_*): value = bytes for OP_EQ_STRING, an int for
-        OP_EQ_INT / OP_EQ_UINT, a float for OP_EQ_FLOAT, a bool for OP_EQ_BOOL"""
+    def _op_value(self, op, value):
+        """the value of a typed predicate as the bytes the C call takes: bytes for OP_EQ_STRING / OP_PREFIX_STRING, an int for the
+        *_INT / *_UINT operators, a float for the *_FLOAT ones, a bool for OP_EQ_BOOL, nothing for the others"""
         import struct
+        if op in (self.OP_EQ_STRING, self.OP_PREFIX_STRING):
+            return bytes(value)
+        if op == self.OP_EQ_INT or self.OP_LT_INT <= op <= self.OP_GE_INT:
+            return struct.pack("<q", int(value))
+        if op == self.OP_EQ_UINT or self.OP_LT_UINT <= op <= self.OP_GE_UINT:
+            return struct.pack("<Q", int(value))
+        if op == self.OP_EQ_FLOAT or self.OP_LT_FLOAT <= op <= self.OP_GE_FLOAT:
+            return struct.pack("<d", float(value))
+        if op == self.OP_EQ_BOOL:
+            return b"\x01" if value else b"\x00"
+        return b""
+
+    def count_where_path(self, path, op, value=None):
+        """records whose element at `path` exists and satisfies op (OP_*): value = bytes for OP_EQ_STRING / OP_PREFIX_STRING, an int
+        for the *_INT / *_UINT operators, a float for the *_FLOAT ones, a bool for OP_EQ_BOOL"""
         blob, lens, n = self._keys(path)
-        if op == self.OP_EQ_STRING:
-            v = bytes(value)
-        elif op == self.OP_EQ_INT:
-            v = struct.pack("<q", int(value))
-        elif op == self.OP_EQ_UINT:
-            v = struct.pack("<Q", int(value))
-        elif op == self.OP_EQ_FLOAT:
-            v = struct.pack("<d", float(value))
-        elif op == self.OP_EQ_BOOL:
-            v = b"\x01" if value else b"\x00"
-        else:
-            v = b""
+        v = self._op_value(op, value)
         buf = C.create_string_buffer(v, max(len(v), 1))
         cnt = C.c_uint64(0)
         self._check(_lib.lib().sjhip_count_where_path(self._h, blob, lens, n, int(op), buf, len(v), C.byref(cnt)))
@@ -428,6 +435,19 @@ class Context:
     def select_records(self):
         """back to one row per record (no error if nothing was selected)"""
         self._check(_lib.lib().sjhip_select_records(self._h))
+
+    def where_path(self, path, op, value=None, negate=False):
+        """keeps the rows -- of the selection in force, or without one the records, which then become a selection of one row each --
+        whose element at `path` exists and satisfies op (count_where_path's predicate and values; an empty path: the row's own
+        value); negate: keeps the others instead.  Successive calls narrow further; select_records() goes back.
+        -> (records, rows kept); fetch_rows(records, rows) delivers the selection"""
+        blob, lens, n = self._keys(path)
+        v = self._op_value(op, value)
+        buf = C.create_string_buffer(v, max(len(v), 1))
+        nr, nw = C.c_size_t(0), C.c_size_t(0)
+        self._check(_lib.lib().sjhip_where_path(self._h, blob if n else None, lens if n else None, n, int(op), buf, len(v),
+                                                self.WHERE_NOT if negate else 0, C.byref(nr), C.byref(nw)))
+        return nr.value, nw.value
 
     def serialize(self, fetch=True, dedup=False):
         """Serializer.Serialize (format v3, CompressNone) of the device-resident result of the last parse.
