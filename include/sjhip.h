@@ -165,7 +165,8 @@ void sjhip_trim_space(const uint8_t *msg, size_t len, size_t *off, size_t *out_l
  *   count_where : number of matching records; 8 bytes cross PCIe.
  *   filter_where: compacts the matching records into a new self-contained (Tape, Strings.B) on the device, identical
  *                 to ParseND of the document made of the matching lines (root chain re-linked, container / string
- *                 offsets rebased); sjhip_fetch_filtered copies it to the host.  Needs SJHIP_FLAG_COPY_STRINGS. */
+ *                 offsets rebased); sjhip_fetch_filtered copies it to the host.  Needs SJHIP_FLAG_COPY_STRINGS.
+ *                 (Any other predicate, and rows inside arrays: sjhip_where_path + sjhip_filter_rows below.) */
 int sjhip_count_where(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const uint8_t *value, size_t vlen, uint64_t *count);
 int sjhip_filter_where(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const uint8_t *value, size_t vlen,
                        uint64_t *n_records, size_t *tape_len, size_t *strings_len);
@@ -322,7 +323,7 @@ int sjhip_fetch_table_column(sjhip_ctx *ctx, uint32_t col, void *values, uint64_
  * sjhip_extract_path_strings, sjhip_extract_path_list[_strings] and sjhip_extract_table; their *records and cap_records count rows.
  * A row that is not an object gets SJHIP_PATH_NOT_OBJECT / SJHIP_COL_NOT_OBJECT, the rule for a root value that is not an object.
  * With no rows they return *records = 0 and launch nothing.  sjhip_count_where, sjhip_filter_where, the serializer, MarshalJSON and
- * the stream's filter work on records and ignore the selection.
+ * the stream's filter work on records and ignore the selection (sjhip_filter_rows below is the filter that reads it).
  * The selection lives in a device arena of its own (sjhip_ctx_device_bytes counts it, sjhip_ctx_trim frees it): it lasts until the
  * next parse, the next sjhip_select_rows or sjhip_select_records, is dropped by everything that drops the other products, survives
  * the string column, the list column, the table, the filter, the serializer and MarshalJSON, and they survive it.  A column, list or
@@ -365,6 +366,31 @@ int sjhip_select_records(sjhip_ctx *ctx);
 #define SJHIP_WHERE_NOT 1u
 int sjhip_where_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int op, const void *value,
                      size_t vlen, uint32_t flags, size_t *records, size_t *rows);
+/* Filter rows: the rows of the selection in force -- sjhip_select_rows' or the one sjhip_where_path narrowed or created -- as a new
+ * self-contained (Tape, Strings.B) on the device, one root per row: what a caller of ParseND reads with Iter.  With it,
+ * sjhip_where_path followed by sjhip_filter_rows is sjhip_filter_where for every operator, for conjunctions and negation, for
+ * nested paths and for rows inside arrays; only the wanted rows cross PCIe.
+ *   sjhip_filter_rows     Every selected row whose value is an object or an array contributes, in selection order, an opening root
+ *                          word 'r' << 56 | index behind its closing root, the row's tape words [v, payload(tape[v])), and a closing
+ *                          root word 'r' << 56 | index of its opening root.  Inside the row the payload of every { } [ ] word is moved
+ *                          by (new index - old index) and the payload of every string word to the new Strings.B; the second words of
+ *                          strings and numbers are copied as they are.  The new Strings.B is the rows' string bytes end to end: a row
+ *                          owns the bytes from its first string to the end of its last one (keys and the strings of nested containers
+ *                          included).  The result is bit for bit the (Tape, Strings.B) ParseND with copied strings returns for the
+ *                          document whose lines are the texts of those rows.  A selected row that is a scalar -- a string, a number,
+ *                          true / false / null -- has no such tape (a scalar line is no document): it is left out and counted.
+ *                          *n_rows = the rows emitted, *skipped = the scalar rows left out, *tape_len / *strings_len = the sizes of
+ *                          the result; any of them may be NULL.  No row emitted is legal: both sizes are 0.  sjhip_fetch_filtered
+ *                          copies the result to the host.
+ * Errors: SJHIP_ERR_ARG, with sjhip_last_error naming the reason and nothing touched, without a whole result on the context (a sharded
+ * ND result says so, as for sjhip_filter_where), without a row selection ("no row selection") and after a parse without
+ * SJHIP_FLAG_COPY_STRINGS; SJHIP_ERR_TOOBIG if the result would exceed 2^32 - 1 tape words (every row gains two root words: the
+ * result of [[],[],[]] is larger than its source).
+ * The result is the filtered result of the context, like sjhip_filter_where's: it replaces the last filtered, serialized or marshaled
+ * product and is replaced by the next one and by the next parse.  The selection, the string column, the list column and the table
+ * stay as they are.  The cost is one pass over the words of the selected rows to measure them, a fixed number of passes over 16
+ * bytes per row, and one pass that copies. */
+int sjhip_filter_rows(sjhip_ctx *ctx, uint64_t *n_rows, uint64_t *skipped, size_t *tape_len, size_t *strings_len);
 
 /* ---- Serializer.Serialize on the device (parsed_serialize.go:200-431, format version 3) -----------------------------
  * Splits the device-resident tape of the last parse (SJHIP_FLAG_COPY_STRINGS) into the reference's three columns --

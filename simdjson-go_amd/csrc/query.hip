@@ -7,6 +7,8 @@
 // sjhip_count_where evaluates exactly that on the device and returns 8 bytes; sjhip_filter_where compacts the
 // matching records into a new, self-contained (Tape, Strings.B) on the device -- bit-identical to what ParseND
 // produces for the document made of the matching lines -- so that only the subset crosses PCIe.
+// sjhip_filter_rows does the same for the rows of the row selection (sjhip_select_rows / sjhip_where_path): any predicate, rows
+// inside arrays, one root per row.
 //
 // Semantics of a match (the reference's countWhere): the record's root value is an object; the FIRST member of that
 // object whose key equals `key` (top level only, FindKey does not descend) has a string value equal to `value`.
@@ -1138,6 +1140,159 @@ __global__ __launch_bounds__(256) void k_q_where_offsets(QView q, QWhere w, u64 
     if (r == q.R) w.off[r + 1] = kept;
 }
 
+// ---- filter rows: the selected rows as a self-contained (Tape, Strings.B) (sjhip_filter_rows) ---------------------------------------
+// The materialiser of the row selection: every selected row that is a container becomes a record of a new result -- an opening
+// root, the row's words [v, payload(tape[v])) with every stored index rebased, a closing root -- and the string bytes of the rows
+// are laid end to end: what ParseND returns for the document whose lines are the texts of those rows.  A scalar row has no such
+// record (stage 1 rejects a scalar line): it is left out and counted.
+//   k_q_frows_measure     per row: its output words (0: a scalar), the Strings.B offset of its first string and the end of its
+//                         last one.  Rows do not tile the tape -- what lies between two rows belongs to neither -- so the last
+//                         string is found by classifying the row's own words: a row of up to FROWS_SHORT words by its lane, entry
+//                         by entry; every longer row of the wave's 64 by the whole wave in turn, 64 words per step, tags told
+//                         from raw words by the parity rule (sj_tapewalk.h; the row's opening word is a tag: the anchor) from one
+//                         ballot, the first and the last string of a step from another.  Emitted and skipped rows are counted
+//                         from the wave's ballots.
+//   scan                  exclusive prefixes of the words and of the string bytes over the rows (the filter's tile pattern:
+//                         sums -> k_tw_scan_sums -> apply); both totals and both counts reach the host in one copy
+//   k_q_frows_copy        one wave per emitted row, the shape of k_q_copy: roots synthesised, bracket payloads moved by
+//                         (new index - old index), string payloads by (new offset - old offset), raw words untouched; then the
+//                         row's bytes, 64 at a time
+// A row owns Strings.B from its first string to the end of its last: strings lie in document order and a row is one stretch of the
+// document, so everything in between is a string of the row (keys and nested strings included).
+static constexpr u32 FROWS_SHORT = 128;  // words of a row its lane walks alone
+struct QFRows {
+    Arr<u32> words;      // [n] output words of the row (0: a scalar) -> their exclusive prefix = new index of its opening root
+    Arr<u32> first_str;  // [n] Strings.B offset of its first string (NONE32: it has none)
+    Arr<u32> s_len;      // [n] bytes of Strings.B it owns (0 for a scalar)
+    Arr<u32> s_pre;      // [n] their exclusive prefix = new Strings.B offset of its first string
+    unsigned long long *tw, *tb;  // [tiles] tile sums of words / s_len -> their exclusive prefixes
+    unsigned long long *totals;   // [0] words, [1] bytes (the scans); [4] rows emitted, [5] scalar rows skipped (the measure)
+};
+__device__ __forceinline__ u32 str_offset(u64 w) { return (u32)(w & (STRINGBUFBIT - 1)); }  // (every string is copied: the host checked)
+// the strings of the row [v, end) by one lane: entry by entry (a number's second word is stepped over)
+__device__ __forceinline__ void lane_row_strings(const QView &q, u64 v, u64 end, u32 *first, u32 *last_end) {
+    u64 last = 0;
+    u32 fs = NONE32;
+    for (u64 i = v; i < end;) {
+        const u64 w = q.tape[i];
+        if ((w >> 56) == '"') {
+            if (fs == NONE32) fs = str_offset(w);
+            last = i;
+        }
+        i += two_word_tag(w) ? 2 : 1;
+    }
+    *first = fs;
+    *last_end = fs == NONE32 ? 0u : str_offset(q.tape[last]) + (u32)q.tape[last + 1];
+}
+// ... and by the whole wave, 64 words per step (arguments and results wave-uniform)
+__device__ __forceinline__ void wave_row_strings(const QView &q, u64 v, u64 end, int lane, u32 *first, u32 *last_end) {
+    const u64 nwords = end - v;
+    long long p_prev = -1;  // last anchor below the group, relative to the row (none: word 0, a tag, is the first)
+    u32 fs = NONE32, le = 0;
+    for (u64 g = 0; g < nwords; g += 64) {
+        const u64 i = g + (u64)lane;
+        const bool in = i < nwords;
+        const u64 w = in ? q.tape[v + i] : 0;
+        const u64 zm = ~__ballot(in && two_word_tag(w)) & __ballot(in);  // the anchors of the group
+        const u64 zeros_below = zm & (lane ? (~0ull >> (64 - lane)) : 0ull);
+        const long long p = zeros_below ? (long long)g + (63 - __builtin_clzll(zeros_below)) : p_prev;
+        const bool raw = p >= 0 && ((((long long)i - p - 1) & 1) != 0);
+        const bool str = in && !raw && (w >> 56) == '"';
+        // (a string's length word may lie in the next group: its own lane reads it; it lies inside the row, a close follows it)
+        const u32 mine = str ? str_offset(w) + (u32)q.tape[v + i + 1] : 0u;
+        const u64 sm = __ballot(str);
+        if (sm) {
+            if (fs == NONE32) fs = (u32)__shfl((int)str_offset(w), __ffsll((unsigned long long)sm) - 1, 64);
+            le = (u32)__shfl((int)mine, 63 - __builtin_clzll(sm), 64);
+        }
+        if (zm) p_prev = (long long)g + (63 - __builtin_clzll(zm));
+    }
+    *first = fs;
+    *last_end = le;
+}
+__global__ __launch_bounds__(256) void k_q_frows_measure(QView q, QFRows o) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool have = r < q_rows(q);
+    u64 v = 0, end = 0;
+    u32 first = NONE32, last_end = 0;
+    bool box = false, wide = false;
+    if (have) {
+        v = row_value(q, r);
+        const u64 w = q.tape[v];
+        const u32 t = (u32)(w >> 56);
+        box = t == '{' || t == '[';
+        if (box) {
+            end = w & TW_PAYLOAD;  // behind the matching close
+            wide = end - v > FROWS_SHORT;
+            if (!wide) lane_row_strings(q, v, end, &first, &last_end);
+        }
+    }
+    for (u64 todo = __ballot(wide); todo; todo &= todo - 1) {  // the wave's long rows, one after another
+        const int j = __ffsll((unsigned long long)todo) - 1;
+        const u64 vj = (u64)__shfl((long long)v, j, 64), ej = (u64)__shfl((long long)end, j, 64);
+        u32 f_j, l_j;
+        wave_row_strings(q, vj, ej, lane, &f_j, &l_j);
+        if (lane == j) {
+            first = f_j;
+            last_end = l_j;
+        }
+    }
+    if (have) {
+        o.words[r] = box ? (u32)(end - v) + 2u : 0u;
+        o.first_str[r] = first;
+        o.s_len[r] = first == NONE32 ? 0u : last_end - first;
+    }
+    count_ballot(box, &o.totals[4]);
+    count_ballot(have && !box, &o.totals[5]);
+}
+__global__ __launch_bounds__(QT) void k_q_frows_tile_sums(QFRows o, u32 n) {
+    tile_sums(arr_raw(o.words), n, o.tw);
+    tile_sums(arr_raw(o.s_len), n, o.tb);
+}
+__global__ __launch_bounds__(QT) void k_q_frows_tile_apply(QFRows o, u32 n) {
+    tile_apply(arr_raw(o.words), arr_raw(o.words), n, o.tw);
+    tile_apply(arr_raw(o.s_len), arr_raw(o.s_pre), n, o.tb);
+}
+__global__ __launch_bounds__(256) void k_q_frows_copy(QView q, QFRows o, Arr<u64> out_tape, Arr<u8> out_strings) {
+    const u32 r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (r >= q_rows(q)) return;  // wave-uniform, like the next one
+    const u64 v = row_value(q, r), w0 = q.tape[v];
+    const u32 t0 = (u32)(w0 >> 56);
+    if (t0 != '{' && t0 != '[') return;
+    const u64 nwords = (w0 & TW_PAYLOAD) - v;  // the row's own words; its record: a root on either side
+    const u64 na = o.words[r];                 // new index of the opening root
+    const long long dw = (long long)(na + 1) - (long long)v;
+    const u32 sb = o.first_str[r], slen = o.s_len[r], ns = o.s_pre[r];
+    const u64 ds = (u64)((long long)ns - (long long)sb);  // only used when the row has a string
+    if (lane == 0) {
+        out_tape[na] = ((u64)'r' << 56) | (na + nwords + 2);  // behind its closing root: the next record, or the tape length
+        out_tape[na + nwords + 1] = ((u64)'r' << 56) | na;
+    }
+    long long p_prev = -1;  // last anchor below the group, relative to the row (none: word 0 is the first)
+    for (u64 g = 0; g < nwords; g += 64) {
+        const u64 i = g + (u64)lane;
+        const bool in = i < nwords;
+        const u64 w = in ? q.tape[v + i] : 0;
+        const u32 t = (u32)(w >> 56);
+        const u64 zm = ~__ballot(in && two_word_tag(w)) & __ballot(in);  // the anchors of the group
+        const u64 zeros_below = zm & (lane ? (~0ull >> (64 - lane)) : 0ull);
+        const long long p = zeros_below ? (long long)g + (63 - __builtin_clzll(zeros_below)) : p_prev;
+        const bool raw = p >= 0 && ((((long long)i - p - 1) & 1) != 0);
+        if (in) {
+            u64 x = w;
+            if (!raw) {
+                if (t == '{' || t == '[' || t == '}' || t == ']') x = (w & ~TW_PAYLOAD) | (u64)((long long)(w & TW_PAYLOAD) + dw);
+                else if (t == '"') x = w + ds;
+            }
+            out_tape[na + 1 + i] = x;
+        }
+        if (zm) p_prev = (long long)g + (63 - __builtin_clzll(zm));
+    }
+    for (u32 k = (u32)lane; k < slen; k += 64) out_strings[(u64)ns + k] = q.strings[(u64)sb + k];
+}
+
 }  // namespace
 
 namespace sj {
@@ -1365,7 +1520,7 @@ int sjhip_filter_where(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const ui
 int sjhip_fetch_filtered(sjhip_ctx *ctx, uint64_t *tape_dst, uint8_t *strings_dst) {
     if (!ctx) return SJHIP_ERR_ARG;
     if (!ctx->res.filtered()) {  // no filter ran, or a later parse / serialize / marshal call re-used its arenas
-        ctx_set_error(ctx, "no filtered result on the device (sjhip_fetch_filtered follows sjhip_filter_where)");
+        ctx_set_error(ctx, "no filtered result on the device (sjhip_fetch_filtered follows sjhip_filter_where or sjhip_filter_rows)");
         return SJHIP_ERR_ARG;
     }
     HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
@@ -1376,7 +1531,7 @@ int sjhip_fetch_filtered(sjhip_ctx *ctx, uint64_t *tape_dst, uint8_t *strings_ds
         HIPCHK(hipMemcpyAsync(strings_dst, ctx->d_qstrings.p, f.strings_len, hipMemcpyDeviceToHost, ctx->stream),
                "D2H filtered strings");
     HIPCHK(hipStreamSynchronize(ctx->stream), "fetch sync");
-    return query_bounds_check(ctx);  // (debug build: the copy kernel of sjhip_filter_where has finished here)
+    return query_bounds_check(ctx);  // (debug build: the copy kernel of sjhip_filter_where / sjhip_filter_rows has finished here)
 }
 
 // ---- paths, typed values, key sets ------------------------------------------------------------------------------------------
@@ -2247,4 +2402,75 @@ int sjhip_where_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_le
         ctx_set_error(ctx, "sjhip_where_path failed and the row selection was given up: %.180s", why);
     }
     return rc;
+}
+
+// ---- filter rows -------------------------------------------------------------------------------------------------------------------
+// sjhip_filter_rows materialises the selection in force as the Filtered tenant of the shared arenas, in sjhip_filter_where's
+// order: the checks (which touch nothing), the claim, the work arrays in d_q, measure and scan, the totals, the output arenas --
+// sized from the measured totals: a row of two words becomes a record of four, the result can be larger than the tape it came
+// from --, the publish, the copy.  It reads the selection and leaves it, and every other product, as they are.
+int sjhip_filter_rows(sjhip_ctx *ctx, uint64_t *n_rows, uint64_t *skipped, size_t *tape_len, size_t *strings_len) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!ctx->res.whole()) return no_whole_result(ctx, "sjhip_filter_rows", "queries follow");  // the unsharded result of ctx itself
+    if (!ctx->res.rows.exists())
+        return no_product(ctx, "no row selection on the device (sjhip_filter_rows follows sjhip_select_rows or sjhip_where_path)");
+    if (!(ctx->p_flags & SJHIP_FLAG_COPY_STRINGS)) {
+        ctx_set_error(ctx, "sjhip_filter_rows needs a parse with SJHIP_FLAG_COPY_STRINGS (the filtered Strings.B is self-contained)");
+        return SJHIP_ERR_ARG;
+    }
+    QView q;
+    int rc = make_view(ctx, ctx, &NO_VALUE, 0, &NO_VALUE, 0, &q, true);
+    if (rc) return rc;
+    const uint32_t n = part_rows(ctx, ctx, true);
+    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    ctx->res.claim_shared();
+    unsigned long long *h = (unsigned long long *)(ctx->h_scratch + 512);
+    memset(h, 0, 48);  // (a selection without rows measures nothing)
+    QFRows o{};
+    if (n) {
+        const u32 tiles = (n + QTILE - 1) / QTILE;
+        rc = reserve_layout(ctx, ctx->d_q, [&](Carve c) {
+            o.totals = c.take<unsigned long long>(32);
+            u32 *const words = c.take<u32>(n), *const first_str = c.take<u32>(n), *const s_len = c.take<u32>(n), *const s_pre = c.take<u32>(n);
+            o.words = SJ_ARR(words, n, A_FROWS_WORDS);
+            o.first_str = SJ_ARR(first_str, n, A_FROWS_STR);
+            o.s_len = SJ_ARR(s_len, n, A_FROWS_STR);
+            o.s_pre = SJ_ARR(s_pre, n, A_FROWS_STR);
+            o.tw = c.take<unsigned long long>(tiles);
+            o.tb = c.take<unsigned long long>(tiles);
+            return c.used;
+        });
+        if (rc) return rc;
+        unsigned long long *const none = nullptr;
+        HIPCHK(hipMemsetAsync(o.totals, 0, 256, ctx->stream), "filter rows totals memset");
+        hipLaunchKernelGGL(k_q_frows_measure, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, q, o);
+        hipLaunchKernelGGL(k_q_frows_tile_sums, dim3(tiles), dim3(QT), 0, ctx->stream, o, n);
+        hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, o.tw, o.tb, none, tiles, o.totals);
+        hipLaunchKernelGGL(k_q_frows_tile_apply, dim3(tiles), dim3(QT), 0, ctx->stream, o, n);
+        HIPCHK(hipGetLastError(), "filter rows launch");
+        HIPCHK(hipMemcpyAsync(h, o.totals, 48, hipMemcpyDeviceToHost, ctx->stream), "D2H filter rows totals");
+        HIPCHK(hipStreamSynchronize(ctx->stream), "filter rows sync");
+    }
+    const unsigned long long words = h[0], bytes = h[1], emitted = h[4], scalars = h[5];  // (sums of 64 bits)
+    if (words > 0xffffffffull) {
+        ctx_set_error(ctx, "sjhip_filter_rows: the result would hold %llu tape words (at most 2^32 - 1)", words);
+        return SJHIP_ERR_TOOBIG;
+    }
+    if (emitted) {
+        rc = arena_reserve(ctx, ctx->d_qtape, (size_t)words * 8 + 64);
+        if (rc) return rc;
+        rc = arena_reserve(ctx, ctx->d_qstrings, (size_t)bytes + 64);
+        if (rc) return rc;
+    }
+    rc = published(ctx, ctx->res.publish_filtered({(size_t)words, (size_t)bytes}));
+    if (rc) return rc;
+    if (n_rows) *n_rows = emitted;
+    if (skipped) *skipped = scalars;
+    if (tape_len) *tape_len = (size_t)words;
+    if (strings_len) *strings_len = (size_t)bytes;
+    if (emitted == 0) return query_bounds_check(ctx);
+    hipLaunchKernelGGL(k_q_frows_copy, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, q, o, SJ_ARR((u64 *)ctx->d_qtape.p, words, A_FROWS_TAPE),
+                       SJ_ARR((u8 *)ctx->d_qstrings.p, bytes, A_FROWS_STRINGS));
+    HIPCHK(hipGetLastError(), "filter rows copy launch");
+    return SJHIP_OK;
 }

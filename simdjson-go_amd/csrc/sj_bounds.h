@@ -34,7 +34,10 @@ enum ArrId : uint32_t {
     A_TABLE_OUT, A_TABLE_WORK, A_TABLE_DATA,
     A_ROWS,  // the row index of a row selection (query.hip): written by the compaction, read by every query that runs on rows
     // a row predicate (query.hip, sjhip_where_path): the flag of every current row / the kept rows in front of it / the new row offsets
-    A_WHERE_FLAG, A_WHERE_PRE, A_WHERE_OFF
+    A_WHERE_FLAG, A_WHERE_PRE, A_WHERE_OFF,
+    // the filtered rows (query.hip, sjhip_filter_rows): the output words of every row and their prefix / the Strings.B range of every
+    // row (first string, bytes, their prefix) / the new tape / the new Strings.B
+    A_FROWS_WORDS, A_FROWS_STR, A_FROWS_TAPE, A_FROWS_STRINGS
 };
 
 #if defined(SJ_DEBUG_BOUNDS)

@@ -449,6 +449,22 @@ class Context:
                                                 self.WHERE_NOT if negate else 0, C.byref(nr), C.byref(nw)))
         return nr.value, nw.value
 
+    def filter_rows(self, fetch=True):
+        """The rows of the selection in force (select_rows / where_path) as a new self-contained (Tape, Strings.B) on the device,
+        one root per row -- what ParseND returns for the document whose lines are the texts of those rows; scalar rows are left
+        out and counted.  where_path + filter_rows is filter_where for every operator, conjunctions, nested paths and rows inside
+        arrays.  -> (n_rows, skipped, ParsedJson), or with fetch=False (n_rows, skipped, (tape_len, strings_len)) and the result
+        stays on the device"""
+        n, sk, tl, sl = C.c_uint64(0), C.c_uint64(0), C.c_size_t(0), C.c_size_t(0)
+        L = _lib.lib()
+        self._check(L.sjhip_filter_rows(self._h, C.byref(n), C.byref(sk), C.byref(tl), C.byref(sl)))
+        if not fetch:
+            return n.value, sk.value, (tl.value, sl.value)
+        tape = np.empty(tl.value, dtype=np.uint64)
+        strings = np.empty(sl.value, dtype=np.uint8)
+        self._check(L.sjhip_fetch_filtered(self._h, tape.ctypes.data, strings.ctypes.data))
+        return n.value, sk.value, ParsedJson(b"", tape, strings)
+
     def serialize(self, fetch=True, dedup=False):
         """Serializer.Serialize (format v3, CompressNone) of the device-resident result of the last parse.
         -> the framed stream as a uint8 array (what the reference's Deserialize reads), or its sizes with fetch=False.
