@@ -446,6 +446,25 @@ int sjhip_fetch_marshaled(sjhip_ctx *ctx, uint8_t *dst);
  *   ready    : 1 if the oldest outstanding block has finished, i.e. sjhip_stream_next would return at once, else 0
  *              (a single-threaded caller drains finished blocks with it before every blocking read of its input,
  *              so that results are not withheld while the reader waits for more data)
+ * The states, call by call (SJHIP_ERR_ARG leaves the stream exactly as it was):
+ *   acquire  : with a block already acquired SJHIP_ERR_ARG, and that block stays the acquired one.  Slots are used in
+ *              ring order: after cancel the same slot's block comes again.  *capacity is the slot's own, which is
+ *              larger than sjhip_stream_block_capacity() (always what create was asked for) once the slot has grown.
+ *   grow     : only with a block acquired (else SJHIP_ERR_ARG).  A new_capacity no larger than the slot's returns the
+ *              same block.  The grown block stays with its slot for the life of the stream.
+ *   submit   : without an acquired block, or with len beyond the slot's capacity, SJHIP_ERR_ARG; in the second case the
+ *              block stays acquired (submit again with a valid len, grow, or cancel).  len = 0 is a block like any
+ *              other: an empty document, i.e. SJHIP_ERR_STAGE1 when its turn comes.
+ *   cancel, release : SJHIP_ERR_ARG without an acquired block / a held result.
+ *   next     : while a result is held (not yet released) SJHIP_ERR_ARG, *out zeroed, the held result untouched; ready
+ *              is 0 then, and the held block's slot counts as busy for acquire.  in_flight counts the blocks
+ *              submitted and not yet handed out by next.
+ *   closed   : after next has returned a block's error, next and acquire (so submit_copy) return
+ *              SJHIP_ERR_STREAM_CLOSED; the first such next waits for the blocks still in flight and drops them
+ *              (in_flight is 0 afterwards), and ready is 1: next does not wait.  Of several failing blocks in flight the
+ *              one submitted first is reported, whichever finishes first, after every result in front of it.
+ *   destroy  : at any time from the caller's thread(s) once no other call is running: queued blocks are dropped, a
+ *              running one is waited for, a held result is given up.
  * One thread may submit while another takes results. */
 typedef struct sjhip_stream sjhip_stream;
 typedef struct sjhip_stream_result {
@@ -473,8 +492,9 @@ int sjhip_stream_next(sjhip_stream *s, sjhip_stream_result *out);
 int sjhip_stream_ready(sjhip_stream *s);
 /* Compose the stream with sjhip_filter_where: every block is parsed and filtered on the device and only the matching
  * records' (Tape, Strings.B) -- identical to ParseND of the block's matching lines -- cross PCIe; result.records counts
- * them (a block without matches delivers the empty result: tape_len 0).  Set before the first block is submitted;
- * klen = 0 turns the filter off. */
+ * them (a block without matches delivers the empty result: tape_len 0, strings_len 0).  Set before the first block is
+ * submitted, or later while no block is acquired or in flight (else SJHIP_ERR_ARG, and the stream goes on as it was);
+ * klen = 0 turns the filter off: results are whole blocks again and records is 0. */
 int sjhip_stream_set_filter(sjhip_stream *s, const uint8_t *key, size_t klen, const uint8_t *value, size_t vlen);
 int sjhip_stream_release(sjhip_stream *s);
 
