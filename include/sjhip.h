@@ -425,6 +425,33 @@ int sjhip_fetch_message(sjhip_ctx *ctx, uint8_t *dst);
  * parsed without SJHIP_FLAG_COPY_STRINGS (the strings that are not copied then lie at message offsets beyond 32 bits). */
 int sjhip_marshal_json(sjhip_ctx *ctx, size_t *text_len);
 int sjhip_fetch_marshaled(sjhip_ctx *ctx, uint8_t *dst);
+/* Marshal rows: the rows of the selection in force (sjhip_select_rows / sjhip_where_path) as NDJSON text, built on the device --
+ * the last step of "read, keep the rows that match, write them back": only the text of the kept rows crosses PCIe.
+ *   sjhip_marshal_rows          The compact JSON text of every selected row, in selection order, joined by '\n' (none behind the
+ *                               last).  A row's text follows the per-entry rules of sjhip_marshal_json exactly: brackets as they
+ *                               are, '"' + escapeBytes + '"' for strings, ':' behind a key, ',' behind a completed value unless a
+ *                               closing bracket follows, strconv.AppendInt / AppendUint / appendFloat, true / false / null.  Unlike
+ *                               sjhip_filter_rows a scalar row is not skipped: its text is the scalar's own ("a\"b", -3, 1e+21,
+ *                               null), what Iter.MarshalJSON returns on a scalar element.  *n_rows = the rows written, *text_len =
+ *                               the bytes; either may be NULL.  No rows is legal: text_len is 0.
+ *   sjhip_fetch_marshaled_rows  The text (`text`, >= text_len bytes) and Arrow-style row offsets (`offsets`, n_rows + 1 entries):
+ *                               offsets[i] = the first byte of row i, offsets[n_rows] = text_len + 1 -- as if the last row had its
+ *                               newline too -- so that row i is text[offsets[i] .. offsets[i + 1] - 1) for every i.  Without rows
+ *                               offsets[0] = 0.  Either destination may be NULL.  SJHIP_ERR_ARG after sjhip_marshal_json, whose text
+ *                               has no rows.
+ * The text is the marshaled product of the context, the same tenant as sjhip_marshal_json's: sjhip_fetch_marshaled copies it as
+ * well, it replaces and is replaced by the filtered / serialized / marshaled products and the next parse; the row offsets live
+ * behind the text with the text's lifetime.  The selection, the string column, the list column and the table stay as they are.
+ * With SJHIP_FLAG_KEY_FLAGS on the parse the kernels read the parser's key flags; without it the call builds the same array once,
+ * in a work array of its own (the text is the same either way).  Parses without SJHIP_FLAG_COPY_STRINGS are supported as in
+ * sjhip_marshal_json, with the same SJHIP_ERR_TOOBIG rule for documents of 4 GiB or more.
+ * Errors: SJHIP_ERR_ARG, with sjhip_last_error naming the reason and nothing touched, without a result on the device, without a row
+ * selection ("no row selection") and on a sharded ND result (it says so, as sjhip_filter_rows does); a float that is INF or NaN
+ * gives the error of sjhip_marshal_json ("INF or NaN number found").
+ * The cost is one pass over the words and strings of the selected rows to measure them, a fixed number of passes over 8 bytes per
+ * row, and one pass that writes. */
+int sjhip_marshal_rows(sjhip_ctx *ctx, uint64_t *n_rows, size_t *text_len);
+int sjhip_fetch_marshaled_rows(sjhip_ctx *ctx, uint64_t *offsets /* [n_rows + 1] */, uint8_t *text /* [text_len] */);
 
 /* ---- ParseNDStream: replaces the block pipeline of simdjson_amd64.go:101-216 --------------------------------------
  * The binding cuts the input into blocks that end at a record boundary (simdjson_amd64.go:155-176; tmpSize = 10 MiB)

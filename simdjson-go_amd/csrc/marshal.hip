@@ -85,7 +85,9 @@ struct KeyView {
 
 // the bytes of a string entry: offset and length come out of tape words -- in the debug build (-DSJ_DEBUG_BOUNDS) they are
 // checked against the buffer they point into, a violation is recorded (sj_bounds.h) and the call fails
-__device__ __forceinline__ const u8 *ms_string(const MsView &p, bool inbuf, u64 off, u64 len) {
+// (V: MsView, or MrView of the row kernels below)
+template <typename V>
+__device__ __forceinline__ const u8 *ms_string(const V &p, bool inbuf, u64 off, u64 len) {
 #if defined(SJ_DEBUG_BOUNDS)
     const u64 size = inbuf ? p.strings_len : p.msg_len;
     if (off > size || len > size - off) {
@@ -867,6 +869,331 @@ static void launch_ms_tile(const MsView &p, hipStream_t st) {
             break;
     }
 }
+// ---- marshal rows: the rows of the row selection as NDJSON text (sjhip_marshal_rows) -------------------------------------------------
+// The text of row r is the text of the tape words [v, end): v = the row's value, end = behind its matching close for a container,
+// behind the entry for a scalar (whose text is just the scalar).  Rows do not tile the tape -- what lies between two rows belongs to
+// neither -- so the work is laid out by row, in sjhip_filter_rows' three steps:
+//   k_mr_measure       one lane per row: the text bytes of the row, as a 64-bit sum.  A row of up to MR_SHORT words is walked by its
+//                      lane, entry by entry; every longer row of the wave's 64 by the whole wave in turn, 64 words per step
+//                      (mr_wave_row: tags told from raw words by the parity rule of sj_tapewalk.h, anchored at the row's opening
+//                      word).  The escaped length of a string of MS_LONG bytes or more is measured by the whole wave in both paths.
+//   scan               off[r] = bytes of row r + 1 (its '\n'; off[n] = 0) -> exclusive prefix over n + 1 elements (tile sums ->
+//                      k_tw_scan_sums -> apply): off[r] = first byte of row r, off[n] = text length + 1 -- the row offsets
+//                      sjhip_fetch_marshaled_rows hands out, and the total the host sizes the text by
+//   k_mr_write         one wave per row, 64 words per step: every lane sizes its entry, a wave-exclusive scan places it, lanes
+//                      write short entries, the whole wave writes long strings (8 bytes per lane and step); lane 0 writes the
+//                      '\n' in front of every row but the first and the row's offset behind the text.
+// Keys are told from value strings by the per-tape-index flags: the parser's (SJHIP_FLAG_KEY_FLAGS), or the same array built by
+// k_mr_keyflags from the flags k_ms_keys recovers by string ordinal.
+static constexpr u32 MR_SHORT = 128;  // words of a row its lane walks alone
+// (both row kernels are bounded to four waves per SIMD: the float formatter's registers must not cost occupancy, and never scratch)
+struct MrView {
+    Arr<const u64> tape;
+    Arr<const u64> rows;  // [n] tape index of every row's value (the selection's row index)
+    u32 n;
+    Arr<const u8> kf;     // [tape index of a string entry >> 1] 1: the string is an object key
+    const u8 *strings, *msg;  // (reached through ms_string)
+    u64 strings_len, msg_len;
+    const u8 *strings_end, *msg_end;
+    Arr<u64> off;         // [n + 1] text bytes of row r + 1 -> their exclusive prefix
+    unsigned long long *tiles;   // [tiles of n + 1] sums -> exclusive prefix
+    unsigned long long *totals;  // [0] text length + 1, [2] error flags (1: INF / NaN or an unknown tag)
+    Arr<u8> text;
+    Arr<u64> out_off;     // [n + 1] the row offsets behind the text
+};
+__device__ __forceinline__ bool mr_closes(u64 w) {
+    const u32 t = (u32)(w >> 56);
+    return t == '}' || t == ']';
+}
+// text bytes of an entry with tag t and second word w1, without the bytes of a string between its quotes
+__device__ __forceinline__ u32 mr_fixed_len(u32 t, u64 w1, u32 sep, bool *bad) {
+    if (t == '"') return 2u + sep;
+    if (t == 'l') return int_text_len(w1) + sep;
+    if (t == 'u') return digit_count(w1) + sep;
+    if (t == 'd') {
+        const u32 nl = float_text_len(w1);
+        if (nl == 0) *bad = true;  // Inf / NaN
+        return nl + sep;
+    }
+    if (t == 't' || t == 'n') return 4u + sep;
+    if (t == 'f') return 5u + sep;
+    if (t == '{' || t == '[') return 1u;
+    if (t == '}' || t == ']') return 1u + sep;
+    *bad = true;  // (a root, or no tag at all: not inside a row)
+    return 0;
+}
+__device__ __forceinline__ void mr_str_loc(u64 w, bool *inbuf, u64 *off) {  // (a whole result: no shard bases)
+    const u64 vr = w & TW_PAYLOAD;
+    *inbuf = (vr & STRINGBUFBIT) != 0;
+    *off = vr & ~STRINGBUFBIT;
+}
+// escaped length of a string: by one lane, and by the whole wave (arguments and result wave-uniform)
+__device__ __forceinline__ u32 mr_esc_len_lane(const MrView &p, bool inbuf, u64 off, u64 len) {
+    const u8 *sp = ms_string(p, inbuf, off, len);
+    const u8 *lim = inbuf ? p.strings_end : p.msg_end;
+    u32 el = 0;
+    for (u64 q = 0; q < len; q += 8) el += esc_size8(str_load8(sp, q, len, lim), (u32)(len - q < 8 ? len - q : 8));
+    return el;
+}
+__device__ __forceinline__ u64 mr_esc_len_wave(const MrView &p, bool inbuf, u64 off, u64 len, int lane) {
+    const u8 *sp = ms_string(p, inbuf, off, len);
+    const u8 *lim = inbuf ? p.strings_end : p.msg_end;
+    u64 el = 0;
+    for (u64 q = (u64)lane * 8; q < len; q += 512) el += esc_size8(str_load8(sp, q, len, lim), (u32)(len - q < 8 ? len - q : 8));
+#pragma unroll
+    for (int sft = 32; sft >= 1; sft >>= 1) el += (u64)__shfl_xor((long long)el, sft, 64);
+    return el;
+}
+// the el escaped bytes of a string into text[at ..), by the whole wave: 512 bytes of the string per step
+__device__ __forceinline__ void mr_write_long(const MrView &p, bool inbuf, u64 off, u64 len, int lane, u64 at, u64 el) {
+    const u8 *sp = ms_string(p, inbuf, off, len);
+    const u8 *lim = inbuf ? p.strings_end : p.msg_end;
+    u8 *o = arr_at(p.text, at, el);
+    for (u64 c0 = 0; c0 < len; c0 += 512) {
+        const u64 q = c0 + (u64)lane * 8;
+        u64 x = 0;
+        u32 valid = 0, sz = 0;
+        if (q < len) {
+            valid = (u32)(len - q < 8 ? len - q : 8);
+            x = str_load8(sp, q, len, lim);
+            sz = esc_size8(x, valid);
+        }
+        u32 incl = sz;
+#pragma unroll
+        for (int sft = 1; sft < 64; sft <<= 1) {
+            const u32 up = (u32)__shfl_up((int)incl, sft, 64);
+            if (lane >= sft) incl += up;
+        }
+        if (valid) write_esc8(o + (incl - sz), x, valid);
+        o += (u32)__shfl((int)incl, 63, 64);
+    }
+}
+// The row [v, end) by the whole wave, 64 words per step (arguments and result wave-uniform): -> its text bytes; EMIT: written to
+// text[at ..).  A string whose length word lies in the next step reads it itself, and so does every entry the tag behind it.
+template <bool EMIT>
+__device__ __forceinline__ u64 mr_wave_row(const MrView &p, u64 v, u64 end, int lane, u64 at, bool *bad) {
+    const u64 nwords = end - v;
+    long long p_prev = -1;  // last anchor below the group, relative to the row (none: word 0, a tag, is the first)
+    u64 total = 0;
+    for (u64 g = 0; g < nwords; g += 64) {
+        const u64 i = g + (u64)lane;
+        const bool in = i < nwords;
+        const u64 w = in ? p.tape[v + i] : 0;
+        const u64 zm = ~__ballot(in && two_word_tag(w)) & __ballot(in);  // the anchors of the group
+        const u64 zeros_below = zm & (lane ? (~0ull >> (64 - lane)) : 0ull);
+        const long long pa = zeros_below ? (long long)g + (63 - __builtin_clzll(zeros_below)) : p_prev;
+        // (the row's opening word is a tag: the word in front of the row counts as an anchor, pa = -1)
+        const bool raw = (((long long)i - pa - 1) & 1) != 0;
+        const bool ent = in && !raw;
+        const u32 t = (u32)(w >> 56);
+        const bool two = ent && two_word_tag(w);
+        const u64 w1 = two ? p.tape[v + i + 1] : 0;  // (inside the row: a close follows every entry of a container)
+        const u64 nx = i + (two ? 2u : 1u);
+        const bool opens = t == '{' || t == '[';  // (nothing behind an opening bracket)
+        const u32 sep = (ent && !opens && nx < nwords && !mr_closes(p.tape[v + nx])) ? 1u : 0u;
+        const bool str = ent && t == '"', lng = str && w1 >= MS_LONG;
+        bool sin = false;
+        u64 soff = 0, sz = 0;
+        if (ent) sz = mr_fixed_len(t, w1, sep, bad);
+        if (str) {
+            mr_str_loc(w, &sin, &soff);
+            if (!lng) sz += mr_esc_len_lane(p, sin, soff, w1);
+        }
+        const u64 longs = __ballot(lng);
+        for (u64 m = longs; m; m &= m - 1) {  // the long strings of the step, one after another
+            const int j = __ffsll((unsigned long long)m) - 1;
+            const u64 el = mr_esc_len_wave(p, __shfl((int)sin, j, 64) != 0, (u64)__shfl((long long)soff, j, 64),
+                                           (u64)__shfl((long long)w1, j, 64), lane);
+            if (lane == j) sz += el;
+        }
+        u64 incl = sz;
+#pragma unroll
+        for (int sft = 1; sft < 64; sft <<= 1) {
+            const u64 up = (u64)__shfl_up((long long)incl, sft, 64);
+            if (lane >= sft) incl += up;
+        }
+        if (EMIT) {
+            const u64 mine = at + total + incl - sz;
+            if (ent && sz) {
+                u8 *o = arr_at(p.text, mine, sz);
+                if (str) {
+                    *o++ = '"';
+                    if (lng) {
+                        o += sz - 2u - sep;  // (the wave writes these below)
+                    } else {
+                        const u8 *sp = ms_string(p, sin, soff, w1);
+                        const u8 *lim = sin ? p.strings_end : p.msg_end;
+                        for (u64 q = 0; q < w1; q += 8) o = write_esc8(o, str_load8(sp, q, w1, lim), (u32)(w1 - q < 8 ? w1 - q : 8));
+                    }
+                    *o++ = '"';
+                    if (sep) *o = p.kf[(v + i) >> 1] ? ':' : ',';
+                } else if (t == 'l' || t == 'u') {
+                    o += t == 'l' ? format_int(w1, o) : format_uint(w1, o);
+                    if (sep) *o = ',';
+                } else if (t == 'd') {
+                    o += format_float(w1, o);
+                    if (sep) *o = ',';
+                } else {  // literals and brackets: a constant selected by the tag (a bracket stands for itself)
+                    u64 piece = t == 't' ? 0x65757274ull : t == 'n' ? 0x6c6c756eull : t == 'f' ? 0x65736c6166ull : (u64)t;
+                    const u32 nb = (u32)sz - sep;
+                    if (sep) piece |= (u64)',' << (8u * nb);
+                    for (u32 k = 0; k < (u32)sz; k++) o[k] = (u8)(piece >> (8u * k));
+                }
+            }
+            for (u64 m = longs; m; m &= m - 1) {
+                const int j = __ffsll((unsigned long long)m) - 1;
+                const u64 at_j = (u64)__shfl((long long)mine, j, 64) + 1u;
+                const u64 el_j = (u64)__shfl((long long)sz, j, 64) - 2u - (u64)__shfl((int)sep, j, 64);
+                mr_write_long(p, __shfl((int)sin, j, 64) != 0, (u64)__shfl((long long)soff, j, 64), (u64)__shfl((long long)w1, j, 64), lane,
+                              at_j, el_j);
+            }
+        }
+        total += (u64)__shfl((long long)incl, 63, 64);
+        if (zm) p_prev = (long long)g + (63 - __builtin_clzll(zm));
+    }
+    return total;
+}
+// where row r lies: [*v, *end); (a scalar: its one or two words)
+__device__ __forceinline__ void mr_row_range(const MrView &p, u32 r, u64 *v, u64 *end) {
+    *v = p.rows[r];
+    const u64 w0 = p.tape[*v];
+    const u32 t0 = (u32)(w0 >> 56);
+    *end = (t0 == '{' || t0 == '[') ? (w0 & TW_PAYLOAD) : *v + (two_word_tag(w0) ? 2u : 1u);
+}
+__global__ __launch_bounds__(256, 4) void k_mr_measure(MrView p) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool have = r < p.n;
+    u64 v = 0, end = 0, i = 0, sum = 0;
+    bool wide = false, bad = false;
+    if (have) {
+        mr_row_range(p, r, &v, &end);
+        wide = end - v > MR_SHORT;
+        i = v;
+    }
+    const bool walks = have && !wide;
+    for (;;) {  // (wave-uniform: every lane walks up to its next long string, the wave measures those, the lanes go on)
+        bool pend = false, pin = false;
+        u64 poff = 0, plen = 0;
+        while (walks && i < end) {
+            const u64 w = p.tape[i];
+            const u32 t = (u32)(w >> 56);
+            const bool two = two_word_tag(w);
+            const u64 w1 = two ? p.tape[i + 1] : 0;
+            const u64 nx = i + (two ? 2u : 1u);
+            const u32 sep = (t != '{' && t != '[' && nx < end && !mr_closes(p.tape[nx])) ? 1u : 0u;
+            sum += mr_fixed_len(t, w1, sep, &bad);
+            i = nx;
+            if (t == '"') {
+                mr_str_loc(w, &pin, &poff);
+                plen = w1;
+                if (plen >= MS_LONG) {
+                    pend = true;
+                    break;
+                }
+                sum += mr_esc_len_lane(p, pin, poff, plen);
+            }
+        }
+        const u64 todo = __ballot(pend);
+        if (!todo) break;
+        for (u64 m = todo; m; m &= m - 1) {
+            const int j = __ffsll((unsigned long long)m) - 1;
+            const u64 el = mr_esc_len_wave(p, __shfl((int)pin, j, 64) != 0, (u64)__shfl((long long)poff, j, 64),
+                                           (u64)__shfl((long long)plen, j, 64), lane);
+            if (lane == j) sum += el;
+        }
+    }
+    for (u64 todo = __ballot(wide); todo; todo &= todo - 1) {  // the wave's long rows, one after another
+        const int j = __ffsll((unsigned long long)todo) - 1;
+        const u64 vj = (u64)__shfl((long long)v, j, 64), ej = (u64)__shfl((long long)end, j, 64);
+        bool bad_j = false;
+        const u64 tot = mr_wave_row<false>(p, vj, ej, lane, 0, &bad_j);
+        bad = bad || bad_j;
+        if (lane == j) sum = tot;
+    }
+    if (r <= p.n) p.off[r] = have ? sum + 1u : 0u;  // (one more byte per row: its '\n'; the scan puts the total into off[n])
+    if (bad) atomicOr(&p.totals[2], 1ull);
+}
+__global__ __launch_bounds__(QT) void k_mr_tile_sums(MrView p) { tile_sums(arr_raw(p.off), p.n + 1u, p.tiles); }
+__global__ __launch_bounds__(QT) void k_mr_tile_apply(MrView p) { tile_apply(arr_raw(p.off), arr_raw(p.off), p.n + 1u, p.tiles); }
+__global__ __launch_bounds__(256, 4) void k_mr_write(MrView p) {
+    const u32 r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (r >= p.n) return;  // wave-uniform
+    u64 v, end;
+    mr_row_range(p, r, &v, &end);
+    const u64 at = p.off[r];
+    if (lane == 0) {
+        if (r) p.text[at - 1] = '\n';
+        p.out_off[r] = at;
+        if (r + 1 == p.n) p.out_off[p.n] = p.off[p.n];
+    }
+    bool bad = false;  // (the measure has reported it)
+    (void)mr_wave_row<true>(p, v, end, lane, at, &bad);
+}
+
+// ---- the key flags by tape index, without the parser's: kf[i >> 1] of the string entry at tape word i = the flag k_ms_keys
+// recovered for its ordinal.  COUNT: cnt[tile] = string entries of the tile (2048 words); then their exclusive prefix
+// (k_tw_scan_sums) and the scatter.  The anchor in front of a tile is searched backwards, 64 words at a time (word 0, a root,
+// is one).
+struct MrKeys {
+    Arr<const u64> tape;
+    u64 n;
+    unsigned long long *cnt;  // [tiles]
+    const u8 *keyflag;        // [string entries] by ordinal (k_ms_keys)
+    Arr<u8> kf;
+};
+template <bool EMIT>
+__global__ __launch_bounds__(TW_THREADS) void k_mr_keyflags(MrKeys p) {
+    __shared__ long long s_l[TW_THREADS / 64];
+    __shared__ unsigned long long s_s[TW_THREADS / 64];
+    __shared__ long long s_carry;
+    const int tid = threadIdx.x;
+    const u64 tb = (u64)blockIdx.x * TW_TILE, base = tb + (u64)tid * TW_ITEMS;
+    u64 w[TW_ITEMS];
+    long long last = -1;
+#pragma unroll
+    for (int k = 0; k < TW_ITEMS; k++) {
+        w[k] = base + k < p.n ? p.tape[base + k] : 0;
+        if (base + k < p.n && !two_word_tag(w[k])) last = (long long)(base + k);
+    }
+    if (tid < 64) {
+        long long c = -1;  // (the first tile: nothing in front of it)
+        for (u64 hi = tb; hi > 0; hi = hi > 64 ? hi - 64 : 0) {
+            const bool have = hi >= 1 + (u64)tid;
+            const u64 b = __ballot(have && !two_word_tag(p.tape[have ? hi - 1 - (u64)tid : 0]));
+            if (b) {
+                c = (long long)(hi - 1 - (u64)ctz64(b));
+                break;
+            }
+        }
+        if (tid == 0) s_carry = c;
+    }
+    long long anchor = block_excl_max(last, s_l, tid);  // (its barriers publish s_carry)
+    anchor = anchor > s_carry ? anchor : s_carry;
+    u32 nstr = 0, strs = 0;
+#pragma unroll
+    for (int k = 0; k < TW_ITEMS; k++) {
+        const u64 i = base + k;
+        if (i >= p.n) continue;
+        const bool raw = anchor >= 0 && ((((long long)i - anchor - 1) & 1) != 0);
+        if (!two_word_tag(w[k])) anchor = (long long)i;
+        if (!raw && (u32)(w[k] >> 56) == '"') {
+            nstr++;
+            strs |= 1u << k;
+        }
+    }
+    unsigned long long tot = 0;
+    const unsigned long long ex = block_excl_sum(nstr, s_s, tid, &tot);
+    if (!EMIT) {
+        if (tid == 0) p.cnt[blockIdx.x] = tot;
+        return;
+    }
+    u64 o = p.cnt[blockIdx.x] + ex;
+#pragma unroll
+    for (int k = 0; k < TW_ITEMS; k++)
+        if ((strs >> k) & 1u) p.kf[(base + k) >> 1] = p.keyflag[o++];
+}
 }  // namespace
 
 // debug build (-DSJ_DEBUG_BOUNDS): an out-of-bounds string of a MarshalJSON kernel fails the call (this translation unit's record)
@@ -1098,6 +1425,134 @@ int sjhip_fetch_marshaled(sjhip_ctx *ctx, uint8_t *dst) {
     HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
     if (ctx->res.marshaled_len() && dst)
         HIPCHK(hipMemcpyAsync(dst, ctx->d_qtape.p, ctx->res.marshaled_len(), hipMemcpyDeviceToHost, ctx->stream), "D2H JSON text");
+    HIPCHK(hipStreamSynchronize(ctx->stream), "fetch sync");
+    return marshal_bounds_check(ctx);  // (debug build: the writing pass has finished here)
+}
+
+// ---- marshal rows ------------------------------------------------------------------------------------------------------------------
+// sjhip_marshal_rows writes the text of the rows of the selection in force as the Marshaled tenant of the shared arenas, in
+// sjhip_filter_rows' order: the checks (which touch nothing), the claim, the work arrays in d_q, the key flags if the parser left
+// none, measure and scan, the total, the text arena -- the text, and behind it (256-byte aligned) the n + 1 row offsets --, the
+// writing pass, the publish.  It reads the selection and leaves it, and every other product, as they are.
+static size_t mr_offsets_at(size_t text_len) { return (text_len + 255) / 256 * 256; }
+
+int sjhip_marshal_rows(sjhip_ctx *ctx, uint64_t *n_rows, size_t *text_len) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!ctx->res.whole()) return no_whole_result(ctx, "sjhip_marshal_rows", "sjhip_marshal_rows follows");
+    if (!ctx->res.rows.exists()) {
+        ctx_set_error(ctx, "no row selection on the device (sjhip_marshal_rows follows sjhip_select_rows or sjhip_where_path)");
+        return SJHIP_ERR_ARG;
+    }
+    if (ctx->p_len >= (1ull << 32) && !(ctx->p_flags & SJHIP_FLAG_COPY_STRINGS)) {  // (sjhip_marshal_json's rule)
+        ctx_set_error(ctx, "sjhip_marshal_rows: a document of 4 GiB or more parsed without SJHIP_FLAG_COPY_STRINGS (message offsets beyond 32 bits)");
+        return SJHIP_ERR_TOOBIG;
+    }
+    const ResultState::Rows z = ctx->res.rows.sizes();
+    if (z.rows >= 0xffffffffull) {
+        ctx_set_error(ctx, "sjhip_marshal_rows: %llu rows (at most 2^32 - 2)", (unsigned long long)z.rows);
+        return SJHIP_ERR_TOOBIG;
+    }
+    const u32 n = (u32)z.rows;
+    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    ctx->res.claim_shared();
+    if (n == 0) {  // no rows: no text, offsets[0] = 0 (the fetch writes it)
+        if (n_rows) *n_rows = 0;
+        if (text_len) *text_len = 0;
+        return published(ctx, ctx->res.publish_marshaled_rows(0, 0));
+    }
+    RowsOut ro;
+    (void)rows_layout(Carve(ctx->d_rows.p), z.records, z.rows, &ro);
+    const bool own_flags = !ctx->res.key_flags();
+    MrView p{};
+    MrKeys mk{};
+    KeyView kv{};
+    kv.kind = ctx->p_kind;
+    kv.n = (u32)ctx->p_n;
+    kv.tiles = (kv.n + 4095u) / 4096u;
+    const u32 tiles = (u32)(((u64)n + 1 + QTILE - 1) / QTILE), tw_tiles = (u32)((ctx->tape_len + TW_TILE - 1) / TW_TILE);
+    const size_t kf_len = ctx->tape_len / 2 + 1;
+    auto layout = [&](Carve c) {
+        p.totals = c.take<unsigned long long>(32);
+        p.off = SJ_ARR(c.take<u64>((size_t)n + 1), (size_t)n + 1, A_MROWS_OFF);
+        p.tiles = c.take<unsigned long long>(tiles);
+        if (own_flags) {
+            kv.cnt = c.take<unsigned long long>(kv.tiles);
+            kv.keyflag = c.take<u8>(kv.n);
+            mk.cnt = c.take<unsigned long long>(tw_tiles);
+            mk.kf = SJ_ARR(c.take<u8>(kf_len), kf_len, A_MROWS_KF);
+        }
+        return c.used;
+    };
+    int rc = arena_reserve(ctx, ctx->d_q, layout(Carve()));
+    if (rc) return rc;
+    (void)layout(Carve(ctx->d_q.p));
+    p.tape = SJ_ARR((const u64 *)ctx->d_tape.p, ctx->tape_len, A_TAPE);
+    p.rows = SJ_ARR((const u64 *)ro.index, z.rows, A_ROWS);
+    p.n = n;
+    p.strings = (const u8 *)ctx->d_strings.p;
+    p.msg = (const u8 *)ctx->p_msg;
+    p.strings_len = ctx->strings_len;
+    p.msg_len = ctx->p_msg ? ctx->p_len : 0;
+    p.strings_end = p.strings + ctx->strings_len;
+    p.msg_end = p.msg ? p.msg + ctx->p_len : nullptr;
+    unsigned long long *const none = nullptr;
+    HIPCHK(hipMemsetAsync(p.totals, 0, 256, ctx->stream), "marshal rows memset");
+    if (own_flags) {  // the flags by string ordinal from the token array, then by tape index (d_keyflag is not written)
+        mk.tape = p.tape;
+        mk.n = ctx->tape_len;
+        mk.keyflag = kv.keyflag;
+        hipLaunchKernelGGL(k_ms_keys<false>, dim3(kv.tiles), dim3(256), 0, ctx->stream, kv);
+        hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, kv.cnt, none, none, kv.tiles, none);
+        hipLaunchKernelGGL(k_ms_keys<true>, dim3(kv.tiles), dim3(256), 0, ctx->stream, kv);
+        hipLaunchKernelGGL(k_mr_keyflags<false>, dim3(tw_tiles), dim3(TW_THREADS), 0, ctx->stream, mk);
+        hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, mk.cnt, none, none, tw_tiles, none);
+        hipLaunchKernelGGL(k_mr_keyflags<true>, dim3(tw_tiles), dim3(TW_THREADS), 0, ctx->stream, mk);
+        p.kf = mk.kf;
+    } else {
+        p.kf = SJ_ARR((const u8 *)ctx->d_keyflag.p, kf_len, A_KEYFLAG);
+    }
+    hipLaunchKernelGGL(k_mr_measure, dim3(n / 256 + 1), dim3(256), 0, ctx->stream, p);  // (row n as well: off[n])
+    hipLaunchKernelGGL(k_mr_tile_sums, dim3(tiles), dim3(QT), 0, ctx->stream, p);
+    hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, p.tiles, none, none, tiles, p.totals);
+    hipLaunchKernelGGL(k_mr_tile_apply, dim3(tiles), dim3(QT), 0, ctx->stream, p);
+    HIPCHK(hipGetLastError(), "marshal rows launch");
+    unsigned long long *h = (unsigned long long *)(ctx->h_scratch + 512);
+    HIPCHK(hipMemcpyAsync(h, p.totals, 24, hipMemcpyDeviceToHost, ctx->stream), "D2H marshal rows totals");
+    HIPCHK(hipStreamSynchronize(ctx->stream), "marshal rows sync");
+    if (h[2] & 1ull) {
+        ctx_set_error(ctx, "INF or NaN number found");  // the reference's error (parsed_json.go:1252)
+        return SJHIP_ERR_ARG;
+    }
+    rc = marshal_bounds_check(ctx);
+    if (rc) return rc;
+    const size_t len = (size_t)h[0] - 1;  // (every row counted its '\n'; none behind the last)
+    rc = arena_reserve(ctx, ctx->d_qtape, mr_offsets_at(len) + ((size_t)n + 1) * 8 + 64);
+    if (rc) return rc;
+    p.text = SJ_ARR((u8 *)ctx->d_qtape.p, len, A_MROWS_TEXT);
+    p.out_off = SJ_ARR((u64 *)((char *)ctx->d_qtape.p + mr_offsets_at(len)), (size_t)n + 1, A_MROWS_OUT_OFF);
+    hipLaunchKernelGGL(k_mr_write, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, p);
+    HIPCHK(hipGetLastError(), "marshal rows write launch");
+    if (n_rows) *n_rows = n;
+    if (text_len) *text_len = len;
+    return published(ctx, ctx->res.publish_marshaled_rows(len, n));
+}
+
+int sjhip_fetch_marshaled_rows(sjhip_ctx *ctx, uint64_t *offsets, uint8_t *text) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!ctx->res.marshaled_by_rows()) {
+        ctx_set_error(ctx, "no marshaled rows on the device (sjhip_fetch_marshaled_rows follows sjhip_marshal_rows; the text of sjhip_marshal_json has no rows)");
+        return SJHIP_ERR_ARG;
+    }
+    const size_t len = ctx->res.marshaled_len(), n = ctx->res.marshaled_rows();
+    if (n == 0) {
+        if (offsets) offsets[0] = 0;
+        return SJHIP_OK;
+    }
+    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    if (text && len) HIPCHK(hipMemcpyAsync(text, ctx->d_qtape.p, len, hipMemcpyDeviceToHost, ctx->stream), "D2H row text");
+    if (offsets)
+        HIPCHK(hipMemcpyAsync(offsets, (const char *)ctx->d_qtape.p + mr_offsets_at(len), (n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream),
+               "D2H row offsets");
     HIPCHK(hipStreamSynchronize(ctx->stream), "fetch sync");
     return marshal_bounds_check(ctx);  // (debug build: the writing pass has finished here)
 }

@@ -264,8 +264,6 @@ __global__ __launch_bounds__(256) void k_q_mark(QView q, QPath key, QRec o) {
 // string of any later record" is a minimum over the records behind it.  Tiles of 1024 records (256 threads x 4
 // consecutive records), tile sums scanned by one block (sj_tapewalk.h), then applied: sums -> scans -> apply (word
 // prefixes, string lengths and their tile sums) -> scan -> apply (string prefixes).
-static constexpr int QT = TW_THREADS, QI = 4, QTILE = QT * QI;
-static_assert(QT == 256, "block_excl_sum / block_excl_max of sj_tapewalk.h scan the four waves of a 256-thread block");
 struct QTiles {
     unsigned long long *tw;  // [tiles] tape words of the tile's matching records -> their exclusive prefix
     unsigned long long *tb;  // [tiles] Strings.B bytes of the tile's matching records -> their exclusive prefix
@@ -294,41 +292,6 @@ __device__ __forceinline__ u32 q_block_excl_suffix_min(u32 v, u32 *s_w, int tid)
     __syncthreads();
     return ex < after ? ex : after;
 }
-// the thread's QI consecutive elements of the tile (16 or 32 bytes per thread); -> their sum
-template <typename T>
-__device__ __forceinline__ unsigned long long q_load4(const T *p, u32 n, T fill, T (&v)[QI]) {
-    const u32 base = blockIdx.x * QTILE + threadIdx.x * QI;
-    unsigned long long sum = 0;
-#pragma unroll
-    for (int k = 0; k < QI; k++) {
-        v[k] = base + k < n ? p[base + k] : fill;
-        sum += v[k];
-    }
-    return sum;
-}
-// The two tile steps of an exclusive prefix over a[0 .. n), around the one-block scan of the tile sums (k_tw_scan_sums):
-// sums[tile] := the sum of the tile's elements;  dst[i] := sums[tile] (scanned) + the elements of the tile in front of i.
-template <typename T>
-__device__ __forceinline__ void tile_sums(const T *a, u32 n, unsigned long long *sums) {
-    __shared__ unsigned long long s_w[QT / 64];
-    T v[QI];
-    unsigned long long tot = 0;
-    (void)block_excl_sum(q_load4(a, n, (T)0, v), s_w, (int)threadIdx.x, &tot);
-    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
-}
-template <typename T>
-__device__ __forceinline__ void tile_apply(const T *a, T *dst, u32 n, const unsigned long long *sums) {
-    __shared__ unsigned long long s_w[QT / 64];
-    const u32 base = blockIdx.x * QTILE + threadIdx.x * QI;
-    T v[QI];
-    unsigned long long pre = block_excl_sum(q_load4(a, n, (T)0, v), s_w, (int)threadIdx.x, nullptr) + sums[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < QI; k++) {
-        if (base + k < n) dst[base + k] = (T)pre;
-        pre += v[k];
-    }
-}
-
 // tile sums of words and flags, and the tile's first string (mirrored: QTiles::tf)
 __global__ __launch_bounds__(QT) void k_q_tile_sums(QRec o, u32 n, QTiles T) {
     __shared__ long long s_l[QT / 64];
@@ -1327,13 +1290,6 @@ static int check_key_value(sjhip_ctx *ctx, const uint8_t *key, size_t klen, cons
 // view of the result held by `part` (ctx itself, or one shard context of ctx's sharded result) with the key and the value of a
 // query (checked by the caller: check_key_value); errors are left in ctx.  on_rows: the query runs on the rows of ctx's row
 // selection, if it has one (the filter and countWhere stay on records).
-struct RowsOut { u64 *off, *index; u8 *status; };
-static size_t rows_layout(Carve c, size_t n, size_t rows, RowsOut *o) {  // the selection of a part in its d_rows
-    o->off = c.take<u64>(n + 1);
-    o->status = c.take<u8>(n);
-    o->index = c.take<u64>(rows);
-    return c.used;
-}
 static bool selected(const sjhip_ctx *ctx, bool on_rows) { return on_rows && ctx->res.rows.exists(); }
 // the rows of this part: what a path query of ctx runs over -- the part's rows of the selection, or its records
 static uint32_t part_rows(const sjhip_ctx *ctx, const sjhip_ctx *part, bool on_rows) {

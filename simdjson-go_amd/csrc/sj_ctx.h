@@ -112,6 +112,15 @@ struct Carve {
         return p;
     }
 };
+// the row selection of a part in its d_rows (query.hip writes it; marshal.hip reads the row index): row offsets over the n records
+// the selection ran over, their statuses, the tape index of every row's value
+struct RowsOut { uint64_t *off, *index; uint8_t *status; };
+inline size_t rows_layout(Carve c, size_t n, size_t rows, RowsOut *o) {
+    o->off = c.take<uint64_t>(n + 1);
+    o->status = c.take<uint8_t>(n);
+    o->index = c.take<uint64_t>(rows);
+    return c.used;
+}
 int parse_packed(sjhip_ctx *ctx, size_t len, uint32_t flags, uint8_t last_byte, int have_last, size_t *tape_len,
                  size_t *strings_len);  // parse_api.hip
 int parse_nd_big(sjhip_ctx *ctx, const uint8_t *msg, size_t len, uint32_t flags, bool d_resident, size_t shard_bytes,

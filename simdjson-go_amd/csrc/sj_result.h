@@ -91,6 +91,15 @@ public:
         if (!resident() && !sharded()) return false;
         tenant_ = Tenant::Marshaled;
         marshaled_len_ = text_len;
+        marshaled_by_rows_ = false;
+        return true;
+    }
+    bool publish_marshaled_rows(size_t text_len, size_t rows) {  // the text of the selected rows: row offsets lie behind it
+        if (!whole()) return false;
+        tenant_ = Tenant::Marshaled;
+        marshaled_len_ = text_len;
+        marshaled_by_rows_ = true;
+        marshaled_rows_ = rows;
         return true;
     }
     // The independent products: a call gives up the last one before anything can fail (begin) and publishes on success, on a
@@ -138,6 +147,8 @@ public:
     const Filtered &filtered_sizes() const { return filtered_; }
     const Serialized &serialized_sizes() const { return serialized_; }
     size_t marshaled_len() const { return marshaled_len_; }
+    bool marshaled_by_rows() const { return marshaled() && marshaled_by_rows_; }  // sjhip_marshal_rows' text, not sjhip_marshal_json's
+    size_t marshaled_rows() const { return marshaled_rows_; }
 
 private:
     enum class Parse : uint8_t { None, Pending, Whole, Shard, Sharded };
@@ -147,7 +158,8 @@ private:
     uint64_t tape_base_ = 0, strings_base_ = 0, msg_base_ = 0;
     Filtered filtered_;
     Serialized serialized_;
-    size_t marshaled_len_ = 0;
+    size_t marshaled_len_ = 0, marshaled_rows_ = 0;
+    bool marshaled_by_rows_ = false;
 };
 
 }  // namespace sj

@@ -187,4 +187,43 @@ __global__ __launch_bounds__(1024) void k_tw_scan_sums(unsigned long long *a0, u
     }
 }
 
+// ---- exclusive prefixes over one value per record / row (query.hip, marshal.hip): tiles of 1024 elements (256 threads x 4
+// consecutive ones), tile sums scanned by one block (k_tw_scan_sums), then applied: sums -> scan -> apply
+static constexpr int QT = TW_THREADS, QI = 4, QTILE = QT * QI;
+static_assert(QT == 256, "block_excl_sum / block_excl_max of sj_tapewalk.h scan the four waves of a 256-thread block");
+// the thread's QI consecutive elements of the tile (16 or 32 bytes per thread); -> their sum
+template <typename T>
+__device__ __forceinline__ unsigned long long q_load4(const T *p, u32 n, T fill, T (&v)[QI]) {
+    const u32 base = blockIdx.x * QTILE + threadIdx.x * QI;
+    unsigned long long sum = 0;
+#pragma unroll
+    for (int k = 0; k < QI; k++) {
+        v[k] = base + k < n ? p[base + k] : fill;
+        sum += v[k];
+    }
+    return sum;
+}
+// The two tile steps of an exclusive prefix over a[0 .. n), around the one-block scan of the tile sums (k_tw_scan_sums):
+// sums[tile] := the sum of the tile's elements;  dst[i] := sums[tile] (scanned) + the elements of the tile in front of i.
+template <typename T>
+__device__ __forceinline__ void tile_sums(const T *a, u32 n, unsigned long long *sums) {
+    __shared__ unsigned long long s_w[QT / 64];
+    T v[QI];
+    unsigned long long tot = 0;
+    (void)block_excl_sum(q_load4(a, n, (T)0, v), s_w, (int)threadIdx.x, &tot);
+    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
+}
+template <typename T>
+__device__ __forceinline__ void tile_apply(const T *a, T *dst, u32 n, const unsigned long long *sums) {
+    __shared__ unsigned long long s_w[QT / 64];
+    const u32 base = blockIdx.x * QTILE + threadIdx.x * QI;
+    T v[QI];
+    unsigned long long pre = block_excl_sum(q_load4(a, n, (T)0, v), s_w, (int)threadIdx.x, nullptr) + sums[blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < QI; k++) {
+        if (base + k < n) dst[base + k] = (T)pre;
+        pre += v[k];
+    }
+}
+
 }  // namespace

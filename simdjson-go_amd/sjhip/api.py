@@ -504,6 +504,21 @@ class Context:
         self._check(L.sjhip_fetch_marshaled(self._h, out.ctypes.data))
         return out.tobytes()
 
+    def marshal_rows(self, fetch=True, offsets=False):
+        """The rows of the selection in force (select_rows / where_path) as NDJSON text built on the device: the compact JSON text
+        of every row, in selection order, joined by newlines (none behind the last); a scalar row is its own text.
+        -> (n_rows, text) or, with offsets=True, (n_rows, text, offsets): a uint64 array of n_rows + 1 entries, row i is
+        text[offsets[i]:offsets[i + 1] - 1]; with fetch=False (n_rows, text_len) and the text stays on the device"""
+        L = _lib.lib()
+        n, tl = C.c_uint64(0), C.c_size_t(0)
+        self._check(L.sjhip_marshal_rows(self._h, C.byref(n), C.byref(tl)))
+        if not fetch:
+            return n.value, tl.value
+        out = np.empty(tl.value, dtype=np.uint8)
+        off = np.empty(n.value + 1, dtype=np.uint64) if offsets else None
+        self._check(L.sjhip_fetch_marshaled_rows(self._h, off.ctypes.data if offsets else None, out.ctypes.data))
+        return (n.value, out.tobytes(), off) if offsets else (n.value, out.tobytes())
+
     def fetch(self, tape_len, strings_len):
         tape = np.empty(tape_len, dtype=np.uint64)
         strings = np.empty(strings_len, dtype=np.uint8)
