@@ -785,12 +785,7 @@ __global__ __launch_bounds__(TW_THREADS, WPE) void k_ms_tile(MsView p) {
                 x = str_load8(sp, q, len, lim);
                 sz = esc_size8(x, valid);
             }
-            u32 incl = sz;
-#pragma unroll
-            for (int sft = 1; sft < 64; sft <<= 1) {
-                const u32 up = (u32)__shfl_up((int)incl, sft, 64);
-                if (lane >= sft) incl += up;
-            }
+            const u32 incl = wave_incl_sum(sz, lane);
             if (valid) {
                 if (staged && word_is_clean(x)) {  // eight bytes, two aligned slots
                     const u32 at = (u32)(o - s_text) + (incl - sz), sh = 8u * (at & 7u);
@@ -802,7 +797,7 @@ __global__ __launch_bounds__(TW_THREADS, WPE) void k_ms_tile(MsView p) {
                     write_esc8(o + (incl - sz), x, valid);
                 }
             }
-            o += (u32)__shfl((int)incl, 63, 64);
+            o += wave_bcast(incl, 63);
         }
         if (lane == 0) {
             *o++ = '"';
@@ -875,8 +870,11 @@ static void launch_ms_tile(const MsView &p, hipStream_t st) {
 // neither -- so the work is laid out by row, in sjhip_filter_rows' three steps:
 //   k_mr_measure       one lane per row: the text bytes of the row, as a 64-bit sum.  A row of up to MR_SHORT words is walked by its
 //                      lane, entry by entry; every longer row of the wave's 64 by the whole wave in turn, 64 words per step
-//                      (mr_wave_row: tags told from raw words by the parity rule of sj_tapewalk.h, anchored at the row's opening
-//                      word).  The escaped length of a string of MS_LONG bytes or more is measured by the whole wave in both paths.
+//                      (mr_wave_row: tags told from raw words by the span walk of sj_tapewalk.h, tw_walk_span, which a scalar row
+//                      needs as it is).  The escaped length of a string of MS_LONG bytes or more is measured by the whole wave in
+//                      both paths.  The "one after another" loops of mr_wave_row and k_mr_measure are written by hand, not with
+//                      wave_each: with it k_mr_write kept more scalar state in vector lanes (14 v_writelane against 4) and all
+//                      1 M rows measured 0.5 - 1.5 % slower (profiles/r17_row_walks_time.txt).
 //   scan               off[r] = bytes of row r + 1 (its '\n'; off[n] = 0) -> exclusive prefix over n + 1 elements (tile sums ->
 //                      k_tw_scan_sums -> apply): off[r] = first byte of row r, off[n] = text length + 1 -- the row offsets
 //                      sjhip_fetch_marshaled_rows hands out, and the total the host sizes the text by
@@ -940,9 +938,7 @@ __device__ __forceinline__ u64 mr_esc_len_wave(const MrView &p, bool inbuf, u64 
     const u8 *lim = inbuf ? p.strings_end : p.msg_end;
     u64 el = 0;
     for (u64 q = (u64)lane * 8; q < len; q += 512) el += esc_size8(str_load8(sp, q, len, lim), (u32)(len - q < 8 ? len - q : 8));
-#pragma unroll
-    for (int sft = 32; sft >= 1; sft >>= 1) el += (u64)__shfl_xor((long long)el, sft, 64);
-    return el;
+    return wave_sum(el);
 }
 // the el escaped bytes of a string into text[at ..), by the whole wave: 512 bytes of the string per step
 __device__ __forceinline__ void mr_write_long(const MrView &p, bool inbuf, u64 off, u64 len, int lane, u64 at, u64 el) {
@@ -958,14 +954,9 @@ __device__ __forceinline__ void mr_write_long(const MrView &p, bool inbuf, u64 o
             x = str_load8(sp, q, len, lim);
             sz = esc_size8(x, valid);
         }
-        u32 incl = sz;
-#pragma unroll
-        for (int sft = 1; sft < 64; sft <<= 1) {
-            const u32 up = (u32)__shfl_up((int)incl, sft, 64);
-            if (lane >= sft) incl += up;
-        }
+        const u32 incl = wave_incl_sum(sz, lane);
         if (valid) write_esc8(o + (incl - sz), x, valid);
-        o += (u32)__shfl((int)incl, 63, 64);
+        o += wave_bcast(incl, 63);
     }
 }
 // The row [v, end) by the whole wave, 64 words per step (arguments and result wave-uniform): -> its text bytes; EMIT: written to
@@ -973,17 +964,9 @@ __device__ __forceinline__ void mr_write_long(const MrView &p, bool inbuf, u64 o
 template <bool EMIT>
 __device__ __forceinline__ u64 mr_wave_row(const MrView &p, u64 v, u64 end, int lane, u64 at, bool *bad) {
     const u64 nwords = end - v;
-    long long p_prev = -1;  // last anchor below the group, relative to the row (none: word 0, a tag, is the first)
     u64 total = 0;
-    for (u64 g = 0; g < nwords; g += 64) {
-        const u64 i = g + (u64)lane;
-        const bool in = i < nwords;
-        const u64 w = in ? p.tape[v + i] : 0;
-        const u64 zm = ~__ballot(in && two_word_tag(w)) & __ballot(in);  // the anchors of the group
-        const u64 zeros_below = zm & (lane ? (~0ull >> (64 - lane)) : 0ull);
-        const long long pa = zeros_below ? (long long)g + (63 - __builtin_clzll(zeros_below)) : p_prev;
-        // (the row's opening word is a tag: the word in front of the row counts as an anchor, pa = -1)
-        const bool raw = (((long long)i - pa - 1) & 1) != 0;
+    // (the row's value is the first word of an entry, as the span walk asks: a scalar row's second word is told raw)
+    tw_walk_span(p.tape, v, nwords, lane, [&](u64 i, u64 w, bool in, bool raw) {
         const bool ent = in && !raw;
         const u32 t = (u32)(w >> 56);
         const bool two = ent && two_word_tag(w);
@@ -1006,12 +989,7 @@ __device__ __forceinline__ u64 mr_wave_row(const MrView &p, u64 v, u64 end, int 
                                            (u64)__shfl((long long)w1, j, 64), lane);
             if (lane == j) sz += el;
         }
-        u64 incl = sz;
-#pragma unroll
-        for (int sft = 1; sft < 64; sft <<= 1) {
-            const u64 up = (u64)__shfl_up((long long)incl, sft, 64);
-            if (lane >= sft) incl += up;
-        }
+        const u64 incl = wave_incl_sum(sz, lane);
         if (EMIT) {
             const u64 mine = at + total + incl - sz;
             if (ent && sz) {
@@ -1048,9 +1026,8 @@ __device__ __forceinline__ u64 mr_wave_row(const MrView &p, u64 v, u64 end, int 
                               at_j, el_j);
             }
         }
-        total += (u64)__shfl((long long)incl, 63, 64);
-        if (zm) p_prev = (long long)g + (63 - __builtin_clzll(zm));
-    }
+        total += wave_bcast(incl, 63);
+    });
     return total;
 }
 // where row r lies: [*v, *end); (a scalar: its one or two words)

@@ -354,42 +354,36 @@ __global__ __launch_bounds__(QT) void k_q_tile_apply1(QRec o, u32 n, QTiles T, u
 __global__ __launch_bounds__(QT) void k_q_tile_apply2(QRec o, u32 n, QTiles T) { tile_apply(o.s_len, o.s_pre, n, T.tb); }
 
 // ---- pass 3: one wave per record: its tape words with every stored index rebased, then its strings -------------------
-// Which words are tags is decided by the parity rule stated at the top of sj_tapewalk.h (the record's opening root is an
-// anchor), which a wave evaluates for 64 words at a time from one ballot.
-__global__ __launch_bounds__(256) void k_q_copy(QView q, QRec o, u64 *out_tape, u8 *out_strings) {
-    const u32 r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (r > q.R || !o.flag[r]) return;  // wave-uniform
-    const u32 a = rec_open(q, r), c = rec_close(q, r);
-    const u32 na = o.words[r];  // new index of the opening root
-    const u32 nwords = c - a + 1u;
-    const long long dw = (long long)na - (long long)a;
-    const u32 sb = o.first_str[r], slen = o.s_len[r], ns = o.s_pre[r];
-    const u64 ds = (u64)((long long)ns - (long long)sb);  // only used when the record has a string
-    long long p_prev = -1;  // last anchor below the group, relative to the record (none: word 0 is the first)
-    for (u32 g = 0; g < nwords; g += 64) {
-        const u32 i = g + (u32)lane;
-        const bool in = i < nwords;
-        const u64 w = in ? q.tape[a + i] : 0;
-        const u32 t = (u32)(w >> 56);
-        const u64 inmask = __ballot(in);
-        const u64 zm = ~__ballot(in && two_word_tag(w)) & inmask;  // the anchors of the group
-        const u64 zeros_below = zm & (lane ? (~0ull >> (64 - lane)) : 0ull);
-        const long long p = zeros_below ? (long long)g + (63 - __builtin_clzll(zeros_below)) : p_prev;
-        const bool raw = p >= 0 && ((((long long)i - p - 1) & 1) != 0);
-        if (in) {
-            u64 v = w;
-            if (!raw) {
-                if (i == 0) v = ((u64)'r' << 56) | (u64)(na + nwords);  // the next record's open root, or the tape length
-                else if (i == nwords - 1) v = ((u64)'r' << 56) | (u64)na;  // its own open root
-                else if (t == '{' || t == '[' || t == '}' || t == ']') v = (w & ~TW_PAYLOAD) | (u64)((long long)(w & TW_PAYLOAD) + dw);
-                else if (t == '"') v = w + ds;
-            }
-            out_tape[na + i] = v;
-        }
-        if (zm) p_prev = (long long)g + (63 - __builtin_clzll(zm));
+// The rebasing copy of both filters (k_q_copy, k_q_frows_copy): a stretch of tape becomes a self-contained record.  By one wave
+// (all arguments wave-uniform): the nwords words of the value at v -- the first word of an entry, as tw_walk_span asks -- go to
+// out_tape[na + 1 ..) between two synthesised roots at na and na + nwords + 1; bracket payloads move by (new index - old index),
+// string payloads by (new offset - old offset), raw words (told by the span walk of sj_tapewalk.h) stay as they are.  Then the
+// slen bytes of Strings.B the value owns go from sb to ns, 64 at a time.
+__device__ __forceinline__ void wave_copy_record(const QView &q, u64 v, u64 nwords, u64 na, u32 sb, u32 slen, u32 ns, int lane,
+                                                 Arr<u64> out_tape, Arr<u8> out_strings) {
+    const long long dw = (long long)(na + 1) - (long long)v;
+    const u64 ds = (u64)((long long)ns - (long long)sb);  // only used when the value has a string
+    if (lane == 0) {
+        out_tape[na] = ((u64)'r' << 56) | (na + nwords + 2);  // behind its closing root: the next record, or the tape length
+        out_tape[na + nwords + 1] = ((u64)'r' << 56) | na;
     }
-    for (u32 k = (u32)lane; k < slen; k += 64) out_strings[ns + k] = q.strings[sb + k];
+    tw_walk_span(q.tape, v, nwords, lane, [&](u64 i, u64 w, bool in, bool raw) {
+        if (!in) return;
+        const u32 t = (u32)(w >> 56);
+        u64 x = w;
+        if (!raw) {
+            if (t == '{' || t == '[' || t == '}' || t == ']') x = (w & ~TW_PAYLOAD) | (u64)((long long)(w & TW_PAYLOAD) + dw);
+            else if (t == '"') x = w + ds;
+        }
+        out_tape[na + 1 + i] = x;
+    });
+    for (u32 k = (u32)lane; k < slen; k += 64) out_strings[(u64)ns + k] = q.strings[(u64)sb + k];
+}
+__global__ __launch_bounds__(256) void k_q_copy(QView q, QRec o, Arr<u64> out_tape, Arr<u8> out_strings) {
+    const u32 r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r > q.R || !o.flag[r]) return;  // wave-uniform
+    const u64 a = rec_open(q, r), c = rec_close(q, r);
+    wave_copy_record(q, a + 1, c - a - 1, o.words[r], o.first_str[r], o.s_len[r], o.s_pre[r], threadIdx.x & 63, out_tape, out_strings);
 }
 
 // ---- the kernels of the path queries ------------------------------------------------------------------------------
@@ -500,6 +494,13 @@ static constexpr u64 COL_SHORT = 32;
 __device__ __forceinline__ void copy_bytes(u8 *dst, const u8 *src, u64 len, u64 first, u64 step) {
     for (u64 k = first; k < len; k += step) dst[k] = src[k];
 }
+// the wave's long strings, one after another: the `len` bytes of the string whose tag word is w, to data[o ..), for every lane with `wide`
+__device__ __forceinline__ void wave_copy_strings(const QView &q, Arr<u8> data, bool wide, u64 o, u64 len, u64 w, int lane) {
+    wave_each(wide, [&](int j) {
+        const u64 oj = wave_bcast(o, j), lj = wave_bcast(len, j);
+        copy_bytes(arr_at(data, oj, lj), str_bytes(q, wave_bcast(w, j), lj), lj, (u64)lane, 64);
+    });
+}
 __global__ __launch_bounds__(256) void k_q_col_gather(QView q, QCol c, u64 *out_off, u8 *out_status, Arr<u8> data) {
     const u32 r = blockIdx.x * 256 + threadIdx.x;
     const int lane = threadIdx.x & 63;
@@ -531,11 +532,7 @@ __global__ __launch_bounds__(256) void k_q_col_gather(QView q, QCol c, u64 *out_
             }
         }
     }
-    for (u64 todo = __ballot(wide); todo; todo &= todo - 1) {  // the wave's long strings, one after another
-        const int j = __ffsll((unsigned long long)todo) - 1;
-        const u64 oj = (u64)__shfl((long long)o, j, 64), lj = (u64)__shfl((long long)len, j, 64), wj = (u64)__shfl((long long)w, j, 64);
-        copy_bytes(arr_at(data, oj, lj), str_bytes(q, wj, lj), lj, (u64)lane, 64);
-    }
+    wave_copy_strings(q, data, wide, o, len, w, lane);
 }
 
 // ---- list columns: the ARRAY at a path of every record, converted (sjhip_extract_path_list / sjhip_extract_path_list_strings) ----
@@ -599,11 +596,6 @@ __device__ __forceinline__ int record_array(const QView &q, const QPath &pth, u3
     *close = (w & TW_PAYLOAD) - 1;
     return SJHIP_COL_OK;
 }
-__device__ __forceinline__ u64 wave_sum(u64 x) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) x += (u64)__shfl_xor((long long)x, s, 64);
-    return x;
-}
 // the strided conversion check of the array (v, close) by one lane (first = 0, step = 1) ...
 __device__ __forceinline__ int lane_list_measure(const QView &q, u64 v, u64 close, int kind, u64 *cnt, u64 *bytes) {
     u64 sum = 0;
@@ -656,6 +648,7 @@ __global__ __launch_bounds__(256) void k_q_list_measure(QView q, QPath pth, int 
             if (!wide) st = lane_list_measure(q, v, close, kind, &cnt, &bytes);
         }
     }
+    // (by hand, not wave_each: with it the skewed FLOAT case of tools/list_column_time.py measured 2 % slower, here and in the gather)
     for (u64 todo = __ballot(wide); todo; todo &= todo - 1) {  // the wave's long arrays, one after another
         const int j = __ffsll((unsigned long long)todo) - 1;
         const u64 vj = (u64)__shfl((long long)v, j, 64), cj = (u64)__shfl((long long)close, j, 64);
@@ -716,6 +709,7 @@ __global__ __launch_bounds__(256) void k_q_list_gather_num(QView q, QList c, int
                 values[o + k] = x;
             }
     }
+    // (by hand, not wave_each: with it the skewed FLOAT case of tools/list_column_time.py measured 2 % slower, here and in the measure)
     for (u64 todo = __ballot(wide); todo; todo &= todo - 1) {
         const int j = __ffsll((unsigned long long)todo) - 1;
         const u64 oj = (u64)__shfl((long long)o, j, 64), nj = (u64)__shfl((long long)cnt, j, 64), vj = (u64)__shfl((long long)v, j, 64);
@@ -785,42 +779,26 @@ __device__ __forceinline__ void list_gather_strings(const QView &q, const QList 
             k++;
             p += two_word_tag(w) ? 2 : 1;
         }
-        u64 todo = __ballot(pend);
-        if (!todo) break;
-        for (; todo; todo &= todo - 1) {
-            const int j = __ffsll((unsigned long long)todo) - 1;
-            const u64 oj = (u64)__shfl((long long)so, j, 64), lj = (u64)__shfl((long long)sl, j, 64), wj = (u64)__shfl((long long)sw, j, 64);
-            copy_bytes(arr_at(data, oj, lj), str_bytes(q, wj, lj), lj, (u64)lane, 64);
-        }
+        if (!__ballot(pend)) break;
+        wave_copy_strings(q, data, pend, so, sl, sw, lane);
     }
     if (CVT) return;
-    for (u64 todo = __ballot(wide); todo; todo &= todo - 1) {  // AsString: the wave's long arrays, one after another
-        const int j = __ffsll((unsigned long long)todo) - 1;
-        const u64 oj = (u64)__shfl((long long)o, j, 64), nj = (u64)__shfl((long long)cnt, j, 64), vj = (u64)__shfl((long long)v, j, 64);
-        u64 base = (u64)__shfl((long long)at0, j, 64);
+    wave_each(wide, [&](int j) {  // AsString: the wave's long arrays, one after another
+        const u64 oj = wave_bcast(o, j), nj = wave_bcast(cnt, j), vj = wave_bcast(v, j);
+        u64 base = wave_bcast(at0, j);
         for (u64 g = 0; g < nj; g += 64) {
             const u64 e = g + (u64)lane;
             const bool in = e < nj;
             const u64 w = in ? q.tape[vj + 1 + 2 * e] : 0, len = in ? q.tape[vj + 2 + 2 * e] : 0;
-            u64 incl = len;
-#pragma unroll
-            for (int s = 1; s < 64; s <<= 1) {
-                const u64 x = (u64)__shfl_up((long long)incl, s, 64);
-                if (lane >= s) incl += x;
-            }
-            const u64 mine = base + incl - len;
+            const u64 incl = wave_incl_sum(len, lane), mine = base + incl - len;
             if (in) {
                 soff[oj + e] = mine;
                 if (len && len <= COL_SHORT) copy_bytes(arr_at(data, mine, len), str_bytes(q, w, len), len, 0, 1);
             }
-            for (u64 big = __ballot(len > COL_SHORT); big; big &= big - 1) {
-                const int i = __ffsll((unsigned long long)big) - 1;
-                const u64 oi = (u64)__shfl((long long)mine, i, 64), li = (u64)__shfl((long long)len, i, 64), wi = (u64)__shfl((long long)w, i, 64);
-                copy_bytes(arr_at(data, oi, li), str_bytes(q, wi, li), li, (u64)lane, 64);
-            }
-            base += (u64)__shfl((long long)incl, 63, 64);
+            wave_copy_strings(q, data, len > COL_SHORT, mine, len, w, lane);
+            base += wave_bcast(incl, 63);
         }
-    }
+    });
 }
 __global__ __launch_bounds__(256) void k_q_list_gather_str(QView q, QList c, u64 *out_off, u8 *out_status, Arr<u64> soff, Arr<u8> data) {
     list_gather_strings<false>(q, c, out_off, out_status, soff, data);
@@ -1111,15 +1089,13 @@ __global__ __launch_bounds__(256) void k_q_where_offsets(QView q, QWhere w, u64 
 //   k_q_frows_measure     per row: its output words (0: a scalar), the Strings.B offset of its first string and the end of its
 //                         last one.  Rows do not tile the tape -- what lies between two rows belongs to neither -- so the last
 //                         string is found by classifying the row's own words: a row of up to FROWS_SHORT words by its lane, entry
-//                         by entry; every longer row of the wave's 64 by the whole wave in turn, 64 words per step, tags told
-//                         from raw words by the parity rule (sj_tapewalk.h; the row's opening word is a tag: the anchor) from one
-//                         ballot, the first and the last string of a step from another.  Emitted and skipped rows are counted
-//                         from the wave's ballots.
+//                         by entry; every longer row of the wave's 64 by the whole wave in turn (wave_each), 64 words per step,
+//                         tags told from raw words by the span walk of sj_tapewalk.h (tw_walk_span; the row's value is the first
+//                         word of an entry), the first and the last string of a step from one ballot.  Emitted and skipped rows
+//                         are counted from the wave's ballots.
 //   scan                  exclusive prefixes of the words and of the string bytes over the rows (the filter's tile pattern:
 //                         sums -> k_tw_scan_sums -> apply); both totals and both counts reach the host in one copy
-//   k_q_frows_copy        one wave per emitted row, the shape of k_q_copy: roots synthesised, bracket payloads moved by
-//                         (new index - old index), string payloads by (new offset - old offset), raw words untouched; then the
-//                         row's bytes, 64 at a time
+//   k_q_frows_copy        one wave per emitted row: wave_copy_record, the rebasing copy it shares with k_q_copy
 // A row owns Strings.B from its first string to the end of its last: strings lie in document order and a row is one stretch of the
 // document, so everything in between is a string of the row (keys and nested strings included).
 static constexpr u32 FROWS_SHORT = 128;  // words of a row its lane walks alone
@@ -1149,27 +1125,17 @@ __device__ __forceinline__ void lane_row_strings(const QView &q, u64 v, u64 end,
 }
 // ... and by the whole wave, 64 words per step (arguments and results wave-uniform)
 __device__ __forceinline__ void wave_row_strings(const QView &q, u64 v, u64 end, int lane, u32 *first, u32 *last_end) {
-    const u64 nwords = end - v;
-    long long p_prev = -1;  // last anchor below the group, relative to the row (none: word 0, a tag, is the first)
     u32 fs = NONE32, le = 0;
-    for (u64 g = 0; g < nwords; g += 64) {
-        const u64 i = g + (u64)lane;
-        const bool in = i < nwords;
-        const u64 w = in ? q.tape[v + i] : 0;
-        const u64 zm = ~__ballot(in && two_word_tag(w)) & __ballot(in);  // the anchors of the group
-        const u64 zeros_below = zm & (lane ? (~0ull >> (64 - lane)) : 0ull);
-        const long long p = zeros_below ? (long long)g + (63 - __builtin_clzll(zeros_below)) : p_prev;
-        const bool raw = p >= 0 && ((((long long)i - p - 1) & 1) != 0);
+    tw_walk_span(q.tape, v, end - v, lane, [&](u64 i, u64 w, bool in, bool raw) {
         const bool str = in && !raw && (w >> 56) == '"';
-        // (a string's length word may lie in the next group: its own lane reads it; it lies inside the row, a close follows it)
+        // (a string's length word may lie in the next step: its own lane reads it; it lies inside the row, a close follows it)
         const u32 mine = str ? str_offset(w) + (u32)q.tape[v + i + 1] : 0u;
         const u64 sm = __ballot(str);
         if (sm) {
-            if (fs == NONE32) fs = (u32)__shfl((int)str_offset(w), __ffsll((unsigned long long)sm) - 1, 64);
-            le = (u32)__shfl((int)mine, 63 - __builtin_clzll(sm), 64);
+            if (fs == NONE32) fs = wave_bcast(str_offset(w), __ffsll((unsigned long long)sm) - 1);
+            le = wave_bcast(mine, 63 - __builtin_clzll(sm));
         }
-        if (zm) p_prev = (long long)g + (63 - __builtin_clzll(zm));
-    }
+    });
     *first = fs;
     *last_end = le;
 }
@@ -1191,16 +1157,14 @@ __global__ __launch_bounds__(256) void k_q_frows_measure(QView q, QFRows o) {
             if (!wide) lane_row_strings(q, v, end, &first, &last_end);
         }
     }
-    for (u64 todo = __ballot(wide); todo; todo &= todo - 1) {  // the wave's long rows, one after another
-        const int j = __ffsll((unsigned long long)todo) - 1;
-        const u64 vj = (u64)__shfl((long long)v, j, 64), ej = (u64)__shfl((long long)end, j, 64);
+    wave_each(wide, [&](int j) {  // the wave's long rows, one after another
         u32 f_j, l_j;
-        wave_row_strings(q, vj, ej, lane, &f_j, &l_j);
+        wave_row_strings(q, wave_bcast(v, j), wave_bcast(end, j), lane, &f_j, &l_j);
         if (lane == j) {
             first = f_j;
             last_end = l_j;
         }
-    }
+    });
     if (have) {
         o.words[r] = box ? (u32)(end - v) + 2u : 0u;
         o.first_str[r] = first;
@@ -1219,41 +1183,12 @@ __global__ __launch_bounds__(QT) void k_q_frows_tile_apply(QFRows o, u32 n) {
 }
 __global__ __launch_bounds__(256) void k_q_frows_copy(QView q, QFRows o, Arr<u64> out_tape, Arr<u8> out_strings) {
     const u32 r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
     if (r >= q_rows(q)) return;  // wave-uniform, like the next one
     const u64 v = row_value(q, r), w0 = q.tape[v];
     const u32 t0 = (u32)(w0 >> 56);
     if (t0 != '{' && t0 != '[') return;
-    const u64 nwords = (w0 & TW_PAYLOAD) - v;  // the row's own words; its record: a root on either side
-    const u64 na = o.words[r];                 // new index of the opening root
-    const long long dw = (long long)(na + 1) - (long long)v;
-    const u32 sb = o.first_str[r], slen = o.s_len[r], ns = o.s_pre[r];
-    const u64 ds = (u64)((long long)ns - (long long)sb);  // only used when the row has a string
-    if (lane == 0) {
-        out_tape[na] = ((u64)'r' << 56) | (na + nwords + 2);  // behind its closing root: the next record, or the tape length
-        out_tape[na + nwords + 1] = ((u64)'r' << 56) | na;
-    }
-    long long p_prev = -1;  // last anchor below the group, relative to the row (none: word 0 is the first)
-    for (u64 g = 0; g < nwords; g += 64) {
-        const u64 i = g + (u64)lane;
-        const bool in = i < nwords;
-        const u64 w = in ? q.tape[v + i] : 0;
-        const u32 t = (u32)(w >> 56);
-        const u64 zm = ~__ballot(in && two_word_tag(w)) & __ballot(in);  // the anchors of the group
-        const u64 zeros_below = zm & (lane ? (~0ull >> (64 - lane)) : 0ull);
-        const long long p = zeros_below ? (long long)g + (63 - __builtin_clzll(zeros_below)) : p_prev;
-        const bool raw = p >= 0 && ((((long long)i - p - 1) & 1) != 0);
-        if (in) {
-            u64 x = w;
-            if (!raw) {
-                if (t == '{' || t == '[' || t == '}' || t == ']') x = (w & ~TW_PAYLOAD) | (u64)((long long)(w & TW_PAYLOAD) + dw);
-                else if (t == '"') x = w + ds;
-            }
-            out_tape[na + 1 + i] = x;
-        }
-        if (zm) p_prev = (long long)g + (63 - __builtin_clzll(zm));
-    }
-    for (u32 k = (u32)lane; k < slen; k += 64) out_strings[(u64)ns + k] = q.strings[(u64)sb + k];
+    // the row's own words, up to its matching close
+    wave_copy_record(q, v, (w0 & TW_PAYLOAD) - v, o.words[r], o.first_str[r], o.s_len[r], o.s_pre[r], threadIdx.x & 63, out_tape, out_strings);
 }
 
 }  // namespace
@@ -1468,7 +1403,8 @@ int sjhip_filter_where(sjhip_ctx *ctx, const uint8_t *key, size_t klen, const ui
     if (tape_len) *tape_len = (size_t)h[1];
     if (strings_len) *strings_len = (size_t)h[2];
     if (h[0] == 0) return query_bounds_check(ctx);
-    hipLaunchKernelGGL(k_q_copy, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, q, o, (u64 *)ctx->d_qtape.p, (u8 *)ctx->d_qstrings.p);
+    hipLaunchKernelGGL(k_q_copy, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, q, o, SJ_ARR((u64 *)ctx->d_qtape.p, h[1], A_FROWS_TAPE),
+                       SJ_ARR((u8 *)ctx->d_qstrings.p, h[2], A_FROWS_STRINGS));
     HIPCHK(hipGetLastError(), "filter copy launch");
     return SJHIP_OK;
 }

@@ -36,7 +36,7 @@ enum ArrId : uint32_t {
     // a row predicate (query.hip, sjhip_where_path): the flag of every current row / the kept rows in front of it / the new row offsets
     A_WHERE_FLAG, A_WHERE_PRE, A_WHERE_OFF,
     // the filtered rows (query.hip, sjhip_filter_rows): the output words of every row and their prefix / the Strings.B range of every
-    // row (first string, bytes, their prefix) / the new tape / the new Strings.B
+    // row (first string, bytes, their prefix) / the new tape / the new Strings.B (these two: sjhip_filter_where's as well)
     A_FROWS_WORDS, A_FROWS_STR, A_FROWS_TAPE, A_FROWS_STRINGS,
     // the marshaled rows (marshal.hip, sjhip_marshal_rows): the text bytes of every row and their prefix / the row offsets behind the
     // text / the text / the key flags recovered without SJHIP_FLAG_KEY_FLAGS, by tape index

@@ -7,6 +7,8 @@
 // one of \" l u d" and p = the last index below i with c(p) = 0 (an anchor; word 0, the opening root, is one):
 //     word i is raw  <=>  i - p - 1 is odd.
 // k_tw_last / k_tw_scan_last give every tile the last anchor in front of it; inside a tile a block max-scan does it.
+// The kernels that walk one row or record per wave apply the rule through tw_walk_span -- the one place that spells it for 64
+// words per step -- and share the wave idioms next to it: wave_bcast, wave_incl_sum, wave_sum, wave_each.
 // (Everything lives in an anonymous namespace: each .hip file that includes this header gets its own copy.)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -23,6 +25,56 @@ static constexpr int TW_THREADS = 256, TW_ITEMS = 8, TW_TILE = TW_THREADS * TW_I
 __device__ __forceinline__ bool two_word_tag(u64 w) {
     const u32 t = (u32)(w >> 56);
     return t == '"' || t == 'l' || t == 'u' || t == 'd';
+}
+
+// ---- one wave: broadcast, sums, the lanes of a ballot in turn ---------------------------------------------------------------------
+__device__ __forceinline__ u64 wave_bcast(u64 x, int j) { return (u64)__shfl((long long)x, j, 64); }  // lane j's x (j wave-uniform)
+__device__ __forceinline__ u32 wave_bcast(u32 x, int j) { return (u32)__shfl((int)x, j, 64); }
+__device__ __forceinline__ u64 wave_up(u64 x, int s) { return (u64)__shfl_up((long long)x, s, 64); }
+__device__ __forceinline__ u32 wave_up(u32 x, int s) { return (u32)__shfl_up((int)x, s, 64); }
+template <typename T>
+__device__ __forceinline__ T wave_incl_sum(T x, int lane) {  // the sum over the lanes up to and including this one (u32 / u64)
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const T up = wave_up(x, s);
+        if (lane >= s) x += up;
+    }
+    return x;
+}
+__device__ __forceinline__ u64 wave_sum(u64 x) {  // the sum over all 64 lanes, in every lane
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) x += (u64)__shfl_xor((long long)x, s, 64);
+    return x;
+}
+// "The wave's long X, one after another": body(j) for every lane j whose `pred` holds, in lane order.  Every lane of the wave makes
+// the call and every lane runs every body(j) -- j is wave-uniform, so a body may ballot and shuffle; it fetches lane j's values with
+// wave_bcast and keeps what belongs to that lane under `if (lane == j)`.
+template <typename F>
+__device__ __forceinline__ void wave_each(bool pred, F body) {
+    for (u64 todo = __ballot(pred); todo; todo &= todo - 1) body(__ffsll((unsigned long long)todo) - 1);
+}
+
+// The span walk: the words [v, v + nwords) of a tape by one wave, 64 per step.  body(i, w, in, raw) runs on every lane in every
+// step -- wave-uniform, so a body may ballot and shuffle -- with i: the lane's word, relative to v; in: i < nwords; w: tape[v + i]
+// (0 when !in); raw: the word is the second word of an entry, by the parity rule at the top of this file (undefined when !in).
+// The step's anchors come from one ballot; the last anchor of a step is carried into the next.
+// THE CALLER GUARANTEES that v is the first word of an entry (a record's root value, a row's value, a member): the word in front
+// of the span then counts as an anchor at -1, whatever it is.  No `p >= 0` guard: a span that is one scalar -- "s" or a number, a
+// two-word tag and no anchor inside -- has its word 1 told raw by exactly that anchor.
+// (Tape: Arr<const u64> -- in the debug build every read goes through its checked operator[].)
+template <typename Tape, typename F>
+__device__ __forceinline__ void tw_walk_span(const Tape &tape, u64 v, u64 nwords, int lane, F body) {
+    long long p_prev = -1;  // last anchor below the step, relative to v
+    for (u64 g = 0; g < nwords; g += 64) {
+        const u64 i = g + (u64)lane;
+        const bool in = i < nwords;
+        const u64 w = in ? tape[v + i] : 0;
+        const u64 zm = ~__ballot(in && two_word_tag(w)) & __ballot(in);  // the anchors of the step
+        const u64 zeros_below = zm & (lane ? (~0ull >> (64 - lane)) : 0ull);
+        const long long p = zeros_below ? (long long)g + (63 - __builtin_clzll(zeros_below)) : p_prev;
+        body(i, w, in, (((long long)i - p - 1) & 1) != 0);
+        if (zm) p_prev = (long long)g + (63 - __builtin_clzll(zm));
+    }
 }
 
 // block-wide exclusive scans over one value per thread (4 waves)

@@ -59,13 +59,17 @@ def test_parking_citations_hond(ctx):  # ndjson_test.go:250-267: 116
     check_query(ctx, park * 7, b"RP State Plate", b"CA")
 
 
+def dbl(bits):
+    return repr(struct.unpack("<d", struct.pack("<Q", bits))[0])
+
+
+tricky = [dbl((ord(c) << 56) | 0x000123456789ab) for c in '"lud{[}]rtfn']  # doubles whose raw word looks like a tag
+
+
 def test_record_shapes(ctx):
     """first-occurrence semantics, nested keys that must not match, non-string values, array roots, escapes (the
     comparison sees unescaped bytes), and numbers whose raw word looks like a tag (the copy classifies tag / raw words
     by position parity)"""
-    def dbl(bits):
-        return repr(struct.unpack("<d", struct.pack("<Q", bits))[0])
-    tricky = [dbl((ord(c) << 56) | 0x000123456789ab) for c in '"lud{[}]rtfn']
     recs = [
         b'{"k":"v"}',
         b'{"k":"x","k":"v"}',                       # first occurrence decides: no match
@@ -93,6 +97,73 @@ def test_record_shapes(ctx):
     check_query(ctx, b'{"k":"v"}', b"k", b"v")
     ctx.parse(b'{"k":"v","z":[1,2]}', ndjson=False)
     assert ctx.count_where(b"k", b"v") == 1 and ctx.count_where(b"z", b"v") == 0
+
+
+def _fill(n, names):
+    """[(member, its tape words)] of n words in all (n == 0 or n >= 3): "f..":<tag-lookalike double> is 4 words, "t..":true 3,
+    "a..":[true x m] 4 + m"""
+    head = {0: [], 3: [('"t%d":true', 3)], 1: [('"a%d":[true]', 5)], 2: [('"a%d":[true,true]', 6)]}[n % 4]
+    rest = n - sum(w for _, w in head)
+    assert rest >= 0, n
+    out = [(m % next(names), w) for m, w in head]
+    for _ in range(rest // 4):
+        i = next(names)
+        out.append(('"f%d":%s' % (i, tricky[i % len(tricky)]), 4))
+    return out
+
+
+def seam_records():
+    """-> [(line, words, [(index in the record, tag)])]: records matching k == "v" with chosen tape word counts (roots included) and
+    a string or a double across the 64-word steps of the copy.  The copy walks a record from the word behind its opening root, the
+    version before it walked from the root itself, so word s and word s - 1 of the record are each the last word of a step in one
+    of the two (s = 64, 128): both are used, which is also the other parity.  Lengths 126..130 reach the first seam, 190..194 both.
+    A record of 62..66 words ends before a two-word entry behind the first seam could close (that takes 68), so there the strings,
+    a double, and a double one word earlier are put last: against the end of the record's only or second step."""
+    import itertools
+    names = itertools.count()
+    out = []
+    KV = ('"k":"v"', 4)
+
+    def record(words, members, marks):
+        """the members, then a fill up to `words`; the first member starts at word 2 (root, brace)"""
+        members = members + _fill(words - 4 - sum(w for _, w in members), names)
+        assert 4 + sum(w for _, w in members) == words
+        out.append((("{" + ",".join(m for m, _ in members) + "}").encode(), words, marks))
+
+    for words in list(range(126, 131)) + list(range(190, 195)):
+        for s in (64, 128):
+            if s + 8 > words:
+                continue
+            for at in (s, s - 1):  # the tag word at `at`, its second word in the next step: of "k", of "v", of a double
+                record(words, _fill(at - 2, names) + [KV], [(at, '"'), (at + 2, '"')])
+                record(words, _fill(at - 4, names) + [KV], [(at - 2, '"'), (at, '"')])
+                record(words, [KV] + _fill(at - 8, names) + [('"x":' + tricky[3], 4)], [(at, "d")])
+    for words in range(62, 67):
+        record(words, _fill(words - 8, names) + [KV], [(words - 6, '"'), (words - 4, '"')])
+        record(words, [KV] + _fill(words - 12, names) + [('"x":' + tricky[0], 4)], [(words - 4, "d")])
+        record(words, [KV] + _fill(words - 14, names) + [('"y":[%s]' % tricky[0], 6)], [(words - 5, "d")])
+    return out
+
+
+def test_filter_copy_at_the_step_seams(ctx):
+    """sjhip_filter_where's copy on records whose length and whose two-word entries sit on the 64-word steps of the span walk
+    (seam_records), short records that do not match in between: Tape and Strings.B bit for bit the oracle's parse of the matching
+    lines (check_query).  The word counts and the marked words are asserted from the oracle's tape first."""
+    recs = seam_records()
+    ref = O.parse(b"\n".join(line for line, _, _ in recs), ndjson=True, copy_strings=True)
+    assert ref.rc == 0
+    at = 0
+    for line, words, marks in recs:
+        assert int(ref.tape[at]) >> 56 == ord("r") and (int(ref.tape[at]) & ((1 << 56) - 1)) - at == words, (line, words)
+        for i, tag in marks:
+            assert int(ref.tape[at + i]) >> 56 == ord(tag), (line, i, tag)
+        at += words
+    assert at == len(ref.tape)
+    assert sorted({w for _, w, _ in recs}) == list(range(62, 67)) + list(range(126, 131)) + list(range(190, 195))
+    short = [b'{"k":"x"}', b'{"j":"v"}', b'[1,2]', b'{"k":' + tricky[0].encode() + b'}', b'{}']
+    doc = b"\n".join(line + b"\n" + short[i % len(short)] for i, (line, _, _) in enumerate(recs))
+    check_query(ctx, doc, b"k", b"v")
+    check_query(ctx, doc, b"k", b"x")
 
 
 def test_random_records(ctx):
