@@ -437,6 +437,191 @@ __global__ __launch_bounds__(256) void k_q_extract(QView q, QPath pth, int kind,
     status[r] = (u8)st;
 }
 
+// ---- aggregates: count, sum, min, max of that column, in all and per record (sjhip_aggregate_path / _aggregate_path_records) -----
+// The reduction of what k_q_extract would write, without writing it: one lane per row walks and converts as above, and what
+// leaves the lane is a partial -- OK and other rows counted, the sum, the smallest and the largest key -- that is reduced
+// SEGMENTED by the record that owns the row.  The records are told by flags, not searched for: a row is the HEAD of a segment if
+// it is the first row of its record and its END if the next row is a head (or there is none), so a selection of one record owning
+// every row and one of a million records owning one row each are the same input.  The total is the same reduction with one
+// segment over all rows (AGG_ONE); without a selection every row is its own segment and is stored as it is (AGG_OWN).
+//   k_q_agg_heads   (AGG_OFFS) one lane per record: head[row_offsets[r]] = r + 1 for every record that has rows (head[] starts as 0;
+//                   the outputs start as 0 as well, which is the answer for a record without rows)
+//   k_q_agg_rows    per tile of AGG_TILE rows: the walk, then agg_tile: a segmented scan by wave shuffles (a head restarts the
+//                   running partial), the waves joined in wave order through LDS.  A segment that begins and ends inside the tile
+//                   is stored at its end row; what the tile cannot finish becomes at most two ITEMS of the next level: slot A, the
+//                   piece of a segment that began in an earlier tile (it ends here, or it covers the whole tile), and slot B, the
+//                   piece of the segment left open at the tile's end, with its record
+//   k_q_agg_fold    the same agg_tile over the items of the level below, AGG_TILE per block, until a level fits one tile: a B item
+//                   is a head, an A item that ends its segment an end.  Every level shrinks by 128, a record that spans any number
+//                   of tiles costs no lane more than one item per level, and the association of a float sum is fixed by the number
+//                   of rows and the offsets alone.
+// Sums: FLOAT is IEEE double addition in that association (identity -0.0, no atomics).  INT / UINT are exact: a value travels as
+// its low and its high 32-bit half (the high half signed for INT), each summed in 64 bits -- exact for 2^32 rows -- and put together
+// as a 128-bit number where a segment is stored.  Min / max compare keys: a uint64 whose unsigned order is the order of the kind
+// (INT: the sign bit flipped; FLOAT: all bits of a negative value flipped, the sign bit of the others: -0.0 below +0.0).
+// The status histogram of the total is six ballots per wave and one integer atomic per status that occurs in it.
+static constexpr int AGG_TILE = 256;
+static constexpr u64 AGG_SIGN = 0x8000000000000000ull;
+enum : u32 { AGG_ONE = 0, AGG_OWN = 1, AGG_OFFS = 2 };        // QAgg::mode
+enum : u32 { AGG_VALID = 1, AGG_HEAD = 2, AGG_END = 4 };      // AggItem::flags (0: no item)
+struct AggVal {
+    u32 ok, bad;  // rows whose conversion is SJHIP_COL_OK / is anything else
+    u64 s0, s1;   // FLOAT: s0 = the bits of the sum; INT / UINT: the sums of the low / of the high halves
+    u64 mn, mx;   // keys (agg_key); ~0 and 0 while no row is OK
+};
+struct AggItem {
+    AggVal v;
+    u32 rec1;     // the record of the segment + 1 (a head), else 0
+    u32 flags;
+};
+struct QAgg {
+    int kind;
+    u32 mode;
+    Arr<const u32> head;       // [rows] AGG_OFFS: record + 1 at the first row of every record that has rows, else 0
+    Arr<AggItem> items;        // [2 * tiles] what this level hands to the next: slots A and B of every tile
+    Arr<u64> out;              // six arrays of `records` entries end to end: count, not_ok, sum, sum_hi, min, max
+    u64 records;
+    unsigned long long *hist;  // [6] rows per status (the total), or null
+};
+__device__ __forceinline__ AggVal agg_identity(bool flt) { return {0u, 0u, flt ? AGG_SIGN : 0ull, 0ull, ~0ull, 0ull}; }
+__device__ __forceinline__ u64 agg_key(u64 x, int kind) {
+    if (kind == SJHIP_COL_UINT) return x;
+    if (kind == SJHIP_COL_INT) return x ^ AGG_SIGN;
+    return (x >> 63) ? ~x : x ^ AGG_SIGN;
+}
+__device__ __forceinline__ u64 agg_unkey(u64 k, int kind) {
+    if (kind == SJHIP_COL_UINT) return k;
+    if (kind == SJHIP_COL_INT) return k ^ AGG_SIGN;
+    return (k >> 63) ? k ^ AGG_SIGN : ~k;
+}
+// a: the rows in front, b: the rows behind
+__device__ __forceinline__ AggVal agg_join(const AggVal &a, const AggVal &b, bool flt) {
+    AggVal r;
+    r.ok = a.ok + b.ok;
+    r.bad = a.bad + b.bad;
+    r.s0 = flt ? (u64)__double_as_longlong(__longlong_as_double((long long)a.s0) + __longlong_as_double((long long)b.s0)) : a.s0 + b.s0;
+    r.s1 = a.s1 + b.s1;
+    r.mn = a.mn < b.mn ? a.mn : b.mn;
+    r.mx = a.mx > b.mx ? a.mx : b.mx;
+    return r;
+}
+__device__ __forceinline__ AggVal agg_up(const AggVal &v, int s) {
+    return {wave_up(v.ok, s), wave_up(v.bad, s), wave_up(v.s0, s), wave_up(v.s1, s), wave_up(v.mn, s), wave_up(v.mx, s)};
+}
+// the finished segment of record `rec`
+__device__ __forceinline__ void agg_store(const QAgg &a, u64 rec, const AggVal &v) {
+    u64 lo = 0, hi = 0;
+    if (v.ok) {
+        if (a.kind == SJHIP_COL_FLOAT) lo = v.s0;
+        else {  // s0 + s1 * 2^32 in 128 bits
+            lo = v.s0 + (v.s1 << 32);
+            hi = (a.kind == SJHIP_COL_INT ? (u64)((long long)v.s1 >> 32) : v.s1 >> 32) + (lo < v.s0 ? 1u : 0u);
+        }
+    }
+    a.out[rec] = v.ok;
+    a.out[a.records + rec] = v.bad;
+    a.out[2 * a.records + rec] = lo;
+    a.out[3 * a.records + rec] = hi;
+    a.out[4 * a.records + rec] = v.ok ? agg_unkey(v.mn, a.kind) : 0;
+    a.out[5 * a.records + rec] = v.ok ? agg_unkey(v.mx, a.kind) : 0;
+}
+// One item per thread of the block, in item order.  Reduces every item with the items of its segment in front of it in the tile,
+// stores the segments that begin and end here, and writes the tile's two slots of a.items.  An item that is not VALID -- a lane
+// behind the last row, an empty slot of the level below -- is transparent: it adds the identity to whatever passes over it (slot
+// B of a tile that lies wholly inside one segment is empty, and sits between that tile's slot A and the next one's).
+__device__ __forceinline__ void agg_tile(const QAgg &a, AggVal v, u32 flags, u32 rec1, AggItem *s_tail /* [AGG_TILE / 64] */) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool flt = a.kind == SJHIP_COL_FLOAT;
+    const bool valid = (flags & AGG_VALID) != 0, end = valid && (flags & AGG_END) != 0, last = tid == AGG_TILE - 1;
+    // bit 0: a head among the items the partial covers -- it starts at its segment's first item; bits 1-2: the last valid item at
+    // or in front of this one in the tile: 2 it leaves its segment open, 4 it ends it (0: none)
+    u32 st = ((flags & AGG_HEAD) ? 1u : 0u) | (valid ? (end ? 4u : 2u) : 0u);
+    u32 rk = rec1;  // the record + 1 of the last head at or in front of the item (they ascend); 0: none in the tile
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const AggVal o = agg_up(v, s);
+        const u32 ost = wave_up(st, s), ork = wave_up(rk, s);
+        if (lane >= s) {
+            if (!(st & 1u)) v = agg_join(o, v, flt);
+            st = ((st | ost) & 1u) | ((st & 6u) ? (st & 6u) : (ost & 6u));
+            rk = ork > rk ? ork : rk;
+        }
+    }
+    if (lane == 63) s_tail[wave] = {v, rk, st};
+    __syncthreads();
+    AggVal acc = agg_identity(flt);
+    u32 ast = 0, ark = 0;
+    for (int w = 0; w < AGG_TILE / 64; w++)
+        if (w < wave) {
+            const AggItem t = s_tail[w];
+            acc = (t.flags & 1u) ? t.v : agg_join(acc, t.v, flt);
+            ast = ((ast | t.flags) & 1u) | ((t.flags & 6u) ? (t.flags & 6u) : (ast & 6u));
+            ark = t.rec1 > ark ? t.rec1 : ark;
+        }
+    if (!(st & 1u)) v = agg_join(acc, v, flt);
+    st = ((st | ast) & 1u) | ((st & 6u) ? (st & 6u) : (ast & 6u));
+    rk = ark > rk ? ark : rk;
+    const bool f = (st & 1u) != 0, open = (st & 6u) == 2u;
+    if (end && f) agg_store(a, (u64)rk - 1u, v);
+    // slot A: the piece of a segment that began in an earlier tile -- it ends here, or it is still open behind the last item (the
+    // whole tile); after an end the next valid item is a head, so at most one item of a tile goes there.  Slot B: the piece of
+    // the segment that began here and is open behind the last item.
+    const bool to_a = !f && (end || (last && open)), to_b = f && last && open;
+    const AggItem none = {agg_identity(flt), 0u, 0u};
+    if (to_a) a.items[2ull * blockIdx.x] = {v, 0u, AGG_VALID | (end ? (u32)AGG_END : 0u)};
+    const int any_a = __syncthreads_or(to_a ? 1 : 0);
+    if (tid == 0 && !any_a) a.items[2ull * blockIdx.x] = none;
+    if (last) a.items[2ull * blockIdx.x + 1] = to_b ? AggItem{v, rk, AGG_VALID | AGG_HEAD} : none;
+}
+__global__ __launch_bounds__(256) void k_q_agg_heads(Arr<const u64> off, u32 records, Arr<u32> head) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= records) return;
+    const u64 a = off[r];
+    if (off[r + 1] > a) head[a] = r + 1u;
+}
+__global__ __launch_bounds__(AGG_TILE) void k_q_agg_rows(QView q, QPath pth, QAgg a) {
+    __shared__ AggItem s_tail[AGG_TILE / 64];
+    const u32 n = q_rows(q), r = blockIdx.x * AGG_TILE + threadIdx.x;
+    AggVal v = agg_identity(a.kind == SJHIP_COL_FLOAT);
+    int st = -1;
+    if (r < n) {
+        const u64 e = pth.n ? record_find_path(q, pth, r) : row_value(q, r);  // (no keys: the row's own value)
+        u64 x = 0;
+        st = e < SJHIP_PATH_NOT_OBJECT ? element_to(q, e, a.kind, &x) : path_status(e);
+        if (st == SJHIP_COL_OK) {
+            v.ok = 1;
+            v.mn = v.mx = agg_key(x, a.kind);
+            if (a.kind == SJHIP_COL_FLOAT) v.s0 = x;
+            else {
+                v.s0 = x & 0xffffffffull;
+                v.s1 = a.kind == SJHIP_COL_INT ? (u64)((long long)x >> 32) : x >> 32;
+            }
+        } else v.bad = 1;
+    }
+    if (a.hist)
+        for (int k = 0; k <= SJHIP_COL_RANGE; k++) count_ballot(st == k, &a.hist[k]);
+    if (a.mode == AGG_OWN) {  // (block-uniform) record r owns row r
+        if (r < n) agg_store(a, r, v);
+        return;
+    }
+    u32 flags = 0, rec1 = 0;  // behind the last row: not VALID
+    if (r < n) {
+        if (a.mode == AGG_ONE) rec1 = r == 0 ? 1u : 0u;
+        else rec1 = a.head[r];
+        const bool end = r + 1 == n || (a.mode == AGG_OFFS && a.head[r + 1] != 0);
+        flags = AGG_VALID | (rec1 ? (u32)AGG_HEAD : 0u) | (end ? (u32)AGG_END : 0u);
+    }
+    agg_tile(a, v, flags, rec1, s_tail);
+}
+// (a.items: the slots of THIS level; in: the m items of the level below)
+__global__ __launch_bounds__(AGG_TILE) void k_q_agg_fold(QAgg a, Arr<const AggItem> in, u32 m) {
+    __shared__ AggItem s_tail[AGG_TILE / 64];
+    const u32 i = blockIdx.x * AGG_TILE + threadIdx.x;
+    AggItem it = {agg_identity(a.kind == SJHIP_COL_FLOAT), 0u, 0u};
+    if (i < m) it = in[i];
+    agg_tile(a, it.v, it.flags, it.rec1, s_tail);
+}
+
 // Strings (Arrow's "large string" layout: u64 offsets, the bytes end to end) in three steps over the n = R + 1 records:
 //   k_q_col_len      one lane per record: FindElement, the status, the length of the record's text and the tape index of the
 //                    element (the gather does not walk the record again); entry n has length 0
@@ -1587,6 +1772,182 @@ int sjhip_extract_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_
                                   hipLaunchKernelGGL(k_q_extract, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, pth, kind,
                                                      (void *)d[0], d[1]);
                               });
+}
+
+// ---- aggregates ---------------------------------------------------------------------------------------------------------------
+// Both calls are one walk of the parts: per part the work arrays in d_kat (the results first, so that one copy brings back what
+// the caller asked for), the heads, the tile kernel and the folds; nothing of the context's result, its products or its
+// selection is written.  The total runs as one segment whose `record` 0 holds the answer; the host joins the parts in part order.
+struct AggWork {
+    u64 *out;                       // [6 * records (+ 6: the histogram of the total)]
+    u32 *head;                      // [rows]
+    std::vector<AggItem *> items;   // per level (AGG_OWN: none)
+    std::vector<u32> tiles;         // tiles of every level: rows -> AGG_TILE per tile -> two items per tile -> ...
+};
+static size_t agg_layout(Carve c, uint32_t n, size_t records, u32 mode, AggWork *w) {
+    const bool hist = mode == AGG_ONE, heads = mode == AGG_OFFS;
+    w->out = c.take<u64>(6 * records + (hist ? 6 : 0));
+    w->head = heads ? c.take<u32>(n) : nullptr;
+    w->items.clear();
+    w->tiles.clear();
+    for (u32 m = n;;) {
+        const u32 tiles = (m + AGG_TILE - 1) / AGG_TILE;
+        w->tiles.push_back(tiles);
+        if (mode == AGG_OWN) {  // every row is stored as it is: no items, no folds
+            w->items.push_back(nullptr);
+            break;
+        }
+        w->items.push_back(c.take<AggItem>(2 * (size_t)tiles));
+        if (tiles == 1) break;
+        m = 2 * tiles;
+    }
+    return c.used;
+}
+// the kernels of one part: n rows (> 0), `records` result slots; off: the row offsets of the selection (AGG_OFFS)
+static int agg_enqueue(sjhip_ctx *ctx, sjhip_ctx *part, const QView &q, const QPath &pth, int kind, u32 mode, uint32_t n, size_t records,
+                       const u64 *off, const AggWork &w) {
+    QAgg a;
+    a.kind = kind;
+    a.mode = mode;
+    a.head = SJ_ARR((const u32 *)w.head, n, A_AGG_HEAD);
+    a.out = SJ_ARR(w.out, 6 * records, A_AGG_OUT);
+    a.records = records;
+    a.hist = mode == AGG_ONE ? (unsigned long long *)(w.out + 6) : nullptr;
+    if (mode != AGG_OWN) HIPCHK(hipMemsetAsync(w.out, 0, (6 * records + (a.hist ? 6 : 0)) * 8, part->stream), "aggregate results memset");
+    if (mode == AGG_OFFS) {
+        HIPCHK(hipMemsetAsync(w.head, 0, (size_t)n * 4, part->stream), "aggregate heads memset");
+        hipLaunchKernelGGL(k_q_agg_heads, dim3(((u32)records + 255) / 256), dim3(256), 0, part->stream, SJ_ARR(off, records + 1, A_WHERE_OFF),
+                           (u32)records, SJ_ARR(w.head, n, A_AGG_HEAD));
+    }
+    AggItem *level = w.items[0];
+    a.items = SJ_ARR(level, level ? 2 * (size_t)w.tiles[0] : 0, A_AGG_ITEMS);
+    hipLaunchKernelGGL(k_q_agg_rows, dim3(w.tiles[0]), dim3(AGG_TILE), 0, part->stream, q, pth, a);
+    a.hist = nullptr;
+    for (size_t l = 1; mode != AGG_OWN && l < w.tiles.size(); l++) {
+        const u32 m = 2 * w.tiles[l - 1];
+        const AggItem *const below = level;
+        level = w.items[l];
+        a.items = SJ_ARR(level, 2 * (size_t)w.tiles[l], A_AGG_ITEMS);
+        hipLaunchKernelGGL(k_q_agg_fold, dim3(w.tiles[l]), dim3(AGG_TILE), 0, part->stream, a, SJ_ARR(below, m, A_AGG_ITEMS), m);
+    }
+    HIPCHK(hipGetLastError(), "aggregate launch");
+    return SJHIP_OK;
+}
+static int agg_args(sjhip_ctx *ctx, const char *who, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int kind, QPath *pth,
+                    size_t *klen, std::vector<sjhip_ctx *> *parts) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (kind != SJHIP_COL_FLOAT && kind != SJHIP_COL_INT && kind != SJHIP_COL_UINT) {
+        ctx_set_error(ctx, "%s: kind %d is not SJHIP_COL_FLOAT, SJHIP_COL_INT or SJHIP_COL_UINT", who, kind);
+        return SJHIP_ERR_ARG;
+    }
+    const int rc = make_path(ctx, keys, key_lens, n_keys, pth, klen, true);
+    return rc ? rc : query_parts(ctx, keys ? keys : &NO_VALUE, *klen, &NO_VALUE, 0, parts);
+}
+// unsigned order of the keys = the order of the kind (the device's agg_key)
+static u64 agg_host_key(u64 x, int kind) {
+    if (kind == SJHIP_COL_UINT) return x;
+    if (kind == SJHIP_COL_INT) return x ^ AGG_SIGN;
+    return (x >> 63) ? ~x : x ^ AGG_SIGN;
+}
+
+int sjhip_aggregate_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int kind, sjhip_agg *out) {
+    QPath pth;
+    size_t klen = 0;
+    std::vector<sjhip_ctx *> parts;
+    int rc = agg_args(ctx, "sjhip_aggregate_path", keys, key_lens, n_keys, kind, &pth, &klen, &parts);
+    if (rc) return rc;
+    if (!out) return SJHIP_ERR_ARG;
+    const uint8_t *const kb = keys ? keys : &NO_VALUE;
+    rc = query_over_parts(ctx, parts, kb, klen, &NO_VALUE, 0, true, "aggregate sync",
+        [&](const sjhip_ctx *, uint32_t n) {
+            AggWork w;
+            return agg_layout(Carve(), n, 1, AGG_ONE, &w) + 64;
+        },
+        [&](size_t, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
+            AggWork w;
+            (void)agg_layout(Carve(part->d_kat.p), n, 1, AGG_ONE, &w);
+            const int rc = agg_enqueue(ctx, part, q, pth, kind, AGG_ONE, n, 1, nullptr, w);
+            if (rc) return rc;
+            HIPCHK(hipMemcpyAsync(part->h_scratch + 512, w.out, 12 * 8, hipMemcpyDeviceToHost, part->stream), "D2H aggregate");
+            return SJHIP_OK;
+        },
+        [](size_t, sjhip_ctx *) {});
+    if (rc) return rc;
+    sjhip_agg t;
+    memset(&t, 0, sizeof t);
+    bool any = false;
+    for (sjhip_ctx *part : parts) {  // in part order: the float sum is added up in it
+        const uint32_t n = part_rows(ctx, part, true);
+        if (n == 0) continue;  // (nothing was launched, nothing came back)
+        const u64 *h = (const u64 *)(part->h_scratch + 512);  // count, not_ok, sum, sum_hi, min, max, status[6]
+        t.rows += n;
+        for (int k = 0; k < 6; k++) t.status[k] += h[6 + k];
+        if (h[0] == 0) continue;
+        if (kind == SJHIP_COL_FLOAT) {
+            double a, b;
+            memcpy(&a, &t.sum_lo, 8);
+            memcpy(&b, &h[2], 8);
+            a = any ? a + b : b;
+            memcpy(&t.sum_lo, &a, 8);
+        } else {
+            const u64 lo = t.sum_lo + h[2];
+            t.sum_hi += h[3] + (lo < t.sum_lo ? 1u : 0u);
+            t.sum_lo = lo;
+        }
+        if (!any || agg_host_key(h[4], kind) < agg_host_key(t.min, kind)) t.min = h[4];
+        if (!any || agg_host_key(h[5], kind) > agg_host_key(t.max, kind)) t.max = h[5];
+        any = true;
+    }
+    *out = t;
+    return SJHIP_OK;
+}
+
+int sjhip_aggregate_path_records(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int kind, uint64_t *count,
+                                 uint64_t *not_ok, void *sum, uint64_t *sum_hi, void *min, void *max, size_t cap_records, size_t *records) {
+    QPath pth;
+    size_t klen = 0;
+    std::vector<sjhip_ctx *> parts;
+    int rc = agg_args(ctx, "sjhip_aggregate_path_records", keys, key_lens, n_keys, kind, &pth, &klen, &parts);
+    if (rc) return rc;
+    if (!records) return SJHIP_ERR_ARG;
+    std::vector<size_t> at(parts.size() + 1, 0);  // the records in front of every part
+    for (size_t k = 0; k < parts.size(); k++) at[k + 1] = at[k] + parts[k]->q_records + 1u;
+    *records = at[parts.size()];
+    if (cap_records < *records) {
+        ctx_set_error(ctx, "sjhip_aggregate_path_records: room for %zu records, the result holds %zu", cap_records, *records);
+        return SJHIP_ERR_ARG;
+    }
+    const uint8_t *const kb = keys ? keys : &NO_VALUE;
+    const bool sel = selected(ctx, true);
+    u8 *const dst[6] = {(u8 *)count, (u8 *)not_ok, (u8 *)sum, (u8 *)sum_hi, (u8 *)min, (u8 *)max};
+    for (size_t k = 0; k < parts.size(); k++)  // a part without rows launches nothing: its records hold no row
+        if (part_rows(ctx, parts[k], true) == 0)
+            for (u8 *d : dst)
+                if (d) memset(d + at[k] * 8, 0, (at[k + 1] - at[k]) * 8);
+    const u32 mode = sel ? AGG_OFFS : AGG_OWN;
+    return query_over_parts(ctx, parts, kb, klen, &NO_VALUE, 0, true, "aggregate sync",
+        [&](const sjhip_ctx *part, uint32_t n) {
+            AggWork w;
+            return agg_layout(Carve(), n, (size_t)part->q_records + 1u, mode, &w) + 64;
+        },
+        [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
+            const size_t recs = (size_t)part->q_records + 1u;
+            AggWork w;
+            (void)agg_layout(Carve(part->d_kat.p), n, recs, mode, &w);
+            RowsOut sel_rows = {nullptr, nullptr, nullptr};
+            if (sel) {
+                const ResultState::Rows &z = part->res.rows.sizes();
+                (void)rows_layout(Carve(part->d_rows.p), z.records, z.rows, &sel_rows);
+            }
+            const int rc = agg_enqueue(ctx, part, q, pth, kind, mode, n, recs, sel_rows.off, w);
+            if (rc) return rc;
+            for (int j = 0; j < 6; j++)
+                if (dst[j])
+                    HIPCHK(hipMemcpyAsync(dst[j] + at[k] * 8, w.out + (size_t)j * recs, recs * 8, hipMemcpyDeviceToHost, part->stream),
+                           "D2H per-record aggregates");
+            return SJHIP_OK;
+        },
+        [](size_t, sjhip_ctx *) {});
 }
 
 // ---- products: built on the device part by part, fetched later -- the string column, the list column, the table ---------------

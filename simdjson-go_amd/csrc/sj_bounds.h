@@ -40,7 +40,10 @@ enum ArrId : uint32_t {
     A_FROWS_WORDS, A_FROWS_STR, A_FROWS_TAPE, A_FROWS_STRINGS,
     // the marshaled rows (marshal.hip, sjhip_marshal_rows): the text bytes of every row and their prefix / the row offsets behind the
     // text / the text / the key flags recovered without SJHIP_FLAG_KEY_FLAGS, by tape index
-    A_MROWS_OFF, A_MROWS_OUT_OFF, A_MROWS_TEXT, A_MROWS_KF
+    A_MROWS_OFF, A_MROWS_OUT_OFF, A_MROWS_TEXT, A_MROWS_KF,
+    // the aggregates (query.hip, sjhip_aggregate_path): the head flag of every row / the items a level of the segmented reduction
+    // hands to the next / the per-record results
+    A_AGG_HEAD, A_AGG_ITEMS, A_AGG_OUT
 };
 
 #if defined(SJ_DEBUG_BOUNDS)

@@ -19,6 +19,12 @@ class StreamResult(C.Structure):
                 ("message", C.c_void_p), ("message_len", C.c_size_t), ("device", C.c_int), ("records", C.c_uint64)]
 
 
+class Agg(C.Structure):
+    """sjhip_agg (include/sjhip.h): 88 bytes"""
+    _fields_ = [("rows", C.c_uint64), ("status", C.c_uint64 * 6), ("sum_lo", C.c_uint64), ("sum_hi", C.c_uint64),
+                ("min", C.c_uint64), ("max", C.c_uint64)]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/sjhip.h
 SYMBOLS = {
     "sjhip_supported": (C.c_int, []),
@@ -62,6 +68,9 @@ SYMBOLS = {
     "sjhip_project_keys": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, szp]),
     "sjhip_extract_path": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                      szp]),
+    "sjhip_aggregate_path": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Agg)]),
+    "sjhip_aggregate_path_records": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, szp]),
     "sjhip_extract_path_strings": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32, szp, szp]),
     "sjhip_fetch_path_strings": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sjhip_extract_path_list": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32, C.c_int, szp, szp]),

@@ -315,6 +315,39 @@ class Context:
                                          C.byref(cnt)))
         return values[: cnt.value], status[: cnt.value]
 
+    # ---- aggregates (include/sjhip.h: sjhip_aggregate_path / sjhip_aggregate_path_records) ----------------------------------------
+    AGG_TILE = 256  # rows per tile of the device's segmented reduction (csrc/query.hip): the shapes of the tests come from it
+
+    def aggregate_path(self, path, kind):
+        """count, sum, min and max of the column extract_path(path, kind) returns (kind = COL_FLOAT / COL_INT / COL_UINT), reduced on
+        the device over all rows of the selection in force (without one: the records); an empty path: the row's own value.
+        -> Aggregate: rows, status (6 ints), count, sum (an exact int, or a float), min, max (None when no row is OK), raw"""
+        blob, lens, n = self._keys(path)
+        raw = _lib.Agg()
+        self._check(_lib.lib().sjhip_aggregate_path(self._h, blob if n else None, lens if n else None, n, int(kind), C.byref(raw)))
+        return Aggregate(raw, int(kind))
+
+    def aggregate_path_records(self, path, kind):
+        """the same per record: record r reduces the rows fetch_rows gives it (without a selection: its root value).
+        -> (count, not_ok: uint64 arrays; sum: float64 array, or the low 64 bits as int64 / uint64; sum_hi: uint64 array -- the
+        high 64 bits of an integer sum --; min, max: float64 / int64 / uint64 arrays), one entry per record; a record without an
+        OK row has count 0 and zeros"""
+        blob, lens, n = self._keys(path)
+        L = _lib.lib()
+        dt = self._COL_DTYPES[int(kind)]
+        cnt = C.c_size_t(0)
+        args = (self._h, blob if n else None, lens if n else None, n, int(kind))
+        rc = L.sjhip_aggregate_path_records(*args, None, None, None, None, None, None, 0, C.byref(cnt))  # (no room: the record count)
+        if rc and not cnt.value:
+            self._check(rc)
+        m = max(cnt.value, 1)
+        count, not_ok, sum_hi = (np.empty(m, dtype=np.uint64) for _ in range(3))  # (the call fills every entry of every record)
+        total, lo, hi = (np.empty(m, dtype=dt) for _ in range(3))
+        self._check(L.sjhip_aggregate_path_records(*args, count.ctypes.data, not_ok.ctypes.data, total.ctypes.data, sum_hi.ctypes.data,
+                                                   lo.ctypes.data, hi.ctypes.data, m, C.byref(cnt)))
+        k = cnt.value
+        return count[:k], not_ok[:k], total[:k], sum_hi[:k], lo[:k], hi[:k]
+
     def extract_path_strings(self, path, cvt=False, fetch=True):
         """Iter.FindElement(path...) then Iter.StringBytes (or StringCvt with cvt=True) on every record, built on the device.
         -> (offsets: uint64 array of records + 1, data: bytes, status: uint8 array) -- Arrow's large-string layout; with
@@ -524,6 +557,30 @@ class Context:
         strings = np.empty(strings_len, dtype=np.uint8)
         self._check(_lib.lib().sjhip_fetch(self._h, tape.ctypes.data, strings.ctypes.data))
         return tape, strings
+
+
+class Aggregate:
+    """what Context.aggregate_path returns: the sjhip_agg of the call (raw) read for its kind"""
+
+    def __init__(self, raw, kind):
+        import struct
+        self.raw, self.kind = raw, kind
+        self.rows = int(raw.rows)
+        self.status = [int(x) for x in raw.status]
+        self.count = self.status[Context.COL_OK]
+        fmt = {Context.COL_FLOAT: "<d", Context.COL_INT: "<q", Context.COL_UINT: "<Q"}[kind]
+        value = lambda bits: struct.unpack(fmt, struct.pack("<Q", int(bits)))[0]  # noqa: E731
+        if kind == Context.COL_FLOAT:
+            self.sum = value(raw.sum_lo)
+        else:
+            self.sum = (int(raw.sum_hi) << 64) | int(raw.sum_lo)
+            if kind == Context.COL_INT and self.sum >> 127:
+                self.sum -= 1 << 128
+        self.min = value(raw.min) if self.count else None
+        self.max = value(raw.max) if self.count else None
+
+    def __repr__(self):
+        return f"Aggregate(rows={self.rows}, status={self.status}, sum={self.sum!r}, min={self.min!r}, max={self.max!r})"
 
 
 class MultiContext:
