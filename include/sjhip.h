@@ -272,6 +272,48 @@ int sjhip_aggregate_path_records(sjhip_ctx *ctx, const uint8_t *keys, const uint
                                  uint64_t *count /* OK rows */, uint64_t *not_ok /* rows with any other status */,
                                  void *sum /* 8 B each: double, or the low 64 bits */, uint64_t *sum_hi,
                                  void *min, void *max, size_t cap_records, size_t *records);
+/* Groups ("group by"): the distinct keys at a path as a dictionary in first-occurrence order, a code into it for every row, and the
+ * aggregates above per distinct key -- the loop a caller of the reference writes with a map from Iter.StringBytes / Iter.Int to a
+ * running count and sum, on the device.  The rows are those of the selection in force (without one: the root value of every
+ * record), numbered in that order.
+ *   key of a row   Iter.FindElement(key path) on the row, then key_kind = SJHIP_COL_STRING: Iter.StringBytes, the unescaped bytes
+ *                  (the empty string is a key; "A" and its escaped spelling, backslash u0041, are one key, with and without SJHIP_FLAG_COPY_STRINGS), or
+ *                  SJHIP_COL_INT: Iter.Int, exactly sjhip_extract_path's conversion (1, 1.0 and 1.9 are the key 1).  Every other
+ *                  key kind is SJHIP_ERR_ARG.  key_n_keys == 0: the key is the row's own value ("hashtags":["a","b","a"]).
+ *                  status[row] is the byte sjhip_extract_path[_strings] would give; a row whose status is not SJHIP_COL_OK is in
+ *                  no group and has the code SJHIP_GROUP_NONE.
+ *   groups         two OK rows are in one group iff their keys are equal (same length and bytes / same int64).  Group g's first
+ *                  row comes before group g + 1's: codes, dictionary, first_row and group_rows are decided by the input alone.
+ *   per group      first_row (the row number of its first row), group_rows (its rows), and with a value column the six arrays of
+ *                  sjhip_aggregate_path_records with the group in the place of the record: the value of a row is
+ *                  FindElement(value path) + the conversion of val_kind = SJHIP_COL_FLOAT / INT / UINT (val_n_keys == 0: the row's
+ *                  own value); count = the group's rows whose value is OK, not_ok = the rest; sums, min and max as described above
+ *                  (the float association depends on the rows and their grouping only; no floating-point atomics).
+ *                  val_kind = SJHIP_GROUP_NO_VALUE: no value column is evaluated, val_keys / val_key_lens are ignored and may be
+ *                  NULL, and sjhip_fetch_group_aggregates is SJHIP_ERR_ARG ("no value column").
+ * sjhip_group_path builds the grouping on the device and returns its sizes: *rows, *groups and *key_bytes (STRING: the bytes of
+ * all keys; INT: 8 * groups).  Without rows nothing is launched and all three are 0; rows without a single OK key: *groups = 0.
+ *   sjhip_fetch_groups            key_offsets [groups + 1] and keys (key_bytes bytes end to end) for STRING keys -- Arrow's large
+ *                                 string layout, key_offsets[0] = 0 is written even without groups --, or keys = int64_t[groups]
+ *                                 for INT keys (key_offsets is ignored); first_row, group_rows [groups]; codes, status [rows].
+ *   sjhip_fetch_group_aggregates  count, not_ok, sum, sum_hi, min, max [groups] each.
+ * Any destination may be NULL.  (codes, keys) is the dictionary-encoded column an Arrow consumer takes in place of the strings.
+ * Lifetime: the grouping is a product of its own with its own device arena (counted by sjhip_ctx_device_bytes, freed by
+ * sjhip_ctx_trim); it lasts until the next parse or the next sjhip_group_path, is materialised data -- it survives a change or drop
+ * of the selection and every other product, and they survive it -- and a call that fails behind its argument checks leaves no
+ * grouping (as sjhip_extract_table leaves no table).  Each path has the limits of sjhip_find_path.
+ * Errors: SJHIP_ERR_ARG, with sjhip_last_error naming the reason and nothing touched (the previous grouping included): no result on
+ * the device, a bad path, an unknown key or value kind, a fetch without a grouping, and a sharded ND result ("... is sharded":
+ * joining the dictionaries of shards is not done here).  More than 2^30 rows: SJHIP_ERR_TOOBIG. */
+#define SJHIP_GROUP_NONE 0xffffffffu
+#define SJHIP_GROUP_NO_VALUE (-1)
+int sjhip_group_path(sjhip_ctx *ctx, const uint8_t *key_keys, const uint32_t *key_key_lens, uint32_t key_n_keys, int key_kind,
+                     const uint8_t *val_keys, const uint32_t *val_key_lens, uint32_t val_n_keys, int val_kind,
+                     size_t *rows, size_t *groups, size_t *key_bytes);
+int sjhip_fetch_groups(sjhip_ctx *ctx, uint64_t *key_offsets, void *keys, uint64_t *first_row, uint64_t *group_rows,
+                       uint32_t *codes, uint8_t *status);
+int sjhip_fetch_group_aggregates(sjhip_ctx *ctx, uint64_t *count, uint64_t *not_ok, void *sum, uint64_t *sum_hi,
+                                 void *min, void *max);
 /* List columns: the ARRAY at `path` of every record, converted on the device -- the reference's Iter.FindElement(path...),
  * Iter.Array() and then Array.AsFloat / AsInteger / AsUint64 / AsString / AsStringCvt (parsed_array.go:145-344); paths, records
  * and limits are those of sjhip_find_path.

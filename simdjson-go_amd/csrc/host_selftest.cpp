@@ -798,8 +798,9 @@ extern "C" int sj_selftest_newlines_to_cr(void) {
 //   17 column.begin   18 publish column   19 list.begin   20 / 21 publish list, numbers / strings
 //   22 / 23 / 24 release_shared of the filtered / serialized / marshaled tenant   25 table.begin   26 publish table
 //   27 rows.begin (sjhip_select_records, and the first step of sjhip_select_rows)   28 publish rows
+//   29 groups.begin (the first step of sjhip_group_path behind its argument checks)   30 publish groups
 // bits: 0 pending, 1 whole, 2 resident, 3 sharded, 4 key_flags, 5 packed, 6 filtered, 7 serialized, 8 marshaled, 9 column,
-// 10 list of numbers, 11 list of strings, 12 table, 13 rows.  Returns 0, or 1 + the index of an unknown code.
+// 10 list of numbers, 11 list of strings, 12 table, 13 rows, 14 groups.  Returns 0, or 1 + the index of an unknown code.
 #include "sj_result.h"
 extern "C" int sj_selftest_result_state(const uint8_t *ops, size_t n, uint32_t *bits_out) {
     sj::ResultState s;
@@ -824,12 +825,14 @@ extern "C" int sj_selftest_result_state(const uint8_t *ops, size_t n, uint32_t *
         else if (op == 26) s.publish(&sj::ResultState::table, {});
         else if (op == 27) s.rows.begin();
         else if (op == 28) s.publish(&sj::ResultState::rows, {1, 1});
+        else if (op == 29) s.groups.begin();
+        else if (op == 30) s.publish(&sj::ResultState::groups, {1, 1, 1, 4, -1});
         else return 1 + (int)k;
         bits_out[k] = (uint32_t)s.pending() | (uint32_t)s.whole() << 1 | (uint32_t)s.resident() << 2 | (uint32_t)s.sharded() << 3 |
                       (uint32_t)s.key_flags() << 4 | (uint32_t)s.packed() << 5 | (uint32_t)s.filtered() << 6 |
                       (uint32_t)s.serialized() << 7 | (uint32_t)s.marshaled() << 8 | (uint32_t)s.column.exists() << 9 |
                       (uint32_t)s.list_of(false) << 10 | (uint32_t)s.list_of(true) << 11 | (uint32_t)s.table.exists() << 12 |
-                      (uint32_t)s.rows.exists() << 13;
+                      (uint32_t)s.rows.exists() << 13 | (uint32_t)s.groups.exists() << 14;
     }
     return 0;
 }

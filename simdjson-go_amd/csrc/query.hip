@@ -25,6 +25,7 @@
 #include "sj_device.h"
 #include "sj_bounds.h"
 #include "sj_ftoa.h"
+#include "sj_group.h"
 #include "sj_stage2.h"
 #include "sj_tapewalk.h"
 #include "sj_tablewalk.h"
@@ -482,6 +483,10 @@ struct QAgg {
     Arr<u64> out;              // six arrays of `records` entries end to end: count, not_ok, sum, sum_hi, min, max
     u64 records;
     unsigned long long *hist;  // [6] rows per status (the total), or null
+    // the grouping (sjhip_group_path): position r of the reduction is row perm[r] of the view, and there are n_perm positions --
+    // the rows that have a key, ordered by group.  Null: position r is row r, and there are as many as the view has rows.
+    Arr<const u32> perm;
+    u32 n_perm;
 };
 __device__ __forceinline__ AggVal agg_identity(bool flt) { return {0u, 0u, flt ? AGG_SIGN : 0ull, 0ull, ~0ull, 0ull}; }
 __device__ __forceinline__ u64 agg_key(u64 x, int kind) {
@@ -581,11 +586,12 @@ __global__ __launch_bounds__(256) void k_q_agg_heads(Arr<const u64> off, u32 rec
 }
 __global__ __launch_bounds__(AGG_TILE) void k_q_agg_rows(QView q, QPath pth, QAgg a) {
     __shared__ AggItem s_tail[AGG_TILE / 64];
-    const u32 n = q_rows(q), r = blockIdx.x * AGG_TILE + threadIdx.x;
+    const u32 n = a.perm ? a.n_perm : q_rows(q), r = blockIdx.x * AGG_TILE + threadIdx.x;
     AggVal v = agg_identity(a.kind == SJHIP_COL_FLOAT);
     int st = -1;
     if (r < n) {
-        const u64 e = pth.n ? record_find_path(q, pth, r) : row_value(q, r);  // (no keys: the row's own value)
+        const u32 row = a.perm ? a.perm[r] : r;
+        const u64 e = pth.n ? record_find_path(q, pth, row) : row_value(q, row);  // (no keys: the row's own value)
         u64 x = 0;
         st = e < SJHIP_PATH_NOT_OBJECT ? element_to(q, e, a.kind, &x) : path_status(e);
         if (st == SJHIP_COL_OK) {
@@ -1376,6 +1382,246 @@ __global__ __launch_bounds__(256) void k_q_frows_copy(QView q, QFRows o, Arr<u64
     wave_copy_record(q, v, (w0 & TW_PAYLOAD) - v, o.words[r], o.first_str[r], o.s_len[r], o.s_pre[r], threadIdx.x & 63, out_tape, out_strings);
 }
 
+// ---- groups: the distinct keys at a path, a code per row, aggregates per key (sjhip_group_path) ---------------------------------------
+// "group by": the key of a row is FindElement(key path) + Iter.StringBytes or Iter.Int; two rows with an OK key are in one group iff
+// their keys are equal, and groups are numbered by first occurrence -- so codes, dictionary, first rows and group sizes are decided
+// by the input alone, not by the hash or by which lane came first.  All on the device, kernel boundaries do the ordering:
+//   k_q_group_keys     one lane per row: the key's status, its element (STRING: the tape index; INT: the value) and its 64-bit hash
+//                      (sj_group.h: 8 bytes per step).  A long key is hashed -- and later compared -- by its lane alone: the keys
+//                      this serves (a make, a language, a screen name) are short.
+//   k_q_group_insert   the dictionary: an open-addressing table of row numbers (empty: GROUP_NONE), capacity a power of two >= twice
+//                      the rows, linear probing.  A row claims an empty slot by compare-and-swap; on an occupied one it compares its
+//                      key with the occupant ROW's key -- read-only tape / Strings.B / message data, so the slot word is all that is
+//                      communicated -- and on equality lowers the slot to the smaller row (atomicMin, skipped when the occupant is
+//                      smaller already: a handful of distinct keys would otherwise draw every row's atomic to a handful of addresses),
+//                      else probes on.  The occupant only ever changes to a smaller row with an EQUAL key, so a comparison stays
+//                      valid whatever happens to the slot afterwards, and a key always ends in the first slot of its probe sequence
+//                      that did not hold a different key.  Every access to the table here is a device-scope atomic (a plain load
+//                      may be served from another XCD's L2).  No lane waits for another: nothing locks, nothing spins, and because
+//                      the capacity exceeds the rows every probe sequence ends (the loop is bounded by the capacity besides).
+//   k_q_group_first    behind the boundary: row r is the first of its group iff table[slot[r]] == r -> flag (and, STRING, the length
+//                      of its key).  Exclusive scans of both (the tile pattern of sj_tapewalk.h) number the groups and place the
+//                      dictionary's keys; the totals are the groups, the key bytes and -- a third tile sum -- the rows with a key.
+//   k_q_group_emit     codes[r] = the number of its slot's first row; the first rows write their group's entries: first_row, the
+//                      key (a short one by the lane, a long one by the wave, like the string column) or the int64
+//   hist/scan/scatter  a stable least-significant-digit radix sort of the rows by code, GROUP_RADIX_BITS per pass and only as many
+//                      passes as the group count needs: per tile a digit histogram, an exclusive scan of the digit-major
+//                      histograms, a scatter whose rank inside the tile is the row order (wave ballots match equal digits, the waves
+//                      and the rounds of a tile are taken in order).  Rows without a key carry the code `groups` and end behind all.
+//   k_q_group_bounds   in the sorted sequence a position whose code differs from the one in front begins a group: the group offsets;
+//   k_q_group_counts   their differences are group_rows -- no contended atomics anywhere.
+// The aggregates are the segmented reduction above with the sorted rows as QAgg::perm and the group offsets as the row offsets
+// (AGG_OFFS): groups in the place of records, so association, 128-bit sums and min / max keys are the tested ones.
+static_assert(GROUP_RADIX == GROUP_SORT_THREADS, "thread d of a sort block owns digit d");
+struct QGroup {
+    int key_kind;                      // SJHIP_COL_STRING / SJHIP_COL_INT
+    u32 n;                             // rows
+    u32 mask;                          // capacity of the table - 1
+    Arr<u8> status;                    // [n] the key's status
+    Arr<u64> kidx;                     // [n] STRING: tape index of the key element; INT: the value
+    Arr<u64> hash;                     // [n]
+    Arr<u32> slot;                     // [n] the slot the row ended in
+    Arr<u32> table;                    // [mask + 1] row numbers
+    Arr<u32> flag;                     // [n + 1] 1 at the first row of a group -> exclusive prefix: the group's number
+    Arr<u64> len;                      // [n + 1] STRING: bytes of a first row's key -> their offset in the dictionary; INT: null
+    unsigned long long *tiles_f, *tiles_l, *tiles_o;  // [tiles] tile sums of flag / len / the rows with a key
+    unsigned long long *totals;        // the totals of the scans: [0] groups, [1] key bytes, [2] rows with a key
+};
+struct GroupOut {  // the product (d_group), see group_layout
+    Arr<u64> key_off;     // [groups + 1] STRING
+    Arr<u8> key_bytes;    // [key bytes] STRING
+    Arr<u64> key_int;     // [groups] INT
+    Arr<u64> first_row;   // [groups]
+    Arr<u64> group_rows;  // [groups]
+    Arr<u32> codes;       // [n]
+    Arr<u8> status;       // [n]
+};
+struct QSort {
+    u32 n, shift;
+    Arr<const u32> keys_in, rows_in;  // rows_in null: position i is row i (the first pass)
+    Arr<u32> keys_out, rows_out;
+    Arr<u32> hist;                    // [GROUP_RADIX * tiles] digit-major: entry d * tiles + t
+};
+__device__ __forceinline__ bool group_keys_equal(const QView &q, const QGroup &g, u32 a, u32 b) {
+    const u64 ka = g.kidx[a], kb = g.kidx[b];
+    if (g.key_kind == SJHIP_COL_INT) return ka == kb;
+    const u64 len = q.tape[ka + 1];
+    if (len != q.tape[kb + 1]) return false;
+    return group_bytes_equal(str_bytes(q, q.tape[ka], len), str_bytes(q, q.tape[kb], len), len);
+}
+__global__ __launch_bounds__(256) void k_q_group_keys(QView q, QPath pth, QGroup g) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= g.n) return;
+    const u64 v = pth.n ? record_find_path(q, pth, r) : row_value(q, r);  // (no keys: the row's own value)
+    int st;
+    u64 k = 0, h = 0;
+    if (v >= SJHIP_PATH_NOT_OBJECT) st = path_status(v);
+    else if (g.key_kind == SJHIP_COL_INT) {
+        st = element_to(q, v, SJHIP_COL_INT, &k);
+        if (st == SJHIP_COL_OK) h = group_hash_int(k);
+    } else {
+        u64 len = 0;
+        st = element_text_len(q, v, false, &len);
+        if (st == SJHIP_COL_OK) {
+            k = v;
+            h = group_hash_bytes(str_bytes(q, q.tape[v], len), len);
+        }
+    }
+    g.status[r] = (u8)st;
+    g.kidx[r] = k;
+    g.hash[r] = h;
+}
+__global__ __launch_bounds__(256) void k_q_group_insert(QView q, QGroup g) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= g.n || g.status[r] != SJHIP_COL_OK) return;
+    const u64 h = g.hash[r];
+    u32 s = (u32)h & g.mask;
+    for (u32 step = 0; step <= g.mask; step++, s = (s + 1u) & g.mask) {
+        u32 *const cell = &g.table[s];
+        u32 cur = __hip_atomic_load(cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == GROUP_NONE) {
+            cur = atomicCAS(cell, GROUP_NONE, r);
+            if (cur == GROUP_NONE) break;  // claimed
+        }
+        if (cur == r) break;
+        if (g.hash[cur] == h && group_keys_equal(q, g, r, cur)) {
+            if (cur > r) (void)atomicMin(cell, r);
+            break;
+        }
+    }
+    g.slot[r] = s;
+}
+// (one lane per entry of the n + 1: entry n is 0, the scans leave the totals there)
+__global__ __launch_bounds__(256) void k_q_group_first(QView q, QGroup g) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    if (r > g.n) return;
+    const bool first = r < g.n && g.status[r] == SJHIP_COL_OK && g.table[g.slot[r]] == r;
+    g.flag[r] = first ? 1u : 0u;
+    if (g.len) g.len[r] = first ? q.tape[g.kidx[r] + 1] : 0ull;
+}
+// (the rows with a key are counted with the tile sums, as a third scanned array: one atomic per wave on one address took as long as
+// the table)
+__global__ __launch_bounds__(QT) void k_q_group_tile_sums(QGroup g, u32 m) {
+    __shared__ unsigned long long s_w[QT / 64];
+    tile_sums(arr_raw(g.flag), m, g.tiles_f);
+    if (g.len) tile_sums(arr_raw(g.len), m, g.tiles_l);
+    const u32 base = blockIdx.x * QTILE + threadIdx.x * QI;
+    unsigned long long ok = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < QI; k++)
+        if (base + k < g.n && g.status[base + k] == SJHIP_COL_OK) ok++;
+    (void)block_excl_sum(ok, s_w, (int)threadIdx.x, &tot);
+    if (threadIdx.x == 0) g.tiles_o[blockIdx.x] = tot;
+}
+__global__ __launch_bounds__(QT) void k_q_group_tile_apply(QGroup g, u32 m) {
+    tile_apply(arr_raw(g.flag), arr_raw(g.flag), m, g.tiles_f);
+    if (g.len) tile_apply(arr_raw(g.len), arr_raw(g.len), m, g.tiles_l);
+}
+// (sort_keys: the first pass's input -- the row's code, or `groups` for a row without a key)
+__global__ __launch_bounds__(256) void k_q_group_emit(QView q, QGroup g, GroupOut o, u32 groups, Arr<u32> sort_keys) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    u64 off = 0, len = 0, w = 0;
+    bool wide = false;
+    if (r < g.n) {
+        const u8 st = g.status[r];
+        u32 code = GROUP_NONE;
+        if (st == SJHIP_COL_OK) {
+            const u32 first = g.table[g.slot[r]];
+            code = g.flag[first];
+            if (first == r) {
+                o.first_row[code] = r;
+                if (g.key_kind == SJHIP_COL_INT) o.key_int[code] = g.kidx[r];
+                else {
+                    off = g.len[r];
+                    len = g.len[r + 1] - off;
+                    o.key_off[code] = off;
+                    w = q.tape[g.kidx[r]];
+                    wide = len > COL_SHORT;
+                    if (!wide && len) copy_bytes(arr_at(o.key_bytes, off, len), str_bytes(q, w, len), len, 0, 1);
+                }
+            }
+        }
+        o.codes[r] = code;
+        o.status[r] = st;
+        sort_keys[r] = code == GROUP_NONE ? groups : code;
+        if (r == 0 && g.key_kind != SJHIP_COL_INT) o.key_off[groups] = g.len[g.n];
+    }
+    wave_copy_strings(q, o.key_bytes, wide, off, len, w, lane);
+}
+// the lanes of the wave whose digit equals this lane's (valid lanes only; undefined on the others), by one ballot per digit bit
+__device__ __forceinline__ u64 group_match_digit(bool valid, u32 d) {
+    u64 m = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < GROUP_RADIX_BITS; b++) {
+        const bool bit = (d >> b) & 1u;
+        const u64 bb = __ballot(valid && bit);
+        m &= bit ? bb : ~bb;
+    }
+    return m;
+}
+__global__ __launch_bounds__(GROUP_SORT_THREADS) void k_q_group_hist(QSort s) {
+    __shared__ u32 s_h[GROUP_RADIX];
+    const int tid = threadIdx.x, lane = tid & 63;
+    s_h[tid] = 0;
+    __syncthreads();
+    for (int k = 0; k < GROUP_SORT_ROUNDS; k++) {
+        const u32 i = blockIdx.x * GROUP_SORT_TILE + k * GROUP_SORT_THREADS + tid;
+        const bool valid = i < s.n;
+        const u32 d = valid ? (s.keys_in[i] >> s.shift) & (GROUP_RADIX - 1) : 0u;
+        const u64 m = group_match_digit(valid, d);
+        if (valid && (m & ((1ull << lane) - 1)) == 0) atomicAdd(&s_h[d], (u32)__popcll(m));  // (LDS: the lowest lane of every digit)
+    }
+    __syncthreads();
+    s.hist[(u64)tid * gridDim.x + blockIdx.x] = s_h[tid];
+}
+__global__ __launch_bounds__(QT) void k_q_group_scan_sums(Arr<u32> a, u32 m, unsigned long long *tiles) { tile_sums(arr_raw(a), m, tiles); }
+__global__ __launch_bounds__(QT) void k_q_group_scan_apply(Arr<u32> a, u32 m, unsigned long long *tiles) {
+    tile_apply(arr_raw(a), arr_raw(a), m, tiles);
+}
+__global__ __launch_bounds__(GROUP_SORT_THREADS) void k_q_group_scatter(QSort s) {
+    __shared__ u32 s_base[GROUP_RADIX], s_cnt[GROUP_SORT_THREADS / 64][GROUP_RADIX];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    s_base[tid] = s.hist[(u64)tid * gridDim.x + blockIdx.x];  // where the tile's rows of digit `tid` begin
+    for (int k = 0; k < GROUP_SORT_ROUNDS; k++) {
+#pragma unroll
+        for (int w = 0; w < GROUP_SORT_THREADS / 64; w++) s_cnt[w][tid] = 0;
+        __syncthreads();
+        const u32 i = blockIdx.x * GROUP_SORT_TILE + k * GROUP_SORT_THREADS + tid;
+        const bool valid = i < s.n;
+        const u32 key = valid ? s.keys_in[i] : 0u, row = valid ? (s.rows_in ? s.rows_in[i] : i) : 0u;
+        const u32 d = (key >> s.shift) & (GROUP_RADIX - 1);
+        const u64 m = group_match_digit(valid, d);
+        const u32 rank = (u32)__popcll(m & ((1ull << lane) - 1));  // equal digits in front of this lane in its wave
+        if (valid && rank == 0) s_cnt[wave][d] = (u32)__popcll(m);
+        __syncthreads();
+        if (valid) {
+            u32 pos = s_base[d] + rank;
+            for (int w = 0; w < GROUP_SORT_THREADS / 64; w++)
+                if (w < wave) pos += s_cnt[w][d];
+            s.keys_out[pos] = key;
+            s.rows_out[pos] = row;
+        }
+        __syncthreads();
+        u32 add = 0;
+#pragma unroll
+        for (int w = 0; w < GROUP_SORT_THREADS / 64; w++) add += s_cnt[w][tid];
+        s_base[tid] += add;  // (thread `tid` alone touches entry `tid` until the next round's barrier)
+    }
+}
+// keys: the sorted codes; the first n_ok positions are the rows with a key.  off[g] = the position group g begins at, off[groups] = n_ok
+__global__ __launch_bounds__(256) void k_q_group_bounds(Arr<const u32> keys, u32 n_ok, u32 groups, Arr<u64> off) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_ok) return;
+    const u32 k = keys[i];
+    if (i == 0 || keys[i - 1] != k) off[k] = i;
+    if (i == 0) off[groups] = n_ok;
+}
+__global__ __launch_bounds__(256) void k_q_group_counts(Arr<const u64> off, u32 groups, Arr<u64> group_rows) {
+    const u32 g = blockIdx.x * 256 + threadIdx.x;
+    if (g < groups) group_rows[g] = off[g + 1] - off[g];
+}
+
 }  // namespace
 
 namespace sj {
@@ -1784,9 +2030,10 @@ struct AggWork {
     std::vector<AggItem *> items;   // per level (AGG_OWN: none)
     std::vector<u32> tiles;         // tiles of every level: rows -> AGG_TILE per tile -> two items per tile -> ...
 };
-static size_t agg_layout(Carve c, uint32_t n, size_t records, u32 mode, AggWork *w) {
+// (own_out false: the results lie elsewhere -- the grouping's are part of its product -- and the caller sets w->out)
+static size_t agg_layout(Carve c, uint32_t n, size_t records, u32 mode, AggWork *w, bool own_out = true) {
     const bool hist = mode == AGG_ONE, heads = mode == AGG_OFFS;
-    w->out = c.take<u64>(6 * records + (hist ? 6 : 0));
+    w->out = own_out ? c.take<u64>(6 * records + (hist ? 6 : 0)) : nullptr;
     w->head = heads ? c.take<u32>(n) : nullptr;
     w->items.clear();
     w->tiles.clear();
@@ -1804,11 +2051,14 @@ static size_t agg_layout(Carve c, uint32_t n, size_t records, u32 mode, AggWork 
     return c.used;
 }
 // the kernels of one part: n rows (> 0), `records` result slots; off: the row offsets of the selection (AGG_OFFS)
+// (perm: the grouping's row order -- position r of the n is row perm[r] of the view, `off` counts positions; null: position = row)
 static int agg_enqueue(sjhip_ctx *ctx, sjhip_ctx *part, const QView &q, const QPath &pth, int kind, u32 mode, uint32_t n, size_t records,
-                       const u64 *off, const AggWork &w) {
+                       const u64 *off, const AggWork &w, const u32 *perm = nullptr) {
     QAgg a;
     a.kind = kind;
     a.mode = mode;
+    a.perm = SJ_ARR(perm, perm ? n : 0, A_GROUP_SORT);
+    a.n_perm = n;
     a.head = SJ_ARR((const u32 *)w.head, n, A_AGG_HEAD);
     a.out = SJ_ARR(w.out, 6 * records, A_AGG_OUT);
     a.records = records;
@@ -2725,5 +2975,240 @@ int sjhip_filter_rows(sjhip_ctx *ctx, uint64_t *n_rows, uint64_t *skipped, size_
     hipLaunchKernelGGL(k_q_frows_copy, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, q, o, SJ_ARR((u64 *)ctx->d_qtape.p, words, A_FROWS_TAPE),
                        SJ_ARR((u8 *)ctx->d_qstrings.p, bytes, A_FROWS_STRINGS));
     HIPCHK(hipGetLastError(), "filter rows copy launch");
+    return SJHIP_OK;
+}
+
+// ---- groups --------------------------------------------------------------------------------------------------------------------------
+// sjhip_group_path works on the whole result of one context (a sharded one is refused: its dictionaries would have to be joined).
+// The work arrays of all its kernels (GroupWork) lie in d_kat, laid out once for the row count -- the group count is only known
+// after the first half, and a second reservation would move the arena --; the product (GroupOut, and the six aggregate arrays
+// behind it) lies in d_group, reserved when the scans have told the group count and the key bytes.  One host round trip in the
+// middle (the three totals), one wait at the end.
+struct GroupWork {
+    unsigned long long *totals;
+    QGroup g;
+    u32 *sort_keys[2], *sort_rows[2];
+    u32 *hist;
+    unsigned long long *hist_tiles;
+    u64 *off;  // [groups + 1] the group offsets in the sorted order (room for one group per row)
+    AggWork agg;
+};
+static u32 group_sort_tiles(u32 n) { return (n + GROUP_SORT_TILE - 1) / GROUP_SORT_TILE; }
+static size_t group_work_layout(Carve c, uint32_t n, int key_kind, bool value, GroupWork *w) {
+    const u64 cap = group_table_capacity(n);
+    const u32 tiles = tiles_of(n), hist_n = (u32)GROUP_RADIX * group_sort_tiles(n);
+    w->totals = c.take<unsigned long long>(32);
+    w->g.key_kind = key_kind;
+    w->g.n = n;
+    w->g.mask = (u32)(cap - 1);
+    w->g.totals = w->totals;
+    u8 *const status = c.take<u8>(n);
+    u64 *const kidx = c.take<u64>(n), *const hash = c.take<u64>(n);
+    u32 *const slot = c.take<u32>(n), *const table = c.take<u32>(cap), *const flag = c.take<u32>((size_t)n + 1);
+    u64 *const len = key_kind == SJHIP_COL_INT ? nullptr : c.take<u64>((size_t)n + 1);
+    w->g.status = SJ_ARR(status, n, A_GROUP_ROW);
+    w->g.kidx = SJ_ARR(kidx, n, A_GROUP_ROW);
+    w->g.hash = SJ_ARR(hash, n, A_GROUP_ROW);
+    w->g.slot = SJ_ARR(slot, n, A_GROUP_ROW);
+    w->g.table = SJ_ARR(table, cap, A_GROUP_TABLE);
+    w->g.flag = SJ_ARR(flag, (size_t)n + 1, A_GROUP_ROW);
+    w->g.len = SJ_ARR(len, len ? (size_t)n + 1 : 0, A_GROUP_ROW);
+    w->g.tiles_f = c.take<unsigned long long>(tiles);
+    w->g.tiles_l = c.take<unsigned long long>(tiles);
+    w->g.tiles_o = c.take<unsigned long long>(tiles);
+    for (int k = 0; k < 2; k++) w->sort_keys[k] = c.take<u32>(n), w->sort_rows[k] = c.take<u32>(n);
+    w->hist = c.take<u32>(hist_n);
+    w->hist_tiles = c.take<unsigned long long>((hist_n + QTILE - 1) / QTILE);
+    w->off = c.take<u64>((size_t)n + 1);
+    if (value) (void)(c.used = agg_layout(c, n, n, AGG_OFFS, &w->agg, false));
+    return c.used;
+}
+// The grouping in d_group: what the two fetches return, and nothing else.
+struct GroupArrays {
+    u64 *key_off, *key_int, *first_row, *group_rows, *agg;
+    u8 *key_bytes, *status;
+    u32 *codes;
+};
+static size_t group_layout(Carve c, const ResultState::Groups &z, GroupArrays *o) {
+    const bool ints = z.key_kind == SJHIP_COL_INT;
+    o->key_off = ints ? nullptr : c.take<u64>(z.groups + 1);
+    o->key_bytes = ints ? nullptr : c.take<u8>(z.key_bytes);
+    o->key_int = ints ? c.take<u64>(z.groups) : nullptr;
+    o->first_row = c.take<u64>(z.groups);
+    o->group_rows = c.take<u64>(z.groups);
+    o->codes = c.take<u32>(z.rows);
+    o->status = c.take<u8>(z.rows);
+    o->agg = z.val_kind == SJHIP_GROUP_NO_VALUE ? nullptr : c.take<u64>(6 * z.groups);
+    return c.used;
+}
+
+int sjhip_group_path(sjhip_ctx *ctx, const uint8_t *key_keys, const uint32_t *key_key_lens, uint32_t key_n_keys, int key_kind,
+                     const uint8_t *val_keys, const uint32_t *val_key_lens, uint32_t val_n_keys, int val_kind, size_t *rows, size_t *groups,
+                     size_t *key_bytes) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!rows || !groups || !key_bytes) {
+        ctx_set_error(ctx, "sjhip_group_path: a null size pointer");
+        return SJHIP_ERR_ARG;
+    }
+    if (key_kind != SJHIP_COL_STRING && key_kind != SJHIP_COL_INT) {
+        ctx_set_error(ctx, "sjhip_group_path: key kind %d is not SJHIP_COL_STRING or SJHIP_COL_INT", key_kind);
+        return SJHIP_ERR_ARG;
+    }
+    const bool value = val_kind != SJHIP_GROUP_NO_VALUE;
+    if (value && val_kind != SJHIP_COL_FLOAT && val_kind != SJHIP_COL_INT && val_kind != SJHIP_COL_UINT) {
+        ctx_set_error(ctx, "sjhip_group_path: value kind %d is not SJHIP_COL_FLOAT, SJHIP_COL_INT, SJHIP_COL_UINT or SJHIP_GROUP_NO_VALUE", val_kind);
+        return SJHIP_ERR_ARG;
+    }
+    QPath kpth, vpth;
+    size_t klen = 0, vlen = 0;
+    int rc = make_path(ctx, key_keys, key_key_lens, key_n_keys, &kpth, &klen, true);
+    if (rc) return rc;
+    if (!value) val_keys = nullptr, val_key_lens = nullptr, val_n_keys = 0;
+    rc = make_path(ctx, val_keys, val_key_lens, val_n_keys, &vpth, &vlen, true);
+    if (rc) return rc;
+    if (ctx->res.sharded()) {
+        ctx_set_error(ctx, "sjhip_group_path: the result is sharded (an ND message beyond one context's reach); the dictionaries of shards are not joined");
+        return SJHIP_ERR_ARG;
+    }
+    if (!ctx->res.whole()) return no_whole_result(ctx, "sjhip_group_path", "queries follow");
+    QView qk, qv;
+    rc = make_view(ctx, ctx, key_keys ? key_keys : &NO_VALUE, klen, &NO_VALUE, 0, &qk, true);
+    if (rc) return rc;
+    rc = make_view(ctx, ctx, val_keys ? val_keys : &NO_VALUE, vlen, &NO_VALUE, 0, &qv, true);
+    if (rc) return rc;
+    const uint32_t n = part_rows(ctx, ctx, true);
+    if (n > (1u << 30)) {
+        ctx_set_error(ctx, "sjhip_group_path: %u rows (at most 2^30)", n);
+        return SJHIP_ERR_TOOBIG;
+    }
+    // ---- nothing was touched up to here; from here on the last grouping is gone ----
+    ctx->res.groups.begin();
+    ResultState::Groups z;
+    z.rows = n, z.key_kind = key_kind, z.val_kind = val_kind;
+    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    if (n == 0) {
+        *rows = *groups = *key_bytes = 0;
+        return published(ctx, ctx->res.publish(&ResultState::groups, z));
+    }
+    GroupWork w;
+    rc = reserve_layout(ctx, ctx->d_kat, [&](Carve c) { return group_work_layout(c, n, key_kind, value, &w); });
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const dim3 per_row((n + 255) / 256), per_entry((n + 1u + 255) / 256), b256(256), one(1), wide(1024);
+    unsigned long long *const none = nullptr;
+    HIPCHK(hipMemsetAsync(w.totals, 0, 256, st), "group totals memset");
+    HIPCHK(hipMemsetAsync(arr_raw(w.g.table), 0xff, ((size_t)w.g.mask + 1) * 4, st), "group table memset");
+    hipLaunchKernelGGL(k_q_group_keys, per_row, b256, 0, st, qk, kpth, w.g);
+    hipLaunchKernelGGL(k_q_group_insert, per_row, b256, 0, st, qk, w.g);
+    hipLaunchKernelGGL(k_q_group_first, per_entry, b256, 0, st, qk, w.g);
+    const u32 tiles = tiles_of(n);
+    hipLaunchKernelGGL(k_q_group_tile_sums, dim3(tiles), dim3(QT), 0, st, w.g, n + 1u);
+    hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.g.tiles_f, w.g.len ? w.g.tiles_l : none, w.g.tiles_o, tiles, w.totals);
+    hipLaunchKernelGGL(k_q_group_tile_apply, dim3(tiles), dim3(QT), 0, st, w.g, n + 1u);
+    HIPCHK(hipGetLastError(), "group launch");
+    unsigned long long *const h = (unsigned long long *)(ctx->h_scratch + 512);
+    HIPCHK(hipMemcpyAsync(h, w.totals, 32, hipMemcpyDeviceToHost, st), "D2H group totals");
+    HIPCHK(hipStreamSynchronize(st), "group sync");
+    rc = query_bounds_check(ctx);
+    if (rc) return rc;
+    const u32 G = (u32)h[0], n_ok = (u32)h[2];
+    z.groups = G;
+    z.key_bytes = key_kind == SJHIP_COL_INT ? (size_t)8 * G : (size_t)h[1];
+    GroupArrays a;
+    rc = reserve_layout(ctx, ctx->d_group, [&](Carve c) { return group_layout(c, z, &a); });
+    if (rc) return rc;
+    GroupOut o;
+    o.key_off = SJ_ARR(a.key_off, a.key_off ? (size_t)G + 1 : 0, A_GROUP_OUT);
+    o.key_bytes = SJ_ARR(a.key_bytes, a.key_bytes ? z.key_bytes : 0, A_GROUP_KEYS);
+    o.key_int = SJ_ARR(a.key_int, a.key_int ? G : 0, A_GROUP_OUT);
+    o.first_row = SJ_ARR(a.first_row, G, A_GROUP_OUT);
+    o.group_rows = SJ_ARR(a.group_rows, G, A_GROUP_OUT);
+    o.codes = SJ_ARR(a.codes, n, A_GROUP_OUT);
+    o.status = SJ_ARR(a.status, n, A_GROUP_OUT);
+    u32 *const first_keys = w.sort_keys[0];
+    hipLaunchKernelGGL(k_q_group_emit, per_row, b256, 0, st, qk, w.g, o, G, SJ_ARR(first_keys, n, A_GROUP_SORT));
+    if (G) {
+        // the rows ordered by code, stably: after pass p the rows lie in sort_*[(p + 1) & 1]
+        const u32 passes = group_sort_passes(G), stiles = group_sort_tiles(n), hist_n = (u32)GROUP_RADIX * stiles;
+        const u32 htiles = (hist_n + QTILE - 1) / QTILE;
+        for (u32 p = 0; p < passes; p++) {
+            QSort s;
+            s.n = n, s.shift = p * GROUP_RADIX_BITS;
+            const u32 *const keys_in = w.sort_keys[p & 1], *const rows_in = p ? w.sort_rows[p & 1] : nullptr;
+            u32 *const keys_out = w.sort_keys[(p + 1) & 1], *const rows_out = w.sort_rows[(p + 1) & 1], *const hist = w.hist;
+            s.keys_in = SJ_ARR(keys_in, n, A_GROUP_SORT);
+            s.rows_in = SJ_ARR(rows_in, p ? n : 0, A_GROUP_SORT);
+            s.keys_out = SJ_ARR(keys_out, n, A_GROUP_SORT);
+            s.rows_out = SJ_ARR(rows_out, n, A_GROUP_SORT);
+            s.hist = SJ_ARR(hist, hist_n, A_GROUP_HIST);
+            hipLaunchKernelGGL(k_q_group_hist, dim3(stiles), dim3(GROUP_SORT_THREADS), 0, st, s);
+            hipLaunchKernelGGL(k_q_group_scan_sums, dim3(htiles), dim3(QT), 0, st, s.hist, hist_n, w.hist_tiles);
+            hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.hist_tiles, none, none, htiles, none);
+            hipLaunchKernelGGL(k_q_group_scan_apply, dim3(htiles), dim3(QT), 0, st, s.hist, hist_n, w.hist_tiles);
+            hipLaunchKernelGGL(k_q_group_scatter, dim3(stiles), dim3(GROUP_SORT_THREADS), 0, st, s);
+        }
+        const u32 *const skeys = w.sort_keys[passes & 1], *const srows = w.sort_rows[passes & 1];
+        hipLaunchKernelGGL(k_q_group_bounds, dim3((n_ok + 255) / 256), b256, 0, st, SJ_ARR(skeys, n, A_GROUP_SORT), n_ok, G,
+                           SJ_ARR(w.off, (size_t)G + 1, A_GROUP_OFF));
+        hipLaunchKernelGGL(k_q_group_counts, dim3((G + 255) / 256), b256, 0, st, SJ_ARR((const u64 *)w.off, (size_t)G + 1, A_GROUP_OFF), G,
+                           o.group_rows);
+        HIPCHK(hipGetLastError(), "group sort launch");
+        if (value) {  // the segmented reduction over the n_ok sorted rows: groups in the place of records
+            AggWork aw;
+            (void)agg_layout(Carve(), n_ok, G, AGG_OFFS, &aw, false);  // (the levels of n_ok rows; the arrays: those laid out for n)
+            aw.out = a.agg;
+            aw.head = w.agg.head;
+            for (size_t l = 0; l < aw.items.size(); l++) aw.items[l] = w.agg.items[l];
+            rc = agg_enqueue(ctx, ctx, qv, vpth, val_kind, AGG_OFFS, n_ok, G, w.off, aw, srows);
+            if (rc) return rc;
+        }
+    }
+    HIPCHK(hipGetLastError(), "group emit launch");
+    HIPCHK(hipStreamSynchronize(st), "group build sync");
+    rc = query_bounds_check(ctx);
+    if (rc) return rc;
+    *rows = n, *groups = G, *key_bytes = z.key_bytes;
+    return published(ctx, ctx->res.publish(&ResultState::groups, z));
+}
+
+static int no_grouping(sjhip_ctx *ctx, const char *call) {
+    ctx_set_error(ctx, "no grouping on the device (%s follows sjhip_group_path, with no parse in between)", call);
+    return SJHIP_ERR_ARG;
+}
+int sjhip_fetch_groups(sjhip_ctx *ctx, uint64_t *key_offsets, void *keys, uint64_t *first_row, uint64_t *group_rows, uint32_t *codes,
+                       uint8_t *status) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!ctx->res.groups.exists()) return no_grouping(ctx, "sjhip_fetch_groups");
+    const ResultState::Groups &z = ctx->res.groups.sizes();
+    const bool ints = z.key_kind == SJHIP_COL_INT;
+    if (key_offsets && !ints && z.groups == 0) key_offsets[0] = 0;
+    if (z.rows == 0) return SJHIP_OK;  // (nothing was launched, no arena was written)
+    GroupArrays a;
+    (void)group_layout(Carve(ctx->d_group.p), z, &a);
+    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    const struct { void *dst; const void *src; size_t bytes; } copies[] = {
+        {ints ? nullptr : key_offsets, a.key_off, (z.groups + 1) * 8}, {keys, ints ? (const void *)a.key_int : (const void *)a.key_bytes, z.key_bytes},
+        {first_row, a.first_row, z.groups * 8}, {group_rows, a.group_rows, z.groups * 8}, {codes, a.codes, z.rows * 4}, {status, a.status, z.rows}};
+    for (const auto &c : copies)
+        if (c.dst && c.bytes) HIPCHK(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, ctx->stream), "D2H groups");
+    HIPCHK(hipStreamSynchronize(ctx->stream), "group fetch sync");
+    return SJHIP_OK;
+}
+int sjhip_fetch_group_aggregates(sjhip_ctx *ctx, uint64_t *count, uint64_t *not_ok, void *sum, uint64_t *sum_hi, void *min, void *max) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!ctx->res.groups.exists()) return no_grouping(ctx, "sjhip_fetch_group_aggregates");
+    const ResultState::Groups &z = ctx->res.groups.sizes();
+    if (z.val_kind == SJHIP_GROUP_NO_VALUE) {
+        ctx_set_error(ctx, "sjhip_fetch_group_aggregates: the grouping has no value column (sjhip_group_path was called with SJHIP_GROUP_NO_VALUE)");
+        return SJHIP_ERR_ARG;
+    }
+    if (z.groups == 0) return SJHIP_OK;
+    GroupArrays a;
+    (void)group_layout(Carve(ctx->d_group.p), z, &a);
+    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    void *const dst[6] = {count, not_ok, sum, sum_hi, min, max};
+    for (int j = 0; j < 6; j++)
+        if (dst[j]) HIPCHK(hipMemcpyAsync(dst[j], a.agg + (size_t)j * z.groups, z.groups * 8, hipMemcpyDeviceToHost, ctx->stream), "D2H group aggregates");
+    HIPCHK(hipStreamSynchronize(ctx->stream), "group aggregates fetch sync");
     return SJHIP_OK;
 }

@@ -43,7 +43,11 @@ enum ArrId : uint32_t {
     A_MROWS_OFF, A_MROWS_OUT_OFF, A_MROWS_TEXT, A_MROWS_KF,
     // the aggregates (query.hip, sjhip_aggregate_path): the head flag of every row / the items a level of the segmented reduction
     // hands to the next / the per-record results
-    A_AGG_HEAD, A_AGG_ITEMS, A_AGG_OUT
+    A_AGG_HEAD, A_AGG_ITEMS, A_AGG_OUT,
+    // the grouping (query.hip, sjhip_group_path): the per-row work arrays (status, key element, hash, slot, first-row flag, key
+    // length) / the table of row numbers / the keys and rows of the sort and the sorted row order / its digit histograms / the group
+    // offsets / the per-group and per-row arrays of the product / the dictionary's key bytes
+    A_GROUP_ROW, A_GROUP_TABLE, A_GROUP_SORT, A_GROUP_HIST, A_GROUP_OFF, A_GROUP_OUT, A_GROUP_KEYS
 };
 
 #if defined(SJ_DEBUG_BOUNDS)

@@ -1,0 +1,65 @@
+// sj_group.h -- the host-and-device pieces of the grouping (query.hip, sjhip_group_path): the hash of a key and the equality of two
+// keys.  Plain C++ under SJ_HD, so the CPU build of a test program can run what the kernels run.
+//
+// The hash only places a key in the open-addressing table; the result of the grouping does not depend on it (groups are numbered
+// by first occurrence, equality is decided by the bytes).  Strings are hashed 8 bytes at a time -- a multiply-xorshift round per
+// word, the tail bytes gathered into one last word, the length mixed in -- and an int64 key is one finalising mix.
+#pragma once
+#include "sj_chunk.h"  // SJ_HD, u8 / u32 / u64
+
+namespace sj {
+
+static constexpr u32 GROUP_NONE = 0xffffffffu;  // SJHIP_GROUP_NONE, and the empty slot of the table
+// the radix sort of the rows by their code: GROUP_RADIX_BITS per pass, tiles of GROUP_SORT_TILE rows (GROUP_SORT_THREADS threads,
+// GROUP_SORT_ROUNDS rows each, taken in rounds so that the order inside a tile is the row order)
+static constexpr int GROUP_RADIX_BITS = 8, GROUP_RADIX = 1 << GROUP_RADIX_BITS;
+static constexpr int GROUP_SORT_THREADS = 256, GROUP_SORT_ROUNDS = 4, GROUP_SORT_TILE = GROUP_SORT_THREADS * GROUP_SORT_ROUNDS;
+
+SJ_HD u64 group_mix(u64 h) {  // (the finaliser of MurmurHash3: every input bit reaches every output bit)
+    h ^= h >> 33;
+    h *= 0xff51afd7ed558ccdull;
+    h ^= h >> 33;
+    h *= 0xc4ceb9fe1a85ec53ull;
+    h ^= h >> 33;
+    return h;
+}
+SJ_HD u64 group_hash_int(u64 x) { return group_mix(x ^ 0x9e3779b97f4a7c15ull); }
+SJ_HD u64 group_hash_bytes(const u8 *s, u64 len) {
+    u64 h = 0x9e3779b97f4a7c15ull ^ (len * 0xff51afd7ed558ccdull);
+    u64 k = 0;
+    for (; k + 8 <= len; k += 8) {
+        u64 w;
+        __builtin_memcpy(&w, s + k, 8);  // (no alignment is promised: a key lies anywhere in Strings.B or the message)
+        h = (h ^ group_mix(w)) * 0x9fb21c651e98df25ull;
+        h ^= h >> 29;
+    }
+    u64 w = 0;
+    for (u32 j = 0; k < len; k++, j += 8) w |= (u64)s[k] << j;
+    return group_mix(h ^ w);
+}
+SJ_HD bool group_bytes_equal(const u8 *a, const u8 *b, u64 len) {
+    u64 k = 0;
+    for (; k + 8 <= len; k += 8) {
+        u64 x, y;
+        __builtin_memcpy(&x, a + k, 8);
+        __builtin_memcpy(&y, b + k, 8);
+        if (x != y) return false;
+    }
+    for (; k < len; k++)
+        if (a[k] != b[k]) return false;
+    return true;
+}
+// the power-of-two capacity of the table of n rows: at least twice the rows, so that every probe sequence meets an empty slot
+SJ_HD u64 group_table_capacity(u64 n) {
+    u64 cap = 64;
+    while (cap < 2 * n) cap <<= 1;
+    return cap;
+}
+// the passes the sort of codes 0 .. groups takes (code `groups`: the rows without a key, which sort behind every group)
+SJ_HD u32 group_sort_passes(u64 groups) {
+    u32 p = 1;
+    while (p < 8 && (groups >> (GROUP_RADIX_BITS * p)) != 0) p++;
+    return p;
+}
+
+}  // namespace sj

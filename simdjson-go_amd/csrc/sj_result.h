@@ -10,7 +10,8 @@
 //   * the string column (d_col), the list column (d_list, numbers or strings) and the table (d_table, d_tabledata), independent of
 //     each other and of the tenant: one mechanism (Product) used three times -- and a fourth time for the row selection (d_rows:
 //     "the rows are the elements of the array at this path"), which the path queries and the other three products are built over
-//     while it exists and which they survive: what was built under a selection is materialised data.
+//     while it exists and which they survive: what was built under a selection is materialised data.  The grouping (d_group:
+//     sjhip_group_path) is the fifth use: built over the rows in force, independent of everything else once it exists.
 // The rule: a parse call, successful or not, drops the previous result and everything derived from it (begin_parse); so do
 // sjhip_deserialize, sjhip_ctx_trim and the stage-1-only calls (drop_result).  A product exists from its publish to the next
 // transition that drops it; a product is only published on a resident result, and a result of no tape words is no result.
@@ -31,6 +32,9 @@ public:
     struct ListColumn { size_t records = 0, elems = 0, bytes = 0; bool strings = false; };  // (numbers or strings: what was published)
     static constexpr int TABLE_COLS = 16;  // SJHIP_TABLE_MAX_COLS
     struct Rows { size_t records = 0, rows = 0; };  // the records the selection ran over, the rows it found
+    // the grouping (sjhip_group_path): the rows it ran over, its groups, the bytes of its dictionary, and what its fetches need to
+    // know: the kind of the keys and of the value column (-1: SJHIP_GROUP_NO_VALUE, no aggregates were built)
+    struct Groups { size_t rows = 0, groups = 0, key_bytes = 0; int key_kind = 0, val_kind = -1; };
     struct Table {  // what a fetch of one column needs: its kind, and the text bytes of a string column (0 for the other kinds)
         size_t records = 0;
         uint32_t n_cols = 0;
@@ -119,7 +123,8 @@ public:
     Product<ListColumn> list;
     Product<Table> table;
     Product<Rows> rows;  // the row selection (sjhip_select_rows; sjhip_select_records is its begin())
-    void drop_products() { column.begin(), list.begin(), table.begin(), rows.begin(); }  // (a stage-1-only call on a sharded result: api.hip)
+    Product<Groups> groups;  // the grouping (sjhip_group_path, d_group): materialised, independent of the selection it was built under
+    void drop_products() { column.begin(), list.begin(), table.begin(), rows.begin(), groups.begin(); }  // (a stage-1-only call on a sharded result: api.hip)
     template <typename S>
     bool publish(Product<S> ResultState::*product, const S &sizes) {  // publish(&ResultState::column, {records, bytes})
         if (!resident() && !sharded()) return false;

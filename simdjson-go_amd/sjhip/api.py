@@ -348,6 +348,50 @@ class Context:
         k = cnt.value
         return count[:k], not_ok[:k], total[:k], sum_hi[:k], lo[:k], hi[:k]
 
+    # ---- groups (include/sjhip.h: sjhip_group_path / sjhip_fetch_groups / sjhip_fetch_group_aggregates) --------------------------
+    GROUP_NONE, GROUP_NO_VALUE = 0xFFFFFFFF, -1
+    GROUP_SORT_TILE = 1024  # rows per tile of the device's sort by code (csrc/sj_group.h): the largest tile of the grouping's kernels
+
+    def group_path(self, key_path, key_kind, value_path=None, value_kind=None, fetch=True):
+        """"group by" on the device: the distinct keys at key_path (key_kind = COL_STRING: Iter.StringBytes, COL_INT: Iter.Int) of the
+        rows of the selection in force, in first-occurrence order, a code per row, and -- with value_kind = COL_FLOAT / COL_INT /
+        COL_UINT -- count, not_ok, sum, sum_hi, min and max of the column at value_path per key (an empty path: the row's own value).
+        -> Groups: rows, groups, key_bytes, keys (a list of bytes, or an int64 array), first_row, group_rows (uint64 arrays), codes
+        (uint32, GROUP_NONE where the row has no key), status (uint8, the key's COL_* status) and, when a value was given, the six
+        arrays in the shape aggregate_path_records returns; with fetch=False only the three sizes (the grouping stays on the device)"""
+        kblob, klens, kn = self._keys(key_path)
+        no_value = value_kind is None
+        vblob, vlens, vn = self._keys(() if no_value or value_path is None else value_path)
+        nr, ng, nb = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        self._check(_lib.lib().sjhip_group_path(self._h, kblob if kn else None, klens if kn else None, kn, int(key_kind),
+                                                vblob if vn else None, vlens if vn else None, vn,
+                                                self.GROUP_NO_VALUE if no_value else int(value_kind), C.byref(nr), C.byref(ng), C.byref(nb)))
+        g = Groups(nr.value, ng.value, nb.value, int(key_kind), None if no_value else int(value_kind))
+        return self.fetch_groups(g) if fetch else g
+
+    def fetch_groups(self, g):
+        """the arrays of the last group_path (g: what it returned with fetch=False) -> g, filled"""
+        L = _lib.lib()
+        g.first_row, g.group_rows = np.empty(g.groups, dtype=np.uint64), np.empty(g.groups, dtype=np.uint64)
+        g.codes, g.status = np.empty(g.rows, dtype=np.uint32), np.empty(g.rows, dtype=np.uint8)
+        ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+        if g.key_kind == self.COL_INT:
+            keys = np.empty(g.groups, dtype=np.int64)
+            self._check(L.sjhip_fetch_groups(self._h, None, ptr(keys), ptr(g.first_row), ptr(g.group_rows), ptr(g.codes), ptr(g.status)))
+            g.keys, g.key_offsets = keys, None
+        else:
+            off, data = np.empty(g.groups + 1, dtype=np.uint64), np.empty(g.key_bytes, dtype=np.uint8)
+            self._check(L.sjhip_fetch_groups(self._h, off.ctypes.data, ptr(data), ptr(g.first_row), ptr(g.group_rows), ptr(g.codes),
+                                             ptr(g.status)))
+            raw = data.tobytes()
+            g.key_offsets, g.keys = off, [raw[int(a):int(b)] for a, b in zip(off[:-1], off[1:])]
+        if g.value_kind is not None:
+            dt = self._COL_DTYPES[g.value_kind]
+            g.count, g.not_ok, g.sum_hi = (np.empty(g.groups, dtype=np.uint64) for _ in range(3))
+            g.sum, g.min, g.max = (np.empty(g.groups, dtype=dt) for _ in range(3))
+            self._check(L.sjhip_fetch_group_aggregates(self._h, ptr(g.count), ptr(g.not_ok), ptr(g.sum), ptr(g.sum_hi), ptr(g.min), ptr(g.max)))
+        return g
+
     def extract_path_strings(self, path, cvt=False, fetch=True):
         """Iter.FindElement(path...) then Iter.StringBytes (or StringCvt with cvt=True) on every record, built on the device.
         -> (offsets: uint64 array of records + 1, data: bytes, status: uint8 array) -- Arrow's large-string layout; with
@@ -581,6 +625,20 @@ class Aggregate:
 
     def __repr__(self):
         return f"Aggregate(rows={self.rows}, status={self.status}, sum={self.sum!r}, min={self.min!r}, max={self.max!r})"
+
+
+class Groups:
+    """what Context.group_path returns: the sizes of the grouping, and after the fetch its arrays (see group_path)"""
+
+    def __init__(self, rows, groups, key_bytes, key_kind, value_kind):
+        self.rows, self.groups, self.key_bytes, self.key_kind, self.value_kind = rows, groups, key_bytes, key_kind, value_kind
+
+    def aggregates(self):
+        """(count, not_ok, sum, sum_hi, min, max): the tuple aggregate_path_records returns, per group"""
+        return self.count, self.not_ok, self.sum, self.sum_hi, self.min, self.max
+
+    def __repr__(self):
+        return f"Groups(rows={self.rows}, groups={self.groups}, key_bytes={self.key_bytes})"
 
 
 class MultiContext:

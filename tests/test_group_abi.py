@@ -1,0 +1,42 @@
+"""CPU: libsjhip.so exports sjhip_group_path, sjhip_fetch_groups and sjhip_fetch_group_aggregates with the argument counts of the
+header, the two constants are in the header and in the Python mirror, and the tile constants of the checker (tests/group_walk.py)
+are the ones of the source."""
+import ctypes as C
+import os
+import re
+
+import __graft_entry__ as G
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "simdjson-go_amd", "csrc")
+HDR = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "sjhip.h")).read(), flags=re.S)
+
+
+def test_library_exports_the_group_calls():
+    L = C.CDLL(G.build_lib())
+    import sjhip
+    for name, n_args in (("sjhip_group_path", 12), ("sjhip_fetch_groups", 7), ("sjhip_fetch_group_aggregates", 7)):
+        assert hasattr(L, name) and hasattr(sjhip.lib(), name)
+        res, args = sjhip._lib.SYMBOLS[name]
+        assert res is C.c_int and len(args) == n_args
+        decl = re.search(r"\bint %s\((.*?)\);" % name, HDR, flags=re.S).group(1)
+        assert len(decl.split(",")) == n_args, decl
+    assert hasattr(sjhip.Context, "group_path") and hasattr(sjhip.Context, "fetch_groups")
+
+
+def test_constants():
+    import group_walk as GW
+    import sjhip
+    assert re.search(r"#define SJHIP_GROUP_NONE 0xffffffffu\b", HDR) and re.search(r"#define SJHIP_GROUP_NO_VALUE \(-1\)", HDR)
+    assert sjhip.Context.GROUP_NONE == GW.GROUP_NONE == 0xFFFFFFFF and sjhip.Context.GROUP_NO_VALUE == GW.GROUP_NO_VALUE == -1
+    assert sjhip.Context.COL_STRING == GW.COL_STRING == int(re.search(r"SJHIP_COL_STRING = (\d+)", HDR).group(1))
+    src = open(os.path.join(CSRC, "sj_group.h")).read()
+
+    def const(name, text=src):
+        return int(re.search(r"\b%s = (\d+)\b" % name, text).group(1))
+    assert const("GROUP_RADIX_BITS") == GW.GROUP_RADIX_BITS
+    assert (const("GROUP_SORT_THREADS"), const("GROUP_SORT_ROUNDS")) == (GW.GROUP_SORT_THREADS, GW.GROUP_SORT_ROUNDS)
+    assert re.search(r"GROUP_SORT_TILE = GROUP_SORT_THREADS \* GROUP_SORT_ROUNDS;", src)
+    assert sjhip.Context.GROUP_SORT_TILE == GW.GROUP_SORT_TILE == GW.GROUP_SORT_THREADS * GW.GROUP_SORT_ROUNDS
+    walk = open(os.path.join(CSRC, "sj_tapewalk.h")).read()
+    assert re.search(r"QT = TW_THREADS, QI = 4, QTILE = QT \* QI;", walk) and const("TW_THREADS", walk) * 4 == GW.QTILE
