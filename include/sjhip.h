@@ -447,6 +447,41 @@ int sjhip_select_records(sjhip_ctx *ctx);
 #define SJHIP_WHERE_NOT 1u
 int sjhip_where_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int op, const void *value,
                      size_t vlen, uint32_t flags, size_t *records, size_t *rows);
+/* Order rows ("order by ... limit k"): rank the rows of the selection in force (without one: the root value of every record) by a
+ * numeric key at a path and keep the first `limit` of them -- "the 10 most retweeted statuses" without the column, the host sort and
+ * the rows that are thrown away crossing PCIe.
+ *   key of a row   Iter.FindElement(path) on the row, converted by kind = SJHIP_COL_FLOAT / INT / UINT: exactly sjhip_extract_path's
+ *                  value and status byte (the amd64 results at 2^63 and 2^64 included).  n_keys == 0: the row's own value.
+ *                  SJHIP_COL_BOOL, the string kinds and unknown kinds are SJHIP_ERR_ARG and sjhip_last_error names the kind.
+ *   order          the rows whose status is SJHIP_COL_OK first, ascending by key -- INT as int64_t, UINT as uint64_t, FLOAT in the
+ *                  total order of the aggregates' min / max (-0.0 below +0.0) --, with SJHIP_ORDER_DESC descending; equal keys stay
+ *                  in row order in both directions (the sort is stable; 0.0 and an integer 0 tie under FLOAT).  The rows whose
+ *                  status is not OK come behind all OK rows, in row order, in both directions (NULLS LAST; a caller who does not
+ *                  want them filters first).  The rank of a row is its position in that order.  Any other flag bit: SJHIP_ERR_ARG.
+ *   limit          0, or at least the number of rows: every row is kept.  Otherwise the rows of rank < limit are kept; stability
+ *                  decides which of a run of equal keys crosses the limit.
+ * The call narrows the selection and builds a product.  The selection stays in document order: it is narrowed exactly as
+ * sjhip_where_path would narrow it for the predicate "rank < limit" -- records keep the kept rows they owned and their status bytes,
+ * without a selection one is created, successive sjhip_where_path and sjhip_order_path calls compose.  *records = the records,
+ * *rows = the rows kept.  The order of the kept rows is a product of its own:
+ *   sjhip_fetch_order   order[i] = the row number, IN THE SELECTION AS THIS CALL LEFT IT, of the row of rank i -- a permutation of
+ *                       0 .. rows - 1 that the host applies with one take to what it fetches for the kept rows (text rows through
+ *                       the offsets of sjhip_fetch_marshaled_rows); values[i] = that row's converted key (8 bytes each: a double,
+ *                       an int64_t or a uint64_t; 0 where not OK), sorted, the rows without an OK key at its tail; status[i] = that
+ *                       row's status byte.  Any destination may be NULL.  With limit = 0 this is a full ORDER BY.
+ * Lifetime: the order has its own device arena (counted by sjhip_ctx_device_bytes, freed by sjhip_ctx_trim) and lasts until the
+ * next parse or the next sjhip_order_path; it survives changes and drops of the selection and of every other product, and they
+ * survive it -- but its row numbers refer to the selection as this call left it, not to a later one.  Works after parses with and
+ * without SJHIP_FLAG_COPY_STRINGS.  Without rows nothing is launched, *rows = 0 and an empty order is published.
+ * Errors: SJHIP_ERR_ARG, with sjhip_last_error naming the reason and nothing touched (the selection and the previous order stay as
+ * they were): no result on the device, a bad path, a bad kind, unknown flag bits, a fetch without an order, and a sharded ND
+ * result ("... is sharded": the ranks of shards are not merged here).  More than 2^30 rows: SJHIP_ERR_TOOBIG.  A call that fails
+ * later (SJHIP_ERR_HIP) gives the selection up, as sjhip_where_path does, and leaves no order.  The cost is one walk of every row,
+ * and one sort pass of 8 key bits for every byte position in which the keys differ at all (counts below 2^20: three, not eight). */
+#define SJHIP_ORDER_DESC 1u
+int sjhip_order_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int kind,
+                     uint32_t flags, uint64_t limit, size_t *records, size_t *rows);
+int sjhip_fetch_order(sjhip_ctx *ctx, uint64_t *order /* [rows] */, void *values /* [rows], 8 B each */, uint8_t *status /* [rows] */);
 /* Filter rows: the rows of the selection in force -- sjhip_select_rows' or the one sjhip_where_path narrowed or created -- as a new
  * self-contained (Tape, Strings.B) on the device, one root per row: what a caller of ParseND reads with Iter.  With it,
  * sjhip_where_path followed by sjhip_filter_rows is sjhip_filter_where for every operator, for conjunctions and negation, for

@@ -799,8 +799,9 @@ extern "C" int sj_selftest_newlines_to_cr(void) {
 //   22 / 23 / 24 release_shared of the filtered / serialized / marshaled tenant   25 table.begin   26 publish table
 //   27 rows.begin (sjhip_select_records, and the first step of sjhip_select_rows)   28 publish rows
 //   29 groups.begin (the first step of sjhip_group_path behind its argument checks)   30 publish groups
+//   31 order.begin (the first step of sjhip_order_path behind its argument checks)   32 publish order
 // bits: 0 pending, 1 whole, 2 resident, 3 sharded, 4 key_flags, 5 packed, 6 filtered, 7 serialized, 8 marshaled, 9 column,
-// 10 list of numbers, 11 list of strings, 12 table, 13 rows, 14 groups.  Returns 0, or 1 + the index of an unknown code.
+// 10 list of numbers, 11 list of strings, 12 table, 13 rows, 14 groups, 15 order.  Returns 0, or 1 + the index of an unknown code.
 #include "sj_result.h"
 extern "C" int sj_selftest_result_state(const uint8_t *ops, size_t n, uint32_t *bits_out) {
     sj::ResultState s;
@@ -827,14 +828,26 @@ extern "C" int sj_selftest_result_state(const uint8_t *ops, size_t n, uint32_t *
         else if (op == 28) s.publish(&sj::ResultState::rows, {1, 1});
         else if (op == 29) s.groups.begin();
         else if (op == 30) s.publish(&sj::ResultState::groups, {1, 1, 1, 4, -1});
+        else if (op == 31) s.order.begin();
+        else if (op == 32) s.publish(&sj::ResultState::order, {1, 1});
         else return 1 + (int)k;
         bits_out[k] = (uint32_t)s.pending() | (uint32_t)s.whole() << 1 | (uint32_t)s.resident() << 2 | (uint32_t)s.sharded() << 3 |
                       (uint32_t)s.key_flags() << 4 | (uint32_t)s.packed() << 5 | (uint32_t)s.filtered() << 6 |
                       (uint32_t)s.serialized() << 7 | (uint32_t)s.marshaled() << 8 | (uint32_t)s.column.exists() << 9 |
                       (uint32_t)s.list_of(false) << 10 | (uint32_t)s.list_of(true) << 11 | (uint32_t)s.table.exists() << 12 |
-                      (uint32_t)s.rows.exists() << 13 | (uint32_t)s.groups.exists() << 14;
+                      (uint32_t)s.rows.exists() << 13 | (uint32_t)s.groups.exists() << 14 |
+                      (uint32_t)s.order.exists() << 15;
     }
     return 0;
+}
+
+// sj_order.h: the sort key of a number and the pass plan of the sort, as the kernels of sjhip_order_path run them
+#include "sj_order.h"
+extern "C" uint64_t sj_selftest_agg_key(uint64_t bits, int kind) { return sj::agg_key(bits, kind); }
+extern "C" uint64_t sj_selftest_agg_unkey(uint64_t key, int kind) { return sj::agg_unkey(key, kind); }
+extern "C" uint32_t sj_selftest_order_pass_mask(uint64_t and_, uint64_t or_) { return sj::order_pass_mask(and_, or_); }
+extern "C" void sj_selftest_order_geometry(int *out4) {
+    out4[0] = sj::ORDER_RADIX_BITS, out4[1] = sj::ORDER_SORT_THREADS, out4[2] = sj::ORDER_SORT_ROUNDS, out4[3] = sj::ORDER_SORT_TILE;
 }
 
 // sj_table.h / sj_tablewalk.h: the plan of a table and its one-walk evaluation, as the kernel k_q_table_walk runs them.

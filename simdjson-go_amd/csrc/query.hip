@@ -26,6 +26,7 @@
 #include "sj_bounds.h"
 #include "sj_ftoa.h"
 #include "sj_group.h"
+#include "sj_order.h"
 #include "sj_stage2.h"
 #include "sj_tapewalk.h"
 #include "sj_tablewalk.h"
@@ -462,7 +463,8 @@ __global__ __launch_bounds__(256) void k_q_extract(QView q, QPath pth, int kind,
 // (INT: the sign bit flipped; FLOAT: all bits of a negative value flipped, the sign bit of the others: -0.0 below +0.0).
 // The status histogram of the total is six ballots per wave and one integer atomic per status that occurs in it.
 static constexpr int AGG_TILE = 256;
-static constexpr u64 AGG_SIGN = 0x8000000000000000ull;
+static_assert(ORDER_KIND_FLOAT == SJHIP_COL_FLOAT && ORDER_KIND_INT == SJHIP_COL_INT && ORDER_KIND_UINT == SJHIP_COL_UINT,
+              "agg_key / agg_unkey (sj_order.h) take the column kinds");
 enum : u32 { AGG_ONE = 0, AGG_OWN = 1, AGG_OFFS = 2 };        // QAgg::mode
 enum : u32 { AGG_VALID = 1, AGG_HEAD = 2, AGG_END = 4 };      // AggItem::flags (0: no item)
 struct AggVal {
@@ -489,16 +491,6 @@ struct QAgg {
     u32 n_perm;
 };
 __device__ __forceinline__ AggVal agg_identity(bool flt) { return {0u, 0u, flt ? AGG_SIGN : 0ull, 0ull, ~0ull, 0ull}; }
-__device__ __forceinline__ u64 agg_key(u64 x, int kind) {
-    if (kind == SJHIP_COL_UINT) return x;
-    if (kind == SJHIP_COL_INT) return x ^ AGG_SIGN;
-    return (x >> 63) ? ~x : x ^ AGG_SIGN;
-}
-__device__ __forceinline__ u64 agg_unkey(u64 k, int kind) {
-    if (kind == SJHIP_COL_UINT) return k;
-    if (kind == SJHIP_COL_INT) return k ^ AGG_SIGN;
-    return (k >> 63) ? k ^ AGG_SIGN : ~k;
-}
 // a: the rows in front, b: the rows behind
 __device__ __forceinline__ AggVal agg_join(const AggVal &a, const AggVal &b, bool flt) {
     AggVal r;
@@ -1622,6 +1614,189 @@ __global__ __launch_bounds__(256) void k_q_group_counts(Arr<const u64> off, u32 
     if (g < groups) group_rows[g] = off[g + 1] - off[g];
 }
 
+// ---- order: the rows ranked by a numeric key at a path, the first `limit` of them kept (sjhip_order_path) ----------------------------
+// The rank of a row is its position in: the rows with an OK key ascending by key (descending: by the complement of the key), equal
+// keys in row order, then the rows without one in row order.  The selection is narrowed to the rows of rank < limit as a row
+// predicate would narrow it (the second half of where_build: k_q_where_apply, k_q_where_offsets), so it stays in document order;
+// the order itself is a product of its own (d_order).
+//   k_q_order_keys     per tile of QTILE rows, one lane per row and round: path, conversion, status (k_q_group_keys' walk); the
+//                      sort key agg_key(x, kind), complemented for a descending order; and the tile's OK rows, the AND and the OR
+//                      of their keys -- wave reductions, the four waves joined through LDS, one plain store per tile and value
+//   scan, k_q_order_fold  the exclusive prefix of the tiles' OK rows (k_tw_scan_sums: its total is n_ok) and the AND / OR of all
+//                      keys, which the host reads in its one copy: a digit whose bits are equal in both takes no pass (sj_order.h)
+//   k_q_order_compact  the OK rows to the front in row order -- (key, row) pairs, the input of the first pass --, the others behind
+//                      them in row order, where they stay: they never enter the sort
+//   hist/scan/scatter  the stable least-significant-digit radix sort of the grouping with 64-bit keys, over the planned digits only
+//   k_q_order_flag     the row at sorted position p is kept iff p < limit -> the flag of a row predicate; k_q_order_flag_sums its
+//                      tile sums
+//   k_q_order_emit     behind the narrowing: order[p] = pre[row(p)], the row's number in the new selection; its value and status
+struct QOrder {
+    int kind;
+    u32 n, desc;
+    Arr<u64> key;                                          // [n] the sort key of the row (0 where the status is not OK)
+    Arr<u8> status;                                        // [n]
+    unsigned long long *tiles_ok, *tiles_and, *tiles_or;   // [tiles] OK rows of the tile -> their exclusive prefix; AND / OR of their keys
+    unsigned long long *totals;                            // [0] the OK rows, [1] the AND, [2] the OR of all their keys
+};
+struct QOrderSort {
+    u32 n, shift;  // n: the rows that are sorted (those with an OK key)
+    Arr<const u64> keys_in;
+    Arr<const u32> rows_in;
+    Arr<u64> keys_out;
+    Arr<u32> rows_out;
+    Arr<u32> hist;  // [ORDER_RADIX * tiles] digit-major: entry d * tiles + t
+};
+static_assert(ORDER_RADIX == ORDER_SORT_THREADS, "thread d of a sort block owns digit d");
+static_assert(ORDER_RADIX_BITS == GROUP_RADIX_BITS, "group_match_digit ballots GROUP_RADIX_BITS bits of a digit");
+__global__ __launch_bounds__(QT) void k_q_order_keys(QView q, QPath pth, QOrder o) {
+    __shared__ unsigned long long s_w[3][QT / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    u64 all = ~0ull, any = 0, ok = 0;
+#pragma unroll 1
+    for (int k = 0; k < QI; k++) {
+        const u32 r = blockIdx.x * QTILE + k * QT + tid;
+        if (r >= o.n) break;
+        const u64 v = pth.n ? record_find_path(q, pth, r) : row_value(q, r);  // (no keys: the row's own value)
+        u64 x = 0, key = 0;
+        const int st = v < SJHIP_PATH_NOT_OBJECT ? element_to(q, v, o.kind, &x) : path_status(v);
+        if (st == SJHIP_COL_OK) {
+            key = agg_key(x, o.kind);
+            if (o.desc) key = ~key;
+            all &= key;
+            any |= key;
+            ok++;
+        }
+        o.key[r] = key;
+        o.status[r] = (u8)st;
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+        all &= (u64)__shfl_xor((long long)all, s, 64);
+        any |= (u64)__shfl_xor((long long)any, s, 64);
+    }
+    ok = wave_sum(ok);
+    if (lane == 0) s_w[0][wave] = ok, s_w[1][wave] = all, s_w[2][wave] = any;
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < QT / 64; w++) ok += s_w[0][w], all &= s_w[1][w], any |= s_w[2][w];
+        o.tiles_ok[blockIdx.x] = ok;
+        o.tiles_and[blockIdx.x] = all;
+        o.tiles_or[blockIdx.x] = any;
+    }
+}
+// one block: the AND and the OR over the tiles (a tile without an OK row holds the identities)
+__global__ __launch_bounds__(256) void k_q_order_fold(QOrder o, u32 tiles) {
+    __shared__ unsigned long long s_w[2][256 / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    u64 all = ~0ull, any = 0;
+    for (u32 t = tid; t < tiles; t += 256) all &= o.tiles_and[t], any |= o.tiles_or[t];
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+        all &= (u64)__shfl_xor((long long)all, s, 64);
+        any |= (u64)__shfl_xor((long long)any, s, 64);
+    }
+    if (lane == 0) s_w[0][wave] = all, s_w[1][wave] = any;
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 256 / 64; w++) all &= s_w[0][w], any |= s_w[1][w];
+        o.totals[1] = all;
+        o.totals[2] = any;
+    }
+}
+// (tiles_ok has been scanned and totals[0] holds the OK rows.  The rows without a key go to both row buffers: whichever the last
+// pass writes, they lie behind it)
+__global__ __launch_bounds__(QT) void k_q_order_compact(QOrder o, Arr<u64> keys, Arr<u32> rows0, Arr<u32> rows1) {
+    __shared__ unsigned long long s_w[QT / 64];
+    const u32 n = o.n, base = blockIdx.x * QTILE + threadIdx.x * QI, n_ok = (u32)o.totals[0];
+    u32 f[QI], sum = 0;
+#pragma unroll
+    for (int k = 0; k < QI; k++) {
+        f[k] = base + k < n && o.status[base + k] == SJHIP_COL_OK ? 1u : 0u;
+        sum += f[k];
+    }
+    u32 at = (u32)(o.tiles_ok[blockIdx.x] + block_excl_sum(sum, s_w, (int)threadIdx.x, nullptr));
+#pragma unroll
+    for (int k = 0; k < QI; k++) {
+        const u32 i = base + k;
+        if (i >= n) break;
+        if (f[k]) {
+            keys[at] = o.key[i];
+            rows0[at] = i;
+            at++;
+        } else {
+            const u32 p = n_ok + (i - at);  // (i - at: the rows without a key in front of row i)
+            rows0[p] = i;
+            rows1[p] = i;
+        }
+    }
+}
+__global__ __launch_bounds__(ORDER_SORT_THREADS) void k_q_order_hist(QOrderSort s) {
+    __shared__ u32 s_h[ORDER_RADIX];
+    const int tid = threadIdx.x, lane = tid & 63;
+    s_h[tid] = 0;
+    __syncthreads();
+    for (int k = 0; k < ORDER_SORT_ROUNDS; k++) {
+        const u32 i = blockIdx.x * ORDER_SORT_TILE + k * ORDER_SORT_THREADS + tid;
+        const bool valid = i < s.n;
+        const u32 d = valid ? (u32)(s.keys_in[i] >> s.shift) & (ORDER_RADIX - 1) : 0u;
+        const u64 m = group_match_digit(valid, d);
+        if (valid && (m & ((1ull << lane) - 1)) == 0) atomicAdd(&s_h[d], (u32)__popcll(m));  // (LDS: the lowest lane of every digit)
+    }
+    __syncthreads();
+    s.hist[(u64)tid * gridDim.x + blockIdx.x] = s_h[tid];
+}
+__global__ __launch_bounds__(ORDER_SORT_THREADS) void k_q_order_scatter(QOrderSort s) {
+    __shared__ u32 s_base[ORDER_RADIX], s_cnt[ORDER_SORT_THREADS / 64][ORDER_RADIX];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    s_base[tid] = s.hist[(u64)tid * gridDim.x + blockIdx.x];  // where the tile's rows of digit `tid` begin
+    for (int k = 0; k < ORDER_SORT_ROUNDS; k++) {
+#pragma unroll
+        for (int w = 0; w < ORDER_SORT_THREADS / 64; w++) s_cnt[w][tid] = 0;
+        __syncthreads();
+        const u32 i = blockIdx.x * ORDER_SORT_TILE + k * ORDER_SORT_THREADS + tid;
+        const bool valid = i < s.n;
+        const u64 key = valid ? s.keys_in[i] : 0ull;
+        const u32 row = valid ? s.rows_in[i] : 0u;
+        const u32 d = (u32)(key >> s.shift) & (ORDER_RADIX - 1);
+        const u64 m = group_match_digit(valid, d);
+        const u32 rank = (u32)__popcll(m & ((1ull << lane) - 1));  // equal digits in front of this lane in its wave
+        if (valid && rank == 0) s_cnt[wave][d] = (u32)__popcll(m);
+        __syncthreads();
+        if (valid) {
+            u32 pos = s_base[d] + rank;
+            for (int w = 0; w < ORDER_SORT_THREADS / 64; w++)
+                if (w < wave) pos += s_cnt[w][d];
+            s.keys_out[pos] = key;
+            s.rows_out[pos] = row;
+        }
+        __syncthreads();
+        u32 add = 0;
+#pragma unroll
+        for (int w = 0; w < ORDER_SORT_THREADS / 64; w++) add += s_cnt[w][tid];
+        s_base[tid] += add;  // (thread `tid` alone touches entry `tid` until the next round's barrier)
+    }
+}
+// rows: the rows in rank order.  One lane per rank: every row is written once
+__global__ __launch_bounds__(256) void k_q_order_flag(Arr<const u32> rows, u32 n, u64 limit, Arr<u8> flag) {
+    const u32 p = blockIdx.x * 256 + threadIdx.x;
+    if (p < n) flag[rows[p]] = p < limit ? 1 : 0;
+}
+__global__ __launch_bounds__(QT) void k_q_order_flag_sums(Arr<u8> flag, u32 n, unsigned long long *tiles) { tile_sums(arr_raw(flag), n, tiles); }
+struct OrderOut {  // the product (d_order), see order_layout
+    Arr<u64> order, values;  // [kept]
+    Arr<u8> status;          // [kept]
+};
+__global__ __launch_bounds__(256) void k_q_order_emit(QOrder o, Arr<const u32> rows, Arr<const u32> pre, u32 kept, OrderOut out) {
+    const u32 p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= kept) return;
+    const u32 row = rows[p];
+    const u8 st = o.status[row];
+    const u64 key = o.key[row];
+    out.order[p] = pre[row];
+    out.values[p] = st == SJHIP_COL_OK ? agg_unkey(o.desc ? ~key : key, o.kind) : 0ull;
+    out.status[p] = st;
+}
+
 }  // namespace
 
 namespace sj {
@@ -2093,12 +2268,8 @@ static int agg_args(sjhip_ctx *ctx, const char *who, const uint8_t *keys, const 
     const int rc = make_path(ctx, keys, key_lens, n_keys, pth, klen, true);
     return rc ? rc : query_parts(ctx, keys ? keys : &NO_VALUE, *klen, &NO_VALUE, 0, parts);
 }
-// unsigned order of the keys = the order of the kind (the device's agg_key)
-static u64 agg_host_key(u64 x, int kind) {
-    if (kind == SJHIP_COL_UINT) return x;
-    if (kind == SJHIP_COL_INT) return x ^ AGG_SIGN;
-    return (x >> 63) ? ~x : x ^ AGG_SIGN;
-}
+// unsigned order of the keys = the order of the kind (the device's agg_key, sj_order.h)
+static u64 agg_host_key(u64 x, int kind) { return agg_key(x, kind); }
 
 int sjhip_aggregate_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int kind, sjhip_agg *out) {
     QPath pth;
@@ -2788,49 +2959,30 @@ int sjhip_select_records(sjhip_ctx *ctx) {
 // and index into d_rows behind the kernels, which is reserved here only when there was no selection (a narrowed one fits where
 // the old one lies, and rows_layout keeps offsets and statuses in their place).
 struct WhereNew { u64 *index, *off; u8 *status; };  // the new selection of a part, in its d_kat
-static int where_build(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, const uint8_t *keys, size_t klen, const uint8_t *val,
-                       size_t vlen, const QPath &pth, int op, u64 want, u32 negate, size_t *records, size_t *rows) {
+// The work arrays of a narrowing over the n rows of a part, in the part's d_kat: the totals of the scan in front, the tile sums, the
+// flags and their prefix, and the new selection.  (sjhip_order_path lays them out behind its own.)
+static size_t where_layout(Carve c, const sjhip_ctx *part, uint32_t n, QWhere *w, WhereNew *nw, unsigned long long **totals) {
+    const size_t recs = (size_t)part->q_records + 1u;
+    *totals = c.take<unsigned long long>(32);
+    w->tiles = c.take<unsigned long long>((n + QTILE - 1) / QTILE);
+    u8 *const flag = c.take<u8>(n);
+    u32 *const pre = c.take<u32>(n);
+    w->flag = SJ_ARR(flag, n, A_WHERE_FLAG);
+    w->pre = SJ_ARR(pre, n, A_WHERE_PRE);
+    nw->index = c.take<u64>(n);  // (room for every row: the count is not known yet)
+    nw->off = c.take<u64>(recs + 1);
+    nw->status = c.take<u8>(recs);
+    return c.used;
+}
+// The second half of a narrowing, whoever marked: work[k].flag holds the keep flag of every row of part k, work[k].tiles the
+// exclusive prefix of the kept rows per tile and kept[k] their number (all of a part without rows: untouched, 0).  The rows are
+// compacted into fresh[k], copied over the selection in d_rows, and the new selection is published.  (Nothing of d_kat is asked
+// for: the arrays stay where the caller laid them out.)
+static int where_narrow(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, const uint8_t *keys, size_t klen, const uint8_t *val,
+                        size_t vlen, const std::vector<QWhere> &work, const std::vector<WhereNew> &fresh, const std::vector<size_t> &kept,
+                        size_t *records, size_t *rows) {
     const bool sel = selected(ctx, true);
-    std::vector<QWhere> work(parts.size());
-    std::vector<WhereNew> fresh(parts.size());
-    std::vector<size_t> kept(parts.size(), 0);
-    auto layout = [](Carve c, const sjhip_ctx *part, uint32_t n, QWhere *w, WhereNew *nw, unsigned long long **totals) {
-        const size_t recs = (size_t)part->q_records + 1u;
-        *totals = c.take<unsigned long long>(32);
-        w->tiles = c.take<unsigned long long>((n + QTILE - 1) / QTILE);
-        u8 *const flag = c.take<u8>(n);
-        u32 *const pre = c.take<u32>(n);
-        w->flag = SJ_ARR(flag, n, A_WHERE_FLAG);
-        w->pre = SJ_ARR(pre, n, A_WHERE_PRE);
-        nw->index = c.take<u64>(n);  // (room for every row: the count is not known yet)
-        nw->off = c.take<u64>(recs + 1);
-        nw->status = c.take<u8>(recs);
-        return c.used;
-    };
-    int rc = query_over_parts(ctx, parts, keys, klen, val, vlen, true, "row predicate sync",
-        [&](const sjhip_ctx *part, uint32_t n) {
-            QWhere w;
-            WhereNew nw;
-            unsigned long long *totals;
-            return layout(Carve(), part, n, &w, &nw, &totals) + 64;
-        },
-        [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
-            unsigned long long *totals, *const none = nullptr;
-            (void)layout(Carve(part->d_kat.p), part, n, &work[k], &fresh[k], &totals);
-            const u32 tiles = (n + QTILE - 1) / QTILE;
-            HIPCHK(hipMemsetAsync(totals, 0, 256, part->stream), "row predicate totals memset");
-            HIPCHK(hipMemsetAsync(work[k].tiles, 0, (size_t)tiles * 8, part->stream), "row predicate tiles memset");
-            hipLaunchKernelGGL(k_q_where_mark, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, pth, op, want, negate, work[k]);
-            hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, part->stream, work[k].tiles, none, none, tiles, totals);
-            HIPCHK(hipGetLastError(), "row predicate launch");
-            HIPCHK(hipMemcpyAsync(part->h_scratch + 512, totals, 8, hipMemcpyDeviceToHost, part->stream), "D2H kept rows");
-            return SJHIP_OK;
-        },
-        [&](size_t k, sjhip_ctx *part) {
-            kept[k] = part_rows(ctx, part, true) ? (size_t)*(const unsigned long long *)(part->h_scratch + 512) : 0;
-        });
-    if (rc) return rc;
-    rc = query_over_parts(ctx, parts, keys, klen, val, vlen, true, "row predicate gather sync", [](const sjhip_ctx *, uint32_t) { return (size_t)0; },
+    int rc = query_over_parts(ctx, parts, keys, klen, val, vlen, true, "row predicate gather sync", [](const sjhip_ctx *, uint32_t) { return (size_t)0; },
         [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
             const size_t recs = (size_t)part->q_records + 1u;
             RowsOut old, o;
@@ -2871,6 +3023,36 @@ static int where_build(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, co
     if (ctx->res.sharded()) ok &= ctx->res.publish(&ResultState::rows, total);
     *records = total.records, *rows = total.rows;
     return published(ctx, ok);
+}
+// sjhip_where_path's first half: the predicate marks, the kept rows are counted; then the narrowing above.
+static int where_build(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, const uint8_t *keys, size_t klen, const uint8_t *val,
+                       size_t vlen, const QPath &pth, int op, u64 want, u32 negate, size_t *records, size_t *rows) {
+    std::vector<QWhere> work(parts.size());
+    std::vector<WhereNew> fresh(parts.size());
+    std::vector<size_t> kept(parts.size(), 0);
+    const int rc = query_over_parts(ctx, parts, keys, klen, val, vlen, true, "row predicate sync",
+        [&](const sjhip_ctx *part, uint32_t n) {
+            QWhere w;
+            WhereNew nw;
+            unsigned long long *totals;
+            return where_layout(Carve(), part, n, &w, &nw, &totals) + 64;
+        },
+        [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
+            unsigned long long *totals, *const none = nullptr;
+            (void)where_layout(Carve(part->d_kat.p), part, n, &work[k], &fresh[k], &totals);
+            const u32 tiles = (n + QTILE - 1) / QTILE;
+            HIPCHK(hipMemsetAsync(totals, 0, 256, part->stream), "row predicate totals memset");
+            HIPCHK(hipMemsetAsync(work[k].tiles, 0, (size_t)tiles * 8, part->stream), "row predicate tiles memset");
+            hipLaunchKernelGGL(k_q_where_mark, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, pth, op, want, negate, work[k]);
+            hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, part->stream, work[k].tiles, none, none, tiles, totals);
+            HIPCHK(hipGetLastError(), "row predicate launch");
+            HIPCHK(hipMemcpyAsync(part->h_scratch + 512, totals, 8, hipMemcpyDeviceToHost, part->stream), "D2H kept rows");
+            return SJHIP_OK;
+        },
+        [&](size_t k, sjhip_ctx *part) {
+            kept[k] = part_rows(ctx, part, true) ? (size_t)*(const unsigned long long *)(part->h_scratch + 512) : 0;
+        });
+    return rc ? rc : where_narrow(ctx, parts, keys, klen, val, vlen, work, fresh, kept, records, rows);
 }
 
 int sjhip_where_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int op, const void *value,
@@ -3210,5 +3392,199 @@ int sjhip_fetch_group_aggregates(sjhip_ctx *ctx, uint64_t *count, uint64_t *not_
     for (int j = 0; j < 6; j++)
         if (dst[j]) HIPCHK(hipMemcpyAsync(dst[j], a.agg + (size_t)j * z.groups, z.groups * 8, hipMemcpyDeviceToHost, ctx->stream), "D2H group aggregates");
     HIPCHK(hipStreamSynchronize(ctx->stream), "group aggregates fetch sync");
+    return SJHIP_OK;
+}
+
+// ---- order ---------------------------------------------------------------------------------------------------------------------------
+// sjhip_order_path works on the whole result of one context (a sharded one is refused: the ranks of shards would have to be merged).
+// The work arrays of all its kernels (OrderWork) lie in d_kat, laid out once for the row count, the arrays of the narrowing
+// (where_layout) behind them; the product (OrderOut) lies in d_order, reserved when the narrowing is through.  One host round trip
+// in the middle -- the OK rows, the AND and the OR of the keys: the pass plan --, the wait of the narrowing, one wait at the end.
+struct OrderWork {
+    unsigned long long *totals;
+    QOrder o;
+    u64 *sort_keys[2];
+    u32 *sort_rows[2];
+    u32 *hist;
+    unsigned long long *hist_tiles;
+    QWhere w;
+    WhereNew nw;
+    unsigned long long *w_totals;
+};
+static u32 order_sort_tiles(u32 n) { return (n + ORDER_SORT_TILE - 1) / ORDER_SORT_TILE; }
+static size_t order_work_layout(Carve c, const sjhip_ctx *ctx, uint32_t n, int kind, u32 desc, OrderWork *w) {
+    const u32 tiles = (n + QTILE - 1) / QTILE, hist_n = (u32)ORDER_RADIX * order_sort_tiles(n);
+    w->totals = c.take<unsigned long long>(32);
+    w->o.kind = kind;
+    w->o.n = n;
+    w->o.desc = desc;
+    w->o.totals = w->totals;
+    u64 *const key = c.take<u64>(n);
+    u8 *const status = c.take<u8>(n);
+    w->o.key = SJ_ARR(key, n, A_ORDER_ROW);
+    w->o.status = SJ_ARR(status, n, A_ORDER_ROW);
+    w->o.tiles_ok = c.take<unsigned long long>(tiles);
+    w->o.tiles_and = c.take<unsigned long long>(tiles);
+    w->o.tiles_or = c.take<unsigned long long>(tiles);
+    for (int k = 0; k < 2; k++) w->sort_keys[k] = c.take<u64>(n), w->sort_rows[k] = c.take<u32>(n);
+    w->hist = c.take<u32>(hist_n);
+    w->hist_tiles = c.take<unsigned long long>((hist_n + QTILE - 1) / QTILE);
+    (void)(c.used = where_layout(c, ctx, n, &w->w, &w->nw, &w->w_totals));
+    return c.used;
+}
+// The order in d_order: what the fetch returns, and nothing else.
+struct OrderArrays {
+    u64 *order, *values;
+    u8 *status;
+};
+static size_t order_layout(Carve c, size_t rows, OrderArrays *o) {
+    o->order = c.take<u64>(rows);
+    o->values = c.take<u64>(rows);
+    o->status = c.take<u8>(rows);
+    return c.used;
+}
+// behind the checks of sjhip_order_path: q is the view of the n > 0 rows in force
+static int order_build(sjhip_ctx *ctx, const QView &q, const QPath &pth, const uint8_t *keys, size_t klen, uint32_t n, int kind, u32 desc,
+                       uint64_t limit, size_t *records, size_t *rows) {
+    OrderWork w;
+    int rc = reserve_layout(ctx, ctx->d_kat, [&](Carve c) { return order_work_layout(c, ctx, n, kind, desc, &w); });
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const u32 tiles = (n + QTILE - 1) / QTILE;
+    const dim3 per_row((n + 255) / 256), per_tile(tiles), b256(256), bqt(QT), one(1), wide(1024);
+    unsigned long long *const none = nullptr;
+    u64 *const keys0 = w.sort_keys[0];
+    u32 *const rows0 = w.sort_rows[0], *const rows1 = w.sort_rows[1];
+    HIPCHK(hipMemsetAsync(w.totals, 0, 256, st), "order totals memset");
+    hipLaunchKernelGGL(k_q_order_keys, per_tile, bqt, 0, st, q, pth, w.o);
+    hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.o.tiles_ok, none, none, tiles, w.totals);
+    hipLaunchKernelGGL(k_q_order_fold, one, b256, 0, st, w.o, tiles);
+    hipLaunchKernelGGL(k_q_order_compact, per_tile, bqt, 0, st, w.o, SJ_ARR(keys0, n, A_ORDER_SORT), SJ_ARR(rows0, n, A_ORDER_SORT),
+                       SJ_ARR(rows1, n, A_ORDER_SORT));
+    HIPCHK(hipGetLastError(), "order launch");
+    unsigned long long *const h = (unsigned long long *)(ctx->h_scratch + 512);
+    HIPCHK(hipMemcpyAsync(h, w.totals, 24, hipMemcpyDeviceToHost, st), "D2H order totals");
+    HIPCHK(hipStreamSynchronize(st), "order sync");
+    rc = query_bounds_check(ctx);
+    if (rc) return rc;
+    // the rows with a key ordered by it, stably: the j-th pass taken reads sort_*[j & 1] and writes sort_*[(j + 1) & 1]
+    const u32 n_ok = (u32)h[0], mask = n_ok > 1 ? order_pass_mask(h[1], h[2]) : 0u;
+    u32 taken = 0;
+    if (mask) {
+        const u32 stiles = order_sort_tiles(n_ok), hist_n = (u32)ORDER_RADIX * stiles, htiles = (hist_n + QTILE - 1) / QTILE;
+        for (u32 p = 0; p < (u32)ORDER_PASSES; p++) {
+            if (!(mask >> p & 1u)) continue;
+            QOrderSort s;
+            s.n = n_ok, s.shift = p * ORDER_RADIX_BITS;
+            const u64 *const keys_in = w.sort_keys[taken & 1];
+            const u32 *const rows_in = w.sort_rows[taken & 1];
+            u64 *const keys_out = w.sort_keys[(taken + 1) & 1];
+            u32 *const rows_out = w.sort_rows[(taken + 1) & 1], *const hist = w.hist;
+            s.keys_in = SJ_ARR(keys_in, n, A_ORDER_SORT);
+            s.rows_in = SJ_ARR(rows_in, n, A_ORDER_SORT);
+            s.keys_out = SJ_ARR(keys_out, n, A_ORDER_SORT);
+            s.rows_out = SJ_ARR(rows_out, n, A_ORDER_SORT);
+            s.hist = SJ_ARR(hist, hist_n, A_ORDER_HIST);
+            hipLaunchKernelGGL(k_q_order_hist, dim3(stiles), dim3(ORDER_SORT_THREADS), 0, st, s);
+            hipLaunchKernelGGL(k_q_group_scan_sums, dim3(htiles), bqt, 0, st, s.hist, hist_n, w.hist_tiles);
+            hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.hist_tiles, none, none, htiles, none);
+            hipLaunchKernelGGL(k_q_group_scan_apply, dim3(htiles), bqt, 0, st, s.hist, hist_n, w.hist_tiles);
+            hipLaunchKernelGGL(k_q_order_scatter, dim3(stiles), dim3(ORDER_SORT_THREADS), 0, st, s);
+            taken++;
+        }
+    }
+    const u32 *const ranked = w.sort_rows[taken & 1];
+    // rank, flag, narrow: the first `kept` ranks stay
+    const size_t kept = limit == 0 || limit >= n ? (size_t)n : (size_t)limit;
+    hipLaunchKernelGGL(k_q_order_flag, per_row, b256, 0, st, SJ_ARR(ranked, n, A_ORDER_SORT), n, (u64)kept, w.w.flag);
+    hipLaunchKernelGGL(k_q_order_flag_sums, per_tile, bqt, 0, st, w.w.flag, n, w.w.tiles);
+    hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.w.tiles, none, none, tiles, none);
+    HIPCHK(hipGetLastError(), "order sort launch");
+    const std::vector<sjhip_ctx *> parts(1, ctx);
+    rc = where_narrow(ctx, parts, keys, klen, &NO_VALUE, 0, std::vector<QWhere>(1, w.w), std::vector<WhereNew>(1, w.nw),
+                      std::vector<size_t>(1, kept), records, rows);
+    if (rc) return rc;
+    OrderArrays a;
+    rc = reserve_layout(ctx, ctx->d_order, [&](Carve c) { return order_layout(c, kept, &a); });
+    if (rc) return rc;
+    OrderOut out;
+    out.order = SJ_ARR(a.order, kept, A_ORDER_OUT);
+    out.values = SJ_ARR(a.values, kept, A_ORDER_OUT);
+    out.status = SJ_ARR(a.status, kept, A_ORDER_OUT);
+    const u32 *const pre = arr_raw(w.w.pre);
+    hipLaunchKernelGGL(k_q_order_emit, dim3(((u32)kept + 255) / 256), b256, 0, st, w.o, SJ_ARR(ranked, n, A_ORDER_SORT),
+                       SJ_ARR(pre, n, A_WHERE_PRE), (u32)kept, out);
+    HIPCHK(hipGetLastError(), "order emit launch");
+    HIPCHK(hipStreamSynchronize(st), "order emit sync");
+    rc = query_bounds_check(ctx);
+    if (rc) return rc;
+    return published(ctx, ctx->res.publish(&ResultState::order, {kept, kind}));
+}
+
+int sjhip_order_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int kind, uint32_t flags,
+                     uint64_t limit, size_t *records, size_t *rows) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!records || !rows) {
+        ctx_set_error(ctx, "sjhip_order_path: a null size pointer");
+        return SJHIP_ERR_ARG;
+    }
+    if (kind != SJHIP_COL_FLOAT && kind != SJHIP_COL_INT && kind != SJHIP_COL_UINT) {
+        ctx_set_error(ctx, "sjhip_order_path: key kind %d is not SJHIP_COL_FLOAT, SJHIP_COL_INT or SJHIP_COL_UINT", kind);
+        return SJHIP_ERR_ARG;
+    }
+    if (flags & ~SJHIP_ORDER_DESC) {
+        ctx_set_error(ctx, "sjhip_order_path: unknown flag bits 0x%x", flags & ~SJHIP_ORDER_DESC);
+        return SJHIP_ERR_ARG;
+    }
+    QPath pth;
+    size_t klen = 0;
+    int rc = make_path(ctx, keys, key_lens, n_keys, &pth, &klen, true);
+    if (rc) return rc;
+    if (ctx->res.sharded()) {
+        ctx_set_error(ctx, "sjhip_order_path: the result is sharded (an ND message beyond one context's reach); the ranks of shards are not merged");
+        return SJHIP_ERR_ARG;
+    }
+    if (!ctx->res.whole()) return no_whole_result(ctx, "sjhip_order_path", "queries follow");
+    const uint8_t *const kb = keys ? keys : &NO_VALUE;
+    QView q;
+    rc = make_view(ctx, ctx, kb, klen, &NO_VALUE, 0, &q, true);
+    if (rc) return rc;
+    const uint32_t n = part_rows(ctx, ctx, true);
+    if (n > (1u << 30)) {
+        ctx_set_error(ctx, "sjhip_order_path: %u rows (at most 2^30)", n);
+        return SJHIP_ERR_TOOBIG;
+    }
+    // ---- nothing was touched up to here; from here on the last order is gone ----
+    ctx->res.order.begin();
+    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    if (n == 0) {  // (a selection without rows: it stays as it is)
+        *records = ctx->res.rows.sizes().records, *rows = 0;
+        return published(ctx, ctx->res.publish(&ResultState::order, {0, kind}));
+    }
+    rc = order_build(ctx, q, pth, kb, klen, n, kind, flags & SJHIP_ORDER_DESC, limit, records, rows);
+    if (rc) {  // half-built: the old selection may have been written over
+        ctx->res.rows.begin();
+        char why[sizeof ctx->err];
+        snprintf(why, sizeof why, "%s", ctx->err);
+        ctx_set_error(ctx, "sjhip_order_path failed and the row selection was given up: %.180s", why);
+    }
+    return rc;
+}
+
+int sjhip_fetch_order(sjhip_ctx *ctx, uint64_t *order, void *values, uint8_t *status) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!ctx->res.order.exists()) {
+        ctx_set_error(ctx, "no order on the device (sjhip_fetch_order follows sjhip_order_path, with no parse in between)");
+        return SJHIP_ERR_ARG;
+    }
+    const size_t kept = ctx->res.order.sizes().rows;
+    if (kept == 0) return SJHIP_OK;  // (nothing was launched, no arena was written)
+    OrderArrays a;
+    (void)order_layout(Carve(ctx->d_order.p), kept, &a);
+    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    const struct { void *dst; const void *src; size_t bytes; } copies[] = {{order, a.order, kept * 8}, {values, a.values, kept * 8}, {status, a.status, kept}};
+    for (const auto &c : copies)
+        if (c.dst) HIPCHK(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, ctx->stream), "D2H order");
+    HIPCHK(hipStreamSynchronize(ctx->stream), "order fetch sync");
     return SJHIP_OK;
 }

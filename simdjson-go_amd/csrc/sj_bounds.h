@@ -47,7 +47,10 @@ enum ArrId : uint32_t {
     // the grouping (query.hip, sjhip_group_path): the per-row work arrays (status, key element, hash, slot, first-row flag, key
     // length) / the table of row numbers / the keys and rows of the sort and the sorted row order / its digit histograms / the group
     // offsets / the per-group and per-row arrays of the product / the dictionary's key bytes
-    A_GROUP_ROW, A_GROUP_TABLE, A_GROUP_SORT, A_GROUP_HIST, A_GROUP_OFF, A_GROUP_OUT, A_GROUP_KEYS
+    A_GROUP_ROW, A_GROUP_TABLE, A_GROUP_SORT, A_GROUP_HIST, A_GROUP_OFF, A_GROUP_OUT, A_GROUP_KEYS,
+    // the ordering (query.hip, sjhip_order_path): the per-row work arrays (sort key, status) / the keys and rows of the sort and the
+    // rows in rank order / its digit histograms / the arrays of the product (order, values, status)
+    A_ORDER_ROW, A_ORDER_SORT, A_ORDER_HIST, A_ORDER_OUT
 };
 
 #if defined(SJ_DEBUG_BOUNDS)

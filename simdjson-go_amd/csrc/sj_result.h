@@ -11,7 +11,8 @@
 //     each other and of the tenant: one mechanism (Product) used three times -- and a fourth time for the row selection (d_rows:
 //     "the rows are the elements of the array at this path"), which the path queries and the other three products are built over
 //     while it exists and which they survive: what was built under a selection is materialised data.  The grouping (d_group:
-//     sjhip_group_path) is the fifth use: built over the rows in force, independent of everything else once it exists.
+//     sjhip_group_path) is the fifth use: built over the rows in force, independent of everything else once it exists.  The
+//     order (d_order: sjhip_order_path) is the sixth: the rank order of the rows the call kept, materialised like the grouping.
 // The rule: a parse call, successful or not, drops the previous result and everything derived from it (begin_parse); so do
 // sjhip_deserialize, sjhip_ctx_trim and the stage-1-only calls (drop_result).  A product exists from its publish to the next
 // transition that drops it; a product is only published on a resident result, and a result of no tape words is no result.
@@ -35,6 +36,8 @@ public:
     // the grouping (sjhip_group_path): the rows it ran over, its groups, the bytes of its dictionary, and what its fetches need to
     // know: the kind of the keys and of the value column (-1: SJHIP_GROUP_NO_VALUE, no aggregates were built)
     struct Groups { size_t rows = 0, groups = 0, key_bytes = 0; int key_kind = 0, val_kind = -1; };
+    // the order (sjhip_order_path): the rows it kept -- its arrays have that many entries -- and the kind of their keys
+    struct Order { size_t rows = 0; int kind = 0; };
     struct Table {  // what a fetch of one column needs: its kind, and the text bytes of a string column (0 for the other kinds)
         size_t records = 0;
         uint32_t n_cols = 0;
@@ -124,7 +127,8 @@ public:
     Product<Table> table;
     Product<Rows> rows;  // the row selection (sjhip_select_rows; sjhip_select_records is its begin())
     Product<Groups> groups;  // the grouping (sjhip_group_path, d_group): materialised, independent of the selection it was built under
-    void drop_products() { column.begin(), list.begin(), table.begin(), rows.begin(), groups.begin(); }  // (a stage-1-only call on a sharded result: api.hip)
+    Product<Order> order;    // the order (sjhip_order_path, d_order): materialised, its row numbers are those of the selection the call left
+    void drop_products() { column.begin(), list.begin(), table.begin(), rows.begin(), groups.begin(), order.begin(); }  // (a stage-1-only call on a sharded result: api.hip)
     template <typename S>
     bool publish(Product<S> ResultState::*product, const S &sizes) {  // publish(&ResultState::column, {records, bytes})
         if (!resident() && !sharded()) return false;

@@ -526,6 +526,33 @@ class Context:
                                                 self.WHERE_NOT if negate else 0, C.byref(nr), C.byref(nw)))
         return nr.value, nw.value
 
+    # ---- order (include/sjhip.h: sjhip_order_path / sjhip_fetch_order) -----------------------------------------------------------
+    ORDER_DESC = 1
+    ORDER_SORT_TILE = 1024  # rows per tile of the device's sort by key (csrc/sj_order.h): the largest tile of the ordering's kernels
+
+    def order_path(self, path, kind, descending=False, limit=0, fetch=True):
+        """"order by ... limit k" on the device: ranks the rows of the selection in force (without one: the records) by the element
+        at `path` converted by kind = COL_FLOAT / COL_INT / COL_UINT (an empty path: the row's own value) -- OK rows first, ascending
+        or descending by key, equal keys in row order, the rows without an OK key last in row order -- and narrows the selection, as
+        where_path would, to the rows of rank < limit (0: all).  The selection stays in document order.
+        -> Order: records, rows (the rows kept), kind and, fetched, order (uint64: order[i] is the row number in the narrowed
+        selection of the row of rank i), values (float64 / int64 / uint64, in rank order, 0 where not OK) and status (uint8); with
+        fetch=False only the sizes (the order stays on the device: fetch_order)"""
+        blob, lens, n = self._keys(path)
+        nr, nw = C.c_size_t(0), C.c_size_t(0)
+        self._check(_lib.lib().sjhip_order_path(self._h, blob if n else None, lens if n else None, n, int(kind),
+                                                self.ORDER_DESC if descending else 0, int(limit), C.byref(nr), C.byref(nw)))
+        o = Order(nr.value, nw.value, int(kind))
+        return self.fetch_order(o) if fetch else o
+
+    def fetch_order(self, o):
+        """the arrays of the last order_path (o: what it returned with fetch=False) -> o, filled"""
+        o.order, o.status = np.empty(o.rows, dtype=np.uint64), np.empty(o.rows, dtype=np.uint8)
+        o.values = np.empty(o.rows, dtype=self._COL_DTYPES[o.kind])
+        ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+        self._check(_lib.lib().sjhip_fetch_order(self._h, ptr(o.order), ptr(o.values), ptr(o.status)))
+        return o
+
     def filter_rows(self, fetch=True):
         """The rows of the selection in force (select_rows / where_path) as a new self-contained (Tape, Strings.B) on the device,
         one root per row -- what ParseND returns for the document whose lines are the texts of those rows; scalar rows are left
@@ -639,6 +666,17 @@ class Groups:
 
     def __repr__(self):
         return f"Groups(rows={self.rows}, groups={self.groups}, key_bytes={self.key_bytes})"
+
+
+class Order:
+    """what Context.order_path returns: the records, the rows kept and the kind of the keys, and after the fetch order, values and
+    status in rank order (see order_path)"""
+
+    def __init__(self, records, rows, kind):
+        self.records, self.rows, self.kind = records, rows, kind
+
+    def __repr__(self):
+        return f"Order(records={self.records}, rows={self.rows}, kind={self.kind})"
 
 
 class MultiContext:
