@@ -841,13 +841,19 @@ extern "C" int sj_selftest_result_state(const uint8_t *ops, size_t n, uint32_t *
     return 0;
 }
 
-// sj_order.h: the sort key of a number and the pass plan of the sort, as the kernels of sjhip_order_path run them
+// sj_order.h, sj_sort.h: the sort key of a number, and the geometry and the two pass plans of the sort, as the kernels of
+// sjhip_order_path and sjhip_group_path run them.  sj_selftest_sort_plan: out2[0] the grouping's plan for `groups` groups, out2[1]
+// the ordering's for the AND and the OR of its keys
 #include "sj_order.h"
+#include "sj_sort.h"
 extern "C" uint64_t sj_selftest_agg_key(uint64_t bits, int kind) { return sj::agg_key(bits, kind); }
 extern "C" uint64_t sj_selftest_agg_unkey(uint64_t key, int kind) { return sj::agg_unkey(key, kind); }
 extern "C" uint32_t sj_selftest_order_pass_mask(uint64_t and_, uint64_t or_) { return sj::order_pass_mask(and_, or_); }
 extern "C" void sj_selftest_order_geometry(int *out4) {
-    out4[0] = sj::ORDER_RADIX_BITS, out4[1] = sj::ORDER_SORT_THREADS, out4[2] = sj::ORDER_SORT_ROUNDS, out4[3] = sj::ORDER_SORT_TILE;
+    out4[0] = sj::SORT_RADIX_BITS, out4[1] = sj::SORT_THREADS, out4[2] = sj::SORT_ROUNDS, out4[3] = sj::SORT_TILE;
+}
+extern "C" void sj_selftest_sort_plan(uint64_t groups, uint64_t and_, uint64_t or_, uint32_t *out2) {
+    out2[0] = sj::group_pass_mask(groups), out2[1] = sj::order_pass_mask(and_, or_);
 }
 
 // sj_table.h / sj_tablewalk.h: the plan of a table and its one-walk evaluation, as the kernel k_q_table_walk runs them.

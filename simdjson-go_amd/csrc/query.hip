@@ -27,6 +27,7 @@
 #include "sj_ftoa.h"
 #include "sj_group.h"
 #include "sj_order.h"
+#include "sj_sort.h"
 #include "sj_stage2.h"
 #include "sj_tapewalk.h"
 #include "sj_tablewalk.h"
@@ -428,6 +429,12 @@ __global__ __launch_bounds__(256) void k_q_project(QView q, QPath set, u64 *out)
 __device__ __forceinline__ int path_status(u64 v) {
     return v == SJHIP_PATH_NOT_FOUND ? SJHIP_COL_NOT_FOUND : SJHIP_COL_NOT_OBJECT;
 }
+// the value at the path of row `row` (no keys: the row's own value) as a number of `kind`: its status, and its bits in *x
+__device__ __forceinline__ int row_number(const QView &q, const QPath &pth, u32 row, int kind, u64 *x) {
+    const u64 v = pth.n ? record_find_path(q, pth, row) : row_value(q, row);
+    *x = 0;
+    return v < SJHIP_PATH_NOT_OBJECT ? element_to(q, v, kind, x) : path_status(v);
+}
 __global__ __launch_bounds__(256) void k_q_extract(QView q, QPath pth, int kind, void *values, u8 *status) {
     const u32 r = blockIdx.x * 256 + threadIdx.x;
     if (r >= q_rows(q)) return;
@@ -583,9 +590,8 @@ __global__ __launch_bounds__(AGG_TILE) void k_q_agg_rows(QView q, QPath pth, QAg
     int st = -1;
     if (r < n) {
         const u32 row = a.perm ? a.perm[r] : r;
-        const u64 e = pth.n ? record_find_path(q, pth, row) : row_value(q, row);  // (no keys: the row's own value)
-        u64 x = 0;
-        st = e < SJHIP_PATH_NOT_OBJECT ? element_to(q, e, a.kind, &x) : path_status(e);
+        u64 x;
+        st = row_number(q, pth, row, a.kind, &x);
         if (st == SJHIP_COL_OK) {
             v.ok = 1;
             v.mn = v.mx = agg_key(x, a.kind);
@@ -1396,15 +1402,12 @@ __global__ __launch_bounds__(256) void k_q_frows_copy(QView q, QFRows o, Arr<u64
 //                      dictionary's keys; the totals are the groups, the key bytes and -- a third tile sum -- the rows with a key.
 //   k_q_group_emit     codes[r] = the number of its slot's first row; the first rows write their group's entries: first_row, the
 //                      key (a short one by the lane, a long one by the wave, like the string column) or the int64
-//   hist/scan/scatter  a stable least-significant-digit radix sort of the rows by code, GROUP_RADIX_BITS per pass and only as many
-//                      passes as the group count needs: per tile a digit histogram, an exclusive scan of the digit-major
-//                      histograms, a scatter whose rank inside the tile is the row order (wave ballots match equal digits, the waves
-//                      and the rounds of a tile are taken in order).  Rows without a key carry the code `groups` and end behind all.
+//   the sort           the stable radix sort of sj_sort.h: the rows by code, position i being row i, over only as many low digits as
+//                      the group count has (group_pass_mask).  Rows without a key carry the code `groups` and end behind all.
 //   k_q_group_bounds   in the sorted sequence a position whose code differs from the one in front begins a group: the group offsets;
 //   k_q_group_counts   their differences are group_rows -- no contended atomics anywhere.
 // The aggregates are the segmented reduction above with the sorted rows as QAgg::perm and the group offsets as the row offsets
 // (AGG_OFFS): groups in the place of records, so association, 128-bit sums and min / max keys are the tested ones.
-static_assert(GROUP_RADIX == GROUP_SORT_THREADS, "thread d of a sort block owns digit d");
 struct QGroup {
     int key_kind;                      // SJHIP_COL_STRING / SJHIP_COL_INT
     u32 n;                             // rows
@@ -1428,12 +1431,6 @@ struct GroupOut {  // the product (d_group), see group_layout
     Arr<u32> codes;       // [n]
     Arr<u8> status;       // [n]
 };
-struct QSort {
-    u32 n, shift;
-    Arr<const u32> keys_in, rows_in;  // rows_in null: position i is row i (the first pass)
-    Arr<u32> keys_out, rows_out;
-    Arr<u32> hist;                    // [GROUP_RADIX * tiles] digit-major: entry d * tiles + t
-};
 __device__ __forceinline__ bool group_keys_equal(const QView &q, const QGroup &g, u32 a, u32 b) {
     const u64 ka = g.kidx[a], kb = g.kidx[b];
     if (g.key_kind == SJHIP_COL_INT) return ka == kb;
@@ -1444,6 +1441,7 @@ __device__ __forceinline__ bool group_keys_equal(const QView &q, const QGroup &g
 __global__ __launch_bounds__(256) void k_q_group_keys(QView q, QPath pth, QGroup g) {
     const u32 r = blockIdx.x * 256 + threadIdx.x;
     if (r >= g.n) return;
+    // (one walk for both kinds -- STRING needs the element itself; row_number in the INT branch would inline the walk a second time)
     const u64 v = pth.n ? record_find_path(q, pth, r) : row_value(q, r);  // (no keys: the row's own value)
     int st;
     u64 k = 0, h = 0;
@@ -1541,66 +1539,6 @@ __global__ __launch_bounds__(256) void k_q_group_emit(QView q, QGroup g, GroupOu
     }
     wave_copy_strings(q, o.key_bytes, wide, off, len, w, lane);
 }
-// the lanes of the wave whose digit equals this lane's (valid lanes only; undefined on the others), by one ballot per digit bit
-__device__ __forceinline__ u64 group_match_digit(bool valid, u32 d) {
-    u64 m = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < GROUP_RADIX_BITS; b++) {
-        const bool bit = (d >> b) & 1u;
-        const u64 bb = __ballot(valid && bit);
-        m &= bit ? bb : ~bb;
-    }
-    return m;
-}
-__global__ __launch_bounds__(GROUP_SORT_THREADS) void k_q_group_hist(QSort s) {
-    __shared__ u32 s_h[GROUP_RADIX];
-    const int tid = threadIdx.x, lane = tid & 63;
-    s_h[tid] = 0;
-    __syncthreads();
-    for (int k = 0; k < GROUP_SORT_ROUNDS; k++) {
-        const u32 i = blockIdx.x * GROUP_SORT_TILE + k * GROUP_SORT_THREADS + tid;
-        const bool valid = i < s.n;
-        const u32 d = valid ? (s.keys_in[i] >> s.shift) & (GROUP_RADIX - 1) : 0u;
-        const u64 m = group_match_digit(valid, d);
-        if (valid && (m & ((1ull << lane) - 1)) == 0) atomicAdd(&s_h[d], (u32)__popcll(m));  // (LDS: the lowest lane of every digit)
-    }
-    __syncthreads();
-    s.hist[(u64)tid * gridDim.x + blockIdx.x] = s_h[tid];
-}
-__global__ __launch_bounds__(QT) void k_q_group_scan_sums(Arr<u32> a, u32 m, unsigned long long *tiles) { tile_sums(arr_raw(a), m, tiles); }
-__global__ __launch_bounds__(QT) void k_q_group_scan_apply(Arr<u32> a, u32 m, unsigned long long *tiles) {
-    tile_apply(arr_raw(a), arr_raw(a), m, tiles);
-}
-__global__ __launch_bounds__(GROUP_SORT_THREADS) void k_q_group_scatter(QSort s) {
-    __shared__ u32 s_base[GROUP_RADIX], s_cnt[GROUP_SORT_THREADS / 64][GROUP_RADIX];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    s_base[tid] = s.hist[(u64)tid * gridDim.x + blockIdx.x];  // where the tile's rows of digit `tid` begin
-    for (int k = 0; k < GROUP_SORT_ROUNDS; k++) {
-#pragma unroll
-        for (int w = 0; w < GROUP_SORT_THREADS / 64; w++) s_cnt[w][tid] = 0;
-        __syncthreads();
-        const u32 i = blockIdx.x * GROUP_SORT_TILE + k * GROUP_SORT_THREADS + tid;
-        const bool valid = i < s.n;
-        const u32 key = valid ? s.keys_in[i] : 0u, row = valid ? (s.rows_in ? s.rows_in[i] : i) : 0u;
-        const u32 d = (key >> s.shift) & (GROUP_RADIX - 1);
-        const u64 m = group_match_digit(valid, d);
-        const u32 rank = (u32)__popcll(m & ((1ull << lane) - 1));  // equal digits in front of this lane in its wave
-        if (valid && rank == 0) s_cnt[wave][d] = (u32)__popcll(m);
-        __syncthreads();
-        if (valid) {
-            u32 pos = s_base[d] + rank;
-            for (int w = 0; w < GROUP_SORT_THREADS / 64; w++)
-                if (w < wave) pos += s_cnt[w][d];
-            s.keys_out[pos] = key;
-            s.rows_out[pos] = row;
-        }
-        __syncthreads();
-        u32 add = 0;
-#pragma unroll
-        for (int w = 0; w < GROUP_SORT_THREADS / 64; w++) add += s_cnt[w][tid];
-        s_base[tid] += add;  // (thread `tid` alone touches entry `tid` until the next round's barrier)
-    }
-}
 // keys: the sorted codes; the first n_ok positions are the rows with a key.  off[g] = the position group g begins at, off[groups] = n_ok
 __global__ __launch_bounds__(256) void k_q_group_bounds(Arr<const u32> keys, u32 n_ok, u32 groups, Arr<u64> off) {
     const u32 i = blockIdx.x * 256 + threadIdx.x;
@@ -1619,14 +1557,15 @@ __global__ __launch_bounds__(256) void k_q_group_counts(Arr<const u64> off, u32 
 // keys in row order, then the rows without one in row order.  The selection is narrowed to the rows of rank < limit as a row
 // predicate would narrow it (the second half of where_build: k_q_where_apply, k_q_where_offsets), so it stays in document order;
 // the order itself is a product of its own (d_order).
-//   k_q_order_keys     per tile of QTILE rows, one lane per row and round: path, conversion, status (k_q_group_keys' walk); the
-//                      sort key agg_key(x, kind), complemented for a descending order; and the tile's OK rows, the AND and the OR
-//                      of their keys -- wave reductions, the four waves joined through LDS, one plain store per tile and value
+//   k_q_order_keys     per tile of QTILE rows, one lane per row and round: path, conversion, status (row_number); the sort key
+//                      agg_key(x, kind), complemented for a descending order; and the tile's OK rows, the AND and the OR of their
+//                      keys -- wave reductions, the four waves joined through LDS (block_and_or), one plain store per tile and value
 //   scan, k_q_order_fold  the exclusive prefix of the tiles' OK rows (k_tw_scan_sums: its total is n_ok) and the AND / OR of all
-//                      keys, which the host reads in its one copy: a digit whose bits are equal in both takes no pass (sj_order.h)
+//                      keys, which the host reads in its one copy: a digit whose bits are equal in both takes no pass
+//                      (order_pass_mask)
 //   k_q_order_compact  the OK rows to the front in row order -- (key, row) pairs, the input of the first pass --, the others behind
 //                      them in row order, where they stay: they never enter the sort
-//   hist/scan/scatter  the stable least-significant-digit radix sort of the grouping with 64-bit keys, over the planned digits only
+//   the sort           the stable radix sort of sj_sort.h with 64-bit keys, over the planned digits only
 //   k_q_order_flag     the row at sorted position p is kept iff p < limit -> the flag of a row predicate; k_q_order_flag_sums its
 //                      tile sums
 //   k_q_order_emit     behind the narrowing: order[p] = pre[row(p)], the row's number in the new selection; its value and status
@@ -1638,16 +1577,20 @@ struct QOrder {
     unsigned long long *tiles_ok, *tiles_and, *tiles_or;   // [tiles] OK rows of the tile -> their exclusive prefix; AND / OR of their keys
     unsigned long long *totals;                            // [0] the OK rows, [1] the AND, [2] the OR of all their keys
 };
-struct QOrderSort {
-    u32 n, shift;  // n: the rows that are sorted (those with an OK key)
-    Arr<const u64> keys_in;
-    Arr<const u32> rows_in;
-    Arr<u64> keys_out;
-    Arr<u32> rows_out;
-    Arr<u32> hist;  // [ORDER_RADIX * tiles] digit-major: entry d * tiles + t
-};
-static_assert(ORDER_RADIX == ORDER_SORT_THREADS, "thread d of a sort block owns digit d");
-static_assert(ORDER_RADIX_BITS == GROUP_RADIX_BITS, "group_match_digit ballots GROUP_RADIX_BITS bits of a digit");
+// all := the AND of every thread's `all`, any := the OR of every thread's `any`, in thread 0 of a block of QT threads: wave
+// reductions, the waves joined through s_w
+__device__ __forceinline__ void block_and_or(u64 &all, u64 &any, unsigned long long (*s_w)[QT / 64]) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+        all &= (u64)__shfl_xor((long long)all, s, 64);
+        any |= (u64)__shfl_xor((long long)any, s, 64);
+    }
+    if (lane == 0) s_w[0][wave] = all, s_w[1][wave] = any;
+    __syncthreads();
+    if (tid == 0)
+        for (int w = 1; w < QT / 64; w++) all &= s_w[0][w], any |= s_w[1][w];
+}
 __global__ __launch_bounds__(QT) void k_q_order_keys(QView q, QPath pth, QOrder o) {
     __shared__ unsigned long long s_w[3][QT / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1656,9 +1599,8 @@ __global__ __launch_bounds__(QT) void k_q_order_keys(QView q, QPath pth, QOrder 
     for (int k = 0; k < QI; k++) {
         const u32 r = blockIdx.x * QTILE + k * QT + tid;
         if (r >= o.n) break;
-        const u64 v = pth.n ? record_find_path(q, pth, r) : row_value(q, r);  // (no keys: the row's own value)
-        u64 x = 0, key = 0;
-        const int st = v < SJHIP_PATH_NOT_OBJECT ? element_to(q, v, o.kind, &x) : path_status(v);
+        u64 x, key = 0;
+        const int st = row_number(q, pth, r, o.kind, &x);
         if (st == SJHIP_COL_OK) {
             key = agg_key(x, o.kind);
             if (o.desc) key = ~key;
@@ -1669,36 +1611,23 @@ __global__ __launch_bounds__(QT) void k_q_order_keys(QView q, QPath pth, QOrder 
         o.key[r] = key;
         o.status[r] = (u8)st;
     }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        all &= (u64)__shfl_xor((long long)all, s, 64);
-        any |= (u64)__shfl_xor((long long)any, s, 64);
-    }
     ok = wave_sum(ok);
-    if (lane == 0) s_w[0][wave] = ok, s_w[1][wave] = all, s_w[2][wave] = any;
-    __syncthreads();
+    if (lane == 0) s_w[2][wave] = ok;
+    block_and_or(all, any, s_w);
     if (tid == 0) {
-        for (int w = 1; w < QT / 64; w++) ok += s_w[0][w], all &= s_w[1][w], any |= s_w[2][w];
+        for (int w = 1; w < QT / 64; w++) ok += s_w[2][w];
         o.tiles_ok[blockIdx.x] = ok;
         o.tiles_and[blockIdx.x] = all;
         o.tiles_or[blockIdx.x] = any;
     }
 }
 // one block: the AND and the OR over the tiles (a tile without an OK row holds the identities)
-__global__ __launch_bounds__(256) void k_q_order_fold(QOrder o, u32 tiles) {
-    __shared__ unsigned long long s_w[2][256 / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+__global__ __launch_bounds__(QT) void k_q_order_fold(QOrder o, u32 tiles) {
+    __shared__ unsigned long long s_w[2][QT / 64];
     u64 all = ~0ull, any = 0;
-    for (u32 t = tid; t < tiles; t += 256) all &= o.tiles_and[t], any |= o.tiles_or[t];
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        all &= (u64)__shfl_xor((long long)all, s, 64);
-        any |= (u64)__shfl_xor((long long)any, s, 64);
-    }
-    if (lane == 0) s_w[0][wave] = all, s_w[1][wave] = any;
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < 256 / 64; w++) all &= s_w[0][w], any |= s_w[1][w];
+    for (u32 t = threadIdx.x; t < tiles; t += QT) all &= o.tiles_and[t], any |= o.tiles_or[t];
+    block_and_or(all, any, s_w);
+    if (threadIdx.x == 0) {
         o.totals[1] = all;
         o.totals[2] = any;
     }
@@ -1728,52 +1657,6 @@ __global__ __launch_bounds__(QT) void k_q_order_compact(QOrder o, Arr<u64> keys,
             rows0[p] = i;
             rows1[p] = i;
         }
-    }
-}
-__global__ __launch_bounds__(ORDER_SORT_THREADS) void k_q_order_hist(QOrderSort s) {
-    __shared__ u32 s_h[ORDER_RADIX];
-    const int tid = threadIdx.x, lane = tid & 63;
-    s_h[tid] = 0;
-    __syncthreads();
-    for (int k = 0; k < ORDER_SORT_ROUNDS; k++) {
-        const u32 i = blockIdx.x * ORDER_SORT_TILE + k * ORDER_SORT_THREADS + tid;
-        const bool valid = i < s.n;
-        const u32 d = valid ? (u32)(s.keys_in[i] >> s.shift) & (ORDER_RADIX - 1) : 0u;
-        const u64 m = group_match_digit(valid, d);
-        if (valid && (m & ((1ull << lane) - 1)) == 0) atomicAdd(&s_h[d], (u32)__popcll(m));  // (LDS: the lowest lane of every digit)
-    }
-    __syncthreads();
-    s.hist[(u64)tid * gridDim.x + blockIdx.x] = s_h[tid];
-}
-__global__ __launch_bounds__(ORDER_SORT_THREADS) void k_q_order_scatter(QOrderSort s) {
-    __shared__ u32 s_base[ORDER_RADIX], s_cnt[ORDER_SORT_THREADS / 64][ORDER_RADIX];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    s_base[tid] = s.hist[(u64)tid * gridDim.x + blockIdx.x];  // where the tile's rows of digit `tid` begin
-    for (int k = 0; k < ORDER_SORT_ROUNDS; k++) {
-#pragma unroll
-        for (int w = 0; w < ORDER_SORT_THREADS / 64; w++) s_cnt[w][tid] = 0;
-        __syncthreads();
-        const u32 i = blockIdx.x * ORDER_SORT_TILE + k * ORDER_SORT_THREADS + tid;
-        const bool valid = i < s.n;
-        const u64 key = valid ? s.keys_in[i] : 0ull;
-        const u32 row = valid ? s.rows_in[i] : 0u;
-        const u32 d = (u32)(key >> s.shift) & (ORDER_RADIX - 1);
-        const u64 m = group_match_digit(valid, d);
-        const u32 rank = (u32)__popcll(m & ((1ull << lane) - 1));  // equal digits in front of this lane in its wave
-        if (valid && rank == 0) s_cnt[wave][d] = (u32)__popcll(m);
-        __syncthreads();
-        if (valid) {
-            u32 pos = s_base[d] + rank;
-            for (int w = 0; w < ORDER_SORT_THREADS / 64; w++)
-                if (w < wave) pos += s_cnt[w][d];
-            s.keys_out[pos] = key;
-            s.rows_out[pos] = row;
-        }
-        __syncthreads();
-        u32 add = 0;
-#pragma unroll
-        for (int w = 0; w < ORDER_SORT_THREADS / 64; w++) add += s_cnt[w][tid];
-        s_base[tid] += add;  // (thread `tid` alone touches entry `tid` until the next round's barrier)
     }
 }
 // rows: the rows in rank order.  One lane per rank: every row is written once
@@ -2232,7 +2115,7 @@ static int agg_enqueue(sjhip_ctx *ctx, sjhip_ctx *part, const QView &q, const QP
     QAgg a;
     a.kind = kind;
     a.mode = mode;
-    a.perm = SJ_ARR(perm, perm ? n : 0, A_GROUP_SORT);
+    a.perm = SJ_ARR(perm, perm ? n : 0, A_SORT);
     a.n_perm = n;
     a.head = SJ_ARR((const u32 *)w.head, n, A_AGG_HEAD);
     a.out = SJ_ARR(w.out, 6 * records, A_AGG_OUT);
@@ -3160,6 +3043,49 @@ int sjhip_filter_rows(sjhip_ctx *ctx, uint64_t *n_rows, uint64_t *skipped, size_
     return SJHIP_OK;
 }
 
+// ---- queries on the whole result of one context (groups, order) ----------------------------------------------------------------------
+// The checks both run behind their own arguments, in this order and with nothing touched: the paths; a sharded result refused
+// (`unjoined`: what would have to be done across shards); a whole result; the views of the rows in force; at most 2^30 rows (*n).
+struct WholePath {
+    const uint8_t *keys;  // in: the call's keys (null: no keys, the row's own value)
+    const uint32_t *key_lens;
+    uint32_t n_keys;
+    QPath pth;            // out
+    size_t klen;
+    QView q;
+};
+static int whole_entry(sjhip_ctx *ctx, const char *call, const char *unjoined, WholePath *paths, int n_paths, uint32_t *n) {
+    int rc = SJHIP_OK;
+    for (int k = 0; k < n_paths && !rc; k++) rc = make_path(ctx, paths[k].keys, paths[k].key_lens, paths[k].n_keys, &paths[k].pth, &paths[k].klen, true);
+    if (rc) return rc;
+    if (ctx->res.sharded()) {
+        ctx_set_error(ctx, "%s: the result is sharded (an ND message beyond one context's reach); %s", call, unjoined);
+        return SJHIP_ERR_ARG;
+    }
+    if (!ctx->res.whole()) return no_whole_result(ctx, call, "queries follow");
+    for (int k = 0; k < n_paths && !rc; k++) {
+        if (!paths[k].keys) paths[k].keys = &NO_VALUE;
+        rc = make_view(ctx, ctx, paths[k].keys, paths[k].klen, &NO_VALUE, 0, &paths[k].q, true);
+    }
+    if (rc) return rc;
+    *n = part_rows(ctx, ctx, true);
+    if (*n > (1u << 30)) {
+        ctx_set_error(ctx, "%s: %u rows (at most 2^30)", call, *n);
+        return SJHIP_ERR_TOOBIG;
+    }
+    return SJHIP_OK;
+}
+// the D2H copies of a fetch on the context's stream, then one wait; a null destination and an empty array are skipped
+struct FetchCopy { void *dst; const void *src; size_t bytes; };
+static int fetch_copies(sjhip_ctx *ctx, const FetchCopy *copies, size_t n, const char *copy_what, const char *sync_what) {
+    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    for (size_t k = 0; k < n; k++)
+        if (copies[k].dst && copies[k].bytes)
+            HIPCHK(hipMemcpyAsync(copies[k].dst, copies[k].src, copies[k].bytes, hipMemcpyDeviceToHost, ctx->stream), copy_what);
+    HIPCHK(hipStreamSynchronize(ctx->stream), sync_what);
+    return SJHIP_OK;
+}
+
 // ---- groups --------------------------------------------------------------------------------------------------------------------------
 // sjhip_group_path works on the whole result of one context (a sharded one is refused: its dictionaries would have to be joined).
 // The work arrays of all its kernels (GroupWork) lie in d_kat, laid out once for the row count -- the group count is only known
@@ -3169,16 +3095,13 @@ int sjhip_filter_rows(sjhip_ctx *ctx, uint64_t *n_rows, uint64_t *skipped, size_
 struct GroupWork {
     unsigned long long *totals;
     QGroup g;
-    u32 *sort_keys[2], *sort_rows[2];
-    u32 *hist;
-    unsigned long long *hist_tiles;
+    SortWork<u32> sort;
     u64 *off;  // [groups + 1] the group offsets in the sorted order (room for one group per row)
     AggWork agg;
 };
-static u32 group_sort_tiles(u32 n) { return (n + GROUP_SORT_TILE - 1) / GROUP_SORT_TILE; }
 static size_t group_work_layout(Carve c, uint32_t n, int key_kind, bool value, GroupWork *w) {
     const u64 cap = group_table_capacity(n);
-    const u32 tiles = tiles_of(n), hist_n = (u32)GROUP_RADIX * group_sort_tiles(n);
+    const u32 tiles = tiles_of(n);
     w->totals = c.take<unsigned long long>(32);
     w->g.key_kind = key_kind;
     w->g.n = n;
@@ -3198,9 +3121,7 @@ static size_t group_work_layout(Carve c, uint32_t n, int key_kind, bool value, G
     w->g.tiles_f = c.take<unsigned long long>(tiles);
     w->g.tiles_l = c.take<unsigned long long>(tiles);
     w->g.tiles_o = c.take<unsigned long long>(tiles);
-    for (int k = 0; k < 2; k++) w->sort_keys[k] = c.take<u32>(n), w->sort_rows[k] = c.take<u32>(n);
-    w->hist = c.take<u32>(hist_n);
-    w->hist_tiles = c.take<unsigned long long>((hist_n + QTILE - 1) / QTILE);
+    sort_carve(c, n, &w->sort);
     w->off = c.take<u64>((size_t)n + 1);
     if (value) (void)(c.used = agg_layout(c, n, n, AGG_OFFS, &w->agg, false));
     return c.used;
@@ -3241,28 +3162,13 @@ int sjhip_group_path(sjhip_ctx *ctx, const uint8_t *key_keys, const uint32_t *ke
         ctx_set_error(ctx, "sjhip_group_path: value kind %d is not SJHIP_COL_FLOAT, SJHIP_COL_INT, SJHIP_COL_UINT or SJHIP_GROUP_NO_VALUE", val_kind);
         return SJHIP_ERR_ARG;
     }
-    QPath kpth, vpth;
-    size_t klen = 0, vlen = 0;
-    int rc = make_path(ctx, key_keys, key_key_lens, key_n_keys, &kpth, &klen, true);
+    WholePath kv[2] = {{key_keys, key_key_lens, key_n_keys}, {nullptr, nullptr, 0}};
+    if (value) kv[1] = {val_keys, val_key_lens, val_n_keys};
+    uint32_t n = 0;
+    int rc = whole_entry(ctx, "sjhip_group_path", "the dictionaries of shards are not joined", kv, 2, &n);
     if (rc) return rc;
-    if (!value) val_keys = nullptr, val_key_lens = nullptr, val_n_keys = 0;
-    rc = make_path(ctx, val_keys, val_key_lens, val_n_keys, &vpth, &vlen, true);
-    if (rc) return rc;
-    if (ctx->res.sharded()) {
-        ctx_set_error(ctx, "sjhip_group_path: the result is sharded (an ND message beyond one context's reach); the dictionaries of shards are not joined");
-        return SJHIP_ERR_ARG;
-    }
-    if (!ctx->res.whole()) return no_whole_result(ctx, "sjhip_group_path", "queries follow");
-    QView qk, qv;
-    rc = make_view(ctx, ctx, key_keys ? key_keys : &NO_VALUE, klen, &NO_VALUE, 0, &qk, true);
-    if (rc) return rc;
-    rc = make_view(ctx, ctx, val_keys ? val_keys : &NO_VALUE, vlen, &NO_VALUE, 0, &qv, true);
-    if (rc) return rc;
-    const uint32_t n = part_rows(ctx, ctx, true);
-    if (n > (1u << 30)) {
-        ctx_set_error(ctx, "sjhip_group_path: %u rows (at most 2^30)", n);
-        return SJHIP_ERR_TOOBIG;
-    }
+    const QView &qk = kv[0].q, &qv = kv[1].q;
+    const QPath &kpth = kv[0].pth, &vpth = kv[1].pth;
     // ---- nothing was touched up to here; from here on the last grouping is gone ----
     ctx->res.groups.begin();
     ResultState::Groups z;
@@ -3307,30 +3213,13 @@ int sjhip_group_path(sjhip_ctx *ctx, const uint8_t *key_keys, const uint32_t *ke
     o.group_rows = SJ_ARR(a.group_rows, G, A_GROUP_OUT);
     o.codes = SJ_ARR(a.codes, n, A_GROUP_OUT);
     o.status = SJ_ARR(a.status, n, A_GROUP_OUT);
-    u32 *const first_keys = w.sort_keys[0];
-    hipLaunchKernelGGL(k_q_group_emit, per_row, b256, 0, st, qk, w.g, o, G, SJ_ARR(first_keys, n, A_GROUP_SORT));
+    u32 *const first_keys = w.sort.keys[0];
+    hipLaunchKernelGGL(k_q_group_emit, per_row, b256, 0, st, qk, w.g, o, G, SJ_ARR(first_keys, n, A_SORT));
     if (G) {
-        // the rows ordered by code, stably: after pass p the rows lie in sort_*[(p + 1) & 1]
-        const u32 passes = group_sort_passes(G), stiles = group_sort_tiles(n), hist_n = (u32)GROUP_RADIX * stiles;
-        const u32 htiles = (hist_n + QTILE - 1) / QTILE;
-        for (u32 p = 0; p < passes; p++) {
-            QSort s;
-            s.n = n, s.shift = p * GROUP_RADIX_BITS;
-            const u32 *const keys_in = w.sort_keys[p & 1], *const rows_in = p ? w.sort_rows[p & 1] : nullptr;
-            u32 *const keys_out = w.sort_keys[(p + 1) & 1], *const rows_out = w.sort_rows[(p + 1) & 1], *const hist = w.hist;
-            s.keys_in = SJ_ARR(keys_in, n, A_GROUP_SORT);
-            s.rows_in = SJ_ARR(rows_in, p ? n : 0, A_GROUP_SORT);
-            s.keys_out = SJ_ARR(keys_out, n, A_GROUP_SORT);
-            s.rows_out = SJ_ARR(rows_out, n, A_GROUP_SORT);
-            s.hist = SJ_ARR(hist, hist_n, A_GROUP_HIST);
-            hipLaunchKernelGGL(k_q_group_hist, dim3(stiles), dim3(GROUP_SORT_THREADS), 0, st, s);
-            hipLaunchKernelGGL(k_q_group_scan_sums, dim3(htiles), dim3(QT), 0, st, s.hist, hist_n, w.hist_tiles);
-            hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.hist_tiles, none, none, htiles, none);
-            hipLaunchKernelGGL(k_q_group_scan_apply, dim3(htiles), dim3(QT), 0, st, s.hist, hist_n, w.hist_tiles);
-            hipLaunchKernelGGL(k_q_group_scatter, dim3(stiles), dim3(GROUP_SORT_THREADS), 0, st, s);
-        }
-        const u32 *const skeys = w.sort_keys[passes & 1], *const srows = w.sort_rows[passes & 1];
-        hipLaunchKernelGGL(k_q_group_bounds, dim3((n_ok + 255) / 256), b256, 0, st, SJ_ARR(skeys, n, A_GROUP_SORT), n_ok, G,
+        // the rows ordered by code, stably
+        const int at = sort_enqueue(st, n, n, group_pass_mask(G), false, w.sort);
+        const u32 *const skeys = w.sort.keys[at], *const srows = w.sort.rows[at];
+        hipLaunchKernelGGL(k_q_group_bounds, dim3((n_ok + 255) / 256), b256, 0, st, SJ_ARR(skeys, n, A_SORT), n_ok, G,
                            SJ_ARR(w.off, (size_t)G + 1, A_GROUP_OFF));
         hipLaunchKernelGGL(k_q_group_counts, dim3((G + 255) / 256), b256, 0, st, SJ_ARR((const u64 *)w.off, (size_t)G + 1, A_GROUP_OFF), G,
                            o.group_rows);
@@ -3367,14 +3256,10 @@ int sjhip_fetch_groups(sjhip_ctx *ctx, uint64_t *key_offsets, void *keys, uint64
     if (z.rows == 0) return SJHIP_OK;  // (nothing was launched, no arena was written)
     GroupArrays a;
     (void)group_layout(Carve(ctx->d_group.p), z, &a);
-    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
-    const struct { void *dst; const void *src; size_t bytes; } copies[] = {
+    const FetchCopy copies[] = {
         {ints ? nullptr : key_offsets, a.key_off, (z.groups + 1) * 8}, {keys, ints ? (const void *)a.key_int : (const void *)a.key_bytes, z.key_bytes},
         {first_row, a.first_row, z.groups * 8}, {group_rows, a.group_rows, z.groups * 8}, {codes, a.codes, z.rows * 4}, {status, a.status, z.rows}};
-    for (const auto &c : copies)
-        if (c.dst && c.bytes) HIPCHK(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, ctx->stream), "D2H groups");
-    HIPCHK(hipStreamSynchronize(ctx->stream), "group fetch sync");
-    return SJHIP_OK;
+    return fetch_copies(ctx, copies, 6, "D2H groups", "group fetch sync");
 }
 int sjhip_fetch_group_aggregates(sjhip_ctx *ctx, uint64_t *count, uint64_t *not_ok, void *sum, uint64_t *sum_hi, void *min, void *max) {
     if (!ctx) return SJHIP_ERR_ARG;
@@ -3387,12 +3272,10 @@ int sjhip_fetch_group_aggregates(sjhip_ctx *ctx, uint64_t *count, uint64_t *not_
     if (z.groups == 0) return SJHIP_OK;
     GroupArrays a;
     (void)group_layout(Carve(ctx->d_group.p), z, &a);
-    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
     void *const dst[6] = {count, not_ok, sum, sum_hi, min, max};
-    for (int j = 0; j < 6; j++)
-        if (dst[j]) HIPCHK(hipMemcpyAsync(dst[j], a.agg + (size_t)j * z.groups, z.groups * 8, hipMemcpyDeviceToHost, ctx->stream), "D2H group aggregates");
-    HIPCHK(hipStreamSynchronize(ctx->stream), "group aggregates fetch sync");
-    return SJHIP_OK;
+    FetchCopy copies[6];
+    for (int j = 0; j < 6; j++) copies[j] = {dst[j], a.agg + (size_t)j * z.groups, z.groups * 8};
+    return fetch_copies(ctx, copies, 6, "D2H group aggregates", "group aggregates fetch sync");
 }
 
 // ---- order ---------------------------------------------------------------------------------------------------------------------------
@@ -3403,17 +3286,13 @@ int sjhip_fetch_group_aggregates(sjhip_ctx *ctx, uint64_t *count, uint64_t *not_
 struct OrderWork {
     unsigned long long *totals;
     QOrder o;
-    u64 *sort_keys[2];
-    u32 *sort_rows[2];
-    u32 *hist;
-    unsigned long long *hist_tiles;
+    SortWork<u64> sort;
     QWhere w;
     WhereNew nw;
     unsigned long long *w_totals;
 };
-static u32 order_sort_tiles(u32 n) { return (n + ORDER_SORT_TILE - 1) / ORDER_SORT_TILE; }
 static size_t order_work_layout(Carve c, const sjhip_ctx *ctx, uint32_t n, int kind, u32 desc, OrderWork *w) {
-    const u32 tiles = (n + QTILE - 1) / QTILE, hist_n = (u32)ORDER_RADIX * order_sort_tiles(n);
+    const u32 tiles = (n + QTILE - 1) / QTILE;
     w->totals = c.take<unsigned long long>(32);
     w->o.kind = kind;
     w->o.n = n;
@@ -3426,9 +3305,7 @@ static size_t order_work_layout(Carve c, const sjhip_ctx *ctx, uint32_t n, int k
     w->o.tiles_ok = c.take<unsigned long long>(tiles);
     w->o.tiles_and = c.take<unsigned long long>(tiles);
     w->o.tiles_or = c.take<unsigned long long>(tiles);
-    for (int k = 0; k < 2; k++) w->sort_keys[k] = c.take<u64>(n), w->sort_rows[k] = c.take<u32>(n);
-    w->hist = c.take<u32>(hist_n);
-    w->hist_tiles = c.take<unsigned long long>((hist_n + QTILE - 1) / QTILE);
+    sort_carve(c, n, &w->sort);
     (void)(c.used = where_layout(c, ctx, n, &w->w, &w->nw, &w->w_totals));
     return c.used;
 }
@@ -3453,50 +3330,25 @@ static int order_build(sjhip_ctx *ctx, const QView &q, const QPath &pth, const u
     const u32 tiles = (n + QTILE - 1) / QTILE;
     const dim3 per_row((n + 255) / 256), per_tile(tiles), b256(256), bqt(QT), one(1), wide(1024);
     unsigned long long *const none = nullptr;
-    u64 *const keys0 = w.sort_keys[0];
-    u32 *const rows0 = w.sort_rows[0], *const rows1 = w.sort_rows[1];
+    u64 *const keys0 = w.sort.keys[0];
+    u32 *const rows0 = w.sort.rows[0], *const rows1 = w.sort.rows[1];
     HIPCHK(hipMemsetAsync(w.totals, 0, 256, st), "order totals memset");
     hipLaunchKernelGGL(k_q_order_keys, per_tile, bqt, 0, st, q, pth, w.o);
     hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.o.tiles_ok, none, none, tiles, w.totals);
     hipLaunchKernelGGL(k_q_order_fold, one, b256, 0, st, w.o, tiles);
-    hipLaunchKernelGGL(k_q_order_compact, per_tile, bqt, 0, st, w.o, SJ_ARR(keys0, n, A_ORDER_SORT), SJ_ARR(rows0, n, A_ORDER_SORT),
-                       SJ_ARR(rows1, n, A_ORDER_SORT));
+    hipLaunchKernelGGL(k_q_order_compact, per_tile, bqt, 0, st, w.o, SJ_ARR(keys0, n, A_SORT), SJ_ARR(rows0, n, A_SORT), SJ_ARR(rows1, n, A_SORT));
     HIPCHK(hipGetLastError(), "order launch");
     unsigned long long *const h = (unsigned long long *)(ctx->h_scratch + 512);
     HIPCHK(hipMemcpyAsync(h, w.totals, 24, hipMemcpyDeviceToHost, st), "D2H order totals");
     HIPCHK(hipStreamSynchronize(st), "order sync");
     rc = query_bounds_check(ctx);
     if (rc) return rc;
-    // the rows with a key ordered by it, stably: the j-th pass taken reads sort_*[j & 1] and writes sort_*[(j + 1) & 1]
+    // the rows with a key ordered by it, stably (fewer than two: no pass)
     const u32 n_ok = (u32)h[0], mask = n_ok > 1 ? order_pass_mask(h[1], h[2]) : 0u;
-    u32 taken = 0;
-    if (mask) {
-        const u32 stiles = order_sort_tiles(n_ok), hist_n = (u32)ORDER_RADIX * stiles, htiles = (hist_n + QTILE - 1) / QTILE;
-        for (u32 p = 0; p < (u32)ORDER_PASSES; p++) {
-            if (!(mask >> p & 1u)) continue;
-            QOrderSort s;
-            s.n = n_ok, s.shift = p * ORDER_RADIX_BITS;
-            const u64 *const keys_in = w.sort_keys[taken & 1];
-            const u32 *const rows_in = w.sort_rows[taken & 1];
-            u64 *const keys_out = w.sort_keys[(taken + 1) & 1];
-            u32 *const rows_out = w.sort_rows[(taken + 1) & 1], *const hist = w.hist;
-            s.keys_in = SJ_ARR(keys_in, n, A_ORDER_SORT);
-            s.rows_in = SJ_ARR(rows_in, n, A_ORDER_SORT);
-            s.keys_out = SJ_ARR(keys_out, n, A_ORDER_SORT);
-            s.rows_out = SJ_ARR(rows_out, n, A_ORDER_SORT);
-            s.hist = SJ_ARR(hist, hist_n, A_ORDER_HIST);
-            hipLaunchKernelGGL(k_q_order_hist, dim3(stiles), dim3(ORDER_SORT_THREADS), 0, st, s);
-            hipLaunchKernelGGL(k_q_group_scan_sums, dim3(htiles), bqt, 0, st, s.hist, hist_n, w.hist_tiles);
-            hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.hist_tiles, none, none, htiles, none);
-            hipLaunchKernelGGL(k_q_group_scan_apply, dim3(htiles), bqt, 0, st, s.hist, hist_n, w.hist_tiles);
-            hipLaunchKernelGGL(k_q_order_scatter, dim3(stiles), dim3(ORDER_SORT_THREADS), 0, st, s);
-            taken++;
-        }
-    }
-    const u32 *const ranked = w.sort_rows[taken & 1];
+    const u32 *const ranked = w.sort.rows[sort_enqueue(st, n_ok, n, mask, true, w.sort)];
     // rank, flag, narrow: the first `kept` ranks stay
     const size_t kept = limit == 0 || limit >= n ? (size_t)n : (size_t)limit;
-    hipLaunchKernelGGL(k_q_order_flag, per_row, b256, 0, st, SJ_ARR(ranked, n, A_ORDER_SORT), n, (u64)kept, w.w.flag);
+    hipLaunchKernelGGL(k_q_order_flag, per_row, b256, 0, st, SJ_ARR(ranked, n, A_SORT), n, (u64)kept, w.w.flag);
     hipLaunchKernelGGL(k_q_order_flag_sums, per_tile, bqt, 0, st, w.w.flag, n, w.w.tiles);
     hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.w.tiles, none, none, tiles, none);
     HIPCHK(hipGetLastError(), "order sort launch");
@@ -3512,7 +3364,7 @@ static int order_build(sjhip_ctx *ctx, const QView &q, const QPath &pth, const u
     out.values = SJ_ARR(a.values, kept, A_ORDER_OUT);
     out.status = SJ_ARR(a.status, kept, A_ORDER_OUT);
     const u32 *const pre = arr_raw(w.w.pre);
-    hipLaunchKernelGGL(k_q_order_emit, dim3(((u32)kept + 255) / 256), b256, 0, st, w.o, SJ_ARR(ranked, n, A_ORDER_SORT),
+    hipLaunchKernelGGL(k_q_order_emit, dim3(((u32)kept + 255) / 256), b256, 0, st, w.o, SJ_ARR(ranked, n, A_SORT),
                        SJ_ARR(pre, n, A_WHERE_PRE), (u32)kept, out);
     HIPCHK(hipGetLastError(), "order emit launch");
     HIPCHK(hipStreamSynchronize(st), "order emit sync");
@@ -3536,24 +3388,10 @@ int sjhip_order_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_le
         ctx_set_error(ctx, "sjhip_order_path: unknown flag bits 0x%x", flags & ~SJHIP_ORDER_DESC);
         return SJHIP_ERR_ARG;
     }
-    QPath pth;
-    size_t klen = 0;
-    int rc = make_path(ctx, keys, key_lens, n_keys, &pth, &klen, true);
+    WholePath k = {keys, key_lens, n_keys};
+    uint32_t n = 0;
+    int rc = whole_entry(ctx, "sjhip_order_path", "the ranks of shards are not merged", &k, 1, &n);
     if (rc) return rc;
-    if (ctx->res.sharded()) {
-        ctx_set_error(ctx, "sjhip_order_path: the result is sharded (an ND message beyond one context's reach); the ranks of shards are not merged");
-        return SJHIP_ERR_ARG;
-    }
-    if (!ctx->res.whole()) return no_whole_result(ctx, "sjhip_order_path", "queries follow");
-    const uint8_t *const kb = keys ? keys : &NO_VALUE;
-    QView q;
-    rc = make_view(ctx, ctx, kb, klen, &NO_VALUE, 0, &q, true);
-    if (rc) return rc;
-    const uint32_t n = part_rows(ctx, ctx, true);
-    if (n > (1u << 30)) {
-        ctx_set_error(ctx, "sjhip_order_path: %u rows (at most 2^30)", n);
-        return SJHIP_ERR_TOOBIG;
-    }
     // ---- nothing was touched up to here; from here on the last order is gone ----
     ctx->res.order.begin();
     HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
@@ -3561,7 +3399,7 @@ int sjhip_order_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_le
         *records = ctx->res.rows.sizes().records, *rows = 0;
         return published(ctx, ctx->res.publish(&ResultState::order, {0, kind}));
     }
-    rc = order_build(ctx, q, pth, kb, klen, n, kind, flags & SJHIP_ORDER_DESC, limit, records, rows);
+    rc = order_build(ctx, k.q, k.pth, k.keys, k.klen, n, kind, flags & SJHIP_ORDER_DESC, limit, records, rows);
     if (rc) {  // half-built: the old selection may have been written over
         ctx->res.rows.begin();
         char why[sizeof ctx->err];
@@ -3581,10 +3419,6 @@ int sjhip_fetch_order(sjhip_ctx *ctx, uint64_t *order, void *values, uint8_t *st
     if (kept == 0) return SJHIP_OK;  // (nothing was launched, no arena was written)
     OrderArrays a;
     (void)order_layout(Carve(ctx->d_order.p), kept, &a);
-    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
-    const struct { void *dst; const void *src; size_t bytes; } copies[] = {{order, a.order, kept * 8}, {values, a.values, kept * 8}, {status, a.status, kept}};
-    for (const auto &c : copies)
-        if (c.dst) HIPCHK(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, ctx->stream), "D2H order");
-    HIPCHK(hipStreamSynchronize(ctx->stream), "order fetch sync");
-    return SJHIP_OK;
+    const FetchCopy copies[] = {{order, a.order, kept * 8}, {values, a.values, kept * 8}, {status, a.status, kept}};
+    return fetch_copies(ctx, copies, 3, "D2H order", "order fetch sync");
 }

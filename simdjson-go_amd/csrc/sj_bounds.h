@@ -45,12 +45,15 @@ enum ArrId : uint32_t {
     // hands to the next / the per-record results
     A_AGG_HEAD, A_AGG_ITEMS, A_AGG_OUT,
     // the grouping (query.hip, sjhip_group_path): the per-row work arrays (status, key element, hash, slot, first-row flag, key
-    // length) / the table of row numbers / the keys and rows of the sort and the sorted row order / its digit histograms / the group
-    // offsets / the per-group and per-row arrays of the product / the dictionary's key bytes
-    A_GROUP_ROW, A_GROUP_TABLE, A_GROUP_SORT, A_GROUP_HIST, A_GROUP_OFF, A_GROUP_OUT, A_GROUP_KEYS,
-    // the ordering (query.hip, sjhip_order_path): the per-row work arrays (sort key, status) / the keys and rows of the sort and the
-    // rows in rank order / its digit histograms / the arrays of the product (order, values, status)
-    A_ORDER_ROW, A_ORDER_SORT, A_ORDER_HIST, A_ORDER_OUT
+    // length) / the table of row numbers / the group offsets / the per-group and per-row arrays of the product / the dictionary's
+    // key bytes
+    A_GROUP_ROW, A_GROUP_TABLE, A_GROUP_OFF, A_GROUP_OUT, A_GROUP_KEYS,
+    // the ordering (query.hip, sjhip_order_path): the per-row work arrays (sort key, status) / the arrays of the product (order,
+    // values, status)
+    A_ORDER_ROW, A_ORDER_OUT,
+    // the radix sort of both (sj_sort.h): the keys and rows of its buffers, and the sorted rows wherever they are read / its digit
+    // histograms
+    A_SORT, A_SORT_HIST
 };
 
 #if defined(SJ_DEBUG_BOUNDS)

@@ -10,10 +10,6 @@
 namespace sj {
 
 static constexpr u32 GROUP_NONE = 0xffffffffu;  // SJHIP_GROUP_NONE, and the empty slot of the table
-// the radix sort of the rows by their code: GROUP_RADIX_BITS per pass, tiles of GROUP_SORT_TILE rows (GROUP_SORT_THREADS threads,
-// GROUP_SORT_ROUNDS rows each, taken in rounds so that the order inside a tile is the row order)
-static constexpr int GROUP_RADIX_BITS = 8, GROUP_RADIX = 1 << GROUP_RADIX_BITS;
-static constexpr int GROUP_SORT_THREADS = 256, GROUP_SORT_ROUNDS = 4, GROUP_SORT_TILE = GROUP_SORT_THREADS * GROUP_SORT_ROUNDS;
 
 SJ_HD u64 group_mix(u64 h) {  // (the finaliser of MurmurHash3: every input bit reaches every output bit)
     h ^= h >> 33;
@@ -54,12 +50,6 @@ SJ_HD u64 group_table_capacity(u64 n) {
     u64 cap = 64;
     while (cap < 2 * n) cap <<= 1;
     return cap;
-}
-// the passes the sort of codes 0 .. groups takes (code `groups`: the rows without a key, which sort behind every group)
-SJ_HD u32 group_sort_passes(u64 groups) {
-    u32 p = 1;
-    while (p < 8 && (groups >> (GROUP_RADIX_BITS * p)) != 0) p++;
-    return p;
 }
 
 }  // namespace sj

@@ -350,7 +350,7 @@ class Context:
 
     # ---- groups (include/sjhip.h: sjhip_group_path / sjhip_fetch_groups / sjhip_fetch_group_aggregates) --------------------------
     GROUP_NONE, GROUP_NO_VALUE = 0xFFFFFFFF, -1
-    GROUP_SORT_TILE = 1024  # rows per tile of the device's sort by code (csrc/sj_group.h): the largest tile of the grouping's kernels
+    GROUP_SORT_TILE = 1024  # rows per tile of the device's sort by code (csrc/sj_sort.h): the largest tile of the grouping's kernels
 
     def group_path(self, key_path, key_kind, value_path=None, value_kind=None, fetch=True):
         """"group by" on the device: the distinct keys at key_path (key_kind = COL_STRING: Iter.StringBytes, COL_INT: Iter.Int) of the
@@ -528,7 +528,7 @@ class Context:
 
     # ---- order (include/sjhip.h: sjhip_order_path / sjhip_fetch_order) -----------------------------------------------------------
     ORDER_DESC = 1
-    ORDER_SORT_TILE = 1024  # rows per tile of the device's sort by key (csrc/sj_order.h): the largest tile of the ordering's kernels
+    ORDER_SORT_TILE = 1024  # rows per tile of the device's sort by key (csrc/sj_sort.h): the largest tile of the ordering's kernels
 
     def order_path(self, path, kind, descending=False, limit=0, fetch=True):
         """"order by ... limit k" on the device: ranks the rows of the selection in force (without one: the records) by the element

@@ -13,7 +13,7 @@ column at a second path.
   arrays       the aggregates as the six arrays the device call fills (aggregate_walk.record_arrays)
 
 GROUP_SORT_TILE (the rows of one tile of the device's sort by code, the largest tile of the new kernels), GROUP_RADIX_BITS (the
-bits of a sort pass) and QTILE (the tile of the scans) come from csrc/sj_group.h and csrc/sj_tapewalk.h; the shapes of
+bits of a sort pass) and QTILE (the tile of the scans) come from csrc/sj_sort.h and csrc/sj_tapewalk.h; the shapes of
 tests/test_gpu_group.py come from them.  Pinned by tests/test_group_walk.py."""
 import aggregate_walk as AW
 import column_walk as CW

@@ -12,10 +12,10 @@ of the row numbers by the converted value, and a slice of the first k.
              The narrowing goes through where_walk.where's compaction -- the predicate "the row is kept" --, so every record keeps
              the kept rows it owned, in document order.  -> Ordering: records, rows, selection (row_offsets, row_index, statuses),
              order (the row number in the new selection of the row of rank i), values (bit patterns, 0 where not OK), status
-  pass_mask  the digits (bytes) of the sort keys of the OK rows that differ at all: csrc/sj_order.h order_pass_mask
+  pass_mask  the digits (bytes) of the sort keys of the OK rows that differ at all: csrc/sj_sort.h order_pass_mask
 
 ORDER_SORT_TILE (the rows of one tile of the device's sort, the largest tile of the new kernels), ORDER_RADIX_BITS (the bits of a
-sort pass) and QTILE (the tile of the scans) come from csrc/sj_order.h and csrc/sj_tapewalk.h; the shapes of tests/test_gpu_order.py
+sort pass) and QTILE (the tile of the scans) come from csrc/sj_sort.h and csrc/sj_tapewalk.h; the shapes of tests/test_gpu_order.py
 come from them.  Pinned by tests/test_order_walk.py and tests/test_order_abi.py."""
 import aggregate_walk as AW
 import column_walk as CW

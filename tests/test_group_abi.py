@@ -30,13 +30,21 @@ def test_constants():
     assert re.search(r"#define SJHIP_GROUP_NONE 0xffffffffu\b", HDR) and re.search(r"#define SJHIP_GROUP_NO_VALUE \(-1\)", HDR)
     assert sjhip.Context.GROUP_NONE == GW.GROUP_NONE == 0xFFFFFFFF and sjhip.Context.GROUP_NO_VALUE == GW.GROUP_NO_VALUE == -1
     assert sjhip.Context.COL_STRING == GW.COL_STRING == int(re.search(r"SJHIP_COL_STRING = (\d+)", HDR).group(1))
-    src = open(os.path.join(CSRC, "sj_group.h")).read()
+    import order_walk as OW
+    src = open(os.path.join(CSRC, "sj_sort.h")).read()  # (the one sort of the grouping and the ordering)
 
     def const(name, text=src):
         return int(re.search(r"\b%s = (\d+)\b" % name, text).group(1))
-    assert const("GROUP_RADIX_BITS") == GW.GROUP_RADIX_BITS
-    assert (const("GROUP_SORT_THREADS"), const("GROUP_SORT_ROUNDS")) == (GW.GROUP_SORT_THREADS, GW.GROUP_SORT_ROUNDS)
-    assert re.search(r"GROUP_SORT_TILE = GROUP_SORT_THREADS \* GROUP_SORT_ROUNDS;", src)
+    assert const("SORT_RADIX_BITS") == GW.GROUP_RADIX_BITS == OW.ORDER_RADIX_BITS
+    assert (const("SORT_THREADS"), const("SORT_ROUNDS")) == (GW.GROUP_SORT_THREADS, GW.GROUP_SORT_ROUNDS)
+    assert (const("SORT_THREADS"), const("SORT_ROUNDS")) == (OW.ORDER_SORT_THREADS, OW.ORDER_SORT_ROUNDS)
+    assert re.search(r"\bSORT_TILE = SORT_THREADS \* SORT_ROUNDS;", src)
     assert sjhip.Context.GROUP_SORT_TILE == GW.GROUP_SORT_TILE == GW.GROUP_SORT_THREADS * GW.GROUP_SORT_ROUNDS
+    assert sjhip.Context.ORDER_SORT_TILE == OW.ORDER_SORT_TILE == GW.GROUP_SORT_TILE
     walk = open(os.path.join(CSRC, "sj_tapewalk.h")).read()
     assert re.search(r"QT = TW_THREADS, QI = 4, QTILE = QT \* QI;", walk) and const("TW_THREADS", walk) * 4 == GW.QTILE
+    # ... and of the compiled selftest (what the kernels are built with)
+    lib = C.CDLL(G.build_selftest())
+    out = (C.c_int * 4)()
+    lib.sj_selftest_order_geometry(out)
+    assert list(out) == [GW.GROUP_RADIX_BITS, GW.GROUP_SORT_THREADS, GW.GROUP_SORT_ROUNDS, GW.GROUP_SORT_TILE]

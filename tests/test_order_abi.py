@@ -28,14 +28,17 @@ def test_constants():
     import sjhip
     assert re.search(r"#define SJHIP_ORDER_DESC 1u\b", HDR)
     assert sjhip.Context.ORDER_DESC == OW.ORDER_DESC == 1
-    src = open(os.path.join(CSRC, "sj_order.h")).read()
+    import group_walk as GW
+    src = open(os.path.join(CSRC, "sj_sort.h")).read()  # (the one sort of the grouping and the ordering)
 
     def const(name, text=src):
         return int(re.search(r"\b%s = (\d+)\b" % name, text).group(1))
-    assert const("ORDER_RADIX_BITS") == OW.ORDER_RADIX_BITS
-    assert (const("ORDER_SORT_THREADS"), const("ORDER_SORT_ROUNDS")) == (OW.ORDER_SORT_THREADS, OW.ORDER_SORT_ROUNDS)
-    assert re.search(r"ORDER_SORT_TILE = ORDER_SORT_THREADS \* ORDER_SORT_ROUNDS;", src)
+    assert const("SORT_RADIX_BITS") == OW.ORDER_RADIX_BITS == GW.GROUP_RADIX_BITS
+    assert (const("SORT_THREADS"), const("SORT_ROUNDS")) == (OW.ORDER_SORT_THREADS, OW.ORDER_SORT_ROUNDS)
+    assert (const("SORT_THREADS"), const("SORT_ROUNDS")) == (GW.GROUP_SORT_THREADS, GW.GROUP_SORT_ROUNDS)
+    assert re.search(r"\bSORT_TILE = SORT_THREADS \* SORT_ROUNDS;", src)
     assert sjhip.Context.ORDER_SORT_TILE == OW.ORDER_SORT_TILE == OW.ORDER_SORT_THREADS * OW.ORDER_SORT_ROUNDS
+    assert sjhip.Context.GROUP_SORT_TILE == GW.GROUP_SORT_TILE == OW.ORDER_SORT_TILE
     walk = open(os.path.join(CSRC, "sj_tapewalk.h")).read()
     assert re.search(r"QT = TW_THREADS, QI = 4, QTILE = QT \* QI;", walk) and const("TW_THREADS", walk) * 4 == OW.QTILE
     # ... and of the compiled selftest (what the kernels are built with)

@@ -1,6 +1,7 @@
-"""The kernels of the ordering (sjhip_order_path, query.hip) exist exactly once, stay off scratch and leave room for at least 4 waves
-per SIMD -- the bar tests/test_group_kernel_resources.py sets for the grouping -- and the where kernels, whose second half the
-ordering shares, the row, aggregate and group kernels named there keep that bar.  Compile-only: hipcc's resource remarks
+"""The kernels of the ordering (sjhip_order_path, query.hip) exist exactly once, those of the sort it shares with the grouping
+(sj_sort.h) once per key width, all stay off scratch and leave room for at least 4 waves per SIMD -- the bar
+tests/test_group_kernel_resources.py sets for the grouping -- and the where kernels, whose second half the ordering shares, the row,
+aggregate and group kernels named there keep that bar.  Compile-only: hipcc's resource remarks
 (tools/kernel_resources.py), on the product and on the bounds-checked build."""
 import os
 import sys
@@ -12,12 +13,11 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import kernel_resources as KR  # noqa: E402
 
 from test_aggregate_kernel_resources import AGG_KERNELS  # noqa: E402
-from test_group_kernel_resources import GROUP_KERNELS  # noqa: E402
+from test_group_kernel_resources import GROUP_KERNELS, SORT_KERNELS, check_sort_kernels  # noqa: E402
 from test_rows_kernel_resources import ROW_KERNELS  # noqa: E402
 from test_where_kernel_resources import WHERE_KERNELS  # noqa: E402
 
-ORDER_KERNELS = ["k_q_order_keys", "k_q_order_fold", "k_q_order_compact", "k_q_order_hist", "k_q_order_scatter", "k_q_order_flag",
-                 "k_q_order_flag_sums", "k_q_order_emit"]
+ORDER_KERNELS = ["k_q_order_keys", "k_q_order_fold", "k_q_order_compact", "k_q_order_flag", "k_q_order_flag_sums", "k_q_order_emit"]
 
 
 @pytest.mark.parametrize("flags", [(), ("-DSJ_DEBUG_BOUNDS",)], ids=["product", "bounds-checked"])
@@ -29,7 +29,8 @@ def test_order_kernels_use_no_scratch(flags):
     for kernel in ORDER_KERNELS + neighbours:
         assert len(rows.get(kernel, [])) == 1, (kernel, sorted(rows))
     assert sorted(k for k in rows if k.startswith("k_q_order_")) == sorted(ORDER_KERNELS)
-    for kernel in ORDER_KERNELS + neighbours:
+    check_sort_kernels(rows)
+    for kernel in ORDER_KERNELS + list(SORT_KERNELS) + neighbours:
         for name, vgprs, scratch, occ, lds in rows[kernel]:
             print(name, "vgprs", vgprs, "scratch", scratch, "waves/SIMD", occ, "lds", lds)
             assert scratch == 0, (name, vgprs, scratch, occ, lds)

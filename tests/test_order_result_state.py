@@ -2,8 +2,8 @@
 csrc/host_selftest.cpp beside the transitions tests/test_group_result_state.py covers: the order is published on a resident or
 sharded state only, is given up by its own begin (the first step of sjhip_order_path behind its argument checks), is dropped by
 everything that drops the other products, survives the selection, every other product and the tenants of the shared arenas, and
-they survive it.  And the host-and-device pieces of csrc/sj_order.h as the same selftest library compiles them: agg_key is monotone
-in the order of its kind, and order_pass_mask names exactly the digits in which AND and OR differ."""
+they survive it.  And the host-and-device pieces of csrc/sj_order.h and csrc/sj_sort.h as the same selftest library compiles
+them: agg_key is monotone in the order of its kind, and order_pass_mask names exactly the digits in which AND and OR differ."""
 import ctypes as C
 import struct
 
@@ -83,7 +83,7 @@ def test_no_other_transition_touches_the_order(run):
     assert len(seen) == 2 + 2 * 2 * 4 * (96 + 24 + 12)  # one more independent bit on every state with a result
 
 
-# ---- sj_order.h ------------------------------------------------------------------------------------------------------------------------
+# ---- sj_order.h, sj_sort.h--------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def lib():
     L = C.CDLL(G.build_selftest())

@@ -12,7 +12,7 @@ For each, alternating on the same device:
   (c) extract_path(key, kind), fetched, + numpy.argsort(kind="stable")       the route of the parent commit (which has no way back
       to the device with the row numbers it found)
 Host wall time of warmed calls; every call ends in a synchronisation.  Median of REPS runs, three medians each.  The pass count is
-the plan of csrc/sj_order.h on the keys of the column (tests/order_walk.pass_mask).  The output is also written to
+the plan of csrc/sj_sort.h on the keys of the column (tests/order_walk.pass_mask).  The output is also written to
 DIR/rNN_order_time.txt (DIR: profiles/ of the repository), NN the next free number."""
 import os
 import random
