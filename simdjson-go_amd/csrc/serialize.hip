@@ -548,7 +548,7 @@ bool get_block(const uint8_t *src, size_t len, size_t *o, uint64_t *size, size_t
         *data_off = *o;
         return true;
     }
-    if (*o + bsize > len || src[*o] != 0 || bsize != usize + 1) return false;  // blockTypeUncompressed only
+    if (bsize > len - *o || src[*o] != 0 || bsize != usize + 1) return false;  // blockTypeUncompressed only (no sum: it could wrap)
     *size = usize;
     *data_off = *o + 1;
     *o += bsize;
