@@ -482,6 +482,45 @@ int sjhip_where_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_le
 int sjhip_order_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int kind,
                      uint32_t flags, uint64_t limit, size_t *records, size_t *rows);
 int sjhip_fetch_order(sjhip_ctx *ctx, uint64_t *order /* [rows] */, void *values /* [rows], 8 B each */, uint8_t *status /* [rows] */);
+/* Unnest rows: the elements of the ARRAY at `path` of every ROW become the rows -- a second Iter.FindElement(path...) -> Iter.Array()
+ * -> Array.Iter() / Advance inside the loop over the outer elements: statuses[].entities.hashtags[], performances[].seatCategories[]
+ * .areas[], items[].tags[].  Everything that runs on "the rows of the selection in force" then runs on the inner elements.
+ *   sjhip_unnest_rows        evaluates FindElement + Iter.Array on the value of every row of the selection in force -- the PARENT rows;
+ *                            without a selection they are the root values of the records -- with the status bytes sjhip_select_rows
+ *                            gives a record: OK, NOT_FOUND, NOT_OBJECT (a scalar parent row with n_keys > 0 included), NULL, TYPE.
+ *                            n_keys == 0 is allowed: the row's own value must be the array ([[1,2],[3]] -> sjhip_select_rows with no
+ *                            keys -> sjhip_unnest_rows with no keys -> the rows 1, 2, 3).  Paths and limits are otherwise those of
+ *                            sjhip_find_path.  The direct elements of those arrays, in document order, are the new rows -- scalars,
+ *                            objects and arrays alike; what lies inside an element is not a row.  A parent whose status is not OK, or
+ *                            whose array is empty, contributes none.
+ *                            The selection is replaced by one over the same records: record r owns the new rows that came from the
+ *                            rows it owned, in document order, and the status bytes of the records stay as they were (without a prior
+ *                            selection: all OK, as when sjhip_where_path creates one).  The result is an ordinary selection:
+ *                            sjhip_fetch_rows, every call that runs on rows, sjhip_where_path, sjhip_order_path, sjhip_group_path,
+ *                            sjhip_aggregate_path[_records], sjhip_filter_rows, sjhip_marshal_rows and a further sjhip_unnest_rows work
+ *                            on it unchanged.  *records = the records, *parents = the rows before the call, *rows = the rows after it.
+ *                            No parents, or no rows, is legal: nothing is launched for a part without parents, and the (empty)
+ *                            selection and an empty parents product are still published.
+ *   sjhip_fetch_row_parents  the join back, Arrow's list layout over the parent rows: parent_offsets[parents + 1] (parent_offsets[0] = 0;
+ *                            parent p produced the new rows parent_offsets[p] .. parent_offsets[p + 1]), parent[rows] = the parent row
+ *                            number of every new row -- the array a host `take` needs to repeat a parent column, fetched before the
+ *                            call, next to a child column --, parent_status[parents].  Any destination may be NULL.  Parent numbers
+ *                            refer to THE SELECTION AS IT WAS BEFORE THE CALL, child numbers to THE SELECTION AS THE CALL LEFT IT, not to
+ *                            a later one: after a later narrowing, match through row_index of sjhip_fetch_rows, which is stable -- the
+ *                            tape index of a row's value does not change when rows around it are dropped.
+ * Lifetime: the parents have their own device arena (counted by sjhip_ctx_device_bytes, freed by sjhip_ctx_trim) and last until the
+ * next parse or the next sjhip_unnest_rows; they survive every change and drop of the selection and every other product, and they
+ * survive them.  Works after parses with and without SJHIP_FLAG_COPY_STRINGS.  On a sharded ND result every shard unnests its own
+ * rows and the fetch joins them: parent_offsets moved up by the rows in front, parent by the parents in front.
+ * Errors: SJHIP_ERR_ARG, with sjhip_last_error naming the reason and nothing touched (the selection and the previous parents stay as
+ * they were): a bad path, a null size pointer, no result on the device, a fetch without the product ("no row parents on the device
+ * ...").  A call that fails later (SJHIP_ERR_HIP) gives the selection up, as sjhip_where_path does, leaves no parents and says so.
+ * The cost is one walk of every parent row to its array and a fixed number of passes over the tape, whatever the arrays' lengths
+ * and whatever the elements hold. */
+int sjhip_unnest_rows(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, size_t *records, size_t *parents,
+                      size_t *rows);
+int sjhip_fetch_row_parents(sjhip_ctx *ctx, uint64_t *parent_offsets /* [parents + 1] */, uint64_t *parent /* [rows] */,
+                            uint8_t *parent_status /* [parents] */);
 /* Filter rows: the rows of the selection in force -- sjhip_select_rows' or the one sjhip_where_path narrowed or created -- as a new
  * self-contained (Tape, Strings.B) on the device, one root per row: what a caller of ParseND reads with Iter.  With it,
  * sjhip_where_path followed by sjhip_filter_rows is sjhip_filter_where for every operator, for conjunctions and negation, for

@@ -1081,18 +1081,20 @@ struct QRows {
     unsigned long long *totals;   // [1] the rows; [3] != 0: a tile found no anchor among the 64 words in front of it
     u32 depth_want;               // n_keys + 1
 };
+// FindElement + Iter.Array on row r (record r without a selection), the path may be empty: the row's own value is then the array
+__device__ __forceinline__ int row_array(const QView &q, const QPath &pth, u32 r, u64 *v, u64 *close) {
+    if (pth.n) return record_array(q, pth, r, v, close);
+    *v = row_value(q, r);
+    const u64 w = q.tape[*v];
+    const u32 t = (u32)(w >> 56);
+    *close = (w & TW_PAYLOAD) - 1;
+    return t == 'n' ? SJHIP_COL_NULL : (t != '[' ? SJHIP_COL_TYPE : SJHIP_COL_OK);
+}
 __global__ __launch_bounds__(256) void k_q_rows_records(QView q, QPath pth, QRows o) {
     const u32 r = blockIdx.x * 256 + threadIdx.x;
     if (r > q.R) return;
-    u64 v = rec_open(q, r) + 1u, close = 0;  // (an empty path: Iter.Array on the root value itself)
-    int st = SJHIP_COL_OK;
-    if (pth.n) st = record_array(q, pth, r, &v, &close);
-    else {
-        const u64 w = q.tape[v];
-        const u32 t = (u32)(w >> 56);
-        st = t == 'n' ? SJHIP_COL_NULL : (t != '[' ? SJHIP_COL_TYPE : SJHIP_COL_OK);
-        close = (w & TW_PAYLOAD) - 1;
-    }
+    u64 v = 0, close = 0;  // (an empty path: Iter.Array on the root value itself)
+    const int st = row_array(q, pth, r, &v, &close);
     o.open[r] = st == SJHIP_COL_OK ? v : 0;
     o.close[r] = st == SJHIP_COL_OK ? close : 0;
     o.status[r] = (u8)st;
@@ -1107,16 +1109,13 @@ __global__ __launch_bounds__(1024) void k_q_rows_scan_last(QRows o, u32 tiles) {
     if (o.totals[3] == 0) return;
     block1024_scan_array<true>(o.tile_last, tiles, s_w, (int)threadIdx.x);
 }
-// MODE 0: the depth sums (`again`: the second run, with the global anchors, if a tile of the first one asked for them);
-// 1: the row starts counted; 2: written.  Indices are local to the part's tape here; what is stored and compared is merged.
-template <int MODE>
-__global__ __launch_bounds__(TW_THREADS) void k_q_rows_tile(QView q, QRows o, u32 again, Arr<u64> row_index) {
-    __shared__ long long s_l[TW_THREADS / 64];
-    __shared__ unsigned long long s_s[TW_THREADS / 64];
-    __shared__ long long s_carry;
+// What both tile walks -- the row selection's and the unnest's -- start from: the thread's TW_ITEMS words of the tile classified by
+// the anchor rule.  tags: the tag words whose tag may start a row (none of } ] r); opens / closes: the brackets among the tag words.
+// !ok (block-uniform, and only without the global anchors): no anchor among the 64 words in front of the tile, nothing can be
+// classified.  Indices are local to the part's tape here.
+struct TileTags { u32 tags, opens, closes; bool ok; };
+__device__ __forceinline__ TileTags tile_classify(const QView &q, const QRows &o, bool global, long long *s_l, long long *s_carry) {
     const int tid = threadIdx.x;
-    const bool global = MODE == 0 ? again != 0 : o.totals[3] != 0;  // (the first depth pass raises the flag: it must not read it)
-    if (MODE == 0 && again && o.totals[3] == 0) return;
     const u64 n = q.tape_len - q.tape_base;
     const u64 base = (u64)blockIdx.x * TW_TILE + (u64)tid * TW_ITEMS;
     u64 w[TW_ITEMS];
@@ -1128,17 +1127,9 @@ __global__ __launch_bounds__(TW_THREADS) void k_q_rows_tile(QView q, QRows o, u3
         if (base + k < n && !two_word_tag(w[k])) last = (long long)(base + k);
     long long anchor = block_excl_max(last, s_l, tid);  // last anchor in front of this thread's words, inside the tile
     const long long carry = global ? o.tile_last[blockIdx.x]
-                                   : tw_local_anchor(arr_raw(q.tape) + q.tape_base, (u64)blockIdx.x * TW_TILE, tid, &s_carry);
-    if (carry == -2) {  // (block-uniform, and only without the global anchors: the first depth pass) nothing can be classified
-        if (tid == 0) {
-            atomicOr(&o.totals[3], 1ull);
-            o.depth[blockIdx.x] = 0;
-        }
-        return;
-    }
+                                   : tw_local_anchor(arr_raw(q.tape) + q.tape_base, (u64)blockIdx.x * TW_TILE, tid, s_carry);
+    if (carry == -2) return {0u, 0u, 0u, false};
     anchor = anchor > carry ? anchor : carry;
-    // the thread's tag words: their depth deltas, and -- as a mask -- those whose tag may start a row
-    int delta = 0;
     u32 tags = 0, opens = 0, closes = 0;
 #pragma unroll
     for (int k = 0; k < TW_ITEMS; k++) {
@@ -1152,36 +1143,65 @@ __global__ __launch_bounds__(TW_THREADS) void k_q_rows_tile(QView q, QRows o, u3
         else if (t == '}' || t == ']') closes |= 1u << k;
         if (t != '}' && t != ']' && t != 'r') tags |= 1u << k;
     }
-    delta = __popc(opens) - __popc(closes);
+    return {tags, opens, closes, true};
+}
+// The row starts among the thread's words, as a mask: the words of `tags` whose depth is `want` and that inside(k) accepts --
+// called for those words only, in ascending k.  depth: in front of the thread's first word.
+template <typename F>
+__device__ __forceinline__ u32 tile_starts(u32 tags, u32 opens, u32 closes, int depth, int want, F inside) {
+    u32 starts = 0;
+#pragma unroll
+    for (int k = 0; k < TW_ITEMS; k++) {
+        const u32 bit = 1u << k;
+        if ((tags & bit) && depth == want && inside(k)) starts |= bit;
+        depth += (int)((opens >> k) & 1u) - (int)((closes >> k) & 1u);
+    }
+    return starts;
+}
+// MODE 0: the depth sums (`again`: the second run, with the global anchors, if a tile of the first one asked for them);
+// 1: the row starts counted; 2: written.  Indices are local to the part's tape here; what is stored and compared is merged.
+template <int MODE>
+__global__ __launch_bounds__(TW_THREADS) void k_q_rows_tile(QView q, QRows o, u32 again, Arr<u64> row_index) {
+    __shared__ long long s_l[TW_THREADS / 64];
+    __shared__ unsigned long long s_s[TW_THREADS / 64];
+    __shared__ long long s_carry;
+    const int tid = threadIdx.x;
+    const bool global = MODE == 0 ? again != 0 : o.totals[3] != 0;  // (the first depth pass raises the flag: it must not read it)
+    if (MODE == 0 && again && o.totals[3] == 0) return;
+    const u64 base = (u64)blockIdx.x * TW_TILE + (u64)tid * TW_ITEMS;
+    const TileTags c = tile_classify(q, o, global, s_l, &s_carry);
+    const u32 tags = c.tags, opens = c.opens, closes = c.closes;
+    if (!c.ok) {  // (only the first depth pass)
+        if (tid == 0) {
+            atomicOr(&o.totals[3], 1ull);
+            o.depth[blockIdx.x] = 0;
+        }
+        return;
+    }
+    const int delta = __popc(opens) - __popc(closes);
     unsigned long long tot = 0;
     const unsigned long long ex = block_excl_sum((unsigned long long)(long long)delta, s_s, tid, &tot);
     if (MODE == 0) {
         if (tid == 0) o.depth[blockIdx.x] = tot;
         return;
     }
-    int depth = (int)(u32)(o.depth[blockIdx.x] + ex);  // in front of this thread's words
-    u32 starts = 0, r = NONE32;
-#pragma unroll
-    for (int k = 0; k < TW_ITEMS; k++) {
-        const u32 bit = 1u << k;
-        if ((tags & bit) && depth == (int)o.depth_want) {
-            const u64 il = base + k;  // (a word inside a record: never a root)
-            if (r == NONE32) {        // the record of the word: the first whose closing root lies behind it
-                u32 lo = 0, hi = q.R;
-                while (lo < hi) {
-                    const u32 mid = lo + (hi - lo) / 2;
-                    if (q.nl_off[mid] < il) lo = mid + 1;
-                    else hi = mid;
-                }
-                r = lo;
-            } else {
-                while (r < q.R && q.nl_off[r] < il) r++;  // (a record is three words or more: two steps at the most per word)
+    u32 r = NONE32;
+    const u32 starts = tile_starts(tags, opens, closes, (int)(u32)(o.depth[blockIdx.x] + ex), (int)o.depth_want, [&](int k) {
+        const u64 il = base + k;  // (a word inside a record: never a root)
+        if (r == NONE32) {        // the record of the word: the first whose closing root lies behind it
+            u32 lo = 0, hi = q.R;
+            while (lo < hi) {
+                const u32 mid = lo + (hi - lo) / 2;
+                if (q.nl_off[mid] < il) lo = mid + 1;
+                else hi = mid;
             }
-            const u64 i = q.tape_base + il;
-            if (o.open[r] < i && i < o.close[r]) starts |= bit;
+            r = lo;
+        } else {
+            while (r < q.R && q.nl_off[r] < il) r++;  // (a record is three words or more: two steps at the most per word)
         }
-        depth += (int)((opens >> k) & 1u) - (int)((closes >> k) & 1u);
-    }
+        const u64 i = q.tape_base + il;
+        return o.open[r] < i && i < o.close[r];
+    });
     unsigned long long at = block_excl_sum((unsigned long long)__popc(starts), s_s, tid, &tot);
     if (MODE == 1) {
         if (tid == 0) o.cnt[blockIdx.x] = tot;
@@ -1192,20 +1212,107 @@ __global__ __launch_bounds__(TW_THREADS) void k_q_rows_tile(QView q, QRows o, u3
     for (int k = 0; k < TW_ITEMS; k++)
         if (starts & (1u << k)) row_index[at++] = q.tape_base + base + k;
 }
-// row_offsets[r] = the rows in front of record r: the row starts below its opening root (they are in document order)
-__global__ __launch_bounds__(256) void k_q_rows_offsets(QView q, QRows o, Arr<const u64> row_index, u64 rows, u64 *out_off, u8 *out_status) {
-    const u32 r = blockIdx.x * 256 + threadIdx.x;
-    if (r > q.R) return;
-    const u64 first = rec_open(q, r);
+// the rows in front of tape index `first`: a lower bound in the row index (the row starts are in document order)
+__device__ __forceinline__ u64 rows_below(const Arr<const u64> &row_index, u64 rows, u64 first) {
     u64 lo = 0, hi = rows;
     while (lo < hi) {
         const u64 mid = lo + (hi - lo) / 2;
         if (row_index[mid] < first) lo = mid + 1;
         else hi = mid;
     }
-    out_off[r] = lo;
+    return lo;
+}
+// row_offsets[r] = the rows in front of record r: the row starts below its opening root (they are in document order)
+__global__ __launch_bounds__(256) void k_q_rows_offsets(QView q, QRows o, Arr<const u64> row_index, u64 rows, u64 *out_off, u8 *out_status) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    if (r > q.R) return;
+    out_off[r] = rows_below(row_index, rows, rec_open(q, r));
     out_status[r] = o.status[r];
     if (r == q.R) out_off[r + 1] = rows;
+}
+
+// ---- unnest rows: the array at a path of every ROW becomes the rows (sjhip_unnest_rows) --------------------------------------------
+// The row selection one level further down: FindElement + Iter.Array on the value of every row in force -- the parents; without a
+// selection the root values of the records -- and the direct elements of those arrays, in document order, are the new rows.
+//   k_q_unnest_parents  one lane per parent row: row_array on the view with rows -> the target '[', its ']' and the status
+//   the depth prefix    the row selection's own passes (k_q_rows_tile<0>, k_q_rows_last, k_q_rows_scan_last, k_tw_scan_sums)
+//   k_q_unnest_tile<1>  per tile: its new row starts, counted;  k_tw_scan_sums: the row number of the first one, and the total
+//   k_q_unnest_tile<2>  the row starts again, written at their row numbers with the number of their parent beside them
+//   k_q_rows_offsets    one lane per record: the new rows in front of it, its status byte handed on
+//   k_q_unnest_offsets  one lane per parent: parent_offsets[p] = the new rows in front of its value, its status byte
+// A word is a new row start iff it is a tag word, its tag is none of } ] r, its depth is that of the parents + n_keys + 1 (all rows
+// of a selection lie at one depth below their record's root, which the selection carries: ResultState::Rows::depth) and it lies
+// strictly inside the target range of its parent.  A word learns its parent -- the last old row that starts below it -- by one
+// search of the old row index per lane, then by stepping: rows are disjoint, in document order and at least one word long, so
+// there is at most one step per word.  No lane's work grows with the length of an array or the size of an element.
+struct QUnnest {
+    QRows t;                      // the tile passes: depth, cnt, tile_last, totals, depth_want (open, close, status: unused)
+    Arr<u64> open, close;         // [n] merged tape index of the parent's target '[' and of its ']' (0, 0: the parent has no rows)
+    Arr<u8> status;               // [n]
+};
+__global__ __launch_bounds__(256) void k_q_unnest_parents(QView q, QPath pth, QUnnest u) {
+    const u32 p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= q_rows(q)) return;
+    u64 v = 0, close = 0;
+    const int st = row_array(q, pth, p, &v, &close);
+    u.open[p] = st == SJHIP_COL_OK ? v : 0;
+    u.close[p] = st == SJHIP_COL_OK ? close : 0;
+    u.status[p] = (u8)st;
+}
+// MODE 1: the new row starts counted; 2: written, each with its parent (the depth sums are the row selection's MODE 0)
+template <int MODE>
+__global__ __launch_bounds__(TW_THREADS) void k_q_unnest_tile(QView q, QUnnest u, Arr<u64> row_index, Arr<u64> parent) {
+    static_assert(MODE == 1 || MODE == 2, "count or write");
+    __shared__ long long s_l[TW_THREADS / 64];
+    __shared__ unsigned long long s_s[TW_THREADS / 64];
+    __shared__ long long s_carry;
+    const int tid = threadIdx.x;
+    const QRows &o = u.t;
+    const u64 base = (u64)blockIdx.x * TW_TILE + (u64)tid * TW_ITEMS;
+    const TileTags c = tile_classify(q, o, o.totals[3] != 0, s_l, &s_carry);
+    const u32 tags = c.tags, opens = c.opens, closes = c.closes;
+    if (!c.ok) return;  // (the depth pass settled it: never)
+    unsigned long long tot = 0;
+    const unsigned long long ex = block_excl_sum((unsigned long long)(long long)(__popc(opens) - __popc(closes)), s_s, tid, &tot);
+    const u32 n = q_rows(q);
+    u32 below = NONE32;    // the parents that start below the word
+    u32 par[TW_ITEMS];     // (MODE 2) the parent of the start at word k
+    const u32 starts = tile_starts(tags, opens, closes, (int)(u32)(o.depth[blockIdx.x] + ex), (int)o.depth_want, [&](int k) {
+        const u64 i = q.tape_base + base + k;
+        if (below == NONE32) {
+            u32 lo = 0, hi = n;
+            while (lo < hi) {
+                const u32 mid = lo + (hi - lo) / 2;
+                if (row_value(q, mid) < i) lo = mid + 1;
+                else hi = mid;
+            }
+            below = lo;
+        } else {
+            while (below < n && row_value(q, below) < i) below++;
+        }
+        if (below == 0) return false;
+        if (MODE == 2) par[k] = below - 1u;
+        return u.open[below - 1u] < i && i < u.close[below - 1u];
+    });
+    unsigned long long at = block_excl_sum((unsigned long long)__popc(starts), s_s, tid, &tot);
+    if (MODE == 1) {
+        if (tid == 0) o.cnt[blockIdx.x] = tot;
+        return;
+    }
+    at += o.cnt[blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < TW_ITEMS; k++)
+        if (starts & (1u << k)) {
+            row_index[at] = q.tape_base + base + k;
+            parent[at++] = par[k];
+        }
+}
+// parent_offsets[p] = the new rows in front of parent p: the new row starts below its value (entry n: all of them)
+__global__ __launch_bounds__(256) void k_q_unnest_offsets(QView q, QUnnest u, Arr<const u64> row_index, u64 rows, Arr<u64> out_off, Arr<u8> out_status) {
+    const u32 p = blockIdx.x * 256 + threadIdx.x, n = q_rows(q);
+    if (p > n) return;
+    out_off[p] = p < n ? rows_below(row_index, rows, row_value(q, p)) : rows;
+    if (p < n) out_status[p] = u.status[p];
 }
 
 
@@ -2337,6 +2444,8 @@ struct Seg {
     int by;            // a part holds count[by] elements
     int values;        // an offset array: the domain its values count in; NO_DOM: data
     const char *what;  // the name of its copy in an error
+    bool ends = true;  // an offset array: the total of its values lies behind its last entry (false: values that count in a domain
+                       // and are moved up like offsets, but one per element and nothing behind them -- the parent of every row)
 };
 struct PartArrays {  // of one part: its counts, from its published sizes, and where its arrays lie in its arena (segs' order)
     size_t count[N_DOMS] = {};
@@ -2378,7 +2487,7 @@ static int fetch_joined(sjhip_ctx *ctx, const char *sync, const Seg *segs, size_
         });
     if (rc) return rc;
     for (size_t s = 0; s < n_segs; s++)
-        if (segs[s].values != NO_DOM && segs[s].dst) ((uint64_t *)segs[s].dst)[at[P][segs[s].by]] = at[P][segs[s].values];
+        if (segs[s].values != NO_DOM && segs[s].ends && segs[s].dst) ((uint64_t *)segs[s].dst)[at[P][segs[s].by]] = at[P][segs[s].values];
     return SJHIP_OK;
 }
 
@@ -2783,8 +2892,8 @@ struct RowsBuild {
         HIPCHK(hipMemcpyAsync(part->h_scratch + 512, totals + 1, 8, hipMemcpyDeviceToHost, part->stream), "D2H row count");
         return SJHIP_OK;
     }
-    Sizes sizes_of(size_t n, const unsigned long long *h) const { return {n, (size_t)h[0]}; }
-    void add(Sizes *t, const Sizes &s) const { t->records += s.records, t->rows += s.rows; }
+    Sizes sizes_of(size_t n, const unsigned long long *h) const { return {n, (size_t)h[0], pth.n + 1u}; }
+    void add(Sizes *t, const Sizes &s) const { t->records += s.records, t->rows += s.rows, t->depth = s.depth; }
     int gather(sjhip_ctx *ctx, sjhip_ctx *part, const QView &q, uint32_t n, const QRows &w, const Sizes &s) const {
         RowsOut o;
         const int rc = reserve_layout(part, part->d_rows, [&](Carve cv) { return rows_layout(cv, n, s.rows, &o); });
@@ -2897,9 +3006,10 @@ static int where_narrow(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, c
         [](size_t, sjhip_ctx *) {});
     if (rc) return rc;
     ResultState::Rows total;
+    total.depth = sel ? ctx->res.rows.sizes().depth : 0u;  // (the rows keep their depth; the root values of the records lie at 0)
     bool ok = true;  // (a part without rows launched nothing and is republished as it was: its records, no rows)
     for (size_t k = 0; k < parts.size(); k++) {
-        const ResultState::Rows s = {(size_t)parts[k]->q_records + 1u, kept[k]};
+        const ResultState::Rows s = {(size_t)parts[k]->q_records + 1u, kept[k], total.depth};
         ok &= parts[k]->res.publish(&ResultState::rows, s);
         total.records += s.records, total.rows += s.rows;
     }
@@ -2970,6 +3080,183 @@ int sjhip_where_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_le
         ctx_set_error(ctx, "sjhip_where_path failed and the row selection was given up: %.180s", why);
     }
     return rc;
+}
+
+// ---- unnest rows -------------------------------------------------------------------------------------------------------------------
+// sjhip_unnest_rows replaces the selection of every part by the one a level further down and leaves the join back as a product of
+// its own (d_parents, parents_layout).  Two passes over the parts, the shape of where_build / where_narrow: pass 1 runs on the old
+// selection -- or, without one, on the records -- (make_view, on_rows) with its work arrays in d_kat: the parents' ranges, the depth
+// prefix, the new rows counted (they come back through h_scratch + 512) and the new row offsets' room; pass 2 reserves d_parents
+// for the counts and writes the new row index and parent[] there -- the old index is the input of that pass and the new selection
+// may be larger than the arena the old one lies in, so the new index waits behind the product's arrays --, then reserves d_rows and
+// copies offsets, statuses and index into it behind the kernels (stream order; a reservation that moves the arena waits for them).
+struct ParentsOut { u64 *off, *parent, *new_index; u8 *status; };
+static size_t parents_layout(Carve c, size_t parents, size_t rows, ParentsOut *o) {
+    o->off = c.take<u64>(parents + 1);
+    o->status = c.take<u8>(parents);
+    o->parent = c.take<u64>(rows);
+    o->new_index = c.take<u64>(rows);  // (on its way into d_rows: not part of what is fetched)
+    return c.used;
+}
+struct UnnestWork {
+    QUnnest u;
+    u64 *new_off;             // [records + 1] the new row offsets
+    u8 *new_status, *ok;      // [records] the statuses handed on; [records] all OK, what records without a selection hand on
+    unsigned long long *totals;
+};
+static size_t unnest_layout(Carve c, const sjhip_ctx *part, uint32_t n, u32 depth_want, UnnestWork *w) {
+    const u32 tiles = RowsBuild::tape_tiles(part);
+    const size_t recs = (size_t)part->q_records + 1u;
+    w->u.t = QRows{};
+    w->totals = w->u.t.totals = c.take<unsigned long long>(32);
+    u64 *const open = c.take<u64>(n), *const close = c.take<u64>(n);
+    u8 *const status = c.take<u8>(n);
+    w->u.open = SJ_ARR(open, n, A_UNNEST_RANGE);
+    w->u.close = SJ_ARR(close, n, A_UNNEST_RANGE);
+    w->u.status = SJ_ARR(status, n, A_UNNEST_STATUS);
+    w->u.t.depth = c.take<unsigned long long>(tiles);
+    w->u.t.cnt = c.take<unsigned long long>(tiles);
+    w->u.t.tile_last = c.take<long long>(tiles);
+    w->u.t.depth_want = depth_want;
+    w->new_off = c.take<u64>(recs + 1);
+    w->new_status = c.take<u8>(recs);
+    w->ok = c.take<u8>(recs);
+    return c.used;
+}
+static int unnest_build(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, const uint8_t *keys, size_t klen, const QPath &pth,
+                        size_t *records, size_t *parents, size_t *rows) {
+    const bool sel = selected(ctx, true);
+    const u32 depth = (sel ? ctx->res.rows.sizes().depth : 0u) + pth.n + 1u;  // of the new rows below their record's root value
+    std::vector<UnnestWork> work(parts.size());
+    std::vector<size_t> found(parts.size(), 0);
+    int rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, true, "unnest sync",
+        [&](const sjhip_ctx *part, uint32_t n) {
+            UnnestWork w;
+            return unnest_layout(Carve(), part, n, depth, &w) + 64;
+        },
+        [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
+            UnnestWork &w = work[k];
+            (void)unnest_layout(Carve(part->d_kat.p), part, n, depth, &w);
+            const dim3 tiles(RowsBuild::tape_tiles(part)), block(TW_THREADS), one(1), wide(1024);
+            unsigned long long *const none = nullptr;
+            const Arr<u64> no_index = SJ_ARR((u64 *)nullptr, 0, A_ROWS), no_parent = SJ_ARR((u64 *)nullptr, 0, A_UNNEST_PARENT);
+            HIPCHK(hipMemsetAsync(w.totals, 0, 256, part->stream), "unnest totals memset");
+            hipLaunchKernelGGL(k_q_unnest_parents, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, pth, w.u);
+            hipLaunchKernelGGL(k_q_rows_tile<0>, tiles, block, 0, part->stream, q, w.u.t, 0u, no_index);
+            hipLaunchKernelGGL(k_q_rows_last, tiles, block, 0, part->stream, q, w.u.t);  // (these three end at once unless a tile asked)
+            hipLaunchKernelGGL(k_q_rows_scan_last, one, wide, 0, part->stream, w.u.t, tiles.x);
+            hipLaunchKernelGGL(k_q_rows_tile<0>, tiles, block, 0, part->stream, q, w.u.t, 1u, no_index);
+            hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, part->stream, w.u.t.depth, none, none, tiles.x, w.totals);
+            hipLaunchKernelGGL(k_q_unnest_tile<1>, tiles, block, 0, part->stream, q, w.u, no_index, no_parent);
+            hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, part->stream, none, w.u.t.cnt, none, tiles.x, w.totals);  // the rows: totals[1]
+            HIPCHK(hipGetLastError(), "unnest launch");
+            HIPCHK(hipMemcpyAsync(part->h_scratch + 512, w.totals + 1, 8, hipMemcpyDeviceToHost, part->stream), "D2H unnested row count");
+            return SJHIP_OK;
+        },
+        [&](size_t k, sjhip_ctx *part) {
+            found[k] = part_rows(ctx, part, true) ? (size_t)*(const unsigned long long *)(part->h_scratch + 512) : 0;
+        });
+    if (rc) return rc;
+    rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, true, "unnest gather sync", [](const sjhip_ctx *, uint32_t) { return (size_t)0; },
+        [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
+            const UnnestWork &w = work[k];
+            const size_t recs = (size_t)part->q_records + 1u, got = found[k];
+            ParentsOut po;
+            int rc = reserve_layout(part, part->d_parents, [&](Carve cv) { return parents_layout(cv, n, got, &po); });
+            if (rc) return rc;
+            const Arr<const u64> index = SJ_ARR((const u64 *)po.new_index, got, A_ROWS);
+            if (got)
+                hipLaunchKernelGGL(k_q_unnest_tile<2>, dim3(RowsBuild::tape_tiles(part)), dim3(TW_THREADS), 0, part->stream, q, w.u,
+                                   SJ_ARR(po.new_index, got, A_ROWS), SJ_ARR(po.parent, got, A_UNNEST_PARENT));
+            // the records: their new offsets, and the status bytes they had (without a selection: OK)
+            QRows hand = w.u.t;
+            hand.status = w.ok;
+            if (sel) {
+                const ResultState::Rows &z = part->res.rows.sizes();
+                RowsOut old;
+                (void)rows_layout(Carve(part->d_rows.p), z.records, z.rows, &old);
+                hand.status = old.status;
+            } else {
+                HIPCHK(hipMemsetAsync(w.ok, SJHIP_COL_OK, recs, part->stream), "unnest status memset");
+            }
+            hipLaunchKernelGGL(k_q_rows_offsets, dim3(((u32)recs + 255) / 256), dim3(256), 0, part->stream, q, hand, index, (u64)got, w.new_off,
+                               w.new_status);
+            hipLaunchKernelGGL(k_q_unnest_offsets, dim3((n + 1u + 255) / 256), dim3(256), 0, part->stream, q, w.u, index, (u64)got,
+                               SJ_ARR(po.off, (size_t)n + 1, A_UNNEST_OFF), SJ_ARR(po.status, n, A_UNNEST_STATUS));
+            HIPCHK(hipGetLastError(), "unnest gather launch");
+            RowsOut o;
+            rc = reserve_layout(part, part->d_rows, [&](Carve cv) { return rows_layout(cv, recs, got, &o); });
+            if (rc) return rc;
+            HIPCHK(hipMemcpyAsync(o.off, w.new_off, (recs + 1) * 8, hipMemcpyDeviceToDevice, part->stream), "row offsets copy");
+            HIPCHK(hipMemcpyAsync(o.status, w.new_status, recs, hipMemcpyDeviceToDevice, part->stream), "row status copy");
+            if (got) HIPCHK(hipMemcpyAsync(o.index, po.new_index, got * 8, hipMemcpyDeviceToDevice, part->stream), "row index copy");
+            return SJHIP_OK;
+        },
+        [](size_t, sjhip_ctx *) {});
+    if (rc) return rc;
+    ResultState::Rows total;
+    ResultState::Parents joined;
+    total.depth = depth;
+    bool ok = true;  // (a part without parents launched nothing: its selection, no rows, keeps its offsets and statuses)
+    for (size_t k = 0; k < parts.size(); k++) {
+        const ResultState::Rows s = {(size_t)parts[k]->q_records + 1u, found[k], depth};
+        const ResultState::Parents p = {(size_t)part_rows(ctx, parts[k], true), found[k]};
+        total.records += s.records, total.rows += s.rows;
+        joined.parents += p.parents, joined.rows += p.rows;
+        ok &= parts[k]->res.publish(&ResultState::rows, s) && parts[k]->res.publish(&ResultState::parents, p);
+    }
+    if (ctx->res.sharded()) ok &= ctx->res.publish(&ResultState::rows, total) && ctx->res.publish(&ResultState::parents, joined);
+    *records = total.records, *parents = joined.parents, *rows = total.rows;
+    return published(ctx, ok);
+}
+
+int sjhip_unnest_rows(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, size_t *records, size_t *parents,
+                      size_t *rows) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!records || !parents || !rows) {
+        ctx_set_error(ctx, "sjhip_unnest_rows: a null size pointer");
+        return SJHIP_ERR_ARG;
+    }
+    QPath pth;
+    size_t klen = 0;
+    int rc = make_path(ctx, keys, key_lens, n_keys, &pth, &klen, true);
+    if (rc) return rc;
+    const uint8_t *const kb = keys ? keys : &NO_VALUE;
+    std::vector<sjhip_ctx *> parts;
+    rc = query_parts(ctx, kb, klen, &NO_VALUE, 0, &parts);
+    if (rc) return rc;
+    // ---- nothing was touched up to here; from here on the last parents product is gone ----
+    ctx->res.parents.begin();
+    for (sjhip_ctx *part : parts) part->res.parents.begin();
+    rc = unnest_build(ctx, parts, kb, klen, pth, records, parents, rows);
+    if (rc) {  // half-built: the old selection may have been written over
+        ctx->res.rows.begin(), ctx->res.parents.begin();
+        for (sjhip_ctx *part : parts) part->res.rows.begin(), part->res.parents.begin();
+        char why[sizeof ctx->err];
+        snprintf(why, sizeof why, "%s", ctx->err);
+        ctx_set_error(ctx, "sjhip_unnest_rows failed, the row selection was given up and no row parents are left: %.160s", why);
+    }
+    return rc;
+}
+
+int sjhip_fetch_row_parents(sjhip_ctx *ctx, uint64_t *parent_offsets, uint64_t *parent, uint8_t *parent_status) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!ctx->res.parents.exists())
+        return no_product(ctx, "no row parents on the device (sjhip_fetch_row_parents follows sjhip_unnest_rows, with no parse in between)");
+    // (RECORDS counts the parents here, ELEMS the new rows; parent[] counts in parents but has no terminating entry)
+    const Seg segs[] = {{parent_offsets, 8, RECORDS, ELEMS, "D2H parent offsets"},
+                        {parent_status, 1, RECORDS, NO_DOM, "D2H parent status"},
+                        {parent, 8, ELEMS, RECORDS, "D2H row parents", false}};
+    const int rc = fetch_joined(ctx, "row parents fetch sync", segs, 3,
+        [](sjhip_ctx *part, size_t *count, const void **src) {
+            const ResultState::Parents &s = part->res.parents.sizes();
+            ParentsOut o;
+            (void)parents_layout(Carve(part->d_parents.p), s.parents, s.rows, &o);
+            count[RECORDS] = s.parents, count[ELEMS] = s.rows;
+            src[0] = o.off, src[1] = o.status, src[2] = o.parent;
+        },
+        [](const size_t *) { return SJHIP_OK; });  // (any destination may be null: that array is not copied)
+    return rc ? rc : query_bounds_check(ctx);  // (debug build: the kernels of sjhip_unnest_rows have finished here)
 }
 
 // ---- filter rows -------------------------------------------------------------------------------------------------------------------

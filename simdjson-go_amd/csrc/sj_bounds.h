@@ -53,7 +53,10 @@ enum ArrId : uint32_t {
     A_ORDER_ROW, A_ORDER_OUT,
     // the radix sort of both (sj_sort.h): the keys and rows of its buffers, and the sorted rows wherever they are read / its digit
     // histograms
-    A_SORT, A_SORT_HIST
+    A_SORT, A_SORT_HIST,
+    // the unnested rows (query.hip, sjhip_unnest_rows): the target range of every parent row / the status byte of every parent, in
+    // the work arrays and in the product / the parent number of every new row / the parent offsets
+    A_UNNEST_RANGE, A_UNNEST_STATUS, A_UNNEST_PARENT, A_UNNEST_OFF
 };
 
 #if defined(SJ_DEBUG_BOUNDS)

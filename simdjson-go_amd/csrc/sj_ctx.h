@@ -46,6 +46,9 @@ struct sjhip_ctx {
     // the grouping of the last sjhip_group_path (query.hip): the dictionary, first_row, group_rows, codes, key statuses, aggregates
     sj::DevBuf d_group;
     sj::DevBuf d_order;                // the order of the last sjhip_order_path (query.hip): row numbers, keys and statuses by rank
+    // the row parents of the last sjhip_unnest_rows (query.hip): parent offsets, parent statuses, the parent of every new row --
+    // and, behind them, the new row index on its way into d_rows (the old one is read while it is written)
+    sj::DevBuf d_parents;
     unsigned ws_clean_gen = 0;         // d_ws.gen of the allocation that has been zeroed for stage 1 (0: none; stage1_enqueue)
     sj::S1Ws s1ws;                     // ... and its launch count (sj_device.h: a launch cleans up for the next one)
     unsigned s1_par = 0;               // control slot of the last stage-1 launch (Stage1State::c[]: stage 2 reads has_starter there)

@@ -13,6 +13,8 @@
 //     while it exists and which they survive: what was built under a selection is materialised data.  The grouping (d_group:
 //     sjhip_group_path) is the fifth use: built over the rows in force, independent of everything else once it exists.  The
 //     order (d_order: sjhip_order_path) is the sixth: the rank order of the rows the call kept, materialised like the grouping.
+//     The row parents (d_parents: sjhip_unnest_rows) are the seventh: which row of the selection the call found every row of the
+//     selection it left came from, materialised like the other two.
 // The rule: a parse call, successful or not, drops the previous result and everything derived from it (begin_parse); so do
 // sjhip_deserialize, sjhip_ctx_trim and the stage-1-only calls (drop_result).  A product exists from its publish to the next
 // transition that drops it; a product is only published on a resident result, and a result of no tape words is no result.
@@ -32,7 +34,10 @@ public:
     struct Column { size_t records = 0, bytes = 0; };
     struct ListColumn { size_t records = 0, elems = 0, bytes = 0; bool strings = false; };  // (numbers or strings: what was published)
     static constexpr int TABLE_COLS = 16;  // SJHIP_TABLE_MAX_COLS
-    struct Rows { size_t records = 0, rows = 0; };  // the records the selection ran over, the rows it found
+    // the records the selection ran over, the rows it found, and the depth of every row's value below its record's root value (0:
+    // the rows are root values; sjhip_select_rows and every sjhip_unnest_rows add n_keys + 1; a narrowing hands it on)
+    struct Rows { size_t records = 0, rows = 0; uint32_t depth = 0; };
+    struct Parents { size_t parents = 0, rows = 0; };  // the rows sjhip_unnest_rows ran over, the rows it left
     // the grouping (sjhip_group_path): the rows it ran over, its groups, the bytes of its dictionary, and what its fetches need to
     // know: the kind of the keys and of the value column (-1: SJHIP_GROUP_NO_VALUE, no aggregates were built)
     struct Groups { size_t rows = 0, groups = 0, key_bytes = 0; int key_kind = 0, val_kind = -1; };
@@ -128,7 +133,10 @@ public:
     Product<Rows> rows;  // the row selection (sjhip_select_rows; sjhip_select_records is its begin())
     Product<Groups> groups;  // the grouping (sjhip_group_path, d_group): materialised, independent of the selection it was built under
     Product<Order> order;    // the order (sjhip_order_path, d_order): materialised, its row numbers are those of the selection the call left
-    void drop_products() { column.begin(), list.begin(), table.begin(), rows.begin(), groups.begin(), order.begin(); }  // (a stage-1-only call on a sharded result: api.hip)
+    // the row parents (sjhip_unnest_rows, d_parents): materialised; parent numbers are those of the selection the call found, row
+    // numbers those of the selection it left
+    Product<Parents> parents;
+    void drop_products() { column.begin(), list.begin(), table.begin(), rows.begin(), groups.begin(), order.begin(), parents.begin(); }  // (a stage-1-only call on a sharded result: api.hip)
     template <typename S>
     bool publish(Product<S> ResultState::*product, const S &sizes) {  // publish(&ResultState::column, {records, bytes})
         if (!resident() && !sharded()) return false;

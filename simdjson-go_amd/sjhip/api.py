@@ -526,6 +526,30 @@ class Context:
                                                 self.WHERE_NOT if negate else 0, C.byref(nr), C.byref(nw)))
         return nr.value, nw.value
 
+    # ---- unnest (include/sjhip.h: sjhip_unnest_rows / sjhip_fetch_row_parents) ---------------------------------------------------
+    def unnest_rows(self, path=()):
+        """Iter.FindElement(path...), Iter.Array, Array.Iter on every ROW of the selection in force (without one: on every record's
+        root value): the elements of those arrays become the rows, every record keeps its status byte and owns the new rows that
+        came from the rows it owned.  An empty path: the row's own value is the array (lists of lists).
+        -> (records, parents: the rows before the call, rows: the rows after it); fetch_rows(records, rows) delivers the
+        selection, fetch_row_parents(parents, rows) the join back"""
+        blob, lens, n = self._keys(path)
+        nr, npar, nw = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        self._check(_lib.lib().sjhip_unnest_rows(self._h, blob if n else None, lens if n else None, n, C.byref(nr), C.byref(npar),
+                                                 C.byref(nw)))
+        return nr.value, npar.value, nw.value
+
+    def fetch_row_parents(self, parents, rows):
+        """the join back of the last unnest_rows (its parents and rows) -> (parent_offsets: uint64 array of parents + 1 over the new
+        rows, parent: uint64 array of the parent row number of every new row -- what np.take needs to repeat a parent column
+        fetched before the call --, parent_status: uint8 array of COL_OK ... per parent).  Parent numbers count in the selection
+        as it was before the call, row numbers in the one the call left"""
+        offsets = np.empty(parents + 1, dtype=np.uint64)
+        parent = np.empty(max(rows, 1), dtype=np.uint64)
+        status = np.empty(max(parents, 1), dtype=np.uint8)
+        self._check(_lib.lib().sjhip_fetch_row_parents(self._h, offsets.ctypes.data, parent.ctypes.data, status.ctypes.data))
+        return offsets, parent[:rows], status[:parents]
+
     # ---- order (include/sjhip.h: sjhip_order_path / sjhip_fetch_order) -----------------------------------------------------------
     ORDER_DESC = 1
     ORDER_SORT_TILE = 1024  # rows per tile of the device's sort by key (csrc/sj_sort.h): the largest tile of the ordering's kernels
