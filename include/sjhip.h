@@ -482,6 +482,26 @@ int sjhip_where_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_le
 int sjhip_order_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int kind,
                      uint32_t flags, uint64_t limit, size_t *records, size_t *rows);
 int sjhip_fetch_order(sjhip_ctx *ctx, uint64_t *order /* [rows] */, void *values /* [rows], 8 B each */, uint8_t *status /* [rows] */);
+/* Order rows by a STRING key: sjhip_order_path for the keys JSON carries as text -- dates, ids, names.
+ *   key of a row   Iter.FindElement(path) on the row, then Iter.StringBytes: the status byte is the one sjhip_extract_path_strings
+ *                  gives without SJHIP_COL_CVT (OK for a string, else NOT_FOUND / NOT_OBJECT / NULL / TYPE), the key the UNESCAPED
+ *                  bytes -- "A" and its escaped spelling are one key, after parses with and without SJHIP_FLAG_COPY_STRINGS.
+ *                  n_keys == 0: the row's own value.
+ *   order          the OK rows first, ascending by bytes.Compare: unsigned bytes from the left, a proper prefix in front of the
+ *                  longer key.  The empty string is the smallest key, and a NUL byte (an escaped U+0000) is a byte like any other:
+ *                  "a" < "a" NUL < "a" NUL NUL.  For valid UTF-8 this is the order of the code points; it is NOT a collation (no
+ *                  locale, no case folding, no normalisation: "z" sorts in front of "e" with an acute accent).  SJHIP_ORDER_DESC: the
+ *                  reverse order of the distinct keys.  Equal keys stay in row order and the rows without an OK key come last in
+ *                  row order, in both directions; any other flag bit is SJHIP_ERR_ARG.
+ * Everything else -- limit, the narrowing of the selection, *records / *rows, the composition with sjhip_where_path,
+ * sjhip_unnest_rows and further order calls, "no rows launches nothing and publishes an empty order", the 2^30 rows, the refusal of
+ * a sharded result and the failure rules -- is sjhip_order_path's, see there.  The product is the same one: a context holds ONE
+ * order, numeric or string, and sjhip_fetch_order(order, NULL, status) delivers it.  A string order has no 8-byte values: a non-NULL
+ * `values` is SJHIP_ERR_ARG.  The sorted keys are sjhip_extract_path_strings on the kept rows, taken through order[].
+ * The cost is one walk of every row and, for every 7 key bytes that rows still tie on, one round over those rows: a sort pass
+ * for every byte position that differs, and one wait of the host.  The rounds end with the longest key. */
+int sjhip_order_path_strings(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, uint32_t flags, uint64_t limit,
+                             size_t *records, size_t *rows);
 /* Unnest rows: the elements of the ARRAY at `path` of every ROW become the rows -- a second Iter.FindElement(path...) -> Iter.Array()
  * -> Array.Iter() / Advance inside the loop over the outer elements: statuses[].entities.hashtags[], performances[].seatCategories[]
  * .areas[], items[].tags[].  Everything that runs on "the rows of the selection in force" then runs on the inner elements.

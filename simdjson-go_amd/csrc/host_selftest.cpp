@@ -855,6 +855,14 @@ extern "C" uint32_t sj_selftest_order_pass_mask(uint64_t and_, uint64_t or_) { r
 extern "C" void sj_selftest_order_geometry(int *out4) {
     out4[0] = sj::SORT_RADIX_BITS, out4[1] = sj::SORT_THREADS, out4[2] = sj::SORT_ROUNDS, out4[3] = sj::SORT_TILE;
 }
+// the chunk key of the string order (sjhip_order_path_strings) as k_q_strord_chunks computes it, complemented for a descending
+// order; out3: the key, the count strord_chunk_count reads back from it, the rounds that bound keys of `len` bytes
+extern "C" void sj_selftest_strord_chunk(const uint8_t *bytes, uint64_t len, uint64_t at, int desc, uint64_t *out3) {
+    const uint64_t k = sj::strord_chunk(bytes, len, at);
+    out3[0] = desc ? ~k : k;
+    out3[1] = sj::strord_chunk_count(out3[0], desc != 0);
+    out3[2] = sj::strord_max_rounds(len);
+}
 extern "C" void sj_selftest_sort_plan(uint64_t groups, uint64_t and_, uint64_t or_, uint32_t *out2) {
     out2[0] = sj::group_pass_mask(groups), out2[1] = sj::order_pass_mask(and_, or_);
 }

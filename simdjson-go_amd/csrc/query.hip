@@ -1787,6 +1787,237 @@ __global__ __launch_bounds__(256) void k_q_order_emit(QOrder o, Arr<const u32> r
     out.status[p] = st;
 }
 
+// ---- string order: the rows ranked by a string key at a path (sjhip_order_path_strings) ----------------------------------------------
+// The rank is the one of the numeric order with bytes.Compare on the unescaped key bytes.  Keys have any length, so the rank is
+// refined most-significant chunk first, STRORD_CHUNK = 7 key bytes per round (strord_chunk, sj_order.h), each round one stable
+// sort of sj_sort.h.  `perm` holds the rows in rank order as far as it is known: the OK rows in front, the others behind them in
+// row order, where they stay.  A CLASS is a run of positions of perm whose rows have equal key bytes in front of the round's
+// chunk; the ACTIVE entries are the members of the classes that are not finished, held as (row, position, class) in ascending
+// position, so classes are numbered in position order and each owns a contiguous stretch of positions.
+//   k_q_strord_keys     per tile of QTILE rows, one lane per row and round: path, status (element_text_len without conversion), the
+//                       tape index of the string element; the tile's OK rows and its longest OK key, one plain store each
+//   scan, k_q_strord_init  the exclusive prefix of the tiles' OK rows, then the OK rows to the front of perm in row order -- all
+//                       active, positions 0 .. n_ok, one class --, the others behind them in row order
+//   round j:
+//   k_q_strord_chunks   the chunk key at byte 7 j of every active entry (complemented for a descending order) and, per tile, the
+//                       AND and the OR of the chunk keys and of the class numbers.  Launched for the active count of the round
+//                       before, an upper bound; the count itself is read on the device (the host learns it in the round's one copy)
+//   k_q_strord_fold     one block: the ANDs and ORs over the tiles (round 0: the longest key as well) -> the host's one copy per
+//                       round: the active count, and the pass plans (order_pass_mask) of the two sorts
+//   the sort            stable by (class, chunk key), least significant first: sort_enqueue<u64> over the chunk-key digits that
+//                       vary, then k_q_strord_classes gathers the class numbers behind the sorted entries and sort_enqueue<u32>
+//                       takes their varying digits (one class: skipped)
+//   k_q_strord_place    the i-th sorted entry goes to the i-th active position (all members of a class are active or none is, so
+//                       every class lands on its own stretch); an entry is a HEAD iff it begins an old class or its chunk key
+//                       differs from the one in front; it STAYS ACTIVE iff its new class has more than one member and its chunk
+//                       was full (count 7: a class whose chunk ended is a run of equal keys, finished in row order because the
+//                       sort is stable).  The tile sums of both flags
+//   scan, k_q_strord_compact  new class numbers (the heads up to and including the entry) and the active entries compacted, with
+//                       their positions, into the other buffer
+// until nothing is active -- at most strord_max_rounds(longest key) rounds.  No atomics anywhere.
+struct QStrOrd {
+    u32 n, desc;
+    Arr<u8> status;                                 // [n] the key's status
+    Arr<u64> kidx;                                  // [n] tape index of the key's string element (OK rows)
+    Arr<u32> perm;                                  // [n] the rows in rank order
+    Arr<u32> row, pos, cls;                         // [n] each: the active entries of the round
+    Arr<u32> row_out, pos_out, cls_out;             // [n] each: those of the next round (the host swaps the two sets)
+    Arr<u64> chunk;                                 // [n] the round's chunk key of active entry i
+    Arr<u8> flags;                                  // [n] bit 0: head, bit 1: stays active -- of the i-th SORTED entry
+    unsigned long long *tiles_ok, *tiles_len;       // [tiles] OK rows of the tile -> their exclusive prefix; its longest OK key
+    unsigned long long *tiles_kand, *tiles_kor, *tiles_cand, *tiles_cor;  // [tiles] AND / OR of the chunk keys / of the class numbers
+    unsigned long long *tiles_head, *tiles_act;     // [tiles] heads / active entries of the tile -> their exclusive prefixes
+    unsigned long long *totals;                     // STRORD_T_*
+};
+// totals: [0] the OK rows (round 0's active count), [4] the classes and [5] the active entries the last round left (k_tw_scan_sums
+// of tiles_head / tiles_act), [6] the longest OK key, [8 .. 12) the AND / OR of the round's chunk keys, of its class numbers
+static constexpr int STRORD_T_OK = 0, STRORD_T_HEADS = 4, STRORD_T_ACTIVE = 5, STRORD_T_LONGEST = 6, STRORD_T_ANDOR = 8, STRORD_T_WORDS = 12;
+// the maximum of every thread's x in thread 0 of a block of QT threads
+__device__ __forceinline__ u64 block_max(u64 x, unsigned long long *s_w) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+        const u64 o = (u64)__shfl_xor((long long)x, s, 64);
+        x = o > x ? o : x;
+    }
+    if (lane == 0) s_w[wave] = x;
+    __syncthreads();
+    if (tid == 0)
+        for (int w = 1; w < QT / 64; w++) x = s_w[w] > x ? s_w[w] : x;
+    return x;
+}
+__global__ __launch_bounds__(QT) void k_q_strord_keys(QView q, QPath pth, QStrOrd o) {
+    __shared__ unsigned long long s_ok[QT / 64], s_len[QT / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    u64 ok = 0, longest = 0;
+#pragma unroll 1
+    for (int k = 0; k < QI; k++) {
+        const u32 r = blockIdx.x * QTILE + k * QT + tid;
+        if (r >= o.n) break;
+        const u64 v = pth.n ? record_find_path(q, pth, r) : row_value(q, r);  // (no keys: the row's own value)
+        u64 len = 0;
+        const int st = v < SJHIP_PATH_NOT_OBJECT ? element_text_len(q, v, false, &len) : path_status(v);
+        if (st == SJHIP_COL_OK) {
+            ok++;
+            longest = len > longest ? len : longest;
+        }
+        o.status[r] = (u8)st;
+        o.kidx[r] = st == SJHIP_COL_OK ? v : 0ull;
+    }
+    ok = wave_sum(ok);
+    if (lane == 0) s_ok[wave] = ok;
+    longest = block_max(longest, s_len);  // (its barrier orders s_ok as well)
+    if (tid == 0) {
+        for (int w = 1; w < QT / 64; w++) ok += s_ok[w];
+        o.tiles_ok[blockIdx.x] = ok;
+        o.tiles_len[blockIdx.x] = longest;
+    }
+}
+// (tiles_ok has been scanned and totals[STRORD_T_OK] holds the OK rows)
+__global__ __launch_bounds__(QT) void k_q_strord_init(QStrOrd o) {
+    __shared__ unsigned long long s_w[QT / 64];
+    const u32 n = o.n, base = blockIdx.x * QTILE + threadIdx.x * QI, n_ok = (u32)o.totals[STRORD_T_OK];
+    u32 f[QI], sum = 0;
+#pragma unroll
+    for (int k = 0; k < QI; k++) {
+        f[k] = base + k < n && o.status[base + k] == SJHIP_COL_OK ? 1u : 0u;
+        sum += f[k];
+    }
+    u32 at = (u32)(o.tiles_ok[blockIdx.x] + block_excl_sum(sum, s_w, (int)threadIdx.x, nullptr));
+#pragma unroll
+    for (int k = 0; k < QI; k++) {
+        const u32 i = base + k;
+        if (i >= n) break;
+        if (f[k]) {
+            o.perm[at] = i;
+            o.row[at] = i;
+            o.pos[at] = at;
+            o.cls[at] = 0;
+            at++;
+        } else o.perm[n_ok + (i - at)] = i;  // (i - at: the rows without a key in front of row i)
+    }
+}
+// active: where the device keeps the round's active count; at: the byte the round's chunks begin at; the first input of the sort
+__global__ __launch_bounds__(QT) void k_q_strord_chunks(QView q, QStrOrd o, const unsigned long long *active, u64 at, Arr<u64> sort_keys,
+                                                       Arr<u32> sort_rows) {
+    __shared__ unsigned long long s_k[2][QT / 64], s_c[2][QT / 64];
+    const int tid = threadIdx.x;
+    const u32 m = (u32)*active;
+    u64 kall = ~0ull, kany = 0, call = ~0ull, cany = 0;
+#pragma unroll 1
+    for (int k = 0; k < QI; k++) {
+        const u32 i = blockIdx.x * QTILE + k * QT + tid;
+        if (i >= m) break;
+        const u64 v = o.kidx[o.row[i]], w = q.tape[v], len = q.tape[v + 1];
+        u64 key = strord_chunk(str_bytes(q, w, len), len, at);
+        if (o.desc) key = ~key;
+        const u64 c = o.cls[i];
+        o.chunk[i] = key;
+        sort_keys[i] = key;
+        sort_rows[i] = i;
+        kall &= key, kany |= key, call &= c, cany |= c;
+    }
+    block_and_or(kall, kany, s_k);
+    block_and_or(call, cany, s_c);
+    if (tid == 0) {
+        o.tiles_kand[blockIdx.x] = kall, o.tiles_kor[blockIdx.x] = kany;
+        o.tiles_cand[blockIdx.x] = call, o.tiles_cor[blockIdx.x] = cany;
+    }
+}
+// one block: the ANDs and ORs over the tiles of k_q_strord_chunks (a tile without an entry holds the identities); key_tiles > 0: the
+// longest key over the tiles of k_q_strord_keys as well
+__global__ __launch_bounds__(QT) void k_q_strord_fold(QStrOrd o, u32 tiles, u32 key_tiles) {
+    __shared__ unsigned long long s_k[2][QT / 64], s_c[2][QT / 64], s_len[QT / 64];
+    u64 kall = ~0ull, kany = 0, call = ~0ull, cany = 0, longest = 0;
+    for (u32 t = threadIdx.x; t < tiles; t += QT) {
+        kall &= o.tiles_kand[t], kany |= o.tiles_kor[t];
+        call &= o.tiles_cand[t], cany |= o.tiles_cor[t];
+    }
+    for (u32 t = threadIdx.x; t < key_tiles; t += QT) longest = o.tiles_len[t] > longest ? o.tiles_len[t] : longest;
+    block_and_or(kall, kany, s_k);
+    block_and_or(call, cany, s_c);
+    longest = block_max(longest, s_len);
+    if (threadIdx.x == 0) {
+        o.totals[STRORD_T_ANDOR] = kall, o.totals[STRORD_T_ANDOR + 1] = kany;
+        o.totals[STRORD_T_ANDOR + 2] = call, o.totals[STRORD_T_ANDOR + 3] = cany;
+        if (key_tiles) o.totals[STRORD_T_LONGEST] = longest;
+    }
+}
+// sorted: the active entries ordered by chunk key -> the input of the sort by class
+__global__ __launch_bounds__(256) void k_q_strord_classes(QStrOrd o, u32 m, Arr<const u32> sorted, Arr<u32> sort_keys, Arr<u32> sort_rows) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    const u32 e = sorted[i];
+    sort_keys[i] = o.cls[e];
+    sort_rows[i] = e;
+}
+// sorted: the m active entries ordered by (class, chunk key).  A thread takes QI consecutive ones and looks at both neighbours
+__global__ __launch_bounds__(QT) void k_q_strord_place(QStrOrd o, u32 m, Arr<const u32> sorted) {
+    __shared__ unsigned long long s_w[QT / 64];
+    const u32 base = blockIdx.x * QTILE + threadIdx.x * QI;
+    u32 e[QI + 2], c[QI + 2];
+    u64 key[QI + 2];
+    bool in[QI + 2];
+#pragma unroll
+    for (int k = 0; k < QI + 2; k++) {
+        const u32 i = base + (u32)k - 1u;  // (base = 0, k = 0: wraps beyond m)
+        in[k] = i < m;
+        e[k] = in[k] ? sorted[i] : 0u;
+        c[k] = in[k] ? o.cls[e[k]] : 0u;
+        key[k] = in[k] ? o.chunk[e[k]] : 0ull;
+    }
+    unsigned long long heads = 0, active = 0, tot_h = 0, tot_a = 0;
+#pragma unroll
+    for (int k = 1; k <= QI; k++) {
+        if (!in[k]) break;
+        const bool head = !in[k - 1] || c[k] != c[k - 1] || key[k] != key[k - 1];
+        const bool next_head = !in[k + 1] || c[k + 1] != c[k] || key[k + 1] != key[k];
+        const bool stays = !(head && next_head) && strord_chunk_count(key[k], o.desc != 0) == (u32)STRORD_CHUNK;
+        const u32 i = base + (u32)k - 1u;
+        o.perm[o.pos[i]] = o.row[e[k]];
+        o.flags[i] = (u8)((head ? 1u : 0u) | (stays ? 2u : 0u));
+        heads += head ? 1u : 0u;
+        active += stays ? 1u : 0u;
+    }
+    (void)block_excl_sum(heads, s_w, (int)threadIdx.x, &tot_h);
+    (void)block_excl_sum(active, s_w, (int)threadIdx.x, &tot_a);
+    if (threadIdx.x == 0) o.tiles_head[blockIdx.x] = tot_h, o.tiles_act[blockIdx.x] = tot_a;
+}
+// (tiles_head and tiles_act have been scanned)  The entries that stay active, in position order, into the next round's arrays: the row, the
+// position it was placed at, and its new class -- the heads up to and including it
+__global__ __launch_bounds__(QT) void k_q_strord_compact(QStrOrd o, u32 m, Arr<const u32> sorted) {
+    __shared__ unsigned long long s_w[QT / 64];
+    const u32 base = blockIdx.x * QTILE + threadIdx.x * QI;
+    u32 f[QI], heads = 0, active = 0;
+#pragma unroll
+    for (int k = 0; k < QI; k++) {
+        f[k] = base + k < m ? o.flags[base + k] : 0u;
+        heads += f[k] & 1u;
+        active += f[k] >> 1;
+    }
+    u32 cl = (u32)(o.tiles_head[blockIdx.x] + block_excl_sum(heads, s_w, (int)threadIdx.x, nullptr));
+    u32 at = (u32)(o.tiles_act[blockIdx.x] + block_excl_sum(active, s_w, (int)threadIdx.x, nullptr));
+#pragma unroll
+    for (int k = 0; k < QI; k++) {
+        const u32 i = base + k;
+        cl += f[k] & 1u;
+        if (f[k] & 2u) {
+            o.row_out[at] = o.row[sorted[i]];
+            o.pos_out[at] = o.pos[i];
+            o.cls_out[at] = cl;
+            at++;
+        }
+    }
+}
+// behind the narrowing: order[p] = pre[row(p)], the row's number in the new selection, and its status (the keys are not emitted)
+__global__ __launch_bounds__(256) void k_q_strord_emit(QStrOrd o, Arr<const u32> pre, u32 kept, Arr<u64> order, Arr<u8> status) {
+    const u32 p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= kept) return;
+    const u32 row = o.perm[p];
+    order[p] = pre[row];
+    status[p] = o.status[row];
+}
+
 }  // namespace
 
 namespace sj {
@@ -3601,9 +3832,10 @@ struct OrderArrays {
     u64 *order, *values;
     u8 *status;
 };
-static size_t order_layout(Carve c, size_t rows, OrderArrays *o) {
+// (kind SJHIP_COL_STRING -- sjhip_order_path_strings -- has no values)
+static size_t order_layout(Carve c, size_t rows, int kind, OrderArrays *o) {
     o->order = c.take<u64>(rows);
-    o->values = c.take<u64>(rows);
+    o->values = kind == SJHIP_COL_STRING ? nullptr : c.take<u64>(rows);
     o->status = c.take<u8>(rows);
     return c.used;
 }
@@ -3644,7 +3876,7 @@ static int order_build(sjhip_ctx *ctx, const QView &q, const QPath &pth, const u
                       std::vector<size_t>(1, kept), records, rows);
     if (rc) return rc;
     OrderArrays a;
-    rc = reserve_layout(ctx, ctx->d_order, [&](Carve c) { return order_layout(c, kept, &a); });
+    rc = reserve_layout(ctx, ctx->d_order, [&](Carve c) { return order_layout(c, kept, kind, &a); });
     if (rc) return rc;
     OrderOut out;
     out.order = SJ_ARR(a.order, kept, A_ORDER_OUT);
@@ -3696,6 +3928,165 @@ int sjhip_order_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_le
     return rc;
 }
 
+// ---- string order --------------------------------------------------------------------------------------------------------------------
+// sjhip_order_path_strings is sjhip_order_path with the sort replaced by the rounds of the k_q_strord_* kernels.  The work arrays
+// (StrOrdWork) lie in d_kat, laid out once for the row count -- every round works on a prefix of them --, the arrays of the
+// narrowing behind them; the product is the order's, without values.  One host round trip per round: the active count and the
+// ANDs / ORs that plan the round's two sorts (round 0's also brings the OK rows and the longest key, which bounds the rounds).
+struct StrOrdWork {
+    QStrOrd o;
+    SortWork<u64> sort;   // by chunk key
+    SortWork<u32> csort;  // by class
+    QWhere w;
+    WhereNew nw;
+    unsigned long long *w_totals;
+};
+static size_t strord_work_layout(Carve c, const sjhip_ctx *ctx, uint32_t n, u32 desc, StrOrdWork *w) {
+    const u32 tiles = (n + QTILE - 1) / QTILE;
+    QStrOrd &o = w->o;
+    o.totals = c.take<unsigned long long>(32);
+    o.n = n;
+    o.desc = desc;
+    u8 *const status = c.take<u8>(n), *const flags = c.take<u8>(n);
+    u64 *const kidx = c.take<u64>(n), *const chunk = c.take<u64>(n);
+    u32 *const perm = c.take<u32>(n);
+    u32 *const row = c.take<u32>(n), *const pos = c.take<u32>(n), *const cls = c.take<u32>(n);
+    u32 *const row_out = c.take<u32>(n), *const pos_out = c.take<u32>(n), *const cls_out = c.take<u32>(n);
+    o.status = SJ_ARR(status, n, A_STRORD_ROW);
+    o.kidx = SJ_ARR(kidx, n, A_STRORD_ROW);
+    o.perm = SJ_ARR(perm, n, A_SORT);
+    o.flags = SJ_ARR(flags, n, A_STRORD_ACT);
+    o.chunk = SJ_ARR(chunk, n, A_STRORD_ACT);
+    o.row = SJ_ARR(row, n, A_STRORD_ACT), o.pos = SJ_ARR(pos, n, A_STRORD_ACT), o.cls = SJ_ARR(cls, n, A_STRORD_ACT);
+    o.row_out = SJ_ARR(row_out, n, A_STRORD_ACT), o.pos_out = SJ_ARR(pos_out, n, A_STRORD_ACT), o.cls_out = SJ_ARR(cls_out, n, A_STRORD_ACT);
+    unsigned long long **const per_tile[] = {&o.tiles_ok,   &o.tiles_len, &o.tiles_kand, &o.tiles_kor,
+                                             &o.tiles_cand, &o.tiles_cor, &o.tiles_head, &o.tiles_act};
+    for (unsigned long long **t : per_tile) *t = c.take<unsigned long long>(tiles);
+    sort_carve(c, n, &w->sort);
+    sort_carve(c, n, &w->csort);
+    (void)(c.used = where_layout(c, ctx, n, &w->w, &w->nw, &w->w_totals));
+    return c.used;
+}
+// behind the checks of sjhip_order_path_strings: q is the view of the n > 0 rows in force
+static int strord_build(sjhip_ctx *ctx, const QView &q, const QPath &pth, const uint8_t *keys, size_t klen, uint32_t n, u32 desc, uint64_t limit,
+                        size_t *records, size_t *rows) {
+    StrOrdWork w;
+    int rc = reserve_layout(ctx, ctx->d_kat, [&](Carve c) { return strord_work_layout(c, ctx, n, desc, &w); });
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const u32 tiles = (n + QTILE - 1) / QTILE;
+    const dim3 per_row((n + 255) / 256), per_tile(tiles), b256(256), bqt(QT), one(1), wide(1024);
+    unsigned long long *const none = nullptr;
+    QStrOrd &o = w.o;
+    u64 *const keys0 = w.sort.keys[0];
+    u32 *const rows0 = w.sort.rows[0], *const ckeys0 = w.csort.keys[0], *const crows0 = w.csort.rows[0];
+    HIPCHK(hipMemsetAsync(o.totals, 0, 256, st), "string order totals memset");
+    hipLaunchKernelGGL(k_q_strord_keys, per_tile, bqt, 0, st, q, pth, o);
+    hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, o.tiles_ok, none, none, tiles, o.totals + STRORD_T_OK);
+    hipLaunchKernelGGL(k_q_strord_init, per_tile, bqt, 0, st, o);
+    HIPCHK(hipGetLastError(), "string order launch");
+    unsigned long long *const h = (unsigned long long *)(ctx->h_scratch + 512), *const h_left = (unsigned long long *)(ctx->h_scratch + 1024);
+    *h_left = 0;
+    u64 bound = 1;  // of the rounds: known after round 0's copy
+    u32 m_max = n;  // the round's active entries are at most this many
+    for (u64 round = 0;; round++) {
+        // the round's chunk keys, and its one round trip
+        const u32 ctiles = (m_max + QTILE - 1) / QTILE;
+        const unsigned long long *const active = o.totals + (round == 0 ? STRORD_T_OK : STRORD_T_ACTIVE);
+        hipLaunchKernelGGL(k_q_strord_chunks, dim3(ctiles), bqt, 0, st, q, o, active, round * (u64)STRORD_CHUNK, SJ_ARR(keys0, n, A_SORT),
+                           SJ_ARR(rows0, n, A_SORT));
+        hipLaunchKernelGGL(k_q_strord_fold, one, bqt, 0, st, o, ctiles, round == 0 ? tiles : 0u);
+        HIPCHK(hipGetLastError(), "string order chunk launch");
+        HIPCHK(hipMemcpyAsync(h, o.totals, STRORD_T_WORDS * 8, hipMemcpyDeviceToHost, st), "D2H string order totals");
+        HIPCHK(hipStreamSynchronize(st), "string order sync");
+        rc = query_bounds_check(ctx);
+        if (rc) return rc;
+        if (round == 0) bound = strord_max_rounds(h[STRORD_T_LONGEST]);
+        const u32 m = (u32)h[round == 0 ? STRORD_T_OK : STRORD_T_ACTIVE];
+        if (m < 2) break;  // (a class has two members at least: nothing is active)
+        // stable by (class, chunk key): the chunk keys first, then the classes
+        const u32 kmask = order_pass_mask(h[STRORD_T_ANDOR], h[STRORD_T_ANDOR + 1]);
+        const u32 cmask = order_pass_mask(h[STRORD_T_ANDOR + 2], h[STRORD_T_ANDOR + 3]);
+        const u32 *sorted = w.sort.rows[sort_enqueue(st, m, n, kmask, true, w.sort)];
+        const dim3 per_entry((m + 255) / 256), per_etile((m + QTILE - 1) / QTILE);
+        if (cmask) {
+            hipLaunchKernelGGL(k_q_strord_classes, per_entry, b256, 0, st, o, m, SJ_ARR(sorted, n, A_SORT), SJ_ARR(ckeys0, n, A_SORT),
+                               SJ_ARR(crows0, n, A_SORT));
+            sorted = w.csort.rows[sort_enqueue(st, m, n, cmask, true, w.csort)];
+        }
+        // place, mark, renumber, compact
+        hipLaunchKernelGGL(k_q_strord_place, per_etile, bqt, 0, st, o, m, SJ_ARR(sorted, n, A_SORT));
+        hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, o.tiles_head, o.tiles_act, none, per_etile.x, o.totals + STRORD_T_HEADS);
+        hipLaunchKernelGGL(k_q_strord_compact, per_etile, bqt, 0, st, o, m, SJ_ARR(sorted, n, A_SORT));
+        HIPCHK(hipGetLastError(), "string order round launch");
+        std::swap(o.row, o.row_out), std::swap(o.pos, o.pos_out), std::swap(o.cls, o.cls_out);
+        m_max = m;
+        if (round + 1 >= bound) {  // the last round the longest key allows: what it left active (nothing) is looked at with the emit's wait
+            HIPCHK(hipMemcpyAsync(h_left, o.totals + STRORD_T_ACTIVE, 8, hipMemcpyDeviceToHost, st), "D2H string order rest");
+            break;
+        }
+    }
+    // rank, flag, narrow: the first `kept` ranks stay
+    const size_t kept = limit == 0 || limit >= n ? (size_t)n : (size_t)limit;
+    const u32 *const ranked = arr_raw(o.perm);
+    hipLaunchKernelGGL(k_q_order_flag, per_row, b256, 0, st, SJ_ARR(ranked, n, A_SORT), n, (u64)kept, w.w.flag);
+    hipLaunchKernelGGL(k_q_order_flag_sums, per_tile, bqt, 0, st, w.w.flag, n, w.w.tiles);
+    hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.w.tiles, none, none, tiles, none);
+    HIPCHK(hipGetLastError(), "string order flag launch");
+    const std::vector<sjhip_ctx *> parts(1, ctx);
+    rc = where_narrow(ctx, parts, keys, klen, &NO_VALUE, 0, std::vector<QWhere>(1, w.w), std::vector<WhereNew>(1, w.nw),
+                      std::vector<size_t>(1, kept), records, rows);
+    if (rc) return rc;
+    OrderArrays a;
+    rc = reserve_layout(ctx, ctx->d_order, [&](Carve c) { return order_layout(c, kept, SJHIP_COL_STRING, &a); });
+    if (rc) return rc;
+    const u32 *const pre = arr_raw(w.w.pre);
+    hipLaunchKernelGGL(k_q_strord_emit, dim3(((u32)kept + 255) / 256), b256, 0, st, o, SJ_ARR(pre, n, A_WHERE_PRE), (u32)kept,
+                       SJ_ARR(a.order, kept, A_ORDER_OUT), SJ_ARR(a.status, kept, A_ORDER_OUT));
+    HIPCHK(hipGetLastError(), "string order emit launch");
+    HIPCHK(hipStreamSynchronize(st), "string order emit sync");
+    rc = query_bounds_check(ctx);
+    if (rc) return rc;
+    if (*h_left) {
+        ctx_set_error(ctx, "sjhip_order_path_strings: %llu rows are still unordered after %llu rounds, the bound of the longest key (%llu bytes)",
+                      *h_left, (unsigned long long)bound, (unsigned long long)bound * STRORD_CHUNK - 1);
+        return SJHIP_ERR_HIP;
+    }
+    return published(ctx, ctx->res.publish(&ResultState::order, {kept, SJHIP_COL_STRING}));
+}
+
+int sjhip_order_path_strings(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, uint32_t flags, uint64_t limit,
+                             size_t *records, size_t *rows) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!records || !rows) {
+        ctx_set_error(ctx, "sjhip_order_path_strings: a null size pointer");
+        return SJHIP_ERR_ARG;
+    }
+    if (flags & ~SJHIP_ORDER_DESC) {
+        ctx_set_error(ctx, "sjhip_order_path_strings: unknown flag bits 0x%x", flags & ~SJHIP_ORDER_DESC);
+        return SJHIP_ERR_ARG;
+    }
+    WholePath k = {keys, key_lens, n_keys};
+    uint32_t n = 0;
+    int rc = whole_entry(ctx, "sjhip_order_path_strings", "the ranks of shards are not merged", &k, 1, &n);
+    if (rc) return rc;
+    // ---- nothing was touched up to here; from here on the last order is gone ----
+    ctx->res.order.begin();
+    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    if (n == 0) {  // (a selection without rows: it stays as it is)
+        *records = ctx->res.rows.sizes().records, *rows = 0;
+        return published(ctx, ctx->res.publish(&ResultState::order, {0, SJHIP_COL_STRING}));
+    }
+    rc = strord_build(ctx, k.q, k.pth, k.keys, k.klen, n, flags & SJHIP_ORDER_DESC, limit, records, rows);
+    if (rc) {  // half-built: the old selection may have been written over
+        ctx->res.rows.begin();
+        char why[sizeof ctx->err];
+        snprintf(why, sizeof why, "%s", ctx->err);
+        ctx_set_error(ctx, "sjhip_order_path_strings failed and the row selection was given up: %.170s", why);
+    }
+    return rc;
+}
+
 int sjhip_fetch_order(sjhip_ctx *ctx, uint64_t *order, void *values, uint8_t *status) {
     if (!ctx) return SJHIP_ERR_ARG;
     if (!ctx->res.order.exists()) {
@@ -3703,9 +4094,15 @@ int sjhip_fetch_order(sjhip_ctx *ctx, uint64_t *order, void *values, uint8_t *st
         return SJHIP_ERR_ARG;
     }
     const size_t kept = ctx->res.order.sizes().rows;
+    const int kind = ctx->res.order.sizes().kind;
+    if (values && kind == SJHIP_COL_STRING) {
+        ctx_set_error(ctx, "sjhip_fetch_order: a string order has no 8-byte values (pass NULL; the keys are sjhip_extract_path_strings on the kept "
+                           "rows, taken through order[])");
+        return SJHIP_ERR_ARG;
+    }
     if (kept == 0) return SJHIP_OK;  // (nothing was launched, no arena was written)
     OrderArrays a;
-    (void)order_layout(Carve(ctx->d_order.p), kept, &a);
+    (void)order_layout(Carve(ctx->d_order.p), kept, kind, &a);
     const FetchCopy copies[] = {{order, a.order, kept * 8}, {values, a.values, kept * 8}, {status, a.status, kept}};
     return fetch_copies(ctx, copies, 3, "D2H order", "order fetch sync");
 }

@@ -56,7 +56,11 @@ enum ArrId : uint32_t {
     A_SORT, A_SORT_HIST,
     // the unnested rows (query.hip, sjhip_unnest_rows): the target range of every parent row / the status byte of every parent, in
     // the work arrays and in the product / the parent number of every new row / the parent offsets
-    A_UNNEST_RANGE, A_UNNEST_STATUS, A_UNNEST_PARENT, A_UNNEST_OFF
+    A_UNNEST_RANGE, A_UNNEST_STATUS, A_UNNEST_PARENT, A_UNNEST_OFF,
+    // the string order (query.hip, sjhip_order_path_strings): the per-row work arrays (status, key element) / the arrays of the
+    // active entries (row, position, class, chunk key, head and active flags).  Its ranked rows and its sorts are A_SORT, its product
+    // A_ORDER_OUT
+    A_STRORD_ROW, A_STRORD_ACT
 };
 
 #if defined(SJ_DEBUG_BOUNDS)

@@ -1,5 +1,5 @@
-// sj_order.h -- the host-and-device piece of the ordering (query.hip, sjhip_order_path): the order-preserving key of a number (the
-// sort and its pass plan: sj_sort.h).  Plain C++ under SJ_HD, so the CPU build of a test program can run what the kernels run
+// sj_order.h -- the host-and-device pieces of the orderings (query.hip, sjhip_order_path and sjhip_order_path_strings): the
+// order-preserving key of a number and the chunk key of a string (the sort and its pass plan: sj_sort.h).  Plain C++ under SJ_HD, so the CPU build of a test program can run what the kernels run
 // (host_selftest.cpp, tests/test_order_result_state.py).
 //
 // The key of a FLOAT, INT or UINT value is a uint64 whose unsigned order is the order of the kind (the min / max of the aggregates
@@ -23,5 +23,24 @@ SJ_HD u64 agg_unkey(u64 k, int kind) {
     if (kind == ORDER_KIND_INT) return k ^ AGG_SIGN;
     return (k >> 63) ? k ^ AGG_SIGN : ~k;
 }
+
+// The string order compares keys STRORD_CHUNK bytes at a time (query.hip, the k_q_strord_* kernels).  The chunk key of the key
+// bytes[0 .. len) at byte `at`: the top 56 bits are the bytes [at, at + 7) big-endian, zero padded behind the end of the key; the
+// low byte is how many of them are the key's own, min(7, len - at), 0 when at >= len.  The unsigned order of the chunk keys is
+// bytes.Compare on the chunks: where the padded bytes tie, the shorter chunk -- a proper prefix, "a" in front of "a" + NUL -- has the
+// smaller count.  A count below 7 also says that the key ends inside this chunk; 7 that it may go on.  A descending order sorts
+// the complement of the whole chunk key, as the numeric order does with its key.
+static constexpr int STRORD_CHUNK = 7;
+SJ_HD u64 strord_chunk(const u8 *bytes, u64 len, u64 at) {
+    u64 k = 0, count = 0;
+    for (int b = 0; b < STRORD_CHUNK; b++) {
+        k <<= 8;
+        if (at < len && (u64)b < len - at) k |= bytes[at + (u64)b], count++;
+    }
+    return k << 8 | count;
+}
+SJ_HD u32 strord_chunk_count(u64 chunk, bool desc) { return (u32)((desc ? ~chunk : chunk) & 0xffu); }
+// the rounds that order keys of at most `longest` bytes: the round at byte 7 j sees the end of every key shorter than 7 (j + 1)
+SJ_HD u64 strord_max_rounds(u64 longest) { return longest / STRORD_CHUNK + 1; }
 
 }  // namespace sj

@@ -569,11 +569,26 @@ class Context:
         o = Order(nr.value, nw.value, int(kind))
         return self.fetch_order(o) if fetch else o
 
+    def order_path_strings(self, path, descending=False, limit=0, fetch=True):
+        """order_path by a STRING key: the element at `path` as Iter.StringBytes returns it (an empty path: the row's own value) --
+        the rows with a string first, ascending or descending by their unescaped bytes compared as unsigned bytes, a proper prefix in
+        front of the longer key (code point order for UTF-8, not a collation); equal keys in row order, the rows without a string
+        last in row order.  Limit, narrowing and composition are order_path's.
+        -> Order with kind = COL_STRING and values = None: the sorted keys are extract_path_strings on the kept rows taken through
+        `order`"""
+        blob, lens, n = self._keys(path)
+        nr, nw = C.c_size_t(0), C.c_size_t(0)
+        self._check(_lib.lib().sjhip_order_path_strings(self._h, blob if n else None, lens if n else None, n,
+                                                        self.ORDER_DESC if descending else 0, int(limit), C.byref(nr), C.byref(nw)))
+        o = Order(nr.value, nw.value, self.COL_STRING)
+        return self.fetch_order(o) if fetch else o
+
     def fetch_order(self, o):
-        """the arrays of the last order_path (o: what it returned with fetch=False) -> o, filled"""
+        """the arrays of the last order_path / order_path_strings (o: what it returned with fetch=False) -> o, filled (a string
+        order has no values: None)"""
         o.order, o.status = np.empty(o.rows, dtype=np.uint64), np.empty(o.rows, dtype=np.uint8)
-        o.values = np.empty(o.rows, dtype=self._COL_DTYPES[o.kind])
-        ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+        o.values = None if o.kind == self.COL_STRING else np.empty(o.rows, dtype=self._COL_DTYPES[o.kind])
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
         self._check(_lib.lib().sjhip_fetch_order(self._h, ptr(o.order), ptr(o.values), ptr(o.status)))
         return o
 
@@ -693,8 +708,8 @@ class Groups:
 
 
 class Order:
-    """what Context.order_path returns: the records, the rows kept and the kind of the keys, and after the fetch order, values and
-    status in rank order (see order_path)"""
+    """what Context.order_path / order_path_strings return: the records, the rows kept and the kind of the keys, and after the fetch
+    order, values (None for a string order) and status in rank order (see order_path)"""
 
     def __init__(self, records, rows, kind):
         self.records, self.rows, self.kind = records, rows, kind
