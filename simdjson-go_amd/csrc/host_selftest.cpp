@@ -867,6 +867,14 @@ extern "C" void sj_selftest_sort_plan(uint64_t groups, uint64_t and_, uint64_t o
     out2[0] = sj::group_pass_mask(groups), out2[1] = sj::order_pass_mask(and_, or_);
 }
 
+// sj_group.h: the hash of a key, the equality of two keys and the capacity of the key table, as k_q_group_keys / k_q_group_insert run
+// them (tests/group_table.py restates the hash and inverts it; tests/test_group_table.py holds the two together)
+#include "sj_group.h"
+extern "C" uint64_t sj_selftest_group_hash_bytes(const uint8_t *s, uint64_t len) { return sj::group_hash_bytes(s, len); }
+extern "C" uint64_t sj_selftest_group_hash_int(uint64_t x) { return sj::group_hash_int(x); }
+extern "C" int sj_selftest_group_bytes_equal(const uint8_t *a, const uint8_t *b, uint64_t len) { return sj::group_bytes_equal(a, b, len) ? 1 : 0; }
+extern "C" uint64_t sj_selftest_group_table_capacity(uint64_t n) { return sj::group_table_capacity(n); }
+
 // sj_table.h / sj_tablewalk.h: the plan of a table and its one-walk evaluation, as the kernel k_q_table_walk runs them.
 //   sj_selftest_table_plan  -> 0 and the plan: nodes_out[j * 6 ..] = key begin, key end (in blob_out), parent (255: the root),
 //                           first child, children, columns mask of node j; or the TablePlanError of a refused table

@@ -14,7 +14,10 @@ column at a second path.
 
 GROUP_SORT_TILE (the rows of one tile of the device's sort by code, the largest tile of the new kernels), GROUP_RADIX_BITS (the
 bits of a sort pass) and QTILE (the tile of the scans) come from csrc/sj_sort.h and csrc/sj_tapewalk.h; the shapes of
-tests/test_gpu_group.py come from them.  Pinned by tests/test_group_walk.py."""
+tests/test_gpu_group.py come from them.  Pinned by tests/test_group_walk.py.
+
+The hash, the capacity and the probing of the device's key table are no part of this restatement (a dict stands in for them);
+tests/group_table.py restates those, and builds the keys that put the table on its seams."""
 import aggregate_walk as AW
 import column_walk as CW
 
