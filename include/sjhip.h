@@ -502,6 +502,36 @@ int sjhip_fetch_order(sjhip_ctx *ctx, uint64_t *order /* [rows] */, void *values
  * for every byte position that differs, and one wait of the host.  The rounds end with the longest key. */
 int sjhip_order_path_strings(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, uint32_t flags, uint64_t limit,
                              size_t *records, size_t *rows);
+/* Order rows by SEVERAL keys: "tickets by Make, then by Fine descending", "statuses by user.screen_name, then newest first" -- the
+ * order a stable sort by the tuple of up to SJHIP_ORDER_MAX_KEYS key columns gives, ties refined column by column on the device.
+ *   keys, key_lens, path_lens   laid out as in sjhip_extract_table: the keys of all paths end to end, column c owns the next
+ *                  path_lens[c] entries of key_lens.  path_lens[c] == 0: the key is the row's own value.  Each path has the limits of
+ *                  sjhip_find_path; all paths together hold at most 32 keys and 1024 bytes.
+ *   kinds[c]       SJHIP_COL_FLOAT / INT / UINT: key and status byte are sjhip_order_path's (the amd64 results at 2^63 and 2^64 and
+ *                  the float total order with -0.0 below +0.0 included); SJHIP_COL_STRING: those of sjhip_order_path_strings (the
+ *                  unescaped bytes, compared as bytes.Compare, in both copy modes).  Anything else is SJHIP_ERR_ARG and
+ *                  sjhip_last_error names the column and the kind.
+ *   flags[c]       SJHIP_ORDER_DESC per column; any other bit is SJHIP_ERR_ARG.  flags == NULL: all ascending.
+ *   n_cols         1 to SJHIP_ORDER_MAX_KEYS.
+ *   order          rows are compared on column 0: the rows whose status there is SJHIP_COL_OK first, ascending by key or, with
+ *                  SJHIP_ORDER_DESC, in the reverse order of the distinct keys, the rows without an OK key behind them (NULLS LAST
+ *                  in both directions).  Rows that tie on column 0 -- the rows without an OK key there tie with each other -- are
+ *                  compared on column 1 in the same way, and so on: a column's rows without a key come last within their tie class,
+ *                  not last overall.  Rows that tie on every column stay in row order.
+ * With n_cols == 1 the call is sjhip_order_path or sjhip_order_path_strings, bit for bit: the same selection and the same order[].
+ * Everything else -- limit (applied once, at the end), the narrowing of the selection, *records / *rows, the composition with
+ * sjhip_where_path, sjhip_unnest_rows and further order calls, "no rows launches nothing and publishes an empty order", the 2^30
+ * rows, the refusal of a sharded result, "argument errors touch nothing" and "a later failure gives the selection up and leaves no
+ * order" -- is sjhip_order_path's, see there.  The product is the context's one order: sjhip_fetch_order(order, NULL, status)
+ * delivers it, status[i] being the status byte ON COLUMN 0 of the row of rank i -- the only column every row is evaluated on.  It
+ * has no 8-byte values: a non-NULL `values` is SJHIP_ERR_ARG.  The sorted keys are sjhip_extract_table on the kept rows, taken
+ * through order[].
+ * The cost is one walk of every row for column 0 and its rounds (a numeric column has one, a string column one per 7 key bytes that
+ * rows still tie on); a column behind the first walks and sorts only the rows that still tie in front of it, and is skipped
+ * when none does.  Every round is one wait of the host. */
+#define SJHIP_ORDER_MAX_KEYS 8
+int sjhip_order_paths(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, const uint32_t *path_lens, const int *kinds,
+                      const uint32_t *flags, uint32_t n_cols, uint64_t limit, size_t *records, size_t *rows);
 /* Unnest rows: the elements of the ARRAY at `path` of every ROW become the rows -- a second Iter.FindElement(path...) -> Iter.Array()
  * -> Array.Iter() / Advance inside the loop over the outer elements: statuses[].entities.hashtags[], performances[].seatCategories[]
  * .areas[], items[].tags[].  Everything that runs on "the rows of the selection in force" then runs on the inner elements.

@@ -863,6 +863,11 @@ extern "C" void sj_selftest_strord_chunk(const uint8_t *bytes, uint64_t len, uin
     out3[1] = sj::strord_chunk_count(out3[0], desc != 0);
     out3[2] = sj::strord_max_rounds(len);
 }
+// the order by several keys (sjhip_order_paths): the second sort's key of an entry, and whether it goes on to the column's next round,
+// as k_q_mkord_chunks and k_q_mkord_place compute them; and the column limit the header mirrors
+extern "C" uint32_t sj_selftest_mkord_class_key(uint32_t cls, int missing) { return sj::mkord_class_key(cls, missing != 0); }
+extern "C" int sj_selftest_mkord_stays(int missing, int alone, int chunk_full) { return sj::mkord_stays(missing != 0, alone != 0, chunk_full != 0) ? 1 : 0; }
+extern "C" int sj_selftest_order_max_keys() { return sj::ORDER_MAX_KEYS; }
 extern "C" void sj_selftest_sort_plan(uint64_t groups, uint64_t and_, uint64_t or_, uint32_t *out2) {
     out2[0] = sj::group_pass_mask(groups), out2[1] = sj::order_pass_mask(and_, or_);
 }

@@ -2018,6 +2018,202 @@ __global__ __launch_bounds__(256) void k_q_strord_emit(QStrOrd o, Arr<const u32>
     status[p] = o.status[row];
 }
 
+// ---- several keys: the rows ranked by up to SJHIP_ORDER_MAX_KEYS key columns of mixed kinds and directions (sjhip_order_paths) -------
+// The order is the one a stable sort by the tuple gives.  It is refined column by column on the state of the string order: `perm`,
+// the rows in rank order as far as known, and the ACTIVE entries (row, position, class) in ascending position -- the members of the
+// classes of tied rows that are not finished.  Two things differ.  The rows without an OK key on a column are not parked: they
+// lie behind the others of their class and tie there, so they still meet the later columns; the sort by class takes
+// mkord_class_key = class << 1 | missing (sj_order.h).  And entries leave a column at different rounds, so what the next column works
+// on is not queued but rebuilt from a boundary byte per position, bnd[p] = 1 where a class begins (bnd[n] = 1):
+//   k_q_mkord_init     all n rows active in row order, one class; perm = the rows; bnd = 1 at 0 and at n
+//   column c:
+//   k_q_mkord_keys     one lane per ACTIVE entry: path, status and, for a numeric column, the sort key agg_key (complemented for
+//                      a descending column); for a string column the tape index of the element, and the tile's longest key.  A column
+//                      behind the first walks only the rows that still tie
+//   round j (a numeric column has one, a string column strord_max_rounds(longest) at most):
+//   k_q_mkord_chunks   the round's chunk key of every active entry -- the numeric key, or the string's chunk at byte 7 j; 0 for a
+//                      missing row -- and its class key; per tile the AND and the OR of the chunk keys of the OK rows and of the class
+//                      keys.  k_q_strord_fold joins them for the host's one copy per round, which plans both sorts (order_pass_mask:
+//                      a round without missing rows plans no extra digit)
+//   the sort           as in the string order: sort_enqueue<u64> by chunk key, k_q_strord_classes, sort_enqueue<u32> by class key
+//   k_q_mkord_place    the i-th sorted entry goes to the i-th active position; a HEAD differs in (class key, chunk key) from the
+//                      entry in front and sets bnd at its position; an entry STAYS in the column iff mkord_stays.  Then
+//                      k_tw_scan_sums and k_q_strord_compact as they are
+//   between columns:
+//   k_q_mkord_bounds   the tile sums of bnd and of "not alone in its class", !(bnd[p] && bnd[p + 1])
+//   k_q_mkord_rebuild  behind their scan: the entries that are not alone, (perm[p], p, the heads up to and including p)
+// Nothing active: the remaining columns are skipped.  The flags, the narrowing and k_q_strord_emit (with column 0's status, the
+// only one every row has) follow as in the single-key orders.  No atomics anywhere.
+static_assert(ORDER_MAX_KEYS == SJHIP_ORDER_MAX_KEYS, "sj_order.h mirrors include/sjhip.h");
+struct QMkOrd {
+    QStrOrd s;      // n; status, kidx: [n] the status and the key / key element of the row ON THE COLUMN AT WORK; the rest as there
+    Arr<u32> ckey;  // [n] the class key of active entry i
+    Arr<u8> bnd;    // [n + 1] 1 where a class begins
+};
+__global__ __launch_bounds__(256) void k_q_mkord_init(QMkOrd o) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x, n = o.s.n;
+    if (i >= n) return;
+    o.s.perm[i] = i;
+    o.s.row[i] = i;
+    o.s.pos[i] = i;
+    o.s.cls[i] = 1;
+    o.bnd[i] = i == 0 ? 1 : 0;
+    if (i == 0) {
+        o.bnd[n] = 1;
+        o.s.totals[STRORD_T_ACTIVE] = n;
+    }
+}
+// active: where the device keeps the number of active entries; kind: SJHIP_COL_FLOAT / INT / UINT or SJHIP_COL_STRING
+__global__ __launch_bounds__(QT) void k_q_mkord_keys(QView q, QPath pth, QMkOrd o, int kind, u32 desc, const unsigned long long *active) {
+    __shared__ unsigned long long s_len[QT / 64];
+    const int tid = threadIdx.x;
+    const u32 m = (u32)*active;
+    u64 longest = 0;
+#pragma unroll 1
+    for (int k = 0; k < QI; k++) {
+        const u32 i = blockIdx.x * QTILE + k * QT + tid;
+        if (i >= m) break;
+        const u32 r = o.s.row[i];
+        const u64 v = pth.n ? record_find_path(q, pth, r) : row_value(q, r);  // (no keys: the row's own value)
+        u64 x = 0, key = 0;
+        int st;
+        if (v >= SJHIP_PATH_NOT_OBJECT) st = path_status(v);
+        else if (kind == SJHIP_COL_STRING) {
+            st = element_text_len(q, v, false, &x);
+            if (st == SJHIP_COL_OK) {
+                key = v;
+                longest = x > longest ? x : longest;
+            }
+        } else {
+            st = element_to(q, v, kind, &x);
+            if (st == SJHIP_COL_OK) {
+                key = agg_key(x, kind);
+                if (desc) key = ~key;
+            }
+        }
+        o.s.status[r] = (u8)st;
+        o.s.kidx[r] = key;
+    }
+    longest = block_max(longest, s_len);
+    if (tid == 0) o.s.tiles_len[blockIdx.x] = longest;
+}
+// at: the byte the round's chunks of a string column begin at; the first input of the sort
+__global__ __launch_bounds__(QT) void k_q_mkord_chunks(QView q, QMkOrd o, int kind, u32 desc, const unsigned long long *active, u64 at,
+                                                      Arr<u64> sort_keys, Arr<u32> sort_rows) {
+    __shared__ unsigned long long s_k[2][QT / 64], s_c[2][QT / 64];
+    const int tid = threadIdx.x;
+    const u32 m = (u32)*active;
+    u64 kall = ~0ull, kany = 0, call = ~0ull, cany = 0;
+#pragma unroll 1
+    for (int k = 0; k < QI; k++) {
+        const u32 i = blockIdx.x * QTILE + k * QT + tid;
+        if (i >= m) break;
+        const u32 r = o.s.row[i];
+        const bool missing = o.s.status[r] != SJHIP_COL_OK;
+        u64 key = 0;
+        if (!missing) {
+            key = o.s.kidx[r];
+            if (kind == SJHIP_COL_STRING) {
+                const u64 w = q.tape[key], len = q.tape[key + 1];
+                key = strord_chunk(str_bytes(q, w, len), len, at);
+                if (desc) key = ~key;
+            }
+            kall &= key, kany |= key;
+        }
+        const u32 c = mkord_class_key(o.s.cls[i], missing);
+        o.s.chunk[i] = key;
+        o.ckey[i] = c;
+        sort_keys[i] = key;
+        sort_rows[i] = i;
+        call &= c, cany |= c;
+    }
+    block_and_or(kall, kany, s_k);
+    block_and_or(call, cany, s_c);
+    if (tid == 0) {
+        o.s.tiles_kand[blockIdx.x] = kall, o.s.tiles_kor[blockIdx.x] = kany;
+        o.s.tiles_cand[blockIdx.x] = call, o.s.tiles_cor[blockIdx.x] = cany;
+    }
+}
+// sorted: the m active entries ordered by (class key, chunk key).  A thread takes QI consecutive ones and looks at both neighbours
+__global__ __launch_bounds__(QT) void k_q_mkord_place(QMkOrd o, u32 m, Arr<const u32> sorted, u32 is_string, u32 desc) {
+    __shared__ unsigned long long s_w[QT / 64];
+    const u32 base = blockIdx.x * QTILE + threadIdx.x * QI;
+    u32 e[QI + 2], c[QI + 2];
+    u64 key[QI + 2];
+    bool in[QI + 2];
+#pragma unroll
+    for (int k = 0; k < QI + 2; k++) {
+        const u32 i = base + (u32)k - 1u;  // (base = 0, k = 0: wraps beyond m)
+        in[k] = i < m;
+        e[k] = in[k] ? sorted[i] : 0u;
+        c[k] = in[k] ? o.ckey[e[k]] : 0u;
+        key[k] = in[k] ? o.s.chunk[e[k]] : 0ull;
+    }
+    unsigned long long heads = 0, active = 0, tot_h = 0, tot_a = 0;
+#pragma unroll
+    for (int k = 1; k <= QI; k++) {
+        if (!in[k]) break;
+        const bool head = !in[k - 1] || c[k] != c[k - 1] || key[k] != key[k - 1];
+        const bool next_head = !in[k + 1] || c[k + 1] != c[k] || key[k + 1] != key[k];
+        const bool full = is_string && strord_chunk_count(key[k], desc != 0) == (u32)STRORD_CHUNK;
+        const bool stays = mkord_stays((c[k] & 1u) != 0, head && next_head, full);
+        const u32 i = base + (u32)k - 1u, p = o.s.pos[i];
+        o.s.perm[p] = o.s.row[e[k]];
+        if (head) o.bnd[p] = 1;
+        o.s.flags[i] = (u8)((head ? 1u : 0u) | (stays ? 2u : 0u));
+        heads += head ? 1u : 0u;
+        active += stays ? 1u : 0u;
+    }
+    (void)block_excl_sum(heads, s_w, (int)threadIdx.x, &tot_h);
+    (void)block_excl_sum(active, s_w, (int)threadIdx.x, &tot_a);
+    if (threadIdx.x == 0) o.s.tiles_head[blockIdx.x] = tot_h, o.s.tiles_act[blockIdx.x] = tot_a;
+}
+// over the n positions: the classes that begin in the tile, and its positions that are not alone in their class
+__global__ __launch_bounds__(QT) void k_q_mkord_bounds(QMkOrd o) {
+    __shared__ unsigned long long s_w[QT / 64];
+    const u32 n = o.s.n, base = blockIdx.x * QTILE + threadIdx.x * QI;
+    unsigned long long heads = 0, active = 0, tot_h = 0, tot_a = 0;
+#pragma unroll
+    for (int k = 0; k < QI; k++) {
+        const u32 p = base + k;
+        if (p >= n) break;
+        const u32 b = o.bnd[p];
+        heads += b;
+        active += b && o.bnd[p + 1] ? 0u : 1u;
+    }
+    (void)block_excl_sum(heads, s_w, (int)threadIdx.x, &tot_h);
+    (void)block_excl_sum(active, s_w, (int)threadIdx.x, &tot_a);
+    if (threadIdx.x == 0) o.s.tiles_head[blockIdx.x] = tot_h, o.s.tiles_act[blockIdx.x] = tot_a;
+}
+// (tiles_head and tiles_act have been scanned)  The next column's active entries, in position order
+__global__ __launch_bounds__(QT) void k_q_mkord_rebuild(QMkOrd o) {
+    __shared__ unsigned long long s_w[QT / 64];
+    const u32 n = o.s.n, base = blockIdx.x * QTILE + threadIdx.x * QI;
+    u32 b[QI + 1], heads = 0, active = 0;
+#pragma unroll
+    for (int k = 0; k <= QI; k++) b[k] = base + k <= n ? o.bnd[base + k] : 1u;
+#pragma unroll
+    for (int k = 0; k < QI; k++) {
+        if (base + k >= n) break;
+        heads += b[k];
+        active += b[k] && b[k + 1] ? 0u : 1u;
+    }
+    u32 cl = (u32)(o.s.tiles_head[blockIdx.x] + block_excl_sum(heads, s_w, (int)threadIdx.x, nullptr));
+    u32 at = (u32)(o.s.tiles_act[blockIdx.x] + block_excl_sum(active, s_w, (int)threadIdx.x, nullptr));
+#pragma unroll
+    for (int k = 0; k < QI; k++) {
+        const u32 p = base + k;
+        if (p >= n) break;
+        cl += b[k];
+        if (!(b[k] && b[k + 1])) {
+            o.s.row[at] = o.s.perm[p];
+            o.s.pos[at] = p;
+            o.s.cls[at] = cl;
+            at++;
+        }
+    }
+}
+
 }  // namespace
 
 namespace sj {
@@ -3832,10 +4028,10 @@ struct OrderArrays {
     u64 *order, *values;
     u8 *status;
 };
-// (kind SJHIP_COL_STRING -- sjhip_order_path_strings -- has no values)
+// (kind SJHIP_COL_STRING -- sjhip_order_path_strings -- and ORDER_KIND_MULTI -- sjhip_order_paths -- have no values)
 static size_t order_layout(Carve c, size_t rows, int kind, OrderArrays *o) {
     o->order = c.take<u64>(rows);
-    o->values = kind == SJHIP_COL_STRING ? nullptr : c.take<u64>(rows);
+    o->values = kind == SJHIP_COL_STRING || kind == ORDER_KIND_MULTI ? nullptr : c.take<u64>(rows);
     o->status = c.take<u8>(rows);
     return c.used;
 }
@@ -4087,6 +4283,240 @@ int sjhip_order_path_strings(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t
     return rc;
 }
 
+// ---- several keys --------------------------------------------------------------------------------------------------------------------
+// sjhip_order_paths is the string order's build with the rounds of every column in turn (the k_q_mkord_* kernels, and the
+// k_q_strord_* ones whose signatures fit).  The work arrays (MkOrdWork) lie in d_kat, laid out once for the row count, the arrays of
+// the narrowing behind them; the product is the order's, without values, its kind ORDER_KIND_MULTI.  One host round trip per round:
+// the active count and the ANDs / ORs that plan the round's two sorts (a string column's first also brings its longest key).
+struct MkOrdCol {
+    QView q;  // (the keys of the column's path are the view's)
+    QPath pth;
+    int kind;
+    u32 desc;
+};
+struct MkOrdWork {
+    QMkOrd o;
+    u8 *status0, *status_c;  // [n] each: column 0's statuses, and those of the column at work behind it
+    SortWork<u64> sort;      // by chunk key
+    SortWork<u32> csort;     // by class key
+    QWhere w;
+    WhereNew nw;
+    unsigned long long *w_totals;
+};
+static size_t mkord_work_layout(Carve c, const sjhip_ctx *ctx, uint32_t n, MkOrdWork *w) {
+    const u32 tiles = (n + QTILE - 1) / QTILE;
+    QStrOrd &o = w->o.s;
+    o.totals = c.take<unsigned long long>(32);
+    o.n = n;
+    o.desc = 0;
+    w->status0 = c.take<u8>(n), w->status_c = c.take<u8>(n);
+    u8 *const flags = c.take<u8>(n), *const bnd = c.take<u8>((size_t)n + 1);
+    u64 *const kidx = c.take<u64>(n), *const chunk = c.take<u64>(n);
+    u32 *const perm = c.take<u32>(n), *const ckey = c.take<u32>(n);
+    u32 *const row = c.take<u32>(n), *const pos = c.take<u32>(n), *const cls = c.take<u32>(n);
+    u32 *const row_out = c.take<u32>(n), *const pos_out = c.take<u32>(n), *const cls_out = c.take<u32>(n);
+    o.status = SJ_ARR(w->status0, n, A_MKORD_ROW);
+    o.kidx = SJ_ARR(kidx, n, A_MKORD_ROW);
+    o.perm = SJ_ARR(perm, n, A_SORT);
+    o.flags = SJ_ARR(flags, n, A_STRORD_ACT);
+    o.chunk = SJ_ARR(chunk, n, A_STRORD_ACT);
+    o.row = SJ_ARR(row, n, A_STRORD_ACT), o.pos = SJ_ARR(pos, n, A_STRORD_ACT), o.cls = SJ_ARR(cls, n, A_STRORD_ACT);
+    o.row_out = SJ_ARR(row_out, n, A_STRORD_ACT), o.pos_out = SJ_ARR(pos_out, n, A_STRORD_ACT), o.cls_out = SJ_ARR(cls_out, n, A_STRORD_ACT);
+    w->o.ckey = SJ_ARR(ckey, n, A_MKORD_ACT);
+    w->o.bnd = SJ_ARR(bnd, (size_t)n + 1, A_MKORD_BND);
+    unsigned long long **const per_tile[] = {&o.tiles_ok,   &o.tiles_len, &o.tiles_kand, &o.tiles_kor,
+                                             &o.tiles_cand, &o.tiles_cor, &o.tiles_head, &o.tiles_act};
+    for (unsigned long long **t : per_tile) *t = c.take<unsigned long long>(tiles);
+    sort_carve(c, n, &w->sort);
+    sort_carve(c, n, &w->csort);
+    (void)(c.used = where_layout(c, ctx, n, &w->w, &w->nw, &w->w_totals));
+    return c.used;
+}
+// behind the checks of sjhip_order_paths: cols[c].q is the view of the n > 0 rows in force
+static int mkord_build(sjhip_ctx *ctx, const MkOrdCol *cols, uint32_t n_cols, const uint8_t *keys, size_t klen, uint32_t n, uint64_t limit,
+                       size_t *records, size_t *rows) {
+    MkOrdWork w;
+    int rc = reserve_layout(ctx, ctx->d_kat, [&](Carve c) { return mkord_work_layout(c, ctx, n, &w); });
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const u32 tiles = (n + QTILE - 1) / QTILE;
+    const dim3 per_row((n + 255) / 256), per_tile(tiles), b256(256), bqt(QT), one(1), wide(1024);
+    unsigned long long *const none = nullptr;
+    QMkOrd &o = w.o;
+    u64 *const keys0 = w.sort.keys[0];
+    u32 *const rows0 = w.sort.rows[0], *const ckeys0 = w.csort.keys[0], *const crows0 = w.csort.rows[0];
+    const unsigned long long *const active = o.s.totals + STRORD_T_ACTIVE;
+    HIPCHK(hipMemsetAsync(o.s.totals, 0, 256, st), "order by several keys totals memset");
+    hipLaunchKernelGGL(k_q_mkord_init, per_row, b256, 0, st, o);
+    unsigned long long *const h = (unsigned long long *)(ctx->h_scratch + 512), *const h_left = (unsigned long long *)(ctx->h_scratch + 1024);
+    for (uint32_t c = 0; c < n_cols; c++) h_left[c] = 0;
+    u64 left_bound[ORDER_MAX_KEYS] = {};
+    bool tied = true;  // rows still tie: the next column has work
+    for (uint32_t c = 0; c < n_cols && tied; c++) {
+        const MkOrdCol &col = cols[c];
+        const bool is_string = col.kind == SJHIP_COL_STRING;
+        if (c > 0) {  // the entries that are not alone in their class, from the boundaries
+            hipLaunchKernelGGL(k_q_mkord_bounds, per_tile, bqt, 0, st, o);
+            hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, o.s.tiles_head, o.s.tiles_act, none, tiles, o.s.totals + STRORD_T_HEADS);
+            hipLaunchKernelGGL(k_q_mkord_rebuild, per_tile, bqt, 0, st, o);
+            o.s.status = SJ_ARR(w.status_c, n, A_MKORD_ROW);
+        }
+        hipLaunchKernelGGL(k_q_mkord_keys, per_tile, bqt, 0, st, col.q, col.pth, o, col.kind, col.desc, active);
+        u64 bound = 1;  // of the column's rounds: a string column's is known after its first copy
+        u32 m_max = n;  // the round's active entries are at most this many
+        for (u64 round = 0;; round++) {
+            // the round's chunk keys, and its one round trip
+            const u32 ctiles = (m_max + QTILE - 1) / QTILE;
+            hipLaunchKernelGGL(k_q_mkord_chunks, dim3(ctiles), bqt, 0, st, col.q, o, col.kind, col.desc, active, round * (u64)STRORD_CHUNK,
+                               SJ_ARR(keys0, n, A_SORT), SJ_ARR(rows0, n, A_SORT));
+            hipLaunchKernelGGL(k_q_strord_fold, one, bqt, 0, st, o.s, ctiles, round == 0 ? tiles : 0u);
+            HIPCHK(hipGetLastError(), "order by several keys chunk launch");
+            HIPCHK(hipMemcpyAsync(h, o.s.totals, STRORD_T_WORDS * 8, hipMemcpyDeviceToHost, st), "D2H order by several keys totals");
+            HIPCHK(hipStreamSynchronize(st), "order by several keys sync");
+            rc = query_bounds_check(ctx);
+            if (rc) return rc;
+            if (round == 0 && is_string) bound = strord_max_rounds(h[STRORD_T_LONGEST]);
+            const u32 m = (u32)h[STRORD_T_ACTIVE];
+            if (m < 2) {  // (a class has two members at least: nothing is active)
+                tied = round > 0;  // (behind the column's first round the classes it finished may still hold ties)
+                break;
+            }
+            // stable by (class key, chunk key): the chunk keys first -- of the OK rows; without one, no digit --, then the class keys
+            const u64 kand = h[STRORD_T_ANDOR], kor = h[STRORD_T_ANDOR + 1];
+            const u32 kmask = (kand & ~kor) ? 0u : order_pass_mask(kand, kor);
+            const u32 cmask = order_pass_mask(h[STRORD_T_ANDOR + 2], h[STRORD_T_ANDOR + 3]);
+            const u32 *sorted = w.sort.rows[sort_enqueue(st, m, n, kmask, true, w.sort)];
+            const dim3 per_entry((m + 255) / 256), per_etile((m + QTILE - 1) / QTILE);
+            if (cmask) {
+                QStrOrd by_class = o.s;
+                by_class.cls = o.ckey;
+                hipLaunchKernelGGL(k_q_strord_classes, per_entry, b256, 0, st, by_class, m, SJ_ARR(sorted, n, A_SORT), SJ_ARR(ckeys0, n, A_SORT),
+                                   SJ_ARR(crows0, n, A_SORT));
+                sorted = w.csort.rows[sort_enqueue(st, m, n, cmask, true, w.csort)];
+            }
+            // place, mark; a string column renumbers and compacts what stays in it
+            hipLaunchKernelGGL(k_q_mkord_place, per_etile, bqt, 0, st, o, m, SJ_ARR(sorted, n, A_SORT), is_string ? 1u : 0u, col.desc);
+            if (is_string) {
+                hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, o.s.tiles_head, o.s.tiles_act, none, per_etile.x, o.s.totals + STRORD_T_HEADS);
+                hipLaunchKernelGGL(k_q_strord_compact, per_etile, bqt, 0, st, o.s, m, SJ_ARR(sorted, n, A_SORT));
+                std::swap(o.s.row, o.s.row_out), std::swap(o.s.pos, o.s.pos_out), std::swap(o.s.cls, o.s.cls_out);
+            }
+            HIPCHK(hipGetLastError(), "order by several keys round launch");
+            m_max = m;
+            if (round + 1 >= bound) {  // the column's last round: what a string column left active (nothing) is looked at with the emit's wait
+                if (is_string) {
+                    HIPCHK(hipMemcpyAsync(h_left + c, o.s.totals + STRORD_T_ACTIVE, 8, hipMemcpyDeviceToHost, st), "D2H order by several keys rest");
+                    left_bound[c] = bound;
+                }
+                break;
+            }
+        }
+    }
+    // rank, flag, narrow: the first `kept` ranks stay
+    const size_t kept = limit == 0 || limit >= n ? (size_t)n : (size_t)limit;
+    const u32 *const ranked = arr_raw(o.s.perm);
+    hipLaunchKernelGGL(k_q_order_flag, per_row, b256, 0, st, SJ_ARR(ranked, n, A_SORT), n, (u64)kept, w.w.flag);
+    hipLaunchKernelGGL(k_q_order_flag_sums, per_tile, bqt, 0, st, w.w.flag, n, w.w.tiles);
+    hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.w.tiles, none, none, tiles, none);
+    HIPCHK(hipGetLastError(), "order by several keys flag launch");
+    const std::vector<sjhip_ctx *> parts(1, ctx);
+    rc = where_narrow(ctx, parts, keys, klen, &NO_VALUE, 0, std::vector<QWhere>(1, w.w), std::vector<WhereNew>(1, w.nw),
+                      std::vector<size_t>(1, kept), records, rows);
+    if (rc) return rc;
+    OrderArrays a;
+    rc = reserve_layout(ctx, ctx->d_order, [&](Carve c) { return order_layout(c, kept, ORDER_KIND_MULTI, &a); });
+    if (rc) return rc;
+    const u32 *const pre = arr_raw(w.w.pre);
+    QStrOrd by_first = o.s;  // (column 0's status: the only column every row is evaluated on)
+    by_first.status = SJ_ARR(w.status0, n, A_MKORD_ROW);
+    hipLaunchKernelGGL(k_q_strord_emit, dim3(((u32)kept + 255) / 256), b256, 0, st, by_first, SJ_ARR(pre, n, A_WHERE_PRE), (u32)kept,
+                       SJ_ARR(a.order, kept, A_ORDER_OUT), SJ_ARR(a.status, kept, A_ORDER_OUT));
+    HIPCHK(hipGetLastError(), "order by several keys emit launch");
+    HIPCHK(hipStreamSynchronize(st), "order by several keys emit sync");
+    rc = query_bounds_check(ctx);
+    if (rc) return rc;
+    for (uint32_t c = 0; c < n_cols; c++)
+        if (h_left[c]) {
+            ctx_set_error(ctx, "sjhip_order_paths: column %u: %llu rows are still unordered after %llu rounds, the bound of its longest key", c,
+                          h_left[c], (unsigned long long)left_bound[c]);
+            return SJHIP_ERR_HIP;
+        }
+    return published(ctx, ctx->res.publish(&ResultState::order, {kept, ORDER_KIND_MULTI}));
+}
+
+int sjhip_order_paths(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, const uint32_t *path_lens, const int *kinds,
+                      const uint32_t *flags, uint32_t n_cols, uint64_t limit, size_t *records, size_t *rows) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!records || !rows) {
+        ctx_set_error(ctx, "sjhip_order_paths: a null size pointer");
+        return SJHIP_ERR_ARG;
+    }
+    if (n_cols < 1 || n_cols > (uint32_t)SJHIP_ORDER_MAX_KEYS) {
+        ctx_set_error(ctx, "sjhip_order_paths: %u key columns (1 to %d)", n_cols, SJHIP_ORDER_MAX_KEYS);
+        return SJHIP_ERR_ARG;
+    }
+    if (!path_lens || !kinds) {
+        ctx_set_error(ctx, "sjhip_order_paths: a null argument (path_lens, kinds)");
+        return SJHIP_ERR_ARG;
+    }
+    size_t n_keys = 0, bytes = 0;
+    for (uint32_t c = 0; c < n_cols; c++) {
+        const int kind = kinds[c];
+        if (kind != SJHIP_COL_FLOAT && kind != SJHIP_COL_INT && kind != SJHIP_COL_UINT && kind != SJHIP_COL_STRING) {
+            ctx_set_error(ctx, "sjhip_order_paths: column %u: key kind %d is not SJHIP_COL_FLOAT, SJHIP_COL_INT, SJHIP_COL_UINT or SJHIP_COL_STRING", c,
+                          kind);
+            return SJHIP_ERR_ARG;
+        }
+        if (flags && (flags[c] & ~SJHIP_ORDER_DESC)) {
+            ctx_set_error(ctx, "sjhip_order_paths: column %u: unknown flag bits 0x%x", c, flags[c] & ~SJHIP_ORDER_DESC);
+            return SJHIP_ERR_ARG;
+        }
+        n_keys += path_lens[c];
+        if (n_keys > (size_t)TABLE_MAX_KEYS) {
+            ctx_set_error(ctx, "sjhip_order_paths: the paths hold more than %d keys together (found at column %u)", TABLE_MAX_KEYS, c);
+            return SJHIP_ERR_ARG;
+        }
+    }
+    if (n_keys && (!keys || !key_lens)) {
+        ctx_set_error(ctx, "sjhip_order_paths: a null argument (%zu keys are announced)", n_keys);
+        return SJHIP_ERR_ARG;
+    }
+    for (size_t j = 0; j < n_keys; j++) bytes += key_lens[j];
+    if (bytes > (size_t)TABLE_MAX_BYTES) {
+        ctx_set_error(ctx, "sjhip_order_paths: the keys of the paths are longer than %d bytes together", TABLE_MAX_BYTES);
+        return SJHIP_ERR_ARG;
+    }
+    std::vector<WholePath> k(n_cols);
+    size_t key_at = 0, byte_at = 0;
+    for (uint32_t c = 0; c < n_cols; c++) {
+        k[c].keys = path_lens[c] ? keys + byte_at : nullptr;
+        k[c].key_lens = path_lens[c] ? key_lens + key_at : nullptr;
+        k[c].n_keys = path_lens[c];
+        for (uint32_t j = 0; j < path_lens[c]; j++) byte_at += key_lens[key_at + j];
+        key_at += path_lens[c];
+    }
+    uint32_t n = 0;
+    int rc = whole_entry(ctx, "sjhip_order_paths", "the ranks of shards are not merged", k.data(), (int)n_cols, &n);
+    if (rc) return rc;
+    // ---- nothing was touched up to here; from here on the last order is gone ----
+    ctx->res.order.begin();
+    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    if (n == 0) {  // (a selection without rows: it stays as it is)
+        *records = ctx->res.rows.sizes().records, *rows = 0;
+        return published(ctx, ctx->res.publish(&ResultState::order, {0, ORDER_KIND_MULTI}));
+    }
+    std::vector<MkOrdCol> cols(n_cols);
+    for (uint32_t c = 0; c < n_cols; c++) cols[c] = {k[c].q, k[c].pth, kinds[c], flags ? flags[c] & SJHIP_ORDER_DESC : 0u};
+    rc = mkord_build(ctx, cols.data(), n_cols, k[0].keys, k[0].klen, n, limit, records, rows);
+    if (rc) {  // half-built: the old selection may have been written over
+        ctx->res.rows.begin();
+        char why[sizeof ctx->err];
+        snprintf(why, sizeof why, "%s", ctx->err);
+        ctx_set_error(ctx, "sjhip_order_paths failed and the row selection was given up: %.180s", why);
+    }
+    return rc;
+}
+
 int sjhip_fetch_order(sjhip_ctx *ctx, uint64_t *order, void *values, uint8_t *status) {
     if (!ctx) return SJHIP_ERR_ARG;
     if (!ctx->res.order.exists()) {
@@ -4098,6 +4528,11 @@ int sjhip_fetch_order(sjhip_ctx *ctx, uint64_t *order, void *values, uint8_t *st
     if (values && kind == SJHIP_COL_STRING) {
         ctx_set_error(ctx, "sjhip_fetch_order: a string order has no 8-byte values (pass NULL; the keys are sjhip_extract_path_strings on the kept "
                            "rows, taken through order[])");
+        return SJHIP_ERR_ARG;
+    }
+    if (values && kind == ORDER_KIND_MULTI) {
+        ctx_set_error(ctx, "sjhip_fetch_order: an order by several keys has no 8-byte values (pass NULL; the keys are sjhip_extract_table on the "
+                           "kept rows, taken through order[])");
         return SJHIP_ERR_ARG;
     }
     if (kept == 0) return SJHIP_OK;  // (nothing was launched, no arena was written)

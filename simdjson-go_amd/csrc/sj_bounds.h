@@ -60,7 +60,11 @@ enum ArrId : uint32_t {
     // the string order (query.hip, sjhip_order_path_strings): the per-row work arrays (status, key element) / the arrays of the
     // active entries (row, position, class, chunk key, head and active flags).  Its ranked rows and its sorts are A_SORT, its product
     // A_ORDER_OUT
-    A_STRORD_ROW, A_STRORD_ACT
+    A_STRORD_ROW, A_STRORD_ACT,
+    // the order by several keys (query.hip, sjhip_order_paths): the per-row work arrays (the statuses on column 0 and on the column
+    // at work, the key or key element) / the class keys of the active entries / the boundary bytes of the n + 1 positions.  The
+    // active entries themselves are A_STRORD_ACT, the ranked rows and the sorts A_SORT, the product A_ORDER_OUT
+    A_MKORD_ROW, A_MKORD_ACT, A_MKORD_BND
 };
 
 #if defined(SJ_DEBUG_BOUNDS)

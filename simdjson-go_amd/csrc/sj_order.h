@@ -43,4 +43,14 @@ SJ_HD u32 strord_chunk_count(u64 chunk, bool desc) { return (u32)((desc ? ~chunk
 // the rounds that order keys of at most `longest` bytes: the round at byte 7 j sees the end of every key shorter than 7 (j + 1)
 SJ_HD u64 strord_max_rounds(u64 longest) { return longest / STRORD_CHUNK + 1; }
 
+// The order by several keys (query.hip, the k_q_mkord_* kernels, sjhip_order_paths) refines classes of tied rows column by column.
+// A round of a column sorts its entries by (class, missing, chunk key): the rows without an OK key on the column lie behind the
+// others of their class, and tie.  The second sort's key is class << 1 | missing -- classes number at most 2^30, so it is a u32.
+// An entry goes on to the column's next round iff it has a key, its new class has company and its chunk was full (a numeric
+// column has one round: its chunk is never "full"); whoever still has company when the column ends meets the next column.
+static constexpr int ORDER_MAX_KEYS = 8;        // SJHIP_ORDER_MAX_KEYS (query.hip asserts it)
+static constexpr int ORDER_KIND_MULTI = -1;     // the kind of the order product after sjhip_order_paths (sj_result.h Order::kind)
+SJ_HD u32 mkord_class_key(u32 cls, bool missing) { return cls << 1 | (missing ? 1u : 0u); }
+SJ_HD bool mkord_stays(bool missing, bool alone, bool chunk_full) { return !missing && !alone && chunk_full; }
+
 }  // namespace sj

@@ -583,11 +583,35 @@ class Context:
         o = Order(nr.value, nw.value, self.COL_STRING)
         return self.fetch_order(o) if fetch else o
 
+    ORDER_MAX_KEYS = 8  # SJHIP_ORDER_MAX_KEYS
+    ORDER_MULTI = -1    # Order.kind of an order by several keys (it has no values)
+
+    def order_paths(self, columns, limit=0, fetch=True):
+        """order_path by SEVERAL keys: columns = [(path, kind, descending), ...], 1 to ORDER_MAX_KEYS of them, kind = COL_FLOAT /
+        COL_INT / COL_UINT (order_path's key and status) or COL_STRING (order_path_strings'), each ascending or descending.  The
+        order is the one a stable sort by the tuple gives: rows that tie on column 0 -- the rows without an OK key there tie with
+        each other, behind the others -- are compared on column 1, and so on; rows that tie everywhere stay in row order.  The
+        limit is applied once, at the end; narrowing and composition are order_path's.
+        -> Order with kind = ORDER_MULTI and values = None; status is the status on column 0.  The sorted keys are extract_table on
+        the kept rows taken through `order`"""
+        cols = [(tuple(path), int(kind), bool(desc)) for path, kind, desc in columns]
+        keys = [bytes(k) for path, _, _ in cols for k in path]
+        n = len(cols)
+        key_lens = (C.c_uint32 * max(len(keys), 1))(*[len(k) for k in keys])
+        path_lens = (C.c_uint32 * max(n, 1))(*[len(path) for path, _, _ in cols])
+        kinds = (C.c_int * max(n, 1))(*[kind for _, kind, _ in cols])
+        flags = (C.c_uint32 * max(n, 1))(*[self.ORDER_DESC if desc else 0 for _, _, desc in cols])
+        nr, nw = C.c_size_t(0), C.c_size_t(0)
+        self._check(_lib.lib().sjhip_order_paths(self._h, b"".join(keys) if keys else None, key_lens if keys else None, path_lens, kinds,
+                                                 flags, n, int(limit), C.byref(nr), C.byref(nw)))
+        o = Order(nr.value, nw.value, self.ORDER_MULTI)
+        return self.fetch_order(o) if fetch else o
+
     def fetch_order(self, o):
-        """the arrays of the last order_path / order_path_strings (o: what it returned with fetch=False) -> o, filled (a string
-        order has no values: None)"""
+        """the arrays of the last order_path / order_path_strings / order_paths (o: what it returned with fetch=False) -> o, filled
+        (a string order and an order by several keys have no values: None)"""
         o.order, o.status = np.empty(o.rows, dtype=np.uint64), np.empty(o.rows, dtype=np.uint8)
-        o.values = None if o.kind == self.COL_STRING else np.empty(o.rows, dtype=self._COL_DTYPES[o.kind])
+        o.values = None if o.kind in (self.COL_STRING, self.ORDER_MULTI) else np.empty(o.rows, dtype=self._COL_DTYPES[o.kind])
         ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
         self._check(_lib.lib().sjhip_fetch_order(self._h, ptr(o.order), ptr(o.values), ptr(o.status)))
         return o
@@ -708,8 +732,9 @@ class Groups:
 
 
 class Order:
-    """what Context.order_path / order_path_strings return: the records, the rows kept and the kind of the keys, and after the fetch
-    order, values (None for a string order) and status in rank order (see order_path)"""
+    """what Context.order_path / order_path_strings / order_paths return: the records, the rows kept and the kind of the keys
+    (Context.ORDER_MULTI after order_paths), and after the fetch order, values (None for a string order and for an order by
+    several keys) and status (after order_paths: the status on column 0) in rank order (see order_path)"""
 
     def __init__(self, records, rows, kind):
         self.records, self.rows, self.kind = records, rows, kind
