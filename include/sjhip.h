@@ -314,6 +314,57 @@ int sjhip_fetch_groups(sjhip_ctx *ctx, uint64_t *key_offsets, void *keys, uint64
                        uint32_t *codes, uint8_t *status);
 int sjhip_fetch_group_aggregates(sjhip_ctx *ctx, uint64_t *count, uint64_t *not_ok, void *sum, uint64_t *sum_hi,
                                  void *min, void *max);
+/* Groups by several keys: the distinct TUPLES of up to SJHIP_GROUP_MAX_KEYS key columns, and the aggregates of up to
+ * SJHIP_GROUP_MAX_VALUES value columns per tuple, from one grouping ("tickets and total fine per (Make, Color)").  keys, key_lens
+ * and the path lengths are laid out as in sjhip_extract_table and sjhip_order_paths: all paths end to end, the key columns first,
+ * then the value columns; key_path_lens[c] / val_path_lens[v] keys each (0: the row's own value).  Each path has the limits of
+ * sjhip_find_path; all paths together hold at most 32 keys and 1024 bytes.  n_key_cols is 1 to 8, n_val_cols 0 to 8 (0: val_path_lens
+ * and val_kinds may be NULL).
+ *   key_kinds[c]   SJHIP_COL_STRING (Iter.StringBytes: the unescaped bytes, with and without SJHIP_FLAG_COPY_STRINGS), SJHIP_COL_INT,
+ *                  SJHIP_COL_UINT or SJHIP_COL_BOOL: sjhip_extract_path's conversion and status byte (1, 1.0 and 1.9 are the INT key
+ *                  1).  SJHIP_COL_FLOAT, SJHIP_COL_STRING_CVT and everything else: SJHIP_ERR_ARG, naming the column and the kind.
+ *   val_kinds[v]   SJHIP_COL_FLOAT, SJHIP_COL_INT or SJHIP_COL_UINT, as sjhip_group_path's value column.
+ *   key_flags[c]   0 or SJHIP_GROUP_NULL_KEY; NULL: all 0; any other bit is SJHIP_ERR_ARG.
+ *   tuple of a row one entry per key column: the converted key where the column's status is SJHIP_COL_OK.  Under
+ *                  SJHIP_GROUP_NULL_KEY a row with any other status on that column (NOT_FOUND, NOT_OBJECT, NULL, TYPE, RANGE alike)
+ *                  has the entry "no key" -- the rows without a key on a column tie with each other on it, as in
+ *                  sjhip_order_paths --; without the flag such a row is in no group and has the code SJHIP_GROUP_NONE.
+ *   groups         two rows are in one group iff their tuples are equal entry by entry: both "no key", or the same bytes / value.
+ *                  Column boundaries count: ("ab","c") and ("a","bc") differ.  Groups are numbered by the first occurrence of
+ *                  their tuple; codes, first_row and group_rows are as in sjhip_group_path and decided by the input alone.
+ * sjhip_group_paths returns *rows, *groups and key_bytes[c] for every key column: STRING: the bytes of the column's entries over all
+ * groups (one entry per group: a key that two groups share counts twice); INT, UINT: 8 * groups; BOOL: groups.
+ *   sjhip_fetch_group_keys(col)          column col's entry of every group: key_offsets [groups + 1] and keys [key_bytes[col]] for
+ *                                        STRING (key_offsets[0] = 0 is written even without groups); int64_t / uint64_t [groups] for
+ *                                        INT / UINT, uint8_t [groups] for BOOL (key_offsets is ignored).  key_ok[g] = 1 where group
+ *                                        g has a key on the column, 0 for "no key" (an empty string slot, or the value 0).
+ *                                        status [rows]: every row's status byte on this column -- every row is evaluated on
+ *                                        every key column, whatever the others give.
+ *   sjhip_fetch_group_aggregates_at(val) the six arrays of sjhip_fetch_group_aggregates for value column val: rows, conversion, the
+ *                                        tree association of float sums and the 128-bit integer sums are sjhip_group_path's.
+ * Any destination may be NULL; a column the grouping does not have is SJHIP_ERR_ARG.
+ * A context holds ONE grouping, built by either call, and each fetch works on it where it is unambiguous: sjhip_fetch_groups gives
+ * first_row, group_rows and codes of any grouping, and key_offsets / keys / status of column 0 when there is exactly one key column
+ * (with more, a non-NULL one is SJHIP_ERR_ARG naming sjhip_fetch_group_keys); sjhip_fetch_group_aggregates is value column 0 when
+ * there is exactly one (else SJHIP_ERR_ARG: "no value column", or naming sjhip_fetch_group_aggregates_at); the two fetches here work
+ * on a grouping of sjhip_group_path: column 0 (key_ok all 1) and value 0.  With one STRING or INT key column, flags 0 and at most one
+ * value column the call IS sjhip_group_path, bit for bit through both families of fetches.
+ * Everything else is sjhip_group_path's: the rows are those of the selection in force (it composes with sjhip_where_path,
+ * sjhip_unnest_rows and sjhip_order_*), the arena, the lifetime and what survives what, no rows (nothing is launched, an empty
+ * grouping with all sizes 0 is published), argument errors that touch nothing -- the previous grouping included --, a later failure
+ * that leaves no grouping, 2^30 rows, and a sharded result refused.
+ * Not done here: joining the groupings of sharded results; FLOAT keys; a further value column on an existing grouping without
+ * grouping again; HAVING-style filtering of groups (a caller orders or filters the fetched aggregates). */
+#define SJHIP_GROUP_MAX_KEYS 8
+#define SJHIP_GROUP_MAX_VALUES 8
+#define SJHIP_GROUP_NULL_KEY 1u /* per key column */
+int sjhip_group_paths(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, const uint32_t *key_path_lens,
+                      const int *key_kinds, const uint32_t *key_flags, uint32_t n_key_cols, const uint32_t *val_path_lens,
+                      const int *val_kinds, uint32_t n_val_cols, size_t *rows, size_t *groups, size_t *key_bytes /* [n_key_cols] */);
+int sjhip_fetch_group_keys(sjhip_ctx *ctx, uint32_t col, uint64_t *key_offsets, void *keys, uint8_t *key_ok /* [groups] */,
+                           uint8_t *status /* [rows] */);
+int sjhip_fetch_group_aggregates_at(sjhip_ctx *ctx, uint32_t val, uint64_t *count, uint64_t *not_ok, void *sum, uint64_t *sum_hi,
+                                    void *min, void *max);
 /* List columns: the ARRAY at `path` of every record, converted on the device -- the reference's Iter.FindElement(path...),
  * Iter.Array() and then Array.AsFloat / AsInteger / AsUint64 / AsString / AsStringCvt (parsed_array.go:145-344); paths, records
  * and limits are those of sjhip_find_path.

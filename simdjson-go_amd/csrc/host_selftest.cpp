@@ -844,6 +844,34 @@ extern "C" int sj_selftest_result_state(const uint8_t *ops, size_t n, uint32_t *
     return 0;
 }
 
+// The sizes of a grouping by several keys (ResultState::Groups with key_cols > 0) through the one `groups` product -- no transition
+// of its own: published on a parsed state, read back, given up by begin, published again and dropped by the next parse.
+// out[0 .. 5): exists after each of those steps; out[5 ..): key_cols, val_cols, key_kinds[1], val_kinds[1], col_bytes[1], groups as
+// read back after the first publish.  Returns GROUP_COLS.
+extern "C" int sj_selftest_groups_sizes(uint64_t *out) {
+    sj::ResultState s;
+    s.begin_parse();
+    s.parse_done(0, 0, 0, 1, false, false);
+    sj::ResultState::Groups z;
+    z.rows = 7, z.groups = 3, z.key_cols = 2, z.val_cols = 2;
+    z.key_kinds[0] = 4, z.key_kinds[1] = 1, z.val_kinds[0] = 0, z.val_kinds[1] = 2;
+    z.col_bytes[0] = 5, z.col_bytes[1] = 24;
+    s.publish(&sj::ResultState::groups, z);
+    out[0] = s.groups.exists();
+    const sj::ResultState::Groups &r = s.groups.sizes();
+    out[5] = r.key_cols, out[6] = r.val_cols, out[7] = (uint64_t)r.key_kinds[1], out[8] = (uint64_t)r.val_kinds[1], out[9] = r.col_bytes[1],
+    out[10] = r.groups;
+    s.groups.begin();
+    out[1] = s.groups.exists();
+    s.publish(&sj::ResultState::groups, z);
+    out[2] = s.groups.exists();
+    s.begin_parse();
+    out[3] = s.groups.exists();
+    s.publish(&sj::ResultState::groups, z);  // (no result: nothing to group)
+    out[4] = s.groups.exists();
+    return sj::ResultState::GROUP_COLS;
+}
+
 // sj_order.h, sj_sort.h: the sort key of a number, and the geometry and the two pass plans of the sort, as the kernels of
 // sjhip_order_path and sjhip_group_path run them.  sj_selftest_sort_plan: out2[0] the grouping's plan for `groups` groups, out2[1]
 // the ordering's for the AND and the OR of its keys
@@ -879,6 +907,13 @@ extern "C" uint64_t sj_selftest_group_hash_bytes(const uint8_t *s, uint64_t len)
 extern "C" uint64_t sj_selftest_group_hash_int(uint64_t x) { return sj::group_hash_int(x); }
 extern "C" int sj_selftest_group_bytes_equal(const uint8_t *a, const uint8_t *b, uint64_t len) { return sj::group_bytes_equal(a, b, len) ? 1 : 0; }
 extern "C" uint64_t sj_selftest_group_table_capacity(uint64_t n) { return sj::group_table_capacity(n); }
+// the tuple hash of the grouping by several keys, as k_q_mkgrp_keys folds it column by column: hs[c] is column c's hash, has[c] == 0
+// stands for "no key" (tests/group_multi_table.py restates the fold and inverts its last step)
+extern "C" uint64_t sj_selftest_group_tuple_hash(const uint64_t *hs, const uint8_t *has, uint32_t n_cols) {
+    uint64_t acc = sj::GROUP_TUPLE_SEED;
+    for (uint32_t c = 0; c < n_cols; c++) acc = sj::group_tuple_fold(acc, has[c] ? hs[c] : sj::GROUP_NO_KEY_HASH);
+    return acc;
+}
 
 // sj_table.h / sj_tablewalk.h: the plan of a table and its one-walk evaluation, as the kernel k_q_table_walk runs them.
 //   sj_selftest_table_plan  -> 0 and the plan: nodes_out[j * 6 ..] = key begin, key end (in blob_out), parent (255: the root),

@@ -1659,6 +1659,204 @@ __global__ __launch_bounds__(256) void k_q_group_counts(Arr<const u64> off, u32 
     if (g < groups) group_rows[g] = off[g + 1] - off[g];
 }
 
+// ---- groups by several keys: the distinct TUPLES of up to SJHIP_GROUP_MAX_KEYS key columns (sjhip_group_paths) -----------------------
+// The key of a row is a tuple with one entry per column: the converted key where the column's status is SJHIP_COL_OK, "no key" where
+// it is not and the column carries SJHIP_GROUP_NULL_KEY; a row with any other column that is not OK is in no group.  Two rows are in
+// one group iff their tuples are equal entry by entry, groups are numbered by first occurrence: the input alone decides.  The
+// pipeline is the single key's with the key side generalised; the sort by code, k_q_group_bounds, k_q_group_counts and the segmented
+// reduction are launched as they are.
+//   k_q_mkgrp_keys        once per column, one lane per row: walk, conversion, status[c][r] and kidx[c][r] (STRING: the tape index;
+//                         INT / UINT / BOOL: the value); the column's hash (sj_group.h; GROUP_NO_KEY_HASH without a key) is folded
+//                         into the row's running tuple hash (group_tuple_fold: order-dependent), and the row's "in a group" byte is
+//                         cleared where the column is not OK and has no flag.
+//   k_q_mkgrp_insert      the protocol of k_q_group_insert, unchanged: a table of row numbers, capacity >= twice the rows, claimed by
+//                         compare-and-swap, lowered by atomicMin to the smaller of two rows with EQUAL tuples, every access a
+//                         device-scope atomic, the probe bounded by the capacity, no lane waiting for another.  Equality is the
+//                         tuple's: the hash first, then per column the two ok flags, then the value, or the length and the bytes.
+//                         What it reads of the occupant ROW -- status, kidx, hash, tape, Strings.B, message -- was written before
+//                         this kernel began and is read-only here, so the slot word is all that is communicated; the occupant only
+//                         ever changes to a smaller row with an equal tuple, so a comparison stays valid whatever happens to the
+//                         slot afterwards, and a tuple ends in the first slot of its probe sequence that held no different one.
+//   k_q_mkgrp_first       flag[r] = row r is the first of its group; per STRING column the length of a first row's key (0 without
+//                         one).  k_q_mkgrp_tile_sums / k_tw_scan_sums / k_q_mkgrp_tile_apply run once per scanned array: the flags
+//                         (with the count of the rows in a group beside them), then every STRING column's lengths.
+//   k_q_mkgrp_emit        once per column: the column's entry of every group (key_ok, and the value, or the offset and the bytes --
+//                         a short key by the lane, a long one by the wave) and the column's status of every row; the launch of
+//                         column 0 writes codes, first_row and the sort's keys as well.
+// A long key is hashed and compared by its lane alone, and every column is one walk of every row: DESIGN.md (Several keys).
+struct QMkGrp {
+    u32 n, mask, n_cols;
+    u32 kinds;       // 4 bits per column: its SJHIP_COL_* kind
+    u32 null_mask;   // bit c: column c carries SJHIP_GROUP_NULL_KEY
+    u32 str_slot;    // 4 bits per column: which of the length arrays a STRING column has
+    u32 tiles;
+    Arr<u8> status;  // [n_cols * n] column-major: the status of row r on column c at c * n + r
+    Arr<u64> kidx;   // [n_cols * n] STRING: tape index of the key element; the other kinds: the value
+    Arr<u64> hash;   // [n] the tuple hash, complete behind the last column's launch
+    Arr<u8> in;      // [n] 1: the row is in a group
+    Arr<u32> slot;   // [n] the slot the row ended in
+    Arr<u32> table;  // [mask + 1] row numbers
+    Arr<u32> flag;   // [n + 1] 1 at the first row of a group -> exclusive prefix: the group's number
+    Arr<u64> len;    // [STRING columns * (n + 1)] bytes of a first row's key -> their offset among the column's entries
+    unsigned long long *tiles_f, *tiles_o, *tiles_l;  // [tiles] flags / rows in a group; [STRING columns * tiles] lengths
+};
+struct MkGrpOut {  // column c of the product (d_group), and what the launch of column 0 writes beside it: see mkgrp_layout
+    Arr<u64> key_off;    // [groups + 1] STRING
+    Arr<u8> key_bytes;   // [key bytes] STRING
+    Arr<u64> key_val;    // [groups] INT, UINT
+    Arr<u8> key_u8;      // [groups] BOOL
+    Arr<u8> key_ok;      // [groups]
+    Arr<u8> status;      // [n]
+    Arr<u64> first_row;  // [groups]
+    Arr<u32> codes;      // [n]
+};
+__device__ __forceinline__ int mkgrp_kind(const QMkGrp &g, u32 c) { return (int)((g.kinds >> (4u * c)) & 15u); }
+__device__ __forceinline__ u64 mkgrp_len_at(const QMkGrp &g, u32 c) { return (u64)((g.str_slot >> (4u * c)) & 15u) * ((u64)g.n + 1u); }
+__device__ __forceinline__ bool mkgrp_tuples_equal(const QView &q, const QMkGrp &g, u32 a, u32 b) {
+    for (u32 c = 0; c < g.n_cols; c++) {
+        const u64 at = (u64)c * g.n;
+        const bool ok = g.status[at + a] == SJHIP_COL_OK;
+        if (ok != (g.status[at + b] == SJHIP_COL_OK)) return false;
+        if (!ok) continue;  // "no key" equals "no key"
+        const u64 ka = g.kidx[at + a], kb = g.kidx[at + b];
+        if (mkgrp_kind(g, c) != SJHIP_COL_STRING) {
+            if (ka != kb) return false;
+            continue;
+        }
+        const u64 len = q.tape[ka + 1];
+        if (len != q.tape[kb + 1]) return false;
+        if (!group_bytes_equal(str_bytes(q, q.tape[ka], len), str_bytes(q, q.tape[kb], len), len)) return false;
+    }
+    return true;
+}
+__global__ __launch_bounds__(256) void k_q_mkgrp_keys(QView q, QPath pth, QMkGrp g, u32 c) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= g.n) return;
+    const int kind = mkgrp_kind(g, c);
+    const u64 v = pth.n ? record_find_path(q, pth, r) : row_value(q, r);  // (no keys: the row's own value)
+    int st;
+    u64 k = 0, h = GROUP_NO_KEY_HASH;
+    if (v >= SJHIP_PATH_NOT_OBJECT) st = path_status(v);
+    else if (kind == SJHIP_COL_STRING) {
+        u64 len = 0;
+        st = element_text_len(q, v, false, &len);
+        if (st == SJHIP_COL_OK) {
+            k = v;
+            h = group_hash_bytes(str_bytes(q, q.tape[v], len), len);
+        }
+    } else {
+        st = element_to(q, v, kind, &k);
+        if (st == SJHIP_COL_OK) h = group_hash_int(k);
+        else k = 0;
+    }
+    const u64 at = (u64)c * g.n + r;
+    g.status[at] = (u8)st;
+    g.kidx[at] = k;
+    g.hash[r] = group_tuple_fold(c ? g.hash[r] : GROUP_TUPLE_SEED, h);
+    const bool keeps = st == SJHIP_COL_OK || ((g.null_mask >> c) & 1u);
+    if (c == 0) g.in[r] = keeps ? 1 : 0;
+    else if (!keeps) g.in[r] = 0;
+}
+__global__ __launch_bounds__(256) void k_q_mkgrp_insert(QView q, QMkGrp g) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= g.n || !g.in[r]) return;
+    const u64 h = g.hash[r];
+    u32 s = (u32)h & g.mask;
+    for (u32 step = 0; step <= g.mask; step++, s = (s + 1u) & g.mask) {
+        u32 *const cell = &g.table[s];
+        u32 cur = __hip_atomic_load(cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == GROUP_NONE) {
+            cur = atomicCAS(cell, GROUP_NONE, r);
+            if (cur == GROUP_NONE) break;  // claimed
+        }
+        if (cur == r) break;
+        if (g.hash[cur] == h && mkgrp_tuples_equal(q, g, r, cur)) {
+            if (cur > r) (void)atomicMin(cell, r);
+            break;
+        }
+    }
+    g.slot[r] = s;
+}
+// (one lane per entry of the n + 1: entry n is 0, the scans leave the totals there)
+__global__ __launch_bounds__(256) void k_q_mkgrp_first(QView q, QMkGrp g) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    if (r > g.n) return;
+    const bool first = r < g.n && g.in[r] && g.table[g.slot[r]] == r;
+    g.flag[r] = first ? 1u : 0u;
+    for (u32 c = 0; c < g.n_cols; c++) {
+        if (mkgrp_kind(g, c) != SJHIP_COL_STRING) continue;
+        const u64 at = (u64)c * g.n + r;
+        g.len[mkgrp_len_at(g, c) + r] = first && g.status[at] == SJHIP_COL_OK ? q.tape[g.kidx[at] + 1] : 0ull;
+    }
+}
+// which = 0: the flags, and the rows in a group counted beside them (as k_q_group_tile_sums counts the rows with a key);
+// which = 1 + s: the lengths of the STRING column with the length array s
+__global__ __launch_bounds__(QT) void k_q_mkgrp_tile_sums(QMkGrp g, u32 m, u32 which) {
+    __shared__ unsigned long long s_w[QT / 64];
+    if (which) {
+        tile_sums(arr_at(g.len, (u64)(which - 1u) * m, m), m, g.tiles_l + (size_t)(which - 1u) * g.tiles);
+        return;
+    }
+    tile_sums(arr_at(g.flag, 0, m), m, g.tiles_f);
+    const u32 base = blockIdx.x * QTILE + threadIdx.x * QI;
+    unsigned long long in = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < QI; k++)
+        if (base + k < g.n && g.in[base + k]) in++;
+    (void)block_excl_sum(in, s_w, (int)threadIdx.x, &tot);
+    if (threadIdx.x == 0) g.tiles_o[blockIdx.x] = tot;
+}
+__global__ __launch_bounds__(QT) void k_q_mkgrp_tile_apply(QMkGrp g, u32 m, u32 which) {
+    if (which) {
+        u64 *const len = arr_at(g.len, (u64)(which - 1u) * m, m);
+        tile_apply(len, len, m, g.tiles_l + (size_t)(which - 1u) * g.tiles);
+        return;
+    }
+    u32 *const flag = arr_at(g.flag, 0, m);
+    tile_apply(flag, flag, m, g.tiles_f);
+}
+// (sort_keys: the first pass's input -- the row's code, or `groups` for a row in no group; written by the launch of column 0)
+__global__ __launch_bounds__(256) void k_q_mkgrp_emit(QView q, QMkGrp g, MkGrpOut o, u32 groups, Arr<u32> sort_keys, u32 c) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int kind = mkgrp_kind(g, c);
+    u64 off = 0, len = 0, w = 0;
+    bool wide = false;
+    if (r < g.n) {
+        const u64 at = (u64)c * g.n + r;
+        const u8 st = g.status[at];
+        u32 code = GROUP_NONE, first = GROUP_NONE;
+        if (g.in[r]) {
+            first = g.table[g.slot[r]];
+            code = g.flag[first];
+        }
+        if (c == 0) {
+            o.codes[r] = code;
+            sort_keys[r] = code == GROUP_NONE ? groups : code;
+            if (first == r) o.first_row[code] = r;
+        }
+        o.status[r] = st;
+        if (first == r) {
+            const bool ok = st == SJHIP_COL_OK;
+            o.key_ok[code] = ok ? 1 : 0;
+            if (kind == SJHIP_COL_STRING) {
+                const u64 la = mkgrp_len_at(g, c) + r;
+                off = g.len[la];
+                len = g.len[la + 1] - off;  // (0 without a key)
+                o.key_off[code] = off;
+                if (len) {
+                    w = q.tape[g.kidx[at]];
+                    wide = len > COL_SHORT;
+                    if (!wide) copy_bytes(arr_at(o.key_bytes, off, len), str_bytes(q, w, len), len, 0, 1);
+                }
+            } else if (kind == SJHIP_COL_BOOL) o.key_u8[code] = (u8)g.kidx[at];
+            else o.key_val[code] = g.kidx[at];
+        }
+        if (r == 0 && kind == SJHIP_COL_STRING) o.key_off[groups] = g.len[mkgrp_len_at(g, c) + g.n];
+    }
+    wave_copy_strings(q, o.key_bytes, wide, off, len, w, lane);
+}
+
 // ---- order: the rows ranked by a numeric key at a path, the first `limit` of them kept (sjhip_order_path) ----------------------------
 // The rank of a row is its position in: the rows with an OK key ascending by key (descending: by the complement of the key), equal
 // keys in row order, then the rows without one in row order.  The selection is narrowed to the rows of rank < limit as a row
@@ -3858,6 +4056,37 @@ static size_t group_layout(Carve c, const ResultState::Groups &z, GroupArrays *o
     o->agg = z.val_kind == SJHIP_GROUP_NO_VALUE ? nullptr : c.take<u64>(6 * z.groups);
     return c.used;
 }
+// Behind the emit of a grouping, by one key or by several: the n rows ordered by code, stably (the first pass's keys lie in
+// sort.keys[0]); the offsets and sizes of the G groups over the n_in sorted rows that are in a group; and one segmented reduction
+// per value column over those rows -- groups in the place of records, on the work arrays `laid` out for n rows.
+struct GroupValue {
+    const QView *q;
+    const QPath *pth;
+    int kind;
+    u64 *out;  // [6 * G] in the product
+};
+static int group_reduce(sjhip_ctx *ctx, uint32_t n, u32 n_in, u32 G, const SortWork<u32> &sort, u64 *off, Arr<u64> group_rows,
+                        const AggWork &laid, const GroupValue *vals, uint32_t n_vals) {
+    if (!G) return SJHIP_OK;
+    hipStream_t st = ctx->stream;
+    const dim3 b256(256);
+    const int at = sort_enqueue(st, n, n, group_pass_mask(G), false, sort);
+    const u32 *const skeys = sort.keys[at], *const srows = sort.rows[at];
+    hipLaunchKernelGGL(k_q_group_bounds, dim3((n_in + 255) / 256), b256, 0, st, SJ_ARR(skeys, n, A_SORT), n_in, G,
+                       SJ_ARR(off, (size_t)G + 1, A_GROUP_OFF));
+    hipLaunchKernelGGL(k_q_group_counts, dim3((G + 255) / 256), b256, 0, st, SJ_ARR((const u64 *)off, (size_t)G + 1, A_GROUP_OFF), G, group_rows);
+    HIPCHK(hipGetLastError(), "group sort launch");
+    for (uint32_t v = 0; v < n_vals; v++) {
+        AggWork aw;
+        (void)agg_layout(Carve(), n_in, G, AGG_OFFS, &aw, false);  // (the levels of n_in rows; the arrays: those laid out for n)
+        aw.out = vals[v].out;
+        aw.head = laid.head;
+        for (size_t l = 0; l < aw.items.size(); l++) aw.items[l] = laid.items[l];
+        const int rc = agg_enqueue(ctx, ctx, *vals[v].q, *vals[v].pth, vals[v].kind, AGG_OFFS, n_in, G, off, aw, srows);
+        if (rc) return rc;
+    }
+    return SJHIP_OK;
+}
 
 int sjhip_group_path(sjhip_ctx *ctx, const uint8_t *key_keys, const uint32_t *key_key_lens, uint32_t key_n_keys, int key_kind,
                      const uint8_t *val_keys, const uint32_t *val_key_lens, uint32_t val_n_keys, int val_kind, size_t *rows, size_t *groups,
@@ -3929,25 +4158,9 @@ int sjhip_group_path(sjhip_ctx *ctx, const uint8_t *key_keys, const uint32_t *ke
     o.status = SJ_ARR(a.status, n, A_GROUP_OUT);
     u32 *const first_keys = w.sort.keys[0];
     hipLaunchKernelGGL(k_q_group_emit, per_row, b256, 0, st, qk, w.g, o, G, SJ_ARR(first_keys, n, A_SORT));
-    if (G) {
-        // the rows ordered by code, stably
-        const int at = sort_enqueue(st, n, n, group_pass_mask(G), false, w.sort);
-        const u32 *const skeys = w.sort.keys[at], *const srows = w.sort.rows[at];
-        hipLaunchKernelGGL(k_q_group_bounds, dim3((n_ok + 255) / 256), b256, 0, st, SJ_ARR(skeys, n, A_SORT), n_ok, G,
-                           SJ_ARR(w.off, (size_t)G + 1, A_GROUP_OFF));
-        hipLaunchKernelGGL(k_q_group_counts, dim3((G + 255) / 256), b256, 0, st, SJ_ARR((const u64 *)w.off, (size_t)G + 1, A_GROUP_OFF), G,
-                           o.group_rows);
-        HIPCHK(hipGetLastError(), "group sort launch");
-        if (value) {  // the segmented reduction over the n_ok sorted rows: groups in the place of records
-            AggWork aw;
-            (void)agg_layout(Carve(), n_ok, G, AGG_OFFS, &aw, false);  // (the levels of n_ok rows; the arrays: those laid out for n)
-            aw.out = a.agg;
-            aw.head = w.agg.head;
-            for (size_t l = 0; l < aw.items.size(); l++) aw.items[l] = w.agg.items[l];
-            rc = agg_enqueue(ctx, ctx, qv, vpth, val_kind, AGG_OFFS, n_ok, G, w.off, aw, srows);
-            if (rc) return rc;
-        }
-    }
+    const GroupValue gv = {&qv, &vpth, val_kind, a.agg};
+    rc = group_reduce(ctx, n, n_ok, G, w.sort, w.off, o.group_rows, w.agg, &gv, value ? 1u : 0u);
+    if (rc) return rc;
     HIPCHK(hipGetLastError(), "group emit launch");
     HIPCHK(hipStreamSynchronize(st), "group build sync");
     rc = query_bounds_check(ctx);
@@ -3956,40 +4169,341 @@ int sjhip_group_path(sjhip_ctx *ctx, const uint8_t *key_keys, const uint32_t *ke
     return published(ctx, ctx->res.publish(&ResultState::groups, z));
 }
 
+// ---- groups by several keys ----------------------------------------------------------------------------------------------------------
+// sjhip_group_paths: the build above with the key side of the k_q_mkgrp_* kernels.  The work arrays (MkGrpWork) lie in d_kat, laid
+// out once for the row count and the columns; the product (mkgrp_layout) in d_group, reserved behind the one host round trip in the
+// middle, which brings the groups, the rows in a group and every STRING column's key bytes.
+struct MkGrpWork {
+    unsigned long long *totals;  // [0] groups, [2] rows in a group, [3 + s] the key bytes of the STRING column with the length array s
+    QMkGrp g;
+    SortWork<u32> sort;
+    u64 *off;  // [groups + 1] the group offsets in the sorted order (room for one group per row)
+    AggWork agg;
+};
+static size_t mkgrp_work_layout(Carve c, uint32_t n, const int *kinds, const uint32_t *flags, uint32_t n_cols, bool value, MkGrpWork *w) {
+    const u64 cap = group_table_capacity(n);
+    const u32 tiles = tiles_of(n);
+    QMkGrp &g = w->g;
+    w->totals = c.take<unsigned long long>(32);
+    g.n = n, g.mask = (u32)(cap - 1), g.n_cols = n_cols, g.tiles = tiles;
+    g.kinds = g.null_mask = g.str_slot = 0;
+    u32 n_str = 0;
+    for (u32 k = 0; k < n_cols; k++) {
+        g.kinds |= (u32)kinds[k] << (4 * k);
+        if (flags && (flags[k] & SJHIP_GROUP_NULL_KEY)) g.null_mask |= 1u << k;
+        if (kinds[k] == SJHIP_COL_STRING) g.str_slot |= n_str++ << (4 * k);
+    }
+    const size_t per_col = (size_t)n_cols * n, lens = (size_t)n_str * ((size_t)n + 1);
+    u8 *const status = c.take<u8>(per_col), *const in = c.take<u8>(n);
+    u64 *const kidx = c.take<u64>(per_col), *const hash = c.take<u64>(n);
+    u32 *const slot = c.take<u32>(n), *const table = c.take<u32>(cap), *const flag = c.take<u32>((size_t)n + 1);
+    u64 *const len = n_str ? c.take<u64>(lens) : nullptr;
+    g.status = SJ_ARR(status, per_col, A_MKGRP_ROW);
+    g.in = SJ_ARR(in, n, A_MKGRP_ROW);
+    g.kidx = SJ_ARR(kidx, per_col, A_MKGRP_ROW);
+    g.hash = SJ_ARR(hash, n, A_MKGRP_ROW);
+    g.slot = SJ_ARR(slot, n, A_MKGRP_ROW);
+    g.table = SJ_ARR(table, cap, A_GROUP_TABLE);
+    g.flag = SJ_ARR(flag, (size_t)n + 1, A_MKGRP_ROW);
+    g.len = SJ_ARR(len, lens, A_MKGRP_LEN);
+    g.tiles_f = c.take<unsigned long long>(tiles);
+    g.tiles_o = c.take<unsigned long long>(tiles);
+    g.tiles_l = c.take<unsigned long long>((size_t)n_str * tiles);
+    sort_carve(c, n, &w->sort);
+    w->off = c.take<u64>((size_t)n + 1);
+    if (value) (void)(c.used = agg_layout(c, n, n, AGG_OFFS, &w->agg, false));
+    return c.used;
+}
+// The grouping by several keys in d_group: what its fetches return, and nothing else.
+struct MkGrpArrays {
+    u64 *first_row, *group_rows, *agg[ResultState::GROUP_COLS], *key_off[ResultState::GROUP_COLS], *key_val[ResultState::GROUP_COLS];
+    u32 *codes;
+    u8 *key_bytes[ResultState::GROUP_COLS], *key_u8[ResultState::GROUP_COLS], *key_ok[ResultState::GROUP_COLS], *status[ResultState::GROUP_COLS];
+};
+static size_t mkgrp_layout(Carve c, const ResultState::Groups &z, MkGrpArrays *o) {
+    *o = MkGrpArrays{};
+    o->first_row = c.take<u64>(z.groups);
+    o->group_rows = c.take<u64>(z.groups);
+    for (uint32_t v = 0; v < z.val_cols; v++) o->agg[v] = c.take<u64>(6 * z.groups);
+    for (uint32_t k = 0; k < z.key_cols; k++) {
+        if (z.key_kinds[k] == SJHIP_COL_STRING) o->key_off[k] = c.take<u64>(z.groups + 1);
+        else if (z.key_kinds[k] != SJHIP_COL_BOOL) o->key_val[k] = c.take<u64>(z.groups);
+    }
+    o->codes = c.take<u32>(z.rows);
+    for (uint32_t k = 0; k < z.key_cols; k++) {
+        if (z.key_kinds[k] == SJHIP_COL_STRING) o->key_bytes[k] = c.take<u8>(z.col_bytes[k]);
+        else if (z.key_kinds[k] == SJHIP_COL_BOOL) o->key_u8[k] = c.take<u8>(z.groups);
+        o->key_ok[k] = c.take<u8>(z.groups);
+        o->status[k] = c.take<u8>(z.rows);
+    }
+    return c.used;
+}
+
+int sjhip_group_paths(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, const uint32_t *key_path_lens, const int *key_kinds,
+                      const uint32_t *key_flags, uint32_t n_key_cols, const uint32_t *val_path_lens, const int *val_kinds,
+                      uint32_t n_val_cols, size_t *rows, size_t *groups, size_t *key_bytes) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!rows || !groups || !key_bytes) {
+        ctx_set_error(ctx, "sjhip_group_paths: a null size pointer");
+        return SJHIP_ERR_ARG;
+    }
+    if (n_key_cols < 1 || n_key_cols > (uint32_t)SJHIP_GROUP_MAX_KEYS) {
+        ctx_set_error(ctx, "sjhip_group_paths: %u key columns (1 to %d)", n_key_cols, SJHIP_GROUP_MAX_KEYS);
+        return SJHIP_ERR_ARG;
+    }
+    if (n_val_cols > (uint32_t)SJHIP_GROUP_MAX_VALUES) {
+        ctx_set_error(ctx, "sjhip_group_paths: %u value columns (0 to %d)", n_val_cols, SJHIP_GROUP_MAX_VALUES);
+        return SJHIP_ERR_ARG;
+    }
+    if (!key_path_lens || !key_kinds || (n_val_cols && (!val_path_lens || !val_kinds))) {
+        ctx_set_error(ctx, "sjhip_group_paths: a null argument (key_path_lens, key_kinds, val_path_lens, val_kinds)");
+        return SJHIP_ERR_ARG;
+    }
+    const uint32_t n_paths = n_key_cols + n_val_cols;
+    size_t n_keys = 0, bytes = 0;
+    for (uint32_t c = 0; c < n_paths; c++) {
+        const bool is_key = c < n_key_cols;
+        const uint32_t j = is_key ? c : c - n_key_cols;
+        const int kind = is_key ? key_kinds[j] : val_kinds[j];
+        if (is_key && kind != SJHIP_COL_STRING && kind != SJHIP_COL_INT && kind != SJHIP_COL_UINT && kind != SJHIP_COL_BOOL) {
+            ctx_set_error(ctx, "sjhip_group_paths: key column %u: kind %d is not SJHIP_COL_STRING, SJHIP_COL_INT, SJHIP_COL_UINT or SJHIP_COL_BOOL", j,
+                          kind);
+            return SJHIP_ERR_ARG;
+        }
+        if (!is_key && kind != SJHIP_COL_FLOAT && kind != SJHIP_COL_INT && kind != SJHIP_COL_UINT) {
+            ctx_set_error(ctx, "sjhip_group_paths: value column %u: kind %d is not SJHIP_COL_FLOAT, SJHIP_COL_INT or SJHIP_COL_UINT", j, kind);
+            return SJHIP_ERR_ARG;
+        }
+        if (is_key && key_flags && (key_flags[j] & ~SJHIP_GROUP_NULL_KEY)) {
+            ctx_set_error(ctx, "sjhip_group_paths: key column %u: unknown flag bits 0x%x", j, key_flags[j] & ~SJHIP_GROUP_NULL_KEY);
+            return SJHIP_ERR_ARG;
+        }
+        n_keys += is_key ? key_path_lens[j] : val_path_lens[j];
+        if (n_keys > (size_t)TABLE_MAX_KEYS) {
+            ctx_set_error(ctx, "sjhip_group_paths: the paths hold more than %d keys together (found at %s column %u)", TABLE_MAX_KEYS,
+                          is_key ? "key" : "value", j);
+            return SJHIP_ERR_ARG;
+        }
+    }
+    if (n_keys && (!keys || !key_lens)) {
+        ctx_set_error(ctx, "sjhip_group_paths: a null argument (%zu keys are announced)", n_keys);
+        return SJHIP_ERR_ARG;
+    }
+    for (size_t j = 0; j < n_keys; j++) bytes += key_lens[j];
+    if (bytes > (size_t)TABLE_MAX_BYTES) {
+        ctx_set_error(ctx, "sjhip_group_paths: the keys of the paths are longer than %d bytes together", TABLE_MAX_BYTES);
+        return SJHIP_ERR_ARG;
+    }
+    std::vector<WholePath> k(n_paths);
+    size_t key_at = 0, byte_at = 0;
+    for (uint32_t c = 0; c < n_paths; c++) {
+        const uint32_t pl = c < n_key_cols ? key_path_lens[c] : val_path_lens[c - n_key_cols];
+        k[c].keys = pl ? keys + byte_at : nullptr;
+        k[c].key_lens = pl ? key_lens + key_at : nullptr;
+        k[c].n_keys = pl;
+        for (uint32_t j = 0; j < pl; j++) byte_at += key_lens[key_at + j];
+        key_at += pl;
+    }
+    uint32_t n = 0;
+    int rc = whole_entry(ctx, "sjhip_group_paths", "the dictionaries of shards are not joined", k.data(), (int)n_paths, &n);
+    if (rc) return rc;
+    // ---- nothing was touched up to here; from here on the last grouping is gone ----
+    ctx->res.groups.begin();
+    ResultState::Groups z;
+    z.rows = n, z.key_cols = n_key_cols, z.val_cols = n_val_cols;
+    for (uint32_t c = 0; c < n_key_cols; c++) z.key_kinds[c] = key_kinds[c], key_bytes[c] = 0;
+    for (uint32_t v = 0; v < n_val_cols; v++) z.val_kinds[v] = val_kinds[v];
+    z.key_kind = key_kinds[0], z.val_kind = n_val_cols ? val_kinds[0] : SJHIP_GROUP_NO_VALUE;
+    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    if (n == 0) {
+        *rows = *groups = 0;
+        return published(ctx, ctx->res.publish(&ResultState::groups, z));
+    }
+    MkGrpWork w;
+    rc = reserve_layout(ctx, ctx->d_kat, [&](Carve c) { return mkgrp_work_layout(c, n, key_kinds, key_flags, n_key_cols, n_val_cols != 0, &w); });
+    if (rc) return rc;
+    const QView &q0 = k[0].q;  // (the kernels behind the walks read the tape and the strings only: any column's view)
+    hipStream_t st = ctx->stream;
+    const dim3 per_row((n + 255) / 256), per_entry((n + 1u + 255) / 256), b256(256), one(1), wide(1024);
+    unsigned long long *const none = nullptr;
+    const u32 tiles = w.g.tiles;
+    u32 n_str = 0;
+    for (uint32_t c = 0; c < n_key_cols; c++) n_str += key_kinds[c] == SJHIP_COL_STRING;
+    HIPCHK(hipMemsetAsync(w.totals, 0, 256, st), "group totals memset");
+    HIPCHK(hipMemsetAsync(arr_raw(w.g.table), 0xff, ((size_t)w.g.mask + 1) * 4, st), "group table memset");
+    for (uint32_t c = 0; c < n_key_cols; c++) hipLaunchKernelGGL(k_q_mkgrp_keys, per_row, b256, 0, st, k[c].q, k[c].pth, w.g, c);
+    hipLaunchKernelGGL(k_q_mkgrp_insert, per_row, b256, 0, st, q0, w.g);
+    hipLaunchKernelGGL(k_q_mkgrp_first, per_entry, b256, 0, st, q0, w.g);
+    for (u32 which = 0; which <= n_str; which++) {  // the flags, then every STRING column's lengths: sums -> scan -> apply
+        hipLaunchKernelGGL(k_q_mkgrp_tile_sums, dim3(tiles), dim3(QT), 0, st, w.g, n + 1u, which);
+        if (which == 0) hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.g.tiles_f, none, w.g.tiles_o, tiles, w.totals);
+        else hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.g.tiles_l + (size_t)(which - 1) * tiles, none, none, tiles, w.totals + 2 + which);
+        hipLaunchKernelGGL(k_q_mkgrp_tile_apply, dim3(tiles), dim3(QT), 0, st, w.g, n + 1u, which);
+    }
+    HIPCHK(hipGetLastError(), "group launch");
+    unsigned long long *const h = (unsigned long long *)(ctx->h_scratch + 512);
+    HIPCHK(hipMemcpyAsync(h, w.totals, (3 + (size_t)ResultState::GROUP_COLS) * 8, hipMemcpyDeviceToHost, st), "D2H group totals");
+    HIPCHK(hipStreamSynchronize(st), "group sync");
+    rc = query_bounds_check(ctx);
+    if (rc) return rc;
+    const u32 G = (u32)h[0], n_in = (u32)h[2];
+    z.groups = G;
+    for (uint32_t c = 0, s = 0; c < n_key_cols; c++) {
+        const int kind = key_kinds[c];
+        z.col_bytes[c] = kind == SJHIP_COL_STRING ? (size_t)h[3 + s++] : (kind == SJHIP_COL_BOOL ? (size_t)G : (size_t)8 * G);
+    }
+    z.key_bytes = z.col_bytes[0];
+    MkGrpArrays a;
+    rc = reserve_layout(ctx, ctx->d_group, [&](Carve c) { return mkgrp_layout(c, z, &a); });
+    if (rc) return rc;
+    u32 *const first_keys = w.sort.keys[0];
+    for (uint32_t c = 0; c < n_key_cols; c++) {
+        MkGrpOut o;
+        u64 *const key_off = a.key_off[c], *const key_val = a.key_val[c];
+        u8 *const col_bytes = a.key_bytes[c], *const key_u8 = a.key_u8[c], *const key_ok = a.key_ok[c], *const status = a.status[c];
+        o.key_off = SJ_ARR(key_off, key_off ? (size_t)G + 1 : 0, A_MKGRP_OUT);
+        o.key_bytes = SJ_ARR(col_bytes, col_bytes ? z.col_bytes[c] : 0, A_MKGRP_KEYS);
+        o.key_val = SJ_ARR(key_val, key_val ? G : 0, A_MKGRP_OUT);
+        o.key_u8 = SJ_ARR(key_u8, key_u8 ? G : 0, A_MKGRP_OUT);
+        o.key_ok = SJ_ARR(key_ok, G, A_MKGRP_OUT);
+        o.status = SJ_ARR(status, n, A_MKGRP_OUT);
+        o.first_row = SJ_ARR(a.first_row, G, A_MKGRP_OUT);
+        o.codes = SJ_ARR(a.codes, n, A_MKGRP_OUT);
+        hipLaunchKernelGGL(k_q_mkgrp_emit, per_row, b256, 0, st, q0, w.g, o, G, SJ_ARR(first_keys, n, A_SORT), c);
+    }
+    GroupValue gv[ResultState::GROUP_COLS];
+    for (uint32_t v = 0; v < n_val_cols; v++) gv[v] = {&k[n_key_cols + v].q, &k[n_key_cols + v].pth, val_kinds[v], a.agg[v]};
+    rc = group_reduce(ctx, n, n_in, G, w.sort, w.off, SJ_ARR(a.group_rows, G, A_MKGRP_OUT), w.agg, gv, n_val_cols);
+    if (rc) return rc;
+    HIPCHK(hipGetLastError(), "group emit launch");
+    HIPCHK(hipStreamSynchronize(st), "group build sync");
+    rc = query_bounds_check(ctx);
+    if (rc) return rc;
+    *rows = n, *groups = G;
+    for (uint32_t c = 0; c < n_key_cols; c++) key_bytes[c] = z.col_bytes[c];
+    return published(ctx, ctx->res.publish(&ResultState::groups, z));
+}
+
 static int no_grouping(sjhip_ctx *ctx, const char *call) {
-    ctx_set_error(ctx, "no grouping on the device (%s follows sjhip_group_path, with no parse in between)", call);
+    ctx_set_error(ctx, "no grouping on the device (%s follows sjhip_group_path or sjhip_group_paths, with no parse in between)", call);
     return SJHIP_ERR_ARG;
+}
+// Column `col` of the grouping in force, whichever call built it (the single key's: column 0, every group has a key): where its
+// entries lie and how many bytes they are.
+struct GroupColumn {
+    int kind;
+    const u64 *key_off;  // STRING
+    const void *keys;
+    size_t key_bytes;
+    const u8 *key_ok;    // null: all 1
+    const u8 *status;
+};
+static GroupColumn group_column(const sjhip_ctx *ctx, const ResultState::Groups &z, uint32_t col) {
+    if (z.key_cols == 0) {
+        GroupArrays a;
+        (void)group_layout(Carve(ctx->d_group.p), z, &a);
+        const bool ints = z.key_kind == SJHIP_COL_INT;
+        return {z.key_kind, a.key_off, ints ? (const void *)a.key_int : (const void *)a.key_bytes, z.key_bytes, nullptr, a.status};
+    }
+    MkGrpArrays a;
+    (void)mkgrp_layout(Carve(ctx->d_group.p), z, &a);
+    const int kind = z.key_kinds[col];
+    const void *const keys = kind == SJHIP_COL_STRING ? (const void *)a.key_bytes[col]
+                                                      : (kind == SJHIP_COL_BOOL ? (const void *)a.key_u8[col] : (const void *)a.key_val[col]);
+    return {kind, a.key_off[col], keys, z.col_bytes[col], a.key_ok[col], a.status[col]};
+}
+static const u64 *group_aggregates(const sjhip_ctx *ctx, const ResultState::Groups &z, uint32_t val) {
+    if (z.key_cols == 0) {
+        GroupArrays a;
+        (void)group_layout(Carve(ctx->d_group.p), z, &a);
+        return a.agg;
+    }
+    MkGrpArrays a;
+    (void)mkgrp_layout(Carve(ctx->d_group.p), z, &a);
+    return a.agg[val];
+}
+static int fetch_aggregates(sjhip_ctx *ctx, const ResultState::Groups &z, uint32_t val, void *const (&dst)[6]) {
+    if (z.groups == 0) return SJHIP_OK;
+    const u64 *const agg = group_aggregates(ctx, z, val);
+    FetchCopy copies[6];
+    for (int j = 0; j < 6; j++) copies[j] = {dst[j], agg + (size_t)j * z.groups, z.groups * 8};
+    return fetch_copies(ctx, copies, 6, "D2H group aggregates", "group aggregates fetch sync");
 }
 int sjhip_fetch_groups(sjhip_ctx *ctx, uint64_t *key_offsets, void *keys, uint64_t *first_row, uint64_t *group_rows, uint32_t *codes,
                        uint8_t *status) {
     if (!ctx) return SJHIP_ERR_ARG;
     if (!ctx->res.groups.exists()) return no_grouping(ctx, "sjhip_fetch_groups");
     const ResultState::Groups &z = ctx->res.groups.sizes();
-    const bool ints = z.key_kind == SJHIP_COL_INT;
-    if (key_offsets && !ints && z.groups == 0) key_offsets[0] = 0;
+    if (z.key_cols > 1 && (key_offsets || keys || status)) {
+        ctx_set_error(ctx, "sjhip_fetch_groups: the grouping has %u key columns (pass NULL for key_offsets, keys and status; the columns are "
+                           "sjhip_fetch_group_keys)", z.key_cols);
+        return SJHIP_ERR_ARG;
+    }
+    const bool strings = z.key_kind == SJHIP_COL_STRING;
+    if (key_offsets && strings && z.groups == 0) key_offsets[0] = 0;
     if (z.rows == 0) return SJHIP_OK;  // (nothing was launched, no arena was written)
-    GroupArrays a;
-    (void)group_layout(Carve(ctx->d_group.p), z, &a);
-    const FetchCopy copies[] = {
-        {ints ? nullptr : key_offsets, a.key_off, (z.groups + 1) * 8}, {keys, ints ? (const void *)a.key_int : (const void *)a.key_bytes, z.key_bytes},
-        {first_row, a.first_row, z.groups * 8}, {group_rows, a.group_rows, z.groups * 8}, {codes, a.codes, z.rows * 4}, {status, a.status, z.rows}};
+    const GroupColumn k = group_column(ctx, z, 0);
+    const u64 *d_first_row, *d_group_rows;
+    const u32 *d_codes;
+    if (z.key_cols == 0) {
+        GroupArrays a;
+        (void)group_layout(Carve(ctx->d_group.p), z, &a);
+        d_first_row = a.first_row, d_group_rows = a.group_rows, d_codes = a.codes;
+    } else {
+        MkGrpArrays a;
+        (void)mkgrp_layout(Carve(ctx->d_group.p), z, &a);
+        d_first_row = a.first_row, d_group_rows = a.group_rows, d_codes = a.codes;
+    }
+    const FetchCopy copies[] = {{strings ? key_offsets : nullptr, k.key_off, (z.groups + 1) * 8}, {keys, k.keys, k.key_bytes},
+                                {first_row, d_first_row, z.groups * 8},  {group_rows, d_group_rows, z.groups * 8},
+                                {codes, d_codes, z.rows * 4},            {status, k.status, z.rows}};
     return fetch_copies(ctx, copies, 6, "D2H groups", "group fetch sync");
+}
+int sjhip_fetch_group_keys(sjhip_ctx *ctx, uint32_t col, uint64_t *key_offsets, void *keys, uint8_t *key_ok, uint8_t *status) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!ctx->res.groups.exists()) return no_grouping(ctx, "sjhip_fetch_group_keys");
+    const ResultState::Groups &z = ctx->res.groups.sizes();
+    const uint32_t cols = z.key_cols ? z.key_cols : 1u;
+    if (col >= cols) {
+        ctx_set_error(ctx, "sjhip_fetch_group_keys: key column %u of a grouping with %u", col, cols);
+        return SJHIP_ERR_ARG;
+    }
+    const int kind = z.key_cols ? z.key_kinds[col] : z.key_kind;
+    const bool strings = kind == SJHIP_COL_STRING;
+    if (key_offsets && strings && z.groups == 0) key_offsets[0] = 0;
+    if (z.rows == 0) return SJHIP_OK;  // (nothing was launched, no arena was written)
+    const GroupColumn k = group_column(ctx, z, col);
+    if (key_ok && !k.key_ok) memset(key_ok, 1, z.groups);  // (the single key's call: a group is a key)
+    const FetchCopy copies[] = {{strings ? key_offsets : nullptr, k.key_off, (z.groups + 1) * 8}, {keys, k.keys, k.key_bytes},
+                                {k.key_ok ? key_ok : nullptr, k.key_ok, z.groups}, {status, k.status, z.rows}};
+    return fetch_copies(ctx, copies, 4, "D2H group keys", "group keys fetch sync");
 }
 int sjhip_fetch_group_aggregates(sjhip_ctx *ctx, uint64_t *count, uint64_t *not_ok, void *sum, uint64_t *sum_hi, void *min, void *max) {
     if (!ctx) return SJHIP_ERR_ARG;
     if (!ctx->res.groups.exists()) return no_grouping(ctx, "sjhip_fetch_group_aggregates");
     const ResultState::Groups &z = ctx->res.groups.sizes();
-    if (z.val_kind == SJHIP_GROUP_NO_VALUE) {
-        ctx_set_error(ctx, "sjhip_fetch_group_aggregates: the grouping has no value column (sjhip_group_path was called with SJHIP_GROUP_NO_VALUE)");
+    if (z.key_cols ? z.val_cols == 0 : z.val_kind == SJHIP_GROUP_NO_VALUE) {
+        ctx_set_error(ctx, "sjhip_fetch_group_aggregates: the grouping has no value column (sjhip_group_path was called with SJHIP_GROUP_NO_VALUE, "
+                           "or sjhip_group_paths without value columns)");
         return SJHIP_ERR_ARG;
     }
-    if (z.groups == 0) return SJHIP_OK;
-    GroupArrays a;
-    (void)group_layout(Carve(ctx->d_group.p), z, &a);
-    void *const dst[6] = {count, not_ok, sum, sum_hi, min, max};
-    FetchCopy copies[6];
-    for (int j = 0; j < 6; j++) copies[j] = {dst[j], a.agg + (size_t)j * z.groups, z.groups * 8};
-    return fetch_copies(ctx, copies, 6, "D2H group aggregates", "group aggregates fetch sync");
+    if (z.val_cols > 1) {
+        ctx_set_error(ctx, "sjhip_fetch_group_aggregates: the grouping has %u value columns (each is sjhip_fetch_group_aggregates_at)", z.val_cols);
+        return SJHIP_ERR_ARG;
+    }
+    return fetch_aggregates(ctx, z, 0, {count, not_ok, sum, sum_hi, min, max});
+}
+int sjhip_fetch_group_aggregates_at(sjhip_ctx *ctx, uint32_t val, uint64_t *count, uint64_t *not_ok, void *sum, uint64_t *sum_hi, void *min,
+                                    void *max) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!ctx->res.groups.exists()) return no_grouping(ctx, "sjhip_fetch_group_aggregates_at");
+    const ResultState::Groups &z = ctx->res.groups.sizes();
+    const uint32_t vals = z.key_cols ? z.val_cols : (z.val_kind == SJHIP_GROUP_NO_VALUE ? 0u : 1u);
+    if (val >= vals) {
+        ctx_set_error(ctx, "sjhip_fetch_group_aggregates_at: value column %u of a grouping with %u", val, vals);
+        return SJHIP_ERR_ARG;
+    }
+    return fetch_aggregates(ctx, z, val, {count, not_ok, sum, sum_hi, min, max});
 }
 
 // ---- order ---------------------------------------------------------------------------------------------------------------------------

@@ -64,7 +64,12 @@ enum ArrId : uint32_t {
     // the order by several keys (query.hip, sjhip_order_paths): the per-row work arrays (the statuses on column 0 and on the column
     // at work, the key or key element) / the class keys of the active entries / the boundary bytes of the n + 1 positions.  The
     // active entries themselves are A_STRORD_ACT, the ranked rows and the sorts A_SORT, the product A_ORDER_OUT
-    A_MKORD_ROW, A_MKORD_ACT, A_MKORD_BND
+    A_MKORD_ROW, A_MKORD_ACT, A_MKORD_BND,
+    // the grouping by several keys (query.hip, sjhip_group_paths): the per-row work arrays, column-major where they are per column
+    // (status, key element or value; tuple hash, in-a-group byte, slot, first-row flag) / the key lengths of the STRING columns /
+    // the per-group and per-row arrays of the product / the bytes of a STRING column's entries.  The table is A_GROUP_TABLE, the
+    // group offsets A_GROUP_OFF, the sort A_SORT
+    A_MKGRP_ROW, A_MKGRP_LEN, A_MKGRP_OUT, A_MKGRP_KEYS
 };
 
 #if defined(SJ_DEBUG_BOUNDS)

@@ -45,6 +45,15 @@ SJ_HD bool group_bytes_equal(const u8 *a, const u8 *b, u64 len) {
         if (a[k] != b[k]) return false;
     return true;
 }
+// Several key columns (sjhip_group_paths, the k_q_mkgrp_* kernels): the hash of a row's tuple is folded column by column from the
+// hashes above -- of the column's bytes or of its 8-byte value; GROUP_NO_KEY_HASH where the row has no key on the column.  The fold
+// depends on the order of the columns (the running hash is multiplied before the column's is added), and for a fixed prefix it is a
+// bijection of the last column's hash: an addition, then the invertible group_mix -- tests/group_multi_table.py solves an INT last
+// column for a chosen tuple hash that way.
+static constexpr u64 GROUP_TUPLE_SEED = 0x9e3779b97f4a7c15ull;
+static constexpr u64 GROUP_NO_KEY_HASH = 0x6a09e667f3bcc909ull;
+SJ_HD u64 group_tuple_fold(u64 acc, u64 h) { return group_mix(acc * 0x9fb21c651e98df25ull + h); }
+
 // the power-of-two capacity of the table of n rows: at least twice the rows, so that every probe sequence meets an empty slot
 SJ_HD u64 group_table_capacity(u64 n) {
     u64 cap = 64;

@@ -40,7 +40,17 @@ public:
     struct Parents { size_t parents = 0, rows = 0; };  // the rows sjhip_unnest_rows ran over, the rows it left
     // the grouping (sjhip_group_path): the rows it ran over, its groups, the bytes of its dictionary, and what its fetches need to
     // know: the kind of the keys and of the value column (-1: SJHIP_GROUP_NO_VALUE, no aggregates were built)
-    struct Groups { size_t rows = 0, groups = 0, key_bytes = 0; int key_kind = 0, val_kind = -1; };
+    // A grouping by several keys (sjhip_group_paths) has key_cols > 0: the kinds of its key and value columns and the bytes of
+    // every key column's entries; key_bytes, key_kind and val_kind are then column 0's and value 0's.  key_cols == 0: the single
+    // key's call built it, with that call's layout of d_group.
+    static constexpr int GROUP_COLS = 8;  // SJHIP_GROUP_MAX_KEYS, SJHIP_GROUP_MAX_VALUES
+    struct Groups {
+        size_t rows = 0, groups = 0, key_bytes = 0;
+        int key_kind = 0, val_kind = -1;
+        uint32_t key_cols = 0, val_cols = 0;
+        int key_kinds[GROUP_COLS] = {}, val_kinds[GROUP_COLS] = {};
+        size_t col_bytes[GROUP_COLS] = {};
+    };
     // the order (sjhip_order_path): the rows it kept -- its arrays have that many entries -- and the kind of their keys
     struct Order { size_t rows = 0; int kind = 0; };
     struct Table {  // what a fetch of one column needs: its kind, and the text bytes of a string column (0 for the other kinds)

@@ -686,3 +686,176 @@ func parseNDStreamHip(r io.Reader, res chan<- Stream, reuse <-chan *ParsedJson, 
 		}
 	}()
 }
+
+// ---- group by several keys on the result a ViewParser holds (sjhip_group_paths) ---------------------------------------
+// What a caller of the reference writes as a loop over the rows with one Iter.FindElement(path...) + Iter.StringBytes /
+// Int / Uint / Bool per key column and a map from the tuple to a group -- on the device, with up to GroupMaxValues
+// aggregates from the one grouping.  The rows are the records of the last Parse / ParseND of the ViewParser.
+
+// GroupMaxKeys, GroupMaxValues: the most key and value columns of one GroupPaths call.
+const (
+	GroupMaxKeys   = int(C.SJHIP_GROUP_MAX_KEYS)
+	GroupMaxValues = int(C.SJHIP_GROUP_MAX_VALUES)
+)
+
+// GroupColumnKind is the conversion of a key or value column.
+type GroupColumnKind int
+
+// (the values of the header's SJHIP_COL_FLOAT .. SJHIP_COL_STRING, which are enumerators there)
+const (
+	GroupFloat  GroupColumnKind = 0 // Iter.Float: value columns
+	GroupInt    GroupColumnKind = 1 // Iter.Int
+	GroupUint   GroupColumnKind = 2 // Iter.Uint
+	GroupBool   GroupColumnKind = 3 // Iter.Bool: key columns
+	GroupString GroupColumnKind = 4 // Iter.StringBytes: key columns
+)
+
+// GroupKeyColumn is one key column: the path below the row, its kind, and whether a row without an OK key on it has
+// the entry "no key" (such rows tie with each other) instead of being in no group.
+type GroupKeyColumn struct {
+	Path    []string
+	Kind    GroupColumnKind
+	NullKey bool
+}
+
+// GroupValueColumn is one value column: the path below the row and GroupFloat, GroupInt or GroupUint.
+type GroupValueColumn struct {
+	Path []string
+	Kind GroupColumnKind
+}
+
+// GroupKeys is one key column of a grouping: one entry per group.  Strings holds the entries of a GroupString column,
+// Values the bits of the others (int64 / uint64 / 0 and 1); OK[g] == 0 where group g has no key on the column; Status
+// holds every row's SJHIP_COL_* status on the column.
+type GroupKeys struct {
+	Kind    GroupColumnKind
+	Strings [][]byte
+	Values  []uint64
+	OK      []uint8
+	Status  []uint8
+}
+
+// GroupAggregates is one value column of a grouping, per group: the rows with an OK value and the others, the sum
+// (float64 bits, or the low 64 bits with SumHi above them), and the minimum and maximum as bits of the column's kind.
+type GroupAggregates struct {
+	Kind                     GroupColumnKind
+	Count, NotOK, Sum, SumHi []uint64
+	Min, Max                 []uint64
+}
+
+// GroupsResult is what GroupPaths returns: groups in the order of their first row, a code per row (GroupNone: the row is
+// in no group), and the columns.
+type GroupsResult struct {
+	Rows, Groups int
+	FirstRow     []uint64
+	GroupRows    []uint64
+	Codes        []uint32
+	Keys         []GroupKeys
+	Values       []GroupAggregates
+}
+
+// GroupNone is the code of a row that is in no group.
+const GroupNone = uint32(C.SJHIP_GROUP_NONE)
+
+func u64ptr(s []uint64) *C.uint64_t {
+	if len(s) == 0 {
+		return nil
+	}
+	return (*C.uint64_t)(unsafe.Pointer(&s[0]))
+}
+
+func u8ptr(s []uint8) *C.uint8_t {
+	if len(s) == 0 {
+		return nil
+	}
+	return (*C.uint8_t)(unsafe.Pointer(&s[0]))
+}
+
+// GroupPaths groups the records of the ViewParser's last parse by the tuple of the key columns and reduces every value
+// column per group (include/sjhip.h: sjhip_group_paths, sjhip_fetch_group_keys, sjhip_fetch_group_aggregates_at).
+func (v *ViewParser) GroupPaths(keys []GroupKeyColumn, values []GroupValueColumn) (*GroupsResult, error) {
+	if len(keys) < 1 || len(keys) > GroupMaxKeys || len(values) > GroupMaxValues {
+		return nil, fmt.Errorf("sjhip: GroupPaths takes 1 to %d key columns and up to %d value columns", GroupMaxKeys, GroupMaxValues)
+	}
+	var blob []byte
+	var keyLens []C.uint32_t
+	keyPathLens := make([]C.uint32_t, len(keys))
+	keyKinds := make([]C.int, len(keys))
+	keyFlags := make([]C.uint32_t, len(keys))
+	valPathLens := make([]C.uint32_t, len(values)+1)
+	valKinds := make([]C.int, len(values)+1)
+	for c, k := range keys {
+		for _, name := range k.Path {
+			blob = append(blob, name...)
+			keyLens = append(keyLens, C.uint32_t(len(name)))
+		}
+		keyPathLens[c], keyKinds[c] = C.uint32_t(len(k.Path)), C.int(k.Kind)
+		if k.NullKey {
+			keyFlags[c] = C.SJHIP_GROUP_NULL_KEY
+		}
+	}
+	for c, val := range values {
+		for _, name := range val.Path {
+			blob = append(blob, name...)
+			keyLens = append(keyLens, C.uint32_t(len(name)))
+		}
+		valPathLens[c], valKinds[c] = C.uint32_t(len(val.Path)), C.int(val.Kind)
+	}
+	blob = append(blob, 0)
+	keyLens = append(keyLens, 0)
+	var rows, groups C.size_t
+	keyBytes := make([]C.size_t, len(keys))
+	rc := C.sjhip_group_paths(v.c.h, (*C.uint8_t)(unsafe.Pointer(&blob[0])), &keyLens[0], &keyPathLens[0], &keyKinds[0], &keyFlags[0],
+		C.uint32_t(len(keys)), &valPathLens[0], &valKinds[0], C.uint32_t(len(values)), &rows, &groups, &keyBytes[0])
+	if rc != C.SJHIP_OK {
+		return nil, fmt.Errorf("sjhip: %s", C.GoString(C.sjhip_last_error(v.c.h)))
+	}
+	n, g := int(rows), int(groups)
+	res := &GroupsResult{Rows: n, Groups: g, FirstRow: make([]uint64, g), GroupRows: make([]uint64, g), Codes: make([]uint32, n)}
+	var codes *C.uint32_t
+	if n > 0 {
+		codes = (*C.uint32_t)(unsafe.Pointer(&res.Codes[0]))
+	}
+	if rc := C.sjhip_fetch_groups(v.c.h, nil, nil, u64ptr(res.FirstRow), u64ptr(res.GroupRows), codes, nil); rc != C.SJHIP_OK {
+		return nil, fmt.Errorf("sjhip: %s", C.GoString(C.sjhip_last_error(v.c.h)))
+	}
+	for c, k := range keys {
+		col := GroupKeys{Kind: k.Kind, OK: make([]uint8, g), Status: make([]uint8, n)}
+		var rc C.int
+		switch k.Kind {
+		case GroupString:
+			offs := make([]uint64, g+1)
+			data := make([]uint8, int(keyBytes[c]))
+			rc = C.sjhip_fetch_group_keys(v.c.h, C.uint32_t(c), u64ptr(offs), unsafe.Pointer(u8ptr(data)), u8ptr(col.OK), u8ptr(col.Status))
+			col.Strings = make([][]byte, g)
+			for j := 0; j < g; j++ {
+				col.Strings[j] = data[offs[j]:offs[j+1]]
+			}
+		case GroupBool:
+			b := make([]uint8, g)
+			rc = C.sjhip_fetch_group_keys(v.c.h, C.uint32_t(c), nil, unsafe.Pointer(u8ptr(b)), u8ptr(col.OK), u8ptr(col.Status))
+			col.Values = make([]uint64, g)
+			for j := range b {
+				col.Values[j] = uint64(b[j])
+			}
+		default:
+			col.Values = make([]uint64, g)
+			rc = C.sjhip_fetch_group_keys(v.c.h, C.uint32_t(c), nil, unsafe.Pointer(u64ptr(col.Values)), u8ptr(col.OK), u8ptr(col.Status))
+		}
+		if rc != C.SJHIP_OK {
+			return nil, fmt.Errorf("sjhip: %s", C.GoString(C.sjhip_last_error(v.c.h)))
+		}
+		res.Keys = append(res.Keys, col)
+	}
+	for c, val := range values {
+		a := GroupAggregates{Kind: val.Kind, Count: make([]uint64, g), NotOK: make([]uint64, g), Sum: make([]uint64, g),
+			SumHi: make([]uint64, g), Min: make([]uint64, g), Max: make([]uint64, g)}
+		rc := C.sjhip_fetch_group_aggregates_at(v.c.h, C.uint32_t(c), u64ptr(a.Count), u64ptr(a.NotOK), unsafe.Pointer(u64ptr(a.Sum)),
+			u64ptr(a.SumHi), unsafe.Pointer(u64ptr(a.Min)), unsafe.Pointer(u64ptr(a.Max)))
+		if rc != C.SJHIP_OK {
+			return nil, fmt.Errorf("sjhip: %s", C.GoString(C.sjhip_last_error(v.c.h)))
+		}
+		res.Values = append(res.Values, a)
+	}
+	return res, nil
+}

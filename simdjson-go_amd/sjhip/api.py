@@ -392,6 +392,70 @@ class Context:
             self._check(L.sjhip_fetch_group_aggregates(self._h, ptr(g.count), ptr(g.not_ok), ptr(g.sum), ptr(g.sum_hi), ptr(g.min), ptr(g.max)))
         return g
 
+    GROUP_MAX_KEYS, GROUP_MAX_VALUES, GROUP_NULL_KEY = 8, 8, 1  # SJHIP_GROUP_MAX_KEYS, SJHIP_GROUP_MAX_VALUES, SJHIP_GROUP_NULL_KEY
+
+    def group_paths(self, key_columns, value_columns=(), fetch=True):
+        """group_path by SEVERAL keys with several aggregates: key_columns = [(path, kind) or (path, kind, null_key), ...], 1 to
+        GROUP_MAX_KEYS of them, kind = COL_STRING / COL_INT / COL_UINT / COL_BOOL; value_columns = [(path, kind), ...], up to
+        GROUP_MAX_VALUES, kind = COL_FLOAT / COL_INT / COL_UINT.  A row's key is the tuple of its keys; with null_key a row without
+        an OK key on that column has the entry "no key" there (such rows tie with each other), without it the row is in no group.
+        -> Groups whose key_kind, key_bytes and value_kind are lists (per column) and, after the fetch, so are keys, key_offsets,
+        key_ok (uint8 per group: 0 for "no key") and status (uint8 per row); first_row, group_rows and codes are group_path's, and
+        values[v] is the tuple (count, not_ok, sum, sum_hi, min, max) of value column v.  fetch=False: only the sizes"""
+        kcols = [(tuple(c[0]), int(c[1]), bool(c[2]) if len(c) > 2 else False) for c in key_columns]
+        vcols = [(tuple(path), int(kind)) for path, kind in value_columns]
+        keys = [bytes(k) for path, *_ in kcols + vcols for k in path]
+        nk, nv = len(kcols), len(vcols)
+        key_lens = (C.c_uint32 * max(len(keys), 1))(*[len(k) for k in keys])
+        kpl = (C.c_uint32 * max(nk, 1))(*[len(path) for path, _, _ in kcols])
+        kk = (C.c_int * max(nk, 1))(*[kind for _, kind, _ in kcols])
+        kf = (C.c_uint32 * max(nk, 1))(*[self.GROUP_NULL_KEY if nul else 0 for _, _, nul in kcols])
+        vpl = (C.c_uint32 * max(nv, 1))(*[len(path) for path, _ in vcols])
+        vk = (C.c_int * max(nv, 1))(*[kind for _, kind in vcols])
+        nr, ng, nb = C.c_size_t(0), C.c_size_t(0), (C.c_size_t * max(nk, 1))()
+        self._check(_lib.lib().sjhip_group_paths(self._h, b"".join(keys) if keys else None, key_lens if keys else None, kpl, kk, kf, nk,
+                                                 vpl if nv else None, vk if nv else None, nv, C.byref(nr), C.byref(ng), nb))
+        g = Groups(nr.value, ng.value, [int(b) for b in nb[:nk]], [kind for _, kind, _ in kcols], [kind for _, kind in vcols])
+        return self.fetch_group_paths(g) if fetch else g
+
+    _GROUP_KEY_DTYPES = {1: np.int64, 2: np.uint64, 3: np.uint8}
+
+    def fetch_group_keys(self, col, kind, groups, key_bytes, rows):
+        """column col of the grouping in force (sjhip_fetch_group_keys) -> (keys, key_offsets, key_ok, status): keys a list of bytes
+        for COL_STRING, else an int64 / uint64 / uint8 array; key_offsets None but for COL_STRING"""
+        ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+        key_ok, status = np.empty(groups, dtype=np.uint8), np.empty(rows, dtype=np.uint8)
+        if kind == self.COL_STRING:
+            off, data = np.empty(groups + 1, dtype=np.uint64), np.empty(key_bytes, dtype=np.uint8)
+            self._check(_lib.lib().sjhip_fetch_group_keys(self._h, col, off.ctypes.data, ptr(data), ptr(key_ok), ptr(status)))
+            raw = data.tobytes()
+            return [raw[int(a):int(b)] for a, b in zip(off[:-1], off[1:])], off, key_ok, status
+        keys = np.empty(groups, dtype=self._GROUP_KEY_DTYPES[kind])
+        self._check(_lib.lib().sjhip_fetch_group_keys(self._h, col, None, ptr(keys), ptr(key_ok), ptr(status)))
+        return keys, None, key_ok, status
+
+    def fetch_group_aggregates_at(self, val, kind, groups):
+        """value column val of the grouping in force (sjhip_fetch_group_aggregates_at) -> (count, not_ok, sum, sum_hi, min, max)"""
+        ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+        dt = self._COL_DTYPES[kind]
+        count, not_ok, sum_hi = (np.empty(groups, dtype=np.uint64) for _ in range(3))
+        total, lo, hi = (np.empty(groups, dtype=dt) for _ in range(3))
+        self._check(_lib.lib().sjhip_fetch_group_aggregates_at(self._h, val, ptr(count), ptr(not_ok), ptr(total), ptr(sum_hi), ptr(lo), ptr(hi)))
+        return count, not_ok, total, sum_hi, lo, hi
+
+    def fetch_group_paths(self, g):
+        """the arrays of the last group_paths (g: what it returned with fetch=False) -> g, filled"""
+        ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+        g.first_row, g.group_rows = np.empty(g.groups, dtype=np.uint64), np.empty(g.groups, dtype=np.uint64)
+        g.codes = np.empty(g.rows, dtype=np.uint32)
+        self._check(_lib.lib().sjhip_fetch_groups(self._h, None, None, ptr(g.first_row), ptr(g.group_rows), ptr(g.codes), None))
+        g.keys, g.key_offsets, g.key_ok, g.status = [], [], [], []
+        for col, (kind, nbytes) in enumerate(zip(g.key_kind, g.key_bytes)):
+            for dst, a in zip((g.keys, g.key_offsets, g.key_ok, g.status), self.fetch_group_keys(col, kind, g.groups, nbytes, g.rows)):
+                dst.append(a)
+        g.values = [self.fetch_group_aggregates_at(v, kind, g.groups) for v, kind in enumerate(g.value_kind)]
+        return g
+
     def extract_path_strings(self, path, cvt=False, fetch=True):
         """Iter.FindElement(path...) then Iter.StringBytes (or StringCvt with cvt=True) on every record, built on the device.
         -> (offsets: uint64 array of records + 1, data: bytes, status: uint8 array) -- Arrow's large-string layout; with
@@ -718,7 +782,9 @@ class Aggregate:
 
 
 class Groups:
-    """what Context.group_path returns: the sizes of the grouping, and after the fetch its arrays (see group_path)"""
+    """what Context.group_path returns: the sizes of the grouping, and after the fetch its arrays (see group_path); from
+    Context.group_paths key_bytes, key_kind and value_kind are lists with one entry per column, and so are the fetched keys,
+    key_offsets, key_ok, status and values (see group_paths)"""
 
     def __init__(self, rows, groups, key_bytes, key_kind, value_kind):
         self.rows, self.groups, self.key_bytes, self.key_kind, self.value_kind = rows, groups, key_bytes, key_kind, value_kind
