@@ -828,7 +828,7 @@ extern "C" int sj_selftest_result_state(const uint8_t *ops, size_t n, uint32_t *
         else if (op == 27) s.rows.begin();
         else if (op == 28) s.publish(&sj::ResultState::rows, {1, 1});
         else if (op == 29) s.groups.begin();
-        else if (op == 30) s.publish(&sj::ResultState::groups, {1, 1, 1, 4, -1});
+        else if (op == 30) s.publish(&sj::ResultState::groups, {1, 1, 1, 0, {4}, {}, {1}});  // (one STRING key column of 1 byte, no value)
         else if (op == 31) s.order.begin();
         else if (op == 32) s.publish(&sj::ResultState::order, {1, 1});
         else if (op == 33) s.parents.begin();
@@ -844,8 +844,7 @@ extern "C" int sj_selftest_result_state(const uint8_t *ops, size_t n, uint32_t *
     return 0;
 }
 
-// The sizes of a grouping by several keys (ResultState::Groups with key_cols > 0) through the one `groups` product -- no transition
-// of its own: published on a parsed state, read back, given up by begin, published again and dropped by the next parse.
+// The sizes of a grouping by several keys (ResultState::Groups) through the one `groups` product -- no transition of its own: published on a parsed state, read back, given up by begin, published again and dropped by the next parse.
 // out[0 .. 5): exists after each of those steps; out[5 ..): key_cols, val_cols, key_kinds[1], val_kinds[1], col_bytes[1], groups as
 // read back after the first publish.  Returns GROUP_COLS.
 extern "C" int sj_selftest_groups_sizes(uint64_t *out) {
@@ -907,11 +906,14 @@ extern "C" uint64_t sj_selftest_group_hash_bytes(const uint8_t *s, uint64_t len)
 extern "C" uint64_t sj_selftest_group_hash_int(uint64_t x) { return sj::group_hash_int(x); }
 extern "C" int sj_selftest_group_bytes_equal(const uint8_t *a, const uint8_t *b, uint64_t len) { return sj::group_bytes_equal(a, b, len) ? 1 : 0; }
 extern "C" uint64_t sj_selftest_group_table_capacity(uint64_t n) { return sj::group_table_capacity(n); }
-// the tuple hash of the grouping by several keys, as k_q_mkgrp_keys folds it column by column: hs[c] is column c's hash, has[c] == 0
-// stands for "no key" (tests/group_multi_table.py restates the fold and inverts its last step)
+// the tuple hash of a grouping, as k_q_group_keys folds it column by column: hs[c] is column c's hash, has[c] == 0 stands for "no
+// key"; column 0's hash begins the fold (tests/group_multi_table.py restates the fold and inverts its last step)
 extern "C" uint64_t sj_selftest_group_tuple_hash(const uint64_t *hs, const uint8_t *has, uint32_t n_cols) {
-    uint64_t acc = sj::GROUP_TUPLE_SEED;
-    for (uint32_t c = 0; c < n_cols; c++) acc = sj::group_tuple_fold(acc, has[c] ? hs[c] : sj::GROUP_NO_KEY_HASH);
+    uint64_t acc = 0;
+    for (uint32_t c = 0; c < n_cols; c++) {
+        const uint64_t h = has[c] ? hs[c] : sj::GROUP_NO_KEY_HASH;
+        acc = c ? sj::group_tuple_fold(acc, h) : h;
+    }
     return acc;
 }
 

@@ -1487,204 +1487,46 @@ __global__ __launch_bounds__(256) void k_q_frows_copy(QView q, QFRows o, Arr<u64
     wave_copy_record(q, v, (w0 & TW_PAYLOAD) - v, o.words[r], o.first_str[r], o.s_len[r], o.s_pre[r], threadIdx.x & 63, out_tape, out_strings);
 }
 
-// ---- groups: the distinct keys at a path, a code per row, aggregates per key (sjhip_group_path) ---------------------------------------
-// "group by": the key of a row is FindElement(key path) + Iter.StringBytes or Iter.Int; two rows with an OK key are in one group iff
-// their keys are equal, and groups are numbered by first occurrence -- so codes, dictionary, first rows and group sizes are decided
-// by the input alone, not by the hash or by which lane came first.  All on the device, kernel boundaries do the ordering:
-//   k_q_group_keys     one lane per row: the key's status, its element (STRING: the tape index; INT: the value) and its 64-bit hash
-//                      (sj_group.h: 8 bytes per step).  A long key is hashed -- and later compared -- by its lane alone: the keys
-//                      this serves (a make, a language, a screen name) are short.
+// ---- groups: the distinct keys at a path, a code per row, aggregates per key (sjhip_group_path, sjhip_group_paths) -------------------
+// "group by": the key of a row is a tuple with one entry per key column -- FindElement(the column's path) + Iter.StringBytes, Iter.Int,
+// Iter.Uint or Iter.Bool; two rows in a group are in one group iff their tuples are equal entry by entry, and groups are numbered by
+// first occurrence -- so codes, dictionary, first rows and group sizes are decided by the input alone, not by the hash or by which lane
+// came first.  sjhip_group_path is the tuple of one column.  All on the device, kernel boundaries do the ordering:
+//   k_q_group_keys     once per column, one lane per row: the walk, the conversion, status[c][r] and kidx[c][r] (STRING: the tape
+//                      index; the other kinds: the value) and the key's 64-bit hash (sj_group.h: 8 bytes per step).  A long key is
+//                      hashed -- and later compared -- by its lane alone: the keys this serves (a make, a language, a screen name)
+//                      are short.
 //   k_q_group_insert   the dictionary: an open-addressing table of row numbers (empty: GROUP_NONE), capacity a power of two >= twice
 //                      the rows, linear probing.  A row claims an empty slot by compare-and-swap; on an occupied one it compares its
-//                      key with the occupant ROW's key -- read-only tape / Strings.B / message data, so the slot word is all that is
-//                      communicated -- and on equality lowers the slot to the smaller row (atomicMin, skipped when the occupant is
-//                      smaller already: a handful of distinct keys would otherwise draw every row's atomic to a handful of addresses),
-//                      else probes on.  The occupant only ever changes to a smaller row with an EQUAL key, so a comparison stays
-//                      valid whatever happens to the slot afterwards, and a key always ends in the first slot of its probe sequence
-//                      that did not hold a different key.  Every access to the table here is a device-scope atomic (a plain load
-//                      may be served from another XCD's L2).  No lane waits for another: nothing locks, nothing spins, and because
-//                      the capacity exceeds the rows every probe sequence ends (the loop is bounded by the capacity besides).
-//   k_q_group_first    behind the boundary: row r is the first of its group iff table[slot[r]] == r -> flag (and, STRING, the length
-//                      of its key).  Exclusive scans of both (the tile pattern of sj_tapewalk.h) number the groups and place the
-//                      dictionary's keys; the totals are the groups, the key bytes and -- a third tile sum -- the rows with a key.
-//   k_q_group_emit     codes[r] = the number of its slot's first row; the first rows write their group's entries: first_row, the
-//                      key (a short one by the lane, a long one by the wave, like the string column) or the int64
+//                      key with the occupant ROW's key -- the hash first, then the entries (group_tuples_equal).  What it reads of
+//                      the occupant -- status, kidx, hash, tape, Strings.B, message -- was written before this kernel began and is
+//                      read-only here, so the slot word is all that is communicated.  On equality it lowers the slot to the smaller
+//                      row (atomicMin, skipped when the occupant is smaller already: a handful of distinct keys would otherwise draw
+//                      every row's atomic to a handful of addresses), else probes on.  The occupant only ever changes to a smaller
+//                      row with an EQUAL key, so a comparison stays valid whatever happens to the slot afterwards, and a key always
+//                      ends in the first slot of its probe sequence that did not hold a different key.  Every access to the table
+//                      here is a device-scope atomic (a plain load may be served from another XCD's L2).  No lane waits for
+//                      another: nothing locks, nothing spins, and because the capacity exceeds the rows every probe sequence ends
+//                      (the loop is bounded by the capacity besides).
+//   k_q_group_first    behind the boundary: row r is the first of its group iff table[slot[r]] == r -> flag; per STRING column the
+//                      length of a first row's key (0 without one).  Exclusive scans (the tile pattern of sj_tapewalk.h:
+//                      k_q_group_tile_sums, k_tw_scan_sums, k_q_group_tile_apply, once per scanned array) number the groups and
+//                      place every STRING column's keys; the totals are the groups, the rows in a group -- counted beside the
+//                      flags' tile sums: one atomic per wave on one address took as long as the table -- and the columns' key bytes.
+//   k_q_group_emit     once per column: the column's status of every row, and by the first rows their group's entry -- key_ok, and
+//                      the value, or the offset and the bytes (a short key by the lane, a long one by the wave, like the string
+//                      column).  The launch of column 0 writes codes, first_row and the sort's keys as well.
 //   the sort           the stable radix sort of sj_sort.h: the rows by code, position i being row i, over only as many low digits as
-//                      the group count has (group_pass_mask).  Rows without a key carry the code `groups` and end behind all.
+//                      the group count has (group_pass_mask).  Rows in no group carry the code `groups` and end behind all.
 //   k_q_group_bounds   in the sorted sequence a position whose code differs from the one in front begins a group: the group offsets;
 //   k_q_group_counts   their differences are group_rows -- no contended atomics anywhere.
 // The aggregates are the segmented reduction above with the sorted rows as QAgg::perm and the group offsets as the row offsets
-// (AGG_OFFS): groups in the place of records, so association, 128-bit sums and min / max keys are the tested ones.
+// (AGG_OFFS), once per value column: groups in the place of records, so association, 128-bit sums and min / max keys are the tested ones.
+// Several keys add three things.  The tuple's hash is folded column by column (group_tuple_fold: order-dependent; the first column's
+// hash begins it, so one column hashes as itself).  A column that carries SJHIP_GROUP_NULL_KEY turns a status that is not OK into
+// the entry "no key" (GROUP_NO_KEY_HASH; equal to "no key" only); without the flag such a row is in no group -- the `in` byte.  And
+// every column is one more walk of every row and one more emit: DESIGN.md (Several keys).
 struct QGroup {
-    int key_kind;                      // SJHIP_COL_STRING / SJHIP_COL_INT
-    u32 n;                             // rows
-    u32 mask;                          // capacity of the table - 1
-    Arr<u8> status;                    // [n] the key's status
-    Arr<u64> kidx;                     // [n] STRING: tape index of the key element; INT: the value
-    Arr<u64> hash;                     // [n]
-    Arr<u32> slot;                     // [n] the slot the row ended in
-    Arr<u32> table;                    // [mask + 1] row numbers
-    Arr<u32> flag;                     // [n + 1] 1 at the first row of a group -> exclusive prefix: the group's number
-    Arr<u64> len;                      // [n + 1] STRING: bytes of a first row's key -> their offset in the dictionary; INT: null
-    unsigned long long *tiles_f, *tiles_l, *tiles_o;  // [tiles] tile sums of flag / len / the rows with a key
-    unsigned long long *totals;        // the totals of the scans: [0] groups, [1] key bytes, [2] rows with a key
-};
-struct GroupOut {  // the product (d_group), see group_layout
-    Arr<u64> key_off;     // [groups + 1] STRING
-    Arr<u8> key_bytes;    // [key bytes] STRING
-    Arr<u64> key_int;     // [groups] INT
-    Arr<u64> first_row;   // [groups]
-    Arr<u64> group_rows;  // [groups]
-    Arr<u32> codes;       // [n]
-    Arr<u8> status;       // [n]
-};
-__device__ __forceinline__ bool group_keys_equal(const QView &q, const QGroup &g, u32 a, u32 b) {
-    const u64 ka = g.kidx[a], kb = g.kidx[b];
-    if (g.key_kind == SJHIP_COL_INT) return ka == kb;
-    const u64 len = q.tape[ka + 1];
-    if (len != q.tape[kb + 1]) return false;
-    return group_bytes_equal(str_bytes(q, q.tape[ka], len), str_bytes(q, q.tape[kb], len), len);
-}
-__global__ __launch_bounds__(256) void k_q_group_keys(QView q, QPath pth, QGroup g) {
-    const u32 r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= g.n) return;
-    // (one walk for both kinds -- STRING needs the element itself; row_number in the INT branch would inline the walk a second time)
-    const u64 v = pth.n ? record_find_path(q, pth, r) : row_value(q, r);  // (no keys: the row's own value)
-    int st;
-    u64 k = 0, h = 0;
-    if (v >= SJHIP_PATH_NOT_OBJECT) st = path_status(v);
-    else if (g.key_kind == SJHIP_COL_INT) {
-        st = element_to(q, v, SJHIP_COL_INT, &k);
-        if (st == SJHIP_COL_OK) h = group_hash_int(k);
-    } else {
-        u64 len = 0;
-        st = element_text_len(q, v, false, &len);
-        if (st == SJHIP_COL_OK) {
-            k = v;
-            h = group_hash_bytes(str_bytes(q, q.tape[v], len), len);
-        }
-    }
-    g.status[r] = (u8)st;
-    g.kidx[r] = k;
-    g.hash[r] = h;
-}
-__global__ __launch_bounds__(256) void k_q_group_insert(QView q, QGroup g) {
-    const u32 r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= g.n || g.status[r] != SJHIP_COL_OK) return;
-    const u64 h = g.hash[r];
-    u32 s = (u32)h & g.mask;
-    for (u32 step = 0; step <= g.mask; step++, s = (s + 1u) & g.mask) {
-        u32 *const cell = &g.table[s];
-        u32 cur = __hip_atomic_load(cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == GROUP_NONE) {
-            cur = atomicCAS(cell, GROUP_NONE, r);
-            if (cur == GROUP_NONE) break;  // claimed
-        }
-        if (cur == r) break;
-        if (g.hash[cur] == h && group_keys_equal(q, g, r, cur)) {
-            if (cur > r) (void)atomicMin(cell, r);
-            break;
-        }
-    }
-    g.slot[r] = s;
-}
-// (one lane per entry of the n + 1: entry n is 0, the scans leave the totals there)
-__global__ __launch_bounds__(256) void k_q_group_first(QView q, QGroup g) {
-    const u32 r = blockIdx.x * 256 + threadIdx.x;
-    if (r > g.n) return;
-    const bool first = r < g.n && g.status[r] == SJHIP_COL_OK && g.table[g.slot[r]] == r;
-    g.flag[r] = first ? 1u : 0u;
-    if (g.len) g.len[r] = first ? q.tape[g.kidx[r] + 1] : 0ull;
-}
-// (the rows with a key are counted with the tile sums, as a third scanned array: one atomic per wave on one address took as long as
-// the table)
-__global__ __launch_bounds__(QT) void k_q_group_tile_sums(QGroup g, u32 m) {
-    __shared__ unsigned long long s_w[QT / 64];
-    tile_sums(arr_raw(g.flag), m, g.tiles_f);
-    if (g.len) tile_sums(arr_raw(g.len), m, g.tiles_l);
-    const u32 base = blockIdx.x * QTILE + threadIdx.x * QI;
-    unsigned long long ok = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < QI; k++)
-        if (base + k < g.n && g.status[base + k] == SJHIP_COL_OK) ok++;
-    (void)block_excl_sum(ok, s_w, (int)threadIdx.x, &tot);
-    if (threadIdx.x == 0) g.tiles_o[blockIdx.x] = tot;
-}
-__global__ __launch_bounds__(QT) void k_q_group_tile_apply(QGroup g, u32 m) {
-    tile_apply(arr_raw(g.flag), arr_raw(g.flag), m, g.tiles_f);
-    if (g.len) tile_apply(arr_raw(g.len), arr_raw(g.len), m, g.tiles_l);
-}
-// (sort_keys: the first pass's input -- the row's code, or `groups` for a row without a key)
-__global__ __launch_bounds__(256) void k_q_group_emit(QView q, QGroup g, GroupOut o, u32 groups, Arr<u32> sort_keys) {
-    const u32 r = blockIdx.x * 256 + threadIdx.x;
-    const int lane = threadIdx.x & 63;
-    u64 off = 0, len = 0, w = 0;
-    bool wide = false;
-    if (r < g.n) {
-        const u8 st = g.status[r];
-        u32 code = GROUP_NONE;
-        if (st == SJHIP_COL_OK) {
-            const u32 first = g.table[g.slot[r]];
-            code = g.flag[first];
-            if (first == r) {
-                o.first_row[code] = r;
-                if (g.key_kind == SJHIP_COL_INT) o.key_int[code] = g.kidx[r];
-                else {
-                    off = g.len[r];
-                    len = g.len[r + 1] - off;
-                    o.key_off[code] = off;
-                    w = q.tape[g.kidx[r]];
-                    wide = len > COL_SHORT;
-                    if (!wide && len) copy_bytes(arr_at(o.key_bytes, off, len), str_bytes(q, w, len), len, 0, 1);
-                }
-            }
-        }
-        o.codes[r] = code;
-        o.status[r] = st;
-        sort_keys[r] = code == GROUP_NONE ? groups : code;
-        if (r == 0 && g.key_kind != SJHIP_COL_INT) o.key_off[groups] = g.len[g.n];
-    }
-    wave_copy_strings(q, o.key_bytes, wide, off, len, w, lane);
-}
-// keys: the sorted codes; the first n_ok positions are the rows with a key.  off[g] = the position group g begins at, off[groups] = n_ok
-__global__ __launch_bounds__(256) void k_q_group_bounds(Arr<const u32> keys, u32 n_ok, u32 groups, Arr<u64> off) {
-    const u32 i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_ok) return;
-    const u32 k = keys[i];
-    if (i == 0 || keys[i - 1] != k) off[k] = i;
-    if (i == 0) off[groups] = n_ok;
-}
-__global__ __launch_bounds__(256) void k_q_group_counts(Arr<const u64> off, u32 groups, Arr<u64> group_rows) {
-    const u32 g = blockIdx.x * 256 + threadIdx.x;
-    if (g < groups) group_rows[g] = off[g + 1] - off[g];
-}
-
-// ---- groups by several keys: the distinct TUPLES of up to SJHIP_GROUP_MAX_KEYS key columns (sjhip_group_paths) -----------------------
-// The key of a row is a tuple with one entry per column: the converted key where the column's status is SJHIP_COL_OK, "no key" where
-// it is not and the column carries SJHIP_GROUP_NULL_KEY; a row with any other column that is not OK is in no group.  Two rows are in
-// one group iff their tuples are equal entry by entry, groups are numbered by first occurrence: the input alone decides.  The
-// pipeline is the single key's with the key side generalised; the sort by code, k_q_group_bounds, k_q_group_counts and the segmented
-// reduction are launched as they are.
-//   k_q_mkgrp_keys        once per column, one lane per row: walk, conversion, status[c][r] and kidx[c][r] (STRING: the tape index;
-//                         INT / UINT / BOOL: the value); the column's hash (sj_group.h; GROUP_NO_KEY_HASH without a key) is folded
-//                         into the row's running tuple hash (group_tuple_fold: order-dependent), and the row's "in a group" byte is
-//                         cleared where the column is not OK and has no flag.
-//   k_q_mkgrp_insert      the protocol of k_q_group_insert, unchanged: a table of row numbers, capacity >= twice the rows, claimed by
-//                         compare-and-swap, lowered by atomicMin to the smaller of two rows with EQUAL tuples, every access a
-//                         device-scope atomic, the probe bounded by the capacity, no lane waiting for another.  Equality is the
-//                         tuple's: the hash first, then per column the two ok flags, then the value, or the length and the bytes.
-//                         What it reads of the occupant ROW -- status, kidx, hash, tape, Strings.B, message -- was written before
-//                         this kernel began and is read-only here, so the slot word is all that is communicated; the occupant only
-//                         ever changes to a smaller row with an equal tuple, so a comparison stays valid whatever happens to the
-//                         slot afterwards, and a tuple ends in the first slot of its probe sequence that held no different one.
-//   k_q_mkgrp_first       flag[r] = row r is the first of its group; per STRING column the length of a first row's key (0 without
-//                         one).  k_q_mkgrp_tile_sums / k_tw_scan_sums / k_q_mkgrp_tile_apply run once per scanned array: the flags
-//                         (with the count of the rows in a group beside them), then every STRING column's lengths.
-//   k_q_mkgrp_emit        once per column: the column's entry of every group (key_ok, and the value, or the offset and the bytes --
-//                         a short key by the lane, a long one by the wave) and the column's status of every row; the launch of
-//                         column 0 writes codes, first_row and the sort's keys as well.
-// A long key is hashed and compared by its lane alone, and every column is one walk of every row: DESIGN.md (Several keys).
-struct QMkGrp {
     u32 n, mask, n_cols;
     u32 kinds;       // 4 bits per column: its SJHIP_COL_* kind
     u32 null_mask;   // bit c: column c carries SJHIP_GROUP_NULL_KEY
@@ -1700,7 +1542,7 @@ struct QMkGrp {
     Arr<u64> len;    // [STRING columns * (n + 1)] bytes of a first row's key -> their offset among the column's entries
     unsigned long long *tiles_f, *tiles_o, *tiles_l;  // [tiles] flags / rows in a group; [STRING columns * tiles] lengths
 };
-struct MkGrpOut {  // column c of the product (d_group), and what the launch of column 0 writes beside it: see mkgrp_layout
+struct GroupOut {  // column c of the product (d_group), and what the launch of column 0 writes beside it: see group_layout
     Arr<u64> key_off;    // [groups + 1] STRING
     Arr<u8> key_bytes;   // [key bytes] STRING
     Arr<u64> key_val;    // [groups] INT, UINT
@@ -1710,16 +1552,16 @@ struct MkGrpOut {  // column c of the product (d_group), and what the launch of 
     Arr<u64> first_row;  // [groups]
     Arr<u32> codes;      // [n]
 };
-__device__ __forceinline__ int mkgrp_kind(const QMkGrp &g, u32 c) { return (int)((g.kinds >> (4u * c)) & 15u); }
-__device__ __forceinline__ u64 mkgrp_len_at(const QMkGrp &g, u32 c) { return (u64)((g.str_slot >> (4u * c)) & 15u) * ((u64)g.n + 1u); }
-__device__ __forceinline__ bool mkgrp_tuples_equal(const QView &q, const QMkGrp &g, u32 a, u32 b) {
+__device__ __forceinline__ int group_kind(const QGroup &g, u32 c) { return (int)((g.kinds >> (4u * c)) & 15u); }
+__device__ __forceinline__ u64 group_len_at(const QGroup &g, u32 c) { return (u64)((g.str_slot >> (4u * c)) & 15u) * ((u64)g.n + 1u); }
+__device__ __forceinline__ bool group_tuples_equal(const QView &q, const QGroup &g, u32 a, u32 b) {
     for (u32 c = 0; c < g.n_cols; c++) {
         const u64 at = (u64)c * g.n;
         const bool ok = g.status[at + a] == SJHIP_COL_OK;
         if (ok != (g.status[at + b] == SJHIP_COL_OK)) return false;
         if (!ok) continue;  // "no key" equals "no key"
         const u64 ka = g.kidx[at + a], kb = g.kidx[at + b];
-        if (mkgrp_kind(g, c) != SJHIP_COL_STRING) {
+        if (group_kind(g, c) != SJHIP_COL_STRING) {
             if (ka != kb) return false;
             continue;
         }
@@ -1729,10 +1571,10 @@ __device__ __forceinline__ bool mkgrp_tuples_equal(const QView &q, const QMkGrp 
     }
     return true;
 }
-__global__ __launch_bounds__(256) void k_q_mkgrp_keys(QView q, QPath pth, QMkGrp g, u32 c) {
+__global__ __launch_bounds__(256) void k_q_group_keys(QView q, QPath pth, QGroup g, u32 c) {
     const u32 r = blockIdx.x * 256 + threadIdx.x;
     if (r >= g.n) return;
-    const int kind = mkgrp_kind(g, c);
+    const int kind = group_kind(g, c);
     const u64 v = pth.n ? record_find_path(q, pth, r) : row_value(q, r);  // (no keys: the row's own value)
     int st;
     u64 k = 0, h = GROUP_NO_KEY_HASH;
@@ -1752,12 +1594,12 @@ __global__ __launch_bounds__(256) void k_q_mkgrp_keys(QView q, QPath pth, QMkGrp
     const u64 at = (u64)c * g.n + r;
     g.status[at] = (u8)st;
     g.kidx[at] = k;
-    g.hash[r] = group_tuple_fold(c ? g.hash[r] : GROUP_TUPLE_SEED, h);
+    g.hash[r] = c ? group_tuple_fold(g.hash[r], h) : h;
     const bool keeps = st == SJHIP_COL_OK || ((g.null_mask >> c) & 1u);
     if (c == 0) g.in[r] = keeps ? 1 : 0;
     else if (!keeps) g.in[r] = 0;
 }
-__global__ __launch_bounds__(256) void k_q_mkgrp_insert(QView q, QMkGrp g) {
+__global__ __launch_bounds__(256) void k_q_group_insert(QView q, QGroup g) {
     const u32 r = blockIdx.x * 256 + threadIdx.x;
     if (r >= g.n || !g.in[r]) return;
     const u64 h = g.hash[r];
@@ -1770,7 +1612,7 @@ __global__ __launch_bounds__(256) void k_q_mkgrp_insert(QView q, QMkGrp g) {
             if (cur == GROUP_NONE) break;  // claimed
         }
         if (cur == r) break;
-        if (g.hash[cur] == h && mkgrp_tuples_equal(q, g, r, cur)) {
+        if (g.hash[cur] == h && group_tuples_equal(q, g, r, cur)) {
             if (cur > r) (void)atomicMin(cell, r);
             break;
         }
@@ -1778,26 +1620,27 @@ __global__ __launch_bounds__(256) void k_q_mkgrp_insert(QView q, QMkGrp g) {
     g.slot[r] = s;
 }
 // (one lane per entry of the n + 1: entry n is 0, the scans leave the totals there)
-__global__ __launch_bounds__(256) void k_q_mkgrp_first(QView q, QMkGrp g) {
+__global__ __launch_bounds__(256) void k_q_group_first(QView q, QGroup g) {
     const u32 r = blockIdx.x * 256 + threadIdx.x;
     if (r > g.n) return;
     const bool first = r < g.n && g.in[r] && g.table[g.slot[r]] == r;
     g.flag[r] = first ? 1u : 0u;
     for (u32 c = 0; c < g.n_cols; c++) {
-        if (mkgrp_kind(g, c) != SJHIP_COL_STRING) continue;
+        if (group_kind(g, c) != SJHIP_COL_STRING) continue;
         const u64 at = (u64)c * g.n + r;
-        g.len[mkgrp_len_at(g, c) + r] = first && g.status[at] == SJHIP_COL_OK ? q.tape[g.kidx[at] + 1] : 0ull;
+        g.len[group_len_at(g, c) + r] = first && g.status[at] == SJHIP_COL_OK ? q.tape[g.kidx[at] + 1] : 0ull;
     }
 }
-// which = 0: the flags, and the rows in a group counted beside them (as k_q_group_tile_sums counts the rows with a key);
-// which = 1 + s: the lengths of the STRING column with the length array s
-__global__ __launch_bounds__(QT) void k_q_mkgrp_tile_sums(QMkGrp g, u32 m, u32 which) {
+// round 0: the flags, the rows in a group counted beside them, and the length array 0 (the first STRING column's, if there is one);
+// round s >= 1: the length array s
+__global__ __launch_bounds__(QT) void k_q_group_tile_sums(QGroup g, u32 m, u32 round) {
     __shared__ unsigned long long s_w[QT / 64];
-    if (which) {
-        tile_sums(arr_at(g.len, (u64)(which - 1u) * m, m), m, g.tiles_l + (size_t)(which - 1u) * g.tiles);
+    if (round) {
+        tile_sums(arr_at(g.len, (u64)round * m, m), m, g.tiles_l + (size_t)round * g.tiles);
         return;
     }
     tile_sums(arr_at(g.flag, 0, m), m, g.tiles_f);
+    if (g.len) tile_sums(arr_at(g.len, 0, m), m, g.tiles_l);
     const u32 base = blockIdx.x * QTILE + threadIdx.x * QI;
     unsigned long long in = 0, tot = 0;
 #pragma unroll
@@ -1806,20 +1649,20 @@ __global__ __launch_bounds__(QT) void k_q_mkgrp_tile_sums(QMkGrp g, u32 m, u32 w
     (void)block_excl_sum(in, s_w, (int)threadIdx.x, &tot);
     if (threadIdx.x == 0) g.tiles_o[blockIdx.x] = tot;
 }
-__global__ __launch_bounds__(QT) void k_q_mkgrp_tile_apply(QMkGrp g, u32 m, u32 which) {
-    if (which) {
-        u64 *const len = arr_at(g.len, (u64)(which - 1u) * m, m);
-        tile_apply(len, len, m, g.tiles_l + (size_t)(which - 1u) * g.tiles);
-        return;
+__global__ __launch_bounds__(QT) void k_q_group_tile_apply(QGroup g, u32 m, u32 round) {
+    if (round || g.len) {
+        u64 *const len = arr_at(g.len, (u64)round * m, m);
+        tile_apply(len, len, m, g.tiles_l + (size_t)round * g.tiles);
     }
+    if (round) return;
     u32 *const flag = arr_at(g.flag, 0, m);
     tile_apply(flag, flag, m, g.tiles_f);
 }
 // (sort_keys: the first pass's input -- the row's code, or `groups` for a row in no group; written by the launch of column 0)
-__global__ __launch_bounds__(256) void k_q_mkgrp_emit(QView q, QMkGrp g, MkGrpOut o, u32 groups, Arr<u32> sort_keys, u32 c) {
+__global__ __launch_bounds__(256) void k_q_group_emit(QView q, QGroup g, GroupOut o, u32 groups, Arr<u32> sort_keys, u32 c) {
     const u32 r = blockIdx.x * 256 + threadIdx.x;
     const int lane = threadIdx.x & 63;
-    const int kind = mkgrp_kind(g, c);
+    const int kind = group_kind(g, c);
     u64 off = 0, len = 0, w = 0;
     bool wide = false;
     if (r < g.n) {
@@ -1840,7 +1683,7 @@ __global__ __launch_bounds__(256) void k_q_mkgrp_emit(QView q, QMkGrp g, MkGrpOu
             const bool ok = st == SJHIP_COL_OK;
             o.key_ok[code] = ok ? 1 : 0;
             if (kind == SJHIP_COL_STRING) {
-                const u64 la = mkgrp_len_at(g, c) + r;
+                const u64 la = group_len_at(g, c) + r;
                 off = g.len[la];
                 len = g.len[la + 1] - off;  // (0 without a key)
                 o.key_off[code] = off;
@@ -1852,9 +1695,21 @@ __global__ __launch_bounds__(256) void k_q_mkgrp_emit(QView q, QMkGrp g, MkGrpOu
             } else if (kind == SJHIP_COL_BOOL) o.key_u8[code] = (u8)g.kidx[at];
             else o.key_val[code] = g.kidx[at];
         }
-        if (r == 0 && kind == SJHIP_COL_STRING) o.key_off[groups] = g.len[mkgrp_len_at(g, c) + g.n];
+        if (r == 0 && kind == SJHIP_COL_STRING) o.key_off[groups] = g.len[group_len_at(g, c) + g.n];
     }
     wave_copy_strings(q, o.key_bytes, wide, off, len, w, lane);
+}
+// keys: the sorted codes; the first n_ok positions are the rows with a key.  off[g] = the position group g begins at, off[groups] = n_ok
+__global__ __launch_bounds__(256) void k_q_group_bounds(Arr<const u32> keys, u32 n_ok, u32 groups, Arr<u64> off) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_ok) return;
+    const u32 k = keys[i];
+    if (i == 0 || keys[i - 1] != k) off[k] = i;
+    if (i == 0) off[groups] = n_ok;
+}
+__global__ __launch_bounds__(256) void k_q_group_counts(Arr<const u64> off, u32 groups, Arr<u64> group_rows) {
+    const u32 g = blockIdx.x * 256 + threadIdx.x;
+    if (g < groups) group_rows[g] = off[g + 1] - off[g];
 }
 
 // ---- order: the rows ranked by a numeric key at a path, the first `limit` of them kept (sjhip_order_path) ----------------------------
@@ -3999,63 +3854,12 @@ static int fetch_copies(sjhip_ctx *ctx, const FetchCopy *copies, size_t n, const
 }
 
 // ---- groups --------------------------------------------------------------------------------------------------------------------------
-// sjhip_group_path works on the whole result of one context (a sharded one is refused: its dictionaries would have to be joined).
-// The work arrays of all its kernels (GroupWork) lie in d_kat, laid out once for the row count -- the group count is only known
-// after the first half, and a second reservation would move the arena --; the product (GroupOut, and the six aggregate arrays
-// behind it) lies in d_group, reserved when the scans have told the group count and the key bytes.  One host round trip in the
-// middle (the three totals), one wait at the end.
-struct GroupWork {
-    unsigned long long *totals;
-    QGroup g;
-    SortWork<u32> sort;
-    u64 *off;  // [groups + 1] the group offsets in the sorted order (room for one group per row)
-    AggWork agg;
-};
-static size_t group_work_layout(Carve c, uint32_t n, int key_kind, bool value, GroupWork *w) {
-    const u64 cap = group_table_capacity(n);
-    const u32 tiles = tiles_of(n);
-    w->totals = c.take<unsigned long long>(32);
-    w->g.key_kind = key_kind;
-    w->g.n = n;
-    w->g.mask = (u32)(cap - 1);
-    w->g.totals = w->totals;
-    u8 *const status = c.take<u8>(n);
-    u64 *const kidx = c.take<u64>(n), *const hash = c.take<u64>(n);
-    u32 *const slot = c.take<u32>(n), *const table = c.take<u32>(cap), *const flag = c.take<u32>((size_t)n + 1);
-    u64 *const len = key_kind == SJHIP_COL_INT ? nullptr : c.take<u64>((size_t)n + 1);
-    w->g.status = SJ_ARR(status, n, A_GROUP_ROW);
-    w->g.kidx = SJ_ARR(kidx, n, A_GROUP_ROW);
-    w->g.hash = SJ_ARR(hash, n, A_GROUP_ROW);
-    w->g.slot = SJ_ARR(slot, n, A_GROUP_ROW);
-    w->g.table = SJ_ARR(table, cap, A_GROUP_TABLE);
-    w->g.flag = SJ_ARR(flag, (size_t)n + 1, A_GROUP_ROW);
-    w->g.len = SJ_ARR(len, len ? (size_t)n + 1 : 0, A_GROUP_ROW);
-    w->g.tiles_f = c.take<unsigned long long>(tiles);
-    w->g.tiles_l = c.take<unsigned long long>(tiles);
-    w->g.tiles_o = c.take<unsigned long long>(tiles);
-    sort_carve(c, n, &w->sort);
-    w->off = c.take<u64>((size_t)n + 1);
-    if (value) (void)(c.used = agg_layout(c, n, n, AGG_OFFS, &w->agg, false));
-    return c.used;
-}
-// The grouping in d_group: what the two fetches return, and nothing else.
-struct GroupArrays {
-    u64 *key_off, *key_int, *first_row, *group_rows, *agg;
-    u8 *key_bytes, *status;
-    u32 *codes;
-};
-static size_t group_layout(Carve c, const ResultState::Groups &z, GroupArrays *o) {
-    const bool ints = z.key_kind == SJHIP_COL_INT;
-    o->key_off = ints ? nullptr : c.take<u64>(z.groups + 1);
-    o->key_bytes = ints ? nullptr : c.take<u8>(z.key_bytes);
-    o->key_int = ints ? c.take<u64>(z.groups) : nullptr;
-    o->first_row = c.take<u64>(z.groups);
-    o->group_rows = c.take<u64>(z.groups);
-    o->codes = c.take<u32>(z.rows);
-    o->status = c.take<u8>(z.rows);
-    o->agg = z.val_kind == SJHIP_GROUP_NO_VALUE ? nullptr : c.take<u64>(6 * z.groups);
-    return c.used;
-}
+// sjhip_group_path and sjhip_group_paths work on the whole result of one context (a sharded one is refused: its dictionaries would
+// have to be joined); each checks its own arguments and hands over to group_build.  The work arrays of all the kernels (GroupWork)
+// lie in d_kat, laid out once for the row count and the columns -- the group count is only known after the first half, and a second
+// reservation would move the arena --; the product (group_layout: per key column its entries and statuses, per value column six
+// aggregate arrays) lies in d_group, reserved when the scans have told the groups and every STRING column's key bytes.  One host
+// round trip in the middle (those totals and the rows in a group), one wait at the end.
 // Behind the emit of a grouping, by one key or by several: the n rows ordered by code, stably (the first pass's keys lie in
 // sort.keys[0]); the offsets and sizes of the G groups over the n_in sorted rows that are in a group; and one segmented reduction
 // per value column over those rows -- groups in the place of records, on the work arrays `laid` out for n rows.
@@ -4087,103 +3891,17 @@ static int group_reduce(sjhip_ctx *ctx, uint32_t n, u32 n_in, u32 G, const SortW
     }
     return SJHIP_OK;
 }
-
-int sjhip_group_path(sjhip_ctx *ctx, const uint8_t *key_keys, const uint32_t *key_key_lens, uint32_t key_n_keys, int key_kind,
-                     const uint8_t *val_keys, const uint32_t *val_key_lens, uint32_t val_n_keys, int val_kind, size_t *rows, size_t *groups,
-                     size_t *key_bytes) {
-    if (!ctx) return SJHIP_ERR_ARG;
-    if (!rows || !groups || !key_bytes) {
-        ctx_set_error(ctx, "sjhip_group_path: a null size pointer");
-        return SJHIP_ERR_ARG;
-    }
-    if (key_kind != SJHIP_COL_STRING && key_kind != SJHIP_COL_INT) {
-        ctx_set_error(ctx, "sjhip_group_path: key kind %d is not SJHIP_COL_STRING or SJHIP_COL_INT", key_kind);
-        return SJHIP_ERR_ARG;
-    }
-    const bool value = val_kind != SJHIP_GROUP_NO_VALUE;
-    if (value && val_kind != SJHIP_COL_FLOAT && val_kind != SJHIP_COL_INT && val_kind != SJHIP_COL_UINT) {
-        ctx_set_error(ctx, "sjhip_group_path: value kind %d is not SJHIP_COL_FLOAT, SJHIP_COL_INT, SJHIP_COL_UINT or SJHIP_GROUP_NO_VALUE", val_kind);
-        return SJHIP_ERR_ARG;
-    }
-    WholePath kv[2] = {{key_keys, key_key_lens, key_n_keys}, {nullptr, nullptr, 0}};
-    if (value) kv[1] = {val_keys, val_key_lens, val_n_keys};
-    uint32_t n = 0;
-    int rc = whole_entry(ctx, "sjhip_group_path", "the dictionaries of shards are not joined", kv, 2, &n);
-    if (rc) return rc;
-    const QView &qk = kv[0].q, &qv = kv[1].q;
-    const QPath &kpth = kv[0].pth, &vpth = kv[1].pth;
-    // ---- nothing was touched up to here; from here on the last grouping is gone ----
-    ctx->res.groups.begin();
-    ResultState::Groups z;
-    z.rows = n, z.key_kind = key_kind, z.val_kind = val_kind;
-    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
-    if (n == 0) {
-        *rows = *groups = *key_bytes = 0;
-        return published(ctx, ctx->res.publish(&ResultState::groups, z));
-    }
-    GroupWork w;
-    rc = reserve_layout(ctx, ctx->d_kat, [&](Carve c) { return group_work_layout(c, n, key_kind, value, &w); });
-    if (rc) return rc;
-    hipStream_t st = ctx->stream;
-    const dim3 per_row((n + 255) / 256), per_entry((n + 1u + 255) / 256), b256(256), one(1), wide(1024);
-    unsigned long long *const none = nullptr;
-    HIPCHK(hipMemsetAsync(w.totals, 0, 256, st), "group totals memset");
-    HIPCHK(hipMemsetAsync(arr_raw(w.g.table), 0xff, ((size_t)w.g.mask + 1) * 4, st), "group table memset");
-    hipLaunchKernelGGL(k_q_group_keys, per_row, b256, 0, st, qk, kpth, w.g);
-    hipLaunchKernelGGL(k_q_group_insert, per_row, b256, 0, st, qk, w.g);
-    hipLaunchKernelGGL(k_q_group_first, per_entry, b256, 0, st, qk, w.g);
-    const u32 tiles = tiles_of(n);
-    hipLaunchKernelGGL(k_q_group_tile_sums, dim3(tiles), dim3(QT), 0, st, w.g, n + 1u);
-    hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.g.tiles_f, w.g.len ? w.g.tiles_l : none, w.g.tiles_o, tiles, w.totals);
-    hipLaunchKernelGGL(k_q_group_tile_apply, dim3(tiles), dim3(QT), 0, st, w.g, n + 1u);
-    HIPCHK(hipGetLastError(), "group launch");
-    unsigned long long *const h = (unsigned long long *)(ctx->h_scratch + 512);
-    HIPCHK(hipMemcpyAsync(h, w.totals, 32, hipMemcpyDeviceToHost, st), "D2H group totals");
-    HIPCHK(hipStreamSynchronize(st), "group sync");
-    rc = query_bounds_check(ctx);
-    if (rc) return rc;
-    const u32 G = (u32)h[0], n_ok = (u32)h[2];
-    z.groups = G;
-    z.key_bytes = key_kind == SJHIP_COL_INT ? (size_t)8 * G : (size_t)h[1];
-    GroupArrays a;
-    rc = reserve_layout(ctx, ctx->d_group, [&](Carve c) { return group_layout(c, z, &a); });
-    if (rc) return rc;
-    GroupOut o;
-    o.key_off = SJ_ARR(a.key_off, a.key_off ? (size_t)G + 1 : 0, A_GROUP_OUT);
-    o.key_bytes = SJ_ARR(a.key_bytes, a.key_bytes ? z.key_bytes : 0, A_GROUP_KEYS);
-    o.key_int = SJ_ARR(a.key_int, a.key_int ? G : 0, A_GROUP_OUT);
-    o.first_row = SJ_ARR(a.first_row, G, A_GROUP_OUT);
-    o.group_rows = SJ_ARR(a.group_rows, G, A_GROUP_OUT);
-    o.codes = SJ_ARR(a.codes, n, A_GROUP_OUT);
-    o.status = SJ_ARR(a.status, n, A_GROUP_OUT);
-    u32 *const first_keys = w.sort.keys[0];
-    hipLaunchKernelGGL(k_q_group_emit, per_row, b256, 0, st, qk, w.g, o, G, SJ_ARR(first_keys, n, A_SORT));
-    const GroupValue gv = {&qv, &vpth, val_kind, a.agg};
-    rc = group_reduce(ctx, n, n_ok, G, w.sort, w.off, o.group_rows, w.agg, &gv, value ? 1u : 0u);
-    if (rc) return rc;
-    HIPCHK(hipGetLastError(), "group emit launch");
-    HIPCHK(hipStreamSynchronize(st), "group build sync");
-    rc = query_bounds_check(ctx);
-    if (rc) return rc;
-    *rows = n, *groups = G, *key_bytes = z.key_bytes;
-    return published(ctx, ctx->res.publish(&ResultState::groups, z));
-}
-
-// ---- groups by several keys ----------------------------------------------------------------------------------------------------------
-// sjhip_group_paths: the build above with the key side of the k_q_mkgrp_* kernels.  The work arrays (MkGrpWork) lie in d_kat, laid
-// out once for the row count and the columns; the product (mkgrp_layout) in d_group, reserved behind the one host round trip in the
-// middle, which brings the groups, the rows in a group and every STRING column's key bytes.
-struct MkGrpWork {
-    unsigned long long *totals;  // [0] groups, [2] rows in a group, [3 + s] the key bytes of the STRING column with the length array s
-    QMkGrp g;
+struct GroupWork {
+    unsigned long long *totals;  // [0] groups, [2] rows in a group; the key bytes of the length array s: [1] for s = 0, else [2 + s]
+    QGroup g;
     SortWork<u32> sort;
     u64 *off;  // [groups + 1] the group offsets in the sorted order (room for one group per row)
     AggWork agg;
 };
-static size_t mkgrp_work_layout(Carve c, uint32_t n, const int *kinds, const uint32_t *flags, uint32_t n_cols, bool value, MkGrpWork *w) {
+static size_t group_work_layout(Carve c, uint32_t n, const int *kinds, const uint32_t *flags, uint32_t n_cols, bool value, GroupWork *w) {
     const u64 cap = group_table_capacity(n);
     const u32 tiles = tiles_of(n);
-    QMkGrp &g = w->g;
+    QGroup &g = w->g;
     w->totals = c.take<unsigned long long>(32);
     g.n = n, g.mask = (u32)(cap - 1), g.n_cols = n_cols, g.tiles = tiles;
     g.kinds = g.null_mask = g.str_slot = 0;
@@ -4198,14 +3916,14 @@ static size_t mkgrp_work_layout(Carve c, uint32_t n, const int *kinds, const uin
     u64 *const kidx = c.take<u64>(per_col), *const hash = c.take<u64>(n);
     u32 *const slot = c.take<u32>(n), *const table = c.take<u32>(cap), *const flag = c.take<u32>((size_t)n + 1);
     u64 *const len = n_str ? c.take<u64>(lens) : nullptr;
-    g.status = SJ_ARR(status, per_col, A_MKGRP_ROW);
-    g.in = SJ_ARR(in, n, A_MKGRP_ROW);
-    g.kidx = SJ_ARR(kidx, per_col, A_MKGRP_ROW);
-    g.hash = SJ_ARR(hash, n, A_MKGRP_ROW);
-    g.slot = SJ_ARR(slot, n, A_MKGRP_ROW);
+    g.status = SJ_ARR(status, per_col, A_GROUP_ROW);
+    g.in = SJ_ARR(in, n, A_GROUP_ROW);
+    g.kidx = SJ_ARR(kidx, per_col, A_GROUP_ROW);
+    g.hash = SJ_ARR(hash, n, A_GROUP_ROW);
+    g.slot = SJ_ARR(slot, n, A_GROUP_ROW);
     g.table = SJ_ARR(table, cap, A_GROUP_TABLE);
-    g.flag = SJ_ARR(flag, (size_t)n + 1, A_MKGRP_ROW);
-    g.len = SJ_ARR(len, lens, A_MKGRP_LEN);
+    g.flag = SJ_ARR(flag, (size_t)n + 1, A_GROUP_ROW);
+    g.len = SJ_ARR(len, lens, A_GROUP_LEN);
     g.tiles_f = c.take<unsigned long long>(tiles);
     g.tiles_o = c.take<unsigned long long>(tiles);
     g.tiles_l = c.take<unsigned long long>((size_t)n_str * tiles);
@@ -4214,14 +3932,14 @@ static size_t mkgrp_work_layout(Carve c, uint32_t n, const int *kinds, const uin
     if (value) (void)(c.used = agg_layout(c, n, n, AGG_OFFS, &w->agg, false));
     return c.used;
 }
-// The grouping by several keys in d_group: what its fetches return, and nothing else.
-struct MkGrpArrays {
+// The grouping in d_group: what the fetches return, and nothing else.
+struct GroupArrays {
     u64 *first_row, *group_rows, *agg[ResultState::GROUP_COLS], *key_off[ResultState::GROUP_COLS], *key_val[ResultState::GROUP_COLS];
     u32 *codes;
     u8 *key_bytes[ResultState::GROUP_COLS], *key_u8[ResultState::GROUP_COLS], *key_ok[ResultState::GROUP_COLS], *status[ResultState::GROUP_COLS];
 };
-static size_t mkgrp_layout(Carve c, const ResultState::Groups &z, MkGrpArrays *o) {
-    *o = MkGrpArrays{};
+static size_t group_layout(Carve c, const ResultState::Groups &z, GroupArrays *o) {
+    *o = GroupArrays{};
     o->first_row = c.take<u64>(z.groups);
     o->group_rows = c.take<u64>(z.groups);
     for (uint32_t v = 0; v < z.val_cols; v++) o->agg[v] = c.take<u64>(6 * z.groups);
@@ -4237,6 +3955,89 @@ static size_t mkgrp_layout(Carve c, const ResultState::Groups &z, MkGrpArrays *o
         o->status[k] = c.take<u8>(z.rows);
     }
     return c.used;
+}
+// The build behind the argument checks of both calls (`call` names the caller in the error texts): k holds the paths of the
+// n_key_cols key columns, then those of the n_val_cols value columns; key_flags may be null (no column has a flag).
+static int group_build(sjhip_ctx *ctx, const char *call, WholePath *k, const int *key_kinds, const uint32_t *key_flags, uint32_t n_key_cols,
+                       const int *val_kinds, uint32_t n_val_cols, size_t *rows, size_t *groups, size_t *key_bytes) {
+    uint32_t n = 0;
+    int rc = whole_entry(ctx, call, "the dictionaries of shards are not joined", k, (int)(n_key_cols + n_val_cols), &n);
+    if (rc) return rc;
+    // ---- nothing was touched up to here; from here on the last grouping is gone ----
+    ctx->res.groups.begin();
+    ResultState::Groups z;
+    z.rows = n, z.key_cols = n_key_cols, z.val_cols = n_val_cols;
+    for (uint32_t c = 0; c < n_key_cols; c++) z.key_kinds[c] = key_kinds[c], key_bytes[c] = 0;
+    for (uint32_t v = 0; v < n_val_cols; v++) z.val_kinds[v] = val_kinds[v];
+    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    if (n == 0) {
+        *rows = *groups = 0;
+        return published(ctx, ctx->res.publish(&ResultState::groups, z));
+    }
+    GroupWork w;
+    rc = reserve_layout(ctx, ctx->d_kat, [&](Carve c) { return group_work_layout(c, n, key_kinds, key_flags, n_key_cols, n_val_cols != 0, &w); });
+    if (rc) return rc;
+    const QView &q0 = k[0].q;  // (the kernels behind the walks read the tape and the strings only: any column's view)
+    hipStream_t st = ctx->stream;
+    const dim3 per_row((n + 255) / 256), per_entry((n + 1u + 255) / 256), b256(256), one(1), wide(1024);
+    unsigned long long *const none = nullptr;
+    const u32 tiles = w.g.tiles;
+    u32 n_str = 0;
+    for (uint32_t c = 0; c < n_key_cols; c++) n_str += key_kinds[c] == SJHIP_COL_STRING;
+    HIPCHK(hipMemsetAsync(w.totals, 0, 256, st), "group totals memset");
+    HIPCHK(hipMemsetAsync(arr_raw(w.g.table), 0xff, ((size_t)w.g.mask + 1) * 4, st), "group table memset");
+    for (uint32_t c = 0; c < n_key_cols; c++) hipLaunchKernelGGL(k_q_group_keys, per_row, b256, 0, st, k[c].q, k[c].pth, w.g, c);
+    hipLaunchKernelGGL(k_q_group_insert, per_row, b256, 0, st, q0, w.g);
+    hipLaunchKernelGGL(k_q_group_first, per_entry, b256, 0, st, q0, w.g);
+    // sums -> scan -> apply: the flags with the length array 0 beside them, then one round per further length array
+    for (u32 round = 0; round == 0 || round < n_str; round++) {
+        hipLaunchKernelGGL(k_q_group_tile_sums, dim3(tiles), dim3(QT), 0, st, w.g, n + 1u, round);
+        if (round == 0) hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.g.tiles_f, n_str ? w.g.tiles_l : none, w.g.tiles_o, tiles, w.totals);
+        else hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.g.tiles_l + (size_t)round * tiles, none, none, tiles, w.totals + 2 + round);
+        hipLaunchKernelGGL(k_q_group_tile_apply, dim3(tiles), dim3(QT), 0, st, w.g, n + 1u, round);
+    }
+    HIPCHK(hipGetLastError(), "group launch");
+    unsigned long long *const h = (unsigned long long *)(ctx->h_scratch + 512);
+    HIPCHK(hipMemcpyAsync(h, w.totals, (3 + (size_t)ResultState::GROUP_COLS) * 8, hipMemcpyDeviceToHost, st), "D2H group totals");
+    HIPCHK(hipStreamSynchronize(st), "group sync");
+    rc = query_bounds_check(ctx);
+    if (rc) return rc;
+    const u32 G = (u32)h[0], n_in = (u32)h[2];
+    z.groups = G;
+    for (uint32_t c = 0, s = 0; c < n_key_cols; c++) {
+        const int kind = key_kinds[c];
+        if (kind != SJHIP_COL_STRING) z.col_bytes[c] = kind == SJHIP_COL_BOOL ? (size_t)G : (size_t)8 * G;
+        else z.col_bytes[c] = (size_t)h[s ? 2 + s : 1], s++;
+    }
+    GroupArrays a;
+    rc = reserve_layout(ctx, ctx->d_group, [&](Carve c) { return group_layout(c, z, &a); });
+    if (rc) return rc;
+    u32 *const first_keys = w.sort.keys[0];
+    for (uint32_t c = 0; c < n_key_cols; c++) {
+        GroupOut o;
+        u64 *const key_off = a.key_off[c], *const key_val = a.key_val[c];
+        u8 *const col_bytes = a.key_bytes[c], *const key_u8 = a.key_u8[c], *const key_ok = a.key_ok[c], *const status = a.status[c];
+        o.key_off = SJ_ARR(key_off, key_off ? (size_t)G + 1 : 0, A_GROUP_OUT);
+        o.key_bytes = SJ_ARR(col_bytes, col_bytes ? z.col_bytes[c] : 0, A_GROUP_KEYS);
+        o.key_val = SJ_ARR(key_val, key_val ? G : 0, A_GROUP_OUT);
+        o.key_u8 = SJ_ARR(key_u8, key_u8 ? G : 0, A_GROUP_OUT);
+        o.key_ok = SJ_ARR(key_ok, G, A_GROUP_OUT);
+        o.status = SJ_ARR(status, n, A_GROUP_OUT);
+        o.first_row = SJ_ARR(a.first_row, G, A_GROUP_OUT);
+        o.codes = SJ_ARR(a.codes, n, A_GROUP_OUT);
+        hipLaunchKernelGGL(k_q_group_emit, per_row, b256, 0, st, q0, w.g, o, G, SJ_ARR(first_keys, n, A_SORT), c);
+    }
+    GroupValue gv[ResultState::GROUP_COLS];
+    for (uint32_t v = 0; v < n_val_cols; v++) gv[v] = {&k[n_key_cols + v].q, &k[n_key_cols + v].pth, val_kinds[v], a.agg[v]};
+    rc = group_reduce(ctx, n, n_in, G, w.sort, w.off, SJ_ARR(a.group_rows, G, A_GROUP_OUT), w.agg, gv, n_val_cols);
+    if (rc) return rc;
+    HIPCHK(hipGetLastError(), "group emit launch");
+    HIPCHK(hipStreamSynchronize(st), "group build sync");
+    rc = query_bounds_check(ctx);
+    if (rc) return rc;
+    *rows = n, *groups = G;
+    for (uint32_t c = 0; c < n_key_cols; c++) key_bytes[c] = z.col_bytes[c];
+    return published(ctx, ctx->res.publish(&ResultState::groups, z));
 }
 
 int sjhip_group_paths(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, const uint32_t *key_path_lens, const int *key_kinds,
@@ -4304,127 +4105,54 @@ int sjhip_group_paths(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_l
         for (uint32_t j = 0; j < pl; j++) byte_at += key_lens[key_at + j];
         key_at += pl;
     }
-    uint32_t n = 0;
-    int rc = whole_entry(ctx, "sjhip_group_paths", "the dictionaries of shards are not joined", k.data(), (int)n_paths, &n);
-    if (rc) return rc;
-    // ---- nothing was touched up to here; from here on the last grouping is gone ----
-    ctx->res.groups.begin();
-    ResultState::Groups z;
-    z.rows = n, z.key_cols = n_key_cols, z.val_cols = n_val_cols;
-    for (uint32_t c = 0; c < n_key_cols; c++) z.key_kinds[c] = key_kinds[c], key_bytes[c] = 0;
-    for (uint32_t v = 0; v < n_val_cols; v++) z.val_kinds[v] = val_kinds[v];
-    z.key_kind = key_kinds[0], z.val_kind = n_val_cols ? val_kinds[0] : SJHIP_GROUP_NO_VALUE;
-    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
-    if (n == 0) {
-        *rows = *groups = 0;
-        return published(ctx, ctx->res.publish(&ResultState::groups, z));
+    return group_build(ctx, "sjhip_group_paths", k.data(), key_kinds, key_flags, n_key_cols, val_kinds, n_val_cols, rows, groups, key_bytes);
+}
+// one key column of kind STRING or INT without a flag -- a row without an OK key is in no group -- and at most one value column
+int sjhip_group_path(sjhip_ctx *ctx, const uint8_t *key_keys, const uint32_t *key_key_lens, uint32_t key_n_keys, int key_kind,
+                     const uint8_t *val_keys, const uint32_t *val_key_lens, uint32_t val_n_keys, int val_kind, size_t *rows, size_t *groups,
+                     size_t *key_bytes) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!rows || !groups || !key_bytes) {
+        ctx_set_error(ctx, "sjhip_group_path: a null size pointer");
+        return SJHIP_ERR_ARG;
     }
-    MkGrpWork w;
-    rc = reserve_layout(ctx, ctx->d_kat, [&](Carve c) { return mkgrp_work_layout(c, n, key_kinds, key_flags, n_key_cols, n_val_cols != 0, &w); });
-    if (rc) return rc;
-    const QView &q0 = k[0].q;  // (the kernels behind the walks read the tape and the strings only: any column's view)
-    hipStream_t st = ctx->stream;
-    const dim3 per_row((n + 255) / 256), per_entry((n + 1u + 255) / 256), b256(256), one(1), wide(1024);
-    unsigned long long *const none = nullptr;
-    const u32 tiles = w.g.tiles;
-    u32 n_str = 0;
-    for (uint32_t c = 0; c < n_key_cols; c++) n_str += key_kinds[c] == SJHIP_COL_STRING;
-    HIPCHK(hipMemsetAsync(w.totals, 0, 256, st), "group totals memset");
-    HIPCHK(hipMemsetAsync(arr_raw(w.g.table), 0xff, ((size_t)w.g.mask + 1) * 4, st), "group table memset");
-    for (uint32_t c = 0; c < n_key_cols; c++) hipLaunchKernelGGL(k_q_mkgrp_keys, per_row, b256, 0, st, k[c].q, k[c].pth, w.g, c);
-    hipLaunchKernelGGL(k_q_mkgrp_insert, per_row, b256, 0, st, q0, w.g);
-    hipLaunchKernelGGL(k_q_mkgrp_first, per_entry, b256, 0, st, q0, w.g);
-    for (u32 which = 0; which <= n_str; which++) {  // the flags, then every STRING column's lengths: sums -> scan -> apply
-        hipLaunchKernelGGL(k_q_mkgrp_tile_sums, dim3(tiles), dim3(QT), 0, st, w.g, n + 1u, which);
-        if (which == 0) hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.g.tiles_f, none, w.g.tiles_o, tiles, w.totals);
-        else hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.g.tiles_l + (size_t)(which - 1) * tiles, none, none, tiles, w.totals + 2 + which);
-        hipLaunchKernelGGL(k_q_mkgrp_tile_apply, dim3(tiles), dim3(QT), 0, st, w.g, n + 1u, which);
+    if (key_kind != SJHIP_COL_STRING && key_kind != SJHIP_COL_INT) {
+        ctx_set_error(ctx, "sjhip_group_path: key kind %d is not SJHIP_COL_STRING or SJHIP_COL_INT", key_kind);
+        return SJHIP_ERR_ARG;
     }
-    HIPCHK(hipGetLastError(), "group launch");
-    unsigned long long *const h = (unsigned long long *)(ctx->h_scratch + 512);
-    HIPCHK(hipMemcpyAsync(h, w.totals, (3 + (size_t)ResultState::GROUP_COLS) * 8, hipMemcpyDeviceToHost, st), "D2H group totals");
-    HIPCHK(hipStreamSynchronize(st), "group sync");
-    rc = query_bounds_check(ctx);
-    if (rc) return rc;
-    const u32 G = (u32)h[0], n_in = (u32)h[2];
-    z.groups = G;
-    for (uint32_t c = 0, s = 0; c < n_key_cols; c++) {
-        const int kind = key_kinds[c];
-        z.col_bytes[c] = kind == SJHIP_COL_STRING ? (size_t)h[3 + s++] : (kind == SJHIP_COL_BOOL ? (size_t)G : (size_t)8 * G);
+    const bool value = val_kind != SJHIP_GROUP_NO_VALUE;
+    if (value && val_kind != SJHIP_COL_FLOAT && val_kind != SJHIP_COL_INT && val_kind != SJHIP_COL_UINT) {
+        ctx_set_error(ctx, "sjhip_group_path: value kind %d is not SJHIP_COL_FLOAT, SJHIP_COL_INT, SJHIP_COL_UINT or SJHIP_GROUP_NO_VALUE", val_kind);
+        return SJHIP_ERR_ARG;
     }
-    z.key_bytes = z.col_bytes[0];
-    MkGrpArrays a;
-    rc = reserve_layout(ctx, ctx->d_group, [&](Carve c) { return mkgrp_layout(c, z, &a); });
-    if (rc) return rc;
-    u32 *const first_keys = w.sort.keys[0];
-    for (uint32_t c = 0; c < n_key_cols; c++) {
-        MkGrpOut o;
-        u64 *const key_off = a.key_off[c], *const key_val = a.key_val[c];
-        u8 *const col_bytes = a.key_bytes[c], *const key_u8 = a.key_u8[c], *const key_ok = a.key_ok[c], *const status = a.status[c];
-        o.key_off = SJ_ARR(key_off, key_off ? (size_t)G + 1 : 0, A_MKGRP_OUT);
-        o.key_bytes = SJ_ARR(col_bytes, col_bytes ? z.col_bytes[c] : 0, A_MKGRP_KEYS);
-        o.key_val = SJ_ARR(key_val, key_val ? G : 0, A_MKGRP_OUT);
-        o.key_u8 = SJ_ARR(key_u8, key_u8 ? G : 0, A_MKGRP_OUT);
-        o.key_ok = SJ_ARR(key_ok, G, A_MKGRP_OUT);
-        o.status = SJ_ARR(status, n, A_MKGRP_OUT);
-        o.first_row = SJ_ARR(a.first_row, G, A_MKGRP_OUT);
-        o.codes = SJ_ARR(a.codes, n, A_MKGRP_OUT);
-        hipLaunchKernelGGL(k_q_mkgrp_emit, per_row, b256, 0, st, q0, w.g, o, G, SJ_ARR(first_keys, n, A_SORT), c);
-    }
-    GroupValue gv[ResultState::GROUP_COLS];
-    for (uint32_t v = 0; v < n_val_cols; v++) gv[v] = {&k[n_key_cols + v].q, &k[n_key_cols + v].pth, val_kinds[v], a.agg[v]};
-    rc = group_reduce(ctx, n, n_in, G, w.sort, w.off, SJ_ARR(a.group_rows, G, A_MKGRP_OUT), w.agg, gv, n_val_cols);
-    if (rc) return rc;
-    HIPCHK(hipGetLastError(), "group emit launch");
-    HIPCHK(hipStreamSynchronize(st), "group build sync");
-    rc = query_bounds_check(ctx);
-    if (rc) return rc;
-    *rows = n, *groups = G;
-    for (uint32_t c = 0; c < n_key_cols; c++) key_bytes[c] = z.col_bytes[c];
-    return published(ctx, ctx->res.publish(&ResultState::groups, z));
+    WholePath kv[2] = {{key_keys, key_key_lens, key_n_keys}, {val_keys, val_key_lens, val_n_keys}};
+    return group_build(ctx, "sjhip_group_path", kv, &key_kind, nullptr, 1, &val_kind, value ? 1u : 0u, rows, groups, key_bytes);
 }
 
 static int no_grouping(sjhip_ctx *ctx, const char *call) {
     ctx_set_error(ctx, "no grouping on the device (%s follows sjhip_group_path or sjhip_group_paths, with no parse in between)", call);
     return SJHIP_ERR_ARG;
 }
-// Column `col` of the grouping in force, whichever call built it (the single key's: column 0, every group has a key): where its
-// entries lie and how many bytes they are.
+static GroupArrays group_arrays(const sjhip_ctx *ctx, const ResultState::Groups &z) {  // the grouping in force
+    GroupArrays a;
+    (void)group_layout(Carve(ctx->d_group.p), z, &a);
+    return a;
+}
+// Column `col` of a grouping: where its entries lie (its bytes: z.col_bytes[col])
 struct GroupColumn {
-    int kind;
     const u64 *key_off;  // STRING
     const void *keys;
-    size_t key_bytes;
-    const u8 *key_ok;    // null: all 1
-    const u8 *status;
+    const u8 *key_ok, *status;
 };
-static GroupColumn group_column(const sjhip_ctx *ctx, const ResultState::Groups &z, uint32_t col) {
-    if (z.key_cols == 0) {
-        GroupArrays a;
-        (void)group_layout(Carve(ctx->d_group.p), z, &a);
-        const bool ints = z.key_kind == SJHIP_COL_INT;
-        return {z.key_kind, a.key_off, ints ? (const void *)a.key_int : (const void *)a.key_bytes, z.key_bytes, nullptr, a.status};
-    }
-    MkGrpArrays a;
-    (void)mkgrp_layout(Carve(ctx->d_group.p), z, &a);
+static GroupColumn group_column(const GroupArrays &a, const ResultState::Groups &z, uint32_t col) {
     const int kind = z.key_kinds[col];
     const void *const keys = kind == SJHIP_COL_STRING ? (const void *)a.key_bytes[col]
                                                       : (kind == SJHIP_COL_BOOL ? (const void *)a.key_u8[col] : (const void *)a.key_val[col]);
-    return {kind, a.key_off[col], keys, z.col_bytes[col], a.key_ok[col], a.status[col]};
-}
-static const u64 *group_aggregates(const sjhip_ctx *ctx, const ResultState::Groups &z, uint32_t val) {
-    if (z.key_cols == 0) {
-        GroupArrays a;
-        (void)group_layout(Carve(ctx->d_group.p), z, &a);
-        return a.agg;
-    }
-    MkGrpArrays a;
-    (void)mkgrp_layout(Carve(ctx->d_group.p), z, &a);
-    return a.agg[val];
+    return {a.key_off[col], keys, a.key_ok[col], a.status[col]};
 }
 static int fetch_aggregates(sjhip_ctx *ctx, const ResultState::Groups &z, uint32_t val, void *const (&dst)[6]) {
     if (z.groups == 0) return SJHIP_OK;
-    const u64 *const agg = group_aggregates(ctx, z, val);
+    const u64 *const agg = group_arrays(ctx, z).agg[val];
     FetchCopy copies[6];
     for (int j = 0; j < 6; j++) copies[j] = {dst[j], agg + (size_t)j * z.groups, z.groups * 8};
     return fetch_copies(ctx, copies, 6, "D2H group aggregates", "group aggregates fetch sync");
@@ -4439,50 +4167,37 @@ int sjhip_fetch_groups(sjhip_ctx *ctx, uint64_t *key_offsets, void *keys, uint64
                            "sjhip_fetch_group_keys)", z.key_cols);
         return SJHIP_ERR_ARG;
     }
-    const bool strings = z.key_kind == SJHIP_COL_STRING;
+    const bool strings = z.key_kinds[0] == SJHIP_COL_STRING;
     if (key_offsets && strings && z.groups == 0) key_offsets[0] = 0;
     if (z.rows == 0) return SJHIP_OK;  // (nothing was launched, no arena was written)
-    const GroupColumn k = group_column(ctx, z, 0);
-    const u64 *d_first_row, *d_group_rows;
-    const u32 *d_codes;
-    if (z.key_cols == 0) {
-        GroupArrays a;
-        (void)group_layout(Carve(ctx->d_group.p), z, &a);
-        d_first_row = a.first_row, d_group_rows = a.group_rows, d_codes = a.codes;
-    } else {
-        MkGrpArrays a;
-        (void)mkgrp_layout(Carve(ctx->d_group.p), z, &a);
-        d_first_row = a.first_row, d_group_rows = a.group_rows, d_codes = a.codes;
-    }
-    const FetchCopy copies[] = {{strings ? key_offsets : nullptr, k.key_off, (z.groups + 1) * 8}, {keys, k.keys, k.key_bytes},
-                                {first_row, d_first_row, z.groups * 8},  {group_rows, d_group_rows, z.groups * 8},
-                                {codes, d_codes, z.rows * 4},            {status, k.status, z.rows}};
+    const GroupArrays a = group_arrays(ctx, z);
+    const GroupColumn k = group_column(a, z, 0);
+    const FetchCopy copies[] = {{strings ? key_offsets : nullptr, k.key_off, (z.groups + 1) * 8}, {keys, k.keys, z.col_bytes[0]},
+                                {first_row, a.first_row, z.groups * 8},  {group_rows, a.group_rows, z.groups * 8},
+                                {codes, a.codes, z.rows * 4},            {status, k.status, z.rows}};
     return fetch_copies(ctx, copies, 6, "D2H groups", "group fetch sync");
 }
 int sjhip_fetch_group_keys(sjhip_ctx *ctx, uint32_t col, uint64_t *key_offsets, void *keys, uint8_t *key_ok, uint8_t *status) {
     if (!ctx) return SJHIP_ERR_ARG;
     if (!ctx->res.groups.exists()) return no_grouping(ctx, "sjhip_fetch_group_keys");
     const ResultState::Groups &z = ctx->res.groups.sizes();
-    const uint32_t cols = z.key_cols ? z.key_cols : 1u;
-    if (col >= cols) {
-        ctx_set_error(ctx, "sjhip_fetch_group_keys: key column %u of a grouping with %u", col, cols);
+    if (col >= z.key_cols) {
+        ctx_set_error(ctx, "sjhip_fetch_group_keys: key column %u of a grouping with %u", col, z.key_cols);
         return SJHIP_ERR_ARG;
     }
-    const int kind = z.key_cols ? z.key_kinds[col] : z.key_kind;
-    const bool strings = kind == SJHIP_COL_STRING;
+    const bool strings = z.key_kinds[col] == SJHIP_COL_STRING;
     if (key_offsets && strings && z.groups == 0) key_offsets[0] = 0;
     if (z.rows == 0) return SJHIP_OK;  // (nothing was launched, no arena was written)
-    const GroupColumn k = group_column(ctx, z, col);
-    if (key_ok && !k.key_ok) memset(key_ok, 1, z.groups);  // (the single key's call: a group is a key)
-    const FetchCopy copies[] = {{strings ? key_offsets : nullptr, k.key_off, (z.groups + 1) * 8}, {keys, k.keys, k.key_bytes},
-                                {k.key_ok ? key_ok : nullptr, k.key_ok, z.groups}, {status, k.status, z.rows}};
+    const GroupColumn k = group_column(group_arrays(ctx, z), z, col);
+    const FetchCopy copies[] = {{strings ? key_offsets : nullptr, k.key_off, (z.groups + 1) * 8}, {keys, k.keys, z.col_bytes[col]},
+                                {key_ok, k.key_ok, z.groups}, {status, k.status, z.rows}};
     return fetch_copies(ctx, copies, 4, "D2H group keys", "group keys fetch sync");
 }
 int sjhip_fetch_group_aggregates(sjhip_ctx *ctx, uint64_t *count, uint64_t *not_ok, void *sum, uint64_t *sum_hi, void *min, void *max) {
     if (!ctx) return SJHIP_ERR_ARG;
     if (!ctx->res.groups.exists()) return no_grouping(ctx, "sjhip_fetch_group_aggregates");
     const ResultState::Groups &z = ctx->res.groups.sizes();
-    if (z.key_cols ? z.val_cols == 0 : z.val_kind == SJHIP_GROUP_NO_VALUE) {
+    if (z.val_cols == 0) {
         ctx_set_error(ctx, "sjhip_fetch_group_aggregates: the grouping has no value column (sjhip_group_path was called with SJHIP_GROUP_NO_VALUE, "
                            "or sjhip_group_paths without value columns)");
         return SJHIP_ERR_ARG;
@@ -4498,9 +4213,8 @@ int sjhip_fetch_group_aggregates_at(sjhip_ctx *ctx, uint32_t val, uint64_t *coun
     if (!ctx) return SJHIP_ERR_ARG;
     if (!ctx->res.groups.exists()) return no_grouping(ctx, "sjhip_fetch_group_aggregates_at");
     const ResultState::Groups &z = ctx->res.groups.sizes();
-    const uint32_t vals = z.key_cols ? z.val_cols : (z.val_kind == SJHIP_GROUP_NO_VALUE ? 0u : 1u);
-    if (val >= vals) {
-        ctx_set_error(ctx, "sjhip_fetch_group_aggregates_at: value column %u of a grouping with %u", val, vals);
+    if (val >= z.val_cols) {
+        ctx_set_error(ctx, "sjhip_fetch_group_aggregates_at: value column %u of a grouping with %u", val, z.val_cols);
         return SJHIP_ERR_ARG;
     }
     return fetch_aggregates(ctx, z, val, {count, not_ok, sum, sum_hi, min, max});

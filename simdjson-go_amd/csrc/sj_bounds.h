@@ -44,10 +44,11 @@ enum ArrId : uint32_t {
     // the aggregates (query.hip, sjhip_aggregate_path): the head flag of every row / the items a level of the segmented reduction
     // hands to the next / the per-record results
     A_AGG_HEAD, A_AGG_ITEMS, A_AGG_OUT,
-    // the grouping (query.hip, sjhip_group_path): the per-row work arrays (status, key element, hash, slot, first-row flag, key
-    // length) / the table of row numbers / the group offsets / the per-group and per-row arrays of the product / the dictionary's
-    // key bytes
-    A_GROUP_ROW, A_GROUP_TABLE, A_GROUP_OFF, A_GROUP_OUT, A_GROUP_KEYS,
+    // the grouping (query.hip, sjhip_group_path and sjhip_group_paths): the per-row work arrays, column-major where they are per key
+    // column (status, key element or value; tuple hash, in-a-group byte, slot, first-row flag) / the key lengths of the STRING
+    // columns / the table of row numbers / the group offsets / the per-group and per-row arrays of the product / the bytes of a
+    // STRING column's entries
+    A_GROUP_ROW, A_GROUP_LEN, A_GROUP_TABLE, A_GROUP_OFF, A_GROUP_OUT, A_GROUP_KEYS,
     // the ordering (query.hip, sjhip_order_path): the per-row work arrays (sort key, status) / the arrays of the product (order,
     // values, status)
     A_ORDER_ROW, A_ORDER_OUT,
@@ -64,12 +65,7 @@ enum ArrId : uint32_t {
     // the order by several keys (query.hip, sjhip_order_paths): the per-row work arrays (the statuses on column 0 and on the column
     // at work, the key or key element) / the class keys of the active entries / the boundary bytes of the n + 1 positions.  The
     // active entries themselves are A_STRORD_ACT, the ranked rows and the sorts A_SORT, the product A_ORDER_OUT
-    A_MKORD_ROW, A_MKORD_ACT, A_MKORD_BND,
-    // the grouping by several keys (query.hip, sjhip_group_paths): the per-row work arrays, column-major where they are per column
-    // (status, key element or value; tuple hash, in-a-group byte, slot, first-row flag) / the key lengths of the STRING columns /
-    // the per-group and per-row arrays of the product / the bytes of a STRING column's entries.  The table is A_GROUP_TABLE, the
-    // group offsets A_GROUP_OFF, the sort A_SORT
-    A_MKGRP_ROW, A_MKGRP_LEN, A_MKGRP_OUT, A_MKGRP_KEYS
+    A_MKORD_ROW, A_MKORD_ACT, A_MKORD_BND
 };
 
 #if defined(SJ_DEBUG_BOUNDS)

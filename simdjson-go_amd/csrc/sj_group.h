@@ -1,5 +1,6 @@
-// sj_group.h -- the host-and-device pieces of the grouping (query.hip, sjhip_group_path): the hash of a key and the equality of two
-// keys.  Plain C++ under SJ_HD, so the CPU build of a test program can run what the kernels run.
+// sj_group.h -- the host-and-device pieces of the grouping (query.hip, sjhip_group_path and sjhip_group_paths): the hash of a key
+// column's entry, the fold of a tuple's hash from them, and the equality of two keys.  Plain C++ under SJ_HD, so the CPU build of a
+// test program can run what the kernels run.
 //
 // The hash only places a key in the open-addressing table; the result of the grouping does not depend on it (groups are numbered
 // by first occurrence, equality is decided by the bytes).  Strings are hashed 8 bytes at a time -- a multiply-xorshift round per
@@ -45,12 +46,12 @@ SJ_HD bool group_bytes_equal(const u8 *a, const u8 *b, u64 len) {
         if (a[k] != b[k]) return false;
     return true;
 }
-// Several key columns (sjhip_group_paths, the k_q_mkgrp_* kernels): the hash of a row's tuple is folded column by column from the
-// hashes above -- of the column's bytes or of its 8-byte value; GROUP_NO_KEY_HASH where the row has no key on the column.  The fold
-// depends on the order of the columns (the running hash is multiplied before the column's is added), and for a fixed prefix it is a
-// bijection of the last column's hash: an addition, then the invertible group_mix -- tests/group_multi_table.py solves an INT last
-// column for a chosen tuple hash that way.
-static constexpr u64 GROUP_TUPLE_SEED = 0x9e3779b97f4a7c15ull;
+// The hash of a row's tuple of key columns (k_q_group_keys) begins as column 0's hash above -- of the column's bytes or of its 8-byte
+// value; GROUP_NO_KEY_HASH where the row has no key on the column -- and every later column's is folded in.  So a tuple of one
+// column hashes as that column (the home slots tests/group_table.py constructs hold for sjhip_group_path and for sjhip_group_paths
+// alike).  The fold depends on the order of the columns (the running hash is multiplied before the column's is added), and for a
+// fixed non-empty prefix it is a bijection of the last column's hash: an addition, then the invertible group_mix --
+// tests/group_multi_table.py solves an INT last column for a chosen tuple hash that way.
 static constexpr u64 GROUP_NO_KEY_HASH = 0x6a09e667f3bcc909ull;
 SJ_HD u64 group_tuple_fold(u64 acc, u64 h) { return group_mix(acc * 0x9fb21c651e98df25ull + h); }
 

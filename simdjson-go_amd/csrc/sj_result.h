@@ -38,15 +38,12 @@ public:
     // the rows are root values; sjhip_select_rows and every sjhip_unnest_rows add n_keys + 1; a narrowing hands it on)
     struct Rows { size_t records = 0, rows = 0; uint32_t depth = 0; };
     struct Parents { size_t parents = 0, rows = 0; };  // the rows sjhip_unnest_rows ran over, the rows it left
-    // the grouping (sjhip_group_path): the rows it ran over, its groups, the bytes of its dictionary, and what its fetches need to
-    // know: the kind of the keys and of the value column (-1: SJHIP_GROUP_NO_VALUE, no aggregates were built)
-    // A grouping by several keys (sjhip_group_paths) has key_cols > 0: the kinds of its key and value columns and the bytes of
-    // every key column's entries; key_bytes, key_kind and val_kind are then column 0's and value 0's.  key_cols == 0: the single
-    // key's call built it, with that call's layout of d_group.
+    // the grouping (sjhip_group_path, sjhip_group_paths): the rows it ran over, its groups, and what its fetches need to know: the
+    // kinds of its key columns (at least one in a published grouping; sjhip_group_path: exactly one) and of its value columns
+    // (none: no aggregates were built), and the bytes of every key column's entries
     static constexpr int GROUP_COLS = 8;  // SJHIP_GROUP_MAX_KEYS, SJHIP_GROUP_MAX_VALUES
     struct Groups {
-        size_t rows = 0, groups = 0, key_bytes = 0;
-        int key_kind = 0, val_kind = -1;
+        size_t rows = 0, groups = 0;
         uint32_t key_cols = 0, val_cols = 0;
         int key_kinds[GROUP_COLS] = {}, val_kinds[GROUP_COLS] = {};
         size_t col_bytes[GROUP_COLS] = {};
@@ -141,7 +138,7 @@ public:
     Product<ListColumn> list;
     Product<Table> table;
     Product<Rows> rows;  // the row selection (sjhip_select_rows; sjhip_select_records is its begin())
-    Product<Groups> groups;  // the grouping (sjhip_group_path, d_group): materialised, independent of the selection it was built under
+    Product<Groups> groups;  // the grouping (sjhip_group_path, sjhip_group_paths; d_group): materialised, independent of the selection it was built under
     Product<Order> order;    // the order (sjhip_order_path, d_order): materialised, its row numbers are those of the selection the call left
     // the row parents (sjhip_unnest_rows, d_parents): materialised; parent numbers are those of the selection the call found, row
     // numbers those of the selection it left

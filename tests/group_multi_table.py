@@ -1,10 +1,11 @@
-"""The key table of the grouping by several keys (csrc/query.hip: k_q_mkgrp_keys, k_q_mkgrp_insert; the fold of the tuple hash:
+"""The key table of the grouping by several keys (csrc/query.hip: k_q_group_keys, k_q_group_insert; the fold of the tuple hash:
 csrc/sj_group.h group_tuple_fold) made controllable from outside, on top of tests/group_table.py: the fold in Python and its
 inverse in the last column's hash, constructors of tuples with a chosen 64-bit tuple hash or a chosen home slot -- the last column
 is INT and solved --, a serial model of the table over tuples, and the seam families built from them.  No GPU import.
 
   fold / unfold          group_tuple_fold, and the column hash that takes a running hash to a chosen next one
-  tuple_hash             the hash of a tuple of entries (bytes, int, or None for "no key"), as the device folds it column by column
+  tuple_hash             the hash of a tuple of entries (bytes, int, or None for "no key"), as the device folds it column by column:
+                         the first entry's hash begins it, so a tuple of one entry hashes as group_table.hash_key of that entry
   solve_last_int         the int64 last entry that gives a prefix of entries a chosen tuple hash
   model                  group_table.model over tuples (equality is the tuple's, entry by entry)
   families               name -> Family: colliding tuples with ONE 64-bit tuple hash, tuples homed at one slot of a 64-slot table whose
@@ -17,7 +18,7 @@ import functools
 import group_table as GT
 
 M64 = GT.M64
-SEED, NO_KEY_HASH, TMUL = GT.GOLD, 0x6A09E667F3BCC909, GT.RMUL
+NO_KEY_HASH, TMUL = 0x6A09E667F3BCC909, GT.RMUL
 
 
 def fold(acc, h):
@@ -34,20 +35,21 @@ def entry_hash(e):
 
 
 def tuple_hash(entries):
-    acc = SEED
+    """(an empty tuple has no hash: None)"""
+    acc = None
     for e in entries:
-        acc = fold(acc, entry_hash(e))
+        acc = entry_hash(e) if acc is None else fold(acc, entry_hash(e))
     return acc
 
 
 def solve_last_int(prefix, target):
-    x = GT.unhash_int(unfold(tuple_hash(prefix), target))
+    x = GT.unhash_int(unfold(tuple_hash(prefix), target) if prefix else target)  # (no prefix: the column's hash is the tuple's)
     assert tuple_hash(tuple(prefix) + (x,)) == target and -(1 << 63) <= x < 1 << 63
     return x
 
 
 def model(tuples, mask, order=None):
-    """k_q_mkgrp_insert with the rows inserted one after another in `order`; tuples[r] None: a row in no group.  -> group_table.Filled"""
+    """k_q_group_insert with the rows inserted one after another in `order`; tuples[r] None: a row in no group.  -> group_table.Filled"""
     n = len(tuples)
     hashes = [None if t is None else tuple_hash(t) for t in tuples]
     assert sum(t is not None for t in tuples) <= mask

@@ -1,6 +1,6 @@
 """The grouping on the bounds-checked build (libsjhip_dbg.so, csrc/sj_bounds.h): the per-row work arrays, the table of row numbers,
 the keys and rows of the sort, its histograms, the group offsets, the arrays of the product and the dictionary's bytes are reached
-through checked views (A_GROUP_ROW, A_GROUP_TABLE, A_SORT, A_SORT_HIST, A_GROUP_OFF, A_GROUP_OUT, A_GROUP_KEYS), and a
+through checked views (A_GROUP_ROW, A_GROUP_LEN, A_GROUP_TABLE, A_SORT, A_SORT_HIST, A_GROUP_OFF, A_GROUP_OUT, A_GROUP_KEYS), and a
 violation fails the call.  The rows of every key status, the 300 cycling keys and the long keys of tests/test_gpu_group.py, in their
 own interpreter with SJHIP_LIB pointing at that build (as tests/test_debug_bounds_aggregate.py runs the aggregates)."""
 import os

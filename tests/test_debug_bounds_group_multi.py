@@ -1,6 +1,6 @@
 """The grouping by several keys on the bounds-checked build (libsjhip_dbg.so, csrc/sj_bounds.h): the per-row and per-column work
 arrays, the key lengths, the table, the buffers of the sort, the group offsets and the arrays of the product are reached through
-checked views (A_MKGRP_ROW, A_MKGRP_LEN, A_GROUP_TABLE, A_SORT, A_SORT_HIST, A_GROUP_OFF, A_MKGRP_OUT, A_MKGRP_KEYS, A_AGG_*), and a
+checked views (A_GROUP_ROW, A_GROUP_LEN, A_GROUP_TABLE, A_SORT, A_SORT_HIST, A_GROUP_OFF, A_GROUP_OUT, A_GROUP_KEYS, A_AGG_*), and a
 violation fails the call.  The tuple-equality, status and collision cases of tests/test_gpu_group_multi.py, in their own
 interpreter with SJHIP_LIB pointing at that build (as tests/test_debug_bounds_order_multi.py runs the order by several keys)."""
 import os

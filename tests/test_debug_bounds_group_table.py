@@ -1,5 +1,5 @@
 """The key table of the grouping on the bounds-checked build (libsjhip_dbg.so, csrc/sj_bounds.h), where the table of row numbers, the
-per-row work arrays and the dictionary's bytes are reached through checked views (A_GROUP_TABLE, A_GROUP_ROW, A_GROUP_KEYS) and a
+per-row work arrays and the dictionary's bytes are reached through checked views (A_GROUP_TABLE, A_GROUP_ROW, A_GROUP_LEN, A_GROUP_KEYS) and a
 violation fails the call: the families of tests/group_table.py whose chains cross the last slot of a table of 64, 128 and 2048
 slots -- a probe step that loses its wrap leaves the table there and nowhere else --, one set of keys with a single 64-bit hash,
 and the keys on either side of the 32 bytes at which the dictionary copy changes hands.  In their own interpreter with SJHIP_LIB

@@ -14,6 +14,7 @@ import pytest
 import column_walk as CW
 import group_table as GT
 import group_walk as GW
+from test_gpu_aggregate import bits
 from test_gpu_group import array_rows, check_group
 from test_gpu_parse import ctx  # noqa: F401
 
@@ -74,6 +75,25 @@ def test_across_waves_and_blocks(ctx, name, copy):
     got = run_family(ctx, name, copy)
     assert FAMILIES[name].capacity == 2048 and got.rows == 600
     assert got.group_rows.tolist() == ([100] * 6 if "cycle" in name else [2] * 300)
+
+
+@pytest.mark.parametrize("name", GT.WRAP_FAMILIES + ["collide16"])
+def test_the_seams_behind_group_paths_on_one_column(ctx, name):
+    """the constructed home slots hold behind the several-keys entry point too (a tuple of one column hashes as that column,
+    tests/test_group_multi_table.py): group_paths on the single column "k" against the same verdict, tests/group_walk.group"""
+    f = FAMILIES[name]
+    kind = I if f.kind == "int" else S
+    rw = array_rows(ctx, GT.rows_json(f))
+    want = GW.group(rw, (b"k",), kind, (b"v",), I)
+    got = ctx.group_paths([((b"k",), kind)], [((b"v",), I)])
+    assert (got.rows, got.groups) == (want.rows, want.groups) == (f.rows, len(f.distinct())), name
+    assert (got.keys[0] if kind == S else got.keys[0].tolist()) == want.keys == f.distinct(), name
+    assert got.key_ok[0].tolist() == [1] * want.groups and got.status[0].tolist() == want.status, name
+    assert got.codes.dtype == np.uint32 and got.codes.tolist() == want.codes, name
+    assert got.first_row.tolist() == want.first_row and got.group_rows.tolist() == want.group_rows, name
+    for j, wanted in enumerate(GW.arrays(want, I)):
+        assert np.array_equal(bits(got.values[0][j]), np.array(wanted, dtype=np.uint64)), (name, j)
+    ctx.select_records()
 
 
 @pytest.mark.parametrize("copy", [True, False], ids=["copied", "in-the-message"])

@@ -36,14 +36,23 @@ def test_fold_is_the_compiled_one(lib):
                        for _ in range(n)]
             assert MT.tuple_hash(entries) == compiled(lib, entries), entries
     src = open(G.os.path.join(G.CSRC, "sj_group.h")).read()
-    assert "GROUP_TUPLE_SEED = 0x%xull" % MT.SEED in src and "GROUP_NO_KEY_HASH = 0x%xull" % MT.NO_KEY_HASH in src
+    assert "GROUP_TUPLE_SEED" not in src and "GROUP_NO_KEY_HASH = 0x%xull" % MT.NO_KEY_HASH in src
+
+
+def test_one_column_hashes_as_that_column(lib):
+    """the first column begins the fold, so behind group_paths on one column a key's home slot is the one tests/group_table.py
+    constructs for group_path: an int, strings around the 8-byte word and beyond the lane's copy, and "no key\""""
+    for e in (7, -(1 << 63), b"", b"1234567", b"12345678", b"123456789", b"x" * 33):
+        assert MT.tuple_hash((e,)) == GT.hash_key(e) == compiled(lib, [e]), e
+    assert MT.tuple_hash((None,)) == MT.NO_KEY_HASH == compiled(lib, [None])
 
 
 def test_fold_depends_on_order_boundaries_and_no_key(lib):
     assert MT.tuple_hash((b"x", b"y")) != MT.tuple_hash((b"y", b"x"))
     assert MT.tuple_hash((b"ab", b"c")) != MT.tuple_hash((b"a", b"bc"))
     assert MT.tuple_hash((b"", 1)) != MT.tuple_hash((None, 1)) and MT.tuple_hash((1, None)) != MT.tuple_hash((None, 1))
-    assert MT.tuple_hash((7,)) != GT.hash_int(7)  # (one column is folded too: the seed is in front of it)
+    assert MT.tuple_hash((7,)) == GT.hash_int(7)  # (one column is not folded: its hash is the tuple's)
+    assert MT.tuple_hash((7, 7)) != GT.hash_int(7) and MT.tuple_hash((b"", None)) != MT.tuple_hash((b"",))
 
 
 def test_the_last_int_column_is_solved_exactly(lib):
@@ -52,7 +61,7 @@ def test_the_last_int_column_is_solved_exactly(lib):
         acc = MT.tuple_hash(prefix)
         for _ in range(50):
             target = rnd.randrange(1 << 64)
-            assert MT.fold(acc, MT.unfold(acc, target)) == target
+            assert acc is None or MT.fold(acc, MT.unfold(acc, target)) == target  # (no prefix: nothing is folded)
             x = MT.solve_last_int(prefix, target)
             assert compiled(lib, list(prefix) + [x]) == target
 
