@@ -498,6 +498,38 @@ int sjhip_select_records(sjhip_ctx *ctx);
 #define SJHIP_WHERE_NOT 1u
 int sjhip_where_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int op, const void *value,
                      size_t vlen, uint32_t flags, size_t *records, size_t *rows);
+/* Row predicates of SEVERAL tests: up to 16 predicates evaluated in ONE walk of every row and combined with AND / OR / NOT -- a
+ * disjunction ("Make is HOND or TOYT", "lang in (en, ja, es)"), which no sequence of sjhip_where_path calls can express, and a
+ * conjunction or a range on one path without a walk, a compaction and a host wait per test.
+ *   predicates  keys / key_lens / path_lens are laid out as in sjhip_extract_table: predicate p owns the next path_lens[p] entries
+ *               of key_lens; path_lens[p] == 0: the row's own value.  The paths have the limits of a table (16 keys each, 32 keys
+ *               and 1024 key bytes together; empty paths do not count).  ops[p] is any SJHIP_OP_* above.  `values` holds the
+ *               values end to end and value_lens[p] is what sjhip_where_path takes for ops[p]: 8 for the numeric operators, 1 for
+ *               EQ_BOOL, 0 for EXISTS and IS_NULL, 0 to 1024 for EQ_STRING / PREFIX_STRING; at most 1024 bytes together.
+ *               Predicate p is TRUE for a row iff the element at its path exists and satisfies ops[p]: sjhip_where_path's
+ *               predicate with flags 0.  FindElement's rules hold per path: the first member with the key wins.
+ *   program     postfix, 1 to SJHIP_WHERE_MAX_PROGRAM bytes: a byte 0 .. n_preds - 1 pushes that predicate's truth,
+ *               SJHIP_WHERE_AND and SJHIP_WHERE_OR pop two values and push one, SJHIP_WHERE_NEG replaces the top.  It must never
+ *               underflow, end with exactly one value, name every predicate at least once and hold no other byte.  NEG over a
+ *               predicate keeps exactly what SJHIP_WHERE_NOT keeps: the rows where the path is missing or the conversion fails
+ *               included.  "a in (x, y)" is two predicates on one path and `0 1 OR`; a range is `0 1 AND`.
+ *   sjhip_where_paths        narrows the selection exactly as sjhip_where_path does, for the predicate "the program is true": the
+ *                            same composition with earlier and later calls, a selection is created when there is none, *records
+ *                            and *rows, keeping no rows is legal, every shard of a sharded result narrows its own rows, a call that
+ *                            fails with SJHIP_ERR_ARG leaves the selection as it was and a later failure gives it up.
+ *   sjhip_count_where_paths  *count = *rows of that call, and the selection is not touched.
+ * SJHIP_ERR_ARG, with sjhip_last_error naming the predicate or the program position: n_preds outside 1 .. 16, an unknown operator,
+ * a value of the wrong size, paths beyond the limits of a table, an invalid program.  The cost is one walk of every row, whatever
+ * n_preds is, and sjhip_where_path's passes behind it. */
+#define SJHIP_WHERE_MAX_PREDS 16      /* = SJHIP_TABLE_MAX_COLS: one plan */
+#define SJHIP_WHERE_MAX_PROGRAM 64
+enum { SJHIP_WHERE_AND = 0x80, SJHIP_WHERE_OR = 0x81, SJHIP_WHERE_NEG = 0x82 };  /* program bytes; 0 .. 15 push predicate p */
+int sjhip_where_paths(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, const uint32_t *path_lens,
+                      const int *ops, const void *values, const uint32_t *value_lens, uint32_t n_preds,
+                      const uint8_t *program, uint32_t program_len, size_t *records, size_t *rows);
+int sjhip_count_where_paths(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, const uint32_t *path_lens,
+                            const int *ops, const void *values, const uint32_t *value_lens, uint32_t n_preds,
+                            const uint8_t *program, uint32_t program_len, uint64_t *count);
 /* Order rows ("order by ... limit k"): rank the rows of the selection in force (without one: the root value of every record) by a
  * numeric key at a path and keep the first `limit` of them -- "the 10 most retweeted statuses" without the column, the host sort and
  * the rows that are thrown away crossing PCIe.

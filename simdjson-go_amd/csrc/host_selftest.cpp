@@ -983,3 +983,20 @@ extern "C" int sj_selftest_table_walk(const uint64_t *tape, size_t tape_len, con
     *records = r;
     return 0;
 }
+
+// sj_where.h: the program of a row predicate over several tests (sjhip_where_paths), as the host checks it and as the kernel
+// k_q_where_multi_mark evaluates it (tests/where_multi_walk.py restates both; tests/test_where_multi_abi.py holds them together).
+//   sj_selftest_where_program  a valid program: its value, 0 or 1, for the truth mask; a refused one: -(256 * WhereProgramError + the
+//                              position -- WHERE_PROG_UNUSED: the predicate -- it was found at)
+//   sj_selftest_where_limits   out5 = the predicate limit, the program limit, and the bytes of AND, OR, NEG
+#include "sj_where.h"
+extern "C" int sj_selftest_where_program(const uint8_t *program, uint32_t len, uint32_t n_preds, uint32_t truth_mask) {
+    uint32_t pos = 0;
+    const int why = sj::where_program_check(program, len, n_preds, &pos);
+    if (why) return -(256 * why + (int)pos);
+    return sj::where_program_eval(program, len, truth_mask) ? 1 : 0;
+}
+extern "C" void sj_selftest_where_limits(int *out5) {
+    out5[0] = sj::WHERE_MAX_PREDS, out5[1] = sj::WHERE_MAX_PROGRAM;
+    out5[2] = sj::WHERE_AND, out5[3] = sj::WHERE_OR, out5[4] = sj::WHERE_NEG;
+}

@@ -31,6 +31,7 @@
 #include "sj_stage2.h"
 #include "sj_tapewalk.h"
 #include "sj_tablewalk.h"
+#include "sj_where.h"
 
 using namespace sj;
 
@@ -177,15 +178,15 @@ __device__ __forceinline__ int element_to(const QView &q, u64 v, int kind, u64 *
 // equalities below, whose code they leave as it was: the element converted as the EQ_* operator of its kind converts it -- an
 // element whose conversion is not OK satisfies nothing --, then Go's comparison of two int64 / uint64 / float64 (a NaN `want`
 // compares false with everything); PREFIX_STRING: bytes.HasPrefix(Iter.StringBytes, value)
-__device__ __forceinline__ bool element_orders(const QView &q, u64 v, int op, u64 want) {
+__device__ __forceinline__ bool element_orders(const QView &q, u64 v, int op, u64 want, const u8 *val, u32 vlen) {
     if (op == SJHIP_OP_PREFIX_STRING) {
         const u64 w = q.tape[v];
         if ((u32)(w >> 56) != '"') return false;
         const u64 len = q.tape[v + 1];
-        if (len < q.vlen) return false;
-        const u8 *s = str_bytes(q, w, q.vlen);
-        for (u32 k = 0; k < q.vlen; k++)
-            if (s[k] != q.val[k]) return false;
+        if (len < vlen) return false;
+        const u8 *s = str_bytes(q, w, vlen);
+        for (u32 k = 0; k < vlen; k++)
+            if (s[k] != val[k]) return false;
         return true;
     }
     if (op < SJHIP_OP_LT_INT || op > SJHIP_OP_GE_FLOAT) return false;
@@ -203,14 +204,15 @@ __device__ __forceinline__ bool element_orders(const QView &q, u64 v, int op, u6
     }
     return rel == 0 ? lt : (rel == 1 ? !gt : (rel == 2 ? gt : !lt));
 }
-// the typed comparisons: the element converted as above (StringBytes for EQ_STRING), compared with the wanted value
-__device__ bool element_is(const QView &q, u64 v, int op, u64 want) {
+// the typed comparisons: the element converted as above (StringBytes for EQ_STRING), compared with the wanted value -- a number or
+// a bool in `want`, a string in val[0 .. vlen)
+__device__ bool element_is(const QView &q, u64 v, int op, u64 want, const u8 *val, u32 vlen) {
     const u64 w = q.tape[v];
     const u32 t = (u32)(w >> 56);
     u64 got;
     switch (op) {
     case SJHIP_OP_EXISTS: return true;
-    case SJHIP_OP_EQ_STRING: return t == '"' && str_equals(q, w, q.tape[v + 1], q.val, q.vlen);
+    case SJHIP_OP_EQ_STRING: return t == '"' && str_equals(q, w, q.tape[v + 1], val, vlen);
     case SJHIP_OP_EQ_BOOL: return element_to(q, v, SJHIP_COL_BOOL, &got) == SJHIP_COL_OK && got == (want != 0);
     case SJHIP_OP_IS_NULL: return t == 'n';
     case SJHIP_OP_EQ_INT: return element_to(q, v, SJHIP_COL_INT, &got) == SJHIP_COL_OK && got == want;
@@ -218,9 +220,11 @@ __device__ bool element_is(const QView &q, u64 v, int op, u64 want) {
     case SJHIP_OP_EQ_FLOAT:  // (a comparison of doubles: -0.0 equals 0.0)
         return element_to(q, v, SJHIP_COL_FLOAT, &got) == SJHIP_COL_OK &&
                __longlong_as_double((long long)got) == __longlong_as_double((long long)want);
-    default: return element_orders(q, v, op, want);
+    default: return element_orders(q, v, op, want, val, vlen);
     }
 }
+// (one predicate per call: its string value is the whole of QView::val)
+__device__ __forceinline__ bool element_is(const QView &q, u64 v, int op, u64 want) { return element_is(q, v, op, want, q.val, q.vlen); }
 // the record's element at the path exists and satisfies the predicate
 __device__ __forceinline__ bool record_is(const QView &q, const QPath &pth, u32 r, int op, u64 want) {
     const u64 v = record_find_path(q, pth, r);
@@ -1347,6 +1351,47 @@ __global__ __launch_bounds__(256) void k_q_where_mark(QView q, QPath pth, int op
     if (i < q_rows(q)) {
         keep = (pth.n ? record_is(q, pth, i, op, want) : element_is(q, row_value(q, i), op, want)) != (negate != 0);
         w.flag[i] = keep ? 1 : 0;
+    }
+    const u64 b = __ballot(keep);  // (the 64 rows of a wave lie in one tile)
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&w.tiles[i / QTILE], (unsigned long long)__popcll(b));
+}
+// ... by SEVERAL tests (sjhip_where_paths): the mark of a plan of predicates (sj_where.h).  One lane per row runs table_walk over
+// the predicates' paths -- every member of the row is met once, however many tests look at it --, the sink evaluates the predicate
+// of the column on the element it is handed (element_is on the predicate's own value span; SJHIP_PATH_NOT_*: false) into one bit
+// of a truth mask, the predicates with an empty path test the row's value, and the program folds the mask into the flag.  The flag
+// and the tile count leave as in k_q_where_mark; with `count` set (sjhip_count_where_paths) the ballot is added to that one
+// counter instead and nothing else is written.  The resume stack is the table kernel's: LDS, one column per lane.
+struct WhereSink {
+    const QView &q;
+    const WherePlan &p;
+    u32 truth;
+    __device__ __forceinline__ void test(u32 k, u64 v) {  // predicate k on the element at v
+        if (element_is(q, v, p.op[k], p.want[k], q.val + p.val_b[k], p.val_n[k])) truth |= 1u << k;
+    }
+    __device__ __forceinline__ void operator()(u32 c, u64 v) {
+        if (v < SJHIP_PATH_NOT_OBJECT) test(p.pred_of_col[c], v);
+    }
+};
+static_assert(sizeof(QView) + sizeof(WherePlan) + sizeof(QWhere) + 8 <= 4096,
+              "k_q_where_multi_mark: the view and the plan travel as kernel arguments (4 KiB)");
+__global__ __launch_bounds__(256) void k_q_where_multi_mark(QView q, WherePlan p, QWhere w, unsigned long long *count) {
+    __shared__ u32 s_stack[TABLE_STACK_WORDS * 256];
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    bool keep = false;
+    if (i < q_rows(q)) {
+        const u64 v0 = row_value(q, i);
+        const TableView view = {q};
+        WhereSink sink = {q, p, 0u};
+        if (p.pl.n_cols) table_walk(view, p.pl, v0, s_stack + threadIdx.x, 256u, sink);
+        if (p.empty)
+            for (u32 k = 0; k < p.n_preds; k++)
+                if ((p.empty >> k) & 1u) sink.test(k, v0);
+        keep = where_program_eval(p.program, p.program_len, sink.truth);
+        if (!count) w.flag[i] = keep ? 1 : 0;
+    }
+    if (count) {
+        count_ballot(keep, count);
+        return;
     }
     const u64 b = __ballot(keep);  // (the 64 rows of a wave lie in one tile)
     if ((threadIdx.x & 63) == 0 && b) atomicAdd(&w.tiles[i / QTILE], (unsigned long long)__popcll(b));
@@ -3497,9 +3542,11 @@ static int where_narrow(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, c
     *records = total.records, *rows = total.rows;
     return published(ctx, ok);
 }
-// sjhip_where_path's first half: the predicate marks, the kept rows are counted; then the narrowing above.
+// The first half of sjhip_where_path and sjhip_where_paths: mark(part, q, n, work) launches the kernel that flags the n rows of
+// the part and counts the kept ones per tile; they are added up; then the narrowing above.
+template <typename M>
 static int where_build(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, const uint8_t *keys, size_t klen, const uint8_t *val,
-                       size_t vlen, const QPath &pth, int op, u64 want, u32 negate, size_t *records, size_t *rows) {
+                       size_t vlen, M mark, size_t *records, size_t *rows) {
     std::vector<QWhere> work(parts.size());
     std::vector<WhereNew> fresh(parts.size());
     std::vector<size_t> kept(parts.size(), 0);
@@ -3516,7 +3563,7 @@ static int where_build(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, co
             const u32 tiles = (n + QTILE - 1) / QTILE;
             HIPCHK(hipMemsetAsync(totals, 0, 256, part->stream), "row predicate totals memset");
             HIPCHK(hipMemsetAsync(work[k].tiles, 0, (size_t)tiles * 8, part->stream), "row predicate tiles memset");
-            hipLaunchKernelGGL(k_q_where_mark, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, pth, op, want, negate, work[k]);
+            mark(part, q, n, work[k]);
             hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, part->stream, work[k].tiles, none, none, tiles, totals);
             HIPCHK(hipGetLastError(), "row predicate launch");
             HIPCHK(hipMemcpyAsync(part->h_scratch + 512, totals, 8, hipMemcpyDeviceToHost, part->stream), "D2H kept rows");
@@ -3526,6 +3573,16 @@ static int where_build(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, co
             kept[k] = part_rows(ctx, part, true) ? (size_t)*(const unsigned long long *)(part->h_scratch + 512) : 0;
         });
     return rc ? rc : where_narrow(ctx, parts, keys, klen, val, vlen, work, fresh, kept, records, rows);
+}
+
+// a narrowing that failed half-built: the old selection may have been written over, so it is given up
+static int where_gave_up(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, const char *who, int rc) {
+    ctx->res.rows.begin();
+    for (sjhip_ctx *part : parts) part->res.rows.begin();
+    char why[sizeof ctx->err];
+    snprintf(why, sizeof why, "%s", ctx->err);
+    ctx_set_error(ctx, "%s failed and the row selection was given up: %.180s", who, why);
+    return rc;
 }
 
 int sjhip_where_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int op, const void *value,
@@ -3551,15 +3608,150 @@ int sjhip_where_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_le
     std::vector<sjhip_ctx *> parts;
     rc = query_parts(ctx, kb, klen, vb, vl, &parts);
     if (rc) return rc;  // (nothing has been queued: the selection is as it was)
-    rc = where_build(ctx, parts, kb, klen, vb, vl, pth, op, want, flags & SJHIP_WHERE_NOT, records, rows);
-    if (rc) {  // half-built: the old selection may have been written over
-        ctx->res.rows.begin();
-        for (sjhip_ctx *part : parts) part->res.rows.begin();
-        char why[sizeof ctx->err];
-        snprintf(why, sizeof why, "%s", ctx->err);
-        ctx_set_error(ctx, "sjhip_where_path failed and the row selection was given up: %.180s", why);
+    const u32 negate = flags & SJHIP_WHERE_NOT;
+    rc = where_build(ctx, parts, kb, klen, vb, vl,
+                     [&](sjhip_ctx *part, const QView &q, uint32_t n, const QWhere &w) {
+                         hipLaunchKernelGGL(k_q_where_mark, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, pth, op, want, negate, w);
+                     },
+                     records, rows);
+    return rc ? where_gave_up(ctx, parts, "sjhip_where_path", rc) : rc;
+}
+
+// ---- row predicates of several tests (sjhip_where_paths, sjhip_count_where_paths) -------------------------------------------------
+// The arguments of both calls, checked in the order the header names them, become the plan (sj_where.h), the keys of its trie
+// and the values end to end -- what travels in QView::key and QView::val.  Nothing of the context is touched here.
+struct WhereMulti {
+    WherePlan plan;
+    uint8_t keys[TABLE_MAX_BYTES];
+    uint32_t klen;
+    const uint8_t *vals;
+    size_t vlen;
+};
+static int where_multi_plan(sjhip_ctx *ctx, const char *who, const uint8_t *keys, const uint32_t *key_lens, const uint32_t *path_lens,
+                            const int *ops, const void *values, const uint32_t *value_lens, uint32_t n_preds, const uint8_t *program,
+                            uint32_t program_len, WhereMulti *m) {
+    if (n_preds < 1 || n_preds > (uint32_t)SJHIP_WHERE_MAX_PREDS) {
+        ctx_set_error(ctx, "%s: %u predicates (1 to %d)", who, n_preds, SJHIP_WHERE_MAX_PREDS);
+        return SJHIP_ERR_ARG;
     }
-    return rc;
+    if (!path_lens || !ops || !value_lens || !program) {
+        ctx_set_error(ctx, "%s: a null argument (path_lens, ops, value_lens, program)", who);
+        return SJHIP_ERR_ARG;
+    }
+    WherePlan &pl = m->plan;
+    memset(&pl, 0, sizeof pl);
+    // the values: what sjhip_where_path takes for the operator, end to end
+    size_t val_at = 0;
+    for (uint32_t p = 0; p < n_preds; p++) {
+        const uint32_t vl = value_lens[p];
+        if (val_at + vl > (size_t)WHERE_MAX_VALUE_BYTES) {
+            ctx_set_error(ctx, "%s: predicate %u: the values are longer than %d bytes together", who, p, WHERE_MAX_VALUE_BYTES);
+            return SJHIP_ERR_ARG;
+        }
+        const int op = ops[p];
+        if (op < SJHIP_OP_EXISTS || op > SJHIP_OP_PREFIX_STRING) {
+            ctx_set_error(ctx, "%s: predicate %u: unknown operator %d", who, p, op);
+            return SJHIP_ERR_ARG;
+        }
+        if (vl && !values) {
+            ctx_set_error(ctx, "%s: predicate %u: a value of %u bytes is announced and `values` is null", who, p, vl);
+            return SJHIP_ERR_ARG;
+        }
+        bool is_str = false;
+        u64 want = 0;
+        const void *const v = vl ? (const void *)((const uint8_t *)values + val_at) : (const void *)&NO_VALUE;
+        if (predicate_value(op, v, vl, &want, &is_str) || ((op == SJHIP_OP_EXISTS || op == SJHIP_OP_IS_NULL) && vl)) {
+            ctx_set_error(ctx, "%s: predicate %u: operator %d with a value of %u bytes", who, p, op, vl);
+            return SJHIP_ERR_ARG;
+        }
+        pl.op[p] = (uint8_t)op;
+        pl.want[p] = want;
+        pl.val_b[p] = (uint16_t)val_at;
+        pl.val_n[p] = (uint16_t)(is_str ? vl : 0u);
+        val_at += vl;
+    }
+    m->vals = val_at ? (const uint8_t *)values : &NO_VALUE;
+    m->vlen = val_at;
+    // the paths: the predicates that have one are the columns of a table plan, in their order
+    uint32_t col_path_lens[TABLE_MAX_COLS], n_cols = 0;
+    int kinds[TABLE_MAX_COLS];
+    size_t n_keys = 0;
+    for (uint32_t p = 0; p < n_preds; p++) {
+        if (path_lens[p] == 0) {
+            pl.empty |= (uint16_t)(1u << p);
+            continue;
+        }
+        pl.pred_of_col[n_cols] = (uint8_t)p;
+        col_path_lens[n_cols] = path_lens[p];
+        kinds[n_cols++] = SJHIP_COL_FLOAT;  // (the walk does not look at the kind of a column)
+        n_keys += path_lens[p];
+    }
+    m->klen = 0;
+    if (n_cols) {
+        if (!keys || !key_lens) {
+            ctx_set_error(ctx, "%s: a null argument (%zu keys are announced)", who, n_keys);
+            return SJHIP_ERR_ARG;
+        }
+        // (the keys of the paths lie end to end whether or not empty paths stand between them: table_plan reads them as they are)
+        uint32_t bad_col = 0;
+        const int why = table_plan(keys, key_lens, col_path_lens, kinds, n_cols, &pl.pl, m->keys, &m->klen, &bad_col);
+        if (why) {
+            ctx_set_error(ctx, "%s: predicate %u: %s", who, (unsigned)pl.pred_of_col[bad_col], table_plan_error(why));
+            return SJHIP_ERR_ARG;
+        }
+    }
+    uint32_t pos = 0;
+    const int why = where_program_check(program, program_len, n_preds, &pos);
+    if (why) {
+        if (why == WHERE_PROG_UNUSED) ctx_set_error(ctx, "%s: predicate %u: %s", who, pos, where_program_error(why));
+        else ctx_set_error(ctx, "%s: program position %u (of %u bytes): %s", who, pos, program_len, where_program_error(why));
+        return SJHIP_ERR_ARG;
+    }
+    pl.n_preds = (uint8_t)n_preds;
+    pl.program_len = (uint8_t)program_len;
+    memcpy(pl.program, program, program_len);
+    return SJHIP_OK;
+}
+static void where_multi_launch(sjhip_ctx *part, const QView &q, uint32_t n, const WherePlan &plan, const QWhere &w, unsigned long long *count) {
+    hipLaunchKernelGGL(k_q_where_multi_mark, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, plan, w, count);
+}
+
+int sjhip_where_paths(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, const uint32_t *path_lens, const int *ops,
+                      const void *values, const uint32_t *value_lens, uint32_t n_preds, const uint8_t *program, uint32_t program_len,
+                      size_t *records, size_t *rows) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!records || !rows) {
+        ctx_set_error(ctx, "sjhip_where_paths: a null size pointer");
+        return SJHIP_ERR_ARG;
+    }
+    WhereMulti m;
+    int rc = where_multi_plan(ctx, "sjhip_where_paths", keys, key_lens, path_lens, ops, values, value_lens, n_preds, program, program_len, &m);
+    if (rc) return rc;
+    std::vector<sjhip_ctx *> parts;
+    rc = query_parts(ctx, m.keys, m.klen, m.vals, m.vlen, &parts);
+    if (rc) return rc;  // (nothing has been queued: the selection is as it was)
+    rc = where_build(ctx, parts, m.keys, m.klen, m.vals, m.vlen,
+                     [&](sjhip_ctx *part, const QView &q, uint32_t n, const QWhere &w) { where_multi_launch(part, q, n, m.plan, w, nullptr); },
+                     records, rows);
+    return rc ? where_gave_up(ctx, parts, "sjhip_where_paths", rc) : rc;
+}
+
+int sjhip_count_where_paths(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, const uint32_t *path_lens, const int *ops,
+                            const void *values, const uint32_t *value_lens, uint32_t n_preds, const uint8_t *program,
+                            uint32_t program_len, uint64_t *count) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!count) {
+        ctx_set_error(ctx, "sjhip_count_where_paths: a null count pointer");
+        return SJHIP_ERR_ARG;
+    }
+    WhereMulti m;
+    const int rc = where_multi_plan(ctx, "sjhip_count_where_paths", keys, key_lens, path_lens, ops, values, value_lens, n_preds, program,
+                                    program_len, &m);
+    if (rc) return rc;
+    return count_over_parts(ctx, m.keys, m.klen, m.vals, m.vlen, true, count,
+                            [&](sjhip_ctx *part, const QView &q, uint32_t n, unsigned long long *d) {
+                                where_multi_launch(part, q, n, m.plan, QWhere(), d);
+                            });
 }
 
 // ---- unnest rows -------------------------------------------------------------------------------------------------------------------

@@ -590,6 +590,39 @@ class Context:
                                                 self.WHERE_NOT if negate else 0, C.byref(nr), C.byref(nw)))
         return nr.value, nw.value
 
+    WHERE_AND, WHERE_OR, WHERE_NEG = 0x80, 0x81, 0x82  # SJHIP_WHERE_AND / _OR / _NEG: the operators of a program
+    WHERE_MAX_PREDS = 16     # SJHIP_WHERE_MAX_PREDS
+    WHERE_MAX_PROGRAM = 64   # SJHIP_WHERE_MAX_PROGRAM
+
+    def _where_paths_args(self, predicates, program):
+        preds = [(tuple(path), int(op), self._op_value(int(op), value)) for path, op, value in predicates]
+        keys = [bytes(k) for path, _, _ in preds for k in path]
+        n = len(preds)
+        key_lens = (C.c_uint32 * max(len(keys), 1))(*[len(k) for k in keys])
+        path_lens = (C.c_uint32 * max(n, 1))(*[len(path) for path, _, _ in preds])
+        ops = (C.c_int * max(n, 1))(*[op for _, op, _ in preds])
+        values = b"".join(v for _, _, v in preds)
+        value_lens = (C.c_uint32 * max(n, 1))(*[len(v) for _, _, v in preds])
+        program = bytes(program)
+        return (self._h, b"".join(keys) if keys else None, key_lens if keys else None, path_lens, ops,
+                C.create_string_buffer(values, max(len(values), 1)), value_lens, n, program, len(program))
+
+    def where_paths(self, predicates, program):
+        """where_path for SEVERAL tests from one walk of every row: predicates = [(path, op, value), ...], 1 to WHERE_MAX_PREDS of
+        them, each where_path's predicate (an empty path: the row's own value); program = bytes, postfix: a byte p < len(predicates)
+        pushes the truth of predicate p, WHERE_AND / WHERE_OR pop two values and push one, WHERE_NEG replaces the top -- e.g.
+        bytes([0, 1, WHERE_OR]) for "a in (x, y)".  Every predicate must be named, one value must be left.  Keeps the rows for
+        which the program is true; narrowing and composition are where_path's.  -> (records, rows kept)"""
+        nr, nw = C.c_size_t(0), C.c_size_t(0)
+        self._check(_lib.lib().sjhip_where_paths(*self._where_paths_args(predicates, program), C.byref(nr), C.byref(nw)))
+        return nr.value, nw.value
+
+    def count_where_paths(self, predicates, program):
+        """the rows where_paths(predicates, program) would keep; the selection stays as it is"""
+        cnt = C.c_uint64(0)
+        self._check(_lib.lib().sjhip_count_where_paths(*self._where_paths_args(predicates, program), C.byref(cnt)))
+        return cnt.value
+
     # ---- unnest (include/sjhip.h: sjhip_unnest_rows / sjhip_fetch_row_parents) ---------------------------------------------------
     def unnest_rows(self, path=()):
         """Iter.FindElement(path...), Iter.Array, Array.Iter on every ROW of the selection in force (without one: on every record's
