@@ -823,11 +823,21 @@ int sjhip_stage1_device(sjhip_ctx *ctx, const void *d_msg, size_t len, int ndjso
                         size_t pos_cap, size_t *n, int *ok);
 /* Queued form of sjhip_stage1_device for a caller that keeps several messages (or blocks of a stream) in flight, as
  * ParseNDStream's reader does with its 10 MB blocks (simdjson_amd64.go:127-215: the next block is read and indexed while the
- * previous one is parsed): _queue launches behind what is already on the context's stream and returns at once; the launch
+ * previous one is parsed): _queue goes behind what is already on the context's stream and returns at once; the message
  * leaves count, end state and error bits in record `slot` (0 .. SJHIP_STAGE1_QUEUE_SLOTS-1) of the context's pinned host
- * memory.  _wait synchronises with the stream; _result turns a record into (*n, *ok) exactly like sjhip_stage1_device and must
- * only be called for a slot whose launch _wait has covered (else SJHIP_ERR_HIP "left no result").  A slot is free again once
- * its result has been taken.  d_msg / d_pos of a queued launch must stay untouched until then. */
+ * memory.  Queued messages of one mode (ndjson or not) are grouped: several of them run as ONE launch of the kernel, so a
+ * queued message starts when its group is full, when another call puts work on the context, and no later than the next
+ * _wait -- not necessarily inside _queue.  _wait launches what is still queued and synchronises with the stream (a caller
+ * that synchronises the stream itself must call _wait first); _result turns a record into (*n, *ok) exactly like
+ * sjhip_stage1_device and must only be called for a slot whose message a _wait has covered (else SJHIP_ERR_HIP "left no
+ * result").  A slot is free again once its result has been taken.  d_msg / d_pos of a queued message must stay untouched
+ * until then; every message has its own verdict, count and positions, whatever it shares a launch with.
+ * Because the launch is deferred, stream order no longer places a queued message in front of work the caller itself puts
+ * on the context's stream (sjhip_ctx_set_stream) between _queue and _wait: a kernel of the caller's that reads d_pos, or
+ * one that overwrites d_msg, must go behind _wait, not merely behind _queue.
+ * If a group cannot be launched (a HIP error), all its messages are dropped: the call that tried to launch it -- _wait, or
+ * a _queue whose message completed or displaced the group, in which case that message is not queued either -- returns the
+ * error, and _result of every dropped message says "left no result".  The caller queues them again. */
 #define SJHIP_STAGE1_QUEUE_SLOTS 64
 int sjhip_stage1_device_queue(sjhip_ctx *ctx, const void *d_msg, size_t len, int ndjson, void *d_pos,
                               size_t pos_cap, int slot);

@@ -111,6 +111,7 @@ size_t sjhip_ctx_device_bytes(const sjhip_ctx *ctx) {
 
 int sjhip_ctx_trim(sjhip_ctx *ctx) {
     if (!ctx) return SJHIP_ERR_ARG;
+    (void)sj::stage1_queue_flush(ctx);
     if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
         return ctx_hip_fail(ctx, hipGetLastError(), "sjhip_ctx_trim");
     ctx->res.drop_result();
@@ -138,6 +139,7 @@ int sjhip_ctx_trim(sjhip_ctx *ctx) {
 
 void sjhip_ctx_destroy(sjhip_ctx *ctx) {
     if (!ctx) return;
+    (void)sj::stage1_queue_flush(ctx);
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     DevBuf *bufs[] = SJ_CTX_ARENAS(ctx);
@@ -180,6 +182,7 @@ const char *sjhip_last_error(const sjhip_ctx *ctx) { return ctx ? ctx->err : "no
 
 int sjhip_ctx_set_stream(sjhip_ctx *ctx, void *hip_stream) {
     if (!ctx) return SJHIP_ERR_ARG;
+    (void)sj::stage1_queue_flush(ctx);  // (queued messages go to the stream they were queued on)
     ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
     return SJHIP_OK;
 }
@@ -204,10 +207,15 @@ static int stage1_verdict(const Stage1State &st, size_t len, uint8_t last_byte) 
 // copy, the positions with the token kinds behind them: queries, the serializer and MarshalJSON must not run on what
 // is left (they return SJHIP_ERR_ARG until the next parse).  sjhip_fetch goes back to the device copies of the tape and
 // Strings.B, which a stage-1 call does not touch; a sharded result lies in the shards' arenas and only loses its products.
-static void stage1_only(sjhip_ctx *ctx) {
+static void stage1_only_result(sjhip_ctx *ctx) {
     if (!ctx->res.sharded()) return ctx->res.drop_result();
     ctx->res.claim_shared();
     ctx->res.drop_products();
+}
+// ... and every stage-1 entry point but the queue itself goes behind the messages that are queued
+static void stage1_only(sjhip_ctx *ctx) {
+    stage1_only_result(ctx);
+    (void)stage1_queue_flush(ctx);
 }
 
 // stage 1 in two halves: enqueue (workspace, launch; the last block of the kernel leaves the packed result -- count,
@@ -218,7 +226,7 @@ static void stage1_only(sjhip_ctx *ctx) {
 // Stage 1 runs without a preparation kernel: every launch zeroes, for the next one, the control slot and the descriptor set
 // the one before it used (sj_device.h Stage1State).  A workspace that has just been allocated is zeroed here, once.
 static int stage1_workspace_clean(sjhip_ctx *ctx) {
-    if (ctx->d_ws.p && ctx->ws_clean_gen != ctx->d_ws.gen) {
+    if (ctx->d_ws.p && (ctx->ws_clean_gen != ctx->d_ws.gen || ctx->s1ws.dirty)) {  // (dirty: a launch on it failed)
         ctx->s1ws.p = ctx->d_ws.p;
         ctx->s1ws.bytes = ctx->d_ws.cap;
         HIPCHK(stage1_prepare(ctx->s1ws, ctx->stream), "stage-1 workspace memset");
@@ -304,24 +312,66 @@ int sjhip_stage1_device(sjhip_ctx *ctx, const void *d_msg, size_t len, int ndjso
     return stage1_run_device(ctx, d_msg, len, ndjson != 0, d_pos, pos_cap, 0, 0, n, ok);
 }
 
-// Queued form: launches behind one another on the context's stream, no synchronisation of their own; every launch has its
-// own record in pinned host memory (the upper half of h_scratch: SJHIP_STAGE1_QUEUE_SLOTS records of 32 bytes).
+// Queued form: no synchronisation of their own; every message has its own record in pinned host memory (the upper half of
+// h_scratch: SJHIP_STAGE1_QUEUE_SLOTS records of 32 bytes).  A queued message is not launched at once: it waits in the context
+// for company, and up to stage1_group_limit() messages of one mode go out as ONE launch of the tile pipeline (stage1.hip GROUP),
+// which pays the pipeline's fill and drain once.  The group is launched when it is full, when a message of the other mode
+// arrives, when the next message's tiles would not fit the descriptor set behind its own, on _wait, and by
+// stage1_queue_flush wherever something else is about to use the context (sj_ctx.h).
 static inline unsigned long long *s1q_record(sjhip_ctx *ctx, int slot) {
     return (unsigned long long *)(ctx->h_scratch + 2048 + (size_t)slot * 32);
+}
+int sj::stage1_queue_flush(sjhip_ctx *ctx) {
+    const int n = ctx->s1q_n;
+    if (n == 0) return SJHIP_OK;
+    ctx->s1q_n = 0;  // (whatever happens: a group that cannot be launched is not tried again)
+    ctx->s1q_tiles = 0;
+    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    const int rc = stage1_workspace_clean(ctx);
+    if (rc) return rc;
+    if (n == 1) {  // one message: the plain launch (a single round of tiles takes its static first tiles)
+        const S1QMsg &m = ctx->s1q[0];
+        HIPCHK(stage1_launch(m.d_msg, m.len, ctx->s1q_nd, m.d_pos, m.pos_cap, ctx->s1ws, ctx->stream, nullptr, nullptr, m.h_state),
+               "stage1 launch (queued)");
+    } else {
+        HIPCHK(stage1_launch_group(ctx->s1q, n, ctx->s1q_nd, ctx->s1ws, ctx->stream), "stage1 launch (queued group)");
+    }
+    return SJHIP_OK;
 }
 int sjhip_stage1_device_queue(sjhip_ctx *ctx, const void *d_msg, size_t len, int ndjson, void *d_pos, size_t pos_cap, int slot) {
     if (!ctx || slot < 0 || slot >= SJHIP_STAGE1_QUEUE_SLOTS) return SJHIP_ERR_ARG;
     static_assert(SJHIP_STAGE1_QUEUE_SLOTS * 32 <= 2048 && S1_HOST_WORDS * 8 <= 32, "the records fill the upper half of h_scratch");
-    stage1_only(ctx);
-    if (len == 0) {  // (no launch: the record says so)
-        unsigned long long *r = s1q_record(ctx, slot);
-        r[0] = r[1] = r[2] = 0;
-        return SJHIP_OK;
+    stage1_only_result(ctx);
+    unsigned long long *rec = s1q_record(ctx, slot);
+    for (int k = 0; k < S1_HOST_WORDS; k++) ((volatile unsigned long long *)rec)[k] = 0;
+    if (len == 0) return SJHIP_OK;  // (no launch: the record says so; the group that waits goes on waiting)
+    if (len >= 0xffffffc0ull) {
+        ctx_set_error(ctx, "message too long for uint32 positions");
+        return SJHIP_ERR_TOOBIG;
     }
-    return stage1_enqueue(ctx, d_msg, len, ndjson != 0, d_pos, pos_cap, nullptr, nullptr, nullptr, 0, s1q_record(ctx, slot));
+    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    // the workspace holds the descriptors of a full group of messages like this one (grow-only; the messages that wait have not
+    // been launched: a new allocation is theirs as well)
+    const int limit = stage1_group_limit();
+    int rc = arena_reserve(ctx, ctx->d_ws, stage1_workspace_bytes(len + 64) * (size_t)limit);
+    if (rc) return rc;
+    rc = stage1_workspace_clean(ctx);
+    if (rc) return rc;
+    const int nd = ndjson != 0;
+    const size_t tiles = stage1_tiles(d_msg, len);
+    if (ctx->s1q_n && (ctx->s1q_n >= limit || ctx->s1q_nd != nd || ctx->s1q_tiles + tiles > stage1_workspace_tiles(ctx->s1ws))) {
+        rc = stage1_queue_flush(ctx);
+        if (rc) return rc;
+    }
+    ctx->s1q[ctx->s1q_n++] = S1QMsg{d_msg, len, (uint32_t *)d_pos, pos_cap, rec};
+    ctx->s1q_nd = nd;
+    ctx->s1q_tiles += tiles;
+    return ctx->s1q_n >= limit ? stage1_queue_flush(ctx) : SJHIP_OK;  // (a full group starts at once: the device works while the host queues on)
 }
 int sjhip_stage1_device_wait(sjhip_ctx *ctx) {
     if (!ctx) return SJHIP_ERR_ARG;
+    const int rc = stage1_queue_flush(ctx);
+    if (rc) return rc;
     HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
     HIPCHK(hipStreamSynchronize(ctx->stream), "stage1 sync");
     return SJHIP_OK;

@@ -51,6 +51,11 @@ struct sjhip_ctx {
     sj::DevBuf d_parents;
     unsigned ws_clean_gen = 0;         // d_ws.gen of the allocation that has been zeroed for stage 1 (0: none; stage1_enqueue)
     sj::S1Ws s1ws;                     // ... and its launch count (sj_device.h: a launch cleans up for the next one)
+    // queued stage-1 messages that wait for their launch (api.hip: the queue runs up to S1_GROUP_MAX messages of one mode as one
+    // launch): s1q_n of them, s1q_tiles descriptors together; stage1_queue_flush launches them
+    sj::S1QMsg s1q[sj::S1_GROUP_MAX];
+    int s1q_n = 0, s1q_nd = 0;
+    size_t s1q_tiles = 0;
     unsigned s1_par = 0;               // control slot of the last stage-1 launch (Stage1State::c[]: stage 2 reads has_starter there)
     sj::Stage1State s1;                // last stage-1 state (host copy)
     // the tape and Strings.B in d_tape / d_strings (what sjhip_fetch copies): of the last parse, or of the last sjhip_deserialize
@@ -92,8 +97,13 @@ int no_result(sjhip_ctx *ctx, const char *follows);
 int no_whole_result(sjhip_ctx *ctx, const char *call, const char *follows);
 // the return code of a call that has just published a product: an internal error if there was no result to publish it on
 int published(sjhip_ctx *ctx, bool ok);
+// Launches the queued stage-1 messages that still wait for company (api.hip).  The one hook of everything that must not
+// overtake them: a parse (begin_parse), a stage-1 entry point, _wait, and whatever changes or frees the stream or the arenas.
+// A failure is left in the context; the messages' records then stay "left no result".
+int stage1_queue_flush(sjhip_ctx *ctx);
 // a parse entry point, before anything that can return: the last result and everything derived from it are gone
 inline void begin_parse(sjhip_ctx *ctx) {
+    if (ctx->s1q_n) (void)stage1_queue_flush(ctx);
     ctx->res.begin_parse();
     ctx->tape_len = ctx->strings_len = 0;
 }

@@ -104,6 +104,7 @@ struct S1Ws {
     size_t bytes = 0;
     unsigned epoch = 0;       // launches since the workspace was zeroed
     unsigned prev_tiles = 0;  // descriptors the last launch used (the next one zeroes them)
+    bool dirty = false;       // a launch on it failed: nothing is launched on it until it has been zeroed again (stage1_prepare)
 };
 // Zeroes a workspace whose contents are unknown and resets its epoch (a parse does not need it: every launch leaves the
 // workspace ready for the next one).  zero2 / zero2_bytes: a second region to zero, or null
@@ -158,6 +159,30 @@ hipError_t stage1_launch(const void *d_msg, size_t len, int ndjson, uint32_t *d_
                          hipStream_t stream, void *aux_buf = nullptr, uint8_t *d_kind = nullptr,
                          unsigned long long *h_state = nullptr, void *zero2 = nullptr, size_t zero2_bytes = 0,
                          unsigned long long *d_trace = nullptr);
+// Grouped launch of plain stage 1 (the queue of api.hip): up to S1_GROUP_MAX messages of one mode in ONE launch of the tile
+// pipeline -- the blocks go from a message's last tiles to the next one's first without leaving the device (stage1.hip).  Every
+// message has its own buffers and host record; none is empty.  stage1_group_limit(): the messages a launch may take (1: the
+// selected kernel variant has no grouped form); stage1_tiles(): the descriptors a message takes of the
+// stage1_workspace_tiles(ws) one launch has.
+// G = 8, measured (profiles/r28_stage1_group_ab.txt; bench.py --steps 64, one box, ms per step at 256 MiB / 64 MiB messages):
+//   G = 1  0.0901 / 0.0362-0.0365     G = 4  0.0885-0.0886 / 0.0259-0.0260
+//   G = 8  0.0862-0.0870 / 0.0238     G = 16 0.0912-0.0928 / 0.0248-0.0249  (the host queues 16 messages before the device starts)
+// 4 is not within 1 % of 8 at either size; the table of 8 messages is 0.6 KB of kernel arguments.
+#if !defined(SJ_S1_GROUP_MAX)
+#define SJ_S1_GROUP_MAX 8  // (A/B builds: -DSJ_S1_GROUP_MAX=16; smaller groups at run time: SJHIP_S1_GROUP)
+#endif
+static constexpr int S1_GROUP_MAX = SJ_S1_GROUP_MAX;
+struct S1QMsg {
+    const void *d_msg;
+    size_t len;
+    uint32_t *d_pos;
+    size_t pos_cap;
+    unsigned long long *h_state;
+};
+int stage1_group_limit();
+unsigned stage1_tiles(const void *d_msg, size_t len);
+size_t stage1_workspace_tiles(const S1Ws &ws);
+hipError_t stage1_launch_group(const S1QMsg *msgs, int n, int ndjson, S1Ws &ws, hipStream_t stream);
 // kernel variant for A/B runs (-1: SJHIP_S1_VARIANT or the default); per-phase trace size of one launch
 int stage1_set_variant(int v);
 size_t stage1_trace_words(size_t len, size_t lead, unsigned *tiles_out, int *waves_out);

@@ -85,18 +85,21 @@ __device__ __forceinline__ void launch_clean(Stage1State *st, const S1Aux &aux) 
     for (u64 i = thr; i < aux.zero2_quads; i += nthr) aux.zero2[i] = make_uint4(0u, 0u, 0u, 0u);
     if (thr == 0) *reinterpret_cast<uint4 *>(&st->c[aux.par ^ 1u]) = make_uint4(0u, 0u, 0u, 0u);
 }
-// an error of the launch: control word (device) and host record (a store of a constant: any number of blocks may do it)
-__device__ __forceinline__ void report_error(Stage1Ctrl *ctl, const S1Aux &aux, u32 bit) {
-    atomicOr(&ctl->error, bit);
-    if (aux.host) __hip_atomic_store(&aux.host[bit == 1u ? 1 : 2], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+// an error of a message: control word (device) and host record (a store of a constant: any number of blocks may do it).  DEV: the
+// launch holds one message, whose state also lives in the workspace; the messages of a grouped launch have their host records only
+template <bool DEV = true>
+__device__ __forceinline__ void report_error(Stage1Ctrl *ctl, unsigned long long *host, u32 bit) {
+    if (DEV) atomicOr(&ctl->error, bit);
+    if (host) __hip_atomic_store(&host[bit == 1u ? 1 : 2], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
-// the block that flattens the last tile leaves the count: device word (stage 2 reads it) and word 0 of the host record
-__device__ __forceinline__ void report_total(Stage1State *st, const S1Aux &aux, u64 total, u32 ends_in_quote, const u8 *msg, u64 len) {
-    __hip_atomic_store(&st->total, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (aux.host) {
+// the block that flattens a message's last tile leaves the count: device word (stage 2 reads it) and word 0 of the host record
+template <bool DEV = true>
+__device__ __forceinline__ void report_total(Stage1State *st, unsigned long long *host, u64 total, u32 ends_in_quote, const u8 *msg, u64 len) {
+    if (DEV) __hip_atomic_store(&st->total, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (host) {
         const u64 word = S1_HOST_VALID | (ends_in_quote ? S1_HOST_IN_QUOTE : 0) | ((u64)(len ? msg[len - 1] : 0u) << S1_HOST_LAST_SHIFT) |
                          (total & S1_HOST_TOTAL_MASK);
-        __hip_atomic_store(&aux.host[0], (unsigned long long)word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&host[0], (unsigned long long)word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 // per-phase timeline of a tile for every wave (profiling builds of the kernels, sjhip_stage1_trace):
@@ -222,7 +225,7 @@ struct UnitRegs {
     uint4 v[4];
     u64 prev8;
 };
-// The first or the last unit of the message (at most two units per launch).  A chunk inside the message is loaded, a chunk
+// The first or the last unit of a message (at most two units per message of the launch).  A chunk inside the message is loaded, a chunk
 // outside is blanks, and the (at most two) chunks the message covers only partly -- the one with its first byte when the
 // message does not begin on a 64-byte boundary, the one with its last -- are fetched a byte per lane (only message bytes are
 // touched), laid down in 64 bytes of LDS and picked up by the lane that owns the chunk.
@@ -279,11 +282,12 @@ struct LookBack {
     u64 Ft0, Ft1;
 };
 
-__device__ __forceinline__ void lookback_load(const u64 *desc, long long j, int lane, u64 (&d)[4]) {
+// lo: the descriptor of the message's first tile (0 unless the launch holds several messages: nothing crosses a message boundary)
+__device__ __forceinline__ void lookback_load(const u64 *desc, long long j, int lane, u64 (&d)[4], long long lo = 0) {
 #pragma unroll
     for (int q = 0; q < 4; q++) {
         const long long idx = j - 4 * lane - q;
-        d[q] = idx >= 0 ? desc_load(&desc[idx]) : pack_prefix(0, 0);  // virtual prefix before tile 0
+        d[q] = idx >= lo ? desc_load(&desc[idx]) : pack_prefix(0, 0);  // virtual prefix before the message's tile 0
     }
 }
 // Evaluates the window d loaded at lb.j.  0: needed descriptors still invalid (reload the same window),
@@ -357,12 +361,19 @@ __device__ __forceinline__ int lookback_eval(const u64 (&d)[4], LookBack &lb, in
 //             count(inside) << 13 | count(outside)          for unit u = pass * WAVES + wave.
 __device__ __forceinline__ bool par_ballot_any(u64 m) { return __ballot(((u32)m | (u32)(m >> 32)) != 0) != 0; }
 template <int BLOCK, int CH, bool NDJSON, bool AUX>
-__device__ __forceinline__ void phase_a(const u8 *__restrict__ base, u64 lead, u64 end, TileMap tm, u32 t, u32 t_next,
+__device__ __forceinline__ void phase_a(const u8 *__restrict__ base, u64 lead, u64 end, TileMap tm, u32 t,
+                                        const u8 *__restrict__ base_n, u64 lead_n, u64 end_n, TileMap tm_n, u32 t_next,
                                         bool has_next, int lane, int wave, UnitRegs &pf, u64 *m, u32 *pre, u32 *s_unit,
                                         const S1Aux &aux, u64 (&kp)[CH][4], uint2 *s_ucnt,
                                         u32 &seen_st, u8 *s_edge_w, bool TOP = false) {
     constexpr int WAVES = BLOCK / 64;
     constexpr int UNITS = WAVES * CH;
+    // the loads of the unit behind pass k: of this tile, or (last pass) of the next tile -- t / t_next are tiles of their own
+    // messages (base, tm, ... and base_n, tm_n, ...: the same message unless the launch holds several and t is one's last tile)
+    auto issue_next = [&](int k, u64 unit_nx) {
+        if (k + 1 < CH) unit_issue(base, lead, end, unit_nx, tm.nu, lane, pf, s_edge_w);
+        else unit_issue(base_n, lead_n, end_n, unit_nx, tm_n.nu, lane, pf, s_edge_w);
+    };
 #if defined(SJ_S1_ROLL)
 #pragma unroll 1
 #else
@@ -372,7 +383,7 @@ __device__ __forceinline__ void phase_a(const u8 *__restrict__ base, u64 lead, u
         const u64 unit = tile_unit<UNITS>(tm, t, k * WAVES + wave);  // wave-uniform
         // the unit behind this one (next pass, or the first pass of the next tile): its loads are issued below
         const u64 unit_nx = k + 1 < CH ? tile_unit<UNITS>(tm, t, (k + 1) * WAVES + wave)
-                                       : (has_next ? tile_unit<UNITS>(tm, t_next, wave) : VOID_UNIT);
+                                       : (has_next ? tile_unit<UNITS>(tm_n, t_next, wave) : VOID_UNIT);
         if (unit == VOID_UNIT) {  // a tail tile holds fewer units than a full one: nothing to classify
             m[(k * 2 + 0) * 64 + lane] = 0;
             m[(k * 2 + 1) * 64 + lane] = 0;
@@ -380,7 +391,7 @@ __device__ __forceinline__ void phase_a(const u8 *__restrict__ base, u64 lead, u
             if (lane == 0) s_unit[k * WAVES + wave] = 0;
             if (AUX && lane == 0) s_ucnt[k * WAVES + wave] = make_uint2(0u, 0u);
             kp[k][0] = kp[k][1] = kp[k][2] = kp[k][3] = 0;
-            if (unit_nx != VOID_UNIT) unit_issue(base, lead, end, unit_nx, tm.nu, lane, pf, s_edge_w);
+            if (unit_nx != VOID_UNIT) issue_next(k, unit_nx);
             continue;
         }
         const u64 unit_off = unit * 4096;
@@ -402,7 +413,7 @@ __device__ __forceinline__ void phase_a(const u8 *__restrict__ base, u64 lead, u
         // the next pass goes in flight before this one is classified: a whole pass of math to arrive in (the compiler
         // keeps the chunk in its own registers; issuing the loads only after classify(), into the registers the chunk
         // dies in, measured 1-2 % slower)
-        if (unit_nx != VOID_UNIT) unit_issue(base, lead, end, unit_nx, tm.nu, lane, pf, s_edge_w);
+        if (unit_nx != VOID_UNIT) issue_next(k, unit_nx);
         __builtin_amdgcn_sched_barrier(0);
         // issue priority by progress: the SIMD arbiter prefers its oldest wave, which then finishes a pass long before
         // the others and leaves the tail of every phase to one or two waves that cannot fill the pipe; with the waves
@@ -676,11 +687,55 @@ __device__ __forceinline__ bool flatten_tile(TileMap tm, u64 *m, const u64 *kpl,
 // Persistent blocks draw tiles from a ticket counter: tiles are started in id order, so every
 // predecessor in the look-back chain is resident or finished (forward progress without any
 // dispatch-order assumption), and no block ever waits for the dispatcher.
-template <int BLOCK, int CH, int WPE, bool NDJSON, bool AUX, bool TRACE = false>
+//
+// GROUP (plain stage 1 of queued messages, sj_device.h stage1_launch_group): one launch runs up to S1_GROUP_MAX messages.
+// Their tile lists lie end to end: a ticket is a global tile id, descriptor t belongs to global tile t, and the blocks stay
+// on the device across a message boundary -- phase A of the next message's first tiles runs beside the flatten of this
+// message's last ones, so the fill and the drain of the pipeline are paid once per launch, not once per message.  The tile
+// a block classifies and the tile it flattens may belong to different messages: each has its own parameter set (TileMsg),
+// looked up from its ticket.  Nothing crosses a message boundary: units, positions and the tile plan are relative to the
+// tile's own message (so its unit 0 starts with no carries and its first and last unit are edge units), its local tile 0
+// publishes a PREFIX descriptor and its look-back stops there, and count, end state and errors go to its own host record.
+struct S1Msg {  // one message of a grouped launch
+    const u8 *base;            // 64-byte aligned; the message is [lead, lead + len) of it
+    u32 *out_pos;
+    unsigned long long *host;  // its host record (S1_HOST_WORDS words)
+    u64 lead, len, pos_cap;
+    TileMap tm;
+    u32 tile0, tiles;          // its first global tile (and descriptor), its tiles
+};
+struct S1Group {
+    u32 first[S1_GROUP_MAX];  // tile0 of message k; 0xffffffff behind the last message
+    S1Msg m[S1_GROUP_MAX];
+};
+static_assert(sizeof(S1Group) + sizeof(S1Aux) + 128 <= 4096, "the message table travels in the kernel arguments");
+struct S1NoGroup {};
+// the message of a tile: everything wave-uniform
+struct TileMsg {
+    const u8 *base;
+    u64 lead, end, len;
+    u32 *out_pos;
+    u64 pos_cap;
+    TileMap tm;
+    u32 tile0, tiles;
+    unsigned long long *host;
+};
+__device__ __forceinline__ TileMsg tile_msg(const S1NoGroup &, u32, const TileMsg &one) { return one; }
+__device__ __forceinline__ TileMsg tile_msg(const S1Group &g, u32 t, const TileMsg &) {  // t: a ticket (any value)
+    u32 k = 0;
+#pragma unroll
+    for (int i = 1; i < S1_GROUP_MAX; i++) k += t >= g.first[i] ? 1u : 0u;  // (scalar compares: t is wave-uniform)
+    const S1Msg &m = g.m[k];
+    return TileMsg{m.base, m.lead, m.lead + m.len, m.len, m.out_pos, m.pos_cap, m.tm, m.tile0, m.tiles, m.host};
+}
+
+template <int BLOCK, int CH, int WPE, bool NDJSON, bool AUX, bool TRACE = false, bool GROUP = false>
 __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel(const u8 *__restrict__ base, u64 lead, u64 len,
                                                                         u32 *__restrict__ out_pos,
                                                                         u64 pos_cap, Stage1State *__restrict__ st,
-                                                                        u64 *__restrict__ desc, u32 num_tiles, TileMap tm, S1Aux aux) {
+                                                                        u64 *__restrict__ desc, u32 num_tiles, TileMap tm, S1Aux aux,
+                                                                        typename std::conditional<GROUP, S1Group, S1NoGroup>::type grp) {
+    static_assert(!GROUP || (!AUX && !TRACE), "grouped launches are plain stage 1");
     constexpr int WAVES = BLOCK / 64;
     constexpr int UNITS = WAVES * CH;  // unit u = pass * WAVES + wave, in byte order
     static_assert(UNITS <= 32, "pre_mask is a u32");
@@ -711,7 +766,8 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel(const u8 *__restrict
     // (Round 4 gave every block a static first tile; with a second kernel holding compute units a block could then draw
     // a later ticket and look back on tiles of blocks that had not been dispatched yet -- a bounded spin, i.e. a
     // spurious "internal error", with several >256-tile parses in flight on one device.)
-    const bool one_round = num_tiles <= gridDim.x;  // (uniform over the grid)
+    // (A grouped launch draws every tile as well: its tiles are those of several messages, small ones in front of large ones.)
+    const bool one_round = !GROUP && num_tiles <= gridDim.x;  // (uniform over the grid)
     const u32 tk_base = one_round ? gridDim.x : 0u;
     // (round 6) the ticket of the SECOND tile is drawn together with the first: phase A of T(0) then sends T(1)'s first unit on
     // its way like every later phase A does for its successor, instead of behind the first barrier with the whole load
@@ -723,10 +779,12 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel(const u8 *__restrict
     __syncthreads();
     const u32 t_first = uniform(s_ticket[0]);
     if (t_first >= num_tiles) return;
+    const TileMsg one = {base, lead, end, len, out_pos, pos_cap, tm, 0u, num_tiles, aux.host};  // the message of a launch without a group
     UnitRegs pf;
     {
-        const u64 un = tile_unit<UNITS>(tm, t_first, wave);
-        if (un != VOID_UNIT) unit_issue(base, lead, end, un, tm.nu, lane, pf, s_edge[wave]);
+        const TileMsg g0 = tile_msg(grp, t_first, one);
+        const u64 un = tile_unit<UNITS>(g0.tm, t_first - g0.tile0, wave);
+        if (un != VOID_UNIT) unit_issue(g0.base, g0.lead, g0.end, un, g0.tm.nu, lane, pf, s_edge[wave]);
     }
 
     // One loop, one copy of phase A and of the flatten in the instruction stream (a peeled first tile made every block
@@ -747,13 +805,17 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel(const u8 *__restrict
         const u32 t_a = uniform(s_ticket[j & 3u]);                               // phase A runs on T(j)
         const u32 t_an = uniform(s_ticket[(j + 1u) & 3u]);  // T(j+1): its first unit is loaded behind T(j)'s last
         const bool has_a = t_a < num_tiles;
+        // the messages of T(j), T(j+1) and T(j-1), and the tiles' numbers inside them
+        const TileMsg ga = tile_msg(grp, t_a, one), gn = tile_msg(grp, t_an, one), gf = tile_msg(grp, t_prev, one);
+        const u32 l_a = t_a - ga.tile0, l_prev = t_prev - gf.tile0;
         const int ma = (int)(j & 1u), ua = (int)(j % 3u);        // mask / unit slot of T(j)
         const int mf = ma ^ 1, uf = ua == 0 ? 2 : ua - 1;        // ... of T(j-1)
         u32 tk2 = 0;  // the ticket drawn now (lane 0 of wave 0); it returns while phase A runs
         if (tid == 0 && has_a) tk2 = tk_base + atomicAdd(&ctl->tile_counter, 1u);
         if (has_a) {
             trace_put<TRACE>(aux.trace, t_a, WAVES, wave, lane, 0);
-            phase_a<BLOCK, CH, NDJSON, AUX>(base, lead, end, tm, t_a, t_an, t_an < num_tiles, lane, wave, pf, s_mask[ma][wave],
+            phase_a<BLOCK, CH, NDJSON, AUX>(ga.base, ga.lead, ga.end, ga.tm, l_a, gn.base, gn.lead, gn.end, gn.tm, t_an - gn.tile0,
+                                            t_an < num_tiles, lane, wave, pf, s_mask[ma][wave],
                                             s_pre[ma][wave], s_unit[ua], aux, kp, s_ucnt[AUX ? ua : 0], seen_st, s_edge[wave], wave == 0 && !first);
             trace_put<TRACE>(aux.trace, t_a, WAVES, wave, lane, 1);
         }
@@ -761,20 +823,21 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel(const u8 *__restrict
         if (wave == 0) {
             u32 G = 0;
             u64 BASE = 0;
-            if (!first && t_prev != 0) {
+            if (!first && l_prev != 0) {
                 LookBack lb = {(long long)t_prev - 1, 0, 0, 0};
+                const long long lo = (long long)gf.tile0;  // the look-back stays inside the message
                 u64 win[4];
-                lookback_load(desc, lb.j, lane, win);
+                lookback_load(desc, lb.j, lane, win, lo);
                 u32 spins = 0;
                 for (;;) {
                     const int r = lookback_eval(win, lb, lane, G, BASE);
                     if (r == 1) break;
                     if (r == 0) __builtin_amdgcn_s_sleep(1);
                     if (++spins > (1u << 22)) {  // bounded: a bug must not hang the device
-                        if (lane == 0) report_error(ctl, aux, 0x80000000u);
+                        if (lane == 0) report_error<!GROUP>(ctl, gf.host, 0x80000000u);
                         break;
                     }
-                    lookback_load(desc, lb.j, lane, win);
+                    lookback_load(desc, lb.j, lane, win, lo);
                 }
                 if (lane == 0) desc_store(&desc[t_prev], pack_prefix(G ^ P0, BASE + (G ? T01 : T00)));
             }
@@ -784,9 +847,9 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel(const u8 *__restrict
                     res[1] = pm0;
                     res[2] = (u32)BASE;
                     res[3] = (u32)(BASE >> 32);
-                    if (t_prev == num_tiles - 1) {
+                    if (l_prev == gf.tiles - 1) {
                         eiq_last = (G ^ P0) & 1u;
-                        __hip_atomic_store(&st->ends_in_quote, eiq_last, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (!GROUP) __hip_atomic_store(&st->ends_in_quote, eiq_last, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     }
                 }
                 if (has_a) s_ticket[(j + 2u) & 3u] = tk2;
@@ -796,17 +859,22 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel(const u8 *__restrict
         __syncthreads();
         if (wave == 0 && has_a) {  // (only wave 0 keeps the aggregates: it resolves the tile in the next iteration)
             tile_aggregate<UNITS>(s_unit[ua], lane, P0, T00, T01, pm0);
-            if (lane == 0) desc_store(&desc[t_a], t_a == 0 ? pack_prefix(P0, T00) : pack_agg(P0, T00, T01));
+            if (lane == 0) desc_store(&desc[t_a], l_a == 0 ? pack_prefix(P0, T00) : pack_agg(P0, T00, T01));
         }
         if (!first) {
             trace_put<TRACE>(aux.trace, t_prev, WAVES, wave, lane, 3);
             const u32 G = uniform(res[0]), pm = uniform(res[1]);
             const u64 BASE = ((u64)uniform(res[3]) << 32) | uniform(res[2]);
             u64 tile_end = 0;
-            err |= flatten_tile<BLOCK, CH, AUX>(tm, s_mask[mf][wave], s_kpl[AUX ? wave : 0], s_pre[mf][wave], s_unit[uf], pm, G, BASE, t_prev, lead, lane, wave,
-                                           S1_POS_VIEW(out_pos, pos_cap), pos_cap, tile_end, AUX ? aux.unit_h : Arr<u8>(nullptr), len,
+            const bool bad = flatten_tile<BLOCK, CH, AUX>(gf.tm, s_mask[mf][wave], s_kpl[AUX ? wave : 0], s_pre[mf][wave], s_unit[uf], pm, G, BASE, l_prev, gf.lead, lane, wave,
+                                           S1_POS_VIEW(gf.out_pos, gf.pos_cap), gf.pos_cap, tile_end, AUX ? aux.unit_h : Arr<u8>(nullptr), gf.len,
                                            AUX ? aux.kind : Arr<u8>(nullptr), aux, s_ucnt[AUX ? uf : 0]);
-            if (t_prev == num_tiles - 1 && tid == 0) report_total(st, aux, tile_end, eiq_last, base + lead, len);
+            if (GROUP) {  // the error belongs to this tile's message (rare: a store per wave that met one)
+                if (__ballot(bad) != 0 && lane == 0) report_error<false>(ctl, gf.host, 1u);
+            } else {
+                err |= bad;
+            }
+            if (l_prev == gf.tiles - 1 && tid == 0) report_total<!GROUP>(st, gf.host, tile_end, eiq_last, gf.base + gf.lead, gf.len);
             trace_put<TRACE>(aux.trace, t_prev, WAVES, wave, lane, 4);
             if (TRACE && lane == 0)
                 aux.trace[((u64)t_prev * WAVES + wave) * TRACE_WORDS + 5] =
@@ -823,7 +891,7 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel(const u8 *__restrict
         }
         t_prev = t_a;
     }
-    if (__ballot(err) != 0 && lane == 0) report_error(ctl, aux, 1u);
+    if (!GROUP && __ballot(err) != 0 && lane == 0) report_error(ctl, aux.host, 1u);
     if (AUX && aux.want_flag) {  // (uniform over the grid)
         // one look and at most one store per BLOCK (an atomicOr per wave -- 4096 of them on one word as the kernel ends -- cost
         // configs[1] 31 us: a word takes ~88 atomics per microsecond)
@@ -906,7 +974,7 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel_nb(const u8 *__restr
     }
     trace_put<TRACE>(aux.trace, t_first, WAVES, wave, lane, 0);
     u32 seen_st_nb = 0;  // (this kernel never runs the whole parse: unused)
-    phase_a<BLOCK, CH, NDJSON, AUX>(base, lead, end, tm, t_first, 0, false, lane, wave, pf, s_mask[0][wave], s_pre[0][wave], s_unit[0],
+    phase_a<BLOCK, CH, NDJSON, AUX>(base, lead, end, tm, t_first, base, lead, end, tm, 0, false, lane, wave, pf, s_mask[0][wave], s_pre[0][wave], s_unit[0],
                                     aux, kp, nullptr, seen_st_nb, s_edge[wave]);
     trace_put<TRACE>(aux.trace, t_first, WAVES, wave, lane, 1);
     __syncthreads();
@@ -939,7 +1007,7 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel_nb(const u8 *__restr
             if (!wait) return false;
             __builtin_amdgcn_s_sleep(1);
             if (++spins > (1u << 24)) {  // bounded: a bug must not hang the device
-                if (lane == 0) report_error(ctl, aux, 0x80000000u);
+                if (lane == 0) report_error(ctl, aux.host, 0x80000000u);
                 break;
             }
         }
@@ -961,7 +1029,7 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel_nb(const u8 *__restr
                     __builtin_amdgcn_s_sleep(1);
                 }
                 if (++spins > (1u << 22)) {
-                    if (lane == 0) report_error(ctl, aux, 0x80000000u);
+                    if (lane == 0) report_error(ctl, aux.host, 0x80000000u);
                     break;
                 }
                 lookback_load(desc, lb.j, lane, win);
@@ -993,7 +1061,7 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel_nb(const u8 *__restr
             while (__hip_atomic_load(&s_tkn, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < it + 3u) {
                 __builtin_amdgcn_s_sleep(1);
                 if (++spins > (1u << 24)) {
-                    if (lane == 0) report_error(ctl, aux, 0x80000000u);
+                    if (lane == 0) report_error(ctl, aux.host, 0x80000000u);
                     break;
                 }
             }
@@ -1005,7 +1073,7 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel_nb(const u8 *__restr
         if (more) {
             const int ma = (int)((it + 1u) % (u32)DEPTH), ua = (int)((it + 1u) & 7u);
             trace_put<TRACE>(aux.trace, ta, WAVES, wave, lane, 0);
-            phase_a<BLOCK, CH, NDJSON, AUX>(base, lead, end, tm, ta, tn, tn < num_tiles, lane, wave, pf, s_mask[ma][wave], s_pre[ma][wave],
+            phase_a<BLOCK, CH, NDJSON, AUX>(base, lead, end, tm, ta, base, lead, end, tm, tn, tn < num_tiles, lane, wave, pf, s_mask[ma][wave], s_pre[ma][wave],
                                             s_unit[ua], aux, kp, nullptr, seen_st_nb, s_edge[wave], wave == 0);
             trace_put<TRACE>(aux.trace, ta, WAVES, wave, lane, 1);
             u32 arrived = 0;
@@ -1044,7 +1112,7 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel_nb(const u8 *__restr
             while (__hip_atomic_load(&s_resflag[f & 3u], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != f + 1u) {
                 __builtin_amdgcn_s_sleep(1);
                 if (++spins > (1u << 24)) {
-                    if (lane == 0) report_error(ctl, aux, 0x80000000u);
+                    if (lane == 0) report_error(ctl, aux.host, 0x80000000u);
                     break;
                 }
             }
@@ -1057,13 +1125,13 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel_nb(const u8 *__restr
         u64 tile_end = 0;
         err |= flatten_tile<BLOCK, CH, false>(tm, s_mask[mf][wave], nullptr, s_pre[mf][wave], s_unit[uf], pm, G, BASE, tf, lead, lane,
                                               wave, S1_POS_VIEW(out_pos, pos_cap), pos_cap, tile_end, Arr<u8>(nullptr), len, Arr<u8>(nullptr), aux, nullptr);
-        if (tf == num_tiles - 1 && tid == 0) report_total(st, aux, tile_end, eiq_last, base + lead, len);
+        if (tf == num_tiles - 1 && tid == 0) report_total(st, aux.host, tile_end, eiq_last, base + lead, len);
         trace_put<TRACE>(aux.trace, tf, WAVES, wave, lane, 4);
         if (TRACE && lane == 0)
             aux.trace[((u64)tf * WAVES + wave) * TRACE_WORDS + 5] =
                 (u64)__builtin_amdgcn_s_getreg(4 | (31 << 11)) | ((u64)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32);
     }
-    if (__ballot(err) != 0 && lane == 0) report_error(ctl, aux, 1u);
+    if (__ballot(err) != 0 && lane == 0) report_error(ctl, aux.host, 1u);
 }
 
 // ---- launcher --------------------------------------------------------------------------
@@ -1158,8 +1226,9 @@ size_t stage1_workspace_bytes(size_t len) {
     const size_t tiles = (len + 128) / (256 * 2 * 64) + 2 + 2048;  // smallest tile of any variant + one round of small tiles
     return sizeof(Stage1State) + 2 * tiles * sizeof(u64) + 64;
 }
+static size_t s1_desc_capacity(const S1Ws &ws) { return (ws.bytes - sizeof(Stage1State)) / 16; }  // descriptors per set
 static u64 *s1_desc_set(const S1Ws &ws, unsigned set) {
-    const size_t half = (ws.bytes - sizeof(Stage1State)) / 16;  // descriptors per set
+    const size_t half = s1_desc_capacity(ws);
     return reinterpret_cast<u64 *>(reinterpret_cast<u8 *>(ws.p) + sizeof(Stage1State)) + (size_t)set * half;
 }
 
@@ -1170,6 +1239,7 @@ hipError_t stage1_prepare(S1Ws &ws, hipStream_t stream, void *zero2, size_t zero
     if (e == hipSuccess && zero2 && zero2_bytes) e = hipMemsetAsync(zero2, 0, zero2_bytes, stream);
     ws.epoch = 0;
     ws.prev_tiles = 0;
+    ws.dirty = e != hipSuccess;
     return e;
 }
 
@@ -1180,6 +1250,19 @@ size_t stage1_trace_words(size_t len, size_t lead, unsigned *tiles_out, int *wav
     if (tiles_out) *tiles_out = tiles;
     if (waves_out) *waves_out = v.block / 64;
     return (size_t)tiles * (size_t)(v.block / 64) * TRACE_WORDS;
+}
+
+// Behind a launch: the workspace counts it only if it went out; after a failed one nobody knows what the next launch would
+// find there, so the workspace is marked and its owner zeroes it before the next launch (stage1_prepare).
+static hipError_t s1_launched(S1Ws &ws, u32 tiles) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) {
+        ws.prev_tiles = tiles;
+        ws.epoch++;
+    } else {
+        ws.dirty = true;
+    }
+    return e;
 }
 
 // d_msg may be any device pointer; ws must hold stage1_workspace_bytes(len + 64) and be clean: zeroed once (stage1_prepare),
@@ -1199,10 +1282,14 @@ hipError_t stage1_launch(const void *d_msg, size_t len, int ndjson, u32 *d_pos, 
     Stage1State *st = reinterpret_cast<Stage1State *>(ws.p);
     const unsigned par = ws.epoch & 1u;
     u64 *desc = s1_desc_set(ws, par);
-    if ((size_t)tiles > (ws.bytes - sizeof(Stage1State)) / 16) return hipErrorInvalidValue;  // (the workspace is too small)
+    // every argument is checked before anything is launched or counted
+    if ((size_t)tiles > s1_desc_capacity(ws)) return hipErrorInvalidValue;  // (the workspace is too small)
+    if ((d_kind != nullptr) != (aux_buf != nullptr)) return hipErrorInvalidValue;  // (the whole-parse kernel writes kinds AND masks: no tests on the device)
+    if (d_trace && ((ndjson & 1) || whole)) return hipErrorInvalidValue;           // (the trace build: plain stage 1 of a non-ND message)
     if (tiles == 0) {  // (nothing is launched: the stage-2 state of an empty message is zeroed the plain way)
         return zero2 && zero2_bytes ? hipMemsetAsync(zero2, 0, zero2_bytes, stream) : hipSuccess;
     }
+    if (ws.dirty) return hipErrorInvalidValue;  // (a launch on it failed: its owner zeroes it first, stage1_prepare)
     const u32 nd = (u32)((ndjson & 1) != 0);
     S1Aux aux = {};
     aux.kind = nullptr;
@@ -1213,14 +1300,11 @@ hipError_t stage1_launch(const void *d_msg, size_t len, int ndjson, u32 *d_pos, 
     aux.par = par;
     aux.clean_desc = s1_desc_set(ws, par ^ 1u);
     aux.clean_tiles = ws.prev_tiles;
-    ws.prev_tiles = tiles;
-    ws.epoch++;
     aux.zero2 = reinterpret_cast<uint4 *>(zero2);
     aux.zero2_quads = zero2 ? (u64)zero2_bytes / 16 : 0;  // (a multiple of 16 bytes, 16-byte aligned: stage2_zero_bytes)
 #if defined(SJ_EXP)
     if (const char *e = getenv("SJHIP_EXP")) aux.exp = (u32)strtoul(e, nullptr, 0);
 #endif
-    if ((d_kind != nullptr) != (aux_buf != nullptr)) return hipErrorInvalidValue;  // (the whole-parse kernel writes kinds AND masks: no tests on the device)
     if (aux_buf) {
         const StrAux a = str_aux_layout(aux_buf, (size_t)lead + len);
         aux.qm = SJ_ARR(a.qm, a.chunks, A_S1_QM);
@@ -1231,27 +1315,25 @@ hipError_t stage1_launch(const void *d_msg, size_t len, int ndjson, u32 *d_pos, 
         aux.unit_str = SJ_ARR(a.unit_str, a.units, A_S1_UNIT_STR);
         aux.tile_unit = SJ_ARR(a.tile_unit, a.units + 1, A_S1_TILE_UNIT);
     }
-#define S1_LAUNCHK(K, B)                                                                                            \
+#define S1_LAUNCHK(K, B, ...)                                                                                       \
     hipLaunchKernelGGL((K), dim3(grid_for(K, B, tiles)), dim3(B), 0, stream, base, lead, (u64)len, d_pos, (u64)pos_cap, \
-                       st, desc, tiles, plan.tm, aux)
+                       st, desc, tiles, plan.tm, aux, ##__VA_ARGS__)
 #define S1_LAUNCH(KERNEL, B, C, W)                                                    \
     do {                                                                              \
         const bool ax = aux_buf || d_kind;                                            \
         if (d_trace) {                                                                \
-            if (nd || ax) return hipErrorInvalidValue;                                \
-            S1_LAUNCHK((KERNEL<B, C, W, false, false, true>), B);                     \
+            S1_LAUNCHK((KERNEL<B, C, W, false, false, true>), B, S1NoGroup{});                     \
         } else if (nd) {                                                              \
-            if (ax) S1_LAUNCHK((KERNEL<B, C, W, true, true>), B);                     \
-            else S1_LAUNCHK((KERNEL<B, C, W, true, false>), B);                       \
+            if (ax) S1_LAUNCHK((KERNEL<B, C, W, true, true>), B, S1NoGroup{});                     \
+            else S1_LAUNCHK((KERNEL<B, C, W, true, false>), B, S1NoGroup{});                       \
         } else {                                                                      \
-            if (ax) S1_LAUNCHK((KERNEL<B, C, W, false, true>), B);                    \
-            else S1_LAUNCHK((KERNEL<B, C, W, false, false>), B);                      \
+            if (ax) S1_LAUNCHK((KERNEL<B, C, W, false, true>), B, S1NoGroup{});                    \
+            else S1_LAUNCHK((KERNEL<B, C, W, false, false>), B, S1NoGroup{});                      \
         }                                                                             \
     } while (0)
 #define S1_LAUNCH_NB(B, C, D, W)                                                            \
     do {                                                                                   \
         if (d_trace) {                                                                     \
-            if (nd) return hipErrorInvalidValue;                                           \
             S1_LAUNCHK((stage1_kernel_nb<B, C, D, W, false, false, true>), B);             \
         } else if (nd) {                                                                   \
             S1_LAUNCHK((stage1_kernel_nb<B, C, D, W, true, false>), B);                    \
@@ -1273,7 +1355,61 @@ hipError_t stage1_launch(const void *d_msg, size_t len, int ndjson, u32 *d_pos, 
 #undef S1_LAUNCH
 #undef S1_LAUNCH_NB
 #undef S1_LAUNCHK
-    return hipGetLastError();
+    return s1_launched(ws, tiles);
+}
+
+// ---- grouped launches (the queue: api.hip) ----------------------------------------------------------------
+// G = 8 messages per launch.  bench.py on configs[1] (64 queued steps of 269 MB) and on 64 MiB messages (--copies 107),
+// one box, G = 1 / 4 / 8 / 16: profiles/r28_stage1_group_ab.txt.
+int stage1_group_limit() {  // the other variants (and the trace build) have no grouped kernel: one message per launch
+    const S1Variant v = s1_variant();
+    const S1Variant d = S1_VARIANTS[S1_DEFAULT_VARIANT];
+    if (v.block != d.block || v.ch != d.ch || v.depth != d.depth) return 1;
+    static const int over = getenv("SJHIP_S1_GROUP") ? atoi(getenv("SJHIP_S1_GROUP")) : 0;  // A/B: smaller groups
+    return over >= 1 && over < S1_GROUP_MAX ? over : S1_GROUP_MAX;
+}
+unsigned stage1_tiles(const void *d_msg, size_t len) {
+    return s1_plan(len, (size_t)(reinterpret_cast<uintptr_t>(d_msg) & 63), S1_VARIANTS[S1_DEFAULT_VARIANT]).tiles;
+}
+size_t stage1_workspace_tiles(const S1Ws &ws) { return ws.p ? s1_desc_capacity(ws) : 0; }
+
+hipError_t stage1_launch_group(const S1QMsg *msgs, int n, int ndjson, S1Ws &ws, hipStream_t stream) {
+    if (n < 1 || n > S1_GROUP_MAX || ws.dirty) return hipErrorInvalidValue;
+    const S1Variant v = S1_VARIANTS[S1_DEFAULT_VARIANT];
+    S1Group grp = {};
+    u64 tiles = 0;
+    for (int k = 0; k < S1_GROUP_MAX; k++) grp.first[k] = 0xffffffffu;
+    for (int k = 0; k < n; k++) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(msgs[k].d_msg);
+        const S1Plan plan = s1_plan(msgs[k].len, a & 63, v);
+        if (msgs[k].len == 0 || plan.tiles == 0 || !msgs[k].h_state) return hipErrorInvalidValue;  // (an empty message launches nothing)
+        S1Msg &m = grp.m[k];
+        m.base = reinterpret_cast<const u8 *>(a & ~(uintptr_t)63);
+        m.lead = a & 63;
+        m.len = msgs[k].len;
+        m.out_pos = msgs[k].d_pos;
+        m.pos_cap = msgs[k].pos_cap;
+        m.host = msgs[k].h_state;
+        m.tm = plan.tm;
+        m.tile0 = grp.first[k] = (u32)tiles;
+        m.tiles = plan.tiles;
+        tiles += plan.tiles;
+    }
+    if (tiles > s1_desc_capacity(ws)) return hipErrorInvalidValue;  // (the caller splits the group)
+    const unsigned par = ws.epoch & 1u;
+    S1Aux aux = {};
+    aux.par = par;
+    aux.clean_desc = s1_desc_set(ws, par ^ 1u);
+    aux.clean_tiles = ws.prev_tiles;
+    Stage1State *st = reinterpret_cast<Stage1State *>(ws.p);
+    u64 *desc = s1_desc_set(ws, par);
+#define S1_LAUNCHG(K)                                                                                                   \
+    hipLaunchKernelGGL((K), dim3(grid_for(K, 1024, (u32)tiles)), dim3(1024), 0, stream, (const u8 *)nullptr, (u64)0, (u64)0, \
+                       (u32 *)nullptr, (u64)0, st, desc, (u32)tiles, TileMap{}, aux, grp)
+    if (ndjson & 1) S1_LAUNCHG((stage1_kernel<1024, 2, 4, true, false, false, true>));
+    else S1_LAUNCHG((stage1_kernel<1024, 2, 4, false, false, false, true>));
+#undef S1_LAUNCHG
+    return s1_launched(ws, (u32)tiles);
 }
 
 // debug build (-DSJ_DEBUG_BOUNDS, sj_bounds.h): 1 and the record of the out-of-bounds accesses of the stage-1 kernels since the

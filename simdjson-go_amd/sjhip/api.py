@@ -121,8 +121,9 @@ class Context:
     STAGE1_QUEUE_SLOTS = 64
 
     def stage1_queue(self, d_msg_ptr, length, d_pos_ptr, pos_cap, slot, ndjson=False):
-        """sjhip_stage1_device without the synchronisation: the launch goes behind what the stream holds; its result is
-        taken with stage1_result(slot, length) after stage1_wait()."""
+        """sjhip_stage1_device without the synchronisation: the message goes behind what the stream holds (queued messages
+        of one mode run several to a launch, started no later than stage1_wait()); its result is taken with
+        stage1_result(slot, length) after stage1_wait()."""
         self._check(_lib.lib().sjhip_stage1_device_queue(self._h, C.c_void_p(d_msg_ptr), length, int(ndjson),
                                                          C.c_void_p(d_pos_ptr), pos_cap, int(slot)))
 
