@@ -882,7 +882,7 @@ extern "C" uint32_t sj_selftest_order_pass_mask(uint64_t and_, uint64_t or_) { r
 extern "C" void sj_selftest_order_geometry(int *out4) {
     out4[0] = sj::SORT_RADIX_BITS, out4[1] = sj::SORT_THREADS, out4[2] = sj::SORT_ROUNDS, out4[3] = sj::SORT_TILE;
 }
-// the chunk key of the string order (sjhip_order_path_strings) as k_q_strord_chunks computes it, complemented for a descending
+// the chunk key of the string order (sjhip_order_path_strings) as k_q_order_chunks computes it, complemented for a descending
 // order; out3: the key, the count strord_chunk_count reads back from it, the rounds that bound keys of `len` bytes
 extern "C" void sj_selftest_strord_chunk(const uint8_t *bytes, uint64_t len, uint64_t at, int desc, uint64_t *out3) {
     const uint64_t k = sj::strord_chunk(bytes, len, at);
@@ -891,7 +891,7 @@ extern "C" void sj_selftest_strord_chunk(const uint8_t *bytes, uint64_t len, uin
     out3[2] = sj::strord_max_rounds(len);
 }
 // the order by several keys (sjhip_order_paths): the second sort's key of an entry, and whether it goes on to the column's next round,
-// as k_q_mkord_chunks and k_q_mkord_place compute them; and the column limit the header mirrors
+// as k_q_order_chunks and k_q_order_place compute them; and the column limit the header mirrors
 extern "C" uint32_t sj_selftest_mkord_class_key(uint32_t cls, int missing) { return sj::mkord_class_key(cls, missing != 0); }
 extern "C" int sj_selftest_mkord_stays(int missing, int alone, int chunk_full) { return sj::mkord_stays(missing != 0, alone != 0, chunk_full != 0) ? 1 : 0; }
 extern "C" int sj_selftest_order_max_keys() { return sj::ORDER_MAX_KEYS; }

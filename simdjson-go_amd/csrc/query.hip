@@ -1757,31 +1757,76 @@ __global__ __launch_bounds__(256) void k_q_group_counts(Arr<const u64> off, u32 
     if (g < groups) group_rows[g] = off[g + 1] - off[g];
 }
 
-// ---- order: the rows ranked by a numeric key at a path, the first `limit` of them kept (sjhip_order_path) ----------------------------
-// The rank of a row is its position in: the rows with an OK key ascending by key (descending: by the complement of the key), equal
-// keys in row order, then the rows without one in row order.  The selection is narrowed to the rows of rank < limit as a row
-// predicate would narrow it (the second half of where_build: k_q_where_apply, k_q_where_offsets), so it stays in document order;
-// the order itself is a product of its own (d_order).
-//   k_q_order_keys     per tile of QTILE rows, one lane per row and round: path, conversion, status (row_number); the sort key
-//                      agg_key(x, kind), complemented for a descending order; and the tile's OK rows, the AND and the OR of their
-//                      keys -- wave reductions, the four waves joined through LDS (block_and_or), one plain store per tile and value
-//   scan, k_q_order_fold  the exclusive prefix of the tiles' OK rows (k_tw_scan_sums: its total is n_ok) and the AND / OR of all
-//                      keys, which the host reads in its one copy: a digit whose bits are equal in both takes no pass
-//                      (order_pass_mask)
-//   k_q_order_compact  the OK rows to the front in row order -- (key, row) pairs, the input of the first pass --, the others behind
-//                      them in row order, where they stay: they never enter the sort
-//   the sort           the stable radix sort of sj_sort.h with 64-bit keys, over the planned digits only
-//   k_q_order_flag     the row at sorted position p is kept iff p < limit -> the flag of a row predicate; k_q_order_flag_sums its
-//                      tile sums
-//   k_q_order_emit     behind the narrowing: order[p] = pre[row(p)], the row's number in the new selection; its value and status
+// ---- order: the rows ranked by key columns at paths, the first `limit` of them kept (sjhip_order_path, _strings, sjhip_order_paths) ---
+// The order is the one a stable sort by the tuple of up to SJHIP_ORDER_MAX_KEYS columns gives: per column the rows with an OK key
+// ascending by it (a number by agg_key, a string by bytes.Compare on the unescaped key bytes; descending: by the complement), equal
+// keys in row order, the rows without one behind them, tied.  A single-key call is the one-column case.  The selection is narrowed
+// to the rows of rank < limit as a row predicate would narrow it (the second half of where_build: k_q_where_apply,
+// k_q_where_offsets), so it stays in document order; the order itself is a product of its own (d_order).
+// `perm` holds the rows in rank order as far as it is known.  A CLASS is a run of positions of perm whose rows tie on everything
+// looked at so far; the ACTIVE entries are the members of the classes that are not finished, held as (row, position, class) in
+// ascending position, so classes are numbered in position order and each owns a contiguous stretch of positions.  A string key has
+// any length, so a string column is refined most-significant chunk first, STRORD_CHUNK = 7 key bytes per round (strord_chunk,
+// sj_order.h); a numeric column is one round.  The rows without an OK key on a column lie behind the others of their class and tie
+// there, so they still meet the later columns: the sort by class takes mkord_class_key = class << 1 | missing.  Entries leave a
+// column at different rounds, so what the next column works on is not queued but rebuilt from a boundary byte per position,
+// bnd[p] = 1 where a class begins (bnd[n] = 1).
+//   k_q_order_init     all n rows active in row order, one class; perm = the rows; bnd = 1 at 0 and at n
+//   (a single-key call starts elsewhere: no later column waits for its rows without a key, so behind k_q_order_keys they are
+//   parked -- the scan of the tiles' OK rows, then k_q_order_park: the OK rows to the front, active in one class, the others behind
+//   them for good -- and the rounds sort by chunk key alone.  A numeric key has no rounds: k_q_order_park writes the (key, row)
+//   pairs, k_q_order_fold the AND / OR of the keys, and one sort of the OK rows is the order.  Measured, DESIGN.md: the missing bit
+//   costs a single-key call a second sort, and a numeric one the chunk and place kernels, that it has no use for)
+//   column c:
+//   k_q_order_keys     one lane per ACTIVE entry: path, status and, for a numeric column, the sort key agg_key (complemented for
+//                      a descending column); for a string column the tape index of the element, and the tile's longest key.  A column
+//                      behind the first walks only the rows that still tie
+//   round j (a numeric column has one, a string column strord_max_rounds(longest) at most):
+//   k_q_order_chunks   the round's chunk key of every active entry -- the numeric key, or the string's chunk at byte 7 j; 0 for a
+//                      missing row -- and its class key; per tile the AND and the OR of the chunk keys of the OK rows and of the class
+//                      keys (block_and_or: wave reductions joined through LDS, one plain store per tile and value).  Launched for the
+//                      active count of the round before, an upper bound; the count itself is read on the device
+//   k_q_order_fold     one block: the ANDs and ORs over the tiles (round 0 of a column: its longest key as well) -> the host's one
+//                      copy per round: the active count, and the pass plans of the two sorts (order_pass_mask: a digit whose bits
+//                      are equal in all keys takes no pass; a round without missing rows plans no extra digit)
+//   the sort           stable by (class key, chunk key), least significant first: sort_enqueue<u64> over the chunk-key digits that
+//                      vary, then k_q_order_classes gathers the class keys behind the sorted entries and sort_enqueue<u32> takes
+//                      their varying digits (one class without missing rows: skipped)
+//   k_q_order_place    the i-th sorted entry goes to the i-th active position (all members of a class are active or none is, so
+//                      every class lands on its own stretch); a HEAD differs in (class key, chunk key) from the entry in front and
+//                      sets bnd at its position; an entry STAYS in the column iff mkord_stays: it has a key, its new class has company
+//                      and its chunk was full (count 7: a class whose chunk ended is a run of equal keys, finished in row order
+//                      because the sort is stable).  The tile sums of both flags
+//   scan, k_q_order_compact  (string columns) new class numbers (the heads up to and including the entry) and the entries that
+//                      stay, with their positions, into the other buffer -- until nothing is active
+//   between columns:
+//   k_q_order_bounds   the tile sums of bnd and of "not alone in its class", !(bnd[p] && bnd[p + 1])
+//   k_q_order_rebuild  behind their scan: the entries that are not alone, (perm[p], p, the heads up to and including p)
+// Nothing active: the remaining columns are skipped.  Then
+//   k_q_order_flag     the row at rank p is kept iff p < limit -> the flag of a row predicate; k_q_order_flag_sums its tile sums
+//   k_q_order_emit     behind the narrowing: order[p] = pre[row(p)], the row's number in the new selection; its status on column 0
+//                      (the only column every row is evaluated on) and, for sjhip_order_path, its value
+// No atomics anywhere.
+static_assert(ORDER_MAX_KEYS == SJHIP_ORDER_MAX_KEYS, "sj_order.h mirrors include/sjhip.h");
 struct QOrder {
-    int kind;
-    u32 n, desc;
-    Arr<u64> key;                                          // [n] the sort key of the row (0 where the status is not OK)
-    Arr<u8> status;                                        // [n]
-    unsigned long long *tiles_ok, *tiles_and, *tiles_or;   // [tiles] OK rows of the tile -> their exclusive prefix; AND / OR of their keys
-    unsigned long long *totals;                            // [0] the OK rows, [1] the AND, [2] the OR of all their keys
+    u32 n;
+    Arr<u8> status;                                 // [n] the key's status ON THE COLUMN AT WORK
+    Arr<u64> kidx;                                  // [n] there: the sort key of a number, the tape index of a string element (OK rows)
+    Arr<u32> perm;                                  // [n] the rows in rank order
+    Arr<u32> row, pos, cls;                         // [n] each: the active entries of the round
+    Arr<u32> row_out, pos_out, cls_out;             // [n] each: those of the next round (the host swaps the two sets)
+    Arr<u64> chunk;                                 // [n] the round's chunk key of active entry i
+    Arr<u32> ckey;                                  // [n] its class key
+    Arr<u8> flags;                                  // [n] bit 0: head, bit 1: stays active -- of the i-th SORTED entry
+    Arr<u8> bnd;                                    // [n + 1] 1 where a class begins
+    unsigned long long *tiles_ok, *tiles_len;       // [tiles] the OK keys of the tile's entries (-> their prefix); its longest OK key
+    unsigned long long *tiles_kand, *tiles_kor, *tiles_cand, *tiles_cor;  // [tiles] AND / OR of the chunk keys / of the class keys
+    unsigned long long *tiles_head, *tiles_act;     // [tiles] heads / active entries of the tile -> their exclusive prefixes
+    unsigned long long *totals;                     // ORDER_T_*
 };
+// totals: [4] the classes and [5] the active entries (k_q_order_init; k_tw_scan_sums of tiles_head / tiles_act), [6] the column's
+// longest OK key, [8 .. 12) the AND / OR of the round's chunk keys, of its class keys
+static constexpr int ORDER_T_HEADS = 4, ORDER_T_ACTIVE = 5, ORDER_T_LONGEST = 6, ORDER_T_ANDOR = 8, ORDER_T_WORDS = 12;
 // all := the AND of every thread's `all`, any := the OR of every thread's `any`, in thread 0 of a block of QT threads: wave
 // reductions, the waves joined through s_w
 __device__ __forceinline__ void block_and_or(u64 &all, u64 &any, unsigned long long (*s_w)[QT / 64]) {
@@ -1796,140 +1841,6 @@ __device__ __forceinline__ void block_and_or(u64 &all, u64 &any, unsigned long l
     if (tid == 0)
         for (int w = 1; w < QT / 64; w++) all &= s_w[0][w], any |= s_w[1][w];
 }
-__global__ __launch_bounds__(QT) void k_q_order_keys(QView q, QPath pth, QOrder o) {
-    __shared__ unsigned long long s_w[3][QT / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    u64 all = ~0ull, any = 0, ok = 0;
-#pragma unroll 1
-    for (int k = 0; k < QI; k++) {
-        const u32 r = blockIdx.x * QTILE + k * QT + tid;
-        if (r >= o.n) break;
-        u64 x, key = 0;
-        const int st = row_number(q, pth, r, o.kind, &x);
-        if (st == SJHIP_COL_OK) {
-            key = agg_key(x, o.kind);
-            if (o.desc) key = ~key;
-            all &= key;
-            any |= key;
-            ok++;
-        }
-        o.key[r] = key;
-        o.status[r] = (u8)st;
-    }
-    ok = wave_sum(ok);
-    if (lane == 0) s_w[2][wave] = ok;
-    block_and_or(all, any, s_w);
-    if (tid == 0) {
-        for (int w = 1; w < QT / 64; w++) ok += s_w[2][w];
-        o.tiles_ok[blockIdx.x] = ok;
-        o.tiles_and[blockIdx.x] = all;
-        o.tiles_or[blockIdx.x] = any;
-    }
-}
-// one block: the AND and the OR over the tiles (a tile without an OK row holds the identities)
-__global__ __launch_bounds__(QT) void k_q_order_fold(QOrder o, u32 tiles) {
-    __shared__ unsigned long long s_w[2][QT / 64];
-    u64 all = ~0ull, any = 0;
-    for (u32 t = threadIdx.x; t < tiles; t += QT) all &= o.tiles_and[t], any |= o.tiles_or[t];
-    block_and_or(all, any, s_w);
-    if (threadIdx.x == 0) {
-        o.totals[1] = all;
-        o.totals[2] = any;
-    }
-}
-// (tiles_ok has been scanned and totals[0] holds the OK rows.  The rows without a key go to both row buffers: whichever the last
-// pass writes, they lie behind it)
-__global__ __launch_bounds__(QT) void k_q_order_compact(QOrder o, Arr<u64> keys, Arr<u32> rows0, Arr<u32> rows1) {
-    __shared__ unsigned long long s_w[QT / 64];
-    const u32 n = o.n, base = blockIdx.x * QTILE + threadIdx.x * QI, n_ok = (u32)o.totals[0];
-    u32 f[QI], sum = 0;
-#pragma unroll
-    for (int k = 0; k < QI; k++) {
-        f[k] = base + k < n && o.status[base + k] == SJHIP_COL_OK ? 1u : 0u;
-        sum += f[k];
-    }
-    u32 at = (u32)(o.tiles_ok[blockIdx.x] + block_excl_sum(sum, s_w, (int)threadIdx.x, nullptr));
-#pragma unroll
-    for (int k = 0; k < QI; k++) {
-        const u32 i = base + k;
-        if (i >= n) break;
-        if (f[k]) {
-            keys[at] = o.key[i];
-            rows0[at] = i;
-            at++;
-        } else {
-            const u32 p = n_ok + (i - at);  // (i - at: the rows without a key in front of row i)
-            rows0[p] = i;
-            rows1[p] = i;
-        }
-    }
-}
-// rows: the rows in rank order.  One lane per rank: every row is written once
-__global__ __launch_bounds__(256) void k_q_order_flag(Arr<const u32> rows, u32 n, u64 limit, Arr<u8> flag) {
-    const u32 p = blockIdx.x * 256 + threadIdx.x;
-    if (p < n) flag[rows[p]] = p < limit ? 1 : 0;
-}
-__global__ __launch_bounds__(QT) void k_q_order_flag_sums(Arr<u8> flag, u32 n, unsigned long long *tiles) { tile_sums(arr_raw(flag), n, tiles); }
-struct OrderOut {  // the product (d_order), see order_layout
-    Arr<u64> order, values;  // [kept]
-    Arr<u8> status;          // [kept]
-};
-__global__ __launch_bounds__(256) void k_q_order_emit(QOrder o, Arr<const u32> rows, Arr<const u32> pre, u32 kept, OrderOut out) {
-    const u32 p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= kept) return;
-    const u32 row = rows[p];
-    const u8 st = o.status[row];
-    const u64 key = o.key[row];
-    out.order[p] = pre[row];
-    out.values[p] = st == SJHIP_COL_OK ? agg_unkey(o.desc ? ~key : key, o.kind) : 0ull;
-    out.status[p] = st;
-}
-
-// ---- string order: the rows ranked by a string key at a path (sjhip_order_path_strings) ----------------------------------------------
-// The rank is the one of the numeric order with bytes.Compare on the unescaped key bytes.  Keys have any length, so the rank is
-// refined most-significant chunk first, STRORD_CHUNK = 7 key bytes per round (strord_chunk, sj_order.h), each round one stable
-// sort of sj_sort.h.  `perm` holds the rows in rank order as far as it is known: the OK rows in front, the others behind them in
-// row order, where they stay.  A CLASS is a run of positions of perm whose rows have equal key bytes in front of the round's
-// chunk; the ACTIVE entries are the members of the classes that are not finished, held as (row, position, class) in ascending
-// position, so classes are numbered in position order and each owns a contiguous stretch of positions.
-//   k_q_strord_keys     per tile of QTILE rows, one lane per row and round: path, status (element_text_len without conversion), the
-//                       tape index of the string element; the tile's OK rows and its longest OK key, one plain store each
-//   scan, k_q_strord_init  the exclusive prefix of the tiles' OK rows, then the OK rows to the front of perm in row order -- all
-//                       active, positions 0 .. n_ok, one class --, the others behind them in row order
-//   round j:
-//   k_q_strord_chunks   the chunk key at byte 7 j of every active entry (complemented for a descending order) and, per tile, the
-//                       AND and the OR of the chunk keys and of the class numbers.  Launched for the active count of the round
-//                       before, an upper bound; the count itself is read on the device (the host learns it in the round's one copy)
-//   k_q_strord_fold     one block: the ANDs and ORs over the tiles (round 0: the longest key as well) -> the host's one copy per
-//                       round: the active count, and the pass plans (order_pass_mask) of the two sorts
-//   the sort            stable by (class, chunk key), least significant first: sort_enqueue<u64> over the chunk-key digits that
-//                       vary, then k_q_strord_classes gathers the class numbers behind the sorted entries and sort_enqueue<u32>
-//                       takes their varying digits (one class: skipped)
-//   k_q_strord_place    the i-th sorted entry goes to the i-th active position (all members of a class are active or none is, so
-//                       every class lands on its own stretch); an entry is a HEAD iff it begins an old class or its chunk key
-//                       differs from the one in front; it STAYS ACTIVE iff its new class has more than one member and its chunk
-//                       was full (count 7: a class whose chunk ended is a run of equal keys, finished in row order because the
-//                       sort is stable).  The tile sums of both flags
-//   scan, k_q_strord_compact  new class numbers (the heads up to and including the entry) and the active entries compacted, with
-//                       their positions, into the other buffer
-// until nothing is active -- at most strord_max_rounds(longest key) rounds.  No atomics anywhere.
-struct QStrOrd {
-    u32 n, desc;
-    Arr<u8> status;                                 // [n] the key's status
-    Arr<u64> kidx;                                  // [n] tape index of the key's string element (OK rows)
-    Arr<u32> perm;                                  // [n] the rows in rank order
-    Arr<u32> row, pos, cls;                         // [n] each: the active entries of the round
-    Arr<u32> row_out, pos_out, cls_out;             // [n] each: those of the next round (the host swaps the two sets)
-    Arr<u64> chunk;                                 // [n] the round's chunk key of active entry i
-    Arr<u8> flags;                                  // [n] bit 0: head, bit 1: stays active -- of the i-th SORTED entry
-    unsigned long long *tiles_ok, *tiles_len;       // [tiles] OK rows of the tile -> their exclusive prefix; its longest OK key
-    unsigned long long *tiles_kand, *tiles_kor, *tiles_cand, *tiles_cor;  // [tiles] AND / OR of the chunk keys / of the class numbers
-    unsigned long long *tiles_head, *tiles_act;     // [tiles] heads / active entries of the tile -> their exclusive prefixes
-    unsigned long long *totals;                     // STRORD_T_*
-};
-// totals: [0] the OK rows (round 0's active count), [4] the classes and [5] the active entries the last round left (k_tw_scan_sums
-// of tiles_head / tiles_act), [6] the longest OK key, [8 .. 12) the AND / OR of the round's chunk keys, of its class numbers
-static constexpr int STRORD_T_OK = 0, STRORD_T_HEADS = 4, STRORD_T_ACTIVE = 5, STRORD_T_LONGEST = 6, STRORD_T_ANDOR = 8, STRORD_T_WORDS = 12;
 // the maximum of every thread's x in thread 0 of a block of QT threads
 __device__ __forceinline__ u64 block_max(u64 x, unsigned long long *s_w) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1944,37 +1855,67 @@ __device__ __forceinline__ u64 block_max(u64 x, unsigned long long *s_w) {
         for (int w = 1; w < QT / 64; w++) x = s_w[w] > x ? s_w[w] : x;
     return x;
 }
-__global__ __launch_bounds__(QT) void k_q_strord_keys(QView q, QPath pth, QStrOrd o) {
-    __shared__ unsigned long long s_ok[QT / 64], s_len[QT / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    u64 ok = 0, longest = 0;
-#pragma unroll 1
-    for (int k = 0; k < QI; k++) {
-        const u32 r = blockIdx.x * QTILE + k * QT + tid;
-        if (r >= o.n) break;
-        const u64 v = pth.n ? record_find_path(q, pth, r) : row_value(q, r);  // (no keys: the row's own value)
-        u64 len = 0;
-        const int st = v < SJHIP_PATH_NOT_OBJECT ? element_text_len(q, v, false, &len) : path_status(v);
-        if (st == SJHIP_COL_OK) {
-            ok++;
-            longest = len > longest ? len : longest;
-        }
-        o.status[r] = (u8)st;
-        o.kidx[r] = st == SJHIP_COL_OK ? v : 0ull;
-    }
-    ok = wave_sum(ok);
-    if (lane == 0) s_ok[wave] = ok;
-    longest = block_max(longest, s_len);  // (its barrier orders s_ok as well)
-    if (tid == 0) {
-        for (int w = 1; w < QT / 64; w++) ok += s_ok[w];
-        o.tiles_ok[blockIdx.x] = ok;
-        o.tiles_len[blockIdx.x] = longest;
+__global__ __launch_bounds__(256) void k_q_order_init(QOrder o) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x, n = o.n;
+    if (i >= n) return;
+    o.perm[i] = i;
+    o.row[i] = i;
+    o.pos[i] = i;
+    o.cls[i] = 1;
+    o.bnd[i] = i == 0 ? 1 : 0;
+    if (i == 0) {
+        o.bnd[n] = 1;
+        o.totals[ORDER_T_ACTIVE] = n;
     }
 }
-// (tiles_ok has been scanned and totals[STRORD_T_OK] holds the OK rows)
-__global__ __launch_bounds__(QT) void k_q_strord_init(QStrOrd o) {
-    __shared__ unsigned long long s_w[QT / 64];
-    const u32 n = o.n, base = blockIdx.x * QTILE + threadIdx.x * QI, n_ok = (u32)o.totals[STRORD_T_OK];
+// active: where the device keeps the number of active entries (first: column 0, the entries are the n rows); kind:
+// SJHIP_COL_FLOAT / INT / UINT or SJHIP_COL_STRING
+__global__ __launch_bounds__(QT) void k_q_order_keys(QView q, QPath pth, QOrder o, int kind, u32 desc, u32 first,
+                                                     const unsigned long long *active) {
+    __shared__ unsigned long long s_len[QT / 64], s_ok[QT / 64];
+    const int tid = threadIdx.x;
+    const u32 m = first ? o.n : (u32)*active;
+    u64 longest = 0;
+    unsigned long long ok = 0, tot_ok = 0;
+#pragma unroll 1
+    for (int k = 0; k < QI; k++) {
+        const u32 i = blockIdx.x * QTILE + k * QT + tid;
+        if (i >= m) break;
+        const u32 r = first ? i : o.row[i];
+        const u64 v = pth.n ? record_find_path(q, pth, r) : row_value(q, r);  // (no keys: the row's own value)
+        u64 x = 0, key = 0;
+        int st;
+        if (v >= SJHIP_PATH_NOT_OBJECT) st = path_status(v);
+        else if (kind == SJHIP_COL_STRING) {
+            st = element_text_len(q, v, false, &x);
+            if (st == SJHIP_COL_OK) {
+                key = v;
+                longest = x > longest ? x : longest;
+            }
+        } else {
+            st = element_to(q, v, kind, &x);
+            if (st == SJHIP_COL_OK) {
+                key = agg_key(x, kind);
+                if (desc) key = ~key;
+            }
+        }
+        o.status[r] = (u8)st;
+        o.kidx[r] = key;
+        ok += st == SJHIP_COL_OK ? 1u : 0u;
+    }
+    (void)block_excl_sum(ok, s_ok, tid, &tot_ok);
+    longest = block_max(longest, s_len);
+    if (tid == 0) o.tiles_len[blockIdx.x] = longest, o.tiles_ok[blockIdx.x] = tot_ok;
+}
+// (a single-key call; tiles_ok has been scanned into totals[ORDER_T_ACTIVE], the OK rows)  The rows without a key are parked: the OK
+// rows go to the front in row order, the others behind them in row order, where they stay.  Without sort_keys into perm, the OK rows
+// active in one class at the positions 0 .. n_ok: the rounds follow.  With sort_keys -- a numeric key, which one sort orders -- as
+// the (key, row) pairs of its first pass, the others into both row buffers (whichever the last pass writes, they lie behind it),
+// and the tile's AND / OR of the keys for k_q_order_fold
+__global__ __launch_bounds__(QT) void k_q_order_park(QOrder o, Arr<u64> sort_keys, Arr<u32> rows0, Arr<u32> rows1) {
+    __shared__ unsigned long long s_w[QT / 64], s_k[2][QT / 64];
+    const u32 n = o.n, base = blockIdx.x * QTILE + threadIdx.x * QI, n_ok = (u32)o.totals[ORDER_T_ACTIVE];
+    const bool direct = sort_keys ? true : false;
     u32 f[QI], sum = 0;
 #pragma unroll
     for (int k = 0; k < QI; k++) {
@@ -1982,22 +1923,38 @@ __global__ __launch_bounds__(QT) void k_q_strord_init(QStrOrd o) {
         sum += f[k];
     }
     u32 at = (u32)(o.tiles_ok[blockIdx.x] + block_excl_sum(sum, s_w, (int)threadIdx.x, nullptr));
+    u64 all = ~0ull, any = 0;
 #pragma unroll
     for (int k = 0; k < QI; k++) {
         const u32 i = base + k;
         if (i >= n) break;
+        const u32 behind = n_ok + (i - at);  // (i - at: the rows without a key in front of row i)
         if (f[k]) {
-            o.perm[at] = i;
-            o.row[at] = i;
-            o.pos[at] = at;
-            o.cls[at] = 0;
+            if (direct) {
+                const u64 key = o.kidx[i];
+                sort_keys[at] = key;
+                rows0[at] = i;
+                all &= key, any |= key;
+            } else {
+                o.perm[at] = i;
+                o.row[at] = i;
+                o.pos[at] = at;
+                o.cls[at] = 1;
+            }
             at++;
-        } else o.perm[n_ok + (i - at)] = i;  // (i - at: the rows without a key in front of row i)
+        } else if (direct) rows0[behind] = i, rows1[behind] = i;
+        else o.perm[behind] = i;
+    }
+    if (!direct) return;
+    block_and_or(all, any, s_k);
+    if (threadIdx.x == 0) {
+        o.tiles_kand[blockIdx.x] = all, o.tiles_kor[blockIdx.x] = any;
+        o.tiles_cand[blockIdx.x] = ~0ull, o.tiles_cor[blockIdx.x] = 0;
     }
 }
-// active: where the device keeps the round's active count; at: the byte the round's chunks begin at; the first input of the sort
-__global__ __launch_bounds__(QT) void k_q_strord_chunks(QView q, QStrOrd o, const unsigned long long *active, u64 at, Arr<u64> sort_keys,
-                                                       Arr<u32> sort_rows) {
+// at: the byte the round's chunks of a string column begin at; the first input of the sort
+__global__ __launch_bounds__(QT) void k_q_order_chunks(QView q, QOrder o, int kind, u32 desc, const unsigned long long *active, u64 at,
+                                                      Arr<u64> sort_keys, Arr<u32> sort_rows) {
     __shared__ unsigned long long s_k[2][QT / 64], s_c[2][QT / 64];
     const int tid = threadIdx.x;
     const u32 m = (u32)*active;
@@ -2006,14 +1963,24 @@ __global__ __launch_bounds__(QT) void k_q_strord_chunks(QView q, QStrOrd o, cons
     for (int k = 0; k < QI; k++) {
         const u32 i = blockIdx.x * QTILE + k * QT + tid;
         if (i >= m) break;
-        const u64 v = o.kidx[o.row[i]], w = q.tape[v], len = q.tape[v + 1];
-        u64 key = strord_chunk(str_bytes(q, w, len), len, at);
-        if (o.desc) key = ~key;
-        const u64 c = o.cls[i];
+        const u32 r = o.row[i];
+        const bool missing = o.status[r] != SJHIP_COL_OK;
+        u64 key = 0;
+        if (!missing) {
+            key = o.kidx[r];
+            if (kind == SJHIP_COL_STRING) {
+                const u64 w = q.tape[key], len = q.tape[key + 1];
+                key = strord_chunk(str_bytes(q, w, len), len, at);
+                if (desc) key = ~key;
+            }
+            kall &= key, kany |= key;
+        }
+        const u32 c = mkord_class_key(o.cls[i], missing);
         o.chunk[i] = key;
+        o.ckey[i] = c;
         sort_keys[i] = key;
         sort_rows[i] = i;
-        kall &= key, kany |= key, call &= c, cany |= c;
+        call &= c, cany |= c;
     }
     block_and_or(kall, kany, s_k);
     block_and_or(call, cany, s_c);
@@ -2022,9 +1989,9 @@ __global__ __launch_bounds__(QT) void k_q_strord_chunks(QView q, QStrOrd o, cons
         o.tiles_cand[blockIdx.x] = call, o.tiles_cor[blockIdx.x] = cany;
     }
 }
-// one block: the ANDs and ORs over the tiles of k_q_strord_chunks (a tile without an entry holds the identities); key_tiles > 0: the
-// longest key over the tiles of k_q_strord_keys as well
-__global__ __launch_bounds__(QT) void k_q_strord_fold(QStrOrd o, u32 tiles, u32 key_tiles) {
+// one block: the ANDs and ORs over the tiles of k_q_order_chunks (a tile without an entry holds the identities); key_tiles > 0: the
+// longest key over the tiles of k_q_order_keys as well
+__global__ __launch_bounds__(QT) void k_q_order_fold(QOrder o, u32 tiles, u32 key_tiles) {
     __shared__ unsigned long long s_k[2][QT / 64], s_c[2][QT / 64], s_len[QT / 64];
     u64 kall = ~0ull, kany = 0, call = ~0ull, cany = 0, longest = 0;
     for (u32 t = threadIdx.x; t < tiles; t += QT) {
@@ -2036,21 +2003,21 @@ __global__ __launch_bounds__(QT) void k_q_strord_fold(QStrOrd o, u32 tiles, u32 
     block_and_or(call, cany, s_c);
     longest = block_max(longest, s_len);
     if (threadIdx.x == 0) {
-        o.totals[STRORD_T_ANDOR] = kall, o.totals[STRORD_T_ANDOR + 1] = kany;
-        o.totals[STRORD_T_ANDOR + 2] = call, o.totals[STRORD_T_ANDOR + 3] = cany;
-        if (key_tiles) o.totals[STRORD_T_LONGEST] = longest;
+        o.totals[ORDER_T_ANDOR] = kall, o.totals[ORDER_T_ANDOR + 1] = kany;
+        o.totals[ORDER_T_ANDOR + 2] = call, o.totals[ORDER_T_ANDOR + 3] = cany;
+        if (key_tiles) o.totals[ORDER_T_LONGEST] = longest;
     }
 }
-// sorted: the active entries ordered by chunk key -> the input of the sort by class
-__global__ __launch_bounds__(256) void k_q_strord_classes(QStrOrd o, u32 m, Arr<const u32> sorted, Arr<u32> sort_keys, Arr<u32> sort_rows) {
+// sorted: the active entries ordered by chunk key; ckey: their class keys -> the input of the sort by class key
+__global__ __launch_bounds__(256) void k_q_order_classes(Arr<const u32> ckey, u32 m, Arr<const u32> sorted, Arr<u32> sort_keys, Arr<u32> sort_rows) {
     const u32 i = blockIdx.x * 256 + threadIdx.x;
     if (i >= m) return;
     const u32 e = sorted[i];
-    sort_keys[i] = o.cls[e];
+    sort_keys[i] = ckey[e];
     sort_rows[i] = e;
 }
-// sorted: the m active entries ordered by (class, chunk key).  A thread takes QI consecutive ones and looks at both neighbours
-__global__ __launch_bounds__(QT) void k_q_strord_place(QStrOrd o, u32 m, Arr<const u32> sorted) {
+// sorted: the m active entries ordered by (class key, chunk key).  A thread takes QI consecutive ones and looks at both neighbours
+__global__ __launch_bounds__(QT) void k_q_order_place(QOrder o, u32 m, Arr<const u32> sorted, u32 is_string, u32 desc) {
     __shared__ unsigned long long s_w[QT / 64];
     const u32 base = blockIdx.x * QTILE + threadIdx.x * QI;
     u32 e[QI + 2], c[QI + 2];
@@ -2061,7 +2028,7 @@ __global__ __launch_bounds__(QT) void k_q_strord_place(QStrOrd o, u32 m, Arr<con
         const u32 i = base + (u32)k - 1u;  // (base = 0, k = 0: wraps beyond m)
         in[k] = i < m;
         e[k] = in[k] ? sorted[i] : 0u;
-        c[k] = in[k] ? o.cls[e[k]] : 0u;
+        c[k] = in[k] ? o.ckey[e[k]] : 0u;
         key[k] = in[k] ? o.chunk[e[k]] : 0ull;
     }
     unsigned long long heads = 0, active = 0, tot_h = 0, tot_a = 0;
@@ -2070,9 +2037,11 @@ __global__ __launch_bounds__(QT) void k_q_strord_place(QStrOrd o, u32 m, Arr<con
         if (!in[k]) break;
         const bool head = !in[k - 1] || c[k] != c[k - 1] || key[k] != key[k - 1];
         const bool next_head = !in[k + 1] || c[k + 1] != c[k] || key[k + 1] != key[k];
-        const bool stays = !(head && next_head) && strord_chunk_count(key[k], o.desc != 0) == (u32)STRORD_CHUNK;
-        const u32 i = base + (u32)k - 1u;
-        o.perm[o.pos[i]] = o.row[e[k]];
+        const bool full = is_string && strord_chunk_count(key[k], desc != 0) == (u32)STRORD_CHUNK;
+        const bool stays = mkord_stays((c[k] & 1u) != 0, head && next_head, full);
+        const u32 i = base + (u32)k - 1u, p = o.pos[i];
+        o.perm[p] = o.row[e[k]];
+        if (head) o.bnd[p] = 1;
         o.flags[i] = (u8)((head ? 1u : 0u) | (stays ? 2u : 0u));
         heads += head ? 1u : 0u;
         active += stays ? 1u : 0u;
@@ -2083,7 +2052,7 @@ __global__ __launch_bounds__(QT) void k_q_strord_place(QStrOrd o, u32 m, Arr<con
 }
 // (tiles_head and tiles_act have been scanned)  The entries that stay active, in position order, into the next round's arrays: the row, the
 // position it was placed at, and its new class -- the heads up to and including it
-__global__ __launch_bounds__(QT) void k_q_strord_compact(QStrOrd o, u32 m, Arr<const u32> sorted) {
+__global__ __launch_bounds__(QT) void k_q_order_compact(QOrder o, u32 m, Arr<const u32> sorted) {
     __shared__ unsigned long long s_w[QT / 64];
     const u32 base = blockIdx.x * QTILE + threadIdx.x * QI;
     u32 f[QI], heads = 0, active = 0;
@@ -2107,208 +2076,73 @@ __global__ __launch_bounds__(QT) void k_q_strord_compact(QStrOrd o, u32 m, Arr<c
         }
     }
 }
-// behind the narrowing: order[p] = pre[row(p)], the row's number in the new selection, and its status (the keys are not emitted)
-__global__ __launch_bounds__(256) void k_q_strord_emit(QStrOrd o, Arr<const u32> pre, u32 kept, Arr<u64> order, Arr<u8> status) {
-    const u32 p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= kept) return;
-    const u32 row = o.perm[p];
-    order[p] = pre[row];
-    status[p] = o.status[row];
-}
-
-// ---- several keys: the rows ranked by up to SJHIP_ORDER_MAX_KEYS key columns of mixed kinds and directions (sjhip_order_paths) -------
-// The order is the one a stable sort by the tuple gives.  It is refined column by column on the state of the string order: `perm`,
-// the rows in rank order as far as known, and the ACTIVE entries (row, position, class) in ascending position -- the members of the
-// classes of tied rows that are not finished.  Two things differ.  The rows without an OK key on a column are not parked: they
-// lie behind the others of their class and tie there, so they still meet the later columns; the sort by class takes
-// mkord_class_key = class << 1 | missing (sj_order.h).  And entries leave a column at different rounds, so what the next column works
-// on is not queued but rebuilt from a boundary byte per position, bnd[p] = 1 where a class begins (bnd[n] = 1):
-//   k_q_mkord_init     all n rows active in row order, one class; perm = the rows; bnd = 1 at 0 and at n
-//   column c:
-//   k_q_mkord_keys     one lane per ACTIVE entry: path, status and, for a numeric column, the sort key agg_key (complemented for
-//                      a descending column); for a string column the tape index of the element, and the tile's longest key.  A column
-//                      behind the first walks only the rows that still tie
-//   round j (a numeric column has one, a string column strord_max_rounds(longest) at most):
-//   k_q_mkord_chunks   the round's chunk key of every active entry -- the numeric key, or the string's chunk at byte 7 j; 0 for a
-//                      missing row -- and its class key; per tile the AND and the OR of the chunk keys of the OK rows and of the class
-//                      keys.  k_q_strord_fold joins them for the host's one copy per round, which plans both sorts (order_pass_mask:
-//                      a round without missing rows plans no extra digit)
-//   the sort           as in the string order: sort_enqueue<u64> by chunk key, k_q_strord_classes, sort_enqueue<u32> by class key
-//   k_q_mkord_place    the i-th sorted entry goes to the i-th active position; a HEAD differs in (class key, chunk key) from the
-//                      entry in front and sets bnd at its position; an entry STAYS in the column iff mkord_stays.  Then
-//                      k_tw_scan_sums and k_q_strord_compact as they are
-//   between columns:
-//   k_q_mkord_bounds   the tile sums of bnd and of "not alone in its class", !(bnd[p] && bnd[p + 1])
-//   k_q_mkord_rebuild  behind their scan: the entries that are not alone, (perm[p], p, the heads up to and including p)
-// Nothing active: the remaining columns are skipped.  The flags, the narrowing and k_q_strord_emit (with column 0's status, the
-// only one every row has) follow as in the single-key orders.  No atomics anywhere.
-static_assert(ORDER_MAX_KEYS == SJHIP_ORDER_MAX_KEYS, "sj_order.h mirrors include/sjhip.h");
-struct QMkOrd {
-    QStrOrd s;      // n; status, kidx: [n] the status and the key / key element of the row ON THE COLUMN AT WORK; the rest as there
-    Arr<u32> ckey;  // [n] the class key of active entry i
-    Arr<u8> bnd;    // [n + 1] 1 where a class begins
-};
-__global__ __launch_bounds__(256) void k_q_mkord_init(QMkOrd o) {
-    const u32 i = blockIdx.x * 256 + threadIdx.x, n = o.s.n;
-    if (i >= n) return;
-    o.s.perm[i] = i;
-    o.s.row[i] = i;
-    o.s.pos[i] = i;
-    o.s.cls[i] = 1;
-    o.bnd[i] = i == 0 ? 1 : 0;
-    if (i == 0) {
-        o.bnd[n] = 1;
-        o.s.totals[STRORD_T_ACTIVE] = n;
-    }
-}
-// active: where the device keeps the number of active entries; kind: SJHIP_COL_FLOAT / INT / UINT or SJHIP_COL_STRING
-__global__ __launch_bounds__(QT) void k_q_mkord_keys(QView q, QPath pth, QMkOrd o, int kind, u32 desc, const unsigned long long *active) {
-    __shared__ unsigned long long s_len[QT / 64];
-    const int tid = threadIdx.x;
-    const u32 m = (u32)*active;
-    u64 longest = 0;
-#pragma unroll 1
-    for (int k = 0; k < QI; k++) {
-        const u32 i = blockIdx.x * QTILE + k * QT + tid;
-        if (i >= m) break;
-        const u32 r = o.s.row[i];
-        const u64 v = pth.n ? record_find_path(q, pth, r) : row_value(q, r);  // (no keys: the row's own value)
-        u64 x = 0, key = 0;
-        int st;
-        if (v >= SJHIP_PATH_NOT_OBJECT) st = path_status(v);
-        else if (kind == SJHIP_COL_STRING) {
-            st = element_text_len(q, v, false, &x);
-            if (st == SJHIP_COL_OK) {
-                key = v;
-                longest = x > longest ? x : longest;
-            }
-        } else {
-            st = element_to(q, v, kind, &x);
-            if (st == SJHIP_COL_OK) {
-                key = agg_key(x, kind);
-                if (desc) key = ~key;
-            }
-        }
-        o.s.status[r] = (u8)st;
-        o.s.kidx[r] = key;
-    }
-    longest = block_max(longest, s_len);
-    if (tid == 0) o.s.tiles_len[blockIdx.x] = longest;
-}
-// at: the byte the round's chunks of a string column begin at; the first input of the sort
-__global__ __launch_bounds__(QT) void k_q_mkord_chunks(QView q, QMkOrd o, int kind, u32 desc, const unsigned long long *active, u64 at,
-                                                      Arr<u64> sort_keys, Arr<u32> sort_rows) {
-    __shared__ unsigned long long s_k[2][QT / 64], s_c[2][QT / 64];
-    const int tid = threadIdx.x;
-    const u32 m = (u32)*active;
-    u64 kall = ~0ull, kany = 0, call = ~0ull, cany = 0;
-#pragma unroll 1
-    for (int k = 0; k < QI; k++) {
-        const u32 i = blockIdx.x * QTILE + k * QT + tid;
-        if (i >= m) break;
-        const u32 r = o.s.row[i];
-        const bool missing = o.s.status[r] != SJHIP_COL_OK;
-        u64 key = 0;
-        if (!missing) {
-            key = o.s.kidx[r];
-            if (kind == SJHIP_COL_STRING) {
-                const u64 w = q.tape[key], len = q.tape[key + 1];
-                key = strord_chunk(str_bytes(q, w, len), len, at);
-                if (desc) key = ~key;
-            }
-            kall &= key, kany |= key;
-        }
-        const u32 c = mkord_class_key(o.s.cls[i], missing);
-        o.s.chunk[i] = key;
-        o.ckey[i] = c;
-        sort_keys[i] = key;
-        sort_rows[i] = i;
-        call &= c, cany |= c;
-    }
-    block_and_or(kall, kany, s_k);
-    block_and_or(call, cany, s_c);
-    if (tid == 0) {
-        o.s.tiles_kand[blockIdx.x] = kall, o.s.tiles_kor[blockIdx.x] = kany;
-        o.s.tiles_cand[blockIdx.x] = call, o.s.tiles_cor[blockIdx.x] = cany;
-    }
-}
-// sorted: the m active entries ordered by (class key, chunk key).  A thread takes QI consecutive ones and looks at both neighbours
-__global__ __launch_bounds__(QT) void k_q_mkord_place(QMkOrd o, u32 m, Arr<const u32> sorted, u32 is_string, u32 desc) {
-    __shared__ unsigned long long s_w[QT / 64];
-    const u32 base = blockIdx.x * QTILE + threadIdx.x * QI;
-    u32 e[QI + 2], c[QI + 2];
-    u64 key[QI + 2];
-    bool in[QI + 2];
+// b: bnd at the thread's QI positions from `base` and at the one behind them (1 beyond n); of its positions, the classes that begin
+// there and those that are not alone in their class
+__device__ __forceinline__ void order_bnd_counts(const QOrder &o, u32 base, u32 (&b)[QI + 1], u32 &heads, u32 &active) {
 #pragma unroll
-    for (int k = 0; k < QI + 2; k++) {
-        const u32 i = base + (u32)k - 1u;  // (base = 0, k = 0: wraps beyond m)
-        in[k] = i < m;
-        e[k] = in[k] ? sorted[i] : 0u;
-        c[k] = in[k] ? o.ckey[e[k]] : 0u;
-        key[k] = in[k] ? o.s.chunk[e[k]] : 0ull;
-    }
-    unsigned long long heads = 0, active = 0, tot_h = 0, tot_a = 0;
-#pragma unroll
-    for (int k = 1; k <= QI; k++) {
-        if (!in[k]) break;
-        const bool head = !in[k - 1] || c[k] != c[k - 1] || key[k] != key[k - 1];
-        const bool next_head = !in[k + 1] || c[k + 1] != c[k] || key[k + 1] != key[k];
-        const bool full = is_string && strord_chunk_count(key[k], desc != 0) == (u32)STRORD_CHUNK;
-        const bool stays = mkord_stays((c[k] & 1u) != 0, head && next_head, full);
-        const u32 i = base + (u32)k - 1u, p = o.s.pos[i];
-        o.s.perm[p] = o.s.row[e[k]];
-        if (head) o.bnd[p] = 1;
-        o.s.flags[i] = (u8)((head ? 1u : 0u) | (stays ? 2u : 0u));
-        heads += head ? 1u : 0u;
-        active += stays ? 1u : 0u;
-    }
-    (void)block_excl_sum(heads, s_w, (int)threadIdx.x, &tot_h);
-    (void)block_excl_sum(active, s_w, (int)threadIdx.x, &tot_a);
-    if (threadIdx.x == 0) o.s.tiles_head[blockIdx.x] = tot_h, o.s.tiles_act[blockIdx.x] = tot_a;
-}
-// over the n positions: the classes that begin in the tile, and its positions that are not alone in their class
-__global__ __launch_bounds__(QT) void k_q_mkord_bounds(QMkOrd o) {
-    __shared__ unsigned long long s_w[QT / 64];
-    const u32 n = o.s.n, base = blockIdx.x * QTILE + threadIdx.x * QI;
-    unsigned long long heads = 0, active = 0, tot_h = 0, tot_a = 0;
+    for (int k = 0; k <= QI; k++) b[k] = base + k <= o.n ? o.bnd[base + k] : 1u;
+    heads = 0, active = 0;
 #pragma unroll
     for (int k = 0; k < QI; k++) {
-        const u32 p = base + k;
-        if (p >= n) break;
-        const u32 b = o.bnd[p];
-        heads += b;
-        active += b && o.bnd[p + 1] ? 0u : 1u;
-    }
-    (void)block_excl_sum(heads, s_w, (int)threadIdx.x, &tot_h);
-    (void)block_excl_sum(active, s_w, (int)threadIdx.x, &tot_a);
-    if (threadIdx.x == 0) o.s.tiles_head[blockIdx.x] = tot_h, o.s.tiles_act[blockIdx.x] = tot_a;
-}
-// (tiles_head and tiles_act have been scanned)  The next column's active entries, in position order
-__global__ __launch_bounds__(QT) void k_q_mkord_rebuild(QMkOrd o) {
-    __shared__ unsigned long long s_w[QT / 64];
-    const u32 n = o.s.n, base = blockIdx.x * QTILE + threadIdx.x * QI;
-    u32 b[QI + 1], heads = 0, active = 0;
-#pragma unroll
-    for (int k = 0; k <= QI; k++) b[k] = base + k <= n ? o.bnd[base + k] : 1u;
-#pragma unroll
-    for (int k = 0; k < QI; k++) {
-        if (base + k >= n) break;
+        if (base + k >= o.n) break;
         heads += b[k];
         active += b[k] && b[k + 1] ? 0u : 1u;
     }
-    u32 cl = (u32)(o.s.tiles_head[blockIdx.x] + block_excl_sum(heads, s_w, (int)threadIdx.x, nullptr));
-    u32 at = (u32)(o.s.tiles_act[blockIdx.x] + block_excl_sum(active, s_w, (int)threadIdx.x, nullptr));
+}
+// over the n positions: the classes that begin in the tile, and its positions that are not alone in their class
+__global__ __launch_bounds__(QT) void k_q_order_bounds(QOrder o) {
+    __shared__ unsigned long long s_w[QT / 64];
+    u32 b[QI + 1], heads, active;
+    order_bnd_counts(o, blockIdx.x * QTILE + threadIdx.x * QI, b, heads, active);
+    unsigned long long tot_h = 0, tot_a = 0;
+    (void)block_excl_sum(heads, s_w, (int)threadIdx.x, &tot_h);
+    (void)block_excl_sum(active, s_w, (int)threadIdx.x, &tot_a);
+    if (threadIdx.x == 0) o.tiles_head[blockIdx.x] = tot_h, o.tiles_act[blockIdx.x] = tot_a;
+}
+// (tiles_head and tiles_act have been scanned)  The next column's active entries, in position order
+__global__ __launch_bounds__(QT) void k_q_order_rebuild(QOrder o) {
+    __shared__ unsigned long long s_w[QT / 64];
+    const u32 n = o.n, base = blockIdx.x * QTILE + threadIdx.x * QI;
+    u32 b[QI + 1], heads, active;
+    order_bnd_counts(o, base, b, heads, active);
+    u32 cl = (u32)(o.tiles_head[blockIdx.x] + block_excl_sum(heads, s_w, (int)threadIdx.x, nullptr));
+    u32 at = (u32)(o.tiles_act[blockIdx.x] + block_excl_sum(active, s_w, (int)threadIdx.x, nullptr));
 #pragma unroll
     for (int k = 0; k < QI; k++) {
         const u32 p = base + k;
         if (p >= n) break;
         cl += b[k];
         if (!(b[k] && b[k + 1])) {
-            o.s.row[at] = o.s.perm[p];
-            o.s.pos[at] = p;
-            o.s.cls[at] = cl;
+            o.row[at] = o.perm[p];
+            o.pos[at] = p;
+            o.cls[at] = cl;
             at++;
         }
+    }
+}
+// rows: the rows in rank order.  One lane per rank: every row is written once
+__global__ __launch_bounds__(256) void k_q_order_flag(Arr<const u32> rows, u32 n, u64 limit, Arr<u8> flag) {
+    const u32 p = blockIdx.x * 256 + threadIdx.x;
+    if (p < n) flag[rows[p]] = p < limit ? 1 : 0;
+}
+__global__ __launch_bounds__(QT) void k_q_order_flag_sums(Arr<u8> flag, u32 n, unsigned long long *tiles) { tile_sums(arr_raw(flag), n, tiles); }
+struct OrderOut {  // the product (d_order), see order_layout
+    Arr<u64> order, values;  // [kept]
+    Arr<u8> status;          // [kept]
+};
+// behind the narrowing: order[p] = pre[row(p)], the row's number in the new selection, and its status.  keys: null, or the sort
+// keys of the rows' numbers of `kind` (desc: complemented) -> values[p], 0 where the status is not OK
+__global__ __launch_bounds__(256) void k_q_order_emit(Arr<const u32> rows, Arr<const u8> status, Arr<const u64> keys, int kind, u32 desc,
+                                                      Arr<const u32> pre, u32 kept, OrderOut out) {
+    const u32 p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= kept) return;
+    const u32 row = rows[p];
+    const u8 st = status[row];
+    out.order[p] = pre[row];
+    out.status[p] = st;
+    if (keys) {
+        const u64 key = keys[row];
+        out.values[p] = st == SJHIP_COL_OK ? agg_unkey(desc ? ~key : key, kind) : 0ull;
     }
 }
 
@@ -4413,33 +4247,52 @@ int sjhip_fetch_group_aggregates_at(sjhip_ctx *ctx, uint32_t val, uint64_t *coun
 }
 
 // ---- order ---------------------------------------------------------------------------------------------------------------------------
-// sjhip_order_path works on the whole result of one context (a sharded one is refused: the ranks of shards would have to be merged).
-// The work arrays of all its kernels (OrderWork) lie in d_kat, laid out once for the row count, the arrays of the narrowing
-// (where_layout) behind them; the product (OrderOut) lies in d_order, reserved when the narrowing is through.  One host round trip
-// in the middle -- the OK rows, the AND and the OR of the keys: the pass plan --, the wait of the narrowing, one wait at the end.
+// sjhip_order_path, sjhip_order_path_strings and sjhip_order_paths work on the whole result of one context (a sharded one is refused:
+// the ranks of shards would have to be merged) and differ in their argument checks, in the columns they hand to order_build and in
+// the kind of the product.  The work arrays of all kernels (OrderWork) lie in d_kat, laid out once for the row count -- every round
+// works on a prefix of them --, the arrays of the narrowing (where_layout) behind them; the product (OrderOut) lies in d_order,
+// reserved when the narrowing is through.  One host round trip per round -- the active count and the ANDs / ORs that plan the
+// round's two sorts; a string column's first also brings its longest key, which bounds its rounds --, the wait of the narrowing,
+// one wait at the end.
+struct OrderCol {
+    QView q;  // (the keys of the column's path are the view's)
+    QPath pth;
+    int kind;
+    u32 desc;
+};
 struct OrderWork {
-    unsigned long long *totals;
     QOrder o;
-    SortWork<u64> sort;
+    u8 *status0, *status_c;  // [n] each: column 0's statuses, and those of the column at work behind it
+    SortWork<u64> sort;      // by chunk key
+    SortWork<u32> csort;     // by class key
     QWhere w;
     WhereNew nw;
     unsigned long long *w_totals;
 };
-static size_t order_work_layout(Carve c, const sjhip_ctx *ctx, uint32_t n, int kind, u32 desc, OrderWork *w) {
+static size_t order_work_layout(Carve c, const sjhip_ctx *ctx, uint32_t n, OrderWork *w) {
     const u32 tiles = (n + QTILE - 1) / QTILE;
-    w->totals = c.take<unsigned long long>(32);
-    w->o.kind = kind;
-    w->o.n = n;
-    w->o.desc = desc;
-    w->o.totals = w->totals;
-    u64 *const key = c.take<u64>(n);
-    u8 *const status = c.take<u8>(n);
-    w->o.key = SJ_ARR(key, n, A_ORDER_ROW);
-    w->o.status = SJ_ARR(status, n, A_ORDER_ROW);
-    w->o.tiles_ok = c.take<unsigned long long>(tiles);
-    w->o.tiles_and = c.take<unsigned long long>(tiles);
-    w->o.tiles_or = c.take<unsigned long long>(tiles);
+    QOrder &o = w->o;
+    o.totals = c.take<unsigned long long>(32);
+    o.n = n;
+    w->status0 = c.take<u8>(n), w->status_c = c.take<u8>(n);
+    u8 *const flags = c.take<u8>(n), *const bnd = c.take<u8>((size_t)n + 1);
+    u64 *const kidx = c.take<u64>(n), *const chunk = c.take<u64>(n);
+    u32 *const perm = c.take<u32>(n), *const ckey = c.take<u32>(n);
+    u32 *const row = c.take<u32>(n), *const pos = c.take<u32>(n), *const cls = c.take<u32>(n);
+    u32 *const row_out = c.take<u32>(n), *const pos_out = c.take<u32>(n), *const cls_out = c.take<u32>(n);
+    o.status = SJ_ARR(w->status0, n, A_ORDER_ROW);
+    o.kidx = SJ_ARR(kidx, n, A_ORDER_ROW);
+    o.perm = SJ_ARR(perm, n, A_SORT);
+    o.flags = SJ_ARR(flags, n, A_ORDER_ACT);
+    o.chunk = SJ_ARR(chunk, n, A_ORDER_ACT);
+    o.ckey = SJ_ARR(ckey, n, A_ORDER_ACT);
+    o.row = SJ_ARR(row, n, A_ORDER_ACT), o.pos = SJ_ARR(pos, n, A_ORDER_ACT), o.cls = SJ_ARR(cls, n, A_ORDER_ACT);
+    o.row_out = SJ_ARR(row_out, n, A_ORDER_ACT), o.pos_out = SJ_ARR(pos_out, n, A_ORDER_ACT), o.cls_out = SJ_ARR(cls_out, n, A_ORDER_ACT);
+    o.bnd = SJ_ARR(bnd, (size_t)n + 1, A_ORDER_BND);
+    unsigned long long **const per_tile[] = {&o.tiles_ok, &o.tiles_len, &o.tiles_kand, &o.tiles_kor, &o.tiles_cand, &o.tiles_cor, &o.tiles_head, &o.tiles_act};
+    for (unsigned long long **t : per_tile) *t = c.take<unsigned long long>(tiles);
     sort_carve(c, n, &w->sort);
+    sort_carve(c, n, &w->csort);
     (void)(c.used = where_layout(c, ctx, n, &w->w, &w->nw, &w->w_totals));
     return c.used;
 }
@@ -4455,38 +4308,112 @@ static size_t order_layout(Carve c, size_t rows, int kind, OrderArrays *o) {
     o->status = c.take<u8>(rows);
     return c.used;
 }
-// behind the checks of sjhip_order_path: q is the view of the n > 0 rows in force
-static int order_build(sjhip_ctx *ctx, const QView &q, const QPath &pth, const uint8_t *keys, size_t klen, uint32_t n, int kind, u32 desc,
-                       uint64_t limit, size_t *records, size_t *rows) {
+// behind the checks of the order call `fn`: cols[c].q is the view of the n > 0 rows in force; kind: the product's -- that of the
+// one numeric column of sjhip_order_path, whose values are emitted, SJHIP_COL_STRING or ORDER_KIND_MULTI
+static int order_build(sjhip_ctx *ctx, const char *fn, const OrderCol *cols, uint32_t n_cols, int kind, const uint8_t *keys, size_t klen,
+                       uint32_t n, uint64_t limit, size_t *records, size_t *rows) {
     OrderWork w;
-    int rc = reserve_layout(ctx, ctx->d_kat, [&](Carve c) { return order_work_layout(c, ctx, n, kind, desc, &w); });
+    int rc = reserve_layout(ctx, ctx->d_kat, [&](Carve c) { return order_work_layout(c, ctx, n, &w); });
     if (rc) return rc;
     hipStream_t st = ctx->stream;
     const u32 tiles = (n + QTILE - 1) / QTILE;
     const dim3 per_row((n + 255) / 256), per_tile(tiles), b256(256), bqt(QT), one(1), wide(1024);
     unsigned long long *const none = nullptr;
+    QOrder &o = w.o;
     u64 *const keys0 = w.sort.keys[0];
-    u32 *const rows0 = w.sort.rows[0], *const rows1 = w.sort.rows[1];
-    HIPCHK(hipMemsetAsync(w.totals, 0, 256, st), "order totals memset");
-    hipLaunchKernelGGL(k_q_order_keys, per_tile, bqt, 0, st, q, pth, w.o);
-    hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.o.tiles_ok, none, none, tiles, w.totals);
-    hipLaunchKernelGGL(k_q_order_fold, one, b256, 0, st, w.o, tiles);
-    hipLaunchKernelGGL(k_q_order_compact, per_tile, bqt, 0, st, w.o, SJ_ARR(keys0, n, A_SORT), SJ_ARR(rows0, n, A_SORT), SJ_ARR(rows1, n, A_SORT));
-    HIPCHK(hipGetLastError(), "order launch");
-    unsigned long long *const h = (unsigned long long *)(ctx->h_scratch + 512);
-    HIPCHK(hipMemcpyAsync(h, w.totals, 24, hipMemcpyDeviceToHost, st), "D2H order totals");
-    HIPCHK(hipStreamSynchronize(st), "order sync");
-    rc = query_bounds_check(ctx);
-    if (rc) return rc;
-    // the rows with a key ordered by it, stably (fewer than two: no pass)
-    const u32 n_ok = (u32)h[0], mask = n_ok > 1 ? order_pass_mask(h[1], h[2]) : 0u;
-    const u32 *const ranked = w.sort.rows[sort_enqueue(st, n_ok, n, mask, true, w.sort)];
+    u32 *const rows0 = w.sort.rows[0], *const ckeys0 = w.csort.keys[0], *const crows0 = w.csort.rows[0];
+    const unsigned long long *const active = o.totals + ORDER_T_ACTIVE;
+    // a single-key call parks the rows without a key in front of its rounds (k_q_order_park), and a numeric key needs no rounds:
+    // one sort of the OK rows orders it
+    const bool single = n_cols == 1, direct = single && cols[0].kind != SJHIP_COL_STRING;
+    const u32 *ranked = arr_raw(o.perm);
+    HIPCHK(hipMemsetAsync(o.totals, 0, 256, st), "order totals memset");
+    if (!single) hipLaunchKernelGGL(k_q_order_init, per_row, b256, 0, st, o);
+    unsigned long long *const h = (unsigned long long *)(ctx->h_scratch + 512), *const h_left = (unsigned long long *)(ctx->h_scratch + 1024);
+    for (uint32_t c = 0; c < n_cols; c++) h_left[c] = 0;
+    u64 left_bound[ORDER_MAX_KEYS] = {};
+    bool tied = true;  // rows still tie: the next column has work
+    for (uint32_t c = 0; c < n_cols && tied; c++) {
+        const OrderCol &col = cols[c];
+        const bool is_string = col.kind == SJHIP_COL_STRING;
+        if (c > 0) {  // the entries that are not alone in their class, from the boundaries
+            hipLaunchKernelGGL(k_q_order_bounds, per_tile, bqt, 0, st, o);
+            hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, o.tiles_head, o.tiles_act, none, tiles, o.totals + ORDER_T_HEADS);
+            hipLaunchKernelGGL(k_q_order_rebuild, per_tile, bqt, 0, st, o);
+            o.status = SJ_ARR(w.status_c, n, A_ORDER_ROW);
+        }
+        hipLaunchKernelGGL(k_q_order_keys, per_tile, bqt, 0, st, col.q, col.pth, o, col.kind, col.desc, c == 0 ? 1u : 0u, active);
+        if (single) {
+            u64 *const pairs = direct ? keys0 : nullptr;
+            u32 *const rows1 = w.sort.rows[1];
+            hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, o.tiles_ok, none, none, tiles, o.totals + ORDER_T_ACTIVE);
+            hipLaunchKernelGGL(k_q_order_park, per_tile, bqt, 0, st, o, SJ_ARR(pairs, n, A_SORT), SJ_ARR(rows0, n, A_SORT), SJ_ARR(rows1, n, A_SORT));
+        }
+        if (direct) {  // the pass plan from the AND and the OR of the keys; fewer than two OK rows: no pass
+            hipLaunchKernelGGL(k_q_order_fold, one, bqt, 0, st, o, tiles, 0u);
+            HIPCHK(hipGetLastError(), "order launch");
+            HIPCHK(hipMemcpyAsync(h, o.totals, ORDER_T_WORDS * 8, hipMemcpyDeviceToHost, st), "D2H order totals");
+            HIPCHK(hipStreamSynchronize(st), "order sync");
+            rc = query_bounds_check(ctx);
+            if (rc) return rc;
+            const u32 n_ok = (u32)h[ORDER_T_ACTIVE], mask = n_ok > 1 ? order_pass_mask(h[ORDER_T_ANDOR], h[ORDER_T_ANDOR + 1]) : 0u;
+            ranked = w.sort.rows[sort_enqueue(st, n_ok, n, mask, true, w.sort)];
+            break;
+        }
+        u64 bound = 1;  // of the column's rounds: a string column's is known after its first copy
+        u32 m_max = n;  // the round's active entries are at most this many
+        for (u64 round = 0;; round++) {
+            // the round's chunk keys, and its one round trip
+            const u32 ctiles = (m_max + QTILE - 1) / QTILE;
+            hipLaunchKernelGGL(k_q_order_chunks, dim3(ctiles), bqt, 0, st, col.q, o, col.kind, col.desc, active, round * (u64)STRORD_CHUNK,
+                               SJ_ARR(keys0, n, A_SORT), SJ_ARR(rows0, n, A_SORT));
+            hipLaunchKernelGGL(k_q_order_fold, one, bqt, 0, st, o, ctiles, round == 0 ? tiles : 0u);
+            HIPCHK(hipGetLastError(), "order chunk launch");
+            HIPCHK(hipMemcpyAsync(h, o.totals, ORDER_T_WORDS * 8, hipMemcpyDeviceToHost, st), "D2H order totals");
+            HIPCHK(hipStreamSynchronize(st), "order sync");
+            rc = query_bounds_check(ctx);
+            if (rc) return rc;
+            if (round == 0 && is_string) bound = strord_max_rounds(h[ORDER_T_LONGEST]);
+            const u32 m = (u32)h[ORDER_T_ACTIVE];
+            if (m < 2) {  // (a class has two members at least: nothing is active)
+                tied = round > 0;  // (behind the column's first round the classes it finished may still hold ties)
+                break;
+            }
+            // stable by (class key, chunk key): the chunk keys first -- of the OK rows; without one, no digit --, then the class keys
+            const u64 kand = h[ORDER_T_ANDOR], kor = h[ORDER_T_ANDOR + 1];
+            const u32 kmask = (kand & ~kor) ? 0u : order_pass_mask(kand, kor);
+            const u32 cmask = order_pass_mask(h[ORDER_T_ANDOR + 2], h[ORDER_T_ANDOR + 3]);
+            const u32 *sorted = w.sort.rows[sort_enqueue(st, m, n, kmask, true, w.sort)];
+            const dim3 per_entry((m + 255) / 256), per_etile((m + QTILE - 1) / QTILE);
+            if (cmask) {
+                hipLaunchKernelGGL(k_q_order_classes, per_entry, b256, 0, st, o.ckey, m, SJ_ARR(sorted, n, A_SORT), SJ_ARR(ckeys0, n, A_SORT),
+                                   SJ_ARR(crows0, n, A_SORT));
+                sorted = w.csort.rows[sort_enqueue(st, m, n, cmask, true, w.csort)];
+            }
+            // place, mark; a string column renumbers and compacts what stays in it
+            hipLaunchKernelGGL(k_q_order_place, per_etile, bqt, 0, st, o, m, SJ_ARR(sorted, n, A_SORT), is_string ? 1u : 0u, col.desc);
+            if (is_string) {
+                hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, o.tiles_head, o.tiles_act, none, per_etile.x, o.totals + ORDER_T_HEADS);
+                hipLaunchKernelGGL(k_q_order_compact, per_etile, bqt, 0, st, o, m, SJ_ARR(sorted, n, A_SORT));
+                std::swap(o.row, o.row_out), std::swap(o.pos, o.pos_out), std::swap(o.cls, o.cls_out);
+            }
+            HIPCHK(hipGetLastError(), "order round launch");
+            m_max = m;
+            if (round + 1 >= bound) {  // the column's last round: what a string column left active (nothing) is looked at with the emit's wait
+                if (is_string) {
+                    HIPCHK(hipMemcpyAsync(h_left + c, o.totals + ORDER_T_ACTIVE, 8, hipMemcpyDeviceToHost, st), "D2H order rest");
+                    left_bound[c] = bound;
+                }
+                break;
+            }
+        }
+    }
     // rank, flag, narrow: the first `kept` ranks stay
     const size_t kept = limit == 0 || limit >= n ? (size_t)n : (size_t)limit;
     hipLaunchKernelGGL(k_q_order_flag, per_row, b256, 0, st, SJ_ARR(ranked, n, A_SORT), n, (u64)kept, w.w.flag);
     hipLaunchKernelGGL(k_q_order_flag_sums, per_tile, bqt, 0, st, w.w.flag, n, w.w.tiles);
     hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.w.tiles, none, none, tiles, none);
-    HIPCHK(hipGetLastError(), "order sort launch");
+    HIPCHK(hipGetLastError(), "order flag launch");
     const std::vector<sjhip_ctx *> parts(1, ctx);
     rc = where_narrow(ctx, parts, keys, klen, &NO_VALUE, 0, std::vector<QWhere>(1, w.w), std::vector<WhereNew>(1, w.nw),
                       std::vector<size_t>(1, kept), records, rows);
@@ -4498,34 +4425,48 @@ static int order_build(sjhip_ctx *ctx, const QView &q, const QPath &pth, const u
     out.order = SJ_ARR(a.order, kept, A_ORDER_OUT);
     out.values = SJ_ARR(a.values, kept, A_ORDER_OUT);
     out.status = SJ_ARR(a.status, kept, A_ORDER_OUT);
+    // (column 0's status: the only column every row is evaluated on.  A product with values has one numeric column: kidx holds its keys)
+    const u8 *const status = w.status0;
+    const u64 *const values_of = a.values ? arr_raw(o.kidx) : nullptr;
     const u32 *const pre = arr_raw(w.w.pre);
-    hipLaunchKernelGGL(k_q_order_emit, dim3(((u32)kept + 255) / 256), b256, 0, st, w.o, SJ_ARR(ranked, n, A_SORT),
-                       SJ_ARR(pre, n, A_WHERE_PRE), (u32)kept, out);
+    hipLaunchKernelGGL(k_q_order_emit, dim3(((u32)kept + 255) / 256), b256, 0, st, SJ_ARR(ranked, n, A_SORT), SJ_ARR(status, n, A_ORDER_ROW),
+                       SJ_ARR(values_of, n, A_ORDER_ROW), cols[0].kind, cols[0].desc, SJ_ARR(pre, n, A_WHERE_PRE), (u32)kept, out);
     HIPCHK(hipGetLastError(), "order emit launch");
     HIPCHK(hipStreamSynchronize(st), "order emit sync");
     rc = query_bounds_check(ctx);
     if (rc) return rc;
+    for (uint32_t c = 0; c < n_cols; c++)
+        if (h_left[c]) {
+            if (single)
+                ctx_set_error(ctx, "%s: %llu rows are still unordered after %llu rounds, the bound of the longest key (%llu bytes)", fn, h_left[c],
+                              (unsigned long long)left_bound[c], (unsigned long long)left_bound[c] * STRORD_CHUNK - 1);
+            else
+                ctx_set_error(ctx, "%s: column %u: %llu rows are still unordered after %llu rounds, the bound of its longest key", fn, c, h_left[c],
+                              (unsigned long long)left_bound[c]);
+            return SJHIP_ERR_HIP;
+        }
     return published(ctx, ctx->res.publish(&ResultState::order, {kept, kind}));
 }
 
-int sjhip_order_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int kind, uint32_t flags,
-                     uint64_t limit, size_t *records, size_t *rows) {
-    if (!ctx) return SJHIP_ERR_ARG;
-    if (!records || !rows) {
-        ctx_set_error(ctx, "sjhip_order_path: a null size pointer");
-        return SJHIP_ERR_ARG;
-    }
-    if (kind != SJHIP_COL_FLOAT && kind != SJHIP_COL_INT && kind != SJHIP_COL_UINT) {
-        ctx_set_error(ctx, "sjhip_order_path: key kind %d is not SJHIP_COL_FLOAT, SJHIP_COL_INT or SJHIP_COL_UINT", kind);
-        return SJHIP_ERR_ARG;
-    }
-    if (flags & ~SJHIP_ORDER_DESC) {
-        ctx_set_error(ctx, "sjhip_order_path: unknown flag bits 0x%x", flags & ~SJHIP_ORDER_DESC);
-        return SJHIP_ERR_ARG;
-    }
-    WholePath k = {keys, key_lens, n_keys};
+// two argument checks of the order call `fn`, made where each call made them: the size pointers; the flags of a column (col < 0: of
+// the call's only one)
+static int order_sizes_check(sjhip_ctx *ctx, const char *fn, const size_t *records, const size_t *rows) {
+    if (records && rows) return SJHIP_OK;
+    ctx_set_error(ctx, "%s: a null size pointer", fn);
+    return SJHIP_ERR_ARG;
+}
+static int order_flags_check(sjhip_ctx *ctx, const char *fn, int col, uint32_t flags) {
+    if (!(flags & ~SJHIP_ORDER_DESC)) return SJHIP_OK;
+    if (col < 0) ctx_set_error(ctx, "%s: unknown flag bits 0x%x", fn, flags & ~SJHIP_ORDER_DESC);
+    else ctx_set_error(ctx, "%s: column %d: unknown flag bits 0x%x", fn, col, flags & ~SJHIP_ORDER_DESC);
+    return SJHIP_ERR_ARG;
+}
+// behind the argument checks of the order call `fn`: the n_cols paths made and viewed (whole_entry), the last order given up, the
+// empty selection, the build (flags null: all ascending)
+static int order_entry(sjhip_ctx *ctx, const char *fn, WholePath *k, const int *kinds, const uint32_t *flags, uint32_t n_cols, int kind,
+                       uint64_t limit, size_t *records, size_t *rows) {
     uint32_t n = 0;
-    int rc = whole_entry(ctx, "sjhip_order_path", "the ranks of shards are not merged", &k, 1, &n);
+    int rc = whole_entry(ctx, fn, "the ranks of shards are not merged", k, (int)n_cols, &n);
     if (rc) return rc;
     // ---- nothing was touched up to here; from here on the last order is gone ----
     ctx->res.order.begin();
@@ -4534,343 +4475,45 @@ int sjhip_order_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_le
         *records = ctx->res.rows.sizes().records, *rows = 0;
         return published(ctx, ctx->res.publish(&ResultState::order, {0, kind}));
     }
-    rc = order_build(ctx, k.q, k.pth, k.keys, k.klen, n, kind, flags & SJHIP_ORDER_DESC, limit, records, rows);
+    OrderCol cols[ORDER_MAX_KEYS];
+    for (uint32_t c = 0; c < n_cols; c++) cols[c] = {k[c].q, k[c].pth, kinds[c], flags ? flags[c] & SJHIP_ORDER_DESC : 0u};
+    rc = order_build(ctx, fn, cols, n_cols, kind, k[0].keys, k[0].klen, n, limit, records, rows);
     if (rc) {  // half-built: the old selection may have been written over
         ctx->res.rows.begin();
         char why[sizeof ctx->err];
         snprintf(why, sizeof why, "%s", ctx->err);
-        ctx_set_error(ctx, "sjhip_order_path failed and the row selection was given up: %.180s", why);
+        ctx_set_error(ctx, "%s failed and the row selection was given up: %.170s", fn, why);
     }
     return rc;
 }
 
-// ---- string order --------------------------------------------------------------------------------------------------------------------
-// sjhip_order_path_strings is sjhip_order_path with the sort replaced by the rounds of the k_q_strord_* kernels.  The work arrays
-// (StrOrdWork) lie in d_kat, laid out once for the row count -- every round works on a prefix of them --, the arrays of the
-// narrowing behind them; the product is the order's, without values.  One host round trip per round: the active count and the
-// ANDs / ORs that plan the round's two sorts (round 0's also brings the OK rows and the longest key, which bounds the rounds).
-struct StrOrdWork {
-    QStrOrd o;
-    SortWork<u64> sort;   // by chunk key
-    SortWork<u32> csort;  // by class
-    QWhere w;
-    WhereNew nw;
-    unsigned long long *w_totals;
-};
-static size_t strord_work_layout(Carve c, const sjhip_ctx *ctx, uint32_t n, u32 desc, StrOrdWork *w) {
-    const u32 tiles = (n + QTILE - 1) / QTILE;
-    QStrOrd &o = w->o;
-    o.totals = c.take<unsigned long long>(32);
-    o.n = n;
-    o.desc = desc;
-    u8 *const status = c.take<u8>(n), *const flags = c.take<u8>(n);
-    u64 *const kidx = c.take<u64>(n), *const chunk = c.take<u64>(n);
-    u32 *const perm = c.take<u32>(n);
-    u32 *const row = c.take<u32>(n), *const pos = c.take<u32>(n), *const cls = c.take<u32>(n);
-    u32 *const row_out = c.take<u32>(n), *const pos_out = c.take<u32>(n), *const cls_out = c.take<u32>(n);
-    o.status = SJ_ARR(status, n, A_STRORD_ROW);
-    o.kidx = SJ_ARR(kidx, n, A_STRORD_ROW);
-    o.perm = SJ_ARR(perm, n, A_SORT);
-    o.flags = SJ_ARR(flags, n, A_STRORD_ACT);
-    o.chunk = SJ_ARR(chunk, n, A_STRORD_ACT);
-    o.row = SJ_ARR(row, n, A_STRORD_ACT), o.pos = SJ_ARR(pos, n, A_STRORD_ACT), o.cls = SJ_ARR(cls, n, A_STRORD_ACT);
-    o.row_out = SJ_ARR(row_out, n, A_STRORD_ACT), o.pos_out = SJ_ARR(pos_out, n, A_STRORD_ACT), o.cls_out = SJ_ARR(cls_out, n, A_STRORD_ACT);
-    unsigned long long **const per_tile[] = {&o.tiles_ok,   &o.tiles_len, &o.tiles_kand, &o.tiles_kor,
-                                             &o.tiles_cand, &o.tiles_cor, &o.tiles_head, &o.tiles_act};
-    for (unsigned long long **t : per_tile) *t = c.take<unsigned long long>(tiles);
-    sort_carve(c, n, &w->sort);
-    sort_carve(c, n, &w->csort);
-    (void)(c.used = where_layout(c, ctx, n, &w->w, &w->nw, &w->w_totals));
-    return c.used;
-}
-// behind the checks of sjhip_order_path_strings: q is the view of the n > 0 rows in force
-static int strord_build(sjhip_ctx *ctx, const QView &q, const QPath &pth, const uint8_t *keys, size_t klen, uint32_t n, u32 desc, uint64_t limit,
-                        size_t *records, size_t *rows) {
-    StrOrdWork w;
-    int rc = reserve_layout(ctx, ctx->d_kat, [&](Carve c) { return strord_work_layout(c, ctx, n, desc, &w); });
-    if (rc) return rc;
-    hipStream_t st = ctx->stream;
-    const u32 tiles = (n + QTILE - 1) / QTILE;
-    const dim3 per_row((n + 255) / 256), per_tile(tiles), b256(256), bqt(QT), one(1), wide(1024);
-    unsigned long long *const none = nullptr;
-    QStrOrd &o = w.o;
-    u64 *const keys0 = w.sort.keys[0];
-    u32 *const rows0 = w.sort.rows[0], *const ckeys0 = w.csort.keys[0], *const crows0 = w.csort.rows[0];
-    HIPCHK(hipMemsetAsync(o.totals, 0, 256, st), "string order totals memset");
-    hipLaunchKernelGGL(k_q_strord_keys, per_tile, bqt, 0, st, q, pth, o);
-    hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, o.tiles_ok, none, none, tiles, o.totals + STRORD_T_OK);
-    hipLaunchKernelGGL(k_q_strord_init, per_tile, bqt, 0, st, o);
-    HIPCHK(hipGetLastError(), "string order launch");
-    unsigned long long *const h = (unsigned long long *)(ctx->h_scratch + 512), *const h_left = (unsigned long long *)(ctx->h_scratch + 1024);
-    *h_left = 0;
-    u64 bound = 1;  // of the rounds: known after round 0's copy
-    u32 m_max = n;  // the round's active entries are at most this many
-    for (u64 round = 0;; round++) {
-        // the round's chunk keys, and its one round trip
-        const u32 ctiles = (m_max + QTILE - 1) / QTILE;
-        const unsigned long long *const active = o.totals + (round == 0 ? STRORD_T_OK : STRORD_T_ACTIVE);
-        hipLaunchKernelGGL(k_q_strord_chunks, dim3(ctiles), bqt, 0, st, q, o, active, round * (u64)STRORD_CHUNK, SJ_ARR(keys0, n, A_SORT),
-                           SJ_ARR(rows0, n, A_SORT));
-        hipLaunchKernelGGL(k_q_strord_fold, one, bqt, 0, st, o, ctiles, round == 0 ? tiles : 0u);
-        HIPCHK(hipGetLastError(), "string order chunk launch");
-        HIPCHK(hipMemcpyAsync(h, o.totals, STRORD_T_WORDS * 8, hipMemcpyDeviceToHost, st), "D2H string order totals");
-        HIPCHK(hipStreamSynchronize(st), "string order sync");
-        rc = query_bounds_check(ctx);
-        if (rc) return rc;
-        if (round == 0) bound = strord_max_rounds(h[STRORD_T_LONGEST]);
-        const u32 m = (u32)h[round == 0 ? STRORD_T_OK : STRORD_T_ACTIVE];
-        if (m < 2) break;  // (a class has two members at least: nothing is active)
-        // stable by (class, chunk key): the chunk keys first, then the classes
-        const u32 kmask = order_pass_mask(h[STRORD_T_ANDOR], h[STRORD_T_ANDOR + 1]);
-        const u32 cmask = order_pass_mask(h[STRORD_T_ANDOR + 2], h[STRORD_T_ANDOR + 3]);
-        const u32 *sorted = w.sort.rows[sort_enqueue(st, m, n, kmask, true, w.sort)];
-        const dim3 per_entry((m + 255) / 256), per_etile((m + QTILE - 1) / QTILE);
-        if (cmask) {
-            hipLaunchKernelGGL(k_q_strord_classes, per_entry, b256, 0, st, o, m, SJ_ARR(sorted, n, A_SORT), SJ_ARR(ckeys0, n, A_SORT),
-                               SJ_ARR(crows0, n, A_SORT));
-            sorted = w.csort.rows[sort_enqueue(st, m, n, cmask, true, w.csort)];
-        }
-        // place, mark, renumber, compact
-        hipLaunchKernelGGL(k_q_strord_place, per_etile, bqt, 0, st, o, m, SJ_ARR(sorted, n, A_SORT));
-        hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, o.tiles_head, o.tiles_act, none, per_etile.x, o.totals + STRORD_T_HEADS);
-        hipLaunchKernelGGL(k_q_strord_compact, per_etile, bqt, 0, st, o, m, SJ_ARR(sorted, n, A_SORT));
-        HIPCHK(hipGetLastError(), "string order round launch");
-        std::swap(o.row, o.row_out), std::swap(o.pos, o.pos_out), std::swap(o.cls, o.cls_out);
-        m_max = m;
-        if (round + 1 >= bound) {  // the last round the longest key allows: what it left active (nothing) is looked at with the emit's wait
-            HIPCHK(hipMemcpyAsync(h_left, o.totals + STRORD_T_ACTIVE, 8, hipMemcpyDeviceToHost, st), "D2H string order rest");
-            break;
-        }
+int sjhip_order_path(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int kind, uint32_t flags,
+                     uint64_t limit, size_t *records, size_t *rows) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (order_sizes_check(ctx, "sjhip_order_path", records, rows)) return SJHIP_ERR_ARG;
+    if (kind != SJHIP_COL_FLOAT && kind != SJHIP_COL_INT && kind != SJHIP_COL_UINT) {
+        ctx_set_error(ctx, "sjhip_order_path: key kind %d is not SJHIP_COL_FLOAT, SJHIP_COL_INT or SJHIP_COL_UINT", kind);
+        return SJHIP_ERR_ARG;
     }
-    // rank, flag, narrow: the first `kept` ranks stay
-    const size_t kept = limit == 0 || limit >= n ? (size_t)n : (size_t)limit;
-    const u32 *const ranked = arr_raw(o.perm);
-    hipLaunchKernelGGL(k_q_order_flag, per_row, b256, 0, st, SJ_ARR(ranked, n, A_SORT), n, (u64)kept, w.w.flag);
-    hipLaunchKernelGGL(k_q_order_flag_sums, per_tile, bqt, 0, st, w.w.flag, n, w.w.tiles);
-    hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.w.tiles, none, none, tiles, none);
-    HIPCHK(hipGetLastError(), "string order flag launch");
-    const std::vector<sjhip_ctx *> parts(1, ctx);
-    rc = where_narrow(ctx, parts, keys, klen, &NO_VALUE, 0, std::vector<QWhere>(1, w.w), std::vector<WhereNew>(1, w.nw),
-                      std::vector<size_t>(1, kept), records, rows);
-    if (rc) return rc;
-    OrderArrays a;
-    rc = reserve_layout(ctx, ctx->d_order, [&](Carve c) { return order_layout(c, kept, SJHIP_COL_STRING, &a); });
-    if (rc) return rc;
-    const u32 *const pre = arr_raw(w.w.pre);
-    hipLaunchKernelGGL(k_q_strord_emit, dim3(((u32)kept + 255) / 256), b256, 0, st, o, SJ_ARR(pre, n, A_WHERE_PRE), (u32)kept,
-                       SJ_ARR(a.order, kept, A_ORDER_OUT), SJ_ARR(a.status, kept, A_ORDER_OUT));
-    HIPCHK(hipGetLastError(), "string order emit launch");
-    HIPCHK(hipStreamSynchronize(st), "string order emit sync");
-    rc = query_bounds_check(ctx);
-    if (rc) return rc;
-    if (*h_left) {
-        ctx_set_error(ctx, "sjhip_order_path_strings: %llu rows are still unordered after %llu rounds, the bound of the longest key (%llu bytes)",
-                      *h_left, (unsigned long long)bound, (unsigned long long)bound * STRORD_CHUNK - 1);
-        return SJHIP_ERR_HIP;
-    }
-    return published(ctx, ctx->res.publish(&ResultState::order, {kept, SJHIP_COL_STRING}));
+    if (order_flags_check(ctx, "sjhip_order_path", -1, flags)) return SJHIP_ERR_ARG;
+    WholePath k = {keys, key_lens, n_keys};
+    return order_entry(ctx, "sjhip_order_path", &k, &kind, &flags, 1, kind, limit, records, rows);
 }
 
 int sjhip_order_path_strings(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, uint32_t flags, uint64_t limit,
                              size_t *records, size_t *rows) {
     if (!ctx) return SJHIP_ERR_ARG;
-    if (!records || !rows) {
-        ctx_set_error(ctx, "sjhip_order_path_strings: a null size pointer");
-        return SJHIP_ERR_ARG;
-    }
-    if (flags & ~SJHIP_ORDER_DESC) {
-        ctx_set_error(ctx, "sjhip_order_path_strings: unknown flag bits 0x%x", flags & ~SJHIP_ORDER_DESC);
-        return SJHIP_ERR_ARG;
-    }
+    if (order_sizes_check(ctx, "sjhip_order_path_strings", records, rows)) return SJHIP_ERR_ARG;
+    if (order_flags_check(ctx, "sjhip_order_path_strings", -1, flags)) return SJHIP_ERR_ARG;
+    const int kind = SJHIP_COL_STRING;
     WholePath k = {keys, key_lens, n_keys};
-    uint32_t n = 0;
-    int rc = whole_entry(ctx, "sjhip_order_path_strings", "the ranks of shards are not merged", &k, 1, &n);
-    if (rc) return rc;
-    // ---- nothing was touched up to here; from here on the last order is gone ----
-    ctx->res.order.begin();
-    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
-    if (n == 0) {  // (a selection without rows: it stays as it is)
-        *records = ctx->res.rows.sizes().records, *rows = 0;
-        return published(ctx, ctx->res.publish(&ResultState::order, {0, SJHIP_COL_STRING}));
-    }
-    rc = strord_build(ctx, k.q, k.pth, k.keys, k.klen, n, flags & SJHIP_ORDER_DESC, limit, records, rows);
-    if (rc) {  // half-built: the old selection may have been written over
-        ctx->res.rows.begin();
-        char why[sizeof ctx->err];
-        snprintf(why, sizeof why, "%s", ctx->err);
-        ctx_set_error(ctx, "sjhip_order_path_strings failed and the row selection was given up: %.170s", why);
-    }
-    return rc;
-}
-
-// ---- several keys --------------------------------------------------------------------------------------------------------------------
-// sjhip_order_paths is the string order's build with the rounds of every column in turn (the k_q_mkord_* kernels, and the
-// k_q_strord_* ones whose signatures fit).  The work arrays (MkOrdWork) lie in d_kat, laid out once for the row count, the arrays of
-// the narrowing behind them; the product is the order's, without values, its kind ORDER_KIND_MULTI.  One host round trip per round:
-// the active count and the ANDs / ORs that plan the round's two sorts (a string column's first also brings its longest key).
-struct MkOrdCol {
-    QView q;  // (the keys of the column's path are the view's)
-    QPath pth;
-    int kind;
-    u32 desc;
-};
-struct MkOrdWork {
-    QMkOrd o;
-    u8 *status0, *status_c;  // [n] each: column 0's statuses, and those of the column at work behind it
-    SortWork<u64> sort;      // by chunk key
-    SortWork<u32> csort;     // by class key
-    QWhere w;
-    WhereNew nw;
-    unsigned long long *w_totals;
-};
-static size_t mkord_work_layout(Carve c, const sjhip_ctx *ctx, uint32_t n, MkOrdWork *w) {
-    const u32 tiles = (n + QTILE - 1) / QTILE;
-    QStrOrd &o = w->o.s;
-    o.totals = c.take<unsigned long long>(32);
-    o.n = n;
-    o.desc = 0;
-    w->status0 = c.take<u8>(n), w->status_c = c.take<u8>(n);
-    u8 *const flags = c.take<u8>(n), *const bnd = c.take<u8>((size_t)n + 1);
-    u64 *const kidx = c.take<u64>(n), *const chunk = c.take<u64>(n);
-    u32 *const perm = c.take<u32>(n), *const ckey = c.take<u32>(n);
-    u32 *const row = c.take<u32>(n), *const pos = c.take<u32>(n), *const cls = c.take<u32>(n);
-    u32 *const row_out = c.take<u32>(n), *const pos_out = c.take<u32>(n), *const cls_out = c.take<u32>(n);
-    o.status = SJ_ARR(w->status0, n, A_MKORD_ROW);
-    o.kidx = SJ_ARR(kidx, n, A_MKORD_ROW);
-    o.perm = SJ_ARR(perm, n, A_SORT);
-    o.flags = SJ_ARR(flags, n, A_STRORD_ACT);
-    o.chunk = SJ_ARR(chunk, n, A_STRORD_ACT);
-    o.row = SJ_ARR(row, n, A_STRORD_ACT), o.pos = SJ_ARR(pos, n, A_STRORD_ACT), o.cls = SJ_ARR(cls, n, A_STRORD_ACT);
-    o.row_out = SJ_ARR(row_out, n, A_STRORD_ACT), o.pos_out = SJ_ARR(pos_out, n, A_STRORD_ACT), o.cls_out = SJ_ARR(cls_out, n, A_STRORD_ACT);
-    w->o.ckey = SJ_ARR(ckey, n, A_MKORD_ACT);
-    w->o.bnd = SJ_ARR(bnd, (size_t)n + 1, A_MKORD_BND);
-    unsigned long long **const per_tile[] = {&o.tiles_ok,   &o.tiles_len, &o.tiles_kand, &o.tiles_kor,
-                                             &o.tiles_cand, &o.tiles_cor, &o.tiles_head, &o.tiles_act};
-    for (unsigned long long **t : per_tile) *t = c.take<unsigned long long>(tiles);
-    sort_carve(c, n, &w->sort);
-    sort_carve(c, n, &w->csort);
-    (void)(c.used = where_layout(c, ctx, n, &w->w, &w->nw, &w->w_totals));
-    return c.used;
-}
-// behind the checks of sjhip_order_paths: cols[c].q is the view of the n > 0 rows in force
-static int mkord_build(sjhip_ctx *ctx, const MkOrdCol *cols, uint32_t n_cols, const uint8_t *keys, size_t klen, uint32_t n, uint64_t limit,
-                       size_t *records, size_t *rows) {
-    MkOrdWork w;
-    int rc = reserve_layout(ctx, ctx->d_kat, [&](Carve c) { return mkord_work_layout(c, ctx, n, &w); });
-    if (rc) return rc;
-    hipStream_t st = ctx->stream;
-    const u32 tiles = (n + QTILE - 1) / QTILE;
-    const dim3 per_row((n + 255) / 256), per_tile(tiles), b256(256), bqt(QT), one(1), wide(1024);
-    unsigned long long *const none = nullptr;
-    QMkOrd &o = w.o;
-    u64 *const keys0 = w.sort.keys[0];
-    u32 *const rows0 = w.sort.rows[0], *const ckeys0 = w.csort.keys[0], *const crows0 = w.csort.rows[0];
-    const unsigned long long *const active = o.s.totals + STRORD_T_ACTIVE;
-    HIPCHK(hipMemsetAsync(o.s.totals, 0, 256, st), "order by several keys totals memset");
-    hipLaunchKernelGGL(k_q_mkord_init, per_row, b256, 0, st, o);
-    unsigned long long *const h = (unsigned long long *)(ctx->h_scratch + 512), *const h_left = (unsigned long long *)(ctx->h_scratch + 1024);
-    for (uint32_t c = 0; c < n_cols; c++) h_left[c] = 0;
-    u64 left_bound[ORDER_MAX_KEYS] = {};
-    bool tied = true;  // rows still tie: the next column has work
-    for (uint32_t c = 0; c < n_cols && tied; c++) {
-        const MkOrdCol &col = cols[c];
-        const bool is_string = col.kind == SJHIP_COL_STRING;
-        if (c > 0) {  // the entries that are not alone in their class, from the boundaries
-            hipLaunchKernelGGL(k_q_mkord_bounds, per_tile, bqt, 0, st, o);
-            hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, o.s.tiles_head, o.s.tiles_act, none, tiles, o.s.totals + STRORD_T_HEADS);
-            hipLaunchKernelGGL(k_q_mkord_rebuild, per_tile, bqt, 0, st, o);
-            o.s.status = SJ_ARR(w.status_c, n, A_MKORD_ROW);
-        }
-        hipLaunchKernelGGL(k_q_mkord_keys, per_tile, bqt, 0, st, col.q, col.pth, o, col.kind, col.desc, active);
-        u64 bound = 1;  // of the column's rounds: a string column's is known after its first copy
-        u32 m_max = n;  // the round's active entries are at most this many
-        for (u64 round = 0;; round++) {
-            // the round's chunk keys, and its one round trip
-            const u32 ctiles = (m_max + QTILE - 1) / QTILE;
-            hipLaunchKernelGGL(k_q_mkord_chunks, dim3(ctiles), bqt, 0, st, col.q, o, col.kind, col.desc, active, round * (u64)STRORD_CHUNK,
-                               SJ_ARR(keys0, n, A_SORT), SJ_ARR(rows0, n, A_SORT));
-            hipLaunchKernelGGL(k_q_strord_fold, one, bqt, 0, st, o.s, ctiles, round == 0 ? tiles : 0u);
-            HIPCHK(hipGetLastError(), "order by several keys chunk launch");
-            HIPCHK(hipMemcpyAsync(h, o.s.totals, STRORD_T_WORDS * 8, hipMemcpyDeviceToHost, st), "D2H order by several keys totals");
-            HIPCHK(hipStreamSynchronize(st), "order by several keys sync");
-            rc = query_bounds_check(ctx);
-            if (rc) return rc;
-            if (round == 0 && is_string) bound = strord_max_rounds(h[STRORD_T_LONGEST]);
-            const u32 m = (u32)h[STRORD_T_ACTIVE];
-            if (m < 2) {  // (a class has two members at least: nothing is active)
-                tied = round > 0;  // (behind the column's first round the classes it finished may still hold ties)
-                break;
-            }
-            // stable by (class key, chunk key): the chunk keys first -- of the OK rows; without one, no digit --, then the class keys
-            const u64 kand = h[STRORD_T_ANDOR], kor = h[STRORD_T_ANDOR + 1];
-            const u32 kmask = (kand & ~kor) ? 0u : order_pass_mask(kand, kor);
-            const u32 cmask = order_pass_mask(h[STRORD_T_ANDOR + 2], h[STRORD_T_ANDOR + 3]);
-            const u32 *sorted = w.sort.rows[sort_enqueue(st, m, n, kmask, true, w.sort)];
-            const dim3 per_entry((m + 255) / 256), per_etile((m + QTILE - 1) / QTILE);
-            if (cmask) {
-                QStrOrd by_class = o.s;
-                by_class.cls = o.ckey;
-                hipLaunchKernelGGL(k_q_strord_classes, per_entry, b256, 0, st, by_class, m, SJ_ARR(sorted, n, A_SORT), SJ_ARR(ckeys0, n, A_SORT),
-                                   SJ_ARR(crows0, n, A_SORT));
-                sorted = w.csort.rows[sort_enqueue(st, m, n, cmask, true, w.csort)];
-            }
-            // place, mark; a string column renumbers and compacts what stays in it
-            hipLaunchKernelGGL(k_q_mkord_place, per_etile, bqt, 0, st, o, m, SJ_ARR(sorted, n, A_SORT), is_string ? 1u : 0u, col.desc);
-            if (is_string) {
-                hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, o.s.tiles_head, o.s.tiles_act, none, per_etile.x, o.s.totals + STRORD_T_HEADS);
-                hipLaunchKernelGGL(k_q_strord_compact, per_etile, bqt, 0, st, o.s, m, SJ_ARR(sorted, n, A_SORT));
-                std::swap(o.s.row, o.s.row_out), std::swap(o.s.pos, o.s.pos_out), std::swap(o.s.cls, o.s.cls_out);
-            }
-            HIPCHK(hipGetLastError(), "order by several keys round launch");
-            m_max = m;
-            if (round + 1 >= bound) {  // the column's last round: what a string column left active (nothing) is looked at with the emit's wait
-                if (is_string) {
-                    HIPCHK(hipMemcpyAsync(h_left + c, o.s.totals + STRORD_T_ACTIVE, 8, hipMemcpyDeviceToHost, st), "D2H order by several keys rest");
-                    left_bound[c] = bound;
-                }
-                break;
-            }
-        }
-    }
-    // rank, flag, narrow: the first `kept` ranks stay
-    const size_t kept = limit == 0 || limit >= n ? (size_t)n : (size_t)limit;
-    const u32 *const ranked = arr_raw(o.s.perm);
-    hipLaunchKernelGGL(k_q_order_flag, per_row, b256, 0, st, SJ_ARR(ranked, n, A_SORT), n, (u64)kept, w.w.flag);
-    hipLaunchKernelGGL(k_q_order_flag_sums, per_tile, bqt, 0, st, w.w.flag, n, w.w.tiles);
-    hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.w.tiles, none, none, tiles, none);
-    HIPCHK(hipGetLastError(), "order by several keys flag launch");
-    const std::vector<sjhip_ctx *> parts(1, ctx);
-    rc = where_narrow(ctx, parts, keys, klen, &NO_VALUE, 0, std::vector<QWhere>(1, w.w), std::vector<WhereNew>(1, w.nw),
-                      std::vector<size_t>(1, kept), records, rows);
-    if (rc) return rc;
-    OrderArrays a;
-    rc = reserve_layout(ctx, ctx->d_order, [&](Carve c) { return order_layout(c, kept, ORDER_KIND_MULTI, &a); });
-    if (rc) return rc;
-    const u32 *const pre = arr_raw(w.w.pre);
-    QStrOrd by_first = o.s;  // (column 0's status: the only column every row is evaluated on)
-    by_first.status = SJ_ARR(w.status0, n, A_MKORD_ROW);
-    hipLaunchKernelGGL(k_q_strord_emit, dim3(((u32)kept + 255) / 256), b256, 0, st, by_first, SJ_ARR(pre, n, A_WHERE_PRE), (u32)kept,
-                       SJ_ARR(a.order, kept, A_ORDER_OUT), SJ_ARR(a.status, kept, A_ORDER_OUT));
-    HIPCHK(hipGetLastError(), "order by several keys emit launch");
-    HIPCHK(hipStreamSynchronize(st), "order by several keys emit sync");
-    rc = query_bounds_check(ctx);
-    if (rc) return rc;
-    for (uint32_t c = 0; c < n_cols; c++)
-        if (h_left[c]) {
-            ctx_set_error(ctx, "sjhip_order_paths: column %u: %llu rows are still unordered after %llu rounds, the bound of its longest key", c,
-                          h_left[c], (unsigned long long)left_bound[c]);
-            return SJHIP_ERR_HIP;
-        }
-    return published(ctx, ctx->res.publish(&ResultState::order, {kept, ORDER_KIND_MULTI}));
+    return order_entry(ctx, "sjhip_order_path_strings", &k, &kind, &flags, 1, kind, limit, records, rows);
 }
 
 int sjhip_order_paths(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, const uint32_t *path_lens, const int *kinds,
                       const uint32_t *flags, uint32_t n_cols, uint64_t limit, size_t *records, size_t *rows) {
     if (!ctx) return SJHIP_ERR_ARG;
-    if (!records || !rows) {
-        ctx_set_error(ctx, "sjhip_order_paths: a null size pointer");
-        return SJHIP_ERR_ARG;
-    }
+    if (order_sizes_check(ctx, "sjhip_order_paths", records, rows)) return SJHIP_ERR_ARG;
     if (n_cols < 1 || n_cols > (uint32_t)SJHIP_ORDER_MAX_KEYS) {
         ctx_set_error(ctx, "sjhip_order_paths: %u key columns (1 to %d)", n_cols, SJHIP_ORDER_MAX_KEYS);
         return SJHIP_ERR_ARG;
@@ -4887,10 +4530,7 @@ int sjhip_order_paths(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_l
                           kind);
             return SJHIP_ERR_ARG;
         }
-        if (flags && (flags[c] & ~SJHIP_ORDER_DESC)) {
-            ctx_set_error(ctx, "sjhip_order_paths: column %u: unknown flag bits 0x%x", c, flags[c] & ~SJHIP_ORDER_DESC);
-            return SJHIP_ERR_ARG;
-        }
+        if (flags && order_flags_check(ctx, "sjhip_order_paths", (int)c, flags[c])) return SJHIP_ERR_ARG;
         n_keys += path_lens[c];
         if (n_keys > (size_t)TABLE_MAX_KEYS) {
             ctx_set_error(ctx, "sjhip_order_paths: the paths hold more than %d keys together (found at column %u)", TABLE_MAX_KEYS, c);
@@ -4906,7 +4546,7 @@ int sjhip_order_paths(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_l
         ctx_set_error(ctx, "sjhip_order_paths: the keys of the paths are longer than %d bytes together", TABLE_MAX_BYTES);
         return SJHIP_ERR_ARG;
     }
-    std::vector<WholePath> k(n_cols);
+    WholePath k[SJHIP_ORDER_MAX_KEYS] = {};
     size_t key_at = 0, byte_at = 0;
     for (uint32_t c = 0; c < n_cols; c++) {
         k[c].keys = path_lens[c] ? keys + byte_at : nullptr;
@@ -4915,26 +4555,7 @@ int sjhip_order_paths(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_l
         for (uint32_t j = 0; j < path_lens[c]; j++) byte_at += key_lens[key_at + j];
         key_at += path_lens[c];
     }
-    uint32_t n = 0;
-    int rc = whole_entry(ctx, "sjhip_order_paths", "the ranks of shards are not merged", k.data(), (int)n_cols, &n);
-    if (rc) return rc;
-    // ---- nothing was touched up to here; from here on the last order is gone ----
-    ctx->res.order.begin();
-    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
-    if (n == 0) {  // (a selection without rows: it stays as it is)
-        *records = ctx->res.rows.sizes().records, *rows = 0;
-        return published(ctx, ctx->res.publish(&ResultState::order, {0, ORDER_KIND_MULTI}));
-    }
-    std::vector<MkOrdCol> cols(n_cols);
-    for (uint32_t c = 0; c < n_cols; c++) cols[c] = {k[c].q, k[c].pth, kinds[c], flags ? flags[c] & SJHIP_ORDER_DESC : 0u};
-    rc = mkord_build(ctx, cols.data(), n_cols, k[0].keys, k[0].klen, n, limit, records, rows);
-    if (rc) {  // half-built: the old selection may have been written over
-        ctx->res.rows.begin();
-        char why[sizeof ctx->err];
-        snprintf(why, sizeof why, "%s", ctx->err);
-        ctx_set_error(ctx, "sjhip_order_paths failed and the row selection was given up: %.180s", why);
-    }
-    return rc;
+    return order_entry(ctx, "sjhip_order_paths", k, kinds, flags, n_cols, ORDER_KIND_MULTI, limit, records, rows);
 }
 
 int sjhip_fetch_order(sjhip_ctx *ctx, uint64_t *order, void *values, uint8_t *status) {

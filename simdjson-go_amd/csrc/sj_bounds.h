@@ -49,23 +49,17 @@ enum ArrId : uint32_t {
     // columns / the table of row numbers / the group offsets / the per-group and per-row arrays of the product / the bytes of a
     // STRING column's entries
     A_GROUP_ROW, A_GROUP_LEN, A_GROUP_TABLE, A_GROUP_OFF, A_GROUP_OUT, A_GROUP_KEYS,
-    // the ordering (query.hip, sjhip_order_path): the per-row work arrays (sort key, status) / the arrays of the product (order,
-    // values, status)
-    A_ORDER_ROW, A_ORDER_OUT,
+    // the ordering (query.hip, sjhip_order_path, _strings and sjhip_order_paths): the per-row work arrays (the statuses on column 0
+    // and on the column at work, the key or key element) / the arrays of the active entries (row, position, class, chunk key, class
+    // key, head and active flags) / the boundary bytes of the n + 1 positions / the arrays of the product (order, values, status).
+    // Its ranked rows and its sorts are A_SORT
+    A_ORDER_ROW, A_ORDER_ACT, A_ORDER_BND, A_ORDER_OUT,
     // the radix sort of both (sj_sort.h): the keys and rows of its buffers, and the sorted rows wherever they are read / its digit
     // histograms
     A_SORT, A_SORT_HIST,
     // the unnested rows (query.hip, sjhip_unnest_rows): the target range of every parent row / the status byte of every parent, in
     // the work arrays and in the product / the parent number of every new row / the parent offsets
-    A_UNNEST_RANGE, A_UNNEST_STATUS, A_UNNEST_PARENT, A_UNNEST_OFF,
-    // the string order (query.hip, sjhip_order_path_strings): the per-row work arrays (status, key element) / the arrays of the
-    // active entries (row, position, class, chunk key, head and active flags).  Its ranked rows and its sorts are A_SORT, its product
-    // A_ORDER_OUT
-    A_STRORD_ROW, A_STRORD_ACT,
-    // the order by several keys (query.hip, sjhip_order_paths): the per-row work arrays (the statuses on column 0 and on the column
-    // at work, the key or key element) / the class keys of the active entries / the boundary bytes of the n + 1 positions.  The
-    // active entries themselves are A_STRORD_ACT, the ranked rows and the sorts A_SORT, the product A_ORDER_OUT
-    A_MKORD_ROW, A_MKORD_ACT, A_MKORD_BND
+    A_UNNEST_RANGE, A_UNNEST_STATUS, A_UNNEST_PARENT, A_UNNEST_OFF
 };
 
 #if defined(SJ_DEBUG_BOUNDS)

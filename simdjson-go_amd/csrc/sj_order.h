@@ -1,4 +1,4 @@
-// sj_order.h -- the host-and-device pieces of the orderings (query.hip, sjhip_order_path and sjhip_order_path_strings): the
+// sj_order.h -- the host-and-device pieces of the orderings (query.hip, sjhip_order_path, sjhip_order_path_strings and sjhip_order_paths): the
 // order-preserving key of a number and the chunk key of a string (the sort and its pass plan: sj_sort.h).  Plain C++ under SJ_HD, so the CPU build of a test program can run what the kernels run
 // (host_selftest.cpp, tests/test_order_result_state.py).
 //
@@ -24,7 +24,7 @@ SJ_HD u64 agg_unkey(u64 k, int kind) {
     return (k >> 63) ? k ^ AGG_SIGN : ~k;
 }
 
-// The string order compares keys STRORD_CHUNK bytes at a time (query.hip, the k_q_strord_* kernels).  The chunk key of the key
+// The string order compares keys STRORD_CHUNK bytes at a time (query.hip, k_q_order_chunks and k_q_order_place).  The chunk key of the key
 // bytes[0 .. len) at byte `at`: the top 56 bits are the bytes [at, at + 7) big-endian, zero padded behind the end of the key; the
 // low byte is how many of them are the key's own, min(7, len - at), 0 when at >= len.  The unsigned order of the chunk keys is
 // bytes.Compare on the chunks: where the padded bytes tie, the shorter chunk -- a proper prefix, "a" in front of "a" + NUL -- has the
@@ -43,7 +43,7 @@ SJ_HD u32 strord_chunk_count(u64 chunk, bool desc) { return (u32)((desc ? ~chunk
 // the rounds that order keys of at most `longest` bytes: the round at byte 7 j sees the end of every key shorter than 7 (j + 1)
 SJ_HD u64 strord_max_rounds(u64 longest) { return longest / STRORD_CHUNK + 1; }
 
-// The order by several keys (query.hip, the k_q_mkord_* kernels, sjhip_order_paths) refines classes of tied rows column by column.
+// The order by several keys (query.hip, the k_q_order_* kernels; a single-key call is the one-column case) refines classes of tied rows column by column.
 // A round of a column sorts its entries by (class, missing, chunk key): the rows without an OK key on the column lie behind the
 // others of their class, and tie.  The second sort's key is class << 1 | missing -- classes number at most 2^30, so it is a u32.
 // An entry goes on to the column's next round iff it has a key, its new class has company and its chunk was full (a numeric

@@ -1,6 +1,7 @@
-"""The ordering on the bounds-checked build (libsjhip_dbg.so, csrc/sj_bounds.h): the per-row keys and statuses, the keys and rows of
+"""The ordering on the bounds-checked build (libsjhip_dbg.so, csrc/sj_bounds.h): the per-row keys and statuses, the active entries and
+the boundary bytes of the one ordering pipeline, the keys and rows of
 the sort, its histograms, the arrays of the product and the flags, prefixes and offsets of the narrowing are reached through checked
-views (A_ORDER_ROW, A_SORT, A_SORT_HIST, A_ORDER_OUT, A_WHERE_FLAG, A_WHERE_PRE, A_WHERE_OFF, A_ROWS), and a violation fails
+views (A_ORDER_ROW, A_ORDER_ACT, A_ORDER_BND, A_SORT, A_SORT_HIST, A_ORDER_OUT, A_WHERE_FLAG, A_WHERE_PRE, A_WHERE_OFF, A_ROWS), and a violation fails
 the call.  The shapes T + 1 and 2 T + 3, the rows of every status and a limit of tests/test_gpu_order.py, in their own interpreter
 with SJHIP_LIB pointing at that build (as tests/test_debug_bounds_group.py runs the grouping)."""
 import os

@@ -1,7 +1,7 @@
 """The order by several keys on the bounds-checked build (libsjhip_dbg.so, csrc/sj_bounds.h): the per-row statuses and keys, the class
 keys and the active entries of the rounds, the boundary bytes, the ranked rows and the buffers of both sorts, the arrays of the
-product and the flags, prefixes and offsets of the narrowing are reached through checked views (A_MKORD_ROW, A_MKORD_ACT,
-A_MKORD_BND, A_STRORD_ACT, A_SORT, A_SORT_HIST, A_ORDER_OUT, A_WHERE_FLAG, A_WHERE_PRE, A_WHERE_OFF, A_ROWS), and a violation fails
+product and the flags, prefixes and offsets of the narrowing are reached through checked views (A_ORDER_ROW, A_ORDER_ACT,
+A_ORDER_BND, A_SORT, A_SORT_HIST, A_ORDER_OUT, A_WHERE_FLAG, A_WHERE_PRE, A_WHERE_OFF, A_ROWS), and a violation fails
 the call.  The shapes T + 1 and 2 T + 3, the mixed kinds, the different-rounds family, every status and one limit of
 tests/test_gpu_order_multi.py, in their own interpreter with SJHIP_LIB pointing at that build (as
 tests/test_debug_bounds_order_strings.py runs the string order)."""

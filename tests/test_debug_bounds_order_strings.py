@@ -1,6 +1,6 @@
 """The string order on the bounds-checked build (libsjhip_dbg.so, csrc/sj_bounds.h): the per-row statuses and key elements, the active
 entries of the rounds, the ranked rows and the buffers of both sorts, the arrays of the product and the flags, prefixes and offsets
-of the narrowing are reached through checked views (A_STRORD_ROW, A_STRORD_ACT, A_SORT, A_SORT_HIST, A_ORDER_OUT, A_WHERE_FLAG,
+of the narrowing are reached through checked views (A_ORDER_ROW, A_ORDER_ACT, A_ORDER_BND, A_SORT, A_SORT_HIST, A_ORDER_OUT, A_WHERE_FLAG,
 A_WHERE_PRE, A_WHERE_OFF, A_ROWS), and a violation fails the call.  The shapes T + 1 and 2 T + 3, the late-difference keys, the rows
 of every status and a limit of tests/test_gpu_order_strings.py, in their own interpreter with SJHIP_LIB pointing at that build (as
 tests/test_debug_bounds_order.py runs the numeric order)."""

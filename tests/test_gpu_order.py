@@ -117,6 +117,39 @@ def test_shapes(ctx, n, pattern):
             assert desc.order.tolist() == list(range(0, n, 2)) + list(range(1, n, 2))
 
 
+# ---- 1b. rows without a key at the seams: they travel through the sort as the missing bit of the class key ------------------------------
+LACKING = {
+    "every-third-lacks": lambda r, n: r % 3 != 2,
+    "only-row-0-has": lambda r, n: r == 0,
+    "only-the-last-has": lambda r, n: r == n - 1,
+    "none-has": lambda r, n: False,
+}
+
+
+def lacking_cut(has):
+    """a limit that cuts inside the block of rows without a key (the whole of it where it has one row)"""
+    missing = has.count(False)
+    return max(1, has.count(True) + (missing + 1) // 2)
+
+
+@pytest.mark.parametrize("pattern", sorted(LACKING))
+@pytest.mark.parametrize("n", [1, 2, 64, 65, OW.QTILE, OW.QTILE + 1])
+def test_rows_without_a_key_at_the_seams(ctx, n, pattern):
+    has = [LACKING[pattern](r, n) for r in range(n)]
+    # (the keys repeat, so rows tie; a row without one lacks the member, or holds a null or a string)
+    lines = ['{"i":%d,"u":%d,"f":%d.5}' % ((r * 7) % 5 - 2, (r * 7) % 5, (r * 7) % 5 - 2) if has[r] else
+             ('{"x":%d}' % r, '{"i":null,"u":null,"f":null}', '{"i":"1","u":"1","f":"1"}')[r % 3] for r in range(n)]
+    w = nd_rows(ctx, lines)
+    for path, kind in (((b"i",), I), ((b"u",), U), ((b"f",), F)):
+        for limit in (0, lacking_cut(has)):
+            for got, want in all_directions(ctx, w, path, kind, (pattern, n), limit):
+                kept = n if limit == 0 else min(n, limit)
+                tail = kept - min(kept, has.count(True))  # the kept rows without a key: behind the others, in row order
+                assert got.rows == kept and [st != CW.COL_OK for st in got.status.tolist()] == [False] * (kept - tail) + [True] * tail
+                assert got.order.tolist()[kept - tail:] == sorted(got.order.tolist()[kept - tail:])
+                assert all(v == 0 for v, st in zip(bits(got.values).tolist(), got.status.tolist()) if st != CW.COL_OK)
+
+
 # ---- 2. one pass at a time ------------------------------------------------------------------------------------------------------------
 DIGIT_SETS = [(d,) for d in range(8)] + [(0, 2), (1, 7), (3, 5)] + [tuple(range(8))]
 

@@ -28,7 +28,7 @@ import where_walk as WW
 import workloads
 from test_group_walk import STATUS_DOC
 from test_gpu_columns import oracle_walk
-from test_gpu_order import N_LIMIT, N_OK, T, array_rows, nd_rows, same_selection
+from test_gpu_order import LACKING, N_LIMIT, N_OK, T, array_rows, lacking_cut, nd_rows, same_selection
 from test_gpu_parse import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -105,6 +105,24 @@ def test_shapes(ctx, n, pattern):
     if pattern == "two-alternating" and n > 1:  # stability across waves, rounds and tiles: each key's rows in row order
         assert asc.order.tolist() == list(range(1, n, 2)) + list(range(0, n, 2))
         assert desc.order.tolist() == list(range(0, n, 2)) + list(range(1, n, 2))
+
+
+# ---- 1b. rows without a key at the seams: they travel through the sort as the missing bit of the class key ------------------------------
+SEAM_KEYS = ("", "abcdefg", "abcdefgh", "abcdefg", "", "abcdefgi")  # 0, 7 and 8 bytes: classes that end in round 0 and in round 1
+
+
+@pytest.mark.parametrize("pattern", sorted(LACKING))
+@pytest.mark.parametrize("n", [1, 2, 64, 65, OW.QTILE, OW.QTILE + 1])
+def test_rows_without_a_key_at_the_seams(ctx, n, pattern):
+    has = [LACKING[pattern](r, n) for r in range(n)]
+    # (the keys repeat, so rows tie; a row without one lacks the member, or holds a null or a number)
+    w = nd_rows(ctx, ['{"k":%s}' % js(SEAM_KEYS[(r * 5) % 6]) if has[r] else ('{"x":%d}' % r, '{"k":null}', '{"k":7}')[r % 3] for r in range(n)])
+    for limit in (0, lacking_cut(has)):
+        for got, want in both_directions(ctx, w, (b"k",), (pattern, n), limit):
+            kept = n if limit == 0 else min(n, limit)
+            tail = kept - min(kept, has.count(True))  # the kept rows without a key: behind the others, in row order
+            assert got.rows == kept and [st != OK for st in got.status.tolist()] == [False] * (kept - tail) + [True] * tail
+            assert got.order.tolist()[kept - tail:] == sorted(got.order.tolist()[kept - tail:])
 
 
 # ---- 2. the rounds ----------------------------------------------------------------------------------------------------------------------

@@ -1,11 +1,13 @@
 """Order rows by a string key on the device-resident tape, next to the host route a caller had before:
-python tools/order_strings_time.py [make] [date] [screen_name] [--out DIR]
+python tools/order_strings_time.py [make] [date] [screen_name] [missing10] [--out DIR]
 
-Three documents of 1 M rows, ND, no selection (the rows are the records):
+Four documents of 1 M rows, ND, no selection (the rows are the records):
   make         configs[4]: parking-citations x1000 ND, key Make: short keys, many duplicates -- one round
   date         the same document, key IssueData: 19-byte dates that share their first bytes -- three rounds
   screen_name  the statuses of twitter.json reduced to {"id":..,"created_at":..,"user":{"screen_name":..}} and repeated to 1 M rows,
                key user.screen_name: up to 15 bytes, 100 distinct keys of 10 000 rows each
+  missing10    {"id":<r>,"name":"user<5 digits>"}, 5000 names of 9 bytes -- two rounds --, one row in ten without the member: the rows
+               without a key travel through both sorts
 For each, alternating on the same device:
   (a) order_path_strings(key, descending, limit=10) + marshal_rows, fetched   "the 10 last by name", as text, and nothing else over PCIe
   (b) order_path_strings(key, limit=0), fetched                               the full ORDER BY: order and status of every row
@@ -17,6 +19,7 @@ of tests/order_strings_walk.max_rounds on the longest key.  The output is also w
 profiles/ of the repository), NN the next free number."""
 import json
 import os
+import random
 import re
 import statistics
 import sys
@@ -65,6 +68,9 @@ def document(name):
         return workloads.c5_parking_nd(1000).rstrip(b"\n"), (b"Make",)
     if name == "date":
         return workloads.c5_parking_nd(1000).rstrip(b"\n"), (b"IssueData",)
+    if name == "missing10":  # synthetic: 5000 names of 9 bytes (two rounds), one row in ten without the key member
+        rnd = random.Random(30)
+        return "\n".join('{"id":%d}' % r if r % 10 == 9 else '{"id":%d,"name":"user%05d"}' % (r, rnd.randrange(5000)) for r in range(N)).encode(), (b"name",)
     statuses = json.loads(fixtures.load("twitter"))["statuses"]
     slim = [json.dumps({"id": s["id"], "created_at": s["created_at"], "user": {"screen_name": s["user"]["screen_name"]}}, separators=(",", ":"))
             for s in statuses]
@@ -87,7 +93,7 @@ def host_sort(off, data, st):
 
 def main():
     ctx = sjhip.Context(0)
-    names = [a for a in ARGS if a in ("make", "date", "screen_name")] or ["make", "date", "screen_name"]
+    names = [a for a in ARGS if a in ("make", "date", "screen_name", "missing10")] or ["make", "date", "screen_name", "missing10"]
     out_dir = ARGS[ARGS.index("--out") + 1] if "--out" in ARGS else os.path.join(ROOT, "profiles")
     say(f"# {torch.cuda.get_device_name(0)}; host wall time in ms, median of {REPS} warmed calls, device-resident result, 1 M rows")
     for name in names:

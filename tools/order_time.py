@@ -1,11 +1,12 @@
 """Order rows on the device-resident tape, next to the host route a caller had before:
-python tools/order_time.py [parking] [digits3] [digits8] [--out DIR]
+python tools/order_time.py [parking] [digits3] [digits8] [missing10] [--out DIR]
 
-Three documents of 1 M rows, ND, no selection (the rows are the records):
+Four documents of 1 M rows, ND, no selection (the rows are the records):
   parking   configs[4]: parking-citations x1000 ND, key Fine FLOAT.  Every member of this document is a string, so no key converts:
             the walk, the compaction and the narrowing run, the sort takes no pass
   digits3   {"id":<r>,"retweet_count":<below 2^20>,"text":"..."}: three digits of the key vary, the plan takes three passes
   digits8   the same rows with a random 64-bit key under INT: all eight digits vary
+  missing10 the rows of digits3, one in ten without the key member: the rows without a key travel through both sorts
 For each, alternating on the same device:
   (a) order_path(key, kind, descending, limit=10) + marshal_rows, fetched     "the 10 largest", as text, and nothing else over PCIe
   (b) order_path(key, kind, limit=0), fetched                                 the full ORDER BY: order, values, status of every row
@@ -62,11 +63,13 @@ def document(ctx, name):
     if name == "parking":
         return workloads.c5_parking_nd(1000).rstrip(b"\n"), (b"Fine",), ctx.COL_FLOAT
     rnd = random.Random(6)
-    if name == "digits3":
+    if name in ("digits3", "missing10"):
         key = lambda: rnd.randrange(1 << 20)  # noqa: E731
     else:
         key = lambda: rnd.randrange(-(1 << 63), 1 << 63)  # noqa: E731
     lines = ['{"id":%d,"retweet_count":%d,"text":"status number %d"}' % (r, key(), r) for r in range(N)]
+    if name == "missing10":
+        lines = ['{"id":%d,"text":"status number %d"}' % (r, r) if r % 10 == 9 else line for r, line in enumerate(lines)]
     return "\n".join(lines).encode(), (b"retweet_count",), ctx.COL_INT
 
 
@@ -86,7 +89,7 @@ def pass_count(vals, st, kind):
 
 def main():
     ctx = sjhip.Context(0)
-    names = [a for a in ARGS if a in ("parking", "digits3", "digits8")] or ["parking", "digits3", "digits8"]
+    names = [a for a in ARGS if a in ("parking", "digits3", "digits8", "missing10")] or ["parking", "digits3", "digits8", "missing10"]
     out_dir = ARGS[ARGS.index("--out") + 1] if "--out" in ARGS else os.path.join(ROOT, "profiles")
     say(f"# {torch.cuda.get_device_name(0)}; host wall time in ms, median of {REPS} warmed calls, device-resident result, 1 M rows")
     for name in names:
