@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/sjhip.h"
+#include "sj_bounds.h"
 #include "sj_chunk.h"
 #include "sj_ctx.h"
 #include "sj_host.h"
@@ -34,7 +35,7 @@ struct DocDesc {
 };
 
 // The document that holds byte `p` of the packed message (or whose separator it is): the last one with dst <= p
-__device__ __forceinline__ uint32_t doc_of(const DocDesc *__restrict__ docs, uint32_t n_docs, uint64_t p) {
+__device__ __forceinline__ uint32_t doc_of(SJ_ARR_PARAM(const DocDesc) docs, uint32_t n_docs, uint64_t p) {
     uint32_t lo = 0, hi = n_docs;  // docs[lo].dst <= p < docs[hi].dst
     while (hi - lo > 1) {
         const uint32_t mid = lo + (hi - lo) / 2;
@@ -60,9 +61,11 @@ __device__ __forceinline__ bool doc_end_ok(const uint8_t *__restrict__ s, uint64
 // its document with a binary search over the descriptors and walks on from there -- copy with '\n' -> '\r', the
 // separator behind every document but the last, and the end check of the documents whose last byte it owns.
 // IN_PLACE: the documents already lie at their packed offsets (host packing), only translation and separators.
+// src (the caller's buffer up to the end of its last document), docs (n_docs) and dst (total) are bounds-checked views in the
+// debug build (sj_bounds.h): the 16-byte accesses and the end check state their range, the byte loop is checked per element.
 template <bool IN_PLACE>
-__global__ __launch_bounds__(256) void k_batch_pack(const uint8_t *__restrict__ src, const DocDesc *__restrict__ docs,
-                                                    uint8_t *__restrict__ dst, uint32_t n_docs, uint64_t total,
+__global__ __launch_bounds__(256) void k_batch_pack(SJ_ARR_PARAM(const uint8_t) src, SJ_ARR_PARAM(const DocDesc) docs,
+                                                    SJ_ARR_PARAM(uint8_t) dst, uint32_t n_docs, uint64_t total,
                                                     unsigned int *bad_host) {
     const uint64_t p0 = (uint64_t)blockIdx.x * 4096 + (uint64_t)threadIdx.x * 16;
     if (p0 >= total) return;
@@ -72,10 +75,10 @@ __global__ __launch_bounds__(256) void k_batch_pack(const uint8_t *__restrict__ 
     bool bad = false;
     if (p1 <= d.dst + d.len && p0 + 16 == p1) {
         // sixteen bytes of one document (the source is byte-aligned at best: unaligned 16-byte loads are fine on gfx950)
-        uint4 v = *reinterpret_cast<const uint4 *>(IN_PLACE ? dst + p0 : src + d.src + (p0 - d.dst));
+        uint4 v = *reinterpret_cast<const uint4 *>(IN_PLACE ? sj::arr_at(dst, p0, 16) : sj::arr_at(src, d.src + (p0 - d.dst), 16));
         v.x = sj::newlines_to_cr(v.x); v.y = sj::newlines_to_cr(v.y); v.z = sj::newlines_to_cr(v.z); v.w = sj::newlines_to_cr(v.w);
-        *reinterpret_cast<uint4 *>(dst + p0) = v;
-        if (!IN_PLACE && p1 == d.dst + d.len) bad = !doc_end_ok(src + d.src, d.len);
+        *reinterpret_cast<uint4 *>(sj::arr_at(dst, p0, 16)) = v;
+        if (!IN_PLACE && p1 == d.dst + d.len) bad = !doc_end_ok(sj::arr_at(src, d.src, d.len), d.len);
     } else {
         uint64_t next_dst = k + 1 < n_docs ? docs[k + 1].dst : ~0ull;
         for (uint64_t p = p0; p < p1; p++) {
@@ -87,7 +90,7 @@ __global__ __launch_bounds__(256) void k_batch_pack(const uint8_t *__restrict__ 
             if (off < d.len) {
                 const uint8_t b = IN_PLACE ? dst[p] : src[d.src + off];
                 dst[p] = b == '\n' ? (uint8_t)'\r' : b;
-                if (!IN_PLACE && off + 1 == d.len) bad |= !doc_end_ok(src + d.src, d.len);
+                if (!IN_PLACE && off + 1 == d.len) bad |= !doc_end_ok(sj::arr_at(src, d.src, d.len), d.len);
             } else {
                 dst[p] = '\n';  // the separator behind document k
             }
@@ -97,6 +100,29 @@ __global__ __launch_bounds__(256) void k_batch_pack(const uint8_t *__restrict__ 
 }
 
 }  // namespace
+
+// debug build (-DSJ_DEBUG_BOUNDS): an out-of-bounds access of the packing kernel fails the call like one of the parse (this
+// translation unit's record; the stream is waited on first, the kernel may still run behind a parse that failed early)
+// -> the code of the call: rc, the parse's, unless the packing recorded a violation (then the result is dropped)
+static int batch_bounds_result(sjhip_ctx *ctx, int rc, size_t *tape_len, size_t *strings_len) {
+#if defined(SJ_DEBUG_BOUNDS)
+    sj::BoundsHit h;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return SJHIP_ERR_HIP;
+    if (sj::bounds_take(&h) && h.hits) {
+        sj::begin_parse(ctx);
+        if (tape_len) *tape_len = 0;
+        if (strings_len) *strings_len = 0;
+        sj::ctx_set_error(ctx, "bounds check: %u out-of-bounds accesses of the batch packing, the first to array %u (sj_bounds.h ArrId) at element %llu of %llu",
+                          h.hits, h.id, h.index, h.size);
+        return SJHIP_ERR_HIP;
+    }
+#else
+    (void)ctx;
+    (void)tape_len;
+    (void)strings_len;
+#endif
+    return rc;
+}
 
 static int batch_common(sjhip_ctx *ctx, size_t n, uint32_t flags, size_t *tape_len, size_t *strings_len) {
     if (tape_len) *tape_len = 0;
@@ -197,13 +223,15 @@ int sjhip_parse_batch(sjhip_ctx *ctx, const uint8_t *const *msgs, const size_t *
     const DocDesc *d_docs = nullptr;
     rc = upload_docs(ctx, docs, &d_docs);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_batch_pack<true>, dim3((unsigned)((total + 4095) / 4096)), dim3(256), 0, ctx->stream, (const uint8_t *)nullptr, d_docs,
-                       (uint8_t *)ctx->d_msg.p, (uint32_t)n, (uint64_t)total, (unsigned int *)nullptr);
+    hipLaunchKernelGGL(k_batch_pack<true>, dim3((unsigned)((total + 4095) / 4096)), dim3(256), 0, ctx->stream,
+                       SJ_ARR((const uint8_t *)nullptr, 0, sj::A_BATCH_SRC), SJ_ARR(d_docs, n, sj::A_BATCH_DOCS),
+                       SJ_ARR((uint8_t *)ctx->d_msg.p, total, sj::A_BATCH_DST), (uint32_t)n, (uint64_t)total, (unsigned int *)nullptr);
     if (hipGetLastError() != hipSuccess) return SJHIP_ERR_HIP;
     const size_t last = n - 1;
     uint8_t last_byte = msgs[last][host_off[last] + docs[last].len - 1];
     if (last_byte == '\n') last_byte = '\r';  // (cannot happen: trimmed)
-    return sj::parse_packed(ctx, (size_t)total, flags | SJHIP_FLAG_NDJSON, last_byte, 1, tape_len, strings_len);
+    rc = sj::parse_packed(ctx, (size_t)total, flags | SJHIP_FLAG_NDJSON, last_byte, 1, tape_len, strings_len);
+    return batch_bounds_result(ctx, rc, tape_len, strings_len);
 }
 
 int sjhip_parse_batch_device(sjhip_ctx *ctx, const void *d_buf, const size_t *offs, const size_t *lens, size_t n,
@@ -217,12 +245,14 @@ int sjhip_parse_batch_device(sjhip_ctx *ctx, const void *d_buf, const size_t *of
     // an empty or all-whitespace one, a scalar, a truncated one -- fails the batch with the stage-1 code like Parse()
     // of it would (checked on the device while the documents are packed)
     std::vector<DocDesc> docs(n);
-    uint64_t total = 0;
+    uint64_t total = 0, src_end = 0;  // src_end: the end of the last document in the caller's buffer (the debug build's bound of src)
     for (size_t k = 0; k < n; k++) {
         if (lens[k] == 0) return SJHIP_ERR_STAGE1;
         docs[k] = DocDesc{offs[k], total, lens[k]};
         total += lens[k] + (k + 1 < n ? 1 : 0);
+        if ((uint64_t)offs[k] + lens[k] > src_end) src_end = (uint64_t)offs[k] + lens[k];
     }
+    (void)src_end;
     if (total > 0xffffffc0ull) {
         sj::ctx_set_error(ctx, "sjhip_parse_batch_device: the packed message exceeds 4 GiB");
         return SJHIP_ERR_TOOBIG;
@@ -236,10 +266,36 @@ int sjhip_parse_batch_device(sjhip_ctx *ctx, const void *d_buf, const size_t *of
     // parse below synchronises the stream, after which the word is final
     volatile unsigned int *bad = (volatile unsigned int *)(ctx->h_scratch + 1024);
     *bad = 0;
-    hipLaunchKernelGGL(k_batch_pack<false>, dim3((unsigned)((total + 4095) / 4096)), dim3(256), 0, ctx->stream, (const uint8_t *)d_buf, d_docs,
-                       (uint8_t *)ctx->d_msg.p, (uint32_t)n, (uint64_t)total, (unsigned int *)bad);
+    hipLaunchKernelGGL(k_batch_pack<false>, dim3((unsigned)((total + 4095) / 4096)), dim3(256), 0, ctx->stream,
+                       SJ_ARR((const uint8_t *)d_buf, src_end, sj::A_BATCH_SRC), SJ_ARR(d_docs, n, sj::A_BATCH_DOCS),
+                       SJ_ARR((uint8_t *)ctx->d_msg.p, total, sj::A_BATCH_DST), (uint32_t)n, (uint64_t)total, (unsigned int *)bad);
     if (hipGetLastError() != hipSuccess) return SJHIP_ERR_HIP;
-    rc = sj::parse_packed(ctx, (size_t)total, flags | SJHIP_FLAG_NDJSON, 0, 0, tape_len, strings_len);
+    // ParseND trims its message (parse_json_amd64.go:55), and the parse on the device expects the trimmed one: whitespace behind
+    // the last document's last token is whitespace of the packed message's end.  Its length is read from the caller's buffer,
+    // a window at a time from the end; an all-whitespace last document fails like anywhere else in the batch.
+    uint64_t tail_ws = 0;
+    uint8_t last_byte = 0;
+    bool found = false;
+    {
+        const DocDesc &ld = docs[n - 1];
+        uint8_t win[256];
+        while (tail_ws < ld.len && !found) {
+            const size_t w = ld.len - tail_ws < sizeof win ? (size_t)(ld.len - tail_ws) : sizeof win;
+            if (hipMemcpyAsync(win, (const uint8_t *)d_buf + ld.src + (ld.len - tail_ws - w), w, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                hipStreamSynchronize(ctx->stream) != hipSuccess) {
+                sj::ctx_set_error(ctx, "sjhip_parse_batch_device: reading the end of the last document failed");
+                return SJHIP_ERR_HIP;
+            }
+            for (size_t j = w; j-- > 0 && !found;) {
+                const uint8_t b = win[j];
+                if (b == ' ' || b == '\t' || b == '\n' || b == '\r') tail_ws++;
+                else last_byte = b, found = true;
+            }
+        }
+    }
+    if (!found) return batch_bounds_result(ctx, SJHIP_ERR_STAGE1, tape_len, strings_len);
+    rc = sj::parse_packed(ctx, (size_t)(total - tail_ws), flags | SJHIP_FLAG_NDJSON, last_byte, 1, tape_len, strings_len);
+    rc = batch_bounds_result(ctx, rc, tape_len, strings_len);
     if (rc != SJHIP_OK && rc != SJHIP_ERR_STAGE1 && rc != SJHIP_ERR_STAGE2) return rc;
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) return SJHIP_ERR_HIP;  // (a parse that failed early may not have waited)
     if (*bad) {  // a document that Parse() rejects in stage 1: that code wins (parse_json_amd64.go:97-105,123-126)

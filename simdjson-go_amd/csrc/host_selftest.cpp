@@ -792,6 +792,11 @@ extern "C" int sj_selftest_newlines_to_cr(void) {
     return 0;
 }
 
+// the same routine over an array of words of the caller's choosing (tests/test_batch_geometry.py)
+extern "C" void sj_selftest_newlines_to_cr_words(const uint32_t *in, uint32_t *out, size_t n) {
+    for (size_t k = 0; k < n; k++) out[k] = newlines_to_cr(in[k]);
+}
+
 // sj_result.h: a byte-coded sequence of transitions applied to a fresh ResultState; bits_out[k] is the predicate set after step k.
 //   0 begin_parse   1 drop_result   2 parse_pending   3 + 4 * shard + 2 * key_flags + packed: parse_done of one tape word
 //   11 parse_done of an empty tape   12 parse_sharded   13 claim_shared   14 / 15 / 16 publish filtered / serialized / marshaled

@@ -59,7 +59,10 @@ enum ArrId : uint32_t {
     A_SORT, A_SORT_HIST,
     // the unnested rows (query.hip, sjhip_unnest_rows): the target range of every parent row / the status byte of every parent, in
     // the work arrays and in the product / the parent number of every new row / the parent offsets
-    A_UNNEST_RANGE, A_UNNEST_STATUS, A_UNNEST_PARENT, A_UNNEST_OFF
+    A_UNNEST_RANGE, A_UNNEST_STATUS, A_UNNEST_PARENT, A_UNNEST_OFF,
+    // the packing kernel of the batch (batch_api.hip, k_batch_pack): the caller's device buffer up to the end of its last document /
+    // the document descriptors / the packed message
+    A_BATCH_SRC, A_BATCH_DOCS, A_BATCH_DST
 };
 
 #if defined(SJ_DEBUG_BOUNDS)

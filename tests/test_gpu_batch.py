@@ -149,7 +149,8 @@ def test_batch_of_256_twitter():
 
 
 def test_batch_of_many_tiny_documents():
-    """More documents than one grid dimension holds (65 535): the packing kernels walk (y, z) block indices."""
+    """More documents than one grid dimension holds (65 535): the packing kernel has a 1-D grid over the packed bytes (one block
+    per 4 KiB), so the number of documents does not enter the grid at all."""
     import sjhip
     ctx = sjhip.Context(0)
     n = 70001
