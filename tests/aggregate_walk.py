@@ -18,6 +18,8 @@ statuses -- and is reduced in plain Python:
   record_arrays  per_record as the six arrays the device call fills (bit patterns; sum split into lo and hi of 128 bits)
 
 AGG_TILE: the rows of one tile of the device's reduction (csrc/query.hip); the shapes of tests/test_gpu_aggregate.py come from it.
+The geometry above one tile -- the two slots a tile hands on, the levels, the rows below a tile of a fold (32 768) and the
+association of a float sum -- is restated in tests/agg_geometry.py; the shapes of tests/test_gpu_aggregate_seams.py come from that.
 Pinned by tests/test_aggregate_walk.py."""
 import math
 
