@@ -123,11 +123,16 @@ struct TileMap {
     u32 su;  // the tiles from nf on hold su units each (1 <= su <= UNITS)
     u32 nu;  // units of the message: ceil((lead + len) / 4096); a tile's units from nu on are void
 };
-static constexpr u64 VOID_UNIT = 1ull << 40;
+// Unit numbers are 32 bits wide everywhere (a message of SINGLE_LIMIT = 2^38 bytes has 2^26 units).  Byte offsets into a
+// message (`Off`: lead, end, the offset of a unit or a chunk) are 32 bits wide in plain stage 1, whose launches refuse
+// lead + len >= 2^32, and 64 bits wide in the whole parse, which lets the positions wrap (parse_api.hip): the wave-uniform
+// state of the tile loop is then half as many scalar registers.  A 64-bit address is formed once, where a pointer is built.
+// The one 32-bit sum that can wrap is the END of the top unit or chunk ((unit + 1) * 4096 == 2^32): nothing computes it.
+static constexpr u32 VOID_UNIT = 0xffffffffu;
 template <int UNITS>
-__device__ __forceinline__ u64 tile_unit(TileMap tm, u32 t, int local) {  // wave-uniform arguments
-    const u64 u = t < tm.nf ? (u64)t * UNITS + (u64)local
-                            : ((u32)local < tm.su ? (u64)tm.nf * UNITS + (u64)(t - tm.nf) * tm.su + (u64)local : VOID_UNIT);
+__device__ __forceinline__ u32 tile_unit(TileMap tm, u32 t, int local) {  // wave-uniform arguments (t: a tile of the message)
+    const u32 u = t < tm.nf ? t * (u32)UNITS + (u32)local
+                            : ((u32)local < tm.su ? tm.nf * (u32)UNITS + (t - tm.nf) * tm.su + (u32)local : VOID_UNIT);
     return u < tm.nu ? u : VOID_UNIT;
 }
 
@@ -178,7 +183,8 @@ __device__ __forceinline__ u32 lanes_below_popc(u64 mask) {  // popcount of mask
 // ---- carries into the first chunk of a wave unit -------------------------------------------
 // Parity of the backslash run that ends right before byte `p` (p > lead), i.e. the reference's
 // prev_iter_ends_odd_backslash at a chunk boundary (find_odd_backslash_sequences_amd64.s:34-58).
-__device__ __forceinline__ u32 peek_backslash_parity(const u8 *base, u64 lead, u64 p, u64 end = ~0ull) {
+template <typename Off>
+__device__ __forceinline__ u32 peek_backslash_parity(const u8 *base, Off lead, Off p, Off end = ~(Off)0) {
     u32 n = 0;
     if (p > end) return 0;  // (a chunk of the last unit that lies behind the message: blanks in front of it)
     while (p > lead && base[p - 1] == '\\') {
@@ -191,20 +197,22 @@ __device__ __forceinline__ u32 peek_backslash_parity(const u8 *base, u64 lead, u
 static constexpr u64 BS8 = 0x5c5c5c5c5c5c5c5cull, SP8 = 0x2020202020202020ull;
 
 // carry_in of the chunk at `off` from the 8 bytes before it
-__device__ __forceinline__ u32 carry_from_prev8(u64 prev8, const u8 *base, u64 lead, u64 off) {
+template <typename Off>
+__device__ __forceinline__ u32 carry_from_prev8(u64 prev8, const u8 *base, Off lead, Off off) {
     const u64 x = prev8 ^ BS8;
-    if (x == 0) return peek_backslash_parity(base, lead, off);  // >= 8 backslashes: walk (rare)
+    if (x == 0) return peek_backslash_parity<Off>(base, lead, off);  // >= 8 backslashes: walk (rare)
     return ((u32)__builtin_clzll(x) >> 3) & 1u;
 }
 // pseudo_pred carry from the previous byte only: whitespace, one of {}[]:, or an
 // unescaped quote.
-__device__ __forceinline__ u32 pseudo_pred_from_prev8(u64 prev8, const u8 *base, u64 lead, u64 off) {
+template <typename Off>
+__device__ __forceinline__ u32 pseudo_pred_from_prev8(u64 prev8, const u8 *base, Off lead, Off off) {
     const u32 b = (u32)(prev8 >> 56);
     if (b == ' ' || b == '\t' || b == '\n' || b == '\r') return 1;
     if (b == '{' || b == '}' || b == '[' || b == ']' || b == ':' || b == ',') return 1;
     if (b != '"') return 0;
     const u64 x = (prev8 ^ BS8) << 8;
-    if (x == 0) return peek_backslash_parity(base, lead, off - 1) ^ 1u;
+    if (x == 0) return peek_backslash_parity<Off>(base, lead, off - 1) ^ 1u;
     return ((((u32)__builtin_clzll(x | 0xffu) >> 3) & 1u)) ^ 1u;
 }
 
@@ -221,40 +229,46 @@ __device__ __forceinline__ u32 pseudo_pred_from_prev8(u64 prev8, const u8 *base,
 // carries into its first chunk come from -- fetched with the chunk so that nothing waits for a scalar load later
 // (measured -2.5 %).  One unit per wave is in flight; a second one (each pass loaded a whole tile ahead) measured
 // 5-8 % SLOWER: the flatten's stores then queue behind twice as many loads.
+// (a native vector, not HIP's uint4 struct: a chunk quarter stays ONE 128-bit value from its load to the classification.  As
+// a struct of four words it was taken apart and put together again by the compiler as it pleased -- whether the edge unit's LDS
+// reads came out as ds_read_b128 into the registers of the global loads, or as dword pairs with ~160 v_mov and a wait right
+// behind every global load to shuffle them, flipped with unrelated changes to the kernel, profiles/r28_stage1_group_ab.txt 3.)
+typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 struct UnitRegs {
-    uint4 v[4];
+    u32x4 v[4];
     u64 prev8;
 };
 // The first or the last unit of a message (at most two units per message of the launch).  A chunk inside the message is loaded, a chunk
 // outside is blanks, and the (at most two) chunks the message covers only partly -- the one with its first byte when the
 // message does not begin on a 64-byte boundary, the one with its last -- are fetched a byte per lane (only message bytes are
 // touched), laid down in 64 bytes of LDS and picked up by the lane that owns the chunk.
-__device__ __forceinline__ void edge_unit_load(const u8 *__restrict__ base, u64 lead, u64 end, u64 unit, int lane, UnitRegs &r,
+template <typename Off>
+__device__ __forceinline__ void edge_unit_load(const u8 *__restrict__ base, Off lead, Off end, u32 unit, int lane, UnitRegs &r,
                                                u8 *s_edge_w) {
-    const u64 c0 = unit * 4096 + (u64)lane * 64;
-    const uint4 blank = make_uint4(0x20202020u, 0x20202020u, 0x20202020u, 0x20202020u);
+    const Off c0 = (Off)unit * 4096 + (Off)lane * 64;
+    const u32x4 blank = {0x20202020u, 0x20202020u, 0x20202020u, 0x20202020u};
 #pragma unroll
     for (int q = 0; q < 4; q++) r.v[q] = blank;
-    if (c0 >= lead && c0 + 64 <= end) {
-        const uint4 *p = reinterpret_cast<const uint4 *>(base + c0);
+    if (c0 >= lead && c0 < end && end - c0 >= 64) {  // (not c0 + 64 <= end: the top chunk of a 32-bit message ends at 2^32)
+        const u32x4 *p = reinterpret_cast<const u32x4 *>(base + c0);
 #pragma unroll
         for (int q = 0; q < 4; q++) r.v[q] = p[q];
     }
-    const u64 cl = (end - 1) & ~63ull;  // the chunk that holds the last byte (len > 0)
+    const Off cl = (end - 1) & ~(Off)63;  // the chunk that holds the last byte (len > 0)
     const bool head = unit == 0 && lead > 0;
     const bool tail = (end & 63) != 0 && (cl >> 12) == unit && !(head && cl == 0);  // (one chunk may hold both ends: once)
 #pragma unroll 1
     for (int k = 0; k < 2; k++) {
         if (!(k == 0 ? head : tail)) continue;  // (uniform)
-        const u64 pc = k == 0 ? 0ull : cl;
-        const u64 a = pc + (u64)lane;
+        const Off pc = k == 0 ? (Off)0 : cl;
+        const Off a = pc + (Off)lane;
         u8 b = 0x20;
         if (a >= lead && a < end) b = base[a];
         s_edge_w[lane] = b;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
         if (c0 == pc) {
-            const uint4 *e = reinterpret_cast<const uint4 *>(s_edge_w);
+            const u32x4 *e = reinterpret_cast<const u32x4 *>(s_edge_w);
 #pragma unroll
             for (int q = 0; q < 4; q++) r.v[q] = e[q];
         }
@@ -262,17 +276,19 @@ __device__ __forceinline__ void edge_unit_load(const u8 *__restrict__ base, u64 
         __builtin_amdgcn_wave_barrier();  // (the window is read: the second round may write it)
     }
 }
-__device__ __forceinline__ void unit_issue(const u8 *__restrict__ base, u64 lead, u64 end, u64 unit, u32 nu, int lane, UnitRegs &r,
+template <typename Off>
+__device__ __forceinline__ void unit_issue(const u8 *__restrict__ base, Off lead, Off end, u32 unit, u32 nu, int lane, UnitRegs &r,
                                            u8 *s_edge_w) {
+    const u8 *__restrict__ ub = base + (u64)unit * 4096;  // (the 64-bit address of the unit: formed here, once)
     if (unit != 0 && unit + 1 != nu) {  // (uniform)
-        const uint4 *p = reinterpret_cast<const uint4 *>(base + unit * 4096) + lane * 4;
+        const u32x4 *p = reinterpret_cast<const u32x4 *>(ub) + lane * 4;
 #pragma unroll
         for (int q = 0; q < 4; q++) r.v[q] = p[q];
     } else {
-        edge_unit_load(base, lead, end, unit, lane, r, s_edge_w);
+        edge_unit_load<Off>(base, lead, end, unit, lane, r, s_edge_w);
     }
     // (unit 0 has nothing in front of it: its own first bytes are read instead and not used)
-    r.prev8 = *reinterpret_cast<const u64 *>(base + (unit ? unit * 4096 - 8 : 0));
+    r.prev8 = *reinterpret_cast<const u64 *>(unit ? ub - 8 : base);
 }
 // ---- the look-back (wave 0 of a block) -------------------------------------------------------
 // Resumable look-back: one call = one window of 256 descriptors (4 per lane, nearest first).
@@ -360,19 +376,27 @@ __device__ __forceinline__ int lookback_eval(const u64 (&d)[4], LookBack &lb, in
 // s_unit[u] = parity << 31 | ctrl-in-string(inside) << 27 | ctrl-in-string(outside) << 26 |
 //             count(inside) << 13 | count(outside)          for unit u = pass * WAVES + wave.
 __device__ __forceinline__ bool par_ballot_any(u64 m) { return __ballot(((u32)m | (u32)(m >> 32)) != 0) != 0; }
-template <int BLOCK, int CH, bool NDJSON, bool AUX>
-__device__ __forceinline__ void phase_a(const u8 *__restrict__ base, u64 lead, u64 end, TileMap tm, u32 t,
-                                        const u8 *__restrict__ base_n, u64 lead_n, u64 end_n, TileMap tm_n, u32 t_next,
+// A, N: the messages of the tile and of the tile behind it (S1Msg below; t_a, t_n: global tile ids).  Their fields are read
+// where they are used -- from the kernel arguments, through the scalar cache -- and not handed in as values: N's are needed
+// once, where the last pass issues the loads of the next tile, and nothing of either message has to stay in registers
+// across the classification.
+template <int BLOCK, int CH, bool NDJSON, bool AUX, typename MSG>
+__device__ __forceinline__ void phase_a(const MSG &A, u32 t_a, const MSG &N, u32 t_n,
                                         bool has_next, int lane, int wave, UnitRegs &pf, u64 *m, u32 *pre, u32 *s_unit,
                                         const S1Aux &aux, u64 (&kp)[CH][4], uint2 *s_ucnt,
                                         u32 &seen_st, u8 *s_edge_w, bool TOP = false) {
     constexpr int WAVES = BLOCK / 64;
     constexpr int UNITS = WAVES * CH;
-    // the loads of the unit behind pass k: of this tile, or (last pass) of the next tile -- t / t_next are tiles of their own
-    // messages (base, tm, ... and base_n, tm_n, ...: the same message unless the launch holds several and t is one's last tile)
-    auto issue_next = [&](int k, u64 unit_nx) {
-        if (k + 1 < CH) unit_issue(base, lead, end, unit_nx, tm.nu, lane, pf, s_edge_w);
-        else unit_issue(base_n, lead_n, end_n, unit_nx, tm_n.nu, lane, pf, s_edge_w);
+    typedef typename std::conditional<AUX, u64, u32>::type Off;
+    const u8 *__restrict__ const base = A.base;
+    const Off lead = (Off)A.lead, end = (Off)(A.lead + A.len);
+    const TileMap tm = A.tm;
+    const u32 t = t_a - A.tile0;
+    // the loads of the unit behind pass k: of this tile, or (last pass) of the next tile -- a tile of its own message
+    // (the same message unless the launch holds several and t is one's last tile)
+    auto issue_next = [&](int k, u32 unit_nx) {
+        if (k + 1 < CH) unit_issue<Off>(base, lead, end, unit_nx, tm.nu, lane, pf, s_edge_w);
+        else unit_issue<Off>(N.base, (Off)N.lead, (Off)(N.lead + N.len), unit_nx, N.tm.nu, lane, pf, s_edge_w);
     };
 #if defined(SJ_S1_ROLL)
 #pragma unroll 1
@@ -380,10 +404,10 @@ __device__ __forceinline__ void phase_a(const u8 *__restrict__ base, u64 lead, u
 #pragma unroll
 #endif
     for (int k = 0; k < CH; k++) {
-        const u64 unit = tile_unit<UNITS>(tm, t, k * WAVES + wave);  // wave-uniform
+        const u32 unit = tile_unit<UNITS>(tm, t, k * WAVES + wave);  // wave-uniform
         // the unit behind this one (next pass, or the first pass of the next tile): its loads are issued below
-        const u64 unit_nx = k + 1 < CH ? tile_unit<UNITS>(tm, t, (k + 1) * WAVES + wave)
-                                       : (has_next ? tile_unit<UNITS>(tm_n, t_next, wave) : VOID_UNIT);
+        const u32 unit_nx = k + 1 < CH ? tile_unit<UNITS>(tm, t, (k + 1) * WAVES + wave)
+                                       : (has_next ? tile_unit<UNITS>(N.tm, t_n - N.tile0, wave) : VOID_UNIT);
         if (unit == VOID_UNIT) {  // a tail tile holds fewer units than a full one: nothing to classify
             m[(k * 2 + 0) * 64 + lane] = 0;
             m[(k * 2 + 1) * 64 + lane] = 0;
@@ -394,7 +418,7 @@ __device__ __forceinline__ void phase_a(const u8 *__restrict__ base, u64 lead, u
             if (unit_nx != VOID_UNIT) issue_next(k, unit_nx);
             continue;
         }
-        const u64 unit_off = unit * 4096;
+        const Off unit_off = (Off)unit * 4096;
         u32 w[16];
 #pragma unroll
         for (int q = 0; q < 4; q++) {
@@ -406,8 +430,8 @@ __device__ __forceinline__ void phase_a(const u8 *__restrict__ base, u64 lead, u
         u32 carry0 = 0, pp0 = 1;  // carries into lane 0 from the bytes in front of the unit
         if (unit != 0) {  // those 8 bytes are message bytes: lead < 64, and the unit begins in front of `end`
             const u64 prev8 = ((u64)uniform((u32)(pf.prev8 >> 32)) << 32) | uniform((u32)pf.prev8);
-            carry0 = carry_from_prev8(prev8, base, lead, unit_off);
-            pp0 = pseudo_pred_from_prev8(prev8, base, lead, unit_off);
+            carry0 = carry_from_prev8<Off>(prev8, base, lead, unit_off);
+            pp0 = pseudo_pred_from_prev8<Off>(prev8, base, lead, unit_off);
         }
 
         // the next pass goes in flight before this one is classified: a whole pass of math to arrive in (the compiler
@@ -443,7 +467,7 @@ __device__ __forceinline__ void phase_a(const u8 *__restrict__ base, u64 lead, u
             const bool all_bs = c.bs == ~0ull;
             const u32 trail_odd = all_bs ? 0u : ((u32)__builtin_clzll(~c.bs) & 1u);
             u32 carry_in = wave_shift_up(trail_odd, carry0);
-            if (__ballot(all_bs) != 0 && lane != 0) carry_in = peek_backslash_parity(base, lead, unit_off + (u64)lane * 64, end);
+            if (__ballot(all_bs) != 0 && lane != 0) carry_in = peek_backslash_parity<Off>(base, lead, unit_off + (Off)lane * 64, end);
             const u64 escaped = escaped_mask(c.bs, carry_in);
             quote_bits &= ~escaped;
             if (AUX) {
@@ -474,7 +498,7 @@ __device__ __forceinline__ void phase_a(const u8 *__restrict__ base, u64 lead, u
         // (AUX: the mask arrays are there -- stage1_launch refuses kinds without them -- and a unit that is not void begins in
         // front of `end`: no tests here, each one would be a branch in the middle of the pass)
         if (AUX && !SJ_S1EXP(aux, 16)) {  // whole parse: stage 2 unescapes the strings from these masks (stage2.hip)
-            const u64 ci = unit * 64 + (u64)lane;
+            const u64 ci = (u64)unit * 64 + (u64)lane;
             aux.qm[ci] = qm;  // relative to the state at the start of the unit: resolved with aux.unit_h
             aux.st[ci] = starters;
             // (hypothesis-free: an escape outside a string makes the document invalid anyway)
@@ -539,8 +563,8 @@ __device__ __forceinline__ void tile_aggregate(const u32 *s_unit, int lane, u32 
 // configs[4], whose 78 M tokens are one gather each.)
 template <int BLOCK, int CH, bool KIND>
 __device__ __forceinline__ bool flatten_tile(TileMap tm, u64 *m, const u64 *kpl, const u32 *pre, const u32 *s_unit, u32 pre_mask, u32 G, u64 BASE, u32 t,
-                                             u64 lead, int lane, int wave, SJ_ARR_PARAM(u32) out_pos, u64 pos_cap,
-                                             u64 &tile_end, Arr<u8> unit_h, u64 len_, Arr<u8> kind_out, const S1Aux &aux,
+                                             u32 lead, int lane, int wave, SJ_ARR_PARAM(u32) out_pos, u64 pos_cap,
+                                             u64 &tile_end, Arr<u8> unit_h, Arr<u8> kind_out, const S1Aux &aux,
                                              const uint2 *s_ucnt) {
     constexpr int WAVES = BLOCK / 64;
     constexpr int UNITS = WAVES * CH;
@@ -567,8 +591,8 @@ __device__ __forceinline__ bool flatten_tile(TileMap tm, u64 *m, const u64 *kpl,
         sel[k] = m[(k * 2 + (int)h) * 64 + lane];
         const u32 both = pre[k * 64 + lane];
         upto[k] = h ? both >> 16 : both & 0xffffu;
-        const u64 un = tile_unit<UNITS>(tm, t, k * WAVES + wave);
-        if (unit_h && lane == 0 && un * 4096 < lead + len_) {  // (a void unit lies behind everything)
+        const u32 un = tile_unit<UNITS>(tm, t, k * WAVES + wave);
+        if (unit_h && lane == 0 && un != VOID_UNIT) {  // (a unit that is not void begins in front of the message's end)
             // bit 0: the state at the start of the unit; bit 1: the unit holds an escape starter; bit 2: it holds an unescaped quote
             unit_h[un] = (u8)(h | (((s_unit[k * WAVES + wave] >> 28) & 3u) << 1));
             if (KIND) {  // whole parse: the unit's counts under the state that is now known
@@ -587,13 +611,13 @@ __device__ __forceinline__ bool flatten_tile(TileMap tm, u64 *m, const u64 *kpl,
         const u64 g = BASE + ((u32)__builtin_amdgcn_readlane((int)incl, u) - C);
         if (KIND && lane == 0 && C != 0) {  // (a unit holds at most 4096 tokens: at most one 4096-token tile begins in it)
             const u64 T = (g + 4095) >> 12;
-            if (T * 4096 < g + C) aux.tile_unit[T] = (u32)tile_unit<UNITS>(tm, t, u);
+            if (T * 4096 < g + C) aux.tile_unit[T] = tile_unit<UNITS>(tm, t, u);
         }
         const u64 s = sel[k];
         const u32 lo0 = (u32)s, hi0 = (u32)(s >> 32);
         const u32 n = (u32)__builtin_popcount(lo0) + (u32)__builtin_popcount(hi0);
         const u32 loc = upto[k] - n;  // offset of this lane's first position inside the unit
-        const u32 ubase = (u32)(tile_unit<UNITS>(tm, t, u) * 4096 - lead);  // (unused for a void unit: no bits)
+        const u32 ubase = tile_unit<UNITS>(tm, t, u) * 4096u - lead;  // (32-bit positions: they wrap; unused for a void unit: no bits)
         u32 pos0 = KIND ? (u32)lane * 64u : ubase + (u32)lane * 64u;        // what a lane stages: position, or offset in the unit
         __builtin_amdgcn_wave_barrier();  // the staging window is free: all masks are in registers / already copied out
         Staged *stage = reinterpret_cast<Staged *>(m);
@@ -692,54 +716,66 @@ __device__ __forceinline__ bool flatten_tile(TileMap tm, u64 *m, const u64 *kpl,
 // Their tile lists lie end to end: a ticket is a global tile id, descriptor t belongs to global tile t, and the blocks stay
 // on the device across a message boundary -- phase A of the next message's first tiles runs beside the flatten of this
 // message's last ones, so the fill and the drain of the pipeline are paid once per launch, not once per message.  The tile
-// a block classifies and the tile it flattens may belong to different messages: each has its own parameter set (TileMsg),
-// looked up from its ticket.  Nothing crosses a message boundary: units, positions and the tile plan are relative to the
+// a block classifies and the tile it flattens may belong to different messages: the message of a tile comes with its ticket
+// (ticket_pack), its fields from the table in the kernel arguments (msg_at).  Nothing crosses a message boundary: units, positions and the tile plan are relative to the
 // tile's own message (so its unit 0 starts with no carries and its first and last unit are edge units), its local tile 0
 // publishes a PREFIX descriptor and its look-back stops there, and count, end state and errors go to its own host record.
-struct S1Msg {  // one message of a grouped launch
+struct S1Msg {  // one message of a launch: 64 bytes of kernel arguments, everything wave-uniform
     const u8 *base;            // 64-byte aligned; the message is [lead, lead + len) of it
-    u32 *out_pos;
-    unsigned long long *host;  // its host record (S1_HOST_WORDS words)
-    u64 lead, len, pos_cap;
+    u64 len;                   // (lead + len < 2^32 in plain stage 1)
+    u32 lead;
+    u32 tile0;                 // its first global tile (and descriptor)
     TileMap tm;
-    u32 tile0, tiles;          // its first global tile (and descriptor), its tiles
+    u32 tiles;
+    u32 *out_pos;
+    u64 pos_cap;
+    unsigned long long *host;  // its host record (S1_HOST_WORDS words) or null
 };
+static_assert(sizeof(S1Msg) == 64, "a message of the table is found with a shift");
 struct S1Group {
     u32 first[S1_GROUP_MAX];  // tile0 of message k; 0xffffffff behind the last message
     S1Msg m[S1_GROUP_MAX];
 };
 static_assert(sizeof(S1Group) + sizeof(S1Aux) + 128 <= 4096, "the message table travels in the kernel arguments");
-struct S1NoGroup {};
-// the message of a tile: everything wave-uniform
-struct TileMsg {
-    const u8 *base;
-    u64 lead, end, len;
-    u32 *out_pos;
-    u64 pos_cap;
-    TileMap tm;
-    u32 tile0, tiles;
-    unsigned long long *host;
+struct S1NoGroup {  // a launch of one message
+    S1Msg m[1];
 };
-__device__ __forceinline__ TileMsg tile_msg(const S1NoGroup &, u32, const TileMsg &one) { return one; }
-__device__ __forceinline__ TileMsg tile_msg(const S1Group &g, u32 t, const TileMsg &) {  // t: a ticket (any value)
+// The message of a ticket (any value) is resolved ONCE, by the lane that draws the ticket: it leaves the index with the ticket
+// in LDS -- one word of s_ticket, the index in its top bits -- and the iterations that classify, resolve and flatten the tile
+// read the pair.  (A ticket stays far below 2^28: a message of SINGLE_LIMIT is 2^21 tiles, and a descriptor set holds fewer.)
+static constexpr int TK_MSG_SHIFT = 28;
+static constexpr u32 TK_MASK = (1u << TK_MSG_SHIFT) - 1u;
+static_assert(S1_GROUP_MAX <= 16, "the message index of a ticket has four bits");
+__device__ __forceinline__ u32 ticket_pack(const S1NoGroup &, u32 t) { return t; }
+__device__ __forceinline__ u32 ticket_pack(const S1Group &g, u32 t) {
     u32 k = 0;
 #pragma unroll
-    for (int i = 1; i < S1_GROUP_MAX; i++) k += t >= g.first[i] ? 1u : 0u;  // (scalar compares: t is wave-uniform)
-    const S1Msg &m = g.m[k];
-    return TileMsg{m.base, m.lead, m.lead + m.len, m.len, m.out_pos, m.pos_cap, m.tm, m.tile0, m.tiles, m.host};
+    for (int i = 1; i < S1_GROUP_MAX; i++) k += t >= g.first[i] ? 1u : 0u;
+    return t | (k << TK_MSG_SHIFT);
+}
+__device__ __forceinline__ u32 ticket_tile(const S1NoGroup &, u32 w) { return w; }
+__device__ __forceinline__ u32 ticket_tile(const S1Group &, u32 w) { return w & TK_MASK; }
+__device__ __forceinline__ u32 ticket_msg(const S1NoGroup &, u32) { return 0u; }
+__device__ __forceinline__ u32 ticket_msg(const S1Group &, u32 w) { return w >> TK_MSG_SHIFT; }
+// Message k of the launch, for ONE section of the tile loop.  The compiler is told nothing about k: the fields the section
+// uses are then scalar loads from the kernel arguments where the section uses them (they hit the scalar cache), and not
+// values of the kernel's first instructions that the whole loop has to keep -- with three messages per iteration (the tile
+// that is classified, the one behind it, the one that is flattened) those were ~70 scalar registers, most of them
+// spilled into lanes of a VGPR and moved back with v_readlane in the middle of the classification.
+template <typename G>
+__device__ __forceinline__ const S1Msg &msg_at(const G &grp, u32 k) {
+    asm volatile("" : "+s"(k));
+    return grp.m[k];
 }
 
 template <int BLOCK, int CH, int WPE, bool NDJSON, bool AUX, bool TRACE = false, bool GROUP = false>
-__global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel(const u8 *__restrict__ base, u64 lead, u64 len,
-                                                                        u32 *__restrict__ out_pos,
-                                                                        u64 pos_cap, Stage1State *__restrict__ st,
-                                                                        u64 *__restrict__ desc, u32 num_tiles, TileMap tm, S1Aux aux,
-                                                                        typename std::conditional<GROUP, S1Group, S1NoGroup>::type grp) {
+__global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel(Stage1State *__restrict__ st, u64 *__restrict__ desc, u32 num_tiles, S1Aux aux,
+                                                            typename std::conditional<GROUP, S1Group, S1NoGroup>::type grp) {
     static_assert(!GROUP || (!AUX && !TRACE), "grouped launches are plain stage 1");
     constexpr int WAVES = BLOCK / 64;
     constexpr int UNITS = WAVES * CH;  // unit u = pass * WAVES + wave, in byte order
     static_assert(UNITS <= 32, "pre_mask is a u32");
-    __shared__ u32 s_ticket[4];
+    __shared__ u32 s_ticket[4];    // a ticket and the message it belongs to (ticket_pack)
     __shared__ u32 s_unit[3][UNITS];
     __shared__ u32 s_res2[2][4];  // look-back result of tile T(i) in slot i & 1: G, pre_mask, BASE (lo, hi)
     __shared__ u64 s_mask[2][WAVES][CH * 2 * 64];
@@ -753,7 +789,6 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel(const u8 *__restrict
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = (int)uniform((u32)tid >> 6);
-    const u64 end = lead + len;
     u64 kp[CH][4];
     Stage1Ctrl *const ctl = &st->c[aux.par];
     launch_clean(st, aux);
@@ -773,18 +808,20 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel(const u8 *__restrict
     // its way like every later phase A does for its successor, instead of behind the first barrier with the whole load
     // latency exposed (64 MiB: 0.0384 -> 0.0370 ms, same box, alternating; nothing at 256 MiB and 1 GiB)
     if (tid == 0) {
-        s_ticket[0] = one_round ? blockIdx.x : atomicAdd(&ctl->tile_counter, 1u);
-        s_ticket[1] = tk_base + atomicAdd(&ctl->tile_counter, 1u);
+        const u32 t0 = one_round ? blockIdx.x : atomicAdd(&ctl->tile_counter, 1u);
+        const u32 t1 = tk_base + atomicAdd(&ctl->tile_counter, 1u);
+        s_ticket[0] = ticket_pack(grp, t0);
+        s_ticket[1] = ticket_pack(grp, t1);
     }
     __syncthreads();
-    const u32 t_first = uniform(s_ticket[0]);
+    const u32 w_first = uniform(s_ticket[0]), t_first = ticket_tile(grp, w_first);
     if (t_first >= num_tiles) return;
-    const TileMsg one = {base, lead, end, len, out_pos, pos_cap, tm, 0u, num_tiles, aux.host};  // the message of a launch without a group
+    typedef typename std::conditional<AUX, u64, u32>::type Off;  // byte offsets into a message (tile_unit above)
     UnitRegs pf;
     {
-        const TileMsg g0 = tile_msg(grp, t_first, one);
-        const u64 un = tile_unit<UNITS>(g0.tm, t_first - g0.tile0, wave);
-        if (un != VOID_UNIT) unit_issue(g0.base, g0.lead, g0.end, un, g0.tm.nu, lane, pf, s_edge[wave]);
+        const S1Msg &g0 = msg_at(grp, ticket_msg(grp, w_first));
+        const u32 un = tile_unit<UNITS>(g0.tm, t_first - g0.tile0, wave);
+        if (un != VOID_UNIT) unit_issue<Off>(g0.base, (Off)g0.lead, (Off)(g0.lead + g0.len), un, g0.tm.nu, lane, pf, s_edge[wave]);
     }
 
     // One loop, one copy of phase A and of the flatten in the instruction stream (a peeled first tile made every block
@@ -795,26 +832,24 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel(const u8 *__restrict
     // into its flatten); everybody flattens T(j-1).  Rings: tickets 4 (T(k) in slot k & 3; iteration j writes T(j+2)
     // before the barrier -- iteration 0 also T(1) -- into slots whose tiles are done), look-back results 2, unit
     // state 3, masks 2 (private per wave).
-    u32 t_prev = 0;                         // T(j-1): the tile that is flattened in iteration j
+    u32 t_prev = 0, k_prev = 0;             // T(j-1), the tile that is flattened in iteration j, and its message
     u32 P0 = 0, T00 = 0, T01 = 0, pm0 = 0;  // its aggregates; meaningful in wave 0 only
     bool err = false;
     u32 seen_st = 0;                        // whole parse: a unit of this wave held an escape starter
     u32 eiq_last = 0;                       // lane 0 of wave 0: the state at the end of the message (the block of the last tile)
     for (u32 j = 0;; j++) {
         const bool first = j == 0;
-        const u32 t_a = uniform(s_ticket[j & 3u]);                               // phase A runs on T(j)
-        const u32 t_an = uniform(s_ticket[(j + 1u) & 3u]);  // T(j+1): its first unit is loaded behind T(j)'s last
+        const u32 w_a = uniform(s_ticket[j & 3u]), w_n = uniform(s_ticket[(j + 1u) & 3u]);
+        const u32 t_a = ticket_tile(grp, w_a), k_a = ticket_msg(grp, w_a);  // phase A runs on T(j)
+        const u32 t_an = ticket_tile(grp, w_n);                             // T(j+1): its first unit is loaded behind T(j)'s last
         const bool has_a = t_a < num_tiles;
-        // the messages of T(j), T(j+1) and T(j-1), and the tiles' numbers inside them
-        const TileMsg ga = tile_msg(grp, t_a, one), gn = tile_msg(grp, t_an, one), gf = tile_msg(grp, t_prev, one);
-        const u32 l_a = t_a - ga.tile0, l_prev = t_prev - gf.tile0;
         const int ma = (int)(j & 1u), ua = (int)(j % 3u);        // mask / unit slot of T(j)
         const int mf = ma ^ 1, uf = ua == 0 ? 2 : ua - 1;        // ... of T(j-1)
         u32 tk2 = 0;  // the ticket drawn now (lane 0 of wave 0); it returns while phase A runs
         if (tid == 0 && has_a) tk2 = tk_base + atomicAdd(&ctl->tile_counter, 1u);
         if (has_a) {
             trace_put<TRACE>(aux.trace, t_a, WAVES, wave, lane, 0);
-            phase_a<BLOCK, CH, NDJSON, AUX>(ga.base, ga.lead, ga.end, ga.tm, l_a, gn.base, gn.lead, gn.end, gn.tm, t_an - gn.tile0,
+            phase_a<BLOCK, CH, NDJSON, AUX>(msg_at(grp, k_a), t_a, msg_at(grp, ticket_msg(grp, w_n)), t_an,
                                             t_an < num_tiles, lane, wave, pf, s_mask[ma][wave],
                                             s_pre[ma][wave], s_unit[ua], aux, kp, s_ucnt[AUX ? ua : 0], seen_st, s_edge[wave], wave == 0 && !first);
             trace_put<TRACE>(aux.trace, t_a, WAVES, wave, lane, 1);
@@ -823,6 +858,8 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel(const u8 *__restrict
         if (wave == 0) {
             u32 G = 0;
             u64 BASE = 0;
+            const S1Msg &gf = msg_at(grp, k_prev);  // (tile0, tiles; the host record on the error path)
+            const u32 l_prev = t_prev - gf.tile0;
             if (!first && l_prev != 0) {
                 LookBack lb = {(long long)t_prev - 1, 0, 0, 0};
                 const long long lo = (long long)gf.tile0;  // the look-back stays inside the message
@@ -852,22 +889,24 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel(const u8 *__restrict
                         if (!GROUP) __hip_atomic_store(&st->ends_in_quote, eiq_last, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     }
                 }
-                if (has_a) s_ticket[(j + 2u) & 3u] = tk2;
+                if (has_a) s_ticket[(j + 2u) & 3u] = ticket_pack(grp, tk2);
             }
             if (!first) trace_put<TRACE>(aux.trace, t_prev, WAVES, wave, lane, 2);
         }
         __syncthreads();
         if (wave == 0 && has_a) {  // (only wave 0 keeps the aggregates: it resolves the tile in the next iteration)
             tile_aggregate<UNITS>(s_unit[ua], lane, P0, T00, T01, pm0);
-            if (lane == 0) desc_store(&desc[t_a], l_a == 0 ? pack_prefix(P0, T00) : pack_agg(P0, T00, T01));
+            if (lane == 0) desc_store(&desc[t_a], t_a == msg_at(grp, k_a).tile0 ? pack_prefix(P0, T00) : pack_agg(P0, T00, T01));
         }
         if (!first) {
             trace_put<TRACE>(aux.trace, t_prev, WAVES, wave, lane, 3);
             const u32 G = uniform(res[0]), pm = uniform(res[1]);
             const u64 BASE = ((u64)uniform(res[3]) << 32) | uniform(res[2]);
             u64 tile_end = 0;
+            const S1Msg &gf = msg_at(grp, k_prev);  // (tm, tile0, lead, out_pos, pos_cap; the rest on the last-tile and error paths)
+            const u32 l_prev = t_prev - gf.tile0;
             const bool bad = flatten_tile<BLOCK, CH, AUX>(gf.tm, s_mask[mf][wave], s_kpl[AUX ? wave : 0], s_pre[mf][wave], s_unit[uf], pm, G, BASE, l_prev, gf.lead, lane, wave,
-                                           S1_POS_VIEW(gf.out_pos, gf.pos_cap), gf.pos_cap, tile_end, AUX ? aux.unit_h : Arr<u8>(nullptr), gf.len,
+                                           S1_POS_VIEW(gf.out_pos, gf.pos_cap), gf.pos_cap, tile_end, AUX ? aux.unit_h : Arr<u8>(nullptr),
                                            AUX ? aux.kind : Arr<u8>(nullptr), aux, s_ucnt[AUX ? uf : 0]);
             if (GROUP) {  // the error belongs to this tile's message (rare: a store per wave that met one)
                 if (__ballot(bad) != 0 && lane == 0) report_error<false>(ctl, gf.host, 1u);
@@ -890,8 +929,9 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel(const u8 *__restrict
             }
         }
         t_prev = t_a;
+        k_prev = k_a;
     }
-    if (!GROUP && __ballot(err) != 0 && lane == 0) report_error(ctl, aux.host, 1u);
+    if (!GROUP && __ballot(err) != 0 && lane == 0) report_error(ctl, grp.m[0].host, 1u);
     if (AUX && aux.want_flag) {  // (uniform over the grid)
         // one look and at most one store per BLOCK (an atomicOr per wave -- 4096 of them on one word as the kernel ends -- cost
         // configs[1] 31 us: a word takes ~88 atomics per microsecond)
@@ -953,7 +993,9 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel_nb(const u8 *__restr
     }
     const int lane = tid & 63;
     const int wave = (int)uniform((u32)tid >> 6);
-    const u64 end = lead + len;
+    // (plain stage 1: 32-bit offsets.  The message as phase_a takes it: a local copy of the kernel's arguments, i.e. registers)
+    const u32 lead32 = (u32)lead, end32 = (u32)(lead + len);
+    const S1Msg one = {base, len, lead32, 0u, tm, num_tiles, out_pos, pos_cap, aux.host};
 
     // prologue (two block barriers, once per block), as in the barrier kernel
     if (tid == 0) s_tk[0] = atomicAdd(&ctl->tile_counter, 1u);
@@ -964,8 +1006,8 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel_nb(const u8 *__restr
     }
     UnitRegs pf;
     {
-        const u64 un = tile_unit<UNITS>(tm, t_first, wave);
-        if (un != VOID_UNIT) unit_issue(base, lead, end, un, tm.nu, lane, pf, s_edge[wave]);
+        const u32 un = tile_unit<UNITS>(tm, t_first, wave);
+        if (un != VOID_UNIT) unit_issue<u32>(base, lead32, end32, un, tm.nu, lane, pf, s_edge[wave]);
     }
     if (tid == 0) {
         s_tk[1] = atomicAdd(&ctl->tile_counter, 1u);
@@ -974,15 +1016,15 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel_nb(const u8 *__restr
     }
     trace_put<TRACE>(aux.trace, t_first, WAVES, wave, lane, 0);
     u32 seen_st_nb = 0;  // (this kernel never runs the whole parse: unused)
-    phase_a<BLOCK, CH, NDJSON, AUX>(base, lead, end, tm, t_first, base, lead, end, tm, 0, false, lane, wave, pf, s_mask[0][wave], s_pre[0][wave], s_unit[0],
+    phase_a<BLOCK, CH, NDJSON, AUX>(one, t_first, one, 0, false, lane, wave, pf, s_mask[0][wave], s_pre[0][wave], s_unit[0],
                                     aux, kp, nullptr, seen_st_nb, s_edge[wave]);
     trace_put<TRACE>(aux.trace, t_first, WAVES, wave, lane, 1);
     __syncthreads();
     {
         const u32 t1 = uniform(s_tk[1]);
         if (t1 < num_tiles) {
-            const u64 un = tile_unit<UNITS>(tm, t1, wave);
-            if (un != VOID_UNIT) unit_issue(base, lead, end, un, tm.nu, lane, pf, s_edge[wave]);
+            const u32 un = tile_unit<UNITS>(tm, t1, wave);
+            if (un != VOID_UNIT) unit_issue<u32>(base, lead32, end32, un, tm.nu, lane, pf, s_edge[wave]);
         }
     }
     if (wave == 0) {
@@ -1073,7 +1115,7 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel_nb(const u8 *__restr
         if (more) {
             const int ma = (int)((it + 1u) % (u32)DEPTH), ua = (int)((it + 1u) & 7u);
             trace_put<TRACE>(aux.trace, ta, WAVES, wave, lane, 0);
-            phase_a<BLOCK, CH, NDJSON, AUX>(base, lead, end, tm, ta, base, lead, end, tm, tn, tn < num_tiles, lane, wave, pf, s_mask[ma][wave], s_pre[ma][wave],
+            phase_a<BLOCK, CH, NDJSON, AUX>(one, ta, one, tn, tn < num_tiles, lane, wave, pf, s_mask[ma][wave], s_pre[ma][wave],
                                             s_unit[ua], aux, kp, nullptr, seen_st_nb, s_edge[wave], wave == 0);
             trace_put<TRACE>(aux.trace, ta, WAVES, wave, lane, 1);
             u32 arrived = 0;
@@ -1123,8 +1165,8 @@ __global__ __launch_bounds__(BLOCK, WPE) void stage1_kernel_nb(const u8 *__restr
         const u32 G = uniform(res[0]), pm = uniform(res[1]);
         const u64 BASE = ((u64)uniform(res[3]) << 32) | uniform(res[2]);
         u64 tile_end = 0;
-        err |= flatten_tile<BLOCK, CH, false>(tm, s_mask[mf][wave], nullptr, s_pre[mf][wave], s_unit[uf], pm, G, BASE, tf, lead, lane,
-                                              wave, S1_POS_VIEW(out_pos, pos_cap), pos_cap, tile_end, Arr<u8>(nullptr), len, Arr<u8>(nullptr), aux, nullptr);
+        err |= flatten_tile<BLOCK, CH, false>(tm, s_mask[mf][wave], nullptr, s_pre[mf][wave], s_unit[uf], pm, G, BASE, tf, lead32, lane,
+                                              wave, S1_POS_VIEW(out_pos, pos_cap), pos_cap, tile_end, Arr<u8>(nullptr), Arr<u8>(nullptr), aux, nullptr);
         if (tf == num_tiles - 1 && tid == 0) report_total(st, aux.host, tile_end, eiq_last, base + lead, len);
         trace_put<TRACE>(aux.trace, tf, WAVES, wave, lane, 4);
         if (TRACE && lane == 0)
@@ -1286,6 +1328,7 @@ hipError_t stage1_launch(const void *d_msg, size_t len, int ndjson, u32 *d_pos, 
     if ((size_t)tiles > s1_desc_capacity(ws)) return hipErrorInvalidValue;  // (the workspace is too small)
     if ((d_kind != nullptr) != (aux_buf != nullptr)) return hipErrorInvalidValue;  // (the whole-parse kernel writes kinds AND masks: no tests on the device)
     if (d_trace && ((ndjson & 1) || whole)) return hipErrorInvalidValue;           // (the trace build: plain stage 1 of a non-ND message)
+    if (!whole && lead + (u64)len > 0xffffffffull) return hipErrorInvalidValue;     // (plain stage 1 keeps its byte offsets in 32 bits: tile_unit)
     if (tiles == 0) {  // (nothing is launched: the stage-2 state of an empty message is zeroed the plain way)
         return zero2 && zero2_bytes ? hipMemsetAsync(zero2, 0, zero2_bytes, stream) : hipSuccess;
     }
@@ -1315,20 +1358,23 @@ hipError_t stage1_launch(const void *d_msg, size_t len, int ndjson, u32 *d_pos, 
         aux.unit_str = SJ_ARR(a.unit_str, a.units, A_S1_UNIT_STR);
         aux.tile_unit = SJ_ARR(a.tile_unit, a.units + 1, A_S1_TILE_UNIT);
     }
-#define S1_LAUNCHK(K, B, ...)                                                                                       \
+    // the message as the barrier kernel reads it: a table of one in its arguments
+    const S1NoGroup one = {{{base, (u64)len, (u32)lead, 0u, plan.tm, tiles, d_pos, (u64)pos_cap, h_state}}};
+#define S1_LAUNCHK(K, B)                                                                                            \
     hipLaunchKernelGGL((K), dim3(grid_for(K, B, tiles)), dim3(B), 0, stream, base, lead, (u64)len, d_pos, (u64)pos_cap, \
-                       st, desc, tiles, plan.tm, aux, ##__VA_ARGS__)
+                       st, desc, tiles, plan.tm, aux)
+#define S1_LAUNCH1(K, B) hipLaunchKernelGGL((K), dim3(grid_for(K, B, tiles)), dim3(B), 0, stream, st, desc, tiles, aux, one)
 #define S1_LAUNCH(KERNEL, B, C, W)                                                    \
     do {                                                                              \
         const bool ax = aux_buf || d_kind;                                            \
         if (d_trace) {                                                                \
-            S1_LAUNCHK((KERNEL<B, C, W, false, false, true>), B, S1NoGroup{});                     \
+            S1_LAUNCH1((KERNEL<B, C, W, false, false, true>), B);                     \
         } else if (nd) {                                                              \
-            if (ax) S1_LAUNCHK((KERNEL<B, C, W, true, true>), B, S1NoGroup{});                     \
-            else S1_LAUNCHK((KERNEL<B, C, W, true, false>), B, S1NoGroup{});                       \
+            if (ax) S1_LAUNCH1((KERNEL<B, C, W, true, true>), B);                     \
+            else S1_LAUNCH1((KERNEL<B, C, W, true, false>), B);                       \
         } else {                                                                      \
-            if (ax) S1_LAUNCHK((KERNEL<B, C, W, false, true>), B, S1NoGroup{});                    \
-            else S1_LAUNCHK((KERNEL<B, C, W, false, false>), B, S1NoGroup{});                      \
+            if (ax) S1_LAUNCH1((KERNEL<B, C, W, false, true>), B);                    \
+            else S1_LAUNCH1((KERNEL<B, C, W, false, false>), B);                      \
         }                                                                             \
     } while (0)
 #define S1_LAUNCH_NB(B, C, D, W)                                                            \
@@ -1354,6 +1400,7 @@ hipError_t stage1_launch(const void *d_msg, size_t len, int ndjson, u32 *d_pos, 
     }
 #undef S1_LAUNCH
 #undef S1_LAUNCH_NB
+#undef S1_LAUNCH1
 #undef S1_LAUNCHK
     return s1_launched(ws, tiles);
 }
@@ -1383,9 +1430,10 @@ hipError_t stage1_launch_group(const S1QMsg *msgs, int n, int ndjson, S1Ws &ws, 
         const uintptr_t a = reinterpret_cast<uintptr_t>(msgs[k].d_msg);
         const S1Plan plan = s1_plan(msgs[k].len, a & 63, v);
         if (msgs[k].len == 0 || plan.tiles == 0 || !msgs[k].h_state) return hipErrorInvalidValue;  // (an empty message launches nothing)
+        if ((a & 63) + (u64)msgs[k].len > 0xffffffffull) return hipErrorInvalidValue;  // (32-bit byte offsets: tile_unit)
         S1Msg &m = grp.m[k];
         m.base = reinterpret_cast<const u8 *>(a & ~(uintptr_t)63);
-        m.lead = a & 63;
+        m.lead = (u32)(a & 63);
         m.len = msgs[k].len;
         m.out_pos = msgs[k].d_pos;
         m.pos_cap = msgs[k].pos_cap;
@@ -1404,8 +1452,7 @@ hipError_t stage1_launch_group(const S1QMsg *msgs, int n, int ndjson, S1Ws &ws, 
     Stage1State *st = reinterpret_cast<Stage1State *>(ws.p);
     u64 *desc = s1_desc_set(ws, par);
 #define S1_LAUNCHG(K)                                                                                                   \
-    hipLaunchKernelGGL((K), dim3(grid_for(K, 1024, (u32)tiles)), dim3(1024), 0, stream, (const u8 *)nullptr, (u64)0, (u64)0, \
-                       (u32 *)nullptr, (u64)0, st, desc, (u32)tiles, TileMap{}, aux, grp)
+    hipLaunchKernelGGL((K), dim3(grid_for(K, 1024, (u32)tiles)), dim3(1024), 0, stream, st, desc, (u32)tiles, aux, grp)
     if (ndjson & 1) S1_LAUNCHG((stage1_kernel<1024, 2, 4, true, false, false, true>));
     else S1_LAUNCHG((stage1_kernel<1024, 2, 4, false, false, false, true>));
 #undef S1_LAUNCHG
