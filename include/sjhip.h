@@ -740,6 +740,33 @@ int sjhip_fetch_marshaled(sjhip_ctx *ctx, uint8_t *dst);
  * row, and one pass that writes. */
 int sjhip_marshal_rows(sjhip_ctx *ctx, uint64_t *n_rows, size_t *text_len);
 int sjhip_fetch_marshaled_rows(sjhip_ctx *ctx, uint64_t *offsets /* [n_rows + 1] */, uint8_t *text /* [text_len] */);
+/* Project rows: sjhip_marshal_rows with a select list -- of every row of the selection in force only the elements at n_cols paths, as
+ * one JSON object per row: {"id":1,"user":{...},"n":null}.
+ *   paths    keys / key_lens / path_lens as in sjhip_extract_table and sjhip_where_paths: column c owns the next path_lens[c] entries
+ *            of key_lens; path_lens[c] == 0 is the row's own value (sjhip_where_paths).  A table's limits: 1 to
+ *            SJHIP_TABLE_MAX_COLS columns, at most 16 keys per path, 32 keys and 1024 key bytes in all paths together.  FindElement's
+ *            rules hold per path as documented for tables: the first member with the key wins and nothing is taken back; two columns
+ *            may name one path, one path may be the beginning of another.
+ *   names    the member names of the output, end to end, name_lens[c] bytes each: empty, repeated, any bytes; at most 1024 bytes
+ *            together.  NULL: every column is named by the last key of its path (an empty path is then SJHIP_ERR_ARG).
+ *   a row    '{' + the present columns in column order, joined by ',' + '}'; a present column is '"' + escapeBytes(name) + '":' +
+ *            the text of the element, byte for byte what sjhip_marshal_rows writes for a row whose value is that element (scalars,
+ *            strings, objects, arrays).  A column is absent when its path gives SJHIP_PATH_NOT_FOUND or SJHIP_PATH_NOT_OBJECT (a
+ *            scalar row: every column with keys): it is left out with its ',', or written as "name":null under SJHIP_PROJECT_NULLS.
+ *            An element that is present and null is written as null either way.  A row with nothing present is {}.
+ * Rows, *n_rows, *text_len, the joining '\n' and the fetch are sjhip_marshal_rows': the result is the marshaled product of the
+ * context with the row offsets behind it, delivered by sjhip_fetch_marshaled_rows and sjhip_fetch_marshaled.  The selection, the
+ * string column, the list column and the table stay as they are (the cell indexes live in the shared work arena, not in the
+ * table's).  Key flags, parses without SJHIP_FLAG_COPY_STRINGS, SJHIP_ERR_TOOBIG and the INF / NaN error are sjhip_marshal_rows'.
+ * Errors: SJHIP_ERR_ARG, with sjhip_last_error naming the column or the reason and nothing touched: no result on the device, no row
+ * selection ("no row selection"), a sharded ND result, an unknown flag bit, n_cols outside 1..16, paths or names beyond the limits, a
+ * NULL `names` with an empty path.
+ * The cost is one walk of every row's members up to the last wanted one (sjhip_extract_table's), 8 bytes per cell written and read
+ * twice, and sjhip_marshal_rows' passes over the words and strings of the cells alone. */
+#define SJHIP_PROJECT_NULLS 1u /* an absent field is written as null instead of being left out */
+int sjhip_marshal_rows_paths(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, const uint32_t *path_lens,
+                             uint32_t n_cols, const uint8_t *names, const uint32_t *name_lens, uint32_t flags,
+                             uint64_t *n_rows, size_t *text_len);
 
 /* ---- ParseNDStream: replaces the block pipeline of simdjson_amd64.go:101-216 --------------------------------------
  * The binding cuts the input into blocks that end at a record boundary (simdjson_amd64.go:155-176; tmpSize = 10 MiB)

@@ -18,8 +18,11 @@
 // string entry k of the tape, and it is a key iff the token behind it is ':' (k_ms_keys).
 // Tag words are told from raw words (the second word of a string / number entry) with the parity rule of sj_tapewalk.h.
 #include <hip/hip_runtime.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+
+#include <vector>
 
 #include "../../include/sjhip.h"
 #include "sj_bounds.h"
@@ -27,6 +30,7 @@
 #include "sj_device.h"
 #include "sj_ftoa.h"
 #include "sj_stage2.h"
+#include "sj_tablewalk.h"
 #include "sj_tapewalk.h"
 
 using namespace sj;
@@ -107,12 +111,13 @@ __device__ __forceinline__ bool entry_is_key(const MsView &p, u64 key_base, u32 
 }
 
 // escapeBytes: bytes below 0x20, '"' and '\\' are escaped (shouldEscape, parsed_json.go:1171-1186)
-__device__ __forceinline__ u32 escaped_size(u8 c) {
+// (host and device: sjhip_marshal_rows_paths escapes the member names of its rows on the host with the same two functions)
+SJ_HD u32 escaped_size(u8 c) {
     if (c == '"' || c == '\\') return 2;
     if (c >= 0x20) return 1;
     return (c == '\b' || c == '\f' || c == '\n' || c == '\r' || c == '\t') ? 2u : 6u;
 }
-__device__ __forceinline__ u8 *write_escaped_byte(u8 *o, u8 c) {
+SJ_HD u8 *write_escaped_byte(u8 *o, u8 c) {
     const char *hex = "0123456789abcdef";
     const u32 sz = escaped_size(c);
     if (sz == 1) {
@@ -1030,24 +1035,22 @@ __device__ __forceinline__ u64 mr_wave_row(const MrView &p, u64 v, u64 end, int 
     });
     return total;
 }
-// where row r lies: [*v, *end); (a scalar: its one or two words)
+// where the value at v ends: behind its matching close, or behind a scalar's one or two words (a row, or a cell of a projected row)
+__device__ __forceinline__ u64 mr_value_end(const MrView &p, u64 v) {
+    const u64 w0 = p.tape[v];
+    const u32 t0 = (u32)(w0 >> 56);
+    return (t0 == '{' || t0 == '[') ? (w0 & TW_PAYLOAD) : v + (two_word_tag(w0) ? 2u : 1u);
+}
+// where row r lies: [*v, *end)
 __device__ __forceinline__ void mr_row_range(const MrView &p, u32 r, u64 *v, u64 *end) {
     *v = p.rows[r];
-    const u64 w0 = p.tape[*v];
-    const u32 t0 = (u32)(w0 >> 56);
-    *end = (t0 == '{' || t0 == '[') ? (w0 & TW_PAYLOAD) : *v + (two_word_tag(w0) ? 2u : 1u);
+    *end = mr_value_end(p, *v);
 }
-__global__ __launch_bounds__(256, 4) void k_mr_measure(MrView p) {
-    const u32 r = blockIdx.x * 256 + threadIdx.x;
-    const int lane = threadIdx.x & 63;
-    const bool have = r < p.n;
-    u64 v = 0, end = 0, i = 0, sum = 0;
-    bool wide = false, bad = false;
-    if (have) {
-        mr_row_range(p, r, &v, &end);
-        wide = end - v > MR_SHORT;
-        i = v;
-    }
+// One lane per value (have: the lane has one, [v, end)), every lane of the wave makes the call: -> the text bytes of the lane's value.
+__device__ __forceinline__ u64 mr_measure_value(const MrView &p, bool have, u64 v, u64 end, int lane, bool *bad_out) {
+    u64 i = v, sum = 0;
+    bool bad = false;
+    const bool wide = have && end - v > MR_SHORT;
     const bool walks = have && !wide;
     for (;;) {  // (wave-uniform: every lane walks up to its next long string, the wave measures those, the lanes go on)
         bool pend = false, pin = false;
@@ -1088,6 +1091,17 @@ __global__ __launch_bounds__(256, 4) void k_mr_measure(MrView p) {
         bad = bad || bad_j;
         if (lane == j) sum = tot;
     }
+    if (bad) *bad_out = true;
+    return sum;
+}
+__global__ __launch_bounds__(256, 4) void k_mr_measure(MrView p) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool have = r < p.n;
+    u64 v = 0, end = 0;
+    bool bad = false;
+    if (have) mr_row_range(p, r, &v, &end);
+    const u64 sum = mr_measure_value(p, have, v, end, lane, &bad);
     if (r <= p.n) p.off[r] = have ? sum + 1u : 0u;  // (one more byte per row: its '\n'; the scan puts the total into off[n])
     if (bad) atomicOr(&p.totals[2], 1ull);
 }
@@ -1170,6 +1184,147 @@ __global__ __launch_bounds__(TW_THREADS) void k_mr_keyflags(MrKeys p) {
 #pragma unroll
     for (int k = 0; k < TW_ITEMS; k++)
         if ((strs >> k) & 1u) p.kf[(base + k) >> 1] = p.keyflag[o++];
+}
+
+// ---- project rows: only the values at k paths of every row (sjhip_marshal_rows_paths) -------------------------------------------------
+// The text of row r is '{' + its present columns, joined by ',' + '}'; a present column is its name piece -- '"' + escapeBytes(name)
+// + '":', built once on the host and uploaded -- and the text of the tape words [v, end) of the element the column's path resolves
+// to: a cell, measured and written exactly as sjhip_marshal_rows measures and writes a row (mr_measure_value, mr_wave_row).  An
+// absent column (SJHIP_PATH_NOT_FOUND / _NOT_OBJECT) is left out, or is its name piece + "null" under SJHIP_PROJECT_NULLS.
+//   k_mp_walk       one lane per row: table_walk (sj_tablewalk.h) over the plan of the columns that have a path; the sink stores the
+//                   tape index or the sentinel of column c into idx[c * n + r] (column-major: the 64 lanes of a wave store next to
+//                   each other).  A column without keys is the row's own value.  The resume stack is LDS, as in k_q_table_walk.
+//   k_mp_measure    one lane per row, column after column: braces, name pieces, commas, nulls, and the cell by mr_measure_value --
+//                   a lane walks at most MR_SHORT words and strings below MS_LONG bytes per cell, the wave does the rest.
+//   scan            k_mr_tile_sums, k_tw_scan_sums, k_mr_tile_apply over the n + 1 lengths, as they are
+//   k_mp_write      one wave per row: lane 0 places '\n', '{', '}', the commas and the row offset; a name piece below 64 bytes is
+//                   one byte per lane, a longer one 8 bytes per lane and step; the cell is mr_wave_row<true> on its span.
+struct MpView {
+    MrView r;                 // the tape, the rows, the strings, the key flags, off / tiles / totals, text and out_off: sjhip_marshal_rows' view
+    Arr<u64> idx;             // [n_cols][n] the tape index of the cell, or SJHIP_PATH_NOT_FOUND / _NOT_OBJECT
+    Arr<const u8> names;      // the name pieces, end to end
+    Arr<const u32> name_off;  // [n_cols + 1] where they begin
+    u32 n_cols, nulls;
+};
+struct MpPlan {
+    TablePlan pl;                // over the columns that have a path (pl.n_cols of them; none: no walk)
+    u8 key[TABLE_MAX_BYTES];     // the keys of its nodes, node after node
+    u8 col_of[TABLE_MAX_COLS];   // column of the plan -> column of the projection
+    u32 empty;                   // bit c: column c has no keys (the row's own value)
+};
+static_assert(sizeof(MpView) + sizeof(MpPlan) <= 4096, "k_mp_walk: the view and the plan travel as kernel arguments (4 KiB)");
+struct MpWalkView {
+    const MrView &p;
+    const MpPlan &t;
+    __device__ __forceinline__ u64 word(u64 i) const { return p.tape[i]; }
+    __device__ __forceinline__ bool key_equals(u64 kw, u64 kl, u32 key_b, u32 key_n) const {
+        if (kl != key_n) return false;
+        bool in;
+        u64 off;
+        mr_str_loc(kw, &in, &off);
+        const u8 *s = ms_string(p, in, off, kl);
+        for (u32 k = 0; k < key_n; k++)
+            if (s[k] != t.key[key_b + k]) return false;
+        return true;
+    }
+};
+struct MpSink {
+    const MpView &m;
+    const MpPlan &t;
+    u32 r;
+    __device__ __forceinline__ void operator()(u32 c, u64 v) const { m.idx[(u64)t.col_of[c] * m.r.n + r] = v; }
+};
+__global__ __launch_bounds__(256) void k_mp_walk(MpView m, MpPlan t) {
+    __shared__ u32 s_stack[TABLE_STACK_WORDS * 256];
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= m.r.n) return;
+    const u64 v0 = m.r.rows[r];
+    if (t.pl.n_cols) {
+        const MpWalkView view = {m.r, t};
+        MpSink sink = {m, t, r};
+        table_walk(view, t.pl, v0, s_stack + threadIdx.x, 256u, sink);
+    }
+    for (u32 e = t.empty; e; e &= e - 1) m.idx[(u64)__builtin_ctz(e) * m.r.n + r] = v0;
+}
+__global__ __launch_bounds__(256, 4) void k_mp_measure(MpView m) {
+    const MrView &p = m.r;
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool have = r < p.n;
+    u64 sum = 2;  // '{' and '}'
+    bool bad = false, any = false;
+    for (u32 c = 0; c < m.n_cols; c++) {  // (wave-uniform: every lane measures its cell of column c, the wave the long ones)
+        u64 v = 0, end = 0;
+        bool cell = false;
+        if (have) {
+            const u64 x = m.idx[(u64)c * p.n + r];
+            cell = x < SJHIP_PATH_NOT_OBJECT;
+            if (cell || m.nulls) {
+                sum += (m.name_off[c + 1] - m.name_off[c]) + (any ? 1u : 0u) + (cell ? 0u : 4u);
+                any = true;
+            }
+            if (cell) {
+                v = x;
+                end = mr_value_end(p, v);
+            }
+        }
+        sum += mr_measure_value(p, cell, v, end, lane, &bad);
+    }
+    if (r <= p.n) p.off[r] = have ? sum + 1u : 0u;  // (one more byte per row: its '\n'; the scan puts the total into off[n])
+    if (bad) atomicOr(&p.totals[2], 1ull);
+}
+// a value every lane of the wave loaded from the same address, as the scalar it is (the loops over a cell then run on scalars)
+__device__ __forceinline__ u64 mp_wave_uniform(u64 x) {
+    return ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(x >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)x);
+}
+// the name piece names[b, b + len) into text[at ..), by the whole wave
+__device__ __forceinline__ void mp_write_name(const MpView &m, u32 b, u32 len, int lane, u64 at) {
+    if (len < 64u) {
+        if ((u32)lane < len) m.r.text[at + (u32)lane] = m.names[b + (u32)lane];
+        return;
+    }
+    for (u32 q = (u32)lane * 8u; q < len; q += 512u) {
+        const u32 nb = len - q < 8u ? len - q : 8u;
+        const u8 *s = arr_at(m.names, b + q, nb);
+        u8 *o = arr_at(m.r.text, at + q, nb);
+        for (u32 k = 0; k < nb; k++) o[k] = s[k];
+    }
+}
+__global__ __launch_bounds__(256, 4) void k_mp_write(MpView m) {
+    const MrView &p = m.r;
+    const u32 r = blockIdx.x * 4 + (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    if (r >= p.n) return;  // wave-uniform
+    const u64 at = mp_wave_uniform(p.off[r]);
+    if (lane == 0) {
+        if (r) p.text[at - 1] = '\n';
+        p.out_off[r] = at;
+        if (r + 1 == p.n) p.out_off[p.n] = p.off[p.n];
+        p.text[at] = '{';
+    }
+    u64 cur = at + 1u;
+    bool any = false, bad = false;  // (the measure has reported it)
+    for (u32 c = 0; c < m.n_cols; c++) {
+        const u64 x = mp_wave_uniform(m.idx[(u64)c * p.n + r]);
+        const bool cell = x < SJHIP_PATH_NOT_OBJECT;
+        if (!cell && !m.nulls) continue;
+        if (any) {
+            if (lane == 0) p.text[cur] = ',';
+            cur++;
+        }
+        any = true;
+        const u32 b = (u32)__builtin_amdgcn_readfirstlane((int)m.name_off[c]);
+        const u32 len = (u32)__builtin_amdgcn_readfirstlane((int)m.name_off[c + 1]) - b;
+        mp_write_name(m, b, len, lane, cur);
+        cur += len;
+        if (cell) {  // (what the shuffles of the walk return is a scalar again: the position stays out of the vector registers)
+            cur += mp_wave_uniform(mr_wave_row<true>(p, x, mp_wave_uniform(mr_value_end(p, x)), lane, cur, &bad));
+        } else {
+            if (lane < 4) p.text[cur + (u32)lane] = (u8)(0x6c6c756eu >> (8 * lane));  // null
+            cur += 4u;
+        }
+    }
+    if (lane == 0) p.text[cur] = '}';
 }
 }  // namespace
 
@@ -1413,20 +1568,35 @@ int sjhip_fetch_marshaled(sjhip_ctx *ctx, uint8_t *dst) {
 // writing pass, the publish.  It reads the selection and leaves it, and every other product, as they are.
 static size_t mr_offsets_at(size_t text_len) { return (text_len + 255) / 256 * 256; }
 
-int sjhip_marshal_rows(sjhip_ctx *ctx, uint64_t *n_rows, size_t *text_len) {
-    if (!ctx) return SJHIP_ERR_ARG;
-    if (!ctx->res.whole()) return no_whole_result(ctx, "sjhip_marshal_rows", "sjhip_marshal_rows follows");
+// what sjhip_marshal_rows_paths adds to the call: the plan of its columns, the name pieces and where each begins
+struct MpHost {
+    MpPlan plan;
+    u32 n_cols, nulls;
+    u32 name_off[TABLE_MAX_COLS + 1];
+    std::vector<u8> names;
+};
+// the state both calls ask for, before they look at anything else (SJHIP_ERR_ARG: nothing is touched)
+static int marshal_rows_state(sjhip_ctx *ctx, const char *who) {
+    if (!ctx->res.whole()) {
+        char follows[64];
+        snprintf(follows, sizeof follows, "%s follows", who);
+        return no_whole_result(ctx, who, follows);
+    }
     if (!ctx->res.rows.exists()) {
-        ctx_set_error(ctx, "no row selection on the device (sjhip_marshal_rows follows sjhip_select_rows or sjhip_where_path)");
+        ctx_set_error(ctx, "no row selection on the device (%s follows sjhip_select_rows or sjhip_where_path)", who);
         return SJHIP_ERR_ARG;
     }
+    return SJHIP_OK;
+}
+// the rows of the selection in force as text: whole (proj null), or the cells of proj's columns
+static int marshal_rows_build(sjhip_ctx *ctx, const char *who, const MpHost *proj, uint64_t *n_rows, size_t *text_len) {
     if (ctx->p_len >= (1ull << 32) && !(ctx->p_flags & SJHIP_FLAG_COPY_STRINGS)) {  // (sjhip_marshal_json's rule)
-        ctx_set_error(ctx, "sjhip_marshal_rows: a document of 4 GiB or more parsed without SJHIP_FLAG_COPY_STRINGS (message offsets beyond 32 bits)");
+        ctx_set_error(ctx, "%s: a document of 4 GiB or more parsed without SJHIP_FLAG_COPY_STRINGS (message offsets beyond 32 bits)", who);
         return SJHIP_ERR_TOOBIG;
     }
     const ResultState::Rows z = ctx->res.rows.sizes();
     if (z.rows >= 0xffffffffull) {
-        ctx_set_error(ctx, "sjhip_marshal_rows: %llu rows (at most 2^32 - 2)", (unsigned long long)z.rows);
+        ctx_set_error(ctx, "%s: %llu rows (at most 2^32 - 2)", who, (unsigned long long)z.rows);
         return SJHIP_ERR_TOOBIG;
     }
     const u32 n = (u32)z.rows;
@@ -1448,10 +1618,19 @@ int sjhip_marshal_rows(sjhip_ctx *ctx, uint64_t *n_rows, size_t *text_len) {
     kv.tiles = (kv.n + 4095u) / 4096u;
     const u32 tiles = (u32)(((u64)n + 1 + QTILE - 1) / QTILE), tw_tiles = (u32)((ctx->tape_len + TW_TILE - 1) / TW_TILE);
     const size_t kf_len = ctx->tape_len / 2 + 1;
+    MpView m{};
+    u8 *d_names = nullptr;
+    u32 *d_name_off = nullptr;
     auto layout = [&](Carve c) {
         p.totals = c.take<unsigned long long>(32);
-        p.off = SJ_ARR(c.take<u64>((size_t)n + 1), (size_t)n + 1, A_MROWS_OFF);
+        p.off = SJ_ARR(c.take<u64>((size_t)n + 1), (size_t)n + 1, proj ? A_MPROJ_OFF : A_MROWS_OFF);
         p.tiles = c.take<unsigned long long>(tiles);
+        if (proj) {
+            const size_t cells = (size_t)n * proj->n_cols;
+            m.idx = SJ_ARR(c.take<u64>(cells), cells, A_MPROJ_IDX);
+            d_names = c.take<u8>(proj->names.size());
+            d_name_off = c.take<u32>(proj->n_cols + 1u);
+        }
         if (own_flags) {
             kv.cnt = c.take<unsigned long long>(kv.tiles);
             kv.keyflag = c.take<u8>(kv.n);
@@ -1488,7 +1667,19 @@ int sjhip_marshal_rows(sjhip_ctx *ctx, uint64_t *n_rows, size_t *text_len) {
     } else {
         p.kf = SJ_ARR((const u8 *)ctx->d_keyflag.p, kf_len, A_KEYFLAG);
     }
-    hipLaunchKernelGGL(k_mr_measure, dim3(n / 256 + 1), dim3(256), 0, ctx->stream, p);  // (row n as well: off[n])
+    if (proj) {  // the name pieces (the host copies outlive the copy commands: the call synchronises on the totals below)
+        HIPCHK(hipMemcpyAsync(d_names, proj->names.data(), proj->names.size(), hipMemcpyHostToDevice, ctx->stream), "H2D name pieces");
+        HIPCHK(hipMemcpyAsync(d_name_off, proj->name_off, (proj->n_cols + 1u) * sizeof(u32), hipMemcpyHostToDevice, ctx->stream), "H2D name offsets");
+        m.names = SJ_ARR((const u8 *)d_names, proj->names.size(), A_MPROJ_NAMES);
+        m.name_off = SJ_ARR((const u32 *)d_name_off, proj->n_cols + 1u, A_MPROJ_NAME_OFF);
+        m.n_cols = proj->n_cols;
+        m.nulls = proj->nulls;
+        m.r = p;
+        hipLaunchKernelGGL(k_mp_walk, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, m, proj->plan);
+        hipLaunchKernelGGL(k_mp_measure, dim3(n / 256 + 1), dim3(256), 0, ctx->stream, m);  // (row n as well: off[n])
+    } else {
+        hipLaunchKernelGGL(k_mr_measure, dim3(n / 256 + 1), dim3(256), 0, ctx->stream, p);  // (row n as well: off[n])
+    }
     hipLaunchKernelGGL(k_mr_tile_sums, dim3(tiles), dim3(QT), 0, ctx->stream, p);
     hipLaunchKernelGGL(k_tw_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, p.tiles, none, none, tiles, p.totals);
     hipLaunchKernelGGL(k_mr_tile_apply, dim3(tiles), dim3(QT), 0, ctx->stream, p);
@@ -1507,11 +1698,110 @@ int sjhip_marshal_rows(sjhip_ctx *ctx, uint64_t *n_rows, size_t *text_len) {
     if (rc) return rc;
     p.text = SJ_ARR((u8 *)ctx->d_qtape.p, len, A_MROWS_TEXT);
     p.out_off = SJ_ARR((u64 *)((char *)ctx->d_qtape.p + mr_offsets_at(len)), (size_t)n + 1, A_MROWS_OUT_OFF);
-    hipLaunchKernelGGL(k_mr_write, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, p);
+    if (proj) {
+        m.r = p;
+        hipLaunchKernelGGL(k_mp_write, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, m);
+    } else {
+        hipLaunchKernelGGL(k_mr_write, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, p);
+    }
     HIPCHK(hipGetLastError(), "marshal rows write launch");
     if (n_rows) *n_rows = n;
     if (text_len) *text_len = len;
     return published(ctx, ctx->res.publish_marshaled_rows(len, n));
+}
+
+int sjhip_marshal_rows(sjhip_ctx *ctx, uint64_t *n_rows, size_t *text_len) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    const int rc = marshal_rows_state(ctx, "sjhip_marshal_rows");
+    return rc ? rc : marshal_rows_build(ctx, "sjhip_marshal_rows", nullptr, n_rows, text_len);
+}
+
+// sjhip_marshal_rows_paths: the same call with a select list.  The checks of the arguments touch nothing; the plan of the paths is a
+// table's (sj_table.h) over the columns that have keys; the name pieces are escaped here, with the functions the kernels escape
+// strings with, and travel to the device with their offsets (6 bytes per name byte at the most: no kernel argument).
+int sjhip_marshal_rows_paths(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, const uint32_t *path_lens, uint32_t n_cols,
+                             const uint8_t *names, const uint32_t *name_lens, uint32_t flags, uint64_t *n_rows, size_t *text_len) {
+    static const char *const who = "sjhip_marshal_rows_paths";
+    if (!ctx) return SJHIP_ERR_ARG;
+    int rc = marshal_rows_state(ctx, who);
+    if (rc) return rc;
+    if (flags & ~(uint32_t)SJHIP_PROJECT_NULLS) {
+        ctx_set_error(ctx, "%s: unknown flag bits 0x%x (SJHIP_PROJECT_NULLS)", who, flags & ~(uint32_t)SJHIP_PROJECT_NULLS);
+        return SJHIP_ERR_ARG;
+    }
+    if (n_cols == 0 || n_cols > (uint32_t)TABLE_MAX_COLS) {
+        ctx_set_error(ctx, "%s: %u columns (a projection holds 1 to 16 columns)", who, n_cols);
+        return SJHIP_ERR_ARG;
+    }
+    if (!path_lens || (names && !name_lens)) {
+        ctx_set_error(ctx, "%s: a null argument (path_lens, or name_lens beside names)", who);
+        return SJHIP_ERR_ARG;
+    }
+    MpHost h;
+    memset(&h.plan, 0, sizeof h.plan);
+    h.n_cols = n_cols;
+    h.nulls = (flags & SJHIP_PROJECT_NULLS) ? 1u : 0u;
+    // the columns that have a path are the columns of a table plan, in their order (as the predicates of sjhip_where_paths are)
+    uint32_t col_path_lens[TABLE_MAX_COLS], plan_cols = 0;
+    int kinds[TABLE_MAX_COLS];
+    size_t n_keys = 0;
+    for (uint32_t c = 0; c < n_cols; c++) {
+        if (path_lens[c] == 0) {
+            if (!names) {
+                ctx_set_error(ctx, "%s: column %u: an empty path has no last key to be named by (names is null)", who, c);
+                return SJHIP_ERR_ARG;
+            }
+            h.plan.empty |= 1u << c;
+            continue;
+        }
+        h.plan.col_of[plan_cols] = (u8)c;
+        col_path_lens[plan_cols] = path_lens[c];
+        kinds[plan_cols++] = SJHIP_COL_FLOAT;  // (the walk does not look at the kind of a column)
+        n_keys += path_lens[c];
+    }
+    if (plan_cols) {
+        if (!keys || !key_lens) {
+            ctx_set_error(ctx, "%s: a null argument (%zu keys are announced)", who, n_keys);
+            return SJHIP_ERR_ARG;
+        }
+        // (the keys of the paths lie end to end whether or not empty paths stand between them: table_plan reads them as they are)
+        uint32_t blob_len = 0, bad_col = 0;
+        const int why = table_plan(keys, key_lens, col_path_lens, kinds, plan_cols, &h.plan.pl, h.plan.key, &blob_len, &bad_col);
+        if (why) {
+            ctx_set_error(ctx, "%s: column %u: %s", who, (unsigned)h.plan.col_of[bad_col], table_plan_error(why));
+            return SJHIP_ERR_ARG;
+        }
+    }
+    // the names: the caller's, or the last key of every path
+    size_t name_bytes = 0;
+    if (names)
+        for (uint32_t c = 0; c < n_cols; c++) {
+            name_bytes += name_lens[c];
+            if (name_bytes > (size_t)TABLE_MAX_BYTES) {
+                ctx_set_error(ctx, "%s: column %u: the names are longer than 1024 bytes together", who, c);
+                return SJHIP_ERR_ARG;
+            }
+        }
+    const uint8_t *name = names, *key = keys;
+    size_t k = 0;
+    for (uint32_t c = 0; c < n_cols; c++) {
+        uint32_t len = names ? name_lens[c] : 0;
+        for (uint32_t j = 0; j < path_lens[c]; j++, k++) {  // (without names: the last key of the path)
+            if (!names && j + 1 == path_lens[c]) name = key, len = key_lens[k];
+            key += key_lens[k];
+        }
+        h.name_off[c] = (u32)h.names.size();
+        h.names.push_back('"');
+        for (uint32_t j = 0; j < len; j++) {
+            u8 esc[6];
+            h.names.insert(h.names.end(), esc, write_escaped_byte(esc, name[j]));
+        }
+        h.names.push_back('"');
+        h.names.push_back(':');
+        if (names) name += len;
+    }
+    h.name_off[n_cols] = (u32)h.names.size();
+    return marshal_rows_build(ctx, who, &h, n_rows, text_len);
 }
 
 int sjhip_fetch_marshaled_rows(sjhip_ctx *ctx, uint64_t *offsets, uint8_t *text) {

@@ -62,7 +62,10 @@ enum ArrId : uint32_t {
     A_UNNEST_RANGE, A_UNNEST_STATUS, A_UNNEST_PARENT, A_UNNEST_OFF,
     // the packing kernel of the batch (batch_api.hip, k_batch_pack): the caller's device buffer up to the end of its last document /
     // the document descriptors / the packed message
-    A_BATCH_SRC, A_BATCH_DOCS, A_BATCH_DST
+    A_BATCH_SRC, A_BATCH_DOCS, A_BATCH_DST,
+    // the projected rows (marshal.hip, sjhip_marshal_rows_paths): the tape index or path status of every cell, column-major / the
+    // text bytes of every row and their prefix / the name pieces / where each begins (text and row offsets: A_MROWS_TEXT, _OUT_OFF)
+    A_MPROJ_IDX, A_MPROJ_OFF, A_MPROJ_NAMES, A_MPROJ_NAME_OFF
 };
 
 #if defined(SJ_DEBUG_BOUNDS)

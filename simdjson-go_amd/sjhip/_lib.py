@@ -110,6 +110,7 @@ SYMBOLS = {
     "sjhip_marshal_json": (C.c_int, [C.c_void_p, szp]),
     "sjhip_fetch_marshaled": (C.c_int, [C.c_void_p, C.c_void_p]),
     "sjhip_marshal_rows": (C.c_int, [C.c_void_p, u64p, szp]),
+    "sjhip_marshal_rows_paths": (C.c_int, [C.c_void_p, C.c_char_p, u32p, u32p, C.c_uint32, C.c_char_p, u32p, C.c_uint32, u64p, szp]),
     "sjhip_fetch_marshaled_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "sjhip_stream_create": (C.c_void_p, [C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_uint32]),
     "sjhip_stream_destroy": (None, [C.c_void_p]),

@@ -784,6 +784,34 @@ class Context:
         self._check(L.sjhip_fetch_marshaled_rows(self._h, off.ctypes.data if offsets else None, out.ctypes.data))
         return (n.value, out.tobytes(), off) if offsets else (n.value, out.tobytes())
 
+    PROJECT_NULLS = 1
+
+    def marshal_rows_paths(self, columns, names=None, nulls=False, fetch=True, offsets=False):
+        """marshal_rows with a select list: of every row of the selection in force only the elements at the paths of `columns` (1 to
+        16 paths, each a sequence of keys; an empty path: the row's own value), as one JSON object per row.  names: the member name
+        of every column (bytes; None: the last key of its path).  A column whose path is not found in a row is left out of that
+        row, or written as null with nulls=True.  -> what marshal_rows returns"""
+        L = _lib.lib()
+        keys = [bytes(k) for path in columns for k in path]
+        nc = len(columns)
+        key_lens = (C.c_uint32 * max(len(keys), 1))(*[len(k) for k in keys])
+        path_lens = (C.c_uint32 * max(nc, 1))(*[len(path) for path in columns])
+        blob = name_lens = None
+        if names is not None:
+            ns = [bytes(x) for x in names]
+            if len(ns) != nc:
+                raise ValueError("marshal_rows_paths: %d names for %d columns" % (len(ns), nc))
+            blob, name_lens = b"".join(ns), (C.c_uint32 * max(nc, 1))(*[len(x) for x in ns])
+        n, tl = C.c_uint64(0), C.c_size_t(0)
+        self._check(L.sjhip_marshal_rows_paths(self._h, b"".join(keys), key_lens, path_lens, nc, blob, name_lens,
+                                               self.PROJECT_NULLS if nulls else 0, C.byref(n), C.byref(tl)))
+        if not fetch:
+            return n.value, tl.value
+        out = np.empty(tl.value, dtype=np.uint8)
+        off = np.empty(n.value + 1, dtype=np.uint64) if offsets else None
+        self._check(L.sjhip_fetch_marshaled_rows(self._h, off.ctypes.data if offsets else None, out.ctypes.data))
+        return (n.value, out.tobytes(), off) if offsets else (n.value, out.tobytes())
+
     def fetch(self, tape_len, strings_len):
         tape = np.empty(tape_len, dtype=np.uint64)
         strings = np.empty(strings_len, dtype=np.uint8)
