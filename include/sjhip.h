@@ -654,6 +654,39 @@ int sjhip_unnest_rows(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_l
                       size_t *rows);
 int sjhip_fetch_row_parents(sjhip_ctx *ctx, uint64_t *parent_offsets /* [parents + 1] */, uint64_t *parent /* [rows] */,
                             uint8_t *parent_status /* [parents] */);
+/* Member rows: the members of the OBJECT at `path` of every row become the rows -- Iter.FindElement(path...) -> Iter.Object() ->
+ * Object.ForEach / NextElementBytes (parsed_object.go), the other half of sjhip_unnest_rows: JSON often keeps a collection as a map
+ * from id to record ("events": {"138586341": {...}, ...}, "plugins": {"git": {...}, ...}).
+ *   sjhip_unnest_members   sjhip_unnest_rows' contract with Iter.Object in the place of Iter.Array: the parents are the rows of the
+ *                          selection in force (without one: the root values of the records); n_keys == 0: the row's own value must be
+ *                          the object.  Parent status: OK, NOT_FOUND, NOT_OBJECT, NULL for a null target, TYPE for an array or a
+ *                          scalar.  The new rows are the VALUES of the direct members, in document order; duplicate names each give
+ *                          a row, as Object.ForEach visits them (not Object.Map's "the last one wins"); what lies inside a value is
+ *                          not a row; an empty object, or a parent whose status is not OK, gives none.  Records keep their status
+ *                          bytes and own what came from the rows they owned; the parents product is the one of sjhip_unnest_rows,
+ *                          and sjhip_fetch_row_parents serves both calls.  The result is an ordinary selection: sjhip_fetch_rows,
+ *                          every call that runs on rows, sjhip_where_path[s], sjhip_order_*, sjhip_group_*, sjhip_aggregate_*,
+ *                          sjhip_filter_rows, sjhip_marshal_rows[_paths] and a further sjhip_unnest_rows / sjhip_unnest_members run
+ *                          on it unchanged (a marshaled or filtered member is its value only).  Errors, failures, lifetime and
+ *                          sharded ND results are those of sjhip_unnest_rows.
+ *   sjhip_extract_row_names  the unescaped names of the rows in force (NextElementBytes' `name`) as the string column: the product of
+ *                          sjhip_extract_path_strings, which it replaces, fetched by sjhip_fetch_path_strings as offsets[rows + 1],
+ *                          data and status; every status is OK.
+ *   sjhip_where_row_names  sjhip_where_path's narrowing with the row's name in the place of the element at a path ("the event whose
+ *                          id is 138586341", "the plugins whose name begins with git").  op: SJHIP_OP_EQ_STRING or
+ *                          SJHIP_OP_PREFIX_STRING, flags: SJHIP_WHERE_NOT; the limits on `value` are sjhip_where_path's.  Every
+ *                          other operator: SJHIP_ERR_ARG.
+ * The two name calls need the selection in force to be one of members -- the one sjhip_unnest_members left, or what sjhip_where_*,
+ * sjhip_where_row_names and the limit of sjhip_order_* narrowed it to: the name of a row is read from the two tape words in front
+ * of its value, nothing is stored per row.  After sjhip_select_rows, sjhip_unnest_rows, sjhip_select_records or a parse they
+ * return SJHIP_ERR_ARG, touch nothing and say "the rows in force are not object members (sjhip_extract_row_names follows
+ * sjhip_unnest_members)".  They work with and without SJHIP_FLAG_COPY_STRINGS and on sharded ND results.
+ * The cost of sjhip_unnest_members is that of sjhip_unnest_rows: one walk of every parent to its object and a fixed number of
+ * passes over the tape, whatever the objects' sizes. */
+int sjhip_unnest_members(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, size_t *records, size_t *parents,
+                         size_t *rows);
+int sjhip_extract_row_names(sjhip_ctx *ctx, size_t *records, size_t *bytes);
+int sjhip_where_row_names(sjhip_ctx *ctx, int op, const void *value, size_t vlen, uint32_t flags, size_t *records, size_t *rows);
 /* Filter rows: the rows of the selection in force -- sjhip_select_rows' or the one sjhip_where_path narrowed or created -- as a new
  * self-contained (Tape, Strings.B) on the device, one root per row: what a caller of ParseND reads with Iter.  With it,
  * sjhip_where_path followed by sjhip_filter_rows is sjhip_filter_where for every operator, for conjunctions and negation, for

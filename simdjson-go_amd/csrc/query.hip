@@ -1263,10 +1263,13 @@ __global__ __launch_bounds__(256) void k_q_unnest_parents(QView q, QPath pth, QU
     u.close[p] = st == SJHIP_COL_OK ? close : 0;
     u.status[p] = (u8)st;
 }
-// MODE 1: the new row starts counted; 2: written, each with its parent (the depth sums are the row selection's MODE 0)
-template <int MODE>
-__global__ __launch_bounds__(TW_THREADS) void k_q_unnest_tile(QView q, QUnnest u, Arr<u64> row_index, Arr<u64> parent) {
+// MODE 1: the new row starts counted; 2: written, each with its parent (the depth sums are the row selection's MODE 0).
+// MEMBERS (sjhip_unnest_members, below): the parents' targets are objects, the starts inside them alternate key, value, and the
+// rows are the values -- the starts of odd rank; the tile counts carry starts, two to a row.
+template <int MODE, bool MEMBERS>
+__device__ __forceinline__ void unnest_tile(const QView &q, const QUnnest &u, Arr<u64> row_index, Arr<u64> parent) {
     static_assert(MODE == 1 || MODE == 2, "count or write");
+    // (the LDS below belongs to the kernel this is inlined into: each of the four instantiations gets its own copy)
     __shared__ long long s_l[TW_THREADS / 64];
     __shared__ unsigned long long s_s[TW_THREADS / 64];
     __shared__ long long s_carry;
@@ -1307,9 +1310,19 @@ __global__ __launch_bounds__(TW_THREADS) void k_q_unnest_tile(QView q, QUnnest u
 #pragma unroll
     for (int k = 0; k < TW_ITEMS; k++)
         if (starts & (1u << k)) {
-            row_index[at] = q.tape_base + base + k;
-            parent[at++] = par[k];
+            if (!MEMBERS) {
+                row_index[at] = q.tape_base + base + k;
+                parent[at] = par[k];
+            } else if (at & 1u) {  // (an even rank: the member's key)
+                row_index[at >> 1] = q.tape_base + base + k;
+                parent[at >> 1] = par[k];
+            }
+            at++;
         }
+}
+template <int MODE>
+__global__ __launch_bounds__(TW_THREADS) void k_q_unnest_tile(QView q, QUnnest u, Arr<u64> row_index, Arr<u64> parent) {
+    unnest_tile<MODE, false>(q, u, row_index, parent);
 }
 // parent_offsets[p] = the new rows in front of parent p: the new row starts below its value (entry n: all of them)
 __global__ __launch_bounds__(256) void k_q_unnest_offsets(QView q, QUnnest u, Arr<const u64> row_index, u64 rows, Arr<u64> out_off, Arr<u8> out_status) {
@@ -1317,6 +1330,48 @@ __global__ __launch_bounds__(256) void k_q_unnest_offsets(QView q, QUnnest u, Ar
     if (p > n) return;
     out_off[p] = p < n ? rows_below(row_index, rows, row_value(q, p)) : rows;
     if (p < n) out_status[p] = u.status[p];
+}
+
+// ---- member rows: the members of the OBJECT at a path of every row become the rows (sjhip_unnest_members) ---------------------------
+// The unnest with Iter.Object in the place of Iter.Array: FindElement + Iter.Object on the value of every parent, and the VALUES of
+// the direct members of those objects, in document order, are the new rows (Object.ForEach / NextElementBytes visit them so:
+// duplicate names each give a row).  The passes are the unnest's, with two kernels of their own:
+//   k_q_members_parents  one lane per parent row: row_object -> the target '{', its '}' and the status, into the unnest's arrays
+//   k_q_members_tile<1>  per tile: the STARTS inside the targets, counted -- keys and values together;  k_tw_scan_sums: the rank
+//                        of the tile's first start, and the total (the host halves it: the rows)
+//   k_q_members_tile<2>  the starts again; the one of rank 2j + 1 is the value of member j: row_index[j], parent[j]
+// A start is what the unnest calls one: a tag word at the parents' depth + n_keys + 1 strictly inside the target of its parent.
+// Inside an object those are the key and the value of every direct member, alternating: a key is a string, two words whose second
+// is raw by the anchor rule, and a value is one start whatever lies inside it.  Every OK parent contributes an even number of them,
+// the parents are disjoint and in document order, so the rank of a start among all starts of the PART is even for a key and odd
+// for a value -- the prefix the count pass computes anyway; a tile that holds an odd number of starts hands the parity on in its
+// prefix.  No object is walked, and no lane's work grows with the members of an object.  The name of a row is not stored: it is
+// the string whose tag word lies two words in front of the row's value (k_q_names_len, k_q_names_mark), which holds for every
+// selection narrowed from this one as well.
+// FindElement + Iter.Object on row r (record r without a selection); an empty path: the row's own value is the object
+__device__ __forceinline__ int row_object(const QView &q, const QPath &pth, u32 r, u64 *v, u64 *close) {
+    *v = pth.n ? record_find_path(q, pth, r) : row_value(q, r);
+    *close = 0;
+    if (*v >= SJHIP_PATH_NOT_OBJECT) return path_status(*v);
+    const u64 w = q.tape[*v];
+    const u32 t = (u32)(w >> 56);
+    if (t == 'n') return SJHIP_COL_NULL;
+    if (t != '{') return SJHIP_COL_TYPE;  // "next item is not object"
+    *close = (w & TW_PAYLOAD) - 1;
+    return SJHIP_COL_OK;
+}
+__global__ __launch_bounds__(256) void k_q_members_parents(QView q, QPath pth, QUnnest u) {
+    const u32 p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= q_rows(q)) return;
+    u64 v = 0, close = 0;
+    const int st = row_object(q, pth, p, &v, &close);
+    u.open[p] = st == SJHIP_COL_OK ? v : 0;
+    u.close[p] = st == SJHIP_COL_OK ? close : 0;
+    u.status[p] = (u8)st;
+}
+template <int MODE>
+__global__ __launch_bounds__(TW_THREADS) void k_q_members_tile(QView q, QUnnest u, Arr<u64> row_index, Arr<u64> parent) {
+    unnest_tile<MODE, true>(q, u, row_index, parent);
 }
 
 
@@ -1354,6 +1409,31 @@ __global__ __launch_bounds__(256) void k_q_where_mark(QView q, QPath pth, int op
     }
     const u64 b = __ballot(keep);  // (the 64 rows of a wave lie in one tile)
     if ((threadIdx.x & 63) == 0 && b) atomicAdd(&w.tiles[i / QTILE], (unsigned long long)__popcll(b));
+}
+// ... by the row's NAME (sjhip_where_row_names): the rows are object members (sjhip_unnest_members), the name of row i is the string
+// whose tag word lies two words in front of its value, and the test is element_is on that string
+__global__ __launch_bounds__(256) void k_q_names_mark(QView q, int op, u64 want, u32 negate, QWhere w) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    bool keep = false;
+    if (i < q_rows(q)) {
+        keep = element_is(q, row_value(q, i) - 2u, op, want) != (negate != 0);
+        w.flag[i] = keep ? 1 : 0;
+    }
+    const u64 b = __ballot(keep);  // (the 64 rows of a wave lie in one tile)
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&w.tiles[i / QTILE], (unsigned long long)__popcll(b));
+}
+// ... and the names as a string column (sjhip_extract_row_names): k_q_col_len's place in front of the column's scan and gather --
+// the element is the name's string, every status is OK; entry n has length 0
+__global__ __launch_bounds__(256) void k_q_names_len(QView q, QCol c) {
+    const u32 r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= q_rows(q)) {
+        if (r == q_rows(q)) c.off[r] = 0;
+        return;
+    }
+    const u64 v = row_value(q, r) - 2u;
+    c.idx[r] = v;
+    c.off[r] = q.tape[v + 1];
+    c.status[r] = (u8)SJHIP_COL_OK;
 }
 // ... by SEVERAL tests (sjhip_where_paths): the mark of a plan of predicates (sj_where.h).  One lane per row runs table_walk over
 // the predicates' paths -- every member of the row is met once, however many tests look at it --, the sink evaluates the predicate
@@ -2882,13 +2962,15 @@ struct ColumnBuild {
     QPath pth;
     uint32_t cvt;
     size_t *records, *bytes;
+    bool names = false;  // sjhip_extract_row_names: the names of the member rows in force, no path
     size_t work(Carve c, const sjhip_ctx *, uint32_t n, QCol *col, unsigned long long **totals) const {
         *totals = c.take<unsigned long long>(32);
         col_work(c, n, col);
         return c.used;
     }
     int measure(sjhip_ctx *ctx, sjhip_ctx *part, const QView &q, uint32_t n, const QCol &c, size_t, unsigned long long *totals) const {
-        hipLaunchKernelGGL(k_q_col_len, dim3((n + 1u + 255) / 256), dim3(256), 0, part->stream, q, pth, cvt, c);
+        if (names) hipLaunchKernelGGL(k_q_names_len, dim3((n + 1u + 255) / 256), dim3(256), 0, part->stream, q, c);
+        else hipLaunchKernelGGL(k_q_col_len, dim3((n + 1u + 255) / 256), dim3(256), 0, part->stream, q, pth, cvt, c);
         col_scan(part, n, c, totals);
         HIPCHK(hipGetLastError(), "column launch");
         HIPCHK(hipMemcpyAsync(part->h_scratch + 512, totals + 2, 8, hipMemcpyDeviceToHost, part->stream), "D2H column bytes");
@@ -3366,9 +3448,10 @@ static int where_narrow(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, c
     if (rc) return rc;
     ResultState::Rows total;
     total.depth = sel ? ctx->res.rows.sizes().depth : 0u;  // (the rows keep their depth; the root values of the records lie at 0)
+    total.members = sel && ctx->res.rows.sizes().members;   // (... and their names: nothing is stored per row)
     bool ok = true;  // (a part without rows launched nothing and is republished as it was: its records, no rows)
     for (size_t k = 0; k < parts.size(); k++) {
-        const ResultState::Rows s = {(size_t)parts[k]->q_records + 1u, kept[k], total.depth};
+        const ResultState::Rows s = {(size_t)parts[k]->q_records + 1u, kept[k], total.depth, total.members};
         ok &= parts[k]->res.publish(&ResultState::rows, s);
         total.records += s.records, total.rows += s.rows;
     }
@@ -3629,12 +3712,17 @@ static size_t unnest_layout(Carve c, const sjhip_ctx *part, uint32_t n, u32 dept
     w->ok = c.take<u8>(recs);
     return c.used;
 }
-static int unnest_build(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, const uint8_t *keys, size_t klen, const QPath &pth,
+// members: sjhip_unnest_members -- the parents' targets are objects and the tile passes are k_q_members_tile, whose counts are
+// starts, two to a row; everything else is the same for both calls.
+static int unnest_build(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, const uint8_t *keys, size_t klen, const QPath &pth, bool members,
                         size_t *records, size_t *parents, size_t *rows) {
     const bool sel = selected(ctx, true);
     const u32 depth = (sel ? ctx->res.rows.sizes().depth : 0u) + pth.n + 1u;  // of the new rows below their record's root value
     std::vector<UnnestWork> work(parts.size());
     std::vector<size_t> found(parts.size(), 0);
+    void (*const k_parents)(QView, QPath, QUnnest) = members ? k_q_members_parents : k_q_unnest_parents;
+    void (*const k_count)(QView, QUnnest, Arr<u64>, Arr<u64>) = members ? k_q_members_tile<1> : k_q_unnest_tile<1>;
+    void (*const k_write)(QView, QUnnest, Arr<u64>, Arr<u64>) = members ? k_q_members_tile<2> : k_q_unnest_tile<2>;
     int rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, true, "unnest sync",
         [&](const sjhip_ctx *part, uint32_t n) {
             UnnestWork w;
@@ -3647,13 +3735,13 @@ static int unnest_build(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, c
             unsigned long long *const none = nullptr;
             const Arr<u64> no_index = SJ_ARR((u64 *)nullptr, 0, A_ROWS), no_parent = SJ_ARR((u64 *)nullptr, 0, A_UNNEST_PARENT);
             HIPCHK(hipMemsetAsync(w.totals, 0, 256, part->stream), "unnest totals memset");
-            hipLaunchKernelGGL(k_q_unnest_parents, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, pth, w.u);
+            hipLaunchKernelGGL(k_parents, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, pth, w.u);
             hipLaunchKernelGGL(k_q_rows_tile<0>, tiles, block, 0, part->stream, q, w.u.t, 0u, no_index);
             hipLaunchKernelGGL(k_q_rows_last, tiles, block, 0, part->stream, q, w.u.t);  // (these three end at once unless a tile asked)
             hipLaunchKernelGGL(k_q_rows_scan_last, one, wide, 0, part->stream, w.u.t, tiles.x);
             hipLaunchKernelGGL(k_q_rows_tile<0>, tiles, block, 0, part->stream, q, w.u.t, 1u, no_index);
             hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, part->stream, w.u.t.depth, none, none, tiles.x, w.totals);
-            hipLaunchKernelGGL(k_q_unnest_tile<1>, tiles, block, 0, part->stream, q, w.u, no_index, no_parent);
+            hipLaunchKernelGGL(k_count, tiles, block, 0, part->stream, q, w.u, no_index, no_parent);
             hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, part->stream, none, w.u.t.cnt, none, tiles.x, w.totals);  // the rows: totals[1]
             HIPCHK(hipGetLastError(), "unnest launch");
             HIPCHK(hipMemcpyAsync(part->h_scratch + 512, w.totals + 1, 8, hipMemcpyDeviceToHost, part->stream), "D2H unnested row count");
@@ -3661,6 +3749,7 @@ static int unnest_build(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, c
         },
         [&](size_t k, sjhip_ctx *part) {
             found[k] = part_rows(ctx, part, true) ? (size_t)*(const unsigned long long *)(part->h_scratch + 512) : 0;
+            if (members) found[k] /= 2;  // (the starts of a part: a key and a value for every member)
         });
     if (rc) return rc;
     rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, true, "unnest gather sync", [](const sjhip_ctx *, uint32_t) { return (size_t)0; },
@@ -3672,7 +3761,7 @@ static int unnest_build(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, c
             if (rc) return rc;
             const Arr<const u64> index = SJ_ARR((const u64 *)po.new_index, got, A_ROWS);
             if (got)
-                hipLaunchKernelGGL(k_q_unnest_tile<2>, dim3(RowsBuild::tape_tiles(part)), dim3(TW_THREADS), 0, part->stream, q, w.u,
+                hipLaunchKernelGGL(k_write, dim3(RowsBuild::tape_tiles(part)), dim3(TW_THREADS), 0, part->stream, q, w.u,
                                    SJ_ARR(po.new_index, got, A_ROWS), SJ_ARR(po.parent, got, A_UNNEST_PARENT));
             // the records: their new offsets, and the status bytes they had (without a selection: OK)
             QRows hand = w.u.t;
@@ -3703,9 +3792,10 @@ static int unnest_build(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, c
     ResultState::Rows total;
     ResultState::Parents joined;
     total.depth = depth;
+    total.members = members;
     bool ok = true;  // (a part without parents launched nothing: its selection, no rows, keeps its offsets and statuses)
     for (size_t k = 0; k < parts.size(); k++) {
-        const ResultState::Rows s = {(size_t)parts[k]->q_records + 1u, found[k], depth};
+        const ResultState::Rows s = {(size_t)parts[k]->q_records + 1u, found[k], depth, members};
         const ResultState::Parents p = {(size_t)part_rows(ctx, parts[k], true), found[k]};
         total.records += s.records, total.rows += s.rows;
         joined.parents += p.parents, joined.rows += p.rows;
@@ -3716,11 +3806,12 @@ static int unnest_build(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, c
     return published(ctx, ok);
 }
 
-int sjhip_unnest_rows(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, size_t *records, size_t *parents,
-                      size_t *rows) {
+// sjhip_unnest_rows and sjhip_unnest_members (`who`): the checks, which touch nothing, then the build
+static int unnest_entry(sjhip_ctx *ctx, const char *who, bool members, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys,
+                        size_t *records, size_t *parents, size_t *rows) {
     if (!ctx) return SJHIP_ERR_ARG;
     if (!records || !parents || !rows) {
-        ctx_set_error(ctx, "sjhip_unnest_rows: a null size pointer");
+        ctx_set_error(ctx, "%s: a null size pointer", who);
         return SJHIP_ERR_ARG;
     }
     QPath pth;
@@ -3734,15 +3825,64 @@ int sjhip_unnest_rows(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_l
     // ---- nothing was touched up to here; from here on the last parents product is gone ----
     ctx->res.parents.begin();
     for (sjhip_ctx *part : parts) part->res.parents.begin();
-    rc = unnest_build(ctx, parts, kb, klen, pth, records, parents, rows);
+    rc = unnest_build(ctx, parts, kb, klen, pth, members, records, parents, rows);
     if (rc) {  // half-built: the old selection may have been written over
         ctx->res.rows.begin(), ctx->res.parents.begin();
         for (sjhip_ctx *part : parts) part->res.rows.begin(), part->res.parents.begin();
         char why[sizeof ctx->err];
         snprintf(why, sizeof why, "%s", ctx->err);
-        ctx_set_error(ctx, "sjhip_unnest_rows failed, the row selection was given up and no row parents are left: %.160s", why);
+        ctx_set_error(ctx, "%s failed, the row selection was given up and no row parents are left: %.160s", who, why);
     }
     return rc;
+}
+int sjhip_unnest_rows(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, size_t *records, size_t *parents,
+                      size_t *rows) {
+    return unnest_entry(ctx, "sjhip_unnest_rows", false, keys, key_lens, n_keys, records, parents, rows);
+}
+int sjhip_unnest_members(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, size_t *records, size_t *parents,
+                         size_t *rows) {
+    return unnest_entry(ctx, "sjhip_unnest_members", true, keys, key_lens, n_keys, records, parents, rows);
+}
+
+// ---- the names of member rows ------------------------------------------------------------------------------------------------------
+// Both calls need the selection in force to be one of object members (ResultState::Rows::members: sjhip_unnest_members and every
+// narrowing of what it left); the check comes first and touches nothing.
+static int need_member_rows(sjhip_ctx *ctx) {
+    if (ctx->res.member_rows()) return SJHIP_OK;
+    ctx_set_error(ctx, "the rows in force are not object members (sjhip_extract_row_names follows sjhip_unnest_members)");
+    return SJHIP_ERR_ARG;
+}
+int sjhip_extract_row_names(sjhip_ctx *ctx, size_t *records, size_t *bytes) {
+    if (!ctx || !records || !bytes) return SJHIP_ERR_ARG;
+    if (need_member_rows(ctx)) return SJHIP_ERR_ARG;
+    ColumnBuild p;
+    p.pth = QPath{}, p.cvt = 0, p.records = records, p.bytes = bytes, p.names = true;
+    return build_product(ctx, &NO_VALUE, 0, p);
+}
+int sjhip_where_row_names(sjhip_ctx *ctx, int op, const void *value, size_t vlen, uint32_t flags, size_t *records, size_t *rows) {
+    if (!ctx || !records || !rows) return SJHIP_ERR_ARG;
+    if (flags & ~SJHIP_WHERE_NOT) {
+        ctx_set_error(ctx, "sjhip_where_row_names: unknown flag bits 0x%x", flags & ~SJHIP_WHERE_NOT);
+        return SJHIP_ERR_ARG;
+    }
+    bool is_str = false;
+    u64 want = 0;
+    if ((op != SJHIP_OP_EQ_STRING && op != SJHIP_OP_PREFIX_STRING) || predicate_value(op, value, vlen, &want, &is_str)) {
+        ctx_set_error(ctx, "sjhip_where_row_names: operator %d with a value of %zu bytes (a name is a string: SJHIP_OP_EQ_STRING, SJHIP_OP_PREFIX_STRING)", op, vlen);
+        return SJHIP_ERR_ARG;
+    }
+    if (need_member_rows(ctx)) return SJHIP_ERR_ARG;
+    const uint8_t *const vb = value ? (const uint8_t *)value : &NO_VALUE;
+    std::vector<sjhip_ctx *> parts;
+    int rc = query_parts(ctx, &NO_VALUE, 0, vb, vlen, &parts);
+    if (rc) return rc;  // (nothing has been queued: the selection is as it was)
+    const u32 negate = flags & SJHIP_WHERE_NOT;
+    rc = where_build(ctx, parts, &NO_VALUE, 0, vb, vlen,
+                     [&](sjhip_ctx *part, const QView &q, uint32_t n, const QWhere &w) {
+                         hipLaunchKernelGGL(k_q_names_mark, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, op, want, negate, w);
+                     },
+                     records, rows);
+    return rc ? where_gave_up(ctx, parts, "sjhip_where_row_names", rc) : rc;
 }
 
 int sjhip_fetch_row_parents(sjhip_ctx *ctx, uint64_t *parent_offsets, uint64_t *parent, uint8_t *parent_status) {

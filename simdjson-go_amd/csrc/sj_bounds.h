@@ -58,7 +58,9 @@ enum ArrId : uint32_t {
     // histograms
     A_SORT, A_SORT_HIST,
     // the unnested rows (query.hip, sjhip_unnest_rows): the target range of every parent row / the status byte of every parent, in
-    // the work arrays and in the product / the parent number of every new row / the parent offsets
+    // the work arrays and in the product / the parent number of every new row / the parent offsets.  The member rows
+    // (sjhip_unnest_members) run on the same arrays under the same ids; their names are read through A_TAPE and written through
+    // A_COL (sjhip_extract_row_names), their predicate marks through A_WHERE_* (sjhip_where_row_names)
     A_UNNEST_RANGE, A_UNNEST_STATUS, A_UNNEST_PARENT, A_UNNEST_OFF,
     // the packing kernel of the batch (batch_api.hip, k_batch_pack): the caller's device buffer up to the end of its last document /
     // the document descriptors / the packed message

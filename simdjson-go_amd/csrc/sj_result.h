@@ -35,8 +35,10 @@ public:
     struct ListColumn { size_t records = 0, elems = 0, bytes = 0; bool strings = false; };  // (numbers or strings: what was published)
     static constexpr int TABLE_COLS = 16;  // SJHIP_TABLE_MAX_COLS
     // the records the selection ran over, the rows it found, and the depth of every row's value below its record's root value (0:
-    // the rows are root values; sjhip_select_rows and every sjhip_unnest_rows add n_keys + 1; a narrowing hands it on)
-    struct Rows { size_t records = 0, rows = 0; uint32_t depth = 0; };
+    // the rows are root values; sjhip_select_rows and every sjhip_unnest_rows / sjhip_unnest_members add n_keys + 1; a narrowing hands
+    // it on); members: the rows are the values of object members (sjhip_unnest_members) -- the name of row r is the string two words
+    // in front of its value; a narrowing hands it on, sjhip_select_rows and sjhip_unnest_rows publish it false
+    struct Rows { size_t records = 0, rows = 0; uint32_t depth = 0; bool members = false; };
     struct Parents { size_t parents = 0, rows = 0; };  // the rows sjhip_unnest_rows ran over, the rows it left
     // the grouping (sjhip_group_path, sjhip_group_paths): the rows it ran over, its groups, and what its fetches need to know: the
     // kinds of its key columns (at least one in a published grouping; sjhip_group_path: exactly one) and of its value columns
@@ -163,6 +165,7 @@ public:
     bool serialized() const { return tenant_ == Tenant::Serialized; }
     bool marshaled() const { return tenant_ == Tenant::Marshaled; }
     bool list_of(bool strings) const { return list.exists() && list.sizes().strings == strings; }  // a list column of this kind
+    bool member_rows() const { return rows.exists() && rows.sizes().members; }  // the selection in force is one of object members
 
     // ---- what the last publish / parse_done left (meaningful while the predicate beside it holds) ----
     uint64_t tape_base() const { return tape_base_; }

@@ -648,6 +648,39 @@ class Context:
         self._check(_lib.lib().sjhip_fetch_row_parents(self._h, offsets.ctypes.data, parent.ctypes.data, status.ctypes.data))
         return offsets, parent[:rows], status[:parents]
 
+    # ---- member rows (include/sjhip.h: sjhip_unnest_members / sjhip_extract_row_names / sjhip_where_row_names) ----------------------
+    def unnest_members(self, path=()):
+        """Iter.FindElement(path...), Iter.Object, Object.ForEach on every ROW of the selection in force (without one: on every
+        record's root value): the VALUES of the members of those objects become the rows, duplicate names included; unnest_rows'
+        contract otherwise.  An empty path: the row's own value is the object (maps of maps).
+        -> (records, parents, rows); fetch_rows and fetch_row_parents deliver the selection and the join back,
+        extract_row_names the names"""
+        blob, lens, n = self._keys(path)
+        nr, npar, nw = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        self._check(_lib.lib().sjhip_unnest_members(self._h, blob if n else None, lens if n else None, n, C.byref(nr), C.byref(npar),
+                                                    C.byref(nw)))
+        return nr.value, npar.value, nw.value
+
+    def extract_row_names(self, fetch=True):
+        """the unescaped member names of the rows in force -- unnest_members' rows, or what where_* / order_*(limit) kept of them --
+        as the string column.  -> extract_path_strings' (offsets, data, status), every status COL_OK; with fetch=False the column
+        stays on the device and (rows, bytes) is returned (fetch_path_strings delivers it)"""
+        nr, nb = C.c_size_t(0), C.c_size_t(0)
+        self._check(_lib.lib().sjhip_extract_row_names(self._h, C.byref(nr), C.byref(nb)))
+        if not fetch:
+            return nr.value, nb.value
+        return self.fetch_path_strings(nr.value, nb.value)
+
+    def where_row_names(self, op, value, negate=False):
+        """where_path with the row's member name in the place of the element at a path: op = OP_EQ_STRING or OP_PREFIX_STRING,
+        value = bytes; negate keeps the others.  Needs a selection of members.  -> (records, rows kept)"""
+        v = bytes(value)
+        buf = C.create_string_buffer(v, max(len(v), 1))
+        nr, nw = C.c_size_t(0), C.c_size_t(0)
+        self._check(_lib.lib().sjhip_where_row_names(self._h, int(op), buf, len(v), self.WHERE_NOT if negate else 0, C.byref(nr),
+                                                     C.byref(nw)))
+        return nr.value, nw.value
+
     # ---- order (include/sjhip.h: sjhip_order_path / sjhip_fetch_order) -----------------------------------------------------------
     ORDER_DESC = 1
     ORDER_SORT_TILE = 1024  # rows per tile of the device's sort by key (csrc/sj_sort.h): the largest tile of the ordering's kernels
