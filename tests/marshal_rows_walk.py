@@ -12,6 +12,8 @@ row's brackets rebased as filter_rows_walk.py does and the strings left where th
 unchanged); the text between the outer '[' and ']' is the row's.  So a scalar row is formatted by the oracle as well.
 
 What this must equal is decided outside it (tests/test_marshal_rows_walk.py asks the oracle's marshal_json of whole documents)."""
+import functools
+
 import numpy as np
 
 import oracle_lib as O
@@ -27,7 +29,12 @@ def row_end(w, v):
 
 
 def row_text(w, v):
-    v = int(v)
+    return _row_text(w, int(v))
+
+
+@functools.lru_cache(maxsize=1 << 16)
+def _row_text(w, v):
+    """(a walk is hashed by identity and never edited: the text of the value at v is computed once per walk)"""
     end = row_end(w, v)
     n = end - v
     dw = 2 - v  # the row's first word becomes word 2

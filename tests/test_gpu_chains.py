@@ -46,6 +46,21 @@ def test_chain(large, chain):
         fresh.close()
 
 
+@pytest.mark.parametrize("chain", CM.CHAINS_M, ids=CM.chain_id)
+def test_member_chain(large, chain):
+    """chain_model.CHAINS_M: the chains of the extended generator -- the member rows and their `members` flag through every
+    narrowing and every selection change, the row names as the string column, the projection as a tenant and beside live
+    products, the two readers --, run and compared as test_chain does"""
+    if not chain[3]:
+        return CM.run_on(large, chain, extended=True)
+    import sjhip
+    fresh = sjhip.Context(0)
+    try:
+        CM.run_on(fresh, chain, extended=True)
+    finally:
+        fresh.close()
+
+
 # ---- a sharded result -----------------------------------------------------------------------------------------------------------------
 SHARDED_CHAIN = [  # eight steps, drawn only from the calls that accept a sharded result
     ("call", "where_path", ((b"k",), 10, 2, {})),                                   # OP_GE_INT: the records with k >= 2
@@ -108,6 +123,70 @@ def test_chain_on_a_sharded_result():
                 assert e.value.code == CM.ERR_ARG, (k, many.last_error())
         assert info["parents"][1] > 5000 and info["column"][0] > 7000  # (the chain ran on rows, not on nothing)
         for what in ("column", "parents", "table"):
+            assert CM.differs(CM.device_fetch(many, what, info[what]), CM.device_fetch(one, what, info[what])) is None, what
+        assert many.find_path(b"k").tolist() == one.find_path(b"k").tolist()
+    finally:
+        many.close()
+        one.close()
+
+
+SHARDED_MEMBER_CHAIN = [
+    ("call", "unnest_members", ((b"m",),)),
+    ("call", "where_row_names", (19, b"b", {"negate": True})),                      # OP_PREFIX_STRING: the members not named b...
+    ("call", "extract_row_names", ({"fetch": False},)),
+    ("call", "where_path", ((), 10, 20, {})),                                       # OP_GE_INT on the member's own value
+    ("call", "aggregate_path_records", ((), CM.I)),
+    ("fetch", "column", ()),
+    ("call", "select_records", ()),
+    ("invalid", "extract_row_names", ("not_members", 4, b"a")),
+]
+
+
+def test_member_chain_on_a_sharded_result():
+    """test_chain_on_a_sharded_result for the member rows: the same padded 11 000 records with one more member each, a map "m" of
+    r % 4 members, and SHARDED_MEMBER_CHAIN on the sharded context and on one that parsed the document whole -- every return value
+    and every array must be equal, and the name call behind select_records is refused on both.  Between the steps every call that
+    refuses a sharded result is issued on the sharded context, sjhip_marshal_rows_paths among them (sjhip.h: "a sharded ND
+    result" is one of its SJHIP_ERR_ARG cases)."""
+    import sjhip
+    pad = "x" * 230
+    doc = "\n".join('{"pad":"%s","k":%d,"m":{%s}}' % (pad, r % 7, ",".join('"%s%d":%d' % ("abc"[j], r % 5, r + j) for j in range(r % 4)))
+                    for r in range(11000)).encode()
+    assert len(doc) > 5 << 19
+    refused = [lambda c: c.filter_rows(fetch=False), lambda c: c.marshal_rows(fetch=False), lambda c: c.marshal_rows_paths([(b"k",)], fetch=False),
+               lambda c: c.marshal_rows_paths([()], names=[b"v"], nulls=True, fetch=False), lambda c: c.serialize(fetch=False),
+               lambda c: c.group_path((b"k",), CM.I, fetch=False), lambda c: c.order_path((b"k",), CM.I, fetch=False)]
+    many, one = sjhip.Context(0), sjhip.Context(0)
+    try:
+        with fixtures.nd_shard_limits(2 << 20, 1 << 20):
+            many.parse(doc, ndjson=True)
+        one.parse(doc, ndjson=True)
+        with pytest.raises(sjhip.ParseError):
+            many.marshal_rows_paths([(b"k",)], fetch=False)
+        assert "shard by shard" in many.last_error()
+        info = {}
+        for k, (do, name, args) in enumerate(SHARDED_MEMBER_CHAIN):
+            if do == "fetch":
+                got, want = (CM.device_fetch(c, name, info[name]) for c in (many, one))
+                assert CM.differs(got, want) is None, (k, name, CM.differs(got, want))
+            elif do == "invalid":
+                assert [CM.device_invalid(c, name, args) for c in (many, one)] == [CM.ERR_ARG] * 2, (k, many.last_error(), one.last_error())
+            else:
+                got, want = (CM.device_call(c, name, args) for c in (many, one))
+                assert got[0] == want[0], (k, name, got[0], want[0])
+                assert (got[3] is None) == (want[3] is None) and (got[3] is None or CM.differs(got[3], want[3]) is None), (k, name)
+                if got[1]:
+                    info[got[1]] = got[2]
+                if name in CM.SELECTION_CALLS_M and name != "select_records":
+                    sizes = (got[0][0], got[0][-1])
+                    info["rows"] = sizes
+                    assert CM.differs(CM.device_fetch(many, "rows", sizes), CM.device_fetch(one, "rows", sizes)) is None, (k, name)
+            for call in refused:
+                with pytest.raises(sjhip.ParseError) as e:
+                    call(many)
+                assert e.value.code == CM.ERR_ARG, (k, many.last_error())
+        assert info["parents"] == (11000, 16500) and 5000 < info["column"][0] < 16500  # (the chain ran on rows, and the names were narrowed)
+        for what in ("column", "parents"):
             assert CM.differs(CM.device_fetch(many, what, info[what]), CM.device_fetch(one, what, info[what])) is None, what
         assert many.find_path(b"k").tolist() == one.find_path(b"k").tolist()
     finally:
