@@ -687,6 +687,39 @@ int sjhip_unnest_members(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *ke
                          size_t *rows);
 int sjhip_extract_row_names(sjhip_ctx *ctx, size_t *records, size_t *bytes);
 int sjhip_where_row_names(sjhip_ctx *ctx, int op, const void *value, size_t vlen, uint32_t flags, size_t *records, size_t *rows);
+/* Row schema: which member names the rows in force have, how often each occurs and with values of which types -- what Arrow's JSON
+ * reader or json_normalize find out before they build a table, without the tape crossing to the host.
+ *   sjhip_row_schema        evaluates FindElement + Iter.Object on the value of every row of the selection in force (without one: the
+ *                           root value of every record), with sjhip_unnest_members' status bytes; n_keys == 0: the row's own value
+ *                           must be the object.  status[s] = the rows with status byte s (SJHIP_COL_OK .. SJHIP_COL_RANGE), *rows
+ *                           their sum.  Every OK row contributes its direct members as Object.ForEach visits them -- a name that
+ *                           occurs twice in one object counts twice --, *members is their number.  A name is the unescaped bytes
+ *                           of the key ("\u0061" and "a" are one name, "a" and "A" are two, the empty name is a name); names are
+ *                           numbered by first occurrence in document order, *names of them, *name_bytes in their dictionary.
+ *   sjhip_fetch_row_schema  name_offsets[names + 1] and name_data[name_bytes]: the dictionary; first_row[k]: the number, in the
+ *                           selection in force at the call, of the first row that has name k; counts[k * SJHIP_SCHEMA_TYPES + (T - 1)]:
+ *                           the members named k whose value has type T -- the reference's Type of the value's tape tag (TagToType):
+ *                           true and false are both BOOL; an integer that fits int64 is INT, a larger one UINT, anything with a
+ *                           fraction or an exponent FLOAT.  The counts add up to *members.  Any destination may be NULL.
+ * The call reads the selection and leaves it -- its rows, its `members` property, its depth --, the row parents and every other
+ * product exactly as they were: sjhip_fetch_rows returns after it what it returned before.  The schema is a product of its own with
+ * its own device arenas (counted by sjhip_ctx_device_bytes, freed by sjhip_ctx_trim) and lasts until the next parse or the next
+ * sjhip_row_schema.  No rows, or no members, is legal: an empty schema is published and nothing more is launched than it takes to
+ * know that.  Works after parses with and without SJHIP_FLAG_COPY_STRINGS.  Nested objects are not descended into: call again with
+ * the path of a name whose OBJECT count is not zero.
+ * Errors: SJHIP_ERR_ARG, with sjhip_last_error naming the reason and nothing touched (the previous schema included): no result on
+ * the device, a bad path, a null size pointer, a fetch without a schema, a sharded ND result ("... is sharded": the dictionaries of
+ * shards are not joined, as for the groups).  More than 2^28 members: SJHIP_ERR_TOOBIG -- known only after the members have been
+ * counted, so, like a call that fails later (SJHIP_ERR_HIP), it leaves no schema (the previous one is gone) and the selection as
+ * it was.  The cost is sjhip_unnest_members' walk and a fixed number of passes over the
+ * members, whatever the number of distinct names. */
+enum { SJHIP_TYPE_NULL = 1, SJHIP_TYPE_STRING = 2, SJHIP_TYPE_INT = 3, SJHIP_TYPE_UINT = 4, SJHIP_TYPE_FLOAT = 5,
+       SJHIP_TYPE_BOOL = 6, SJHIP_TYPE_OBJECT = 7, SJHIP_TYPE_ARRAY = 8 };   /* the reference's Type values (TagToType) */
+#define SJHIP_SCHEMA_TYPES 8
+int sjhip_row_schema(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys,
+                     size_t *rows, uint64_t status[6], uint64_t *members, size_t *names, size_t *name_bytes);
+int sjhip_fetch_row_schema(sjhip_ctx *ctx, uint64_t *name_offsets /* [names + 1] */, uint8_t *name_data /* [name_bytes] */,
+                           uint64_t *first_row /* [names] */, uint64_t *counts /* [names * SJHIP_SCHEMA_TYPES] */);
 /* Filter rows: the rows of the selection in force -- sjhip_select_rows' or the one sjhip_where_path narrowed or created -- as a new
  * self-contained (Tape, Strings.B) on the device, one root per row: what a caller of ParseND reads with Iter.  With it,
  * sjhip_where_path followed by sjhip_filter_rows is sjhip_filter_where for every operator, for conjunctions and negation, for

@@ -808,8 +808,9 @@ extern "C" void sj_selftest_newlines_to_cr_words(const uint32_t *in, uint32_t *o
 //   33 parents.begin (the first step of sjhip_unnest_rows behind its argument checks)   34 publish parents
 //   35 publish rows as sjhip_unnest_members does (members set)   36 publish rows as a narrowing does (where_narrow: `members` of the
 //   selection in force handed on, false without one)
+//   37 drop_schema (the first step of sjhip_row_schema behind its argument checks)   38 publish_schema
 // bits: 0 pending, 1 whole, 2 resident, 3 sharded, 4 key_flags, 5 packed, 6 filtered, 7 serialized, 8 marshaled, 9 column,
-// 10 list of numbers, 11 list of strings, 12 table, 13 rows, 14 groups, 15 order, 16 parents, 17 the rows are object members.  Returns 0, or 1 + the index of an unknown code.
+// 10 list of numbers, 11 list of strings, 12 table, 13 rows, 14 groups, 15 order, 16 parents, 17 the rows are object members, 18 schema.  Returns 0, or 1 + the index of an unknown code.
 #include "sj_result.h"
 extern "C" int sj_selftest_result_state(const uint8_t *ops, size_t n, uint32_t *bits_out) {
     sj::ResultState s;
@@ -842,13 +843,15 @@ extern "C" int sj_selftest_result_state(const uint8_t *ops, size_t n, uint32_t *
         else if (op == 34) s.publish(&sj::ResultState::parents, {1, 1});
         else if (op == 35) s.publish(&sj::ResultState::rows, {1, 1, 1, true});
         else if (op == 36) s.publish(&sj::ResultState::rows, {1, 1, s.rows.exists() ? s.rows.sizes().depth : 0u, s.member_rows()});
+        else if (op == 37) s.drop_schema();
+        else if (op == 38) s.publish_schema({1, 1, 1, 1});
         else return 1 + (int)k;
         bits_out[k] = (uint32_t)s.pending() | (uint32_t)s.whole() << 1 | (uint32_t)s.resident() << 2 | (uint32_t)s.sharded() << 3 |
                       (uint32_t)s.key_flags() << 4 | (uint32_t)s.packed() << 5 | (uint32_t)s.filtered() << 6 |
                       (uint32_t)s.serialized() << 7 | (uint32_t)s.marshaled() << 8 | (uint32_t)s.column.exists() << 9 |
                       (uint32_t)s.list_of(false) << 10 | (uint32_t)s.list_of(true) << 11 | (uint32_t)s.table.exists() << 12 |
                       (uint32_t)s.rows.exists() << 13 | (uint32_t)s.groups.exists() << 14 |
-                      (uint32_t)s.order.exists() << 15 | (uint32_t)s.parents.exists() << 16 | (uint32_t)s.member_rows() << 17;
+                      (uint32_t)s.order.exists() << 15 | (uint32_t)s.parents.exists() << 16 | (uint32_t)s.member_rows() << 17 | (uint32_t)s.schema.exists() << 18;
     }
     return 0;
 }

@@ -15,6 +15,7 @@
 // Strings are compared after unescaping (they are read from Strings.B / the message exactly as the Iter API does).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <array>
@@ -1372,6 +1373,211 @@ __global__ __launch_bounds__(256) void k_q_members_parents(QView q, QPath pth, Q
 template <int MODE>
 __global__ __launch_bounds__(TW_THREADS) void k_q_members_tile(QView q, QUnnest u, Arr<u64> row_index, Arr<u64> parent) {
     unnest_tile<MODE, true>(q, u, row_index, parent);
+}
+
+// ---- row schema: the distinct member names of the rows, counted per value type (sjhip_row_schema) -----------------------------------
+// "Which names do these rows have, how often, and with values of which types": FindElement + Iter.Object on every row in force, as
+// sjhip_unnest_members evaluates it, and every direct member of those objects counted under (its unescaped name, the Type of its
+// value).  Names are numbered by first occurrence in document order, so the dictionary, first_row and the counts are decided by the
+// input alone.  The selection and every other product are read, never written: the member walk runs into the work arenas.
+//   the member walk     k_q_members_parents, the depth prefix, k_q_members_tile<1>, the scan, k_q_members_tile<2> -- launched as
+//                       sjhip_unnest_members launches them -- leave the value index of every member (idx[j], document order) and the
+//                       number of its parent row (parent[j])
+//   k_q_schema_status   the parents' status bytes counted: six ballots per 64 parents, four such steps per wave, then ONE atomic
+//                       instruction per wave -- lane s adds the count of status s
+//   k_q_schema_keys     one lane per member: the name is the string two words in front of the value (k_q_names_len); its hash
+//                       (sj_group.h, over the unescaped bytes wherever they lie: str_bytes) and the type class of the value's tag
+//   k_q_schema_insert   the dictionary: k_q_group_insert's open-addressing table of MEMBER numbers behind a wave-level election, below
+//   k_q_schema_first    member j is the first of its name iff table[slot[j]] == j -> flag, and the length of its name; exclusive
+//                       scans (k_q_schema_tile_sums, k_tw_scan_sums, k_q_schema_tile_apply) number the names and place their bytes;
+//                       the totals are the names and the dictionary's bytes -- the one value of the second half the host waits for
+//   k_q_schema_emit     every member: the sort key code * 8 + class; the first members: their name's offset, bytes (a short name by
+//                       the lane, a long one by the wave) and first_row = the parent row
+//   the sort            sj_sort.h, stable, over only the digits names * 8 has
+//   k_q_schema_bounds   in the sorted keys a run of one key begins where the key in front differs and ends where the next one does
+//   k_q_schema_counts   counts[key] = end - begin (0, 0 for a key that does not occur) -- no contended atomics anywhere
+// THE ELECTION.  A schema call brings tens of members per row to a handful of names: on parking-citations a million rows are
+// twenty million members on about twenty slots.  In k_q_group_insert every lane probes for itself, so the 64 lanes of a wave issue
+// 64 atomic loads that land on a few L2 lines -- the channel serialises them -- and then compare their bytes with the occupant's.
+// Here the wave first settles what it can inside itself, in at most SCHEMA_ELECT_ROUNDS rounds: the lowest pending lane is the
+// leader (one ballot, one find-first-set); its hash, name length and string word are broadcast (three shuffles); every pending lane
+// whose hash and length equal the leader's compares its name's bytes with the leader's -- all of them read the same addresses, one
+// request --; the leader alone probes the table, exactly as k_q_group_insert probes it, and the slot it ended in is broadcast; the
+// lanes whose bytes matched take that slot and retire.  The lanes still pending after the rounds probe for themselves.
+// Why this is the same dictionary: (1) a lane takes the leader's slot only after comparing the bytes -- equal hashes with different
+// bytes stay pending, nothing merges; (2) a pending lane either matches the leader, or stays pending and reaches its own probe, so
+// nothing is lost; (3) a name ends in the first slot of its probe sequence that did not hold a different name whoever probes for it
+// (the argument of k_q_group_insert), so the leader's slot IS the slot of every lane with its name; (4) member numbers grow with
+// the lane, so a leader is the smallest member of its name in its wave; the smallest member of a name in the whole input is
+// therefore never retired by another lane -- it probes, as a leader or for itself -- and atomicMin leaves it in the slot.
+// SCHEMA_ELECT_ROUNDS is measured, not reasoned (tools/schema_time.py --exp, profiles/r37_schema_time.txt; DESIGN.md, Row schema): against
+// no election, 2 rounds take 4 % off the call on parking-citations (19 names cycling through every wave) and 25 % on the users of
+// twitter, and cost nothing on 2^20 distinct names; 4 rounds are the best on twitter but 5 % SLOWER than none on parking, 8 and 24
+// lose everywhere -- a round serialises a probe behind a broadcast, and a wave that holds more distinct names than rounds pays for
+// the rounds and still sends most of its lanes to the table.
+static constexpr u32 SCHEMA_ELECT_ROUNDS = 2;
+struct QSchema {
+    u32 n, mask;          // the members; the table's capacity - 1
+    Arr<u64> idx;         // [n] tape index of the member's value, in document order
+    Arr<u64> parent;      // [n] the row the member belongs to
+    Arr<u64> hash;        // [n] of the name's bytes
+    Arr<u8> cls;          // [n] SJHIP_TYPE_* - 1 of the value
+    Arr<u32> slot;        // [n] the slot the member's name ended in
+    Arr<u32> table;       // [mask + 1] member numbers (empty: GROUP_NONE)
+    Arr<u32> flag;        // [n + 1] 1 at the first member of a name -> exclusive prefix: the name's number
+    Arr<u64> len;         // [n + 1] bytes of a first member's name -> their offset in the dictionary
+    unsigned long long *tiles_f, *tiles_l;  // [tiles] each
+};
+struct SchemaOut {
+    Arr<u64> name_off;   // [names + 1]
+    Arr<u64> first_row;  // [names]
+    Arr<u8> name_data;   // [name bytes]
+};
+// the reference's Type of a value, from its tape tag (TagToType, parsed_json.go), minus one
+__device__ __forceinline__ u32 schema_class(u64 w) {
+    switch ((u32)(w >> 56)) {
+        case '"': return SJHIP_TYPE_STRING - 1;
+        case 'l': return SJHIP_TYPE_INT - 1;
+        case 'u': return SJHIP_TYPE_UINT - 1;
+        case 'd': return SJHIP_TYPE_FLOAT - 1;
+        case 't':
+        case 'f': return SJHIP_TYPE_BOOL - 1;
+        case '{': return SJHIP_TYPE_OBJECT - 1;
+        case '[': return SJHIP_TYPE_ARRAY - 1;
+        default: return SJHIP_TYPE_NULL - 1;  // 'n' (a member's value has no other tag)
+    }
+}
+static constexpr int SCHEMA_STATUS_STEPS = 4;  // 64-parent steps per wave of k_q_schema_status
+__global__ __launch_bounds__(256) void k_q_schema_status(QUnnest u, u32 n, Arr<unsigned long long> hist) {
+    const u32 lane = threadIdx.x & 63u;
+    const u32 base = (blockIdx.x * 4u + (threadIdx.x >> 6)) * (64u * SCHEMA_STATUS_STEPS);
+    unsigned long long mine = 0;
+    for (int k = 0; k < SCHEMA_STATUS_STEPS; k++) {
+        const u32 p = base + (u32)k * 64u + lane;
+        const u32 st = p < n ? (u32)u.status[p] : NONE32;
+#pragma unroll
+        for (u32 s = 0; s <= (u32)SJHIP_COL_RANGE; s++) {
+            const u64 b = __ballot(st == s);
+            if (lane == s) mine += (unsigned long long)__popcll(b);
+        }
+    }
+    if (lane <= (u32)SJHIP_COL_RANGE && mine) atomicAdd(&hist[lane], mine);
+}
+__global__ __launch_bounds__(256) void k_q_schema_keys(QView q, QSchema s) {
+    const u32 j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= s.n) return;
+    const u64 v = s.idx[j];
+    const u64 len = q.tape[v - 1];
+    s.hash[j] = group_hash_bytes(str_bytes(q, q.tape[v - 2], len), len);
+    s.cls[j] = (u8)schema_class(q.tape[v]);
+}
+// k_q_group_insert's probe for member j, whose name is the `len` bytes of the string word kw with hash h: the slot it ended in
+__device__ __forceinline__ u32 schema_probe(const QView &q, const QSchema &s, u32 j, u64 h, u64 kw, u64 len) {
+    u32 at = (u32)h & s.mask;
+    for (u32 step = 0; step <= s.mask; step++, at = (at + 1u) & s.mask) {
+        u32 *const cell = &s.table[at];
+        u32 cur = __hip_atomic_load(cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == GROUP_NONE) {
+            cur = atomicCAS(cell, GROUP_NONE, j);
+            if (cur == GROUP_NONE) break;  // claimed
+        }
+        if (cur == j) break;
+        if (s.hash[cur] != h) continue;
+        const u64 vc = s.idx[cur];
+        if (q.tape[vc - 1] != len || !group_bytes_equal(str_bytes(q, kw, len), str_bytes(q, q.tape[vc - 2], len), len)) continue;
+        if (cur > j) (void)atomicMin(cell, j);
+        break;
+    }
+    return at;
+}
+// E: the election's rounds.  The product instantiates SCHEMA_ELECT_ROUNDS alone; E = 0 is k_q_group_insert's protocol on members, with
+// no election code in it (SJ_EXP builds instantiate it, and a few other counts, for the A/B of tools/schema_time.py).
+template <u32 E>
+__global__ __launch_bounds__(256) void k_q_schema_insert(QView q, QSchema s) {
+    const u32 j = blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    bool pending = j < s.n;
+    u64 h = 0, kw = 0, len = 0;
+    if (pending) {
+        const u64 v = s.idx[j];
+        kw = q.tape[v - 2];
+        len = q.tape[v - 1];
+        h = s.hash[j];
+    }
+    u32 mine = 0;
+#pragma unroll 1
+    for (u32 round = 0; round < E; round++) {
+        const u64 todo = __ballot(pending);
+        if (!todo) break;  // (wave-uniform)
+        const int leader = __ffsll((unsigned long long)todo) - 1;
+        const u64 h_l = wave_bcast(h, leader), len_l = wave_bcast(len, leader), kw_l = wave_bcast(kw, leader);
+        const bool same = pending && h == h_l && len == len_l &&
+                          (lane == leader || group_bytes_equal(str_bytes(q, kw, len), str_bytes(q, kw_l, len), len));
+        u32 at = 0;
+        if (lane == leader) at = schema_probe(q, s, j, h, kw, len);
+        at = wave_bcast(at, leader);
+        if (same) {
+            mine = at;
+            pending = false;
+        }
+    }
+    if (pending) mine = schema_probe(q, s, j, h, kw, len);
+    if (j < s.n) s.slot[j] = mine;
+}
+// (one lane per entry of the n + 1: entry n is 0, the scans leave the totals there)
+__global__ __launch_bounds__(256) void k_q_schema_first(QView q, QSchema s) {
+    const u32 j = blockIdx.x * 256 + threadIdx.x;
+    if (j > s.n) return;
+    const bool first = j < s.n && s.table[s.slot[j]] == j;
+    s.flag[j] = first ? 1u : 0u;
+    s.len[j] = first ? q.tape[s.idx[j] - 1] : 0ull;
+}
+__global__ __launch_bounds__(QT) void k_q_schema_tile_sums(QSchema s, u32 m) {
+    tile_sums(arr_at(s.flag, 0, m), m, s.tiles_f);
+    tile_sums(arr_at(s.len, 0, m), m, s.tiles_l);
+}
+__global__ __launch_bounds__(QT) void k_q_schema_tile_apply(QSchema s, u32 m) {
+    u32 *const flag = arr_at(s.flag, 0, m);
+    u64 *const len = arr_at(s.len, 0, m);
+    tile_apply(flag, flag, m, s.tiles_f);
+    tile_apply(len, len, m, s.tiles_l);
+}
+__global__ __launch_bounds__(256) void k_q_schema_emit(QView q, QSchema s, SchemaOut o, u32 names, Arr<u32> sort_keys) {
+    const u32 j = blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    u64 off = 0, len = 0, w = 0;
+    bool wide = false;
+    if (j < s.n) {
+        const u32 first = s.table[s.slot[j]];
+        const u32 code = s.flag[first];
+        sort_keys[j] = code * (u32)SJHIP_SCHEMA_TYPES + s.cls[j];
+        if (first == j) {
+            off = s.len[j];
+            len = s.len[j + 1u] - off;
+            o.name_off[code] = off;
+            o.first_row[code] = s.parent[j];
+            if (len) {
+                w = q.tape[s.idx[j] - 2];
+                wide = !(len <= COL_SHORT);  // (a short name by its lane, a long one by the wave, below)
+                if (!wide) copy_bytes(arr_at(o.name_data, off, len), str_bytes(q, w, len), len, 0, 1);
+            }
+        }
+        if (j == 0) o.name_off[names] = s.len[s.n];
+    }
+    wave_copy_strings(q, o.name_data, wide, off, len, w, lane);
+}
+// keys: the n sorted keys.  lo[k] = where the run of key k begins, hi[k] = where it ends (both stay 0 for a key that does not occur)
+__global__ __launch_bounds__(256) void k_q_schema_bounds(Arr<const u32> keys, u32 n, Arr<u64> lo, Arr<u64> hi) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const u32 k = keys[i];
+    if (i == 0 || keys[i - 1] != k) lo[k] = i;
+    if (i + 1u == n || keys[i + 1] != k) hi[k] = (u64)i + 1u;
+}
+// counts: the run ends on entry, the run lengths on exit
+__global__ __launch_bounds__(256) void k_q_schema_counts(Arr<const u64> lo, u32 m, Arr<u64> counts) {
+    const u32 k = blockIdx.x * 256 + threadIdx.x;
+    if (k < m) counts[k] = counts[k] - lo[k];
 }
 
 
@@ -3712,17 +3918,40 @@ static size_t unnest_layout(Carve c, const sjhip_ctx *part, uint32_t n, u32 dept
     w->ok = c.take<u8>(recs);
     return c.used;
 }
-// members: sjhip_unnest_members -- the parents' targets are objects and the tile passes are k_q_members_tile, whose counts are
+// The walk of both calls on one part, in two halves, with nothing published -- sjhip_row_schema runs the same walk into its work
+// arenas.  members: sjhip_unnest_members -- the parents' targets are objects and the tile passes are k_q_members_tile, whose counts are
 // starts, two to a row; everything else is the same for both calls.
+// unnest_count_enqueue: the parents' ranges, the depth prefix and the starts counted, on the work arrays `w` (unnest_layout); the
+// count lies in w.totals[1] behind it.
+static int unnest_count_enqueue(sjhip_ctx *ctx, sjhip_ctx *part, const QView &q, uint32_t n, const QPath &pth, bool members, const UnnestWork &w) {
+    void (*const k_parents)(QView, QPath, QUnnest) = members ? k_q_members_parents : k_q_unnest_parents;
+    void (*const k_count)(QView, QUnnest, Arr<u64>, Arr<u64>) = members ? k_q_members_tile<1> : k_q_unnest_tile<1>;
+    const dim3 tiles(RowsBuild::tape_tiles(part)), block(TW_THREADS), one(1), wide(1024);
+    unsigned long long *const none = nullptr;
+    const Arr<u64> no_index = SJ_ARR((u64 *)nullptr, 0, A_ROWS), no_parent = SJ_ARR((u64 *)nullptr, 0, A_UNNEST_PARENT);
+    HIPCHK(hipMemsetAsync(w.totals, 0, 256, part->stream), "unnest totals memset");
+    hipLaunchKernelGGL(k_parents, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, pth, w.u);
+    hipLaunchKernelGGL(k_q_rows_tile<0>, tiles, block, 0, part->stream, q, w.u.t, 0u, no_index);
+    hipLaunchKernelGGL(k_q_rows_last, tiles, block, 0, part->stream, q, w.u.t);  // (these three end at once unless a tile asked)
+    hipLaunchKernelGGL(k_q_rows_scan_last, one, wide, 0, part->stream, w.u.t, tiles.x);
+    hipLaunchKernelGGL(k_q_rows_tile<0>, tiles, block, 0, part->stream, q, w.u.t, 1u, no_index);
+    hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, part->stream, w.u.t.depth, none, none, tiles.x, w.totals);
+    hipLaunchKernelGGL(k_count, tiles, block, 0, part->stream, q, w.u, no_index, no_parent);
+    hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, part->stream, none, w.u.t.cnt, none, tiles.x, w.totals);  // the rows: totals[1]
+    HIPCHK(hipGetLastError(), "unnest launch");
+    return SJHIP_OK;
+}
+// unnest_write_enqueue: the `got` new rows (members: the values) written, each with its parent
+static void unnest_write_enqueue(sjhip_ctx *part, const QView &q, bool members, const UnnestWork &w, Arr<u64> index, Arr<u64> parent) {
+    void (*const k_write)(QView, QUnnest, Arr<u64>, Arr<u64>) = members ? k_q_members_tile<2> : k_q_unnest_tile<2>;
+    hipLaunchKernelGGL(k_write, dim3(RowsBuild::tape_tiles(part)), dim3(TW_THREADS), 0, part->stream, q, w.u, index, parent);
+}
 static int unnest_build(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, const uint8_t *keys, size_t klen, const QPath &pth, bool members,
                         size_t *records, size_t *parents, size_t *rows) {
     const bool sel = selected(ctx, true);
     const u32 depth = (sel ? ctx->res.rows.sizes().depth : 0u) + pth.n + 1u;  // of the new rows below their record's root value
     std::vector<UnnestWork> work(parts.size());
     std::vector<size_t> found(parts.size(), 0);
-    void (*const k_parents)(QView, QPath, QUnnest) = members ? k_q_members_parents : k_q_unnest_parents;
-    void (*const k_count)(QView, QUnnest, Arr<u64>, Arr<u64>) = members ? k_q_members_tile<1> : k_q_unnest_tile<1>;
-    void (*const k_write)(QView, QUnnest, Arr<u64>, Arr<u64>) = members ? k_q_members_tile<2> : k_q_unnest_tile<2>;
     int rc = query_over_parts(ctx, parts, keys, klen, &NO_VALUE, 0, true, "unnest sync",
         [&](const sjhip_ctx *part, uint32_t n) {
             UnnestWork w;
@@ -3731,19 +3960,8 @@ static int unnest_build(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, c
         [&](size_t k, sjhip_ctx *part, const QView &q, uint32_t n) -> int {
             UnnestWork &w = work[k];
             (void)unnest_layout(Carve(part->d_kat.p), part, n, depth, &w);
-            const dim3 tiles(RowsBuild::tape_tiles(part)), block(TW_THREADS), one(1), wide(1024);
-            unsigned long long *const none = nullptr;
-            const Arr<u64> no_index = SJ_ARR((u64 *)nullptr, 0, A_ROWS), no_parent = SJ_ARR((u64 *)nullptr, 0, A_UNNEST_PARENT);
-            HIPCHK(hipMemsetAsync(w.totals, 0, 256, part->stream), "unnest totals memset");
-            hipLaunchKernelGGL(k_parents, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, pth, w.u);
-            hipLaunchKernelGGL(k_q_rows_tile<0>, tiles, block, 0, part->stream, q, w.u.t, 0u, no_index);
-            hipLaunchKernelGGL(k_q_rows_last, tiles, block, 0, part->stream, q, w.u.t);  // (these three end at once unless a tile asked)
-            hipLaunchKernelGGL(k_q_rows_scan_last, one, wide, 0, part->stream, w.u.t, tiles.x);
-            hipLaunchKernelGGL(k_q_rows_tile<0>, tiles, block, 0, part->stream, q, w.u.t, 1u, no_index);
-            hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, part->stream, w.u.t.depth, none, none, tiles.x, w.totals);
-            hipLaunchKernelGGL(k_count, tiles, block, 0, part->stream, q, w.u, no_index, no_parent);
-            hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, part->stream, none, w.u.t.cnt, none, tiles.x, w.totals);  // the rows: totals[1]
-            HIPCHK(hipGetLastError(), "unnest launch");
+            const int rc = unnest_count_enqueue(ctx, part, q, n, pth, members, w);
+            if (rc) return rc;
             HIPCHK(hipMemcpyAsync(part->h_scratch + 512, w.totals + 1, 8, hipMemcpyDeviceToHost, part->stream), "D2H unnested row count");
             return SJHIP_OK;
         },
@@ -3760,9 +3978,7 @@ static int unnest_build(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, c
             int rc = reserve_layout(part, part->d_parents, [&](Carve cv) { return parents_layout(cv, n, got, &po); });
             if (rc) return rc;
             const Arr<const u64> index = SJ_ARR((const u64 *)po.new_index, got, A_ROWS);
-            if (got)
-                hipLaunchKernelGGL(k_write, dim3(RowsBuild::tape_tiles(part)), dim3(TW_THREADS), 0, part->stream, q, w.u,
-                                   SJ_ARR(po.new_index, got, A_ROWS), SJ_ARR(po.parent, got, A_UNNEST_PARENT));
+            if (got) unnest_write_enqueue(part, q, members, w, SJ_ARR(po.new_index, got, A_ROWS), SJ_ARR(po.parent, got, A_UNNEST_PARENT));
             // the records: their new offsets, and the status bytes they had (without a selection: OK)
             QRows hand = w.u.t;
             hand.status = w.ok;
@@ -4384,6 +4600,195 @@ int sjhip_fetch_group_aggregates_at(sjhip_ctx *ctx, uint32_t val, uint64_t *coun
         return SJHIP_ERR_ARG;
     }
     return fetch_aggregates(ctx, z, val, {count, not_ok, sum, sum_hi, min, max});
+}
+
+// ---- row schema ----------------------------------------------------------------------------------------------------------------------
+// sjhip_row_schema works on the whole result of one context, like the grouping (a sharded one is refused: the dictionaries would
+// have to be joined), and reads the selection in force without replacing it.  Two halves with a host round trip each: the member
+// walk's count pass on the work arrays of the unnest in d_kat, with the parents' statuses counted beside it -> the members; then,
+// in d_schema_work, laid out for that many members, the walk's write pass, the keys, the dictionary and the scans -> the names
+// and their bytes; then the product in d_schema (schema_layout), the emit, the sort and the counts, and one wait at the end.
+struct SchemaWork {
+    unsigned long long *totals;  // [0] names, [1] the bytes of the dictionary
+    QSchema s;
+    SortWork<u32> sort;
+};
+static size_t schema_work_layout(Carve c, uint32_t m, SchemaWork *w) {
+    const u64 cap = group_table_capacity(m);
+    const u32 tiles = tiles_of(m);
+    QSchema &s = w->s;
+    w->totals = c.take<unsigned long long>(32);
+    s.n = m, s.mask = (u32)(cap - 1);
+    u64 *const idx = c.take<u64>(m), *const parent = c.take<u64>(m), *const hash = c.take<u64>(m);
+    u8 *const cls = c.take<u8>(m);
+    u32 *const slot = c.take<u32>(m), *const table = c.take<u32>(cap), *const flag = c.take<u32>((size_t)m + 1);
+    u64 *const len = c.take<u64>((size_t)m + 1);
+    s.idx = SJ_ARR(idx, m, A_SCHEMA_MEMBER);
+    s.parent = SJ_ARR(parent, m, A_SCHEMA_PARENT);
+    s.hash = SJ_ARR(hash, m, A_SCHEMA_WORK);
+    s.cls = SJ_ARR(cls, m, A_SCHEMA_WORK);
+    s.slot = SJ_ARR(slot, m, A_SCHEMA_WORK);
+    s.table = SJ_ARR(table, cap, A_SCHEMA_TABLE);
+    s.flag = SJ_ARR(flag, (size_t)m + 1, A_SCHEMA_WORK);
+    s.len = SJ_ARR(len, (size_t)m + 1, A_SCHEMA_WORK);
+    s.tiles_f = c.take<unsigned long long>(tiles);
+    s.tiles_l = c.take<unsigned long long>(tiles);
+    sort_carve(c, m, &w->sort);
+    return c.used;
+}
+// The schema in d_schema: what the fetch returns, and behind it the run bounds on their way into the counts.
+struct SchemaArrays { u64 *name_off, *first_row, *counts, *lo; u8 *name_data; };
+static size_t schema_layout(Carve c, const ResultState::Schema &z, SchemaArrays *o) {
+    o->name_off = c.take<u64>(z.names + 1);
+    o->first_row = c.take<u64>(z.names);
+    o->counts = c.take<u64>(z.names * SJHIP_SCHEMA_TYPES);
+    o->name_data = c.take<u8>(z.name_bytes);
+    o->lo = c.take<u64>(z.names * SJHIP_SCHEMA_TYPES);  // (not part of what is fetched)
+    return c.used;
+}
+// the insert of the product; SJ_EXP builds only (A/B timing; the results stay correct): SJHIP_SCHEMA_ELECT=E picks the
+// instantiation with E election rounds among 0 (none: every lane probes for itself), 1, 2, 4, 8, 24
+typedef void (*SchemaInsert)(QView, QSchema);
+static SchemaInsert schema_insert_kernel() {
+#if defined(SJ_EXP)
+    const char *e = getenv("SJHIP_SCHEMA_ELECT");
+    switch (e ? strtoul(e, nullptr, 0) : (unsigned long)SCHEMA_ELECT_ROUNDS) {
+        case 0: return k_q_schema_insert<0>;
+        case 1: return k_q_schema_insert<1>;
+        case 2: return k_q_schema_insert<2>;
+        case 4: return k_q_schema_insert<4>;
+        case 8: return k_q_schema_insert<8>;
+        case 24: return k_q_schema_insert<24>;
+    }
+#endif
+    return k_q_schema_insert<SCHEMA_ELECT_ROUNDS>;
+}
+static int schema_build(sjhip_ctx *ctx, const WholePath &k, uint32_t n, size_t *rows, uint64_t *status, uint64_t *members, size_t *names,
+                        size_t *name_bytes) {
+    const u32 depth = (selected(ctx, true) ? ctx->res.rows.sizes().depth : 0u) + k.pth.n + 1u;  // of the members' values
+    ResultState::Schema z;
+    z.rows = n;
+    *rows = n, *members = 0, *names = *name_bytes = 0;
+    for (int s = 0; s <= SJHIP_COL_RANGE; s++) status[s] = 0;
+    HIPCHK(hipSetDevice(ctx->device), "hipSetDevice");
+    if (n == 0) {
+        ctx->res.publish_schema(z);
+        return published(ctx, ctx->res.schema.exists());
+    }
+    hipStream_t st = ctx->stream;
+    const dim3 b256(256), one(1), wide(1024);
+    unsigned long long *const none = nullptr;
+    // ---- the first half: the members counted, the parents' statuses counted ----
+    UnnestWork uw;
+    unsigned long long *hist = nullptr;
+    int rc = reserve_layout(ctx, ctx->d_kat, [&](Carve c) {
+        c.used = unnest_layout(c, ctx, n, depth, &uw);
+        hist = c.take<unsigned long long>(32);
+        return c.used;
+    });
+    if (rc) return rc;
+    rc = unnest_count_enqueue(ctx, ctx, k.q, n, k.pth, true, uw);
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(hist, 0, 256, st), "schema status memset");
+    hipLaunchKernelGGL(k_q_schema_status, dim3((n + 256u * SCHEMA_STATUS_STEPS - 1) / (256u * SCHEMA_STATUS_STEPS)), b256, 0, st, uw.u, n,
+                       SJ_ARR(hist, 32, A_SCHEMA_HIST));
+    HIPCHK(hipGetLastError(), "schema status launch");
+    unsigned long long *const h = (unsigned long long *)(ctx->h_scratch + 512);
+    HIPCHK(hipMemcpyAsync(h, uw.totals + 1, 8, hipMemcpyDeviceToHost, st), "D2H member count");
+    HIPCHK(hipMemcpyAsync(h + 1, hist, 8 * (SJHIP_COL_RANGE + 1), hipMemcpyDeviceToHost, st), "D2H schema statuses");
+    HIPCHK(hipStreamSynchronize(st), "schema sync");
+    rc = query_bounds_check(ctx);
+    if (rc) return rc;
+    const u64 m64 = h[0] / 2;  // (the starts: a key and a value for every member)
+    for (int s = 0; s <= SJHIP_COL_RANGE; s++) status[s] = h[1 + s];
+    if (m64 > (1ull << 28)) {
+        ctx_set_error(ctx, "sjhip_row_schema: %llu members (at most 2^28)", (unsigned long long)m64);
+        return SJHIP_ERR_TOOBIG;
+    }
+    const u32 m = (u32)m64;
+    z.members = m;
+    *members = m;
+    if (m == 0) {
+        ctx->res.publish_schema(z);
+        return published(ctx, ctx->res.schema.exists());
+    }
+    // ---- the second half: the members, their keys, the dictionary, the names numbered ----
+    SchemaWork w;
+    rc = reserve_layout(ctx, ctx->d_schema_work, [&](Carve c) { return schema_work_layout(c, m, &w); });
+    if (rc) return rc;
+    const dim3 per_member((m + 255) / 256), per_entry((m + 1u + 255) / 256);
+    const u32 tiles = tiles_of(m);
+    unnest_write_enqueue(ctx, k.q, true, uw, w.s.idx, w.s.parent);
+    HIPCHK(hipMemsetAsync(w.totals, 0, 256, st), "schema totals memset");
+    HIPCHK(hipMemsetAsync(arr_raw(w.s.table), 0xff, ((size_t)w.s.mask + 1) * 4, st), "schema table memset");
+    hipLaunchKernelGGL(k_q_schema_keys, per_member, b256, 0, st, k.q, w.s);
+    hipLaunchKernelGGL(schema_insert_kernel(), per_member, b256, 0, st, k.q, w.s);
+    hipLaunchKernelGGL(k_q_schema_first, per_entry, b256, 0, st, k.q, w.s);
+    hipLaunchKernelGGL(k_q_schema_tile_sums, dim3(tiles), dim3(QT), 0, st, w.s, m + 1u);
+    hipLaunchKernelGGL(k_tw_scan_sums, one, wide, 0, st, w.s.tiles_f, w.s.tiles_l, none, tiles, w.totals);
+    hipLaunchKernelGGL(k_q_schema_tile_apply, dim3(tiles), dim3(QT), 0, st, w.s, m + 1u);
+    HIPCHK(hipGetLastError(), "schema launch");
+    HIPCHK(hipMemcpyAsync(h, w.totals, 16, hipMemcpyDeviceToHost, st), "D2H schema totals");
+    HIPCHK(hipStreamSynchronize(st), "schema dictionary sync");
+    rc = query_bounds_check(ctx);
+    if (rc) return rc;
+    const u32 N = (u32)h[0], keys_n = N * (u32)SJHIP_SCHEMA_TYPES;
+    z.names = N, z.name_bytes = (size_t)h[1];
+    // ---- the product: the dictionary, the first rows, the counts ----
+    SchemaArrays a;
+    rc = reserve_layout(ctx, ctx->d_schema, [&](Carve c) { return schema_layout(c, z, &a); });
+    if (rc) return rc;
+    SchemaOut o;
+    o.name_off = SJ_ARR(a.name_off, (size_t)N + 1, A_SCHEMA_OUT);
+    o.first_row = SJ_ARR(a.first_row, N, A_SCHEMA_OUT);
+    o.name_data = SJ_ARR(a.name_data, z.name_bytes, A_SCHEMA_NAMES);
+    HIPCHK(hipMemsetAsync(a.counts, 0, (size_t)keys_n * 8, st), "schema counts memset");
+    HIPCHK(hipMemsetAsync(a.lo, 0, (size_t)keys_n * 8, st), "schema bounds memset");
+    u32 *const first_keys = w.sort.keys[0];
+    hipLaunchKernelGGL(k_q_schema_emit, per_member, b256, 0, st, k.q, w.s, o, N, SJ_ARR(first_keys, m, A_SORT));
+    const int at = sort_enqueue(st, m, m, group_pass_mask((u64)keys_n - 1u), false, w.sort);
+    const u32 *const skeys = w.sort.keys[at];
+    hipLaunchKernelGGL(k_q_schema_bounds, per_member, b256, 0, st, SJ_ARR(skeys, m, A_SORT), m, SJ_ARR(a.lo, keys_n, A_SCHEMA_BOUNDS),
+                       SJ_ARR(a.counts, keys_n, A_SCHEMA_OUT));
+    hipLaunchKernelGGL(k_q_schema_counts, dim3((keys_n + 255) / 256), b256, 0, st, SJ_ARR((const u64 *)a.lo, keys_n, A_SCHEMA_BOUNDS), keys_n,
+                       SJ_ARR(a.counts, keys_n, A_SCHEMA_OUT));
+    HIPCHK(hipGetLastError(), "schema emit launch");
+    HIPCHK(hipStreamSynchronize(st), "schema build sync");
+    rc = query_bounds_check(ctx);
+    if (rc) return rc;
+    *names = z.names, *name_bytes = z.name_bytes;
+    ctx->res.publish_schema(z);
+    return published(ctx, ctx->res.schema.exists());
+}
+int sjhip_row_schema(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, size_t *rows, uint64_t status[6],
+                     uint64_t *members, size_t *names, size_t *name_bytes) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!rows || !status || !members || !names || !name_bytes) {
+        ctx_set_error(ctx, "sjhip_row_schema: a null size pointer");
+        return SJHIP_ERR_ARG;
+    }
+    WholePath k = {keys, key_lens, n_keys};
+    uint32_t n = 0;
+    const int rc = whole_entry(ctx, "sjhip_row_schema", "the dictionaries of shards are not joined", &k, 1, &n);
+    if (rc) return rc;
+    // ---- nothing was touched up to here; from here on the last schema is gone (the selection and every other product stay) ----
+    ctx->res.drop_schema();
+    return schema_build(ctx, k, n, rows, status, members, names, name_bytes);
+}
+int sjhip_fetch_row_schema(sjhip_ctx *ctx, uint64_t *name_offsets, uint8_t *name_data, uint64_t *first_row, uint64_t *counts) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!ctx->res.schema.exists())
+        return no_product(ctx, "no row schema on the device (sjhip_fetch_row_schema follows sjhip_row_schema, with no parse in between)");
+    const ResultState::Schema &z = ctx->res.schema.sizes();
+    if (z.names == 0) {  // (nothing was launched for the product, no arena was written)
+        if (name_offsets) name_offsets[0] = 0;
+        return SJHIP_OK;
+    }
+    SchemaArrays a;
+    (void)schema_layout(Carve(ctx->d_schema.p), z, &a);
+    const FetchCopy copies[] = {{name_offsets, a.name_off, (z.names + 1) * 8}, {name_data, a.name_data, z.name_bytes},
+                                {first_row, a.first_row, z.names * 8}, {counts, a.counts, z.names * SJHIP_SCHEMA_TYPES * 8}};
+    return fetch_copies(ctx, copies, 4, "D2H row schema", "row schema fetch sync");
 }
 
 // ---- order ---------------------------------------------------------------------------------------------------------------------------

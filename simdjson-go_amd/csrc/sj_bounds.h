@@ -67,7 +67,12 @@ enum ArrId : uint32_t {
     A_BATCH_SRC, A_BATCH_DOCS, A_BATCH_DST,
     // the projected rows (marshal.hip, sjhip_marshal_rows_paths): the tape index or path status of every cell, column-major / the
     // text bytes of every row and their prefix / the name pieces / where each begins (text and row offsets: A_MROWS_TEXT, _OUT_OFF)
-    A_MPROJ_IDX, A_MPROJ_OFF, A_MPROJ_NAMES, A_MPROJ_NAME_OFF
+    A_MPROJ_IDX, A_MPROJ_OFF, A_MPROJ_NAMES, A_MPROJ_NAME_OFF,
+    // the row schema (query.hip, sjhip_row_schema): the value index of every member (written by the member walk) / its parent row /
+    // the per-member work arrays (hash, type class, slot, first-occurrence flag, name length) / the table of member numbers / the
+    // status histogram / the run bounds of the sorted (name, type) keys / the arrays of the product (name offsets, first rows,
+    // counts) / the names' bytes.  Its sort is A_SORT
+    A_SCHEMA_MEMBER, A_SCHEMA_PARENT, A_SCHEMA_WORK, A_SCHEMA_TABLE, A_SCHEMA_HIST, A_SCHEMA_BOUNDS, A_SCHEMA_OUT, A_SCHEMA_NAMES
 };
 
 #if defined(SJ_DEBUG_BOUNDS)

@@ -49,6 +49,10 @@ struct sjhip_ctx {
     // the row parents of the last sjhip_unnest_rows (query.hip): parent offsets, parent statuses, the parent of every new row --
     // and, behind them, the new row index on its way into d_rows (the old one is read while it is written)
     sj::DevBuf d_parents;
+    // the row schema of the last sjhip_row_schema (query.hip): name offsets, first rows, counts per name and type, the names' bytes
+    // (d_schema), and the work arrays of its second half, sized by the members the first half counted (d_schema_work: d_kat holds
+    // the member walk's arrays, which that half still reads, and a second reservation would move it)
+    sj::DevBuf d_schema, d_schema_work;
     unsigned ws_clean_gen = 0;         // d_ws.gen of the allocation that has been zeroed for stage 1 (0: none; stage1_enqueue)
     sj::S1Ws s1ws;                     // ... and its launch count (sj_device.h: a launch cleans up for the next one)
     // queued stage-1 messages that wait for their launch (api.hip: the queue runs up to S1_GROUP_MAX messages of one mode as one

@@ -14,7 +14,9 @@
 //     sjhip_group_path) is the fifth use: built over the rows in force, independent of everything else once it exists.  The
 //     order (d_order: sjhip_order_path) is the sixth: the rank order of the rows the call kept, materialised like the grouping.
 //     The row parents (d_parents: sjhip_unnest_rows) are the seventh: which row of the selection the call found every row of the
-//     selection it left came from, materialised like the other two.
+//     selection it left came from, materialised like the other two.  The row schema (d_schema: sjhip_row_schema) is the eighth:
+//     the distinct member names of the rows in force and their counts per value type, materialised; it reads the selection and
+//     leaves it, and every other product, as they are.
 // The rule: a parse call, successful or not, drops the previous result and everything derived from it (begin_parse); so do
 // sjhip_deserialize, sjhip_ctx_trim and the stage-1-only calls (drop_result).  A product exists from its publish to the next
 // transition that drops it; a product is only published on a resident result, and a result of no tape words is no result.
@@ -52,6 +54,8 @@ public:
     };
     // the order (sjhip_order_path): the rows it kept -- its arrays have that many entries -- and the kind of their keys
     struct Order { size_t rows = 0; int kind = 0; };
+    // the row schema (sjhip_row_schema): the rows it ran over, the members it met, its distinct names and the bytes of their dictionary
+    struct Schema { size_t rows = 0, members = 0, names = 0, name_bytes = 0; };
     struct Table {  // what a fetch of one column needs: its kind, and the text bytes of a string column (0 for the other kinds)
         size_t records = 0;
         uint32_t n_cols = 0;
@@ -145,7 +149,11 @@ public:
     // the row parents (sjhip_unnest_rows, d_parents): materialised; parent numbers are those of the selection the call found, row
     // numbers those of the selection it left
     Product<Parents> parents;
-    void drop_products() { column.begin(), list.begin(), table.begin(), rows.begin(), groups.begin(), order.begin(), parents.begin(); }  // (a stage-1-only call on a sharded result: api.hip)
+    // the row schema (sjhip_row_schema, d_schema): materialised; first_row counts in the selection the call ran under
+    Product<Schema> schema;
+    void publish_schema(const Schema &z) { (void)publish(&ResultState::schema, z); }  // (what sjhip_row_schema ends with)
+    void drop_schema() { schema.begin(); }  // (... and what it begins with behind its argument checks)
+    void drop_products() { column.begin(), list.begin(), table.begin(), rows.begin(), groups.begin(), order.begin(), parents.begin(), schema.begin(); }  // (a stage-1-only call on a sharded result: api.hip)
     template <typename S>
     bool publish(Product<S> ResultState::*product, const S &sizes) {  // publish(&ResultState::column, {records, bytes})
         if (!resident() && !sharded()) return false;

@@ -104,6 +104,8 @@ SYMBOLS = {
     "sjhip_extract_row_names": (C.c_int, [C.c_void_p, szp, szp]),
     "sjhip_where_row_names": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, szp, szp]),
     "sjhip_fetch_row_parents": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sjhip_row_schema": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32, szp, u64p, u64p, szp, szp]),
+    "sjhip_fetch_row_schema": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sjhip_filter_rows": (C.c_int, [C.c_void_p, u64p, u64p, szp, szp]),
     "sjhip_serialize": (C.c_int, [C.c_void_p, szp, szp, szp, szp]),
     "sjhip_serialize_ex": (C.c_int, [C.c_void_p, C.c_uint32, szp, szp, szp, szp]),

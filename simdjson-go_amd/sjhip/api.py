@@ -29,6 +29,9 @@ class ParseError(Exception):
         self.code = code
 
 
+TYPE_NULL, TYPE_STRING, TYPE_INT, TYPE_UINT, TYPE_FLOAT, TYPE_BOOL, TYPE_OBJECT, TYPE_ARRAY = range(1, 9)  # SJHIP_TYPE_* (row_schema)
+
+
 def supported() -> bool:
     return bool(_lib.lib().sjhip_supported())
 
@@ -681,6 +684,37 @@ class Context:
                                                      C.byref(nw)))
         return nr.value, nw.value
 
+    # ---- row schema (include/sjhip.h: sjhip_row_schema / sjhip_fetch_row_schema) -------------------------------------------------
+    TYPE_NULL, TYPE_STRING, TYPE_INT, TYPE_UINT, TYPE_FLOAT, TYPE_BOOL, TYPE_OBJECT, TYPE_ARRAY = range(1, 9)  # SJHIP_TYPE_*
+    SCHEMA_TYPES = 8  # SJHIP_SCHEMA_TYPES
+
+    def row_schema(self, path=(), fetch=True):
+        """Iter.FindElement(path...), Iter.Object on every ROW of the selection in force (without one: on every record's root value)
+        and the direct members of those objects counted by (unescaped name, type of the value); the selection and every other
+        product stay as they are.  An empty path: the row's own value is the object.
+        -> Schema: rows, status (uint64 array of 6: the rows per COL_* status), members, n_names, name_bytes and -- unless fetch=False,
+        when the schema stays on the device for fetch_row_schema -- names (a list of bytes, in first-occurrence order), first_row
+        (uint64 array: the first row that has the name) and counts (uint64 array [names, 8]: column TYPE_x - 1 counts the members
+        of that name whose value has type x)"""
+        blob, lens, n = self._keys(path)
+        status = (C.c_uint64 * 6)()
+        nr, nn, nb, nm = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_uint64(0)
+        self._check(_lib.lib().sjhip_row_schema(self._h, blob if n else None, lens if n else None, n, C.byref(nr), status, C.byref(nm),
+                                                C.byref(nn), C.byref(nb)))
+        s = Schema(nr.value, np.array(list(status), dtype=np.uint64), nm.value, nn.value, nb.value)
+        return self.fetch_row_schema(s) if fetch else s
+
+    def fetch_row_schema(self, s):
+        """the arrays of the last row_schema (s: what it returned with fetch=False) -> s, filled"""
+        off, data = np.empty(s.n_names + 1, dtype=np.uint64), np.empty(max(s.name_bytes, 1), dtype=np.uint8)
+        s.first_row = np.empty(s.n_names, dtype=np.uint64)
+        s.counts = np.empty((s.n_names, self.SCHEMA_TYPES), dtype=np.uint64)
+        ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+        self._check(_lib.lib().sjhip_fetch_row_schema(self._h, off.ctypes.data, data.ctypes.data, ptr(s.first_row), ptr(s.counts)))
+        raw = data.tobytes()
+        s.name_offsets, s.names = off, [raw[int(a):int(b)] for a, b in zip(off[:-1], off[1:])]
+        return s
+
     # ---- order (include/sjhip.h: sjhip_order_path / sjhip_fetch_order) -----------------------------------------------------------
     ORDER_DESC = 1
     ORDER_SORT_TILE = 1024  # rows per tile of the device's sort by key (csrc/sj_sort.h): the largest tile of the ordering's kernels
@@ -890,6 +924,18 @@ class Groups:
 
     def __repr__(self):
         return f"Groups(rows={self.rows}, groups={self.groups}, key_bytes={self.key_bytes})"
+
+
+class Schema:
+    """what Context.row_schema returns: rows, status, members, n_names and name_bytes, and after the fetch names, name_offsets,
+    first_row and counts (see row_schema)"""
+
+    def __init__(self, rows, status, members, n_names, name_bytes):
+        self.rows, self.status, self.members, self.n_names, self.name_bytes = rows, status, members, n_names, name_bytes
+        self.names = self.name_offsets = self.first_row = self.counts = None
+
+    def __repr__(self):
+        return f"Schema(rows={self.rows}, members={self.members}, names={self.n_names}, name_bytes={self.name_bytes})"
 
 
 class Order:
