@@ -530,6 +530,44 @@ int sjhip_where_paths(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_l
 int sjhip_count_where_paths(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, const uint32_t *path_lens,
                             const int *ops, const void *values, const uint32_t *value_lens, uint32_t n_preds,
                             const uint8_t *program, uint32_t program_len, uint64_t *count);
+/* Row predicates by MEMBERSHIP: keep the rows whose key at `path` is one of a set of values -- the result of one query narrowing
+ * another ("the tickets whose Make is one of the 200 makes sjhip_fetch_groups just returned", "the statuses whose user.id is in
+ * this list of 50 000 ids", and with SJHIP_WHERE_NOT "the plugins whose name is not in the installed set"): a semi-join, and an
+ * anti-join, whose cost per row does not depend on the size of the set.
+ *   the set        kind = SJHIP_COL_STRING: value_offsets[n_values + 1] and `values` as bytes end to end -- Arrow's large-string layout,
+ *                  exactly what sjhip_fetch_groups, sjhip_fetch_group_keys and sjhip_fetch_path_strings hand out; value_offsets[0] == 0
+ *                  and the offsets never decrease.  kind = SJHIP_COL_INT: `values` is int64_t[n_values]; SJHIP_COL_UINT:
+ *                  uint64_t[n_values]; value_offsets is ignored for both and may be NULL.  Every other kind (FLOAT, BOOL, STRING_CVT,
+ *                  unknown) is SJHIP_ERR_ARG and sjhip_last_error names the kind.  Duplicates are legal and change nothing.
+ *                  n_values == 0 is legal: no row matches, and all three pointers may be NULL.
+ *   the predicate  a row matches iff the set holds a value s for which sjhip_where_path on the same path with SJHIP_OP_EQ_STRING /
+ *                  EQ_INT / EQ_UINT and s, flags 0, would keep it: a string is compared by its unescaped bytes, with and without
+ *                  SJHIP_FLAG_COPY_STRINGS; under INT the elements 1, 1.0 and 1.9 all match 1; an element that is missing, null, of
+ *                  the wrong type or out of range matches nothing.  flags: SJHIP_WHERE_NOT keeps exactly the rows the same call
+ *                  without it drops, the rows without a usable key included; any other bit is SJHIP_ERR_ARG.  n_keys == 0: the row's
+ *                  own value.  Paths have the limits of sjhip_find_path.
+ *   sjhip_where_path_in        narrows what sjhip_where_path narrows, as it narrows it: with a selection the records keep their
+ *                  status bytes and the matching rows among those they owned; without one a selection is created, one row per
+ *                  matching record; *records and *rows as there; it composes with every earlier and later where / order / unnest
+ *                  call; keeping no rows is legal; the other products survive it.
+ *   sjhip_count_where_path_in  *count = *rows of that call; nothing is touched.
+ * SJHIP_ERR_ARG, with sjhip_last_error naming the reason, and nothing touched -- all checked on the host before anything is
+ * uploaded or launched, the number of values before any of them is read: no result on the device, a bad path, a bad kind, unknown
+ * flag bits, n_values > SJHIP_WHERE_IN_MAX_VALUES, a NULL `values` or `value_offsets` where one is needed, value_offsets[0] != 0 or an
+ * offset smaller than the one in front (the index is named), a string value longer than the 1024 bytes EQ_STRING allows (the index
+ * is named).  A call that fails later (SJHIP_ERR_HIP) gives the selection up, as sjhip_where_path does.  On a sharded ND result
+ * every shard narrows its own rows (each builds the table for itself) and the fetch joins them.
+ * The uploaded values, their hashes and the table over them -- the grouping's hash and open-addressing table, at most half full --
+ * are working data of the call in a device arena of their own (sjhip_ctx_device_bytes counts it, sjhip_ctx_trim frees it): nothing
+ * of them can be fetched and nothing refers to them afterwards.  The cost is sjhip_where_path's, plus the upload of the set and
+ * one lane per value to build the table. */
+#define SJHIP_WHERE_IN_MAX_VALUES (1u << 24)
+int sjhip_where_path_in(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int kind,
+                        const uint64_t *value_offsets, const void *values, size_t n_values, uint32_t flags,
+                        size_t *records, size_t *rows);
+int sjhip_count_where_path_in(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int kind,
+                              const uint64_t *value_offsets, const void *values, size_t n_values, uint32_t flags,
+                              uint64_t *count);
 /* Order rows ("order by ... limit k"): rank the rows of the selection in force (without one: the root value of every record) by a
  * numeric key at a path and keep the first `limit` of them -- "the 10 most retweeted statuses" without the column, the host sort and
  * the rows that are thrown away crossing PCIe.

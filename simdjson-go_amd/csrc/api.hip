@@ -99,7 +99,7 @@ sjhip_ctx *sjhip_ctx_create(int device) {
     {&(ctx)->d_msg, &(ctx)->d_pos, &(ctx)->d_ws, &(ctx)->d_kat, &(ctx)->d_tape, &(ctx)->d_strings, &(ctx)->d_s2, &(ctx)->d_s2z, \
      &(ctx)->d_aux, &(ctx)->d_scol, &(ctx)->d_stab, &(ctx)->d_q, &(ctx)->d_qtape, &(ctx)->d_qstrings,       \
      &(ctx)->d_keyflag, &(ctx)->d_col, &(ctx)->d_list, &(ctx)->d_table, &(ctx)->d_tabledata, &(ctx)->d_rows, &(ctx)->d_group, \
-     &(ctx)->d_order, &(ctx)->d_parents, &(ctx)->d_schema, &(ctx)->d_schema_work}
+     &(ctx)->d_order, &(ctx)->d_parents, &(ctx)->d_schema, &(ctx)->d_schema_work, &(ctx)->d_in}
 
 size_t sjhip_ctx_device_bytes(const sjhip_ctx *ctx) {
     if (!ctx) return 0;

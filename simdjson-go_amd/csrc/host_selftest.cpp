@@ -1012,3 +1012,204 @@ extern "C" void sj_selftest_where_limits(int *out5) {
     out5[0] = sj::WHERE_MAX_PREDS, out5[1] = sj::WHERE_MAX_PROGRAM;
     out5[2] = sj::WHERE_AND, out5[3] = sj::WHERE_OR, out5[4] = sj::WHERE_NEG;
 }
+
+// sj_wherein.h: the table over the set of a set predicate (sjhip_where_path_in) and the probe of a row's key, as k_q_in_build and
+// k_q_in_mark run them, replayed serially (InPlainTable) and held to std::set.  The inputs are constructed here: INT values homed at
+// one slot by inverting group_hash_int (32 at the last of 64 slots, 33 at slot 120 of 128: chains that wrap; strangers homed there
+// and inside the chain), 16-byte strings with one 64-bit hash by inverting the word round of group_hash_bytes, strings homed at the
+// last slot by search, every length around the 8-byte word with twins that differ in the last byte, duplicates, the empty set, and
+// random sets.  Every set is filled in three insertion orders; after each, every distinct value must sit in exactly one slot under
+// its smallest index, and every probe must answer as the std::set does.
+//   sj_selftest_where_in  -> 0, or the line of the first check that failed; out8 = sets replayed, probes, hits, probes that crossed
+//                         the last slot, probes that met an equal hash with other bytes, the longest probe
+#include <set>
+#include <string>
+
+#include "sj_wherein.h"
+namespace {
+uint64_t in_inv64(uint64_t a) {  // the inverse of an odd number modulo 2^64 (Newton)
+    uint64_t x = a;
+    for (int i = 0; i < 6; i++) x *= 2 - a * x;
+    return x;
+}
+uint64_t in_unmix(uint64_t h) {  // the inverse of group_mix
+    h ^= h >> 33;
+    h *= in_inv64(0xc4ceb9fe1a85ec53ull);
+    h ^= h >> 33;
+    h *= in_inv64(0xff51afd7ed558ccdull);
+    h ^= h >> 33;
+    return h;
+}
+uint64_t in_int_with_hash(uint64_t h) { return in_unmix(h) ^ 0x9e3779b97f4a7c15ull; }
+uint64_t in_int_at(uint32_t slot, uint32_t mask, uint64_t i) { return in_int_with_hash((sj::group_mix(i + 1) & ~(uint64_t)mask) | slot); }
+struct InReplay {
+    uint64_t sets = 0, probes = 0, hits = 0, wrapped = 0, equal_hashes = 0, longest = 0;
+    // kind: 1 INT / 4 STRING; values and keys as strings (an INT: its 8 bytes)
+    int run(int kind, const std::vector<std::string> &values, const std::vector<std::string> &keys) {
+        const bool str = kind == sj::IN_KIND_STRING;
+        const uint32_t n = (uint32_t)values.size();
+        std::vector<uint64_t> vals;
+        std::vector<uint8_t> bytes(1, 0);
+        if (str) {
+            vals.push_back(0);
+            for (const std::string &v : values) {
+                bytes.insert(bytes.end(), v.begin(), v.end());
+                vals.push_back(bytes.size() - 1);
+            }
+            bytes.erase(bytes.begin());
+            bytes.push_back(0);
+        } else {
+            for (const std::string &v : values) {
+                uint64_t x;
+                memcpy(&x, v.data(), 8);
+                vals.push_back(x);
+            }
+            vals.push_back(0);
+        }
+        const uint64_t cap = sj::group_table_capacity(n);
+        std::vector<uint64_t> hash(n + 1);
+        std::vector<uint32_t> table(cap);
+        sj::InSet s;
+        s.kind = kind, s.n = n, s.mask = (uint32_t)(cap - 1);
+        s.vals = SJ_ARR((const uint64_t *)vals.data(), vals.size(), sj::A_IN_VALS);
+        s.bytes = SJ_ARR((const uint8_t *)bytes.data(), bytes.size(), sj::A_IN_BYTES);
+        s.hash = SJ_ARR(hash.data(), n, sj::A_IN_HASH);
+        s.table = SJ_ARR(table.data(), cap, sj::A_IN_TABLE);
+        const std::set<std::string> want(values.begin(), values.end());
+        for (int order = 0; order < 3; order++) {
+            std::fill(table.begin(), table.end(), sj::GROUP_NONE);
+            for (uint32_t k = 0; k < n; k++) {
+                const uint32_t j = order == 0 ? k : (order == 1 ? n - 1 - k : (uint32_t)(((uint64_t)k * 7919u + 13u) % n));
+                if (order == 2 && n % 7919u == 0) return __LINE__;
+                hash[j] = sj::in_value_hash(s, j);
+                const uint32_t slot = sj::in_insert(s, j, hash[j], sj::InPlainTable());
+                if (slot > s.mask || table[slot] == sj::GROUP_NONE || values[table[slot]] != values[j]) return __LINE__;
+            }
+            // the table's content is decided by the set alone: every distinct value once, under its smallest index
+            std::set<std::string> seen;
+            for (uint32_t slot = 0; slot <= s.mask; slot++) {
+                const uint32_t j = table[slot];
+                if (j == sj::GROUP_NONE) continue;
+                if (j >= n || !seen.insert(values[j]).second) return __LINE__;
+                for (uint32_t k = 0; k < j; k++)
+                    if (values[k] == values[j]) return __LINE__;
+            }
+            if (seen != want) return __LINE__;
+            for (const std::string &key : keys) {
+                uint64_t x = 0;
+                if (!str) memcpy(&x, key.data(), 8);
+                const uint8_t *const p = (const uint8_t *)key.data();
+                const uint64_t h = str ? sj::group_hash_bytes(p, key.size()) : sj::group_hash_int(x);
+                uint32_t steps = 0;
+                const bool found = sj::in_probe(s, h, x, str ? p : nullptr, str ? key.size() : 0, &steps);
+                if (found != (want.count(key) != 0)) return __LINE__;
+                probes++, hits += found;
+                if (((uint32_t)h & s.mask) + steps - 1 > s.mask) wrapped++;
+                if (steps > longest) longest = steps;
+                if (!found)
+                    for (uint32_t j = 0; j < n; j++)
+                        if (hash[j] == h) {
+                            equal_hashes++;
+                            break;
+                        }
+            }
+        }
+        sets++;
+        return 0;
+    }
+};
+std::string in_bytes_of(uint64_t x) { return std::string((const char *)&x, 8); }
+// a 16-byte string with the hash of `like` (16 bytes too) and the first word w0: the second word is solved from the round
+std::string in_colliding(const std::string &like, uint64_t w0) {
+    const uint64_t rmul = 0x9fb21c651e98df25ull;
+    auto round = [&](uint64_t h, uint64_t w) {
+        h = (h ^ sj::group_mix(w)) * rmul;
+        return h ^ (h >> 29);
+    };
+    uint64_t a, b;
+    memcpy(&a, like.data(), 8);
+    memcpy(&b, like.data() + 8, 8);
+    const uint64_t h0 = 0x9e3779b97f4a7c15ull ^ (16 * 0xff51afd7ed558ccdull);
+    const uint64_t target = round(round(h0, a), b), h1 = round(h0, w0);
+    const uint64_t x = target ^ (target >> 29) ^ (target >> 58);
+    const uint64_t w1 = in_unmix((x * in_inv64(rmul)) ^ h1);
+    return in_bytes_of(w0) + in_bytes_of(w1);
+}
+}  // namespace
+extern "C" int sj_selftest_where_in(uint64_t *out8) {
+    InReplay r;
+    int rc = 0;
+    auto ints = [](std::initializer_list<std::pair<uint32_t, std::pair<uint32_t, std::pair<uint64_t, uint64_t>>>> runs) {
+        std::vector<std::string> v;  // (slot, (mask, (first, count)))
+        for (const auto &run : runs)
+            for (uint64_t i = 0; i < run.second.second.second; i++)
+                v.push_back(in_bytes_of(in_int_at(run.first, run.second.first, run.second.second.first + i)));
+        return v;
+    };
+    // INT: chains that wrap, strangers homed at the chain's home and inside it
+    if (!rc) rc = r.run(1, ints({{63, {63, {0, 32}}}}), ints({{63, {63, {0, 40}}}, {10, {63, {100, 6}}}, {40, {63, {200, 6}}}}));
+    if (!rc) rc = r.run(1, ints({{120, {127, {0, 33}}}}), ints({{120, {127, {0, 40}}}, {2, {127, {100, 6}}}, {60, {127, {200, 6}}}}));
+    // duplicates, one value, the empty set
+    {
+        std::vector<std::string> dup(100, in_bytes_of(5));
+        dup.push_back(in_bytes_of(7)), dup.insert(dup.begin() + 50, in_bytes_of((uint64_t)-3));
+        std::vector<std::string> keys;
+        for (uint64_t x = 0; x < 16; x++) keys.push_back(in_bytes_of(x - 4));
+        if (!rc) rc = r.run(1, dup, keys);
+        if (!rc) rc = r.run(1, {in_bytes_of(9)}, keys);
+        if (!rc) rc = r.run(1, {}, keys);
+        if (!rc) rc = r.run(sj::IN_KIND_STRING, {}, {"", "a"});
+    }
+    // random INT sets: 1000 values from 1500, probed with all 1500 and more
+    {
+        std::vector<std::string> vals, keys;
+        uint64_t x = 88172645463325252ull;
+        for (int i = 0; i < 3000; i++) {
+            x ^= x << 13, x ^= x >> 7, x ^= x << 17;
+            if (i < 1000 || i % 3 == 0) vals.push_back(in_bytes_of(x % 1500));
+            keys.push_back(in_bytes_of(x % 2200));
+        }
+        if (!rc) rc = r.run(1, vals, keys);
+        if (!rc) rc = r.run(2, vals, keys);
+    }
+    // STRING: one 64-bit hash for four 16-byte strings; two of them (and a duplicate) are the set
+    {
+        const std::string a = "sixteen bytes :)";
+        const std::string b = in_colliding(a, 0x1122334455667788ull), c = in_colliding(a, 0x0102030405060708ull), d = in_colliding(a, 42);
+        if (sj::group_hash_bytes((const uint8_t *)b.data(), 16) != sj::group_hash_bytes((const uint8_t *)a.data(), 16) || a == b || c == d) return __LINE__;
+        if (!rc) rc = r.run(sj::IN_KIND_STRING, {a, c, a}, {a, b, c, d, "sixteen bytes :(", a.substr(0, 15)});
+        if (!rc) rc = r.run(sj::IN_KIND_STRING, {b}, {a, b, c, d});
+    }
+    // ... every length around the word, with twins that differ in the last byte, and the lengths' neighbours
+    {
+        std::vector<std::string> vals, keys;
+        for (size_t n = 0; n <= 40; n++) {
+            std::string v;
+            for (size_t i = 0; i < n; i++) v.push_back((char)('a' + (n * 3 + i * 7) % 26));
+            vals.push_back(v);
+            keys.push_back(v);
+            if (n) {
+                std::string t = v;
+                t[n - 1] ^= 1;
+                keys.push_back(t);
+            }
+            keys.push_back(v + "!");
+        }
+        vals.push_back(std::string(1024, 'x'));
+        keys.push_back(std::string(1024, 'x')), keys.push_back(std::string(1023, 'x') + "y"), keys.push_back(std::string(1023, 'x'));
+        if (!rc) rc = r.run(sj::IN_KIND_STRING, vals, keys);
+    }
+    // ... 32 strings homed at the last of 64 slots, found by search; strangers homed there too
+    {
+        std::vector<std::string> homed;
+        for (uint64_t i = 0; homed.size() < 40 && i < 100000; i++) {
+            const std::string v = "key-" + std::to_string(i);
+            if ((sj::group_hash_bytes((const uint8_t *)v.data(), v.size()) & 63) == 63) homed.push_back(v);
+        }
+        if (homed.size() != 40) return __LINE__;
+        if (!rc) rc = r.run(sj::IN_KIND_STRING, std::vector<std::string>(homed.begin(), homed.begin() + 32), homed);
+    }
+    out8[0] = r.sets, out8[1] = r.probes, out8[2] = r.hits, out8[3] = r.wrapped, out8[4] = r.equal_hashes, out8[5] = r.longest;
+    out8[6] = out8[7] = 0;
+    return rc;
+}

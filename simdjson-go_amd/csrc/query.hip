@@ -33,6 +33,7 @@
 #include "sj_tapewalk.h"
 #include "sj_tablewalk.h"
 #include "sj_where.h"
+#include "sj_wherein.h"
 
 using namespace sj;
 
@@ -1673,6 +1674,72 @@ __global__ __launch_bounds__(256) void k_q_where_multi_mark(QView q, WherePlan p
             for (u32 k = 0; k < p.n_preds; k++)
                 if ((p.empty >> k) & 1u) sink.test(k, v0);
         keep = where_program_eval(p.program, p.program_len, sink.truth);
+        if (!count) w.flag[i] = keep ? 1 : 0;
+    }
+    if (count) {
+        count_ballot(keep, count);
+        return;
+    }
+    const u64 b = __ballot(keep);  // (the 64 rows of a wave lie in one tile)
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&w.tiles[i / QTILE], (unsigned long long)__popcll(b));
+}
+// ... by MEMBERSHIP in a set of values (sjhip_where_path_in: a semi-join, and with NOT an anti-join).  The set is the caller's:
+// uploaded as it came, hashed and entered into an open-addressing table of value indices (sj_wherein.h) by
+//   k_q_in_build   one lane per value: the grouping's hash of the value (group_hash_bytes / group_hash_int: a row's key hashes as
+//                  in the grouping) is stored for the probes, and the value claims a slot of the u32 table of
+//                  group_table_capacity(n_values) slots -- k_q_group_insert's loop: compare-and-swap on an empty slot, an equal
+//                  value already there ends the probe and the smaller index stays (atomicMin), anything else probes on.  Occupants
+//                  are compared by VALUE here, not by hash[]: the values lay on the device before the kernel began, the hash of
+//                  another lane's value may not.  Every access to the table is a device-scope atomic; no locks, no spinning,
+//                  bounded by the capacity.
+//   k_q_in_mark    k_q_where_mark's place in where_build, one lane per row: FindElement (an empty path: the row's value), the
+//                  conversion of the EQ_* operator of the set's kind -- the string's unescaped bytes wherever they lie, element_to
+//                  for INT / UINT; no usable key: no match --, the hash, and the probe from the home slot to the first empty one:
+//                  at an occupied slot the stored hash first, then the value (a string's length before any byte).  The cost of a
+//                  row is its walk, its hash and a chain whose expected length does not depend on the size of the set (load <= 1/2).
+//                  The flag and the tile count leave as in k_q_where_mark, with `count` set the ballot goes to that one counter
+//                  and nothing else is written (k_q_where_multi_mark's rule).  An empty set has no table: every flag is `negate`.
+// The string probe is inlined: the kernel then needs k_q_where_mark's registers and no scratch on both builds, whereas a call
+// would have to hand the view and the set over in memory -- kernel arguments copied to scratch (64 bytes per lane in the product
+// build, the whole view in the bounds-checked one).  tests/test_where_in_kernel_resources.py holds both kernels to that.
+struct InAtomicTable {
+    __device__ __forceinline__ u32 load(u32 *cell) const { return __hip_atomic_load(cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    __device__ __forceinline__ u32 claim(u32 *cell, u32 j) const { return atomicCAS(cell, GROUP_NONE, j); }
+    __device__ __forceinline__ void lower(u32 *cell, u32 j) const { (void)atomicMin(cell, j); }
+};
+static_assert(IN_KIND_STRING == SJHIP_COL_STRING && IN_MAX_STRING == (u32)QMAX, "sj_wherein.h takes the header's kind and EQ_STRING's limit");
+__global__ __launch_bounds__(256) void k_q_in_build(InSet s) {
+    const u32 j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= s.n) return;
+    const u64 h = in_value_hash(s, j);
+    s.hash[j] = h;
+    (void)in_insert(s, j, h, InAtomicTable());
+}
+__device__ __forceinline__ bool in_string_matches(const QView &q, const InSet &s, u64 w, u64 len) {
+    const u8 *const p = str_bytes(q, w, len);
+    return in_probe(s, group_hash_bytes(p, len), 0, p, len);
+}
+__device__ __forceinline__ bool in_element_matches(const QView &q, const InSet &s, u64 v) {
+    if (s.kind == SJHIP_COL_STRING) {
+        const u64 w = q.tape[v];
+        if ((u32)(w >> 56) != '"') return false;
+        const u64 len = q.tape[v + 1];
+        return len <= IN_MAX_STRING && in_string_matches(q, s, w, len);  // (no value of a set is longer)
+    }
+    u64 x;
+    return element_to(q, v, s.kind, &x) == SJHIP_COL_OK && in_probe(s, group_hash_int(x), x, nullptr, 0);
+}
+static_assert(sizeof(QView) + sizeof(QPath) + sizeof(InSet) + sizeof(QWhere) + 16 <= 4096, "k_q_in_mark: its arguments travel as kernel arguments (4 KiB)");
+__global__ __launch_bounds__(256) void k_q_in_mark(QView q, QPath pth, InSet s, u32 negate, QWhere w, unsigned long long *count) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    bool keep = false;
+    if (i < q_rows(q)) {
+        bool in = false;
+        if (s.n) {
+            const u64 v = pth.n ? record_find_path(q, pth, i) : row_value(q, i);
+            in = v < SJHIP_PATH_NOT_OBJECT && in_element_matches(q, s, v);
+        }
+        keep = in != (negate != 0);
         if (!count) w.flag[i] = keep ? 1 : 0;
     }
     if (count) {
@@ -3874,6 +3941,173 @@ int sjhip_count_where_paths(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t 
     return count_over_parts(ctx, m.keys, m.klen, m.vals, m.vlen, true, count,
                             [&](sjhip_ctx *part, const QView &q, uint32_t n, unsigned long long *d) {
                                 where_multi_launch(part, q, n, m.plan, QWhere(), d);
+                            });
+}
+
+// ---- row predicates by membership in a set (sjhip_where_path_in, sjhip_count_where_path_in) ----------------------------------------
+// The arguments of both calls are checked on the host -- nothing of the context is touched, nothing of the values is read before
+// their number has been --; then every part that has rows gets the set in its d_in (uploaded as it came, the table cleared,
+// k_q_in_build queued on the part's stream, in front of the mark that probes it), and the rest is where_build with k_q_in_mark, or
+// the count.  The set is working data of the call: d_in is written over by the next one and freed by sjhip_ctx_trim.
+struct InArgs {
+    int kind;
+    const uint64_t *offs;  // STRING
+    const void *values;
+    u32 n;
+    size_t bytes;          // STRING: of all values
+    QPath pth;
+    const uint8_t *keys;
+    size_t klen;
+    u32 negate;
+};
+static int in_args(sjhip_ctx *ctx, const char *who, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int kind,
+                   const uint64_t *value_offsets, const void *values, size_t n_values, uint32_t flags, InArgs *a) {
+    if (flags & ~SJHIP_WHERE_NOT) {
+        ctx_set_error(ctx, "%s: unknown flag bits 0x%x", who, flags & ~SJHIP_WHERE_NOT);
+        return SJHIP_ERR_ARG;
+    }
+    if (kind != SJHIP_COL_STRING && kind != SJHIP_COL_INT && kind != SJHIP_COL_UINT) {
+        ctx_set_error(ctx, "%s: kind %d (a set holds SJHIP_COL_STRING, SJHIP_COL_INT or SJHIP_COL_UINT values)", who, kind);
+        return SJHIP_ERR_ARG;
+    }
+    if (n_values > (size_t)SJHIP_WHERE_IN_MAX_VALUES) {
+        ctx_set_error(ctx, "%s: %zu values (at most %u)", who, n_values, (unsigned)SJHIP_WHERE_IN_MAX_VALUES);
+        return SJHIP_ERR_ARG;
+    }
+    a->kind = kind, a->offs = nullptr, a->values = values, a->n = (u32)n_values, a->bytes = 0, a->negate = flags & SJHIP_WHERE_NOT;
+    if (kind == SJHIP_COL_STRING && n_values) {
+        if (!value_offsets) {
+            ctx_set_error(ctx, "%s: %zu string values are announced and `value_offsets` is null", who, n_values);
+            return SJHIP_ERR_ARG;
+        }
+        if (value_offsets[0] != 0) {
+            ctx_set_error(ctx, "%s: value_offsets[0] is %llu, not 0", who, (unsigned long long)value_offsets[0]);
+            return SJHIP_ERR_ARG;
+        }
+        for (size_t j = 0; j < n_values; j++) {
+            if (value_offsets[j + 1] < value_offsets[j]) {
+                ctx_set_error(ctx, "%s: value_offsets[%zu] is smaller than the offset in front of it", who, j + 1);
+                return SJHIP_ERR_ARG;
+            }
+            if (value_offsets[j + 1] - value_offsets[j] > (uint64_t)QMAX) {
+                ctx_set_error(ctx, "%s: value %zu is %llu bytes long (a string value holds at most %d)", who, j,
+                              (unsigned long long)(value_offsets[j + 1] - value_offsets[j]), QMAX);
+                return SJHIP_ERR_ARG;
+            }
+        }
+        a->offs = value_offsets;
+        a->bytes = (size_t)value_offsets[n_values];
+    }
+    if (!values && (kind == SJHIP_COL_STRING ? a->bytes != 0 : n_values != 0)) {
+        ctx_set_error(ctx, "%s: %zu values are announced and `values` is null", who, n_values);
+        return SJHIP_ERR_ARG;
+    }
+    const int rc = make_path(ctx, keys, key_lens, n_keys, &a->pth, &a->klen, true);
+    a->keys = keys ? keys : &NO_VALUE;
+    return rc;
+}
+static size_t in_layout(Carve c, const InArgs &a, InSet *s) {
+    const bool str = a.kind == SJHIP_COL_STRING;
+    const size_t cap = (size_t)group_table_capacity(a.n), n_vals = (size_t)a.n + (str ? 1u : 0u);
+    const u64 *const vals = c.take<u64>(n_vals);
+    const u8 *const bytes = c.take<u8>(str ? a.bytes : 0);
+    u64 *const hash = c.take<u64>(a.n);
+    u32 *const table = c.take<u32>(cap);
+    s->kind = a.kind, s->n = a.n, s->mask = (u32)(cap - 1);
+    s->vals = SJ_ARR(vals, n_vals, A_IN_VALS);
+    s->bytes = SJ_ARR(bytes, str ? a.bytes : 0, A_IN_BYTES);
+    s->hash = SJ_ARR(hash, a.n, A_IN_HASH);
+    s->table = SJ_ARR(table, cap, A_IN_TABLE);
+    return c.used;
+}
+// the set of every part that has rows, in the part's d_in, its build queued on the part's stream; sets[k]: part k's (n == 0: none)
+static int in_upload(sjhip_ctx *ctx, sjhip_ctx *part, const InArgs &a, InSet *s) {
+    HIPCHK(hipSetDevice(part->device), "hipSetDevice");
+    const int rc = reserve_layout(part, part->d_in, [&](Carve c) { return in_layout(c, a, s); });
+    if (rc) return rc;
+    const bool str = a.kind == SJHIP_COL_STRING;
+    HIPCHK(hipMemcpyAsync((void *)arr_raw(s->vals), str ? (const void *)a.offs : a.values, ((size_t)a.n + (str ? 1u : 0u)) * 8,
+                          hipMemcpyHostToDevice, part->stream), "H2D set values");
+    if (str && a.bytes)
+        HIPCHK(hipMemcpyAsync((void *)arr_raw(s->bytes), a.values, a.bytes, hipMemcpyHostToDevice, part->stream), "H2D set bytes");
+    HIPCHK(hipMemsetAsync(arr_raw(s->table), 0xff, ((size_t)s->mask + 1u) * 4, part->stream), "set table memset");
+    hipLaunchKernelGGL(k_q_in_build, dim3((a.n + 255) / 256), dim3(256), 0, part->stream, *s);
+    HIPCHK(hipGetLastError(), "set build launch");
+    return SJHIP_OK;
+}
+// the parts of either call: query_parts, and every part's result still on the device (make_view's check, made here before
+// anything is uploaded)
+static int in_parts(sjhip_ctx *ctx, const InArgs &a, std::vector<sjhip_ctx *> *parts) {
+    const int rc = query_parts(ctx, a.keys, a.klen, &NO_VALUE, 0, parts);
+    if (rc) return rc;
+    for (const sjhip_ctx *part : *parts)
+        if (!part->res.resident()) return no_result(ctx);
+    return SJHIP_OK;
+}
+static int in_prepare(sjhip_ctx *ctx, const std::vector<sjhip_ctx *> &parts, const InArgs &a, std::vector<InSet> *sets) {
+    sets->assign(parts.size(), InSet());
+    int rc = SJHIP_OK;
+    size_t k = 0;
+    for (; k < parts.size() && rc == SJHIP_OK; k++)
+        if (a.n && part_rows(ctx, parts[k], true)) rc = in_upload(ctx, parts[k], a, &(*sets)[k]);
+    if (rc)  // (the copies read the caller's arrays: none is left in flight behind the return)
+        for (size_t j = 0; j < k; j++)
+            if (hipSetDevice(parts[j]->device) == hipSuccess) (void)hipStreamSynchronize(parts[j]->stream);
+    (void)hipSetDevice(ctx->device);
+    return rc;
+}
+static const InSet &in_set_of(const std::vector<sjhip_ctx *> &parts, const std::vector<InSet> &sets, const sjhip_ctx *part) {
+    size_t k = 0;
+    while (k + 1 < parts.size() && parts[k] != part) k++;
+    return sets[k];
+}
+static void in_launch(sjhip_ctx *part, const QView &q, uint32_t n, const InArgs &a, const InSet &s, const QWhere &w, unsigned long long *count) {
+    hipLaunchKernelGGL(k_q_in_mark, dim3((n + 255) / 256), dim3(256), 0, part->stream, q, a.pth, s, a.negate, w, count);
+}
+
+int sjhip_where_path_in(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int kind,
+                        const uint64_t *value_offsets, const void *values, size_t n_values, uint32_t flags, size_t *records, size_t *rows) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!records || !rows) {
+        ctx_set_error(ctx, "sjhip_where_path_in: a null size pointer");
+        return SJHIP_ERR_ARG;
+    }
+    InArgs a;
+    int rc = in_args(ctx, "sjhip_where_path_in", keys, key_lens, n_keys, kind, value_offsets, values, n_values, flags, &a);
+    if (rc) return rc;
+    std::vector<sjhip_ctx *> parts;
+    rc = in_parts(ctx, a, &parts);
+    if (rc) return rc;  // (nothing has been queued: the selection is as it was)
+    std::vector<InSet> sets;
+    rc = in_prepare(ctx, parts, a, &sets);
+    if (rc == SJHIP_OK)
+        rc = where_build(ctx, parts, a.keys, a.klen, &NO_VALUE, 0,
+                         [&](sjhip_ctx *part, const QView &q, uint32_t n, const QWhere &w) {
+                             in_launch(part, q, n, a, in_set_of(parts, sets, part), w, nullptr);
+                         },
+                         records, rows);
+    return rc ? where_gave_up(ctx, parts, "sjhip_where_path_in", rc) : rc;
+}
+
+int sjhip_count_where_path_in(sjhip_ctx *ctx, const uint8_t *keys, const uint32_t *key_lens, uint32_t n_keys, int kind,
+                              const uint64_t *value_offsets, const void *values, size_t n_values, uint32_t flags, uint64_t *count) {
+    if (!ctx) return SJHIP_ERR_ARG;
+    if (!count) {
+        ctx_set_error(ctx, "sjhip_count_where_path_in: a null count pointer");
+        return SJHIP_ERR_ARG;
+    }
+    InArgs a;
+    int rc = in_args(ctx, "sjhip_count_where_path_in", keys, key_lens, n_keys, kind, value_offsets, values, n_values, flags, &a);
+    if (rc) return rc;
+    std::vector<sjhip_ctx *> parts;
+    rc = in_parts(ctx, a, &parts);
+    if (rc) return rc;
+    std::vector<InSet> sets;
+    rc = in_prepare(ctx, parts, a, &sets);
+    if (rc) return rc;
+    return count_over_parts(ctx, a.keys, a.klen, &NO_VALUE, 0, true, count,
+                            [&](sjhip_ctx *part, const QView &q, uint32_t n, unsigned long long *d) {
+                                in_launch(part, q, n, a, in_set_of(parts, sets, part), QWhere(), d);
                             });
 }
 

@@ -72,7 +72,10 @@ enum ArrId : uint32_t {
     // the per-member work arrays (hash, type class, slot, first-occurrence flag, name length) / the table of member numbers / the
     // status histogram / the run bounds of the sorted (name, type) keys / the arrays of the product (name offsets, first rows,
     // counts) / the names' bytes.  Its sort is A_SORT
-    A_SCHEMA_MEMBER, A_SCHEMA_PARENT, A_SCHEMA_WORK, A_SCHEMA_TABLE, A_SCHEMA_HIST, A_SCHEMA_BOUNDS, A_SCHEMA_OUT, A_SCHEMA_NAMES
+    A_SCHEMA_MEMBER, A_SCHEMA_PARENT, A_SCHEMA_WORK, A_SCHEMA_TABLE, A_SCHEMA_HIST, A_SCHEMA_BOUNDS, A_SCHEMA_OUT, A_SCHEMA_NAMES,
+    // the set of a set predicate (query.hip, sjhip_where_path_in; sj_wherein.h): the values or the offsets of the string values /
+    // the string values' bytes / the hash of every value / the table of value indices
+    A_IN_VALS, A_IN_BYTES, A_IN_HASH, A_IN_TABLE
 };
 
 #if defined(SJ_DEBUG_BOUNDS)

@@ -53,6 +53,9 @@ struct sjhip_ctx {
     // (d_schema), and the work arrays of its second half, sized by the members the first half counted (d_schema_work: d_kat holds
     // the member walk's arrays, which that half still reads, and a second reservation would move it)
     sj::DevBuf d_schema, d_schema_work;
+    // the set of the sjhip_where_path_in call at work (query.hip): the uploaded values, their hashes and the table over them.  Working
+    // data, not a product: nothing refers to it once the call has returned
+    sj::DevBuf d_in;
     unsigned ws_clean_gen = 0;         // d_ws.gen of the allocation that has been zeroed for stage 1 (0: none; stage1_enqueue)
     sj::S1Ws s1ws;                     // ... and its launch count (sj_device.h: a launch cleans up for the next one)
     // queued stage-1 messages that wait for their launch (api.hip: the queue runs up to S1_GROUP_MAX messages of one mode as one

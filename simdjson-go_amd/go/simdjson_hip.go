@@ -859,3 +859,77 @@ func (v *ViewParser) GroupPaths(keys []GroupKeyColumn, values []GroupValueColumn
 	}
 	return res, nil
 }
+
+// ---- row predicates by membership in a set on the result a ViewParser holds (sjhip_where_path_in) --------------------------
+// What a caller of the reference writes as a map of the wanted values and a loop over the rows with one
+// Iter.FindElement(path...) + Iter.StringBytes / Int / Uint and a lookup per row -- on the device, the set as a hash table
+// there.  The rows are those of the selection in force: the records of the last Parse / ParseND, or what an earlier
+// WherePathIn kept.
+
+// WhereInMaxValues: the most values of one set.
+const WhereInMaxValues = int(C.SJHIP_WHERE_IN_MAX_VALUES)
+
+// WhereInSet is the set of a WherePathIn call: Strings for Kind GroupString, else Values -- the bits of int64 (GroupInt) or
+// uint64 (GroupUint) values.  Duplicates are legal; an empty set matches no row.
+type WhereInSet struct {
+	Kind    GroupColumnKind
+	Strings [][]byte
+	Values  []uint64
+}
+
+// whereInArgs lays a set out as the C call takes it: Arrow's large-string layout, or the values as they are.
+func whereInArgs(path []string, set WhereInSet) (blob []byte, keyLens []C.uint32_t, offs []uint64, data []uint8, values unsafe.Pointer, n int) {
+	for _, name := range path {
+		blob = append(blob, name...)
+		keyLens = append(keyLens, C.uint32_t(len(name)))
+	}
+	blob = append(blob, 0)
+	keyLens = append(keyLens, 0)
+	if set.Kind == GroupString {
+		n = len(set.Strings)
+		offs = make([]uint64, n+1)
+		for j, s := range set.Strings {
+			data = append(data, s...)
+			offs[j+1] = uint64(len(data))
+		}
+		values = unsafe.Pointer(u8ptr(data))
+	} else {
+		n = len(set.Values)
+		values = unsafe.Pointer(u64ptr(set.Values))
+	}
+	return
+}
+
+// WherePathIn keeps the rows whose element at path (no keys: the row's own value) is a value of the set -- with negate
+// the others, the rows without a usable key included -- and returns the records and the rows kept (include/sjhip.h:
+// sjhip_where_path_in).
+func (v *ViewParser) WherePathIn(path []string, set WhereInSet, negate bool) (records, rows int, err error) {
+	blob, keyLens, offs, _, values, n := whereInArgs(path, set)
+	var flags C.uint32_t
+	if negate {
+		flags = C.SJHIP_WHERE_NOT
+	}
+	var nr, nw C.size_t
+	rc := C.sjhip_where_path_in(v.c.h, (*C.uint8_t)(unsafe.Pointer(&blob[0])), &keyLens[0], C.uint32_t(len(path)), C.int(set.Kind),
+		u64ptr(offs), values, C.size_t(n), flags, &nr, &nw)
+	if rc != C.SJHIP_OK {
+		return 0, 0, fmt.Errorf("sjhip: %s", C.GoString(C.sjhip_last_error(v.c.h)))
+	}
+	return int(nr), int(nw), nil
+}
+
+// CountWherePathIn returns the rows WherePathIn would keep and leaves the selection as it is (sjhip_count_where_path_in).
+func (v *ViewParser) CountWherePathIn(path []string, set WhereInSet, negate bool) (uint64, error) {
+	blob, keyLens, offs, _, values, n := whereInArgs(path, set)
+	var flags C.uint32_t
+	if negate {
+		flags = C.SJHIP_WHERE_NOT
+	}
+	var count C.uint64_t
+	rc := C.sjhip_count_where_path_in(v.c.h, (*C.uint8_t)(unsafe.Pointer(&blob[0])), &keyLens[0], C.uint32_t(len(path)), C.int(set.Kind),
+		u64ptr(offs), values, C.size_t(n), flags, &count)
+	if rc != C.SJHIP_OK {
+		return 0, fmt.Errorf("sjhip: %s", C.GoString(C.sjhip_last_error(v.c.h)))
+	}
+	return uint64(count), nil
+}

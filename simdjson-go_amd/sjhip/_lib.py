@@ -95,6 +95,10 @@ SYMBOLS = {
                                     C.c_char_p, C.c_uint32, szp, szp]),
     "sjhip_count_where_paths": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                           C.c_char_p, C.c_uint32, u64p]),
+    "sjhip_where_path_in": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                      szp, szp]),
+    "sjhip_count_where_path_in": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                            C.c_uint32, u64p]),
     "sjhip_order_path": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_uint64, szp, szp]),
     "sjhip_fetch_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sjhip_order_path_strings": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, szp, szp]),

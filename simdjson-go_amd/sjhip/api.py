@@ -627,6 +627,54 @@ class Context:
         self._check(_lib.lib().sjhip_count_where_paths(*self._where_paths_args(predicates, program), C.byref(cnt)))
         return cnt.value
 
+    WHERE_IN_MAX_VALUES = 1 << 24  # SJHIP_WHERE_IN_MAX_VALUES
+
+    def _where_in_args(self, path, kind, values, negate):
+        """the arguments of sjhip_where_path_in up to `flags`, and the arrays they point into (to be kept until the call returns)"""
+        blob, lens, n = self._keys(path)
+        kind = int(kind)
+        offs = data = None
+        if kind == self.COL_STRING:
+            if isinstance(values, tuple) and len(values) == 2 and isinstance(values[0], np.ndarray):
+                offs = np.ascontiguousarray(values[0], dtype=np.uint64)
+                data = np.ascontiguousarray(values[1], dtype=np.uint8)
+            else:
+                vs = [bytes(v) for v in values]
+                offs = np.zeros(len(vs) + 1, dtype=np.uint64)
+                offs[1:] = np.cumsum([len(v) for v in vs], dtype=np.uint64)
+                data = np.frombuffer(b"".join(vs), dtype=np.uint8)
+            count = max(len(offs) - 1, 0)
+        elif isinstance(values, np.ndarray) and values.dtype in (np.int64, np.uint64):
+            data, count = np.ascontiguousarray(values), len(values)
+        else:
+            data = np.array([int(v) & 0xFFFFFFFFFFFFFFFF for v in values], dtype=np.uint64)
+            count = len(data)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        args = (self._h, blob if n else None, lens if n else None, n, kind, ptr(offs) if count else None, ptr(data), count,
+                self.WHERE_NOT if negate else 0)
+        return args, (offs, data)
+
+    def where_path_in(self, path, kind, values, negate=False):
+        """where_path by MEMBERSHIP: keeps the rows whose element at `path` (an empty path: the row's own value) equals one of
+        `values` as OP_EQ_STRING (kind = COL_STRING), OP_EQ_INT (COL_INT) or OP_EQ_UINT (COL_UINT) compare -- a list of bytes, or
+        an (offsets, data) pair of numpy arrays in Arrow's large-string layout; a list or an int64 / uint64 array of ints.  What
+        group_path returns as keys can be passed straight back.  negate: keeps the others instead, the rows without a usable key
+        included.  Duplicates change nothing; no values: no row matches.  Narrowing and composition are where_path's.
+        -> (records, rows kept)"""
+        args, keep = self._where_in_args(path, kind, values, negate)
+        nr, nw = C.c_size_t(0), C.c_size_t(0)
+        self._check(_lib.lib().sjhip_where_path_in(*args, C.byref(nr), C.byref(nw)))
+        del keep
+        return nr.value, nw.value
+
+    def count_where_path_in(self, path, kind, values, negate=False):
+        """the rows where_path_in(path, kind, values, negate) would keep; the selection stays as it is"""
+        args, keep = self._where_in_args(path, kind, values, negate)
+        cnt = C.c_uint64(0)
+        self._check(_lib.lib().sjhip_count_where_path_in(*args, C.byref(cnt)))
+        del keep
+        return cnt.value
+
     # ---- unnest (include/sjhip.h: sjhip_unnest_rows / sjhip_fetch_row_parents) ---------------------------------------------------
     def unnest_rows(self, path=()):
         """Iter.FindElement(path...), Iter.Array, Array.Iter on every ROW of the selection in force (without one: on every record's
