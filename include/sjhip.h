@@ -110,7 +110,16 @@ int sjhip_parse_device(sjhip_ctx *ctx, const void *d_msg, size_t len, uint32_t f
  *   begin : stage 1 + stage 2 up to the scan; returns this shard's tape_len / strings_len (message already on
  *           the device, trimmed, starting at a record boundary)
  *   ...   : all-gather the sizes (RCCL), compute the bases
- *   finish: emits tape and Strings.B with the rebased indices; then sjhip_fetch as usual. */
+ *   finish: emits tape and Strings.B with the rebased indices; then sjhip_fetch as usual.
+ *
+ * The window of a shard is its cut range inside the TrimSpace window of the whole message, without the JSON whitespace
+ * (space, \t, \n, \r) at its ends and nothing else: the reference trims the message once, every other byte between two
+ * records is parsed as it stands (and rejected).  SJHIP_FLAG_INNER_SHARD (sjhip_parse_shard_begin only) says that a later
+ * shard holds something, i.e. that the message does not end with this window: "the last structural is a closing bracket"
+ * (stage1_find_marks_amd64.go:120-129) is asked of the end of the message, so a window that ends otherwise -- a stray byte
+ * or a scalar behind its last record, a record broken across a newline -- and has no other stage-1 fault fails with
+ * SJHIP_ERR_STAGE2, the verdict of the whole message, not with SJHIP_ERR_STAGE1. */
+#define SJHIP_FLAG_INNER_SHARD 8u
 int sjhip_parse_shard_begin(sjhip_ctx *ctx, const void *d_msg, size_t len, uint32_t flags, size_t *tape_len,
                             size_t *strings_len);
 int sjhip_parse_shard_finish(sjhip_ctx *ctx, uint64_t tape_base, uint64_t strings_base, uint64_t msg_base);

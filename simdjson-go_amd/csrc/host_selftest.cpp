@@ -155,22 +155,30 @@ extern "C" int sj_selftest_int_fast(const uint8_t *buf, size_t len, uint64_t *va
 extern "C" void sj_selftest_trim(const uint8_t *msg, size_t len, size_t *off, size_t *out_len) {
     trim_space(msg, len, off, out_len);
 }
+// the windows of a message cut into n shards, the global window, and which shards a later one follows (sj_host.h)
+extern "C" void sj_selftest_shard_windows(const uint8_t *msg, size_t len, size_t n, size_t *starts, size_t *lens, uint8_t *inner,
+                                          size_t *g_off, size_t *g_len) {
+    sj::shard_windows(msg, len, n, starts, lens, g_off, g_len);
+    sj::shard_inner(lens, n, inner);
+}
 
-static int selftest_parse(const uint8_t *msg0, size_t len0, uint32_t flags, uint64_t tape_base, uint64_t strings_base,
+static int selftest_parse(const uint8_t *msg0, size_t len0, uint32_t flags, bool shard, uint64_t tape_base, uint64_t strings_base,
                           uint64_t msg_base, uint64_t **tape_out, size_t *tape_len, uint8_t **strings_out,
                           size_t *strings_len, size_t *msg_off, size_t *msg_len);
 extern "C" int sj_selftest_parse(const uint8_t *msg0, size_t len0, uint32_t flags, uint64_t **tape_out, size_t *tape_len,
                                  uint8_t **strings_out, size_t *strings_len, size_t *msg_off, size_t *msg_len) {
-    return selftest_parse(msg0, len0, flags, 0, 0, 0, tape_out, tape_len, strings_out, strings_len, msg_off, msg_len);
+    return selftest_parse(msg0, len0, flags, false, 0, 0, 0, tape_out, tape_len, strings_out, strings_len, msg_off, msg_len);
 }
-// one NDJSON shard of a larger document: the tape is emitted with rebased indices (sj_stage2.h, Tokens::*_base)
+// one NDJSON shard of a larger document: the tape is emitted with rebased indices (sj_stage2.h, Tokens::*_base).  As
+// sjhip_parse_shard_begin the replay parses the window as it stands -- the caller has trimmed it (sj_host.h shard_windows) --
+// and flag bit 8 (SJHIP_FLAG_INNER_SHARD) turns an end that is not a closing bracket into a stage-2 verdict.
 extern "C" int sj_selftest_parse_shard(const uint8_t *msg0, size_t len0, uint32_t flags, uint64_t tape_base,
                                        uint64_t strings_base, uint64_t msg_base, uint64_t **tape_out, size_t *tape_len,
                                        uint8_t **strings_out, size_t *strings_len, size_t *msg_off, size_t *msg_len) {
-    return selftest_parse(msg0, len0, flags, tape_base, strings_base, msg_base, tape_out, tape_len, strings_out,
+    return selftest_parse(msg0, len0, flags, true, tape_base, strings_base, msg_base, tape_out, tape_len, strings_out,
                           strings_len, msg_off, msg_len);
 }
-static int selftest_parse(const uint8_t *msg0, size_t len0, uint32_t flags, uint64_t tape_base, uint64_t strings_base,
+static int selftest_parse(const uint8_t *msg0, size_t len0, uint32_t flags, bool shard, uint64_t tape_base, uint64_t strings_base,
                           uint64_t msg_base, uint64_t **tape_out, size_t *tape_len, uint8_t **strings_out,
                           size_t *strings_len, size_t *msg_off, size_t *msg_len) {
     const bool ndjson = flags & 1;
@@ -178,8 +186,8 @@ static int selftest_parse(const uint8_t *msg0, size_t len0, uint32_t flags, uint
     bool copy = copy_all;       // every string copied through the emit masks (byte-parallel path)
     bool masks = true;          // the emit masks are computed (both modes); false after a surrogate-walk overflow
     bool force_copy = false;    // every string copied, but through the per-string walks (after an overflow, parse_api.hip)
-    size_t off, len;
-    trim_space(msg0, len0, &off, &len);
+    size_t off = 0, len = len0;
+    if (!shard) trim_space(msg0, len0, &off, &len);
     *msg_off = off;
     *msg_len = len;
     *tape_out = nullptr;
@@ -204,7 +212,8 @@ static int selftest_parse(const uint8_t *msg0, size_t len0, uint32_t flags, uint
     g_slow = v_slow.data();
     sj_selftest_stage1(msg, len, ndjson, pos.data(), pos.size(), &n, &err, &inq);
     g_qm = g_q = g_st = g_slow = nullptr;
-    if (len == 0 || err || inq || n == 0 || !(msg[len - 1] == '}' || msg[len - 1] == ']')) return 1;
+    if (len == 0 || err || inq || n == 0) return 1;
+    if (!(msg[len - 1] == '}' || msg[len - 1] == ']')) return shard && (flags & 8u) ? 2 : 1;
     const MsgView mv{msg, len};
     // stage 2: the kernels of stage2.hip as loops, in launch order
     static constexpr KindLut KLUT = make_kind_lut();

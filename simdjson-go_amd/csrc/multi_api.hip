@@ -26,7 +26,8 @@ namespace {
 struct Shard {
     sjhip_ctx *ctx = nullptr;
     int device = 0;
-    size_t start = 0, len = 0;  // window of the (trimmed) shard inside the caller's message
+    size_t start = 0, len = 0;  // window of the shard inside the caller's message (sj_host.h shard_windows)
+    bool inner = false;         // a later shard holds something: this one does not end the message
     size_t tape_len = 0, strings_len = 0;
     size_t tape_base = 0, strings_base = 0;
     int rc = 0;
@@ -115,9 +116,10 @@ static int agree(sjhip_multi *m, const char *phase) {
 }
 
 // A message that lies in device memory is only looked at through small windows copied to the host: the record cuts and
-// the whitespace at the ends of every shard (the reference trims what it parses, simdjson_amd64.go:87,
-// parse_json_amd64.go:55).  JSON whitespace and the other ASCII blanks bytes.TrimSpace removes; a shard of a
-// device-resident message that ends in a multi-byte Unicode blank keeps it (and fails like any other stray byte).
+// the whitespace at the ends of every shard.  The outer ends of the message lose the ASCII blanks bytes.TrimSpace removes
+// (the reference trims what it parses, simdjson_amd64.go:87, parse_json_amd64.go:55) -- ASCII only: a device-resident
+// message that begins or ends with a multi-byte Unicode blank keeps it (and fails like any other stray byte).  The ends of
+// a shard inside the message lose JSON whitespace only, as for a host message (sj_host.h shard_windows).
 namespace {
 constexpr size_t WINDOW = 64 << 10;
 struct DevPeek {
@@ -137,13 +139,14 @@ struct DevPeek {
         }
         return len;
     }
-    static bool blank(uint8_t c) { return c == ' ' || (c >= '\t' && c <= '\r'); }
-    void trim(size_t a, size_t b, size_t *off, size_t *ln) {  // [a, b) without the ASCII blanks at its ends
+    static bool blank(uint8_t c) { return c == ' ' || (c >= '\t' && c <= '\r'); }  // the outer ends of the message
+    static bool json_ws(uint8_t c) { return sj::json_ws(c); }                       // the ends of a shard inside it
+    void trim(size_t a, size_t b, bool (*strip)(uint8_t), size_t *off, size_t *ln) {  // [a, b) without such bytes at its ends
         while (a < b && ok) {
             const size_t n = b - a < WINDOW ? b - a : WINDOW;
             const uint8_t *w = get(a, n);
             size_t k = 0;
-            while (k < n && blank(w[k])) k++;
+            while (k < n && strip(w[k])) k++;
             a += k;
             if (k < n) break;
         }
@@ -151,7 +154,7 @@ struct DevPeek {
             const size_t n = b - a < WINDOW ? b - a : WINDOW;
             const uint8_t *w = get(b - n, n);
             size_t k = n;
-            while (k > 0 && blank(w[k - 1])) k--;
+            while (k > 0 && strip(w[k - 1])) k--;
             b -= n - k;
             if (k > 0) break;
         }
@@ -171,7 +174,7 @@ static int multi_parse(sjhip_multi *m, const uint8_t *msg, size_t len, uint32_t 
     DevPeek peek{msg};
     size_t g_off = 0, g_len = 0;
     if (len) {
-        if (d_resident) peek.trim(0, len, &g_off, &g_len);
+        if (d_resident) peek.trim(0, len, DevPeek::blank, &g_off, &g_len);
         else sj::trim_space(msg, len, &g_off, &g_len);  // pj.Message = bytes.TrimSpace(msg), parse_json_amd64.go:55
     }
     if (msg_off) *msg_off = g_off;
@@ -182,36 +185,34 @@ static int multi_parse(sjhip_multi *m, const uint8_t *msg, size_t len, uint32_t 
     // Record cuts: right behind the first raw newline at or after k * len / n.  A raw newline never lies inside a string
     // of a valid document (stage-1 error, find_quote_mask_and_bits_amd64.s:67-80) and inside a record it is a stage-2
     // error (stage2_build_tape_amd64.go:196-221), so every raw newline of a valid ND document separates records.
+    // The window of a shard (sj_host.h shard_windows, the one rule of every sharded path): its cut range inside the global
+    // TrimSpace window, without the JSON whitespace (space, \t, \n, \r) at its ends and nothing else.  The reference trims
+    // the message once and parses every byte between two records as it stands: a '\f' or a U+00A0 behind a record is a
+    // stage-2 error of the whole message, so it stays in the shard and fails there, wherever k * len / n falls.
     const size_t n = m->shards.size();
-    size_t cut = 0;
+    std::vector<size_t> starts(n), lens(n);
+    if (d_resident) {
+        size_t cut = 0;
+        for (size_t k = 0; k < n; k++) {
+            const size_t end = sj::shard_cut_end(len, cut, k, n, [&](size_t at) { return peek.find_newline(at, len); });
+            size_t a = cut, b = end, ln = 0;
+            sj::shard_clip(&a, &b, g_off, g_len);
+            peek.trim(a, b, DevPeek::json_ws, &starts[k], &ln);
+            lens[k] = ln;
+            cut = end;
+        }
+    } else {
+        sj::shard_windows(msg, len, n, starts.data(), lens.data(), &g_off, &g_len);
+    }
+    std::vector<uint8_t> inner(n);
+    sj::shard_inner(lens.data(), n, inner.data());
     for (size_t k = 0; k < n; k++) {
         Shard &s = m->shards[k];
-        size_t end = len;
-        if (k + 1 < n) {
-            size_t target = len * (k + 1) / n;
-            if (target < cut) target = cut;
-            if (d_resident) {
-                const size_t nl = peek.find_newline(target, len);
-                end = nl < len ? nl + 1 : len;
-            } else {
-                const void *nl = target < len ? memchr(msg + target, '\n', len - target) : nullptr;
-                end = nl ? (size_t)((const uint8_t *)nl - msg) + 1 : len;
-            }
-        }
-        size_t off = 0, ln = 0;
-        if (end > cut) {
-            if (d_resident) {
-                peek.trim(cut, end, &off, &ln);
-                off -= cut;
-            } else {
-                sj::trim_space(msg + cut, end - cut, &off, &ln);
-            }
-        }
-        s.start = cut + off;
-        s.len = ln;
+        s.start = starts[k];
+        s.len = lens[k];
+        s.inner = inner[k] != 0;
         s.tape_len = s.strings_len = 0;
         s.rc = 0;
-        cut = end;
     }
     if (!peek.ok) {
         snprintf(m->err, sizeof m->err, "reading the device-resident message failed");
@@ -226,7 +227,7 @@ static int multi_parse(sjhip_multi *m, const uint8_t *msg, size_t len, uint32_t 
             return;
         }
         if (d_resident) {
-            s.rc = sjhip_parse_shard_begin(ctx, msg + s.start, s.len, fl, &s.tape_len, &s.strings_len);
+            s.rc = sjhip_parse_shard_begin(ctx, msg + s.start, s.len, fl | (s.inner ? SJHIP_FLAG_INNER_SHARD : 0u), &s.tape_len, &s.strings_len);
             return;
         }
         s.rc = sj::arena_reserve(ctx, ctx->d_msg, s.len + 128);
@@ -235,7 +236,7 @@ static int multi_parse(sjhip_multi *m, const uint8_t *msg, size_t len, uint32_t 
             s.rc = SJHIP_ERR_HIP;
             return;
         }
-        s.rc = sjhip_parse_shard_begin(ctx, ctx->d_msg.p, s.len, fl, &s.tape_len, &s.strings_len);
+        s.rc = sjhip_parse_shard_begin(ctx, ctx->d_msg.p, s.len, fl | (s.inner ? SJHIP_FLAG_INNER_SHARD : 0u), &s.tape_len, &s.strings_len);
     });
     int code = agree(m, "phase 1");
     if (code) return code;

@@ -361,7 +361,12 @@ int sjhip_parse_shard_begin(sjhip_ctx *ctx, const void *d_msg, size_t len, uint3
     begin_parse(ctx);
     if (!tape_len || !strings_len) return SJHIP_ERR_ARG;
     *tape_len = *strings_len = 0;
-    return parse_begin(ctx, d_msg, len, flags, 0, 0, tape_len, strings_len);
+    const int rc = parse_begin(ctx, d_msg, len, flags & ~SJHIP_FLAG_INNER_SHARD, 0, 0, tape_len, strings_len);
+    // A shard the message goes on behind: the end-of-document test is not its own.  Stage 1 found nothing else (ctx->s1 is what
+    // stage1_collect read back), so the whole message passes it here and stage 2 rejects what the window ends with.
+    if (rc == SJHIP_ERR_STAGE1 && (flags & SJHIP_FLAG_INNER_SHARD) && len > 0 && !ctx->s1.error && ctx->s1.total != 0 && !ctx->s1.ends_in_quote)
+        return SJHIP_ERR_STAGE2;
+    return rc;
 }
 
 int sjhip_parse_shard_finish(sjhip_ctx *ctx, uint64_t tape_base, uint64_t strings_base, uint64_t msg_base) {

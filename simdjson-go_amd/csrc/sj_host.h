@@ -2,6 +2,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 namespace sj {
 
@@ -78,6 +79,64 @@ inline void trim_space(const uint8_t *s, size_t n, size_t *off, size_t *len) {
     }
     *off = a;
     *len = b - a;
+}
+
+// ---- the windows of a sharded ND message (multi_api.hip multi_parse, sjhip/ndshard.py parse_shard) -------------------------
+// The reference trims the message ONCE (pj.Message = bytes.TrimSpace(msg), parse_json_amd64.go:55) and parses every byte
+// between two records as it stands: a '\f' behind a record is a stage-2 error there.  So a shard is
+//   its cut range  [cut k, cut k+1)   cut k+1 = right behind the first '\n' at or after max(cut k, len * (k+1) / n), the last = len
+//   intersected with the global TrimSpace window of the message
+//   without the four JSON whitespace bytes at its ends -- and nothing else: '\v', '\f', U+0085, U+00A0, U+2028 ... stay and fail
+// A window may be empty (it contributes nothing).
+inline bool json_ws(uint8_t c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r'; }
+
+// the end of shard k of n: `first_newline(at)` = position of the first '\n' at or behind `at`, len if there is none
+template <typename FindNewline>
+inline size_t shard_cut_end(size_t len, size_t prev_cut, size_t k, size_t n, FindNewline first_newline) {
+    if (k + 1 >= n) return len;
+    size_t target = (size_t)((unsigned __int128)len * (k + 1) / n);
+    if (target < prev_cut) target = prev_cut;
+    const size_t nl = target < len ? first_newline(target) : len;
+    return nl < len ? nl + 1 : len;
+}
+
+// [a, b) clipped to the global window [g_off, g_off + g_len); an empty result has a == b
+inline void shard_clip(size_t *a, size_t *b, size_t g_off, size_t g_len) {
+    if (*a < g_off) *a = g_off;
+    if (*b > g_off + g_len) *b = g_off + g_len;
+    if (*b < *a) *b = *a;
+}
+
+// host message: the window of every shard (absolute start, length) and the global window
+inline void shard_windows(const uint8_t *msg, size_t len, size_t n, size_t *starts, size_t *lens, size_t *g_off, size_t *g_len) {
+    *g_off = *g_len = 0;
+    if (len) trim_space(msg, len, g_off, g_len);
+    size_t cut = 0;
+    for (size_t k = 0; k < n; k++) {
+        const size_t end = shard_cut_end(len, cut, k, n, [&](size_t at) {
+            const void *nl = memchr(msg + at, '\n', len - at);
+            return nl ? (size_t)((const uint8_t *)nl - msg) : len;
+        });
+        size_t a = cut, b = end;
+        shard_clip(&a, &b, *g_off, *g_len);
+        while (a < b && json_ws(msg[a])) a++;
+        while (b > a && json_ws(msg[b - 1])) b--;
+        starts[k] = a;
+        lens[k] = b - a;
+        cut = end;
+    }
+}
+
+// A shard in front of the last non-empty one ends where the whole message goes on: "the last structural is a closing bracket"
+// (stage1_find_marks_amd64.go:120-129) is asked of the END of the message only.  Such a shard whose window ends otherwise --
+// a stray byte or a scalar behind its last record, a record broken across a newline -- is what stage 2 of the whole message
+// rejects (stage2_build_tape_amd64.go:196-221), and SJHIP_FLAG_INNER_SHARD makes sjhip_parse_shard_begin say so.
+inline void shard_inner(const size_t *lens, size_t n, uint8_t *inner) {
+    bool later = false;
+    for (size_t k = n; k-- > 0;) {
+        inner[k] = later ? 1 : 0;
+        if (lens[k]) later = true;
+    }
 }
 
 }  // namespace sj

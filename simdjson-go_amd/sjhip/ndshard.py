@@ -9,14 +9,21 @@ shards: the only data exchanged is one (tape_len, strings_len) pair per rank (an
 bytes, RCCL over xGMI on the GPUs, gloo in the CPU tests) plus each rank's return code, so that an invalid
 shard fails the parse on every rank instead of leaving the others in a collective.
 
+The window of a shard (the rule of csrc/sj_host.h shard_windows, restated by shard_windows below): its cut range,
+intersected with the bytes.TrimSpace window of the whole message, without the four JSON whitespace bytes (space, \\t,
+\\n, \\r) at its ends -- and nothing else.  The reference trims the message once (pj.Message = bytes.TrimSpace(msg),
+parse_json_amd64.go:55) and parses every other byte between two records as it stands: a \\f, a \\v or a U+00A0 behind
+a record is a stage-2 error of the whole message, so it stays in the shard and fails there wherever a cut falls.
+
 The functions here are pure host logic (no device code) and are exercised on the CPU by
-tests/test_ndshard_gloo.py with the host replay standing in for the kernels.
+tests/test_ndshard_gloo.py and tests/test_shard_model.py with the host replay standing in for the kernels.
 """
 from typing import Callable, List, Sequence, Tuple
 
 import numpy as np
 
-WS = b" \t\n\v\f\r"
+JSON_WS = b" \t\n\r"  # what a shard loses at its ends inside the message; the ends of the message are the caller's TrimSpace
+FLAG_INNER_SHARD = 8  # include/sjhip.h SJHIP_FLAG_INNER_SHARD
 
 
 def record_cuts(data: bytes, n_shards: int) -> List[Tuple[int, int]]:
@@ -33,6 +40,20 @@ def record_cuts(data: bytes, n_shards: int) -> List[Tuple[int, int]]:
         cuts.append(n if j < 0 else j + 1)
     cuts.append(n)
     return [(cuts[i], cuts[i + 1]) for i in range(n_shards)]
+
+
+def shard_windows(data: bytes, n_shards: int, g_off: int, g_len: int) -> List[Tuple[int, int]]:
+    """[start, end) of every shard's window: its cut range inside the global window [g_off, g_off + g_len) of the message
+    (bytes.TrimSpace), without JSON whitespace at its ends.  start == end: the shard contributes nothing."""
+    out = []
+    for a, b in record_cuts(data, n_shards):
+        a, b = max(a, g_off), min(b, g_off + g_len)
+        while a < b and data[a] in JSON_WS:
+            a += 1
+        while b > a and data[b - 1] in JSON_WS:
+            b -= 1
+        out.append((a, max(a, b)))
+    return out
 
 
 def bases_from_sizes(sizes: Sequence[Tuple[int, int]]) -> List[Tuple[int, int]]:
@@ -72,12 +93,29 @@ def _code_of(exc):
     return c if isinstance(c, int) and c != 0 else -1
 
 
+def _takes_inner(begin):
+    """begin(window, inner) or the older begin(window)?  A callback of the older form is called as before: a window that ends in
+    no closing bracket then fails with its stage-1 code on its own, as it did before SJHIP_FLAG_INNER_SHARD."""
+    import inspect
+    try:
+        params = list(inspect.signature(begin).parameters.values())
+    except (TypeError, ValueError):
+        return False
+    if any(p.kind == p.VAR_POSITIONAL for p in params):
+        return True
+    return len([p for p in params if p.kind in (p.POSITIONAL_ONLY, p.POSITIONAL_OR_KEYWORD)]) >= 2
+
+
 def parse_shard(data: bytes, rank: int, world: int, trim: Callable, begin: Callable, finish: Callable,
                 all_gather: Callable, copy_strings: bool = True):
     """Runs one rank's part of a sharded ParseND.
 
-    trim(bytes) -> (off, len)                              bytes.TrimSpace
-    begin(shard_bytes) -> (tape_len, strings_len)          stage 1 + measure (0, 0 for an empty shard)
+    trim(bytes) -> (off, len)                              bytes.TrimSpace, applied ONCE, to the whole message
+    begin(window[, inner]) -> (tape_len, strings_len)      stage 1 + measure; the window is parsed as it stands.  begin(window, True)
+                                                           is called (if begin takes a second argument) for a window that a later non-empty one follows and that does
+                                                           not end in a closing bracket: the end-of-document test belongs to the
+                                                           end of the message, such a window is a stage-2 error unless stage 1 finds
+                                                           another fault (SJHIP_FLAG_INNER_SHARD)
     all_gather(tuple of ints) -> list of tuples            one per rank, in rank order (called TWICE per parse,
                                                            by every rank, whatever happens locally)
     finish(tape_base, strings_base, msg_base) -> (tape, strings)
@@ -88,12 +126,16 @@ def parse_shard(data: bytes, rank: int, world: int, trim: Callable, begin: Calla
 
     Returns (tape, strings, tape_base, strings_base); concatenating the ranks' tapes / strings in rank
     order gives the merged ParsedJson, whose Message is TrimSpace(data)."""
-    g_off, _ = trim(data)
-    start, end = record_cuts(data, world)[rank]
-    shard = data[start:end]
-    off, ln = trim(shard)
-    window = shard[off:off + ln]
-    return run_shard(rank, world, ln == 0, lambda: begin(window), finish, all_gather, start + off - g_off)
+    g_off, g_len = trim(data)
+    windows = shard_windows(data, world, g_off, g_len)
+    start, end = windows[rank]
+    window = data[start:end]
+    inner = any(b > a for a, b in windows[rank + 1:])
+    if inner and window[-1:] not in (b"}", b"]", b"") and _takes_inner(begin):
+        first = lambda: begin(window, True)
+    else:
+        first = lambda: begin(window)
+    return run_shard(rank, world, end == start, first, finish, all_gather, start - g_off)
 
 
 def run_shard(rank: int, world: int, empty: bool, begin: Callable, finish: Callable, all_gather: Callable, msg_base: int):
@@ -229,14 +271,15 @@ def device_callbacks(ctx, copy_strings=True):
         L.sjhip_trim_space(a.ctypes.data if a.size else None, a.size, C.byref(off), C.byref(ln))
         return off.value, ln.value
 
-    def begin(window):
+    def begin(window, inner=False):
         dev = torch.device("cuda", ctx.device)
         d = torch.empty(len(window) + 256, dtype=torch.uint8, device=dev)
         d[:len(window)].copy_(torch.frombuffer(bytearray(window), dtype=torch.uint8))
         torch.cuda.synchronize(dev)
         keep["d"] = d
         tl, sl = C.c_size_t(0), C.c_size_t(0)
-        ctx._check(L.sjhip_parse_shard_begin(ctx._h, C.c_void_p(d.data_ptr()), len(window), flags, C.byref(tl), C.byref(sl)))
+        ctx._check(L.sjhip_parse_shard_begin(ctx._h, C.c_void_p(d.data_ptr()), len(window), flags | (FLAG_INNER_SHARD if inner else 0),
+                                             C.byref(tl), C.byref(sl)))
         keep["sizes"] = (tl.value, sl.value)
         return tl.value, sl.value
 
